@@ -11,20 +11,27 @@ one pair and ~9 % of C2 pairs run all 100 000 samples, so a batch needs many pai
 are resident in HBM before the timed region; the per-pair results are gathered over RCCL inside it.
 
   python bench.py --gpus 1 --steps K --warmup W
-  python bench.py --gpus N --steps K --warmup W        (no WORLD_SIZE in the environment: re-executes itself under
+  python bench.py --gpus N --steps K --warmup W        (no WORLD_SIZE in the environment: starts itself as a child process under
                                                         torch.distributed.run with N ranks, one per GPU; fails loudly when
                                                         fewer than N devices are visible)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
   python bench.py --gpus N --single-process             (ONE process, the C-ABI's device-list mode *_batch_multi, no collective)
-  ... --gpus N --c4-single-process                      (N ranks, and rank 0 also measures the literal C4 batch through one process: on request only)
+  ... --full                                            (everything besides the headline, see below)
+  ... --gpus N --full --c4-single-process               (N ranks, and rank 0 also measures the literal C4 batch through one process: on request only)
+  ... --dump-outputs DIR                                (the last timed step's results as DIR/*.npy, see dump_outputs)
 
-Prints ONE JSON line on rank 0 (contract of the driver) with `roofline` and `cpu_baseline` (the reference on one host
-core, the north-star denominator) plus `cpu_baseline_all_cores` (one reference process per host core).
+Prints ONE JSON line on rank 0 (contract of the driver).  A plain run sets up, warms up, times the K steps and prints the line
+(`value`, `ms_per_step`, `roofline` from the same steps' HIP events and stats).  --full adds what takes runs or checks of its own:
+the parity check of the timed batch against the CPU oracle (--parity-pairs, default 16 with --full, 0 without), `cpu_baseline`
+(the reference on one host core, the north-star denominator) and `cpu_baseline_all_cores` (one reference process per host core,
+SURVEY 8d) with the parity check over every pair that leg ran, `single_call_ms`, the `secondary` configurations and, with
+N > 1 ranks, the literal C4 batch.
 """
 import argparse
 import ctypes as C
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -330,6 +337,35 @@ def single_call_ms(reps=7):
             "note": "host-pointer API, PCIe staging included, 1 pair = 1 workgroup; never used as `value`"}
 
 
+DUMP_CAP_BYTES = 64 << 20
+DUMP_STATS_WORDS = 12            # MI_ST_SAMPLES .. MI_ST_AUX_PASSES; words 12-15 are device-clock ticks and the kernel variant
+
+
+def dump_outputs(out_dir, models, masks, stats, cap=DUMP_CAP_BYTES):
+    """--dump-outputs: what the timed path returned in its last step, as .npy files in float64 / float32, at most `cap` bytes
+    in all, so that two builds can be compared output for output (same arguments = same inputs and seeds):
+      models.npy   [k, 9] float64  the returned model of each pair (homogeneous, sign as returned)
+      masks.npy    [k, n] float32  the inlier mask (0 / 1)
+      stats.npy    [k, 12] float64 the per-pair counters MI_ST_SAMPLES .. MI_ST_AUX_PASSES (include/mi_degensac.h); the
+                                   device-clock and kernel-variant words vary from run to run and are left out
+      pair_ids.npy [k] float64     the global pair id of each row
+    k = every pair when they fit, else a fixed sample (seed 0) of pairs in ascending order.  Returns k."""
+    models = np.asarray(models, dtype=np.float64).reshape(-1, 9)
+    masks = np.asarray(masks)
+    P = models.shape[0]
+    masks = masks.reshape(P, -1)
+    stats = np.asarray(stats).reshape(P, -1)[:, :DUMP_STATS_WORDS]
+    per_pair = 8 * 9 + 4 * masks.shape[1] + 8 * DUMP_STATS_WORDS + 8
+    fit = max(1, (cap - 4 * 4096) // per_pair)                  # room for the four .npy headers
+    ids = np.arange(P) if P <= fit else np.sort(np.random.default_rng(0).choice(P, size=fit, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "models.npy"), models[ids])
+    np.save(os.path.join(out_dir, "masks.npy"), masks[ids].astype(np.float32))
+    np.save(os.path.join(out_dir, "stats.npy"), stats[ids].astype(np.float64))
+    np.save(os.path.join(out_dir, "pair_ids.npy"), ids.astype(np.float64))
+    return len(ids)
+
+
 def measure(pairs_per_gpu, steps, warmup, parity_pairs, world, rank, local_rank, dev, always_collective=False):
     """K timed steps of the hot path for the CURRENT config (set_config) on this rank's shard of `pairs_per_gpu * world`
     pairs.  Returns a dict of raw results (rank-local stats, gathered stats, times); the caller formats the JSON line."""
@@ -534,14 +570,15 @@ def measure_single_process(n_dev, pairs_per_gpu, steps, warmup, parity_pairs):
     n_checked = n_aside = 0
     if parity_pairs > 0:
         n_checked, n_aside = parity_check(CFG["which"], P, parity_pairs, 0, M, mask.reshape(P, N_CORR), st)
-    return dict(dt=dt, st=st, P=P, n_checked=n_checked, n_aside_checked=n_aside, masks=mask.reshape(P, N_CORR))
+    return dict(dt=dt, st=st, P=P, n_checked=n_checked, n_aside_checked=n_aside, masks=mask.reshape(P, N_CORR), models=M)
 
 
 def single_process_line(args, n_dev):
     r = measure_single_process(n_dev, args.pairs_per_gpu, args.steps, args.warmup, args.parity_pairs)
     st, dt = r["st"], r["dt"]
     models_step = int(st[:, 4].sum())
-    return {"metric": "models/sec, findFundamentalMatrix @2000 corrs (LO-RANSAC + DEGENSAC, batched pairs)" if args.config == "c2" else f"models/sec, config {args.config}",
+    dumped = dump_outputs(args.dump_outputs, r["models"], r["masks"], st) if args.dump_outputs else None
+    line = {"metric": "models/sec, findFundamentalMatrix @2000 corrs (LO-RANSAC + DEGENSAC, batched pairs)" if args.config == "c2" else f"models/sec, config {args.config}",
             "value": models_step * args.steps / dt, "unit": "models/s", "n_gpus": n_dev, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
             "config": {"workload": f"{args.config.upper()} x {args.pairs_per_gpu} pairs per GPU, {N_CORR} correspondences", "pairs_total": r["P"],
@@ -553,6 +590,9 @@ def single_process_line(args, n_dev):
             "roofline": None, "cpu_baseline": None,
             "parity_checked": r["n_checked"], "parity_checked_set_aside": r["n_aside_checked"], "sign_flips": SIGN_FLIPS[:8],
             "devices_used": sorted(set(int(x) for x in range(n_dev)))}
+    if dumped is not None:
+        line["outputs_dumped"] = {"dir": args.dump_outputs, "pairs": dumped}
+    return line
 
 
 def main():
@@ -563,18 +603,26 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2")
     ap.add_argument("--pairs-per-gpu", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short C2 x 512 / C3 / C5 measurements of the `secondary` object")
-    ap.add_argument("--parity-pairs", type=int, default=16, help="pairs of the timed batch checked against the oracle afterwards")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the short C2 x 512 / C3 / C5 measurements of the `secondary` object")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the parity check of the timed batch (--parity-pairs), the CPU baselines with "
+                         "their parity check, single_call_ms, the `secondary` configurations and, with N > 1 ranks, the literal C4 batch")
+    ap.add_argument("--parity-pairs", type=int, default=None,
+                    help="pairs of the timed batch checked against the oracle afterwards (default: 16 with --full, 0 without)")
     ap.add_argument("--dump-results", default="", help="rank 0 writes the gathered per-pair results of the last timed step to this .npz (tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step returned as DIR/*.npy in float64 / float32, at most 64 MB (see dump_outputs)")
     ap.add_argument("--single-process", action="store_true",
                     help="drive the N GPUs from ONE process through the device-list entry points (*_batch_multi, no collective, host buffers)")
     ap.add_argument("--c4-single-process", action="store_true",
-                    help="with N > 1 ranks: rank 0 also measures the literal C4 batch through ONE process over the same N GPUs (secondary.c4_literal_single_process) "
+                    help="with N > 1 ranks and --full: rank 0 also measures the literal C4 batch through ONE process over the same N GPUs (secondary.c4_literal_single_process) "
                          "while the other ranks wait at a barrier; off by default: it opens every GPU from rank 0 next to the ranks' own processes, and the N-rank "
                          "line must not depend on it")
     ap.add_argument("--dist-always", action="store_true",
                     help="initialise the RCCL process group and run the result all-gather even with one rank (tests the N > 1 code path on one GPU)")
     args = ap.parse_args()
+    if args.parity_pairs is None:
+        args.parity_pairs = 16 if args.full else 0
     set_config(args.config)
     if args.pairs_per_gpu <= 0:
         args.pairs_per_gpu = PAIRS_PER_GPU
@@ -586,9 +634,10 @@ def main():
     action, world = resolve_world(args.gpus, args.single_process, os.environ, visible_gpus())
     if action == "exec":
         cmd = relaunch_argv(args.gpus, sys.argv[1:])
-        print("bench.py: --gpus %d without a launcher: re-executing as  %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
+        print("bench.py: --gpus %d without a launcher: running  %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
         env = dict(os.environ); env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execve(sys.executable, cmd, env)
+        # a child process, not an exec: counting the devices above has already initialised the GPU runtime in this one
+        sys.exit(subprocess.call(cmd, env=env))
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU: the product has no CPU path")
     if args.single_process:
@@ -611,7 +660,7 @@ def main():
     # C4 as BASELINE.json words it: ONE batch of 4096 pairs over the N GPUs (strong scaling, 4096 / N pairs per GPU), measured
     # by every rank next to the weak-scaling headline (4096 pairs PER GPU); at N = 1 it IS the headline
     c4 = None
-    if args.config == "c2" and world > 1 and not args.no_secondary and 4096 % world == 0:
+    if args.full and args.config == "c2" and world > 1 and not args.no_secondary and 4096 % world == 0:
         r4 = measure(4096 // world, 3, 1, 4, world, rank, local_rank, dev, always_collective=use_dist)
         m4 = int(r4["st"][:, 4].sum())
         c4 = {"workload": f"C4 literal: 4096 C2 pairs over {world} GPUs = {4096 // world} per GPU (strong scaling)", "n_gpus": world,
@@ -635,6 +684,9 @@ def main():
 
     if rank == 0 and args.dump_results:
         np.savez(args.dump_results, models=r["gm"].cpu().numpy(), stats=st, masks=gmask.cpu().numpy())
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, r["gm"].cpu().numpy(), gmask.cpu().numpy(), st)
     if rank == 0:
         inl = gmask.sum(dim=1).cpu().numpy()
         ticks = st[:, 13].astype(np.float64) / 100e6                           # 100 MHz device wall clock
@@ -686,9 +738,11 @@ def main():
             "pairs_set_aside": int(((local_st[:, 15] >> 8) & 1).sum()),
             "pairs_streamed": int(((local_st[:, 15] >> 9) & 1).sum()),   # pairs whose sample stream / solves / scoring moved to a producer workgroup (stream mode)        # pairs written back after the discovery round and resumed by priority
         }
-        if world == 1:
+        if dumped is not None:
+            out["outputs_dumped"] = {"dir": args.dump_outputs, "pairs": dumped}
+        if args.full and world == 1:
             out["single_call_ms"] = single_call_ms()
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cb = cpu_baseline()
             out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
             if "time_to_best_ms" in cb and cb["pair_ids"][1] < P:
@@ -711,7 +765,7 @@ def main():
                                 "batch: samples, LO runs, inlier count equal, mask bit-exact, model <= 1e-6 relative Frobenius (any mismatch ends the "
                                 "bench); the scored-model count is compared too and its differences are listed (pair, GPU, reference): the reference's own "
                                 "count varies from call to call on some homography pairs (same mask, model and trajectory), see bench.py"}
-        if world == 1 and not args.no_secondary and args.config == "c2":
+        if args.full and world == 1 and not args.no_secondary and args.config == "c2":
             # the other BASELINE configurations, short runs inside the same driver-timed process (about a minute together)
             sec = {}
             if P != 512:

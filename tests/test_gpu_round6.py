@@ -141,6 +141,44 @@ def test_bench_gpus_flag_is_a_request_not_a_label():
     assert line["n_gpus"] == 1 and line["config"]["process_group"] is None and line["parity_checked"] >= 3 and line["value"] > 0
 
 
+def test_plain_bench_run_is_lean_and_dumps_what_it_timed(tmp_path, oracle_port):
+    """A plain bench.py run times --steps steps and prints the headline only (no parity check, CPU baseline, single call or
+    secondary configurations: those need --full); --dump-outputs writes the last timed step's results as float64 / float32
+    .npy files, the same from run to run for the same arguments, and equal to the oracle's for the same pairs and seeds."""
+    from pydegensac_amd import parallel
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for steps in (2, 1):
+        d = tmp_path / f"s{steps}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                              "--pairs-per-gpu", "48", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-800:]
+        lines = out.stdout.strip().splitlines()
+        assert len(lines) == 1, lines
+        j = json.loads(lines[0])
+        assert j["steps"] == steps and j["ms_per_step"] > 0 and j["value"] > 0 and j["unit"] == "models/s" and j["dtype"] == "f64"
+        assert j["parity_checked"] == 0 and j["outputs_dumped"]["pairs"] == 48
+        for k in ("cpu_baseline", "cpu_baseline_all_cores", "single_call_ms", "secondary"):
+            assert k not in j, k
+        arrs = {n: np.load(d / f"{n}.npy") for n in ("models", "masks", "stats", "pair_ids")}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert arrs["models"].shape == (48, 9) and arrs["masks"].shape == (48, 2000) and arrs["stats"].shape == (48, 12)
+        dumps.append(arrs)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    a = dumps[0]
+    for p in (0, 17, 47):
+        p1, p2 = bench.make_pair(p)
+        Fo, mo, so = bench.cpu_call(oracle_port, p1, p2, parallel.pair_seed(p))
+        assert int(a["pair_ids"][p]) == p
+        assert np.array_equal(a["masks"][p].astype(bool), mo)
+        assert (a["stats"][p, 0], a["stats"][p, 1], a["stats"][p, 3]) == (so["samples"], so["lo_runs"], so["I"])
+        assert bench.model_rel(a["models"][p], Fo)[0] < 1e-6
+
+
 def test_fan_mode_equals_the_cooperative_mode_and_the_oracle(oracle_port):
     """Fan mode (dg_f_fan.h; automatic for one large pair per owner on an idle device): the owner draws the sample stream into the ring, worker
     workgroups solve and score the chunks, the owner commits the completed entries in order.  Same results as the cooperative mode alone

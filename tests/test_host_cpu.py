@@ -297,6 +297,34 @@ def test_bench_gpus_request_resolution():
     assert out.returncode != 0 and "only 0 GPU(s) are visible" in out.stderr and not out.stdout.strip()
 
 
+def test_bench_dump_outputs_is_float_capped_and_seeded(tmp_path):
+    """bench.py --dump-outputs: float64 / float32 .npy files only; a batch over the size cap is written as a fixed sample of
+    pairs (the same every time), with the clock / variant words of the stats dropped."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    P, n = 300, 2000
+    models = rng.normal(size=(P, 9)); masks = (rng.random((P, n)) < 0.4).astype(np.uint8)
+    stats = rng.integers(0, 1000, size=(P, 16)).astype(np.int32)
+    assert bench.dump_outputs(str(tmp_path / "all"), models, masks, stats) == P
+    a = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in ("models", "masks", "stats", "pair_ids")}
+    assert a["models"].dtype == np.float64 and a["masks"].dtype == np.float32 and a["stats"].dtype == np.float64
+    assert np.array_equal(a["models"], models) and np.array_equal(a["masks"], masks) and np.array_equal(a["stats"], stats[:, :12])
+    assert np.array_equal(a["pair_ids"], np.arange(P))
+    cap = 1 << 20
+    for d in ("s1", "s2"):
+        k = bench.dump_outputs(str(tmp_path / d), models, masks, stats, cap=cap)
+        assert 0 < k < P
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= cap
+    ids1 = np.load(tmp_path / "s1" / "pair_ids.npy"); ids2 = np.load(tmp_path / "s2" / "pair_ids.npy")
+    assert np.array_equal(ids1, ids2) and (np.diff(ids1) > 0).all()
+    assert np.array_equal(np.load(tmp_path / "s1" / "masks.npy"), masks[ids1.astype(int)])
+    # a plain run is lean: --full and --dump-outputs are there, everything else is behind --full
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs" in out.stdout
+
+
 def test_bench_model_distance_is_up_to_sign():
     import importlib.util
     spec = importlib.util.spec_from_file_location("bench_mod2", os.path.join(ROOT, "bench.py"))
