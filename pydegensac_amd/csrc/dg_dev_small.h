@@ -166,6 +166,13 @@ static __device__ __forceinline__ double dg_rdl_d(double v, int l)
 #define DG_WSYNC_LDS() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local"); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); \
                             __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local"); } while (0)
 
+/* dg_lds_ptr<P>::value: P points into LDS by type (address space 3).  A solver instantiated for such pointers only (dg_eig_sym_wave,
+ * dg_svd_lastcol_9x8_wave from dg_u2f_small_wave) makes ds_ accesses only, and its wave barriers wait for LDS operations only
+ * (DG_WSYNC_IF_LDS): the wave's global loads and stores stay in flight across it.  Any generic pointer keeps the full DG_WSYNC. */
+template <class P> struct dg_lds_ptr { static constexpr bool value = false; };
+template <class T> struct dg_lds_ptr<__attribute__((address_space(3))) T *> { static constexpr bool value = true; };
+#define DG_WSYNC_IF_LDS(lds_only) do { if constexpr (lds_only) DG_WSYNC_LDS(); else DG_WSYNC(); } while (0)
+
 #ifdef DG_EIG_TIMING
 static __device__ long long dg_eig_ticks[4];
 #define DG_ET(i) do { long long t_ = wall_clock64(); if (lane == 0) dg_eig_ticks[i] += t_ - t_et; t_et = t_; } while (0)
@@ -193,13 +200,17 @@ static __device__ long long dg_steqr_ticks[2], dg_steqr_tq;
 #endif
 #include "dg_steqr9.h"
 struct dg_eig_ws { double d[9], e[9], tau[9], work[18]; };
-static __device__ __noinline__ int dg_eig_sym_wave(double *a, double *w, int lane, dg_eig_ws *ews)
+/* PA / PW / PE: generic pointers, or LDS-qualified ones (__attribute__((address_space(3)))) from a caller whose scratch is typed as LDS —
+ * then every access of the solver is a ds_ instruction, in the caller's instantiation only */
+template <class PA, class PW, class PE>
+static __device__ __noinline__ int dg_eig_sym_wave(PA a, PW w, int lane, PE ews)
 {
     const int n = 9;
 #ifdef DG_EIG_TIMING
     long long t_et = wall_clock64();
 #endif
-    double *d = ews->d, *e = ews->e, *tau = ews->tau;
+    auto d = &ews->d[0], e = &ews->e[0], tau = &ews->tau[0];
+    constexpr bool lds_only = dg_lds_ptr<PA>::value && dg_lds_ptr<PW>::value && dg_lds_ptr<PE>::value;
     int i, j, k, ii;
 #define A_(r,c) a[(c)*n + (r)]
     /* ---- dsytd2, UPLO='U' ----
@@ -254,7 +265,7 @@ static __device__ __noinline__ int dg_eig_sym_wave(double *a, double *w, int lan
 #pragma unroll
             for (int cc = 0; cc < 9; cc++) A_(lane, cc) = R[cc];
         }
-        DG_WSYNC();
+        DG_WSYNC_IF_LDS(lds_only);
     }
     DG_ET(0);
     /* ---- dorgtr 'U' + dorg2l(n-1, n-1, n-1) ----
@@ -275,7 +286,7 @@ static __device__ __noinline__ int dg_eig_sym_wave(double *a, double *w, int lan
         double tq[8];
 #pragma unroll
         for (int q = 0; q < 8; q++) tq[q] = tau[q];
-        DG_WSYNC();
+        DG_WSYNC_IF_LDS(lds_only);
 #pragma unroll
         for (int iq = 0; iq < n - 1; iq++) {
             if (lane == iq) Cq[iq] = 1.;
@@ -302,7 +313,7 @@ static __device__ __noinline__ int dg_eig_sym_wave(double *a, double *w, int lan
 #pragma unroll
             for (int r = 0; r < 9; r++) A_(r, lane) = Cq[r];
         }
-        DG_WSYNC();
+        DG_WSYNC_IF_LDS(lds_only);
     }
     DG_ET(1);
     /* ---- dsteqr 'V' ----
@@ -310,30 +321,30 @@ static __device__ __noinline__ int dg_eig_sym_wave(double *a, double *w, int lan
      * rotates row r of Z in place (a[c*9 + r]); lanes 9..63 repeat rows 0..8, same values to the same addresses. */
     {
         double p;
-        DG_WSYNC();
+        DG_WSYNC_IF_LDS(lds_only);
 #ifdef DG_EIG_TIMING
         if (lane == 0) dg_steqr_tq = wall_clock64();
 #endif
         const int info = dg_steqr9((DG_STEQR_PTR)d, (DG_STEQR_PTR)e, (DG_STEQR_PTR)(a + (lane % 9)), 9, lane);
         const int jtot = info ? n * 30 : 0, nmaxit = n * 30;
         DG_STEQR_T(0);
-        DG_WSYNC();
+        DG_WSYNC_IF_LDS(lds_only);
         DG_ET(2);
         /* dsteqr ends with an ascending selection sort; every caller only consumes the smallest pair (column 0,
          * or the first minimum of w[]), which the sort's first pass already puts in place: run that pass only */
         for (ii = 1; ii < 2; ii++) {
             i = ii - 1; k = i; p = d[i];
             for (j = ii; j < n; j++) if (d[j] < p) { k = j; p = d[j]; }
-            DG_WSYNC();
+            DG_WSYNC_IF_LDS(lds_only);
             if (k != i) {
                 double dk = d[i];
                 if (lane == 0) { d[k] = dk; d[i] = p; }
                 if (lane < n) { double t = A_(lane, i); A_(lane, i) = A_(lane, k); A_(lane, k) = t; }
             }
-            DG_WSYNC();
+            DG_WSYNC_IF_LDS(lds_only);
         }
         if (lane < n) w[lane] = d[lane];
-        DG_WSYNC();
+        DG_WSYNC_IF_LDS(lds_only);
         DG_ET(3);
         return jtot >= nmaxit ? 1 : 0;
     }
@@ -345,9 +356,11 @@ static __device__ __noinline__ int dg_eig_sym_wave(double *a, double *w, int lan
  * (Cl[0..8]) — so the column reflector finds its column locally in lane i and the row reflector its row locally
  * in lane i; scalars and reflector entries travel by v_readlane with compile-time lane numbers, and every update is
  * applied to both copies with the same operands (bitwise equal).  All 64 lanes of one wave. */
-static __device__ __noinline__ void dg_svd_lastcol_9x8_wave(double *a /* LDS 9x8 row-major */, double *col /* LDS 9 */, int lane)
+template <class PA, class PC>          /* generic or LDS-qualified pointers, as dg_eig_sym_wave */
+static __device__ __noinline__ void dg_svd_lastcol_9x8_wave(PA a /* LDS 9x8 row-major */, PC col /* LDS 9 */, int lane)
 {
     const int m = 9, n = 8;
+    constexpr bool lds_only = dg_lds_ptr<PA>::value && dg_lds_ptr<PC>::value;
     double Rw[8], Cl[9];
 #pragma unroll
     for (int c = 0; c < 8; c++) Rw[c] = lane < m ? a[lane * n + c] : 0.;
@@ -465,7 +478,7 @@ static __device__ __noinline__ void dg_svd_lastcol_9x8_wave(double *a /* LDS 9x8
             for (int i = 0; i < 9; i++) col[i] = c[i];
         }
     }
-    DG_WSYNC();
+    DG_WSYNC_IF_LDS(lds_only);
 }
 
 /* ------------------------------------------------------------------------------------------------

@@ -275,7 +275,7 @@ __device__ __noinline__ dg_score dg_inFrani_serial(CTX &c, int ninl, double th, 
 /* one wave's pass of model Fm under metric `kind` over all n points: I = #(d <= thJ), J = the reference-order MSAC sum, the
  * ordered id lists at thL (la) and thL2 (lb, optional); `tile` = the wave's LDS tile for the MSAC terms (dg_wpass_impl) */
 template <int LDSPTS>
-__device__ __noinline__ dg_pass_res dg_f_wpass(const dg_pt *P, int n, int kind, const double *Fm /* LDS */, double thJ, int *la_, double thL, int *lb_,
+__device__ __forceinline__ dg_pass_res dg_f_wpass(const dg_pt *P, int n, int kind, const double *Fm /* LDS */, double thJ, int *la_, double thL, int *lb_,
     double thL2,
                                                double *tile, int lane)
 {
@@ -288,10 +288,14 @@ __device__ __noinline__ dg_pass_res dg_f_wpass(const dg_pt *P, int n, int kind, 
 
 #define DG_LO_ASSUMED_DRAWS 16          /* two 8-subsets per repetition: the most frequent count (62 % on C2 data) */
 /* one repetition (sample lg->ids, generator lg->g right behind the sample's draws, iterID for the table lookups) by one wave:
- * the 14-point fit and exp_iterFcustom (exp_ranF.c:621-743) */
+ * the 14-point fit and exp_iterFcustom (exp_ranF.c:621-743).  Inlined into the round with its passes and small fits: as calls
+ * their callee-saved register saves and restores were ~340 scratch operations per repetition.  Every branch in it is wave-uniform and
+ * taken on a scalar condition (readfirstlane / ballot), as is the caller's `wave < nr`: no loop or wave barrier of it runs
+ * with a partial or empty exec mask. */
 template <int LDSPTS>
-__device__ __noinline__ void dg_lo_rep_wave(CTX &c, dg_lo_log *lg, int ssiz, double th, int mk_full, int mk_ex, int lane, int wave)
+__device__ __forceinline__ void dg_lo_rep_wave(CTX &c, dg_lo_log *lg, int ssiz, double th, int mk_full, int mk_ex, int lane, int wave)
 {
+    ssiz = __builtin_amdgcn_readfirstlane(ssiz); wave = __builtin_amdgcn_readfirstlane(wave);
     dg_f_shared *S = c.S; const int n = c.n, nm = c.K->n_max; const dg_pt *P = c.P;
     dg_wave_ws *w = &S->ww[wave];
     int *ib = c.K->wlist + (size_t)wave * nm;                                    /* this repetition's `inliers` (intbuff) */
@@ -344,11 +348,11 @@ __device__ __noinline__ void dg_lo_rep_wave(CTX &c, dg_lo_log *lg, int ssiz, dou
     for (; it < DG_ILSQ_ITERS; it++) {
         if (stale()) { if (lane == 0) lg->aborted = 1; DG_WSYNC(); return; }
         const dg_pass_res r1 = dg_f_wpass<LDSPTS>(P, n, mk_ex, fl, th, ib, th, alt, ths * DG_MWM, jb, lane);
-        const int improve = mJ < r1.J;
+        const int improve = __builtin_amdgcn_readfirstlane(mJ < r1.J);        /* (every lane holds the same sums) */
         unsigned nL2 = r1.nL2;
         /* exp_ranF.c:687-696: after a rotation `d` is the OLD errs[0]: that list is taken on the residuals of the previous best */
         if (improve) { const dg_pass_res r2 = dg_f_wpass<LDSPTS>(P, n, kind0, f, 0.0, alt, ths * DG_MWM, (int *)0, 0.0, jb, lane); nL2 = r2.nL; }
-        const int fit = nL2 >= 8;
+        const int fit = __builtin_amdgcn_readfirstlane(nL2 >= 8);
         DG_WSYNC();
         DG_RW(9);
         const unsigned hash = dg_hash_list(ib, (int)r1.I, small_ids);
@@ -389,7 +393,7 @@ __device__ __noinline__ void dg_lo_rep_wave(CTX &c, dg_lo_log *lg, int ssiz, dou
     if (!ended) {
         const dg_pass_res r3 = dg_f_wpass<LDSPTS>(P, n, mk_full, fl, th, ib, th, (int *)0, 0.0, jb, lane);
         if (lane == 0) lg->has_fin = 1;
-        if (mJ < r3.J) { mI = r3.I; mJ = r3.J; kind0 = mk_full; DG_WSYNC(); if (lane < 9) f[lane] = fl[lane]; DG_WSYNC(); }
+        if (__builtin_amdgcn_readfirstlane(mJ < r3.J)) { mI = r3.I; mJ = r3.J; kind0 = mk_full; DG_WSYNC(); if (lane < 9) f[lane] = fl[lane]; DG_WSYNC(); }
     }
     DG_WSYNC();
     if (lane < 9) lg->f[lane] = f[lane];
@@ -452,7 +456,12 @@ __device__ __noinline__ dg_score dg_inFrani_waves(CTX &c, int ninl, double th, d
         __syncthreads();
         DG_LW(0);
         if constexpr (COOP) dg_lo_round_coop<LDSPTS>(c, nr, ssiz, th, mk_full, mk_ex);
-        else { if (wave < nr) dg_lo_rep_wave<LDSPTS>(c, &S->lo[wave], ssiz, th, mk_full, mk_ex, lane, wave); }
+        else {
+            /* scalar branch: a wave runs a whole repetition or skips it (an exec-masked region around the inlined repetition would run
+             * its scalar loop control and address arithmetic with no lane active) */
+            const int wv = __builtin_amdgcn_readfirstlane(wave);
+            if (wv < __builtin_amdgcn_readfirstlane(nr)) dg_lo_rep_wave<LDSPTS>(c, &S->lo[wv], ssiz, th, mk_full, mk_ex, lane, wv);
+        }
         __syncthreads();
         DG_LW(1);
         /* replay in repetition order (thread 0): the hash table with each repetition's own iterID, what it really drew */

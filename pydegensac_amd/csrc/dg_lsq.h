@@ -101,7 +101,7 @@ __device__ __forceinline__ void dg_u2f_norm_w(SC *s, PP p, const double *wts, in
     DG_WSYNC();
     dg_cov9_wave(&s->V[0], &s->Z[0], len, lane);
     DG_WSYNC();
-    dg_eig_sym_wave((double *)&s->V[0], (double *)&s->D[0], lane, (dg_eig_ws *)&s->ews);
+    dg_eig_sym_wave(&s->V[0], &s->D[0], lane, &s->ews);
     if (lane == 0) {
         int j = 0; for (int i = 1; i < 9; i++) if (s->D[i] < s->D[j]) j = i;
         for (int i = 0; i < 9; i++) F[i] = s->V[j*9 + i];
@@ -136,13 +136,14 @@ __device__ __noinline__ void dg_u2f_small_w(dg_lsq_scratch *s, const double *p, 
     }
 }
 
-/* dg_u2f_small_w on a wave's own scratch (dg_wave_ws: Z doubles as the 9 x 8 system, V as the left factor's column) */
-__device__ __noinline__ void dg_u2f_small_wave(dg_wave_ws *s_, const double *p_, const double *wts /* LDS or 0 */, int len, double *F_, int lane)
+/* dg_u2f_small_w on a wave's own scratch (dg_wave_ws: Z doubles as the 9 x 8 system, V as the left factor's column); inlined into the
+ * repetition of the local optimisation (dg_lo_rep_wave), its only caller, which enters it behind a DG_WSYNC */
+__device__ __forceinline__ void dg_u2f_small_wave(dg_wave_ws *s_, const double *p_, const double *wts /* LDS or 0 */, int len, double *F_, int lane)
 {
     /* the wave's scratch, the gathered points and the model are LDS on every call: address-space-qualified views, so that every access of
      * this function and of the helpers inlined into it is a ds_ instruction (through the generic parameters they were all FLAT: 62 stores and
-     * 54 loads).  The callees below take generic pointers again; they begin (prologue) and end (DG_WSYNC) with a wait for the wave's memory
-     * operations, so the two paths never meet an unordered pair of accesses. */
+     * 54 loads).  The solvers it calls (dg_eig_sym_wave, dg_svd_lastcol_9x8_wave) are instantiated for these LDS-qualified pointers, so the
+     * scratch is written and read through ds_ instructions only. */
     __attribute__((address_space(3))) dg_wave_ws *s = (__attribute__((address_space(3))) dg_wave_ws *)s_;
     const __attribute__((address_space(3))) double *p = (const __attribute__((address_space(3))) double *)p_;
     __attribute__((address_space(3))) double *F = (__attribute__((address_space(3))) double *)F_;
@@ -161,7 +162,7 @@ __device__ __noinline__ void dg_u2f_small_wave(dg_wave_ws *s_, const double *p_,
             s->Z[e] = z;
         }
         DG_WSYNC();
-        dg_svd_lastcol_9x8_wave((double *)&s->Z[0], (double *)&s->V[0], lane);
+        dg_svd_lastcol_9x8_wave(&s->Z[0], &s->V[0], lane);
         if (lane == 0) { for (int i = 0; i < 9; i++) F[i] = s->V[i]; dg_singulF(F); }
         DG_WSYNC();
     }
