@@ -349,6 +349,50 @@ int mi_degensac_kpts_to_xyA(const float *kpts, int n, int device, double *out);
 int mi_degensac_kpts_to_xyA_dev(const float *d_kpts, int n, int device, void *stream, double *d_out);
 const char *mi_degensac_match_last_error(void);
 
+/* ---- batched match-and-verify: many image pairs from descriptors to F / H -------------------------------------------
+ * A ragged batch of K image pairs: pair p owns the rows offsets1_host[p] .. offsets1_host[p+1] of desc1 / kp1 (its queries) and
+ * offsets2_host[p] .. offsets2_host[p+1] of desc2 / kp2 (its train set); offsets are host arrays of K + 1 non-decreasing values.
+ *
+ * The batched 2-NN: for every query the two nearest train rows OF ITS OWN PAIR, in one launch over all pairs (64-query tiles;
+ * the train set is split over more workgroups only when the batch is too small to fill the device).  d_idx / d_dist:
+ * [offsets1_host[K], 2]; indices are local to the pair (0 .. n2_p - 1).  Per pair bit-identical to mi_degensac_match_knn2_dev
+ * on that pair (-1 / inf when the pair has fewer than two train rows).  Asynchronous on `stream`. */
+int mi_degensac_match_knn2_batch_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
+                                     const int64_t *offsets2_host, int n_pairs, int dim, int device, void *stream,
+                                     int32_t *d_idx, float *d_dist);
+typedef struct mi_degensac_match_params {
+    int32_t norm;          /* MI_DEGENSAC_NORM_L2 (float32 rows) / MI_DEGENSAC_NORM_HAMMING (uint8 rows, dim % 4 == 0)     */
+    int32_t dim;           /* descriptor length (elements)                                                              */
+    float   ratio;         /* tentative when dist[0] < ratio * dist[1]; finite and > 0                                   */
+    int32_t mutual;        /* bool: also require that the query is the nearest neighbour of its nearest train row         */
+    int32_t struct_size;   /* sizeof(mi_degensac_match_params) of the caller's header (0 = this layout); fields added later
+                              are only read when struct_size covers them                                                  */
+    int32_t reserved;
+} mi_degensac_match_params;
+/* Match and verify: per pair the 2-NN search, the ratio test (+ mutual check) of mi_degensac_match, then the estimator of
+ * mi_degensac_find_fundamental_batch_dev (homography = 0) or _homography_batch_dev (homography = 1) on the pair's tentatives in
+ * query order — exactly the rows mi_degensac_match + the per-pair gather would hand it.  kp1 / kp2: [rows, kp_dim] float64,
+ * kp_dim 2 or 6 (LAF rows).  A pair with fewer than 8 (F) / 4 (H) tentatives is SHORT: it is not estimated, gets a zero model
+ * and a zero stats row, and does not make the call fail.  d_seeds[K]: seed of pair p (results of a pair do not depend on the other
+ * pairs of the batch).  Outputs per pair: d_model [K*9] (the driver's form, as the batch entry points), d_stats [K*16] or NULL;
+ * per query row of desc1: d_match = train row local to the pair or -1 when the row is not a tentative, d_inlier = 1 when it is a
+ * tentative and an inlier of the pair's model.  h_counts (host, [K], nullable): tentatives per pair.
+ * Synchronisation: the matching is enqueued on `stream`, then the call reads the K tentative counts back (ONE device-to-host copy
+ * followed by a wait for `stream`: the only synchronisation; the estimator's launch is sized from them on the host), enqueues the
+ * gather, the estimator and the scatter and returns.  Discarded pairs (hand-over time-out) carry bit 10 of stats[15] as with the
+ * other *_dev entry points.  Errors: MI_DEGENSAC_EINVAL for a bad norm / dim / kp_dim, Hamming with dim % 4 != 0, decreasing offsets,
+ * a ratio that is not finite and > 0, bad params; n_pairs == 0 returns 0. */
+int mi_degensac_match_verify_batch_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
+                                       const int64_t *offsets1_host, const int64_t *offsets2_host, const double *d_kp1, const double *d_kp2,
+                                       int kp_dim, int n_pairs, const mi_degensac_params *prm, const uint32_t *d_seeds, int device, void *stream,
+                                       double *d_model, int32_t *d_match, uint8_t *d_inlier, int32_t *d_stats, int32_t *h_counts /*nullable*/);
+/* the same on host pointers (blocking; seeds[K] on the host).  Like the other host-pointer entry points, pairs discarded after a
+ * hand-over time-out are run again without producer / helper workgroups (bit 11 of stats[15]). */
+int mi_degensac_match_verify_batch(int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2,
+                                   const int64_t *offsets1, const int64_t *offsets2, const double *kp1, const double *kp2, int kp_dim,
+                                   int n_pairs, const mi_degensac_params *prm, const uint32_t *seeds, int device,
+                                   double *model, int32_t *match, uint8_t *inlier, int32_t *stats /*nullable*/, int32_t *counts /*nullable*/);
+
 /* ---- unit-level device entry points (parity tests of the kernels' building blocks) ------------ */
 /* score n_models fundamental (kind 0: Sampson, 1: symmetric epipolar) or homography (kind 10..14:
  * H Sampson, symm_sq_max, symm_max, symm_sq_sum, symm_sum) models against all n points: I (<= th)

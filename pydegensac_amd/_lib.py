@@ -53,6 +53,15 @@ class H2elParams(C.Structure):
                 ("inl_limit", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MatchParams(C.Structure):
+    """mi_degensac_match_params (include/mi_degensac.h) of the batched match-and-verify entry points"""
+    _fields_ = [("norm", C.c_int32), ("dim", C.c_int32), ("ratio", C.c_float), ("mutual", C.c_int32), ("struct_size", C.c_int32),
+                ("reserved", C.c_int32)]
+
+    def __init__(self, norm=0, dim=0, ratio=0.9, mutual=False):
+        super().__init__(int(norm), int(dim), float(ratio), int(bool(mutual)), C.sizeof(MatchParams), 0)
+
+
 class MiDegensacError(RuntimeError):
     pass
 
@@ -155,6 +164,16 @@ def lib():
         l.mi_degensac_match_knn2_dev.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         l.mi_degensac_match_filter_dev.restype = C.c_int
         l.mi_degensac_match_filter_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        l.mi_degensac_match_knn2_batch_dev.restype = C.c_int
+        l.mi_degensac_match_knn2_batch_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, lp, lp, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]
+        mpp = C.POINTER(MatchParams)
+        l.mi_degensac_match_verify_batch_dev.restype = C.c_int
+        l.mi_degensac_match_verify_batch_dev.argtypes = [C.c_int, mpp, C.c_void_p, C.c_void_p, lp, lp, C.c_void_p, C.c_void_p, C.c_int, C.c_int, pp,
+                                                         C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, ip]
+        l.mi_degensac_match_verify_batch.restype = C.c_int
+        l.mi_degensac_match_verify_batch.argtypes = [C.c_int, mpp, C.c_void_p, C.c_void_p, lp, lp, dp, dp, C.c_int, C.c_int, pp, up, C.c_int,
+                                                     dp, ip, bp, ip, ip]
         l.mi_degensac_kpts_to_xyA.restype = C.c_int
         l.mi_degensac_kpts_to_xyA.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, dp]
         l.mi_degensac_kpts_to_xyA_dev.restype = C.c_int

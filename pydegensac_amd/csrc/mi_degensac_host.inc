@@ -1,5 +1,7 @@
 /* Host side of the C-ABI (include/mi_degensac.h): per-device state, contexts, the per-(device, stream)
  * scratch cache and the batch launch.  Included by mi_degensac.hip after the device headers. */
+#include <math.h>
+#include "mi_match_batch.h"
 
 static thread_local char g_err[512] = "";
 static void set_err(const char *fmt, const char *a = "", const char *b = "") { snprintf(g_err, sizeof g_err, fmt, a, b); }
@@ -723,6 +725,15 @@ extern "C" int mi_degensac_last_call_timing(double *out)
 }
 static double host_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+/* the parameters of a re-run after a hand-over time-out: no producer workgroups, no homography helpers and no helper workgroups
+ * of the cooperative mode (results do not depend on them) */
+static mi_degensac_params rerun_params(const mi_degensac_params *prm, int homography)
+{
+    mi_degensac_params p2s = *prm; p2s.flags = (p2s.flags & ~MI_DEGENSAC_FLAG_STREAM_ON) | MI_DEGENSAC_FLAG_NO_STREAM | MI_DEGENSAC_FLAG_NO_HJOB;
+    if (!homography) p2s.tuning = (p2s.tuning & ~(255u << 8)) | MI_DEGENSAC_TUNE_HELPERS(255);
+    return p2s;
+}
+
 /* host pointers -> one packed pinned block -> one H2D copy -> kernel -> one D2H copy, all on the context's stream */
 static int ctx_batch(mi_degensac_ctx *c, int homography, const double *p1, const double *p2, const int64_t *off, int n_pairs, int dim,
                      const mi_degensac_params *prm, const uint32_t *seeds, double *model, uint8_t *mask, int32_t *stats, int depth = 0)
@@ -808,9 +819,7 @@ static int ctx_batch(mi_degensac_ctx *c, int homography, const double *p1, const
         memcpy(mask, c->h_pin + o_mask, total);
         if (stats) memcpy(stats, c->h_pin + o_stats, (size_t)n_pairs * 64);
         if (redo.empty()) return 0;
-        mi_degensac_params p2s = *prm; p2s.flags = (p2s.flags & ~MI_DEGENSAC_FLAG_STREAM_ON) | MI_DEGENSAC_FLAG_NO_STREAM | MI_DEGENSAC_FLAG_NO_HJOB;
-        /* ... and no helper workgroups of the cooperative mode */
-        if (!homography) p2s.tuning = (p2s.tuning & ~(255u << 8)) | MI_DEGENSAC_TUNE_HELPERS(255);
+        const mi_degensac_params p2s = rerun_params(prm, homography);
         std::vector<double> q1, q2, qm(redo.size() * 9); std::vector<int64_t> qo(redo.size() + 1, 0); std::vector<uint32_t> qs(redo.size());
         std::vector<int32_t> qst(redo.size() * 16);
         for (size_t i = 0; i < redo.size(); i++) { const int p = redo[i]; qo[i + 1] = qo[i] + (off[p + 1] - off[p]); qs[i] = seeds[p]; }
@@ -1050,3 +1059,185 @@ extern "C" int mi_degensac_find_homography_resids(const double *pts1, const doub
 extern "C" int mi_degensac_find_fundamental_hist(const double *pts1, const double *pts2, int n, int dim, const mi_degensac_params *prm,
         uint32_t seed, int device, double *F, uint8_t *mask, int32_t *stats, int32_t *hist)
 { return pair_resids(0, pts1, pts2, n, dim, prm, seed, device, F, mask, stats, nullptr, 0, hist); }
+
+/* ---- batched match-and-verify (include/mi_degensac.h mi_degensac_match_verify_batch[_dev]) ---------------------------------
+ * matching, ratio test and ranks on the device -> ONE read of the per-pair tentative counts -> gather of the eligible pairs'
+ * tentatives -> launch_batch -> scatter back to pair / query order.  Scratch: two stream-ordered blocks per call. */
+static int match_rc(int rc) { if (rc) set_err("%s", mi_degensac_match_last_error()); return rc; }
+
+static int mv_check(int homography, const mi_degensac_match_params *mp, const int64_t *off1, const int64_t *off2, int kp_dim, int n_pairs)
+{
+    if (homography != 0 && homography != 1) { set_err("homography must be 0 or 1"); return MI_DEGENSAC_EINVAL; }
+    if (!mp) { set_err("match params are NULL"); return MI_DEGENSAC_EINVAL; }
+    if ((mp->norm != MI_DEGENSAC_NORM_L2 && mp->norm != MI_DEGENSAC_NORM_HAMMING) || mp->dim <= 0) { set_err("bad norm or descriptor dim");
+        return MI_DEGENSAC_EINVAL; }
+    if (mp->norm == MI_DEGENSAC_NORM_HAMMING && mp->dim % 4) { set_err("Hamming descriptors must be padded to a multiple of 4 bytes");
+        return MI_DEGENSAC_EINVAL; }
+    if (!(isfinite(mp->ratio) && mp->ratio > 0.f)) { set_err("ratio must be finite and > 0"); return MI_DEGENSAC_EINVAL; }
+    if (kp_dim != 2 && kp_dim != 6) { set_err("keypoint rows must be [n,2] or [n,6]"); return MI_DEGENSAC_EINVAL; }
+    if (n_pairs < 0) { set_err("n_pairs < 0"); return MI_DEGENSAC_EINVAL; }
+    if (n_pairs == 0) return 0;
+    for (const int64_t *o : {off1, off2}) {
+        if (!o || o[0] < 0) { set_err("offsets must be given and start at >= 0"); return MI_DEGENSAC_EINVAL; }
+        for (int p = 0; p < n_pairs; p++) if (o[p + 1] < o[p]) { set_err("offsets must be non-decreasing"); return MI_DEGENSAC_EINVAL; }
+        if (o[n_pairs] - o[0] > 0x3fffffff) { set_err("too many descriptor rows in one batch"); return MI_DEGENSAC_EINVAL; }
+    }
+    return 0;
+}
+
+/* stream-ordered device blocks freed (on the stream) when the call returns, whichever way */
+struct MvBlocks {
+    hipStream_t s; char *a = nullptr, *b = nullptr;
+    ~MvBlocks() { if (a) (void)hipFreeAsync(a, s); if (b) (void)hipFreeAsync(b, s); }
+};
+
+static int match_verify_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const int64_t *off1,
+                            const int64_t *off2, const double *d_kp1, const double *d_kp2, int kd, int K, const mi_degensac_params *prm,
+                            const uint32_t *d_seeds, int device, hipStream_t s, double *d_model, int32_t *d_match, uint8_t *d_inlier,
+                            int32_t *d_stats, int32_t *h_counts)
+{
+    int rc = mv_check(homography, mp, off1, off2, kd, K); if (rc) return rc;
+    if (K == 0) return 0;
+    dg_params chk; rc = fill_params(prm, homography, kd, &chk); if (rc) return rc;
+    if (device < 0 || device >= 64) { set_err("bad device index"); return MI_DEGENSAC_EINVAL; }
+    if (mi_degensac_device_count() == 0) { set_err("no HIP device: this library has no CPU path"); return MI_DEGENSAC_ENODEV; }
+    const int64_t n1 = off1[K] - off1[0], n2 = off2[K] - off2[0];
+    if (!d_seeds || !d_model || (n1 > 0 && (!d_desc1 || !d_kp1 || !d_match || !d_inlier)) || (n2 > 0 && (!d_desc2 || !d_kp2))) {
+        set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
+    DevGuard g; rc = g.enter(device); if (rc) return rc;
+    const int words = mp->norm == MI_DEGENSAC_NORM_L2 ? mp->dim : mp->dim / 4;
+    const bool mutual = mp->mutual != 0;
+    /* relative offsets; every row pointer moves to the batch's first row */
+    std::vector<int64_t> o1(K + 1), o2(K + 1); std::vector<int32_t> o32(2 * (size_t)(K + 1));
+    for (int p = 0; p <= K; p++) { o1[p] = off1[p] - off1[0]; o2[p] = off2[p] - off2[0]; o32[p] = (int32_t)o1[p]; o32[K + 1 + p] = (int32_t)o2[p]; }
+    const uint32_t *q1 = (const uint32_t *)d_desc1 + (size_t)off1[0] * words, *q2 = (const uint32_t *)d_desc2 + (size_t)off2[0] * words;
+    const double *kp1 = d_kp1 + (size_t)off1[0] * kd, *kp2 = d_kp2 + (size_t)off2[0] * kd;
+    int32_t *match = d_match + off1[0]; uint8_t *inlier = d_inlier + off1[0];
+
+    /* block A: offsets, forward (and backward) 2-NN, keep / rank / count */
+    const size_t b_off = align_up(o32.size() * 4, 256), b_idx = align_up((size_t)n1 * 8, 256), b_bidx = mutual ? align_up((size_t)n2 * 8, 256) : 0,
+                 b_keep = align_up((size_t)n1, 256), b_cnt = align_up((size_t)K * 4, 256);
+    const size_t a_idx = b_off, a_dist = a_idx + b_idx, a_bidx = a_dist + b_idx, a_bdist = a_bidx + b_bidx, a_keep = a_bdist + b_bidx,
+                 a_rank = a_keep + b_keep, a_cnt = a_rank + b_idx, a_all = a_cnt + b_cnt;
+    MvBlocks blk{s};
+    HIPCHK(hipMallocAsync((void **)&blk.a, a_all, s));
+    char *A = blk.a;
+    const int32_t *d_o1 = (const int32_t *)A, *d_o2 = d_o1 + (K + 1);
+    int32_t *idx = (int32_t *)(A + a_idx), *bidx = mutual ? (int32_t *)(A + a_bidx) : nullptr, *rank = (int32_t *)(A + a_rank), *cnt = (int32_t *)(A + a_cnt);
+    float *dist = (float *)(A + a_dist), *bdist = (float *)(A + a_bdist);
+    uint8_t *keep = (uint8_t *)(A + a_keep);
+    rc = match_rc(mt_batch_upload(device, s, o32.data(), o32.size() * 4, A)); if (rc) return rc;
+    rc = match_rc(mt_batch_knn2(mp->norm, words, q1, q2, o1.data(), o2.data(), K, device, s, idx, dist)); if (rc) return rc;
+    if (mutual) { rc = match_rc(mt_batch_knn2(mp->norm, words, q2, q1, o2.data(), o1.data(), K, device, s, bidx, bdist)); if (rc) return rc; }
+    rc = match_rc(mt_batch_filter_rank(idx, dist, d_o1, d_o2, K, mp->ratio, bidx, s, keep, rank, cnt)); if (rc) return rc;
+
+    /* the one synchronisation: the estimator's launch is sized and configured from the tentative counts on the host */
+    std::vector<int32_t> counts(K);
+    HIPCHK(hipMemcpyAsync(counts.data(), cnt, (size_t)K * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h_counts) memcpy(h_counts, counts.data(), (size_t)K * 4);
+    const int min_pts = homography ? 4 : 8;
+    std::vector<int64_t> est_off(1, 0); std::vector<int32_t> e_of_p(K, -1), pair_of_e;
+    for (int p = 0; p < K; p++)
+        if (counts[p] >= min_pts) { e_of_p[p] = (int32_t)pair_of_e.size(); pair_of_e.push_back(p); est_off.push_back(est_off.back() + counts[p]); }
+    const int E = (int)pair_of_e.size(); const int64_t T = est_off.back();
+
+    /* block B: est_off | e_of_p | pair_of_e (one upload), seeds, models, stats, the estimator's input rows and masks */
+    const size_t c_eoff = 0, c_eop = (size_t)(E + 1) * 8, c_poe = c_eop + (size_t)K * 4, c_all = c_poe + (size_t)E * 4;
+    std::vector<char> tab(c_all);
+    memcpy(tab.data() + c_eoff, est_off.data(), (size_t)(E + 1) * 8); memcpy(tab.data() + c_eop, e_of_p.data(), (size_t)K * 4);
+    if (E) memcpy(tab.data() + c_poe, pair_of_e.data(), (size_t)E * 4);
+    const size_t g_seed = align_up(c_all, 256), g_model = g_seed + align_up((size_t)E * 4, 256), g_stats = g_model + align_up((size_t)E * 72, 256),
+                 g_p1 = g_stats + align_up((size_t)E * 64, 256), g_p2 = g_p1 + align_up((size_t)T * kd * 8, 256),
+                 g_mask = g_p2 + align_up((size_t)T * kd * 8, 256), g_all = g_mask + align_up((size_t)T, 256);
+    HIPCHK(hipMallocAsync((void **)&blk.b, g_all, s));
+    char *B = blk.b;
+    const int64_t *d_eoff = (const int64_t *)(B + c_eoff); const int32_t *d_eop = (const int32_t *)(B + c_eop), *d_poe = (const int32_t *)(B + c_poe);
+    uint32_t *seeds_e = (uint32_t *)(B + g_seed); double *model_e = (double *)(B + g_model), *pts1 = (double *)(B + g_p1), *pts2 = (double *)(B + g_p2);
+    int32_t *stats_e = (int32_t *)(B + g_stats); uint8_t *mask_e = (uint8_t *)(B + g_mask);
+    rc = match_rc(mt_batch_upload(device, s, tab.data(), c_all, B)); if (rc) return rc;
+    if (E > 0) {
+        rc = match_rc(mt_batch_gather(E, d_poe, d_eoff, d_o1, d_o2, keep, rank, idx, kp1, kp2, kd, d_seeds, s, pts1, pts2, seeds_e)); if (rc) return rc;
+        rc = launch_batch(homography, pts1, pts2, d_eoff, est_off.data(), E, kd, prm, seeds_e, device, s, model_e, mask_e, stats_e);
+        if (rc) return rc;
+    }
+    return match_rc(mt_batch_scatter(K, d_eop, d_eoff, d_o1, keep, rank, idx, model_e, stats_e, mask_e, s, d_model, d_stats, match, inlier));
+}
+
+extern "C" int mi_degensac_match_verify_batch_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
+        const int64_t *offsets1_host, const int64_t *offsets2_host, const double *d_kp1, const double *d_kp2, int kp_dim, int n_pairs,
+        const mi_degensac_params *prm, const uint32_t *d_seeds, int device, void *stream, double *d_model, int32_t *d_match, uint8_t *d_inlier,
+        int32_t *d_stats, int32_t *h_counts)
+{
+    return match_verify_dev(homography, mp, d_desc1, d_desc2, offsets1_host, offsets2_host, d_kp1, d_kp2, kp_dim, n_pairs, prm, d_seeds, device,
+                            (hipStream_t)stream, d_model, d_match, d_inlier, d_stats, h_counts);
+}
+
+/* host pointers: stage on the calling thread's context, run the device path on its stream, copy back; pairs discarded after a
+ * hand-over time-out go through ctx_batch's re-run (depth 1) on exactly their gathered tentatives */
+extern "C" int mi_degensac_match_verify_batch(int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2,
+        const int64_t *offsets1, const int64_t *offsets2, const double *kp1, const double *kp2, int kd, int K, const mi_degensac_params *prm,
+        const uint32_t *seeds, int device, double *model, int32_t *match, uint8_t *inlier, int32_t *stats, int32_t *counts)
+{
+    int rc = mv_check(homography, mp, offsets1, offsets2, kd, K); if (rc) return rc;
+    if (K == 0) return 0;
+    if (!desc1 || !desc2 || !kp1 || !kp2 || !seeds || !model || !match || !inlier) { set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
+    mi_degensac_ctx *c; rc = thread_ctx(device, &c); if (rc) return rc;
+    DevGuard g; rc = g.enter(device); if (rc) return rc;
+    const int64_t n1 = offsets1[K] - offsets1[0], n2 = offsets2[K] - offsets2[0];
+    const size_t row = (size_t)mp->dim * (mp->norm == MI_DEGENSAC_NORM_L2 ? 4 : 1);
+    std::vector<int64_t> o1(K + 1), o2(K + 1);
+    for (int p = 0; p <= K; p++) { o1[p] = offsets1[p] - offsets1[0]; o2[p] = offsets2[p] - offsets2[0]; }
+    const size_t s_d1 = align_up(n1 * row, 256), s_d2 = align_up(n2 * row, 256), s_k1 = align_up((size_t)n1 * kd * 8, 256),
+                 s_k2 = align_up((size_t)n2 * kd * 8, 256), s_sd = align_up((size_t)K * 4, 256), s_mo = align_up((size_t)K * 72, 256),
+                 s_ma = align_up((size_t)n1 * 4, 256), s_in = align_up((size_t)n1, 256), s_st = align_up((size_t)K * 64, 256);
+    const size_t a_d2 = s_d1, a_k1 = a_d2 + s_d2, a_k2 = a_k1 + s_k1, a_sd = a_k2 + s_k2, a_mo = a_sd + s_sd, a_ma = a_mo + s_mo, a_in = a_ma + s_ma,
+                 a_st = a_in + s_in, a_all = a_st + s_st;
+    char *D = nullptr;
+    struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
+    HIPCHK(hipMalloc((void **)&D, a_all));
+    HIPCHK(hipMemcpy(D, (const char *)desc1 + offsets1[0] * row, n1 * row, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(D + a_d2, (const char *)desc2 + offsets2[0] * row, n2 * row, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(D + a_k1, kp1 + offsets1[0] * kd, (size_t)n1 * kd * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(D + a_k2, kp2 + offsets2[0] * kd, (size_t)n2 * kd * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(D + a_sd, seeds, (size_t)K * 4, hipMemcpyHostToDevice));
+    std::vector<int32_t> cnt(K), st((size_t)K * 16);
+    rc = match_verify_dev(homography, mp, D, D + a_d2, o1.data(), o2.data(), (const double *)(D + a_k1), (const double *)(D + a_k2), kd, K, prm,
+                          (const uint32_t *)(D + a_sd), device, c->stream, (double *)(D + a_mo), (int32_t *)(D + a_ma), (uint8_t *)(D + a_in),
+                          (int32_t *)(D + a_st), cnt.data());
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    int32_t *mt = match + offsets1[0]; uint8_t *in = inlier + offsets1[0];
+    HIPCHK(hipMemcpy(model, D + a_mo, (size_t)K * 72, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(mt, D + a_ma, (size_t)n1 * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(in, D + a_in, (size_t)n1, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(st.data(), D + a_st, (size_t)K * 64, hipMemcpyDeviceToHost));
+    std::vector<int> redo;
+    for (int p = 0; p < K; p++) if (st[(size_t)p * 16 + 15] & 1024) redo.push_back(p);
+    if (!redo.empty()) {
+        /* exactly the discarded pairs' tentatives, in the order the device gathered them (query order) */
+        const double *k1 = kp1 + offsets1[0] * kd, *k2 = kp2 + offsets2[0] * kd;
+        std::vector<double> q1, q2; std::vector<int64_t> qo(1, 0); std::vector<uint32_t> qs;
+        for (int p : redo) {
+            for (int64_t i = o1[p]; i < o1[p + 1]; i++) if (mt[i] >= 0) {
+                q1.insert(q1.end(), k1 + i * kd, k1 + (i + 1) * kd);
+                q2.insert(q2.end(), k2 + (o2[p] + mt[i]) * kd, k2 + (o2[p] + mt[i] + 1) * kd);
+            }
+            qo.push_back((int64_t)q1.size() / kd); qs.push_back(seeds[p]);
+        }
+        const int R = (int)redo.size();
+        const mi_degensac_params p2s = rerun_params(prm, homography);
+        std::vector<double> qm((size_t)R * 9); std::vector<uint8_t> qk((size_t)qo.back()); std::vector<int32_t> qst((size_t)R * 16);
+        rc = ctx_batch(c, homography, q1.data(), q2.data(), qo.data(), R, kd, &p2s, qs.data(), qm.data(), qk.data(), qst.data(), 1);
+        if (rc) return rc;
+        for (int r = 0; r < R; r++) {
+            const int p = redo[r]; int64_t k = qo[r];
+            memcpy(model + (size_t)p * 9, qm.data() + (size_t)r * 9, 72);
+            for (int64_t i = o1[p]; i < o1[p + 1]; i++) if (mt[i] >= 0) in[i] = qk[k++];
+            memcpy(st.data() + (size_t)p * 16, qst.data() + (size_t)r * 16, 64); st[(size_t)p * 16 + 15] |= 2048;     /* bit 11: run again */
+        }
+    }
+    if (stats) memcpy(stats, st.data(), (size_t)K * 64);
+    if (counts) memcpy(counts, cnt.data(), (size_t)K * 4);
+    return 0;
+}

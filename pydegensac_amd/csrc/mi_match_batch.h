@@ -1,0 +1,34 @@
+/* Internal interface between the batched matcher stages (mi_matcher.hip) and the match-and-verify orchestration in
+ * mi_degensac_host.inc, which needs launch_batch.  Not part of the C-ABI: hidden symbols of libmi_degensac.so.
+ *
+ * Row offsets passed here are relative (offs[0] = 0) and every device pointer is already moved to the batch's first row.
+ * All functions enqueue on `s` and never synchronise; the device must be current.  Errors: a MI_DEGENSAC_E* code, message in
+ * mi_degensac_match_last_error(). */
+#ifndef MI_MATCH_BATCH_H
+#define MI_MATCH_BATCH_H
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define MT_HIDDEN __attribute__((visibility("hidden")))
+
+/* host -> device copy of `bytes` through a pinned staging block: asynchronous, the host block may be reused at once */
+MT_HIDDEN int mt_batch_upload(int device, hipStream_t s, const void *h, size_t bytes, void *d);
+/* batched 2-NN: every row of pair p in q (rows oq[p] .. oq[p+1]) against the rows ot[p] .. ot[p+1] of t; idx / dist [oq[K], 2],
+ * indices local to the pair.  words = 32-bit words per descriptor row. */
+MT_HIDDEN int mt_batch_knn2(int norm, int words, const void *dq, const void *dt, const int64_t *oq, const int64_t *ot, int n_pairs, int device,
+                            hipStream_t s, int32_t *idx, float *dist);
+/* ratio test (+ mutual check when d_back is set) and the rank of every kept query among its pair's kept queries; one
+ * workgroup per pair.  d_off1 / d_off2: [K + 1] relative int32 row offsets on the device. */
+MT_HIDDEN int mt_batch_filter_rank(const int32_t *d_idx, const float *d_dist, const int32_t *d_off1, const int32_t *d_off2, int n_pairs, float ratio,
+                                   const int32_t *d_back, hipStream_t s, uint8_t *d_keep, int32_t *d_rank, int32_t *d_count);
+/* the estimator's input rows of the E eligible pairs: pts[est_off[e] + rank[i]] = kp rows of query i and of its nearest train row;
+ * seeds_e[e] = seeds[pair_of_e[e]] */
+MT_HIDDEN int mt_batch_gather(int n_eligible, const int32_t *d_pair_of_e, const int64_t *d_est_off, const int32_t *d_off1, const int32_t *d_off2,
+                              const uint8_t *d_keep, const int32_t *d_rank, const int32_t *d_idx, const double *d_kp1, const double *d_kp2, int kp_dim,
+                              const uint32_t *d_seeds, hipStream_t s, double *d_pts1, double *d_pts2, uint32_t *d_seeds_e);
+/* results back to pair order: model / stats of eligible index e_of_p[p] (zeros for short pairs, e_of_p[p] = -1), match[i] = the
+ * pair-local train row of a tentative or -1, inlier[i] = tentative and inlier of the pair's model */
+MT_HIDDEN int mt_batch_scatter(int n_pairs, const int32_t *d_e_of_p, const int64_t *d_est_off, const int32_t *d_off1, const uint8_t *d_keep,
+                               const int32_t *d_rank, const int32_t *d_idx, const double *d_model_e, const int32_t *d_stats_e, const uint8_t *d_mask_e,
+                               hipStream_t s, double *d_model, int32_t *d_stats /*nullable*/, int32_t *d_match, uint8_t *d_inlier);
+#endif /* MI_MATCH_BATCH_H */

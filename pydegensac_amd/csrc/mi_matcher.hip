@@ -11,12 +11,17 @@
  * images' worth of descriptors, and is LDS-tiled instead: a workgroup owns 64 queries, streams the train set through
  * LDS 64 rows at a time (both tiles stored dimension-major, so a wave reads consecutive words / one broadcast word),
  * every thread keeps a 4 x 4 block of running sums in registers and its own running top-2 per query; the 16 threads
- * sharing a query merge their candidates at the end.  The train set is additionally split over blockIdx.y (see mt_knn2_kernel). */
+ * sharing a query merge their candidates at the end.  The train set is additionally split over blockIdx.y (see mt_knn2_kernel).
+ * The batched form (mt_knn2_batch_kernel, mi_degensac_match_*_batch*) runs the same tile body over every pair's query tiles in one
+ * launch and feeds the match-and-verify path in mi_degensac_host.inc (filter + rank, gather, scatter below). */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <mutex>
+#include <vector>
 #include "../../include/mi_degensac.h"
+#include "mi_match_batch.h"
 
 #define MT_Q   64            /* queries per workgroup */
 #define MT_T   64            /* train rows per LDS tile */
@@ -33,25 +38,18 @@ __device__ __forceinline__ void mt_push(mt_best &b, float d, int i)
     else if (lt1) { b.d1 = d; b.i1 = i; }
 }
 
-/* NORM: 0 = L2 over float words, 1 = Hamming over 32-bit words of packed bytes.  q, t: [n, words] row-major. */
-/* Launch shape: grid = (ceil(n1 / 64), train splits).  Two images' worth of descriptors give only a few dozen query
- * tiles (1 500 queries = 24), so the train set is split over blockIdx.y until the grid covers the CUs about twice; a split
- * writes its top-2 per query (squared distances) to part[split][query] and mt_merge_kernel merges the splits with the same
- * (distance, index) order, so the result does not depend on the split count.  With one split the kernel writes the final
- * answer itself. */
+/* One workgroup's tile: queries q0 .. q_end - 1 (at most 64) of q against train rows t_lo .. t_hi - 1 of t, candidates
+ * indexed from t_base (0 for a single pair, the pair's first train row in a batch).  NORM: 0 = L2 over float words,
+ * 1 = Hamming over 32-bit words of packed bytes; q, t: [n, words] row-major.  Returns true in the threads tid < 64 whose
+ * query exists, with that query's merged top-2 (squared distances for L2) in m. */
 template <int NORM>
-__global__ __launch_bounds__(256) void mt_knn2_kernel(const uint32_t *q, int n1, const uint32_t *t, int n2, int words,
-    int t_chunk /* train rows per split, multiple of 64 */,
-                                                      int32_t *idx /* [n1,2] */, float *dist /* [n1,2] */, mt_best *part /* [splits][n1] or null */)
+__device__ __forceinline__ bool mt_knn2_tile(const uint32_t *q, int q0, int q_end, const uint32_t *t, int t_lo, int t_hi, int t_base, int words,
+                                             uint32_t (&qs)[MT_DC][MT_Q + 1], uint32_t (&ts)[MT_DC][MT_T + 1], mt_best (&merge)[MT_Q][16], mt_best &m)
 {
-    __shared__ uint32_t qs[MT_DC][MT_Q + 1], ts[MT_DC][MT_T + 1];
-    __shared__ mt_best merge[MT_Q][16];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const int q0 = blockIdx.x * MT_Q;
     mt_best best[4];
 #pragma unroll
     for (int a = 0; a < 4; a++) { best[a].d0 = best[a].d1 = __builtin_inff(); best[a].i0 = best[a].i1 = -1; }
-    const int t_lo = (int)blockIdx.y * t_chunk, t_hi = t_lo + t_chunk < n2 ? t_lo + t_chunk : n2;
     for (int t0 = t_lo; t0 < t_hi; t0 += MT_T) {
         float acc[4][4]; unsigned hacc[4][4];
 #pragma unroll
@@ -63,7 +61,7 @@ __global__ __launch_bounds__(256) void mt_knn2_kernel(const uint32_t *q, int n1,
             /* stage both tiles dimension-major: thread r loads row (r / 4), a quarter of the chunk's words, coalesced per row */
             for (int e = tid; e < MT_Q * MT_DC; e += 256) {
                 const int r = e / MT_DC, w = e - r * MT_DC;
-                const bool okq = q0 + r < n1 && w0 + w < words, okt = t0 + r < t_hi && w0 + w < words;
+                const bool okq = q0 + r < q_end && w0 + w < words, okt = t0 + r < t_hi && w0 + w < words;
                 qs[w][r] = okq ? q[(size_t)(q0 + r) * words + w0 + w] : 0u;
                 ts[w][r] = okt ? t[(size_t)(t0 + r) * words + w0 + w] : 0u;
             }
@@ -89,21 +87,63 @@ __global__ __launch_bounds__(256) void mt_knn2_kernel(const uint32_t *q, int n1,
 #pragma unroll
             for (int b = 0; b < 4; b++) {
                 const int ti = t0 + tx + 16 * b;
-                if (ti < t_hi) mt_push(best[a], NORM == 0 ? acc[a][b] : (float)hacc[a][b], ti);
+                if (ti < t_hi) mt_push(best[a], NORM == 0 ? acc[a][b] : (float)hacc[a][b], ti - t_base);
             }
     }
     /* the 16 threads of a query row merge their candidates (lane order does not matter: mt_push orders by (d, i)) */
 #pragma unroll
     for (int a = 0; a < 4; a++) merge[4 * ty + a][tx] = best[a];
     __syncthreads();
-    if (tid < MT_Q && q0 + tid < n1) {
-        mt_best m = merge[tid][0];
-        for (int k = 1; k < 16; k++) { const mt_best c = merge[tid][k]; if (c.i0 >= 0) mt_push(m, c.d0, c.i0); if (c.i1 >= 0) mt_push(m, c.d1, c.i1); }
-        if (part) { part[(size_t)blockIdx.y * n1 + q0 + tid] = m; return; }
-        const size_t o = (size_t)(q0 + tid) * 2;
-        idx[o] = m.i0; idx[o + 1] = m.i1;
-        dist[o] = NORM == 0 ? sqrtf(m.d0) : m.d0; dist[o + 1] = NORM == 0 ? sqrtf(m.d1) : m.d1;
-    }
+    if (tid >= MT_Q || q0 + tid >= q_end) return false;
+    m = merge[tid][0];
+    for (int k = 1; k < 16; k++) { const mt_best c = merge[tid][k]; if (c.i0 >= 0) mt_push(m, c.d0, c.i0); if (c.i1 >= 0) mt_push(m, c.d1, c.i1); }
+    return true;
+}
+
+/* final answer of query row r from its merged top-2, or its partial of split `split` when the train set is split */
+template <int NORM>
+__device__ __forceinline__ void mt_store(const mt_best &m, int r, int n_rows, int split, int32_t *idx, float *dist, mt_best *part)
+{
+    if (part) { part[(size_t)split * n_rows + r] = m; return; }
+    const size_t o = (size_t)r * 2;
+    idx[o] = m.i0; idx[o + 1] = m.i1;
+    dist[o] = NORM == 0 ? sqrtf(m.d0) : m.d0; dist[o + 1] = NORM == 0 ? sqrtf(m.d1) : m.d1;
+}
+
+/* Launch shape: grid = (ceil(n1 / 64), train splits).  Two images' worth of descriptors give only a few dozen query
+ * tiles (1 500 queries = 24), so the train set is split over blockIdx.y until the grid covers the CUs about twice; a split
+ * writes its top-2 per query (squared distances) to part[split][query] and mt_merge_kernel merges the splits with the same
+ * (distance, index) order, so the result does not depend on the split count.  With one split the kernel writes the final
+ * answer itself. */
+template <int NORM>
+__global__ __launch_bounds__(256) void mt_knn2_kernel(const uint32_t *q, int n1, const uint32_t *t, int n2, int words,
+    int t_chunk /* train rows per split, multiple of 64 */,
+                                                      int32_t *idx /* [n1,2] */, float *dist /* [n1,2] */, mt_best *part /* [splits][n1] or null */)
+{
+    __shared__ uint32_t qs[MT_DC][MT_Q + 1], ts[MT_DC][MT_T + 1];
+    __shared__ mt_best merge[MT_Q][16];
+    const int q0 = blockIdx.x * MT_Q;
+    const int t_lo = (int)blockIdx.y * t_chunk, t_hi = t_lo + t_chunk < n2 ? t_lo + t_chunk : n2;
+    mt_best m;
+    if (mt_knn2_tile<NORM>(q, q0, n1, t, t_lo, t_hi, 0, words, qs, ts, merge, m))
+        mt_store<NORM>(m, q0 + threadIdx.x, n1, blockIdx.y, idx, dist, part);
+}
+
+/* The ragged batch (include/mi_degensac.h mi_degensac_match_knn2_batch_dev): one launch over every pair's 64-query tiles.
+ * tiles[blockIdx.x] = (first query row, end of the pair's query rows, first train row of the pair, end of its train rows), built on
+ * the host from the host offsets; rows are global over the batch, the indices written are local to the pair.  Split y takes
+ * the pair's train rows t_begin + y t_chunk .. + t_chunk (possibly none: the partial then stays at (inf, -1)). */
+template <int NORM>
+__global__ __launch_bounds__(256) void mt_knn2_batch_kernel(const uint32_t *q, const uint32_t *t, int words, const int4 *tiles, int n_rows,
+                                                            int t_chunk, int32_t *idx, float *dist, mt_best *part)
+{
+    __shared__ uint32_t qs[MT_DC][MT_Q + 1], ts[MT_DC][MT_T + 1];
+    __shared__ mt_best merge[MT_Q][16];
+    const int4 tl = tiles[blockIdx.x];
+    const int t_lo = tl.z + (int)blockIdx.y * t_chunk, t_hi = t_lo + t_chunk < tl.w ? t_lo + t_chunk : tl.w;
+    mt_best m;
+    if (mt_knn2_tile<NORM>(q, tl.x, tl.y, t, t_lo, t_hi, tl.z, words, qs, ts, merge, m))
+        mt_store<NORM>(m, tl.x + threadIdx.x, n_rows, blockIdx.y, idx, dist, part);
 }
 
 /* merge the per-split top-2 of every query (any order gives the same result: mt_push orders by (distance, index)) */
@@ -140,6 +180,70 @@ __global__ void mt_kpts_to_xyA_kernel(const float *kp, int n, double *out)
     const double r = a * 3.141592653589793 / 180.0, cs = cos(r), sn = sin(r);
     double *o = out + (size_t)i * 6;
     o[0] = x; o[1] = y; o[2] = s * cs; o[3] = s * sn; o[4] = -s * sn; o[5] = s * cs;
+}
+
+/* ---- the batched match-and-verify stages (mi_match_batch.h) ------------------------------------------------------------ */
+/* One workgroup per pair sweeps its queries 256 at a time: keep[i] is mt_filter_kernel's decision, rank[i] its position
+ * among the pair's kept queries in ascending query order (-1 when not kept), count[p] their number.  Positions come from
+ * wave ballots and a four-entry prefix over the waves, so they do not depend on scheduling. */
+__global__ __launch_bounds__(256) void mt_filter_rank_kernel(const int32_t *idx, const float *dist, const int32_t *off1, const int32_t *off2,
+                                                             float ratio, const int32_t *back, uint8_t *keep, int32_t *rank, int32_t *count)
+{
+    __shared__ int wsum[4];
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int lo = off1[p], hi = off1[p + 1], b2 = off2[p];
+    int base = 0;
+    for (int i0 = lo; i0 < hi; i0 += 256) {
+        const int i = i0 + tid;
+        bool ok = false;
+        if (i < hi) {
+            const int j = idx[2 * i], j2 = idx[2 * i + 1];
+            ok = j >= 0 && j2 >= 0 && dist[2 * i] < ratio * dist[2 * i + 1];
+            if (ok && back) ok = back[2 * (b2 + j)] == i - lo;
+        }
+        const unsigned long long bal = __ballot(ok);
+        if (lane == 0) wsum[wv] = __popcll(bal);
+        __syncthreads();
+        int pre = base;
+        for (int w = 0; w < wv; w++) pre += wsum[w];
+        if (i < hi) { keep[i] = ok ? 1 : 0; rank[i] = ok ? pre + __popcll(bal & ((1ull << lane) - 1ull)) : -1; }
+        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+    if (tid == 0) count[p] = base;
+}
+
+/* one workgroup per eligible pair: its tentatives in query order become rows est_off[e] .. of the estimator's input */
+__global__ __launch_bounds__(256) void mt_gather_kernel(const int32_t *pair_of_e, const int64_t *est_off, const int32_t *off1, const int32_t *off2,
+                                                        const uint8_t *keep, const int32_t *rank, const int32_t *idx, const double *kp1,
+                                                        const double *kp2, int kd, const uint32_t *seeds, double *pts1, double *pts2, uint32_t *seeds_e)
+{
+    const int e = blockIdx.x, p = pair_of_e[e];
+    const int lo = off1[p], hi = off1[p + 1];
+    const int64_t o = est_off[e], b2 = off2[p];
+    if (threadIdx.x == 0) seeds_e[e] = seeds[p];
+    for (int i = lo + (int)threadIdx.x; i < hi; i += 256) {
+        if (!keep[i]) continue;
+        const int64_t r = o + rank[i], j = b2 + idx[2 * i];
+        for (int c = 0; c < kd; c++) { pts1[r * kd + c] = kp1[(int64_t)i * kd + c]; pts2[r * kd + c] = kp2[j * kd + c]; }
+    }
+}
+
+/* one workgroup per pair: model / stats from the eligible index (zeros for a short pair), match and inlier per query */
+__global__ __launch_bounds__(256) void mt_scatter_kernel(const int32_t *e_of_p, const int64_t *est_off, const int32_t *off1, const uint8_t *keep,
+                                                         const int32_t *rank, const int32_t *idx, const double *model_e, const int32_t *stats_e,
+                                                         const uint8_t *mask_e, double *model, int32_t *stats, int32_t *match, uint8_t *inlier)
+{
+    const int p = blockIdx.x, tid = threadIdx.x, e = e_of_p[p];
+    if (tid < 9) model[(int64_t)p * 9 + tid] = e >= 0 ? model_e[(int64_t)e * 9 + tid] : 0.0;
+    if (stats && tid < MI_DEGENSAC_STATS_LEN)
+        stats[(int64_t)p * MI_DEGENSAC_STATS_LEN + tid] = e >= 0 ? stats_e[(int64_t)e * MI_DEGENSAC_STATS_LEN + tid] : 0;
+    const int64_t o = e >= 0 ? est_off[e] : 0;
+    for (int i = off1[p] + tid; i < off1[p + 1]; i += 256) {
+        const bool k = keep[i] != 0;
+        match[i] = k ? idx[2 * i] : -1;
+        inlier[i] = (k && e >= 0) ? mask_e[o + rank[i]] : 0;
+    }
 }
 
 static thread_local char mt_err[256] = "";
@@ -264,4 +368,145 @@ extern "C" int mi_degensac_kpts_to_xyA(const float *kpts, int n, int device, dou
     MTCHK(hipDeviceSynchronize());
     MTCHK(hipMemcpy(out, dout, (size_t)n * 48, hipMemcpyDeviceToHost));
     return 0;
+}
+
+/* ---- batched matcher: host side ------------------------------------------------------------------------------------ */
+static int mt_cus(int device)
+{
+    static int cache[64] = {0};
+    if (device >= 0 && device < 64 && cache[device] > 0) return cache[device];
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
+    if (device >= 0 && device < 64) cache[device] = cus;
+    return cus;
+}
+
+/* Pinned staging blocks of the uploads: a block is taken again only once the copy that read it has run (its event), so an
+ * upload never waits for the stream; when all blocks of the device are busy a new one is made (at most 16, then the oldest
+ * fitting one is waited for). */
+struct MtPin { int device; char *h; size_t cap; hipEvent_t ev; };
+static std::mutex mt_pin_mu;
+static std::vector<MtPin> mt_pins;
+
+int mt_batch_upload(int device, hipStream_t s, const void *h, size_t bytes, void *d)
+{
+    if (bytes == 0) return 0;
+    std::lock_guard<std::mutex> lk(mt_pin_mu);
+    MtPin *b = nullptr, *busy = nullptr; int mine = 0;
+    for (auto &e : mt_pins) {
+        if (e.device != device) continue;
+        mine++;
+        if (e.cap < bytes) continue;
+        if (hipEventQuery(e.ev) == hipSuccess) { b = &e; break; }
+        (void)hipGetLastError();
+        if (!busy) busy = &e;
+    }
+    if (!b && busy && mine >= 16) { MTCHK(hipEventSynchronize(busy->ev)); b = busy; }
+    if (!b) {
+        MtPin n{device, nullptr, bytes < ((size_t)1 << 16) ? ((size_t)1 << 16) : bytes + bytes / 4, nullptr};
+        MTCHK(hipHostMalloc((void **)&n.h, n.cap, hipHostMallocDefault));
+        if (hipEventCreateWithFlags(&n.ev, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(n.h); MTCHK(hipErrorOutOfMemory); }
+        mt_pins.push_back(n); b = &mt_pins.back();
+    }
+    memcpy(b->h, h, bytes);
+    MTCHK(hipMemcpyAsync(d, b->h, bytes, hipMemcpyHostToDevice, s));
+    MTCHK(hipEventRecord(b->ev, s));
+    return 0;
+}
+
+/* One launch over the 64-query tiles of every pair.  The train set is split over blockIdx.y only when the batch's tiles do not
+ * cover the CUs about twice (as in mi_degensac_match_knn2_dev, with the largest pair's train set deciding the chunk). */
+int mt_batch_knn2(int norm, int words, const void *dq, const void *dt, const int64_t *oq, const int64_t *ot, int n_pairs, int device, hipStream_t s,
+                  int32_t *idx, float *dist)
+{
+    const int n_rows = (int)oq[n_pairs];
+    if (n_rows == 0) return 0;
+    std::vector<int4> tiles;
+    int max_n2 = 0;
+    for (int p = 0; p < n_pairs; p++) {
+        const int q_end = (int)oq[p + 1], t_b = (int)ot[p], t_e = (int)ot[p + 1];
+        if (t_e - t_b > max_n2) max_n2 = t_e - t_b;
+        for (int q0 = (int)oq[p]; q0 < q_end; q0 += MT_Q) tiles.push_back(make_int4(q0, q_end, t_b, t_e));
+    }
+    const int qtiles = (int)tiles.size(), ttiles = max_n2 > 0 ? (max_n2 + MT_T - 1) / MT_T : 1, cus = mt_cus(device);
+    int splits = qtiles >= 2 * cus ? 1 : (2 * cus + qtiles - 1) / qtiles;
+    if (splits > ttiles) splits = ttiles; if (splits < 1) splits = 1; if (splits > 256) splits = 256;
+    const int t_chunk = max_n2 > 0 ? ((ttiles + splits - 1) / splits) * MT_T : MT_T;
+    splits = max_n2 > 0 ? (max_n2 + t_chunk - 1) / t_chunk : 1;
+    const size_t b_tiles = ((size_t)qtiles * sizeof(int4) + 255) / 256 * 256, b_part = splits > 1 ? (size_t)splits * n_rows * sizeof(mt_best) : 0;
+    char *buf = nullptr;
+    MTCHK(hipMallocAsync((void **)&buf, b_tiles + b_part, s));
+    int rc = mt_batch_upload(device, s, tiles.data(), (size_t)qtiles * sizeof(int4), buf);
+    if (rc) { (void)hipFreeAsync(buf, s); return rc; }
+    mt_best *part = splits > 1 ? (mt_best *)(buf + b_tiles) : nullptr;
+    const dim3 grid(qtiles, splits), block(256);
+    if (norm == MI_DEGENSAC_NORM_L2) hipLaunchKernelGGL(mt_knn2_batch_kernel<0>, grid, block, 0, s, (const uint32_t *)dq, (const uint32_t *)dt, words,
+        (const int4 *)buf, n_rows, t_chunk, idx, dist, part);
+    else                             hipLaunchKernelGGL(mt_knn2_batch_kernel<1>, grid, block, 0, s, (const uint32_t *)dq, (const uint32_t *)dt, words,
+        (const int4 *)buf, n_rows, t_chunk, idx, dist, part);
+    hipError_t le = hipGetLastError();
+    if (le == hipSuccess && part) {
+        hipLaunchKernelGGL(mt_merge_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, s, part, splits, n_rows, norm == MI_DEGENSAC_NORM_L2 ? 1 : 0, idx, dist);
+        le = hipGetLastError();
+    }
+    (void)hipFreeAsync(buf, s);
+    MTCHK(le);
+    return 0;
+}
+
+int mt_batch_filter_rank(const int32_t *d_idx, const float *d_dist, const int32_t *d_off1, const int32_t *d_off2, int n_pairs, float ratio,
+                         const int32_t *d_back, hipStream_t s, uint8_t *d_keep, int32_t *d_rank, int32_t *d_count)
+{
+    if (n_pairs <= 0) return 0;
+    hipLaunchKernelGGL(mt_filter_rank_kernel, dim3(n_pairs), dim3(256), 0, s, d_idx, d_dist, d_off1, d_off2, ratio, d_back, d_keep, d_rank, d_count);
+    MTCHK(hipGetLastError());
+    return 0;
+}
+
+int mt_batch_gather(int n_eligible, const int32_t *d_pair_of_e, const int64_t *d_est_off, const int32_t *d_off1, const int32_t *d_off2,
+                    const uint8_t *d_keep, const int32_t *d_rank, const int32_t *d_idx, const double *d_kp1, const double *d_kp2, int kp_dim,
+                    const uint32_t *d_seeds, hipStream_t s, double *d_pts1, double *d_pts2, uint32_t *d_seeds_e)
+{
+    if (n_eligible <= 0) return 0;
+    hipLaunchKernelGGL(mt_gather_kernel, dim3(n_eligible), dim3(256), 0, s, d_pair_of_e, d_est_off, d_off1, d_off2, d_keep, d_rank, d_idx, d_kp1, d_kp2,
+        kp_dim, d_seeds, d_pts1, d_pts2, d_seeds_e);
+    MTCHK(hipGetLastError());
+    return 0;
+}
+
+int mt_batch_scatter(int n_pairs, const int32_t *d_e_of_p, const int64_t *d_est_off, const int32_t *d_off1, const uint8_t *d_keep, const int32_t *d_rank,
+                     const int32_t *d_idx, const double *d_model_e, const int32_t *d_stats_e, const uint8_t *d_mask_e, hipStream_t s, double *d_model,
+                     int32_t *d_stats, int32_t *d_match, uint8_t *d_inlier)
+{
+    if (n_pairs <= 0) return 0;
+    hipLaunchKernelGGL(mt_scatter_kernel, dim3(n_pairs), dim3(256), 0, s, d_e_of_p, d_est_off, d_off1, d_keep, d_rank, d_idx, d_model_e, d_stats_e,
+        d_mask_e, d_model, d_stats, d_match, d_inlier);
+    MTCHK(hipGetLastError());
+    return 0;
+}
+
+/* offsets of a ragged batch: non-decreasing, starting at >= 0, rows addressable with int32 */
+static int mt_check_offsets(const int64_t *o, int n_pairs)
+{
+    if (!o || o[0] < 0) return 0;
+    for (int p = 0; p < n_pairs; p++) if (o[p + 1] < o[p]) return 0;
+    return o[n_pairs] - o[0] <= 0x3fffffff;
+}
+
+extern "C" int mi_degensac_match_knn2_batch_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
+                                                const int64_t *offsets2_host, int n_pairs, int dim, int device, void *stream, int32_t *d_idx,
+                                                float *d_dist)
+{
+    if ((norm != MI_DEGENSAC_NORM_L2 && norm != MI_DEGENSAC_NORM_HAMMING) || n_pairs < 0 || dim <= 0) { snprintf(mt_err, sizeof mt_err, "bad argument");
+        return MI_DEGENSAC_EINVAL; }
+    const int words = mt_words(norm, dim);
+    if (words < 0) { snprintf(mt_err, sizeof mt_err, "Hamming descriptors must be padded to a multiple of 4 bytes"); return MI_DEGENSAC_EINVAL; }
+    if (n_pairs == 0) return 0;
+    if (!mt_check_offsets(offsets1_host, n_pairs) || !mt_check_offsets(offsets2_host, n_pairs)) {
+        snprintf(mt_err, sizeof mt_err, "offsets must be non-negative and non-decreasing"); return MI_DEGENSAC_EINVAL; }
+    MtDevGuard g; int rc = g.enter(device); if (rc) return rc;
+    std::vector<int64_t> o1(n_pairs + 1), o2(n_pairs + 1);
+    for (int p = 0; p <= n_pairs; p++) { o1[p] = offsets1_host[p] - offsets1_host[0]; o2[p] = offsets2_host[p] - offsets2_host[0]; }
+    return mt_batch_knn2(norm, words, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words,
+                         (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words, o1.data(), o2.data(), n_pairs, device, (hipStream_t)stream, d_idx + 2 * offsets1_host[0], d_dist + 2 * offsets1_host[0]);
 }

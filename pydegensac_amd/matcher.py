@@ -83,3 +83,138 @@ def kpts_to_xyA(kpts, device=0):
     if rc != 0:
         raise _lib.MiDegensacError(f"mi_degensac error {rc}: {_lib.lib().mi_degensac_match_last_error().decode()}")
     return out
+
+
+# ---- many image pairs at once: descriptors + keypoints -> tentatives -> F / H (include/mi_degensac.h mi_degensac_match_verify_batch*) ----
+_MODEL_DEFAULTS = {"F": (0.5, 0.9999, 100000), "H": (1.0, 0.999, 50000)}          # findFundamentalMatrix / findHomography
+
+
+def _dtype_name(dt):
+    s = str(dt)
+    return s[6:] if s.startswith("torch.") else np.dtype(dt).name
+
+
+def check_match_verify_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype, counts1, counts2):
+    """The argument checks of the batched match-and-verify calls, on shapes and dtype names only (numpy or torch).  Returns
+    (norm code, "xy" for float64 rows [n, 2] / [n, 6] or "kpts" for float32 keypoints [n, 4], offsets1, offsets2); raises ValueError."""
+    if model not in ("F", "H"):
+        raise ValueError("model should be 'F' or 'H'")
+    try:
+        r = float(ratio)
+    except (TypeError, ValueError):
+        raise ValueError("ratio should be a number")
+    if not np.isfinite(r) or r <= 0:
+        raise ValueError("ratio should be finite and > 0")
+    if len(d1_shape) != 2 or len(d2_shape) != 2 or d1_shape[1] != d2_shape[1] or d1_shape[1] == 0:
+        raise ValueError("descriptors should be [N1, dim] and [N2, dim] with the same dim")
+    t1, t2 = _dtype_name(d1_dtype), _dtype_name(d2_dtype)
+    if t1 != t2 or t1 not in ("float32", "uint8"):
+        raise ValueError("descriptors should both be float32 (L2) or both uint8 (Hamming)")
+    if norm is None:
+        norm = "hamming" if t1 == "uint8" else "l2"
+    if norm not in ("l2", "hamming"):
+        raise ValueError("norm should be 'l2' or 'hamming'")
+    if norm == "hamming" and t1 != "uint8":
+        raise ValueError("the Hamming norm needs uint8 descriptors")
+    if norm == "l2" and t1 != "float32":
+        raise ValueError("the L2 norm needs float32 descriptors")
+    kinds = []
+    for shp, dt in ((k1_shape, k1_dtype), (k2_shape, k2_dtype)):
+        name = _dtype_name(dt)
+        if len(shp) == 2 and name == "float64" and shp[1] in (2, 6):
+            kinds.append(("xy", shp[1]))
+        elif len(shp) == 2 and name == "float32" and shp[1] == 4:
+            kinds.append(("kpts", 4))
+        else:
+            raise ValueError("keypoints should be float64 [n, 2] / [n, 6] rows or float32 [n, 4] = (x, y, size, angle)")
+    if kinds[0] != kinds[1]:
+        raise ValueError("kps1 and kps2 should have the same layout")
+    if k1_shape[0] != d1_shape[0] or k2_shape[0] != d2_shape[0]:
+        raise ValueError("one keypoint row per descriptor row")
+    c1 = np.asarray(counts1); c2 = np.asarray(counts2)
+    if c1.ndim != 1 or c2.ndim != 1 or len(c1) != len(c2):
+        raise ValueError("counts1 and counts2 should be 1-D with one entry per pair")
+    if (c1.size and not np.issubdtype(c1.dtype, np.integer)) or (c2.size and not np.issubdtype(c2.dtype, np.integer)):
+        raise ValueError("counts should be integers")
+    if (c1 < 0).any() or (c2 < 0).any():
+        raise ValueError("counts should be >= 0")
+    o1 = np.zeros(len(c1) + 1, np.int64); np.cumsum(c1, out=o1[1:])
+    o2 = np.zeros(len(c2) + 1, np.int64); np.cumsum(c2, out=o2[1:])
+    if o1[-1] != d1_shape[0] or o2[-1] != d2_shape[0]:
+        raise ValueError("counts do not add up to the number of descriptor rows")
+    return (NORM_L2 if norm == "l2" else NORM_HAMMING), kinds[0][0], o1, o2
+
+
+def estimator_params(model, px_th=None, conf=None, max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
+                     enable_degeneracy_check=True):
+    """mi_degensac_params of findFundamentalMatrix / findHomography with their defaults where an argument is None"""
+    from .api import _error_type, error_type_dict_fundamental, error_type_dict_homography
+    d = _MODEL_DEFAULTS[model]
+    et = _error_type(error_type_dict_fundamental if model == "F" else error_type_dict_homography, error_type)
+    return _lib.make_params(d[0] if px_th is None else px_th, d[1] if conf is None else conf, d[2] if max_iters is None else max_iters, et,
+                            symmetric_error_check, max(0.0, laf_consistensy_coef), enable_degeneracy_check if model == "F" else True)
+
+
+def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
+                           max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
+                           enable_degeneracy_check=True, seeds=None, norm=None, device=0):
+    """K image pairs from descriptors and keypoints to models in one call: per pair the 2-NN ratio test of match_snn (optionally
+    mutual), then findFundamentalMatrix (model "F") or findHomography ("H") on its tentatives, all pairs in one launch.  kps are
+    float64 [n, 2] / [n, 6] rows or float32 [n, 4] keypoints (x, y, size, angle -> LAF rows as kpts_to_xyA); descriptors float32
+    (L2) or uint8 (Hamming; padded to whole 32-bit words here).  A pair with fewer than 8 (F) / 4 (H) tentatives gets a zero model
+    and no inliers.  seeds default to parallel.pair_seeds(0, K).  Returns (models [K, 3, 3], [match_p], [inlier_p]): match_p[i] =
+    the train row of query i or -1, inlier_p[i] = query i is a tentative and an inlier; H is the user-facing inv(H_c^T).
+    last_stats() holds the per-pair statistics, with "tentatives"."""
+    from . import api, parallel
+    K = len(desc1_list)
+    if not (len(kps1_list) == len(kps2_list) == len(desc2_list) == K):
+        raise ValueError("kps1_list, kps2_list, desc1_list and desc2_list should hold one entry per pair")
+    a = [np.asarray(x) for x in desc1_list]; b = [np.asarray(x) for x in desc2_list]
+    k1 = [np.asarray(x) for x in kps1_list]; k2 = [np.asarray(x) for x in kps2_list]
+    if K == 0:
+        raise ValueError("at least one pair")
+    for lst in (a, b, k1, k2):
+        if any(x.ndim != 2 or x.dtype != lst[0].dtype or x.shape[1] != lst[0].shape[1] for x in lst):
+            raise ValueError("every pair's arrays should be 2-D with the dtype and width of pair 0")
+    c1 = [x.shape[0] for x in a]; c2 = [x.shape[0] for x in b]
+    if [x.shape[0] for x in k1] != c1 or [x.shape[0] for x in k2] != c2:
+        raise ValueError("one keypoint row per descriptor row")
+    A = np.concatenate(a); B = np.concatenate(b); K1 = np.concatenate(k1); K2 = np.concatenate(k2)
+    code, kind, o1, o2 = check_match_verify_args(model, ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape, K2.dtype,
+                                                 np.asarray(c1, np.int64), np.asarray(c2, np.int64))
+    prm = estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
+    if code == NORM_HAMMING and A.shape[1] % 4:
+        pad = (-A.shape[1]) % 4
+        A = np.pad(A, ((0, 0), (0, pad))); B = np.pad(B, ((0, 0), (0, pad)))
+    A = np.ascontiguousarray(A); B = np.ascontiguousarray(B)
+    if kind == "kpts":
+        K1 = kpts_to_xyA(K1, device); K2 = kpts_to_xyA(K2, device)
+    K1 = np.ascontiguousarray(K1, np.float64); K2 = np.ascontiguousarray(K2, np.float64)
+    if seeds is None:
+        seeds = parallel.pair_seeds(0, K)
+    sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+    if sd.shape != (K,):
+        raise ValueError("one seed per pair")
+    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual)
+    n1 = A.shape[0]
+    M = np.zeros((K, 9)); match = np.full(n1, -1, np.int32); inl = np.zeros(n1, np.uint8)
+    st = np.zeros((K, 16), np.int32); cnt = np.zeros(K, np.int32)
+    rc = _lib.lib().mi_degensac_match_verify_batch(1 if model == "H" else 0, C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p),
+                                                   o1.ctypes.data_as(C.POINTER(C.c_int64)), o2.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                   _lib.dptr(K1), _lib.dptr(K2), K1.shape[1], K, C.byref(prm),
+                                                   sd.ctypes.data_as(C.POINTER(C.c_uint32)), int(device), _lib.dptr(M),
+                                                   match.ctypes.data_as(C.POINTER(C.c_int32)), inl.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                   st.ctypes.data_as(C.POINTER(C.c_int32)), cnt.ctypes.data_as(C.POINTER(C.c_int32)))
+    _lib.check(rc)
+    stats = [_lib.stats_dict(s) for s in st]
+    for d, c in zip(stats, cnt):
+        d["tentatives"] = int(c)
+    api._tls.stats = stats
+    M = M.reshape(K, 3, 3)
+    if model == "H":
+        out = np.zeros_like(M)
+        for i in range(K):
+            if np.abs(M[i]).sum() != 0:
+                out[i] = np.linalg.inv(M[i].T)
+        M = out
+    return M, [match[o1[p]:o1[p + 1]] for p in range(K)], [inl[o1[p]:o1[p + 1]].astype(bool) for p in range(K)]

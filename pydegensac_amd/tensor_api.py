@@ -152,3 +152,105 @@ def kpts_to_xyA_tensors(kpts):
         raise _lib.MiDegensacError(f"mi_degensac error {rc}: {_lib.lib().mi_degensac_match_last_error().decode()}")
     k.record_stream(stream)
     return out
+
+
+# ---- many image pairs: descriptors + keypoints -> tentatives -> F / H on the device (include/mi_degensac.h mi_degensac_match_*_batch*) ----
+def _word_aligned(t):
+    # the kernels read descriptor rows as 32-bit words: a contiguous view into a packed buffer may start at any byte
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() % 4 else t
+
+
+def _desc_pair(desc1, desc2):
+    import torch
+    if not (isinstance(desc1, torch.Tensor) and isinstance(desc2, torch.Tensor)) or desc1.device.type != "cuda" or desc2.device != desc1.device:
+        raise ValueError("descriptors must be torch tensors on the same ROCm device")
+    if desc1.dtype == torch.uint8 and desc1.shape[1] % 4:
+        raise ValueError("uint8 descriptors (Hamming) need dim % 4 == 0: pad with zero bytes")
+    return _word_aligned(desc1), _word_aligned(desc2)
+
+
+def knn_match_batch_tensors(desc1, desc2, counts1, counts2):
+    """knn_match_tensors for K image pairs in one launch: pair p's queries are the next counts1[p] rows of desc1, its train set the
+    next counts2[p] rows of desc2.  Returns (idx [N1, 2] int32 with indices LOCAL to the pair, dist [N1, 2] float32) on the device,
+    per pair bit-identical to knn_match_tensors on that pair; asynchronous on the current stream."""
+    import torch
+    from . import matcher
+    if not (isinstance(desc1, torch.Tensor) and isinstance(desc2, torch.Tensor)):
+        raise ValueError("descriptors must be torch tensors on a ROCm device")
+    code, _, o1, o2 = matcher.check_match_verify_args("F", 1.0, None, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
+                                                      (desc1.shape[0], 2), np.float64, (desc2.shape[0], 2), np.float64, counts1, counts2)
+    a, b = _desc_pair(desc1, desc2)
+    dev = a.device; n1 = a.shape[0]; K = len(o1) - 1
+    idx = torch.full((n1, 2), -1, dtype=torch.int32, device=dev)
+    dist = torch.full((n1, 2), float("inf"), dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    rc = _lib.lib().mi_degensac_match_knn2_batch_dev(code, a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                     o2.ctypes.data_as(C.POINTER(C.c_int64)), K, int(a.shape[1]), dev.index or 0,
+                                                     C.c_void_p(stream.cuda_stream), idx.data_ptr(), dist.data_ptr())
+    if rc != 0:
+        raise _lib.MiDegensacError(f"mi_degensac error {rc}: {_lib.lib().mi_degensac_match_last_error().decode()}")
+    for t in (a, b):
+        t.record_stream(stream)
+    return idx, dist
+
+
+def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
+                                   max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
+                                   enable_degeneracy_check=True, seeds=None):
+    """K image pairs from descriptors to models with ONE host synchronisation (the read of the per-pair tentative counts): per pair
+    the 2-NN ratio test (`m.distance < ratio * n.distance`, optionally mutual) of match_snn_tensors, then the estimator of
+    find_fundamental_batch_tensors (model "F") / find_homography_batch_tensors ("H") on its tentatives in query order.
+    kps: float64 [N, 2] / [N, 6] rows, or float32 [N, 4] keypoints (x, y, size, angle) that go through kpts_to_xyA_tensors;
+    descriptors float32 (L2) or uint8 with dim % 4 == 0 (Hamming).  Defaults are findFundamentalMatrix's / findHomography's; seeds
+    default to parallel.pair_seeds(0, K) and belong to the pair, whatever else is in the batch.  A pair with fewer than 8 (F) / 4 (H)
+    tentatives is not estimated: zero model, zero stats row, no inliers.
+    Returns (model [K, 3, 3] float64 — H as the user-facing inv(H_c^T), zeros where none was found —, match [N1] int32 = pair-local
+    train row or -1, inlier [N1] bool, stats [K, 16] int32, n_tentatives [K] numpy int64); all but the last on the device."""
+    import torch
+    from . import matcher, parallel
+    ts = (kps1, kps2, desc1, desc2)
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
+    code, kind, o1, o2 = matcher.check_match_verify_args(model, ratio, None, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
+                                                         tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype, counts1, counts2)
+    if any(t.device != desc1.device for t in ts):
+        raise ValueError("kps1, kps2, desc1 and desc2 must live on the same ROCm device")
+    prm = matcher.estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
+    a, b = _desc_pair(desc1, desc2)
+    dev = a.device; K = len(o1) - 1; n1 = a.shape[0]
+    if kind == "kpts":
+        k1 = kpts_to_xyA_tensors(kps1); k2 = kpts_to_xyA_tensors(kps2)
+    else:
+        k1 = kps1.contiguous(); k2 = kps2.contiguous()
+    if seeds is None:
+        seeds = parallel.pair_seeds(0, K)
+    seeds = np.asarray(seeds, dtype=np.int64).ravel()
+    if seeds.shape != (K,):
+        raise ValueError("one seed per pair")
+    # pinned + non_blocking: a pageable copy would wait for the stream (the call's one synchronisation is the count read)
+    d_seeds = torch.from_numpy((seeds & 0xFFFFFFFF).astype(np.uint32).view(np.int32)).pin_memory().to(dev, non_blocking=True)
+    M = torch.zeros((K, 9), dtype=torch.float64, device=dev)
+    match = torch.full((n1,), -1, dtype=torch.int32, device=dev)
+    inlier = torch.zeros(n1, dtype=torch.uint8, device=dev)
+    stats = torch.zeros((K, 16), dtype=torch.int32, device=dev)
+    cnt = np.zeros(K, np.int32)
+    mp = _lib.MatchParams(code, a.shape[1], ratio, mutual)
+    stream = torch.cuda.current_stream(dev)
+    rc = _lib.lib().mi_degensac_match_verify_batch_dev(1 if model == "H" else 0, C.byref(mp), a.data_ptr(), b.data_ptr(),
+                                                       o1.ctypes.data_as(C.POINTER(C.c_int64)), o2.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                       k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]), K, C.byref(prm), d_seeds.data_ptr(),
+                                                       dev.index or 0, C.c_void_p(stream.cuda_stream), M.data_ptr(), match.data_ptr(),
+                                                       inlier.data_ptr(), stats.data_ptr(), cnt.ctypes.data_as(C.POINTER(C.c_int32)))
+    _lib.check(rc)
+    # the estimator and the scatter read these asynchronously: keep them alive until the stream reaches this point
+    for t in (a, b, k1, k2, d_seeds):
+        t.record_stream(stream)
+    M = M.view(K, 3, 3)
+    if model == "H":
+        # inv(H_c^T) where a model was found, without a host round trip: short / failed pairs invert the identity and are zeroed
+        found = (M.abs().sum(dim=(1, 2)) != 0).view(K, 1, 1)
+        eye = torch.eye(3, dtype=M.dtype, device=dev).expand(K, 3, 3)
+        inv = torch.linalg.inv_ex(torch.where(found, M.transpose(1, 2), eye)).inverse      # inv_ex: no error check, no sync
+        M = torch.where(found, inv, torch.zeros_like(M))
+    return M, match, inlier.to(torch.bool), stats, cnt.astype(np.int64)

@@ -1,0 +1,222 @@
+"""GPU: batched match-and-verify (include/mi_degensac.h mi_degensac_match_knn2_batch_dev / mi_degensac_match_verify_batch[_dev]).
+Every stage equals its single-pair counterpart bit for bit: the batched 2-NN equals matcher.knn_match and the numpy oracle, the
+tentatives equal match_snn, and the models / masks / counters equal findFundamentalMatrixBatch / findHomographyBatch on those
+tentatives, whatever else is in the batch."""
+import numpy as np
+import pytest
+
+import pydegensac_amd as pd
+from oracle import matcher_np as mo
+from pydegensac_amd import matcher, parallel, synthetic as syn, tensor_api
+
+pytestmark = pytest.mark.gpu
+
+MI_ST_SAMPLES, MI_ST_LO_RUNS, MI_ST_I = 0, 1, 3
+
+
+def _descs(rng, n1, n2, dim, kind):
+    # copy of tests/test_matcher.py::_descs: true matches, exact duplicate train rows (ties)
+    if kind == "l2":
+        b = rng.normal(size=(n2, dim)).astype(np.float32)
+        a = rng.normal(size=(n1, dim)).astype(np.float32)
+        m = min(n1, n2) // 2
+        a[:m] = b[rng.permutation(n2)[:m]] + 0.05 * rng.normal(size=(m, dim)).astype(np.float32)
+        if n2 > 8:
+            b[5] = b[3]; b[7] = b[3]
+        return a, b
+    b = rng.integers(0, 256, size=(n2, dim), dtype=np.uint8)
+    a = rng.integers(0, 256, size=(n1, dim), dtype=np.uint8)
+    m = min(n1, n2) // 2
+    a[:m] = b[rng.permutation(n2)[:m]] ^ (rng.random((m, dim)) < 0.03).astype(np.uint8)
+    if n2 > 8:
+        b[5] = b[3]
+    return a, b
+
+
+def _dev():
+    import torch
+    return torch.device("cuda", 0)
+
+
+def _t(x):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(x)).to(_dev())
+
+
+def _ragged(kind, dim, sizes, seed):
+    rng = np.random.default_rng(seed)
+    D1, D2 = [], []
+    for n1, n2 in sizes:
+        a, b = _descs(rng, n1, n2, dim, kind)
+        if kind == "hamming":
+            _, a, b = matcher._prep(a, b, "hamming")                   # padded to whole 32-bit words
+        D1.append(a); D2.append(b)
+    return D1, D2
+
+
+def _sizes(rng, K, lo, hi):
+    s = [(0, 50), (40, 0), (70, 1), (1, 3), (130, 2), (64, 64), (65, 200)]
+    return s + [(int(a), int(b)) for a, b in zip(rng.integers(lo, hi, K - len(s)), rng.integers(lo, hi, K - len(s)))]
+
+
+@pytest.mark.parametrize("kind,dim", [("l2", 37), ("l2", 64), ("l2", 128), ("hamming", 32), ("hamming", 61)])
+@pytest.mark.parametrize("large", [False, True])
+def test_batched_knn2_equals_single_pair_and_oracle(kind, dim, large):
+    import torch
+    rng = np.random.default_rng(dim + 7 * large)
+    sizes = _sizes(rng, 40, 1000, 1400) if large else _sizes(rng, 40, 2, 300)
+    tiles = sum((n1 + 63) // 64 for n1, _ in sizes)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert (tiles >= 2 * cus) == large                                 # small: the train split is taken; large: it is not
+    D1, D2 = _ragged(kind, dim, sizes, seed=dim)
+    idx, dist = tensor_api.knn_match_batch_tensors(_t(np.concatenate(D1)), _t(np.concatenate(D2)), [s[0] for s in sizes], [s[1] for s in sizes])
+    idx = idx.cpu().numpy(); dist = dist.cpu().numpy()
+    o = 0
+    for p, (a, b) in enumerate(zip(D1, D2)):
+        n1 = a.shape[0]
+        si, sd = matcher.knn_match(a, b, kind)
+        assert np.array_equal(idx[o:o + n1], si), p
+        assert np.array_equal(dist[o:o + n1].view(np.uint32), sd.view(np.uint32)), p
+        if not large or p < 8:                                         # the numpy oracle is slow on the large pairs
+            ri, rd = mo.knn2(a, b, kind)
+            assert np.array_equal(idx[o:o + n1], ri) and np.array_equal(dist[o:o + n1], rd), p
+        o += n1
+
+
+def _f_batch(sizes, seed, dim=64):
+    """two-view pairs with descriptors as examples/simple_example_amd.py builds them; image 2 permuted"""
+    rng = np.random.default_rng(seed)
+    K1, K2, D1, D2 = [], [], [], []
+    for i, n in enumerate(sizes):
+        if n == 0:
+            K1.append(np.zeros((0, 2))); K2.append(np.zeros((0, 2)))
+            D1.append(np.zeros((0, dim), np.float32)); D2.append(np.zeros((0, dim), np.float32)); continue
+        p1, p2, lab, _ = syn.two_view_fundamental(max(n, 50), 0.5, 0.1, seed=seed * 1000 + i)
+        p1, p2, lab = p1[:n], p2[:n], lab[:n]
+        d1 = rng.normal(size=(n, dim)).astype(np.float32)
+        d2 = d1 + 0.15 * rng.normal(size=d1.shape).astype(np.float32)
+        d2[~lab] = rng.normal(size=((~lab).sum(), dim)).astype(np.float32)
+        perm = rng.permutation(n)
+        K1.append(p1); K2.append(p2[perm]); D1.append(d1); D2.append(d2[perm])
+    return K1, K2, D1, D2
+
+
+def _run_tensors(K1, K2, D1, D2, **kw):
+    c1 = [len(x) for x in D1]; c2 = [len(x) for x in D2]
+    M, match, inl, st, cnt = tensor_api.match_and_verify_batch_tensors(_t(np.concatenate(K1)), _t(np.concatenate(K2)), _t(np.concatenate(D1)),
+                                                                       _t(np.concatenate(D2)), c1, c2, **kw)
+    o = np.zeros(len(c1) + 1, np.int64); o[1:] = np.cumsum(c1)
+    match = match.cpu().numpy(); inl = inl.cpu().numpy()
+    return (M.cpu().numpy(), [match[o[p]:o[p + 1]] for p in range(len(c1))], [inl[o[p]:o[p + 1]] for p in range(len(c1))], st.cpu().numpy(), cnt)
+
+
+def _tentatives(K1, K2, match):
+    q = [np.flatnonzero(m >= 0) for m in match]
+    return [K1[p][q[p]] for p in range(len(q))], [K2[p][match[p][q[p]]] for p in range(len(q))], q
+
+
+@pytest.mark.parametrize("mutual", [False, True])
+def test_tentatives_equal_match_snn(mutual):
+    rng = np.random.default_rng(5 + mutual)
+    sizes = _sizes(rng, 24, 10, 900)
+    D1, D2 = _ragged("l2", 64, sizes, seed=3)
+    K1 = [rng.uniform(0, 500, (a.shape[0], 2)) for a in D1]; K2 = [rng.uniform(0, 500, (b.shape[0], 2)) for b in D2]
+    _, match, _, _, cnt = _run_tensors(K1, K2, D1, D2, model="H", ratio=0.9, mutual=mutual, max_iters=2000)
+    for p in range(len(sizes)):
+        q, t, _ = matcher.match_snn(D1[p], D2[p], 0.9, mutual, "l2")
+        assert np.array_equal(np.flatnonzero(match[p] >= 0), q) and np.array_equal(match[p][q], t), p
+        assert cnt[p] == len(q), p
+
+
+def test_fundamental_end_to_end_equals_composed_api(oracle_port):
+    rng = np.random.default_rng(11)
+    sizes = [int(n) for n in rng.integers(300, 2500, 46)] + [6, 0]
+    K1, K2, D1, D2 = _f_batch(sizes, seed=2)
+    K = len(sizes); seeds = parallel.pair_seeds(100, 100 + K)
+    M, match, inl, st, cnt = _run_tensors(K1, K2, D1, D2, model="F", seeds=seeds)
+    A, B, q = _tentatives(K1, K2, match)
+    assert list(cnt) == [len(x) for x in q]
+    elig = [p for p in range(K) if cnt[p] >= 8]
+    assert K - 2 <= len(elig) < K and cnt[K - 1] == 0 and cnt[K - 2] < 8
+    Fh, mh = pd.findFundamentalMatrixBatch([A[p] for p in elig], [B[p] for p in elig], seeds=[seeds[p] for p in elig])
+    sth = np.array([[s["samples"], s["lo_runs"], s["I"]] for s in pd.last_stats()])
+    for e, p in enumerate(elig):
+        assert np.array_equal(M[p], Fh[e]), p
+        assert np.array_equal(inl[p][q[p]], mh[e]) and not inl[p][match[p] < 0].any(), p
+        assert np.array_equal(st[p, [MI_ST_SAMPLES, MI_ST_LO_RUNS, MI_ST_I]], sth[e]), p
+    for p in set(range(K)) - set(elig):                                   # short pairs
+        assert not M[p].any() and not st[p].any() and not inl[p].any(), p
+    for p in sorted(elig, key=lambda p: cnt[p])[:3]:                      # ... and three pairs straight against the CPU oracle
+        Fo, mo_, so = oracle_port.find_fundamental(A[p], B[p], 0.5, 0.9999, 100000, seed=int(seeds[p]))
+        assert (int(st[p, 0]), int(st[p, 1])) == (so["samples"], so["lo_runs"]), p
+        assert np.array_equal(inl[p][q[p]], mo_), p
+        assert np.linalg.norm(M[p].ravel() - np.asarray(Fo).ravel()) <= 1e-9 * np.linalg.norm(Fo), p
+
+
+def test_homography_end_to_end_with_laf():
+    rng = np.random.default_rng(4)
+    sizes = [900, 300, 1500, 3, 700]
+    K4a, K4b, D1, D2 = [], [], [], []
+    for i, n in enumerate(sizes):
+        p1, p2, lab, _ = syn.homography_pairs(max(n, 20), 0.5, 0.5, seed=40 + i, laf=True)
+        p1, p2, lab = p1[:n], p2[:n], lab[:n]
+        ang2 = np.degrees(np.arctan2(p2[:, 3], p2[:, 2])); s2 = np.sqrt(np.abs(p2[:, 2] * p2[:, 5] - p2[:, 3] * p2[:, 4]))
+        K4a.append(np.c_[p1[:, :2], np.full(n, 5.0), np.zeros(n)].astype(np.float32))
+        K4b.append(np.c_[p2[:, :2], s2, ang2].astype(np.float32))
+        d1 = rng.normal(size=(n, 64)).astype(np.float32)
+        d2 = d1 + 0.15 * rng.normal(size=d1.shape).astype(np.float32); d2[~lab] = rng.normal(size=((~lab).sum(), 64)).astype(np.float32)
+        D1.append(d1); D2.append(d2)
+    X1 = [matcher.kpts_to_xyA(k) for k in K4a]; X2 = [matcher.kpts_to_xyA(k) for k in K4b]
+    seeds = [3, 5, 7, 9, 11]
+    kw = dict(model="H", px_th=2.0, conf=0.999, max_iters=20000, laf_consistensy_coef=3.0, error_type="symm_max", seeds=seeds)
+    r6 = _run_tensors(X1, X2, D1, D2, **kw)
+    r4 = _run_tensors(K4a, K4b, D1, D2, **kw)
+    cols = [MI_ST_SAMPLES, MI_ST_LO_RUNS, MI_ST_I]
+    assert np.array_equal(r6[0], r4[0]) and np.array_equal(r6[3][:, cols], r4[3][:, cols]) and np.array_equal(r6[4], r4[4])
+    assert all(np.array_equal(u, v) for u, v in zip(r6[1], r4[1])) and all(np.array_equal(u, v) for u, v in zip(r6[2], r4[2]))
+    M, match, inl, st, cnt = r6
+    A, B, q = _tentatives(X1, X2, match)
+    elig = [p for p in range(len(sizes)) if cnt[p] >= 4]
+    assert 3 not in elig and len(elig) == 4
+    Hh, mh = pd.findHomographyBatch([A[p] for p in elig], [B[p] for p in elig], 2.0, 0.999, 20000, 3.0, "symm_max", True,
+                                    seeds=[seeds[p] for p in elig])
+    sth = np.array([[s["samples"], s["lo_runs"], s["I"]] for s in pd.last_stats()])
+    for e, p in enumerate(elig):
+        assert np.array_equal(inl[p][q[p]], mh[e]), p
+        assert np.array_equal(st[p, [MI_ST_SAMPLES, MI_ST_LO_RUNS, MI_ST_I]], sth[e]), p
+        # inv() runs in numpy on the host path and in torch.linalg on the device path: same to rounding
+        assert np.linalg.norm(M[p] - Hh[e]) <= 1e-9 * max(np.linalg.norm(Hh[e]), 1e-300), p
+    assert not M[3].any() and not inl[3].any()
+
+
+def test_results_do_not_depend_on_batch_composition():
+    sizes = [800, 6, 1200, 0, 500, 7, 1500]
+    K1, K2, D1, D2 = _f_batch(sizes, seed=7)
+    seeds = parallel.pair_seeds(0, len(sizes))
+    full = _run_tensors(K1, K2, D1, D2, model="F", seeds=seeds)
+    keep = [0, 2, 4, 6]
+    part = _run_tensors([K1[p] for p in keep], [K2[p] for p in keep], [D1[p] for p in keep], [D2[p] for p in keep], model="F",
+                        seeds=[seeds[p] for p in keep])
+    cols = [MI_ST_SAMPLES, MI_ST_LO_RUNS, MI_ST_I]
+    for j, p in enumerate(keep):
+        alone = _run_tensors([K1[p]], [K2[p]], [D1[p]], [D2[p]], model="F", seeds=[seeds[p]])
+        for other, k in ((part, j), (alone, 0)):
+            assert np.array_equal(full[0][p], other[0][k]), p
+            assert np.array_equal(full[1][p], other[1][k]) and np.array_equal(full[2][p], other[2][k]), p
+            assert np.array_equal(full[3][p, cols], other[3][k, cols]) and full[4][p] == other[4][k], p
+    assert full[3][:, MI_ST_SAMPLES][keep].min() > 0
+
+
+def test_host_pointer_form_equals_tensor_form():
+    sizes = [600, 5, 1100, 0, 900]
+    K1, K2, D1, D2 = _f_batch(sizes, seed=9)
+    seeds = parallel.pair_seeds(0, len(sizes))
+    for mutual in (False, True):
+        M, match, inl, st, cnt = _run_tensors(K1, K2, D1, D2, model="F", mutual=mutual, seeds=seeds)
+        Mh, mh, ih = matcher.match_and_verify_batch(K1, K2, D1, D2, model="F", mutual=mutual, seeds=seeds)
+        sth = pd.last_stats()
+        assert np.array_equal(M, Mh)
+        for p in range(len(sizes)):
+            assert np.array_equal(match[p], mh[p]) and np.array_equal(inl[p], ih[p]), p
+            assert [sth[p][k] for k in ("samples", "lo_runs", "I")] == list(st[p, [MI_ST_SAMPLES, MI_ST_LO_RUNS, MI_ST_I]]), p
+            assert sth[p]["tentatives"] == cnt[p]
