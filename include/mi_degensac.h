@@ -393,6 +393,48 @@ int mi_degensac_match_verify_batch(int homography, const mi_degensac_match_param
                                    int n_pairs, const mi_degensac_params *prm, const uint32_t *seeds, int device,
                                    double *model, int32_t *match, uint8_t *inlier, int32_t *stats /*nullable*/, int32_t *counts /*nullable*/);
 
+/* ---- guided matching: the batched 2-NN restricted to each pair's model inlier band (mi_guided.hip) ------------------------
+ * Same ragged batch as mi_degensac_match_knn2_batch_dev (host offsets of K + 1 values, pair-local indices), plus keypoints
+ * kp1 / kp2 [rows, kp_dim] float64 (kp_dim 2 or 6; only x, y are read) and one model per pair, d_models [K*9] in the driver's form
+ * (what mi_degensac_match_verify_batch_dev and the *_batch_dev entry points write).  For pair p with model M_p:
+ *   gate(q, t) = r(M_p; x1_q, y1_q, x2_t, y2_t) <= th with the estimator's own residual and threshold for (homography, error_type,
+ *                px_th) — F: 0 Sampson, 1 symmetric epipolar, th = px_th^2; H: 0 Sampson, 1..4 the symmetric transfer errors, th =
+ *                px_th^2 (0, 1, 3) or px_th (2, 4) — in fp64 with the reference's operation order; `<=` as the reference's inlier
+ *                rule, a NaN residual fails, a model of nine zeros passes nothing.  The symmetric check and the LAF check of the
+ *                estimators are not part of the gate.
+ *   guided 2-NN = the two nearest train rows of the pair that pass the gate (the matcher's distances and (distance, index) order;
+ *                -1 / inf where fewer than two pass).
+ *   decision: a query gets match = idx[q][0] when at least one row passes and dist[q][0] < ratio * dist[q][1].  With exactly one
+ *                candidate dist[q][1] = inf and the query passes — unlike the unguided filter, which needs two train rows.  mutual:
+ *                the reverse guided 2-NN (the pair's train rows as queries against its query rows, the same gate(q, t)) must return q.
+ * Cost follows the rows that pass the gate (a screen without division first, the exact residual for the survivors, distances only
+ * for the candidates); a gate that passes everything is correct and slower than mi_degensac_match_knn2_batch_dev.
+ * Errors: MI_DEGENSAC_EINVAL for a bad norm / dim / kp_dim / error_type / offsets / ratio, a px_th that is negative or NaN, bad
+ * params; n_pairs == 0 returns 0. */
+typedef struct mi_degensac_guide_params {
+    int32_t homography;    /* 0 = fundamental matrix, 1 = homography                                                     */
+    int32_t error_type;    /* MI_DEGENSAC_F_* / MI_DEGENSAC_H_*                                                          */
+    double  px_th;         /* pixel threshold, >= 0; th derived as the estimators derive it                              */
+    int32_t struct_size;   /* sizeof(mi_degensac_guide_params) of the caller's header (0 = this layout)                  */
+    int32_t reserved;
+} mi_degensac_guide_params;
+/* the guided 2-NN alone: d_idx / d_dist [offsets1_host[K], 2]; asynchronous on `stream`, no host synchronisation */
+int mi_degensac_match_guided_knn2_batch_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
+                                            const int64_t *offsets2_host, int n_pairs, int dim, const double *d_kp1, const double *d_kp2,
+                                            int kp_dim, const double *d_models, const mi_degensac_guide_params *gp, int device, void *stream,
+                                            int32_t *d_idx, float *d_dist);
+/* the guided 2-NN + the decision (mp: norm, dim, ratio, mutual): d_idx / d_dist as above, d_match [rows] = pair-local train row or -1,
+ * d_counts [K] (nullable) guided matches per pair on the device.  Asynchronous; it synchronises (once) only when h_counts is given. */
+int mi_degensac_match_guided_batch_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
+                                       const int64_t *offsets2_host, const double *d_kp1, const double *d_kp2, int kp_dim, int n_pairs,
+                                       const double *d_models, const mi_degensac_guide_params *gp, int device, void *stream, int32_t *d_idx,
+                                       float *d_dist, int32_t *d_match, int32_t *d_counts /*nullable*/, int32_t *h_counts /*nullable*/);
+/* the same on host pointers (blocking) */
+int mi_degensac_match_guided_batch(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
+                                   const int64_t *offsets2, const double *kp1, const double *kp2, int kp_dim, int n_pairs, const double *models,
+                                   const mi_degensac_guide_params *gp, int device, int32_t *idx, float *dist, int32_t *match,
+                                   int32_t *counts /*nullable*/);
+
 /* ---- unit-level device entry points (parity tests of the kernels' building blocks) ------------ */
 /* score n_models fundamental (kind 0: Sampson, 1: symmetric epipolar) or homography (kind 10..14:
  * H Sampson, symm_sq_max, symm_max, symm_sq_sum, symm_sum) models against all n points: I (<= th)

@@ -62,6 +62,14 @@ class MatchParams(C.Structure):
         super().__init__(int(norm), int(dim), float(ratio), int(bool(mutual)), C.sizeof(MatchParams), 0)
 
 
+class GuideParams(C.Structure):
+    """mi_degensac_guide_params (include/mi_degensac.h): the gate of the guided-matching entry points"""
+    _fields_ = [("homography", C.c_int32), ("error_type", C.c_int32), ("px_th", C.c_double), ("struct_size", C.c_int32), ("reserved", C.c_int32)]
+
+    def __init__(self, homography=0, error_type=0, px_th=0.5):
+        super().__init__(int(bool(homography)), int(error_type), float(px_th), C.sizeof(GuideParams), 0)
+
+
 class MiDegensacError(RuntimeError):
     pass
 
@@ -174,6 +182,16 @@ def lib():
         l.mi_degensac_match_verify_batch.restype = C.c_int
         l.mi_degensac_match_verify_batch.argtypes = [C.c_int, mpp, C.c_void_p, C.c_void_p, lp, lp, dp, dp, C.c_int, C.c_int, pp, up, C.c_int,
                                                      dp, ip, bp, ip, ip]
+        gpp = C.POINTER(GuideParams)
+        l.mi_degensac_match_guided_knn2_batch_dev.restype = C.c_int
+        l.mi_degensac_match_guided_knn2_batch_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, lp, lp, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                              C.c_void_p, gpp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.mi_degensac_match_guided_batch_dev.restype = C.c_int
+        l.mi_degensac_match_guided_batch_dev.argtypes = [mpp, C.c_void_p, C.c_void_p, lp, lp, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, gpp,
+                                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, ip]
+        l.mi_degensac_match_guided_batch.restype = C.c_int
+        l.mi_degensac_match_guided_batch.argtypes = [mpp, C.c_void_p, C.c_void_p, lp, lp, dp, dp, C.c_int, C.c_int, dp, gpp, C.c_int, ip,
+                                                     C.POINTER(C.c_float), ip, ip]
         l.mi_degensac_kpts_to_xyA.restype = C.c_int
         l.mi_degensac_kpts_to_xyA.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, dp]
         l.mi_degensac_kpts_to_xyA_dev.restype = C.c_int
@@ -205,6 +223,15 @@ def check(rc):
         msg = lib().mi_degensac_last_error().decode()
         if rc == -1:
             raise ValueError(msg)          # std::invalid_argument -> ValueError in the reference binding
+        raise MiDegensacError(f"mi_degensac error {rc}: {msg}")
+
+
+def check_match(rc):
+    """check() for the matcher-stage entry points, whose message is mi_degensac_match_last_error()"""
+    if rc != 0:
+        msg = lib().mi_degensac_match_last_error().decode()
+        if rc == -1:
+            raise ValueError(msg)
         raise MiDegensacError(f"mi_degensac error {rc}: {msg}")
 
 

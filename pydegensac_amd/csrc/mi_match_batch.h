@@ -11,6 +11,21 @@
 
 #define MT_HIDDEN __attribute__((visibility("hidden")))
 
+/* a running top-2 of (distance, train index) candidates, shared by the dense matcher and the guided stage (mi_guided.hip) */
+struct mt_best { float d0, d1; int i0, i1; };     /* (d0, i0) <= (d1, i1) lexicographically */
+
+/* candidate (d, i) into a running top-2; equal distances keep the lower index first */
+__device__ __forceinline__ void mt_push(mt_best &b, float d, int i)
+{
+    const bool lt0 = d < b.d0 || (d == b.d0 && i < b.i0);
+    const bool lt1 = d < b.d1 || (d == b.d1 && i < b.i1);
+    if (lt0) { b.d1 = b.d0; b.i1 = b.i0; b.d0 = d; b.i0 = i; }
+    else if (lt1) { b.d1 = d; b.i1 = i; }
+}
+
+/* the message mi_degensac_match_last_error() returns for the calling thread */
+MT_HIDDEN void mt_set_error(const char *msg);
+
 /* host -> device copy of `bytes` through a pinned staging block: asynchronous, the host block may be reused at once */
 MT_HIDDEN int mt_batch_upload(int device, hipStream_t s, const void *h, size_t bytes, void *d);
 /* batched 2-NN: every row of pair p in q (rows oq[p] .. oq[p+1]) against the rows ot[p] .. ot[p+1] of t; idx / dist [oq[K], 2],
@@ -31,4 +46,20 @@ MT_HIDDEN int mt_batch_gather(int n_eligible, const int32_t *d_pair_of_e, const 
 MT_HIDDEN int mt_batch_scatter(int n_pairs, const int32_t *d_e_of_p, const int64_t *d_est_off, const int32_t *d_off1, const uint8_t *d_keep,
                                const int32_t *d_rank, const int32_t *d_idx, const double *d_model_e, const int32_t *d_stats_e, const uint8_t *d_mask_e,
                                hipStream_t s, double *d_model, int32_t *d_stats /*nullable*/, int32_t *d_match, uint8_t *d_inlier);
+
+/* ---- guided matching (mi_guided.hip) ---- */
+/* the gate of a model kind: th from px_th / error_type as fill_params derives it; EINVAL (message set) for a bad error_type or a
+ * px_th that is negative or NaN */
+struct mt_gate { int gk, hk; double th, tb; int screen; };
+MT_HIDDEN int mt_guided_gate(int homography, int error_type, double px_th, mt_gate *g);
+/* guided 2-NN: every row of pair p in q against the rows of t that pass the gate of model d_models[9 p ..]; same layout and index
+ * convention as mt_batch_knn2.  kq / kt: keypoint rows [rows, kd] of the two sides.  swap = 0: q is side 1 (queries), gate(q, t);
+ * swap = 1: q is side 2 (the reverse search of the mutual check), gate(t, q). */
+MT_HIDDEN int mt_batch_guided_knn2(int norm, int words, const void *dq, const void *dt, const double *kq, const double *kt, int kd, const int64_t *oq,
+                                   const int64_t *ot, int n_pairs, const double *d_models, const mt_gate &g, int swap, int device, hipStream_t s,
+                                   int32_t *idx, float *dist);
+/* the decision: match[i] = idx[i][0] when it exists and dist[i][0] < ratio * dist[i][1] (and back[b2 + idx[i][0]][0] == i - lo when
+ * d_back is set), else -1; count[p] (nullable) = guided matches of pair p.  d_off1 / d_off2: [K + 1] relative int32 row offsets */
+MT_HIDDEN int mt_batch_guided_decide(const int32_t *d_idx, const float *d_dist, const int32_t *d_off1, const int32_t *d_off2, int n_pairs, float ratio,
+                                     const int32_t *d_back, hipStream_t s, int32_t *d_match, int32_t *d_count);
 #endif /* MI_MATCH_BATCH_H */

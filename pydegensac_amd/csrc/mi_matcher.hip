@@ -27,16 +27,7 @@
 #define MT_T   64            /* train rows per LDS tile */
 #define MT_DC  64            /* descriptor words per LDS chunk */
 
-struct mt_best { float d0, d1; int i0, i1; };     /* (d0, i0) <= (d1, i1) lexicographically */
-
-/* candidate (d, i) into a running top-2; equal distances keep the lower index first */
-__device__ __forceinline__ void mt_push(mt_best &b, float d, int i)
-{
-    const bool lt0 = d < b.d0 || (d == b.d0 && i < b.i0);
-    const bool lt1 = d < b.d1 || (d == b.d1 && i < b.i1);
-    if (lt0) { b.d1 = b.d0; b.i1 = b.i0; b.d0 = d; b.i0 = i; }
-    else if (lt1) { b.d1 = d; b.i1 = i; }
-}
+/* mt_best / mt_push (the running top-2 and its tie rule): mi_match_batch.h */
 
 /* One workgroup's tile: queries q0 .. q_end - 1 (at most 64) of q against train rows t_lo .. t_hi - 1 of t, candidates
  * indexed from t_base (0 for a single pair, the pair's first train row in a batch).  NORM: 0 = L2 over float words,
@@ -248,6 +239,7 @@ __global__ __launch_bounds__(256) void mt_scatter_kernel(const int32_t *e_of_p, 
 
 static thread_local char mt_err[256] = "";
 extern "C" const char *mi_degensac_match_last_error(void) { return mt_err; }
+void mt_set_error(const char *msg) { snprintf(mt_err, sizeof mt_err, "%s", msg); }
 #define MTCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { snprintf(mt_err, sizeof mt_err, "%s failed: %s", #x, hipGetErrorString(e_)); \
     (void)hipGetLastError(); return MI_DEGENSAC_EHIP; } } while (0)
 

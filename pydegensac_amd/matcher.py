@@ -155,15 +155,127 @@ def estimator_params(model, px_th=None, conf=None, max_iters=None, laf_consisten
                             symmetric_error_check, max(0.0, laf_consistensy_coef), enable_degeneracy_check if model == "F" else True)
 
 
+def check_guided_args(model, px_th, error_type, models_shape, models_dtype, K):
+    """The guided stage's own argument checks, after check_match_verify_args (shapes and dtype names only, numpy or torch): models
+    float64 [K, 3, 3], px_th >= 0 (None = the model's default), error_type one of the model's names.  Returns (px_th, error_type code);
+    raises ValueError."""
+    from .api import _error_type, error_type_dict_fundamental, error_type_dict_homography
+    if model not in ("F", "H"):
+        raise ValueError("model should be 'F' or 'H'")
+    if tuple(models_shape) != (K, 3, 3):
+        raise ValueError(f"models should be [K, 3, 3] = [{K}, 3, 3], one model per pair")
+    if _dtype_name(models_dtype) != "float64":
+        raise ValueError("models should be float64")
+    px = _MODEL_DEFAULTS[model][0] if px_th is None else px_th
+    try:
+        px = float(px)
+    except (TypeError, ValueError):
+        raise ValueError("px_th should be a number")
+    if not px >= 0:
+        raise ValueError("px_th should be >= 0 (and not NaN)")
+    et = _error_type(error_type_dict_fundamental if model == "F" else error_type_dict_homography, error_type)
+    return px, et
+
+
+def _h_driver_form(M):
+    """user-facing H -> the driver's form H_c = inv(H)^T (utils.py:108 inverted); zero models stay zero"""
+    out = np.zeros_like(M)
+    for i in range(M.shape[0]):
+        if np.abs(M[i]).sum() != 0:
+            out[i] = np.linalg.inv(M[i]).T
+    return out
+
+
+def _stack_pairs(kps1_list, kps2_list, desc1_list, desc2_list, model, ratio, norm, device):
+    """the per-pair lists of the batched calls -> (norm code, A, B, K1, K2, offsets1, offsets2): descriptors padded to whole 32-bit
+    words for Hamming, keypoints as float64 [n, 2] / [n, 6] rows"""
+    K = len(desc1_list)
+    if not (len(kps1_list) == len(kps2_list) == len(desc2_list) == K):
+        raise ValueError("kps1_list, kps2_list, desc1_list and desc2_list should hold one entry per pair")
+    a = [np.asarray(x) for x in desc1_list]; b = [np.asarray(x) for x in desc2_list]
+    k1 = [np.asarray(x) for x in kps1_list]; k2 = [np.asarray(x) for x in kps2_list]
+    if K == 0:
+        raise ValueError("at least one pair")
+    for lst in (a, b, k1, k2):
+        if any(x.ndim != 2 or x.dtype != lst[0].dtype or x.shape[1] != lst[0].shape[1] for x in lst):
+            raise ValueError("every pair's arrays should be 2-D with the dtype and width of pair 0")
+    c1 = [x.shape[0] for x in a]; c2 = [x.shape[0] for x in b]
+    if [x.shape[0] for x in k1] != c1 or [x.shape[0] for x in k2] != c2:
+        raise ValueError("one keypoint row per descriptor row")
+    A = np.concatenate(a); B = np.concatenate(b); K1 = np.concatenate(k1); K2 = np.concatenate(k2)
+    code, kind, o1, o2 = check_match_verify_args(model, ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape, K2.dtype,
+                                                 np.asarray(c1, np.int64), np.asarray(c2, np.int64))
+    return code, kind, A, B, K1, K2, o1, o2
+
+
+def _finish_pairs(code, kind, A, B, K1, K2, device):
+    if code == NORM_HAMMING and A.shape[1] % 4:
+        pad = (-A.shape[1]) % 4
+        A = np.pad(A, ((0, 0), (0, pad))); B = np.pad(B, ((0, 0), (0, pad)))
+    A = np.ascontiguousarray(A); B = np.ascontiguousarray(B)
+    if kind == "kpts":
+        K1 = kpts_to_xyA(K1, device); K2 = kpts_to_xyA(K2, device)
+    return A, B, np.ascontiguousarray(K1, np.float64), np.ascontiguousarray(K2, np.float64)
+
+
+def _guided_host(code, A, B, K1, K2, o1, o2, Md, model, ratio, mutual, px, et, device):
+    """mi_degensac_match_guided_batch on prepared host arrays; Md = [K, 9] driver-form models.  Returns (match, idx, dist, counts)."""
+    K = len(o1) - 1; n1 = A.shape[0]
+    idx = np.full((n1, 2), -1, np.int32); dist = np.full((n1, 2), np.inf, np.float32); match = np.full(n1, -1, np.int32)
+    cnt = np.zeros(K, np.int32)
+    Md = np.ascontiguousarray(Md, np.float64).reshape(K, 9)
+    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual); gp = _lib.GuideParams(model == "H", et, px)
+    rc = _lib.lib().mi_degensac_match_guided_batch(C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p),
+                                                   o1.ctypes.data_as(C.POINTER(C.c_int64)), o2.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                   _lib.dptr(K1), _lib.dptr(K2), K1.shape[1], K, _lib.dptr(Md), C.byref(gp), int(device),
+                                                   idx.ctypes.data_as(C.POINTER(C.c_int32)), dist.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   match.ctypes.data_as(C.POINTER(C.c_int32)), cnt.ctypes.data_as(C.POINTER(C.c_int32)))
+    _lib.check_match(rc)
+    return match, idx, dist, cnt
+
+
+def guided_match_batch(kps1_list, kps2_list, desc1_list, desc2_list, models, model="F", ratio=0.9, mutual=False, px_th=None,
+                       error_type="sampson", norm=None, driver_form=False, device=0):
+    """Guided matching of K image pairs in one call: per pair the 2-NN search restricted to the train keypoints that are inliers of
+    the pair's model (models [K, 3, 3] float64: F, or the user-facing H that findHomography returns; driver_form=True takes them in the
+    driver's form, H_c = inv(H)^T), with the estimator's residual for error_type and its threshold from px_th (None = the model's
+    default, 0.5 for F, 1.0 for H).  The ratio test then keeps a query whose nearest gated row is closer than ratio times the second;
+    a query with a single gated row passes (nothing competes with it).  A zero model gives its pair no matches.  Arrays as for
+    match_and_verify_batch.  Returns per pair (query indices, train indices, distances) in query order, like match_snn.
+    A gate that lets everything through (a huge px_th) is correct but slower than the unguided matcher."""
+    code, kind, A, B, K1, K2, o1, o2 = _stack_pairs(kps1_list, kps2_list, desc1_list, desc2_list, model, ratio, norm, device)
+    K = len(o1) - 1
+    M = np.asarray(models)
+    px, et = check_guided_args(model, px_th, error_type, M.shape, M.dtype, K)
+    A, B, K1, K2 = _finish_pairs(code, kind, A, B, K1, K2, device)
+    Md = M if (model == "F" or driver_form) else _h_driver_form(M)
+    match, _, dist, _ = _guided_host(code, A, B, K1, K2, o1, o2, Md, model, ratio, mutual, px, et, device)
+    out = []
+    for p in range(K):
+        m = match[o1[p]:o1[p + 1]]
+        q = np.flatnonzero(m >= 0)
+        out.append((q.astype(np.int64), m[q].astype(np.int64), dist[o1[p]:o1[p + 1]][q, 0]))
+    return out
+
+
+def guided_match(kps1, kps2, desc1, desc2, M, model="F", ratio=0.9, mutual=False, px_th=None, error_type="sampson", norm=None,
+                 driver_form=False, device=0):
+    """guided_match_batch for one pair: (query indices, train indices, distances) of the guided matches under model M [3, 3]"""
+    return guided_match_batch([kps1], [kps2], [desc1], [desc2], np.asarray(M)[None], model, ratio, mutual, px_th, error_type, norm,
+                              driver_form, device)[0]
+
+
 def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
                            max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
-                           enable_degeneracy_check=True, seeds=None, norm=None, device=0):
+                           enable_degeneracy_check=True, seeds=None, norm=None, device=0, guided=False):
     """K image pairs from descriptors and keypoints to models in one call: per pair the 2-NN ratio test of match_snn (optionally
     mutual), then findFundamentalMatrix (model "F") or findHomography ("H") on its tentatives, all pairs in one launch.  kps are
     float64 [n, 2] / [n, 6] rows or float32 [n, 4] keypoints (x, y, size, angle -> LAF rows as kpts_to_xyA); descriptors float32
     (L2) or uint8 (Hamming; padded to whole 32-bit words here).  A pair with fewer than 8 (F) / 4 (H) tentatives gets a zero model
     and no inliers.  seeds default to parallel.pair_seeds(0, K).  Returns (models [K, 3, 3], [match_p], [inlier_p]): match_p[i] =
     the train row of query i or -1, inlier_p[i] = query i is a tentative and an inlier; H is the user-facing inv(H_c^T).
+    guided=True runs guided_match_batch after the estimator with the driver-form models it returned (no conversion), this call's
+    px_th / error_type / ratio / mutual, and adds a fourth element [guided_p]: the guided match of every query or -1.
     last_stats() holds the per-pair statistics, with "tentatives"."""
     from . import api, parallel
     K = len(desc1_list)
@@ -210,6 +322,9 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
     for d, c in zip(stats, cnt):
         d["tentatives"] = int(c)
     api._tls.stats = stats
+    gm = None
+    if guided:                  # the driver-form models as the library wrote them, before the inversion below
+        gm = _guided_host(code, A, B, K1, K2, o1, o2, M, model, ratio, mutual, prm.px_th, prm.error_type, device)[0]
     M = M.reshape(K, 3, 3)
     if model == "H":
         out = np.zeros_like(M)
@@ -217,4 +332,5 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
             if np.abs(M[i]).sum() != 0:
                 out[i] = np.linalg.inv(M[i].T)
         M = out
-    return M, [match[o1[p]:o1[p + 1]] for p in range(K)], [inl[o1[p]:o1[p + 1]].astype(bool) for p in range(K)]
+    res = (M, [match[o1[p]:o1[p + 1]] for p in range(K)], [inl[o1[p]:o1[p + 1]].astype(bool) for p in range(K)])
+    return res + ([gm[o1[p]:o1[p + 1]] for p in range(K)],) if guided else res

@@ -195,9 +195,65 @@ def knn_match_batch_tensors(desc1, desc2, counts1, counts2):
     return idx, dist
 
 
+def _guided_dev(code, a, b, k1, k2, o1, o2, Md, model, ratio, mutual, px, et):
+    """mi_degensac_match_guided_batch_dev on prepared device tensors (Md: [K, 9] driver-form models), asynchronous on the current
+    stream.  Returns (match [N1] int32, idx [N1, 2] int32, dist [N1, 2] float32)."""
+    import torch
+    dev = a.device; n1 = a.shape[0]; K = len(o1) - 1
+    idx = torch.full((n1, 2), -1, dtype=torch.int32, device=dev)
+    dist = torch.full((n1, 2), float("inf"), dtype=torch.float32, device=dev)
+    match = torch.full((n1,), -1, dtype=torch.int32, device=dev)
+    mp = _lib.MatchParams(code, a.shape[1], ratio, mutual); gp = _lib.GuideParams(model == "H", et, px)
+    stream = torch.cuda.current_stream(dev)
+    rc = _lib.lib().mi_degensac_match_guided_batch_dev(C.byref(mp), a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                       o2.ctypes.data_as(C.POINTER(C.c_int64)), k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]), K,
+                                                       Md.data_ptr(), C.byref(gp), dev.index or 0, C.c_void_p(stream.cuda_stream), idx.data_ptr(),
+                                                       dist.data_ptr(), match.data_ptr(), None, None)
+    _lib.check_match(rc)
+    for t in (a, b, k1, k2, Md):
+        t.record_stream(stream)
+    return match, idx, dist
+
+
+def guided_match_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, models, model="F", ratio=0.9, mutual=False, px_th=None,
+                               error_type="sampson", norm=None, driver_form=False):
+    """Guided matching on the device (include/mi_degensac.h mi_degensac_match_guided_batch_dev): per pair the 2-NN search of
+    knn_match_batch_tensors restricted to the train keypoints that are inliers of the pair's model under the estimator's own residual
+    for error_type and its threshold from px_th (None = the model's default: 0.5 for F, 1.0 for H), then the ratio test (and, with
+    mutual, the reverse guided search).  A query with a single gated train row passes the ratio test (nothing competes with it); a
+    zero model gives its pair no matches.  models: [K, 3, 3] float64 on the device — F, or the user-facing H (converted here to the
+    driver's form H_c = inv(H)^T without a host round trip); driver_form=True takes them as the *_batch_dev entry points write them.
+    Keypoints and descriptors as for match_and_verify_batch_tensors.  Cost follows the rows that pass the gate; a gate that passes
+    everything (a huge px_th) is correct but slower than the unguided matcher.  Returns (match [N1] int32 = pair-local train row or -1,
+    idx [N1, 2] int32, dist [N1, 2] float32) on the device, asynchronous on the current stream (no host synchronisation)."""
+    import torch
+    from . import matcher
+    ts = (kps1, kps2, desc1, desc2, models)
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        raise ValueError("kps1, kps2, desc1, desc2 and models must be torch tensors on a ROCm device")
+    code, kind, o1, o2 = matcher.check_match_verify_args(model, ratio, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
+                                                         tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype, counts1, counts2)
+    K = len(o1) - 1
+    px, et = matcher.check_guided_args(model, px_th, error_type, tuple(models.shape), models.dtype, K)
+    if any(t.device != desc1.device for t in ts) or desc1.device.type != "cuda":
+        raise ValueError("kps1, kps2, desc1, desc2 and models must live on the same ROCm device")
+    a, b = _desc_pair(desc1, desc2)
+    if kind == "kpts":
+        k1 = kpts_to_xyA_tensors(kps1); k2 = kpts_to_xyA_tensors(kps2)
+    else:
+        k1 = kps1.contiguous(); k2 = kps2.contiguous()
+    M = models.contiguous()
+    if model == "H" and not driver_form:
+        # H_c = inv(H)^T where the model is not zero, without a host round trip (inv_ex: no error check, no sync)
+        found = (M.abs().sum(dim=(1, 2)) != 0).view(K, 1, 1)
+        eye = torch.eye(3, dtype=M.dtype, device=M.device).expand(K, 3, 3)
+        M = torch.where(found, torch.linalg.inv_ex(torch.where(found, M, eye)).inverse.transpose(1, 2), torch.zeros_like(M))
+    return _guided_dev(code, a, b, k1, k2, o1, o2, M.reshape(K, 9).contiguous(), model, ratio, mutual, px, et)
+
+
 def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
                                    max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
-                                   enable_degeneracy_check=True, seeds=None):
+                                   enable_degeneracy_check=True, seeds=None, guided=False):
     """K image pairs from descriptors to models with ONE host synchronisation (the read of the per-pair tentative counts): per pair
     the 2-NN ratio test (`m.distance < ratio * n.distance`, optionally mutual) of match_snn_tensors, then the estimator of
     find_fundamental_batch_tensors (model "F") / find_homography_batch_tensors ("H") on its tentatives in query order.
@@ -206,7 +262,10 @@ def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, m
     default to parallel.pair_seeds(0, K) and belong to the pair, whatever else is in the batch.  A pair with fewer than 8 (F) / 4 (H)
     tentatives is not estimated: zero model, zero stats row, no inliers.
     Returns (model [K, 3, 3] float64 — H as the user-facing inv(H_c^T), zeros where none was found —, match [N1] int32 = pair-local
-    train row or -1, inlier [N1] bool, stats [K, 16] int32, n_tentatives [K] numpy int64); all but the last on the device."""
+    train row or -1, inlier [N1] bool, stats [K, 16] int32, n_tentatives [K] numpy int64); all but the last on the device.
+    guided=True then runs guided_match_batch_tensors on the same stream with the estimator's driver-form models straight from device
+    memory (no conversion) and this call's px_th / error_type / ratio / mutual, and appends its match [N1] int32 (the guided match of
+    every query or -1); the call still synchronises exactly once."""
     import torch
     from . import matcher, parallel
     ts = (kps1, kps2, desc1, desc2)
@@ -246,6 +305,7 @@ def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, m
     # the estimator and the scatter read these asynchronously: keep them alive until the stream reaches this point
     for t in (a, b, k1, k2, d_seeds):
         t.record_stream(stream)
+    gm = _guided_dev(code, a, b, k1, k2, o1, o2, M, model, ratio, mutual, prm.px_th, prm.error_type)[0] if guided else None
     M = M.view(K, 3, 3)
     if model == "H":
         # inv(H_c^T) where a model was found, without a host round trip: short / failed pairs invert the identity and are zeroed
@@ -253,4 +313,5 @@ def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, m
         eye = torch.eye(3, dtype=M.dtype, device=dev).expand(K, 3, 3)
         inv = torch.linalg.inv_ex(torch.where(found, M.transpose(1, 2), eye)).inverse      # inv_ex: no error check, no sync
         M = torch.where(found, inv, torch.zeros_like(M))
-    return M, match, inlier.to(torch.bool), stats, cnt.astype(np.int64)
+    res = (M, match, inlier.to(torch.bool), stats, cnt.astype(np.int64))
+    return res + (gm,) if guided else res
