@@ -337,6 +337,12 @@ int mi_degensac_find_fundamental_hist(const double *pts1, const double *pts2, in
 #define MI_DEGENSAC_NORM_HAMMING  1
 int mi_degensac_match(int norm, const void *desc1, int n1, const void *desc2, int n2, int dim, float ratio, int mutual,
                       int device, int32_t *idx /*[n1,2]*/, float *dist /*[n1,2]*/, uint8_t *keep /*[n1], nullable*/);
+/* Non-finite distances (L2 only; a Hamming distance is always finite): a train row whose distance to the query is NaN or +inf —
+ * NaN or +-inf in either descriptor row, or finite rows whose fp32 sum of squares overflows — is NOT a neighbour.  It takes no
+ * slot of idx; a query left with fewer than two finite distances gets idx = -1 / dist = inf in the free slots, exactly as with
+ * fewer than two train rows, and such a slot never passes the ratio test or the mutual check.  The same rule holds in
+ * mi_degensac_match_knn2_batch_dev and, for the rows that pass the gate, in the guided entry points; oracle/matcher_np.py
+ * (top2) states it for the tests. */
 /* device pointers, asynchronous on `stream` */
 int mi_degensac_match_knn2_dev(int norm, const void *d_desc1, int n1, const void *d_desc2, int n2, int dim, int device,
                                void *stream, int32_t *d_idx, float *d_dist);

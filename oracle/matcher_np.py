@@ -20,14 +20,29 @@ def dist_matrix(desc1, desc2, norm="l2"):
     return np.unpackbits(x, axis=2).sum(axis=2).astype(np.float32)
 
 
-def knn2(desc1, desc2, norm="l2"):
-    D = dist_matrix(desc1, desc2, norm)
+def top2(D, ok=None):
+    """The two smallest entries of every row of D in (distance, index) order, among the columns where ok (bool, optional) holds.
+    The non-finite rule of include/mi_degensac.h: a train row whose distance to the query is NaN or +inf (NaN / inf in a descriptor
+    row, or an fp32 overflow of the squared sum) is not a neighbour — it takes no slot, and a query with fewer than two finite
+    candidates gets idx = -1 / dist = inf, exactly as with fewer than two train rows."""
     n1, n2 = D.shape
     idx = np.full((n1, 2), -1, np.int32); dist = np.full((n1, 2), np.inf, np.float32)
-    order = np.argsort(D, axis=1, kind="stable")[:, :2]          # stable: the lower index wins a tie
-    for k in range(min(2, n2)):
-        idx[:, k] = order[:, k]; dist[:, k] = D[np.arange(n1), order[:, k]]
+    if n2 == 0:
+        return idx, dist
+    fin = np.isfinite(D) if ok is None else (np.isfinite(D) & ok)
+    Dm = np.where(fin, D, np.float32(np.inf))
+    order = np.argsort(Dm, axis=1, kind="stable")[:, :2]         # stable: the lower index wins a tie
+    r = np.arange(n1)
+    for k in range(order.shape[1]):
+        is_nb = fin[r, order[:, k]]
+        idx[:, k] = np.where(is_nb, order[:, k], -1); dist[:, k] = np.where(is_nb, Dm[r, order[:, k]], np.inf)
     return idx, dist
+
+
+def knn2(desc1, desc2, norm="l2"):
+    with np.errstate(invalid="ignore", over="ignore"):
+        D = dist_matrix(desc1, desc2, norm)
+    return top2(D)
 
 
 def match_snn(desc1, desc2, ratio=0.9, mutual=False, norm="l2"):

@@ -1,5 +1,5 @@
 """GPU: guided matching (include/mi_degensac.h mi_degensac_match_guided_*; tensor_api.guided_match_batch_tensors,
-matcher.guided_match_batch, the guided=True stage of the batched match-and-verify calls).  The guided restatement below forms every
+matcher.guided_match_batch, the guided=True stage of the batched match-and-verify calls).  The guided restatement (tests/guided_ref.py) forms every
 (query, train) residual with the CPU oracle's own metric functions, gates it with `<=`, ranks the gated rows by the matcher's numpy
 distances, and must agree with the device bit for bit: indices, distances, decisions and counts."""
 import ctypes as C
@@ -7,8 +7,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from oracle import matcher_np as mo
 from pydegensac_amd import _lib, matcher, parallel, synthetic as syn, tensor_api
+from tests.guided_ref import oracle as _oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -21,52 +21,6 @@ def _dev():
 def _t(x):
     import torch
     return torch.from_numpy(np.ascontiguousarray(x)).to(_dev())
-
-
-def _th(model, et, px):
-    return px if (model == "H" and et in (2, 4)) else px * px
-
-
-def _resid(P, model, et, Md, x1, x2):
-    """r(M; x1_q, y1_q, x2_t, y2_t) for every (q, t) of a pair, [n1, n2], from the oracle's metrics on u = [x1, y1, 1, x2, y2, 1]"""
-    n1, n2 = len(x1), len(x2)
-    u = np.ones((n1 * n2, 6)); u[:, 0:2] = np.repeat(x1[:, :2], n2, 0); u[:, 3:5] = np.tile(x2[:, :2], (n1, 1))
-    d = np.zeros(n1 * n2); m = np.ascontiguousarray(Md, np.float64).ravel().copy(); L = P.lib(); dp = P.dp
-    if model == "F":
-        (L.dg_oracle_FDs if et == 0 else L.dg_oracle_FDsSym)(dp(u), dp(m), dp(d), n1 * n2)
-    else:
-        L.dg_oracle_HDS_full(et, dp(u), dp(m), dp(d), n1 * n2)
-    return d.reshape(n1, n2)
-
-
-def _gated_knn2(gate, D):
-    n1 = D.shape[0]
-    idx = np.full((n1, 2), -1, np.int32); dist = np.full((n1, 2), np.inf, np.float32)
-    if D.shape[1] == 0:
-        return idx, dist
-    Dm = np.where(gate, D, np.float32(np.inf))
-    order = np.argsort(Dm, axis=1, kind="stable")[:, :2]          # stable: the lower index wins a tie; gated rows are finite
-    r = np.arange(n1)
-    for k in range(order.shape[1]):
-        ok = gate[r, order[:, k]]
-        idx[:, k] = np.where(ok, order[:, k], -1); dist[:, k] = np.where(ok, Dm[r, order[:, k]], np.inf)
-    return idx, dist
-
-
-def _oracle(P, model, et, px, Md, k1, k2, d1, d2, norm, ratio, mutual):
-    n1, n2 = len(d1), len(d2)
-    if n1 and n2 and np.any(Md):
-        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-            gate = _resid(P, model, et, Md, k1, k2) <= _th(model, et, px)        # NaN fails
-    else:
-        gate = np.zeros((n1, n2), bool)
-    D = mo.dist_matrix(d1, d2, norm) if n1 and n2 else np.zeros((n1, n2), np.float32)
-    idx, dist = _gated_knn2(gate, D)
-    keep = (idx[:, 0] >= 0) & (dist[:, 0] < np.float32(ratio) * dist[:, 1])
-    if mutual:
-        back, _ = _gated_knn2(gate.T, D.T)
-        keep &= back[np.clip(idx[:, 0], 0, None), 0] == np.arange(n1) if n2 else keep
-    return idx, dist, np.where(keep, idx[:, 0], -1).astype(np.int32)
 
 
 def _scene(model, n1, n2, seed, dim, norm, dup=True):
