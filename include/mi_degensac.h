@@ -330,11 +330,18 @@ int mi_degensac_find_fundamental_hist(const double *pts1, const double *pts2, in
  * second-nearest-neighbour ratio test and an optional mutual-nearest-neighbour check.
  *   norm L2:      float32 descriptors [n, dim]; distance = sqrt(sum_k (a_k - b_k)^2), fp32, summed in ascending k
  *   norm HAMMING: uint8 descriptors [n, dim] with dim % 4 == 0 (pad with zero bytes); distance = differing bits
+ *   norm L2_U8:   uint8 descriptors [n, dim] with dim % 4 == 0 (pad with zero bytes on both sides: they add nothing) and
+ *                 dim <= MI_DEGENSAC_L2_U8_MAX_DIM (SIFT / RootSIFT x 512, quantised HardNet / SOSNet / SuperPoint);
+ *                 S = sum_k (a_k - b_k)^2 as an exact integer (int8 matrix cores in the dense matcher), distance = sqrtf((float)S),
+ *                 ranking by (S, lower index).  S <= 256 * 255^2 < 2^24, so S is exact in fp32 too and idx / dist are bit for bit
+ *                 those of norm L2 on the same rows cast to float32.  No non-finite cases.  Wider rows: cast to float32, norm L2.
  * idx[i] = the two nearest train rows of query i (ties: lower index first; -1 when desc2 has fewer rows),
  * dist[i] their distances, keep[i] = dist[i][0] < ratio * dist[i][1] (and, with mutual, the nearest neighbour of
  * desc2[idx[i][0]] in desc1 is i). */
 #define MI_DEGENSAC_NORM_L2       0
 #define MI_DEGENSAC_NORM_HAMMING  1
+#define MI_DEGENSAC_NORM_L2_U8    4     /* (2 and 3 are not norms: MI_DEGENSAC_EINVAL) */
+#define MI_DEGENSAC_L2_U8_MAX_DIM 256
 int mi_degensac_match(int norm, const void *desc1, int n1, const void *desc2, int n2, int dim, float ratio, int mutual,
                       int device, int32_t *idx /*[n1,2]*/, float *dist /*[n1,2]*/, uint8_t *keep /*[n1], nullable*/);
 /* Non-finite distances (L2 only; a Hamming distance is always finite): a train row whose distance to the query is NaN or +inf —
@@ -367,7 +374,8 @@ int mi_degensac_match_knn2_batch_dev(int norm, const void *d_desc1, const void *
                                      const int64_t *offsets2_host, int n_pairs, int dim, int device, void *stream,
                                      int32_t *d_idx, float *d_dist);
 typedef struct mi_degensac_match_params {
-    int32_t norm;          /* MI_DEGENSAC_NORM_L2 (float32 rows) / MI_DEGENSAC_NORM_HAMMING (uint8 rows, dim % 4 == 0)     */
+    int32_t norm;          /* MI_DEGENSAC_NORM_L2 (float32 rows) / _HAMMING (uint8 rows, dim % 4 == 0) / _L2_U8 (uint8 rows,
+                              dim % 4 == 0, dim <= 256)                                                                 */
     int32_t dim;           /* descriptor length (elements)                                                              */
     float   ratio;         /* tentative when dist[0] < ratio * dist[1]; finite and > 0                                   */
     int32_t mutual;        /* bool: also require that the query is the nearest neighbour of its nearest train row         */
@@ -386,7 +394,8 @@ typedef struct mi_degensac_match_params {
  * Synchronisation: the matching is enqueued on `stream`, then the call reads the K tentative counts back (ONE device-to-host copy
  * followed by a wait for `stream`: the only synchronisation; the estimator's launch is sized from them on the host), enqueues the
  * gather, the estimator and the scatter and returns.  Discarded pairs (hand-over time-out) carry bit 10 of stats[15] as with the
- * other *_dev entry points.  Errors: MI_DEGENSAC_EINVAL for a bad norm / dim / kp_dim, Hamming with dim % 4 != 0, decreasing offsets,
+ * other *_dev entry points.  Errors: MI_DEGENSAC_EINVAL for a bad norm / dim / kp_dim, uint8 rows with dim % 4 != 0
+ * (or dim > 256 under L2_U8), decreasing offsets,
  * a ratio that is not finite and > 0, bad params; n_pairs == 0 returns 0. */
 int mi_degensac_match_verify_batch_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
                                        const int64_t *offsets1_host, const int64_t *offsets2_host, const double *d_kp1, const double *d_kp2,

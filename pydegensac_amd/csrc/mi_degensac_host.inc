@@ -1069,10 +1069,8 @@ static int mv_check(int homography, const mi_degensac_match_params *mp, const in
 {
     if (homography != 0 && homography != 1) { set_err("homography must be 0 or 1"); return MI_DEGENSAC_EINVAL; }
     if (!mp) { set_err("match params are NULL"); return MI_DEGENSAC_EINVAL; }
-    if ((mp->norm != MI_DEGENSAC_NORM_L2 && mp->norm != MI_DEGENSAC_NORM_HAMMING) || mp->dim <= 0) { set_err("bad norm or descriptor dim");
-        return MI_DEGENSAC_EINVAL; }
-    if (mp->norm == MI_DEGENSAC_NORM_HAMMING && mp->dim % 4) { set_err("Hamming descriptors must be padded to a multiple of 4 bytes");
-        return MI_DEGENSAC_EINVAL; }
+    if (!mt_norm_known(mp->norm) || mp->dim <= 0) { set_err("bad norm or descriptor dim"); return MI_DEGENSAC_EINVAL; }
+    if (const char *e = mt_norm_dim_error(mp->norm, mp->dim)) { set_err("%s", e); return MI_DEGENSAC_EINVAL; }
     if (!(isfinite(mp->ratio) && mp->ratio > 0.f)) { set_err("ratio must be finite and > 0"); return MI_DEGENSAC_EINVAL; }
     if (kp_dim != 2 && kp_dim != 6) { set_err("keypoint rows must be [n,2] or [n,6]"); return MI_DEGENSAC_EINVAL; }
     if (n_pairs < 0) { set_err("n_pairs < 0"); return MI_DEGENSAC_EINVAL; }
@@ -1105,7 +1103,7 @@ static int match_verify_dev(int homography, const mi_degensac_match_params *mp, 
     if (!d_seeds || !d_model || (n1 > 0 && (!d_desc1 || !d_kp1 || !d_match || !d_inlier)) || (n2 > 0 && (!d_desc2 || !d_kp2))) {
         set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
     DevGuard g; rc = g.enter(device); if (rc) return rc;
-    const int words = mp->norm == MI_DEGENSAC_NORM_L2 ? mp->dim : mp->dim / 4;
+    const int words = mt_row_words(mp->norm, mp->dim);
     const bool mutual = mp->mutual != 0;
     /* relative offsets; every row pointer moves to the batch's first row */
     std::vector<int64_t> o1(K + 1), o2(K + 1); std::vector<int32_t> o32(2 * (size_t)(K + 1));
@@ -1185,7 +1183,7 @@ extern "C" int mi_degensac_match_verify_batch(int homography, const mi_degensac_
     mi_degensac_ctx *c; rc = thread_ctx(device, &c); if (rc) return rc;
     DevGuard g; rc = g.enter(device); if (rc) return rc;
     const int64_t n1 = offsets1[K] - offsets1[0], n2 = offsets2[K] - offsets2[0];
-    const size_t row = (size_t)mp->dim * (mp->norm == MI_DEGENSAC_NORM_L2 ? 4 : 1);
+    const size_t row = mt_row_bytes(mp->norm, mp->dim);
     std::vector<int64_t> o1(K + 1), o2(K + 1);
     for (int p = 0; p <= K; p++) { o1[p] = offsets1[p] - offsets1[0]; o2[p] = offsets2[p] - offsets2[0]; }
     const size_t s_d1 = align_up(n1 * row, 256), s_d2 = align_up(n2 * row, 256), s_k1 = align_up((size_t)n1 * kd * 8, 256),

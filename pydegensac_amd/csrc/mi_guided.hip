@@ -11,7 +11,8 @@
  *                 correspondence that is already chosen (a second metric with its own threshold; the affine frames of both
  *                 keypoints), they do not describe the model's inlier band that the search is restricted to.
  *   guided 2-NN  the two nearest train rows of the query's own pair among those that pass the gate, in the matcher's distance
- *                (L2 = sqrt of the fp32 sum over ascending dimension, Hamming = popcount) and (distance, index) order, ties to
+ *                (L2 = sqrt of the fp32 sum over ascending dimension, Hamming = popcount, L2 over uint8 rows = sqrt of the exact
+ *                integer sum) and (distance, index) order, ties to
  *                the lower index (mt_push); -1 / inf where fewer than two rows pass.
  *
  * Cost follows the candidates, not n1 n2 dim: a workgroup owns MG_Q queries of one pair (MG_QPW per wave) and streams the pair's
@@ -71,7 +72,9 @@ __device__ __forceinline__ bool mg_gate(const double *M, const double *Hinv, con
 }
 
 /* the first n (<= 64) entries of a wave's candidate list: lane l takes entry l, forms its distance to the query row in the order of
- * mt_knn2_tile (fp32 sum of squared differences over ascending words / popcount) and pushes it into b */
+ * mt_knn2_tile (fp32 sum of squared differences over ascending words / popcount) and pushes it into b.  NORM 2 (uint8 rows under
+ * L2): the integer sum of the squared byte differences, at most 256 * 255^2 < 2^24 and so exact as the float it is pushed as (the
+ * value the dense matcher's matrix-core form gives) */
 template <int NORM>
 __device__ __forceinline__ void mg_flush(const uint32_t *qrow, const uint32_t *dt, int words, int t_b, const int *lst, int n, int lane, mt_best &b)
 {
@@ -84,7 +87,11 @@ __device__ __forceinline__ void mg_flush(const uint32_t *qrow, const uint32_t *d
         for (int w = 0; w < words; w++) {
             const uint32_t a = qrow[w], t = trow[w];
             if (NORM == 0) { const float df = __uint_as_float(a) - __uint_as_float(t); acc = acc + df * df; }
-            else h += (unsigned)__popc(a ^ t);
+            else if (NORM == 1) h += (unsigned)__popc(a ^ t);
+            else {
+#pragma unroll
+                for (int k = 0; k < 32; k += 8) { const int d = (int)((a >> k) & 255u) - (int)((t >> k) & 255u); h += (unsigned)(d * d); }
+            }
         }
         mt_push(b, NORM == 0 ? acc : (float)h, c);
     }
@@ -163,7 +170,7 @@ __global__ __launch_bounds__(256) void mg_guided_kernel(const uint32_t *dq, cons
         }
         if (lane == 0) {
             idx[2 * (size_t)q] = m.i0; idx[2 * (size_t)q + 1] = m.i1;
-            dist[2 * (size_t)q] = NORM == 0 ? sqrtf(m.d0) : m.d0; dist[2 * (size_t)q + 1] = NORM == 0 ? sqrtf(m.d1) : m.d1;
+            dist[2 * (size_t)q] = NORM != 1 ? sqrtf(m.d0) : m.d0; dist[2 * (size_t)q + 1] = NORM != 1 ? sqrtf(m.d1) : m.d1;
         }
     }
 }
@@ -243,7 +250,7 @@ int mt_batch_guided_knn2(int norm, int words, const void *dq, const void *dt, co
     const dim3 grid((unsigned)tiles), block(256);
 #define MG_LAUNCH(N, G) hipLaunchKernelGGL((mg_guided_kernel<N, G>), grid, block, 0, s, (const uint32_t *)dq, (const uint32_t *)dt, words, kq, kt, kd, \
         d_tab, n_pairs, d_models, g.hk, g.th, g.tb, g.screen, swap, idx, dist)
-    switch ((norm == MI_DEGENSAC_NORM_L2 ? 0 : 4) + g.gk) {
+    switch (4 * mt_norm_index(norm) + g.gk) {
     case 0: MG_LAUNCH(0, MG_F_SAMPSON); break;
     case 1: MG_LAUNCH(0, MG_F_SYM); break;
     case 2: MG_LAUNCH(0, MG_H_SAMPSON); break;
@@ -251,7 +258,11 @@ int mt_batch_guided_knn2(int norm, int words, const void *dq, const void *dt, co
     case 4: MG_LAUNCH(1, MG_F_SAMPSON); break;
     case 5: MG_LAUNCH(1, MG_F_SYM); break;
     case 6: MG_LAUNCH(1, MG_H_SAMPSON); break;
-    default: MG_LAUNCH(1, MG_H_SYM); break;
+    case 7: MG_LAUNCH(1, MG_H_SYM); break;
+    case 8: MG_LAUNCH(2, MG_F_SAMPSON); break;
+    case 9: MG_LAUNCH(2, MG_F_SYM); break;
+    case 10: MG_LAUNCH(2, MG_H_SAMPSON); break;
+    default: MG_LAUNCH(2, MG_H_SYM); break;
     }
 #undef MG_LAUNCH
     const hipError_t le = hipGetLastError();
@@ -272,8 +283,8 @@ int mt_batch_guided_decide(const int32_t *d_idx, const float *d_dist, const int3
 /* ---- C-ABI ----------------------------------------------------------------------------------------------------------- */
 static int mg_check(int norm, int dim, int kp_dim, const mi_degensac_guide_params *gp, const int64_t *o1, const int64_t *o2, int n_pairs, mt_gate *g)
 {
-    if ((norm != MI_DEGENSAC_NORM_L2 && norm != MI_DEGENSAC_NORM_HAMMING) || dim <= 0) return mg_einval("bad norm or descriptor dim");
-    if (norm == MI_DEGENSAC_NORM_HAMMING && dim % 4) return mg_einval("Hamming descriptors must be padded to a multiple of 4 bytes");
+    if (!mt_norm_known(norm) || dim <= 0) return mg_einval("bad norm or descriptor dim");
+    if (const char *e = mt_norm_dim_error(norm, dim)) return mg_einval(e);
     if (kp_dim != 2 && kp_dim != 6) return mg_einval("keypoint rows must be [n,2] or [n,6]");
     if (!gp) return mg_einval("guide params are NULL");
     if (gp->struct_size != 0 && gp->struct_size < (int32_t)sizeof(mi_degensac_guide_params)) return mg_einval("guide params: struct_size too small");
@@ -289,7 +300,7 @@ static int mg_check(int norm, int dim, int kp_dim, const mi_degensac_guide_param
     return 0;
 }
 
-static int mg_words(int norm, int dim) { return norm == MI_DEGENSAC_NORM_L2 ? dim : dim / 4; }
+static int mg_words(int norm, int dim) { return mt_row_words(norm, dim); }
 
 extern "C" int mi_degensac_match_guided_knn2_batch_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
                                                        const int64_t *offsets2_host, int n_pairs, int dim, const double *d_kp1, const double *d_kp2,
@@ -372,7 +383,7 @@ extern "C" int mi_degensac_match_guided_batch(const mi_degensac_match_params *mp
     if (!desc1 || !desc2 || !kp1 || !kp2 || !models || !idx || !dist || !match) return mg_einval("NULL argument");
     MgDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     const int64_t n1 = offsets1[K] - offsets1[0], n2 = offsets2[K] - offsets2[0];
-    const size_t row = (size_t)mp->dim * (mp->norm == MI_DEGENSAC_NORM_L2 ? 4 : 1);
+    const size_t row = mt_row_bytes(mp->norm, mp->dim);
     std::vector<int64_t> o1(K + 1), o2(K + 1);
     for (int p = 0; p <= K; p++) { o1[p] = offsets1[p] - offsets1[0]; o2[p] = offsets2[p] - offsets2[0]; }
     auto up = [](size_t b) { return (b + 255) / 256 * 256; };

@@ -8,6 +8,7 @@
 #define MI_MATCH_BATCH_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/mi_degensac.h"
 
 #define MT_HIDDEN __attribute__((visibility("hidden")))
 
@@ -22,6 +23,23 @@ __device__ __forceinline__ void mt_push(mt_best &b, float d, int i)
     if (lt0) { b.d1 = b.d0; b.i1 = b.i0; b.d0 = d; b.i0 = i; }
     else if (lt1) { b.d1 = d; b.i1 = i; }
 }
+
+/* ---- the norms (include/mi_degensac.h MI_DEGENSAC_NORM_*): one place for "is it a norm", the kernels' template index, the row size ---- */
+static inline bool mt_norm_known(int norm) { return norm == MI_DEGENSAC_NORM_L2 || norm == MI_DEGENSAC_NORM_HAMMING || norm == MI_DEGENSAC_NORM_L2_U8; }
+/* template index of the kernels: 0 = L2 over float words, 1 = Hamming, 2 = L2 over uint8 rows */
+static inline int mt_norm_index(int norm) { return norm == MI_DEGENSAC_NORM_L2 ? 0 : norm == MI_DEGENSAC_NORM_HAMMING ? 1 : 2; }
+/* what is wrong with dim (> 0) under a known norm, or null */
+static inline const char *mt_norm_dim_error(int norm, int dim)
+{
+    if (norm == MI_DEGENSAC_NORM_HAMMING && dim % 4) return "Hamming descriptors must be padded to a multiple of 4 bytes";
+    if (norm == MI_DEGENSAC_NORM_L2_U8 && dim % 4) return "uint8 L2 descriptors must be padded with zero bytes to a multiple of 4 bytes";
+    if (norm == MI_DEGENSAC_NORM_L2_U8 && dim > MI_DEGENSAC_L2_U8_MAX_DIM)
+        return "uint8 L2 descriptors are limited to dim <= 256 (the squared distance stays exact in fp32): use float32 rows beyond that";
+    return nullptr;
+}
+/* 32-bit words / bytes of a descriptor row (float32 elements for L2, packed bytes else) */
+static inline int mt_row_words(int norm, int dim) { return norm == MI_DEGENSAC_NORM_L2 ? dim : dim / 4; }
+static inline size_t mt_row_bytes(int norm, int dim) { return (size_t)dim * (norm == MI_DEGENSAC_NORM_L2 ? 4 : 1); }
 
 /* the message mi_degensac_match_last_error() returns for the calling thread */
 MT_HIDDEN void mt_set_error(const char *msg);

@@ -6,9 +6,11 @@
  * Distances are formed the way the tests' oracle (oracle/matcher_np.py) forms them, so that ranks, ties and ratio
  * decisions are bit-reproducible: L2 = sqrt of the fp32 sum of squared differences accumulated over the descriptor
  * dimension in ascending order (no FMA contraction: compiled with -ffp-contract=off), Hamming = popcount over the
- * bytes; ties go to the lower train index.  That rules out the |a|^2 + |b|^2 - 2ab matrix-core form (different
- * roundings, cancellation near duplicates); the direct form is 3 n1 n2 dim flop, a few tens of microseconds for two
- * images' worth of descriptors, and is LDS-tiled instead: a workgroup owns 64 queries, streams the train set through
+ * bytes; ties go to the lower train index.  For float rows that rules out the |a|^2 + |b|^2 - 2ab matrix-core form (different
+ * roundings, cancellation near duplicates).  For uint8 rows under L2 (MI_DEGENSAC_NORM_L2_U8, dim <= 256) the same form is exact:
+ * every term is an integer, the int8 matrix cores accumulate it in int32 in any order, and the result is < 2^24, hence bit for bit
+ * the fp32 sum of the direct form on the same values; that tile body is mi_matcher_u8.h.  The direct form is 3 n1 n2 dim flop, a
+ * few tens of microseconds for two images' worth of float descriptors, and is LDS-tiled: a workgroup owns 64 queries, streams the train set through
  * LDS 64 rows at a time (both tiles stored dimension-major, so a wave reads consecutive words / one broadcast word),
  * every thread keeps a 4 x 4 block of running sums in registers and its own running top-2 per query; the 16 threads
  * sharing a query merge their candidates at the end.  The train set is additionally split over blockIdx.y (see mt_knn2_kernel).
@@ -28,6 +30,7 @@
 #define MT_DC  64            /* descriptor words per LDS chunk */
 
 /* mt_best / mt_push (the running top-2 and its tie rule): mi_match_batch.h */
+#include "mi_matcher_u8.h"
 
 /* One workgroup's tile: queries q0 .. q_end - 1 (at most 64) of q against train rows t_lo .. t_hi - 1 of t, candidates
  * indexed from t_base (0 for a single pair, the pair's first train row in a batch).  NORM: 0 = L2 over float words,
@@ -91,14 +94,29 @@ __device__ __forceinline__ bool mt_knn2_tile(const uint32_t *q, int q0, int q_en
     return true;
 }
 
-/* final answer of query row r from its merged top-2, or its partial of split `split` when the train set is split */
+/* final answer of query row r from its merged top-2, or its partial of split `split` when the train set is split
+ * (NORM 2, uint8 rows under L2, carries the exact integer S as a float and takes the root as L2 does) */
 template <int NORM>
 __device__ __forceinline__ void mt_store(const mt_best &m, int r, int n_rows, int split, int32_t *idx, float *dist, mt_best *part)
 {
     if (part) { part[(size_t)split * n_rows + r] = m; return; }
     const size_t o = (size_t)r * 2;
     idx[o] = m.i0; idx[o + 1] = m.i1;
-    dist[o] = NORM == 0 ? sqrtf(m.d0) : m.d0; dist[o + 1] = NORM == 0 ? sqrtf(m.d1) : m.d1;
+    dist[o] = NORM != 1 ? sqrtf(m.d0) : m.d0; dist[o + 1] = NORM != 1 ? sqrtf(m.d1) : m.d1;
+}
+
+/* the tile body of a norm: NORM 0 / 1 = mt_knn2_tile over LDS tiles, NORM 2 = mu_knn2_tile<NS> (mi_matcher_u8.h) */
+template <int NORM, int NS>
+__device__ __forceinline__ bool mt_tile(const uint32_t *q, int q0, int q_end, const uint32_t *t, int t_lo, int t_hi, int t_base, int words,
+                                        mt_best (&merge)[MT_Q][16], mt_best &m)
+{
+    if constexpr (NORM == 2) {
+        __shared__ int ntl[4 * 32];
+        return mu_knn2_tile<NS>(q, q0, q_end, t, t_lo, t_hi, t_base, words, ntl, merge, m);
+    } else {
+        __shared__ uint32_t qs[MT_DC][MT_Q + 1], ts[MT_DC][MT_T + 1];
+        return mt_knn2_tile<NORM>(q, q0, q_end, t, t_lo, t_hi, t_base, words, qs, ts, merge, m);
+    }
 }
 
 /* Launch shape: grid = (ceil(n1 / 64), train splits).  Two images' worth of descriptors give only a few dozen query
@@ -106,17 +124,16 @@ __device__ __forceinline__ void mt_store(const mt_best &m, int r, int n_rows, in
  * writes its top-2 per query (squared distances) to part[split][query] and mt_merge_kernel merges the splits with the same
  * (distance, index) order, so the result does not depend on the split count.  With one split the kernel writes the final
  * answer itself. */
-template <int NORM>
+template <int NORM, int NS = 0>
 __global__ __launch_bounds__(256) void mt_knn2_kernel(const uint32_t *q, int n1, const uint32_t *t, int n2, int words,
     int t_chunk /* train rows per split, multiple of 64 */,
                                                       int32_t *idx /* [n1,2] */, float *dist /* [n1,2] */, mt_best *part /* [splits][n1] or null */)
 {
-    __shared__ uint32_t qs[MT_DC][MT_Q + 1], ts[MT_DC][MT_T + 1];
     __shared__ mt_best merge[MT_Q][16];
     const int q0 = blockIdx.x * MT_Q;
     const int t_lo = (int)blockIdx.y * t_chunk, t_hi = t_lo + t_chunk < n2 ? t_lo + t_chunk : n2;
     mt_best m;
-    if (mt_knn2_tile<NORM>(q, q0, n1, t, t_lo, t_hi, 0, words, qs, ts, merge, m))
+    if (mt_tile<NORM, NS>(q, q0, n1, t, t_lo, t_hi, 0, words, merge, m))
         mt_store<NORM>(m, q0 + threadIdx.x, n1, blockIdx.y, idx, dist, part);
 }
 
@@ -124,16 +141,15 @@ __global__ __launch_bounds__(256) void mt_knn2_kernel(const uint32_t *q, int n1,
  * tiles[blockIdx.x] = (first query row, end of the pair's query rows, first train row of the pair, end of its train rows), built on
  * the host from the host offsets; rows are global over the batch, the indices written are local to the pair.  Split y takes
  * the pair's train rows t_begin + y t_chunk .. + t_chunk (possibly none: the partial then stays at (inf, -1)). */
-template <int NORM>
+template <int NORM, int NS = 0>
 __global__ __launch_bounds__(256) void mt_knn2_batch_kernel(const uint32_t *q, const uint32_t *t, int words, const int4 *tiles, int n_rows,
                                                             int t_chunk, int32_t *idx, float *dist, mt_best *part)
 {
-    __shared__ uint32_t qs[MT_DC][MT_Q + 1], ts[MT_DC][MT_T + 1];
     __shared__ mt_best merge[MT_Q][16];
     const int4 tl = tiles[blockIdx.x];
     const int t_lo = tl.z + (int)blockIdx.y * t_chunk, t_hi = t_lo + t_chunk < tl.w ? t_lo + t_chunk : tl.w;
     mt_best m;
-    if (mt_knn2_tile<NORM>(q, tl.x, tl.y, t, t_lo, t_hi, tl.z, words, qs, ts, merge, m))
+    if (mt_tile<NORM, NS>(q, tl.x, tl.y, t, t_lo, t_hi, tl.z, words, merge, m))
         mt_store<NORM>(m, tl.x + threadIdx.x, n_rows, blockIdx.y, idx, dist, part);
 }
 
@@ -258,20 +274,30 @@ struct MtDevGuard {
     ~MtDevGuard() { if (armed) (void)hipSetDevice(prev); }
 };
 
-static int mt_words(int norm, int dim)
+/* norm and dim of a dense entry point (refused before the library looks for a device); uint8 rows are passed padded to whole
+ * 32-bit words */
+static int mt_check_norm(int norm, int dim)
 {
-    if (norm == MI_DEGENSAC_NORM_L2) return dim;
-    return dim % 4 == 0 ? dim / 4 : -1;           /* Hamming rows are passed padded to whole 32-bit words */
+    if (!mt_norm_known(norm) || dim <= 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
+    if (const char *e = mt_norm_dim_error(norm, dim)) { snprintf(mt_err, sizeof mt_err, "%s", e); return MI_DEGENSAC_EINVAL; }
+    return 0;
 }
+
+/* one of the two dense kernels for a norm code; uint8 L2 rows take the instance with the fewest 32-byte k-steps covering the row */
+#define MT_LAUNCH_NORM(KERNEL, norm, words, grid, block, s, ...) do { \
+    if ((norm) == MI_DEGENSAC_NORM_L2)           hipLaunchKernelGGL((KERNEL<0>), grid, block, 0, s, __VA_ARGS__); \
+    else if ((norm) == MI_DEGENSAC_NORM_HAMMING) hipLaunchKernelGGL((KERNEL<1>), grid, block, 0, s, __VA_ARGS__); \
+    else if ((words) <= 16)                      hipLaunchKernelGGL((KERNEL<2, 2>), grid, block, 0, s, __VA_ARGS__); \
+    else if ((words) <= 32)                      hipLaunchKernelGGL((KERNEL<2, 4>), grid, block, 0, s, __VA_ARGS__); \
+    else                                         hipLaunchKernelGGL((KERNEL<2, 8>), grid, block, 0, s, __VA_ARGS__); } while (0)
 
 extern "C" int mi_degensac_match_knn2_dev(int norm, const void *d_desc1, int n1, const void *d_desc2, int n2, int dim, int device,
                                           void *stream, int32_t *d_idx, float *d_dist)
 {
-    if ((norm != MI_DEGENSAC_NORM_L2 && norm != MI_DEGENSAC_NORM_HAMMING) || n1 < 0 || n2 < 0 || dim <= 0) { snprintf(mt_err, sizeof mt_err, "bad argument");
-        return MI_DEGENSAC_EINVAL; }
-    const int words = mt_words(norm, dim);
-    if (words < 0) { snprintf(mt_err, sizeof mt_err, "Hamming descriptors must be padded to a multiple of 4 bytes"); return MI_DEGENSAC_EINVAL; }
-    MtDevGuard g; int rc = g.enter(device); if (rc) return rc;
+    if (n1 < 0 || n2 < 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
+    int rc = mt_check_norm(norm, dim); if (rc) return rc;
+    const int words = mt_row_words(norm, dim);
+    MtDevGuard g; rc = g.enter(device); if (rc) return rc;
     if (n1 == 0) return 0;
     /* train splits: enough workgroups to cover the device about twice, never less than one 64-row tile per split */
     const int qtiles = (n1 + MT_Q - 1) / MT_Q, ttiles = n2 > 0 ? (n2 + MT_T - 1) / MT_T : 1;
@@ -282,14 +308,12 @@ extern "C" int mi_degensac_match_knn2_dev(int norm, const void *d_desc1, int n1,
     mt_best *part = nullptr;
     if (splits > 1) MTCHK(hipMallocAsync((void **)&part, (size_t)splits * n1 * sizeof(mt_best), (hipStream_t)stream));
     const dim3 grid(qtiles, splits), block(256);
-    if (norm == MI_DEGENSAC_NORM_L2) hipLaunchKernelGGL(mt_knn2_kernel<0>, grid, block, 0, (hipStream_t)stream, (const uint32_t *)d_desc1, n1,
-        (const uint32_t *)d_desc2, n2, words, n2 > 0 ? t_chunk : MT_T, d_idx, d_dist, part);
-    else                             hipLaunchKernelGGL(mt_knn2_kernel<1>, grid, block, 0, (hipStream_t)stream, (const uint32_t *)d_desc1, n1,
-        (const uint32_t *)d_desc2, n2, words, n2 > 0 ? t_chunk : MT_T, d_idx, d_dist, part);
+    MT_LAUNCH_NORM(mt_knn2_kernel, norm, words, grid, block, (hipStream_t)stream, (const uint32_t *)d_desc1, n1, (const uint32_t *)d_desc2, n2, words,
+        n2 > 0 ? t_chunk : MT_T, d_idx, d_dist, part);
     hipError_t le = hipGetLastError();
     if (le == hipSuccess && part) {
-        hipLaunchKernelGGL(mt_merge_kernel, dim3((n1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, part, splits, n1, norm == MI_DEGENSAC_NORM_L2 ? 1 : 0,
-            d_idx, d_dist);
+        hipLaunchKernelGGL(mt_merge_kernel, dim3((n1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, part, splits, n1,
+            norm != MI_DEGENSAC_NORM_HAMMING ? 1 : 0, d_idx, d_dist);
         le = hipGetLastError();
     }
     if (part) (void)hipFreeAsync(part, (hipStream_t)stream);
@@ -313,9 +337,10 @@ extern "C" int mi_degensac_match(int norm, const void *desc1, int n1, const void
                                  int32_t *idx /* [n1,2] */, float *dist /* [n1,2] */, uint8_t *keep /* [n1] or NULL */)
 {
     if (!desc1 || !desc2 || !idx || !dist || n1 < 0 || n2 < 0 || dim <= 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
-    MtDevGuard g; int rc = g.enter(device); if (rc) return rc;
+    int rc = mt_check_norm(norm, dim); if (rc) return rc;
+    MtDevGuard g; rc = g.enter(device); if (rc) return rc;
     if (n1 == 0) return 0;
-    const size_t esz = norm == MI_DEGENSAC_NORM_L2 ? 4 : 1, b1 = (size_t)n1 * dim * esz, b2 = (size_t)n2 * dim * esz;
+    const size_t b1 = (size_t)n1 * mt_row_bytes(norm, dim), b2 = (size_t)n2 * mt_row_bytes(norm, dim);
     char *d1 = nullptr, *d2 = nullptr; int32_t *di = nullptr, *dbi = nullptr; float *dd = nullptr, *dbd = nullptr; uint8_t *dk = nullptr;
     struct Free { char *&a, *&b; int32_t *&c, *&d; float *&e, *&f; uint8_t *&g;
                   ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(d); (void)hipFree(e); (void)hipFree(f); (void)hipFree(g);
@@ -432,13 +457,12 @@ int mt_batch_knn2(int norm, int words, const void *dq, const void *dt, const int
     if (rc) { (void)hipFreeAsync(buf, s); return rc; }
     mt_best *part = splits > 1 ? (mt_best *)(buf + b_tiles) : nullptr;
     const dim3 grid(qtiles, splits), block(256);
-    if (norm == MI_DEGENSAC_NORM_L2) hipLaunchKernelGGL(mt_knn2_batch_kernel<0>, grid, block, 0, s, (const uint32_t *)dq, (const uint32_t *)dt, words,
-        (const int4 *)buf, n_rows, t_chunk, idx, dist, part);
-    else                             hipLaunchKernelGGL(mt_knn2_batch_kernel<1>, grid, block, 0, s, (const uint32_t *)dq, (const uint32_t *)dt, words,
-        (const int4 *)buf, n_rows, t_chunk, idx, dist, part);
+    MT_LAUNCH_NORM(mt_knn2_batch_kernel, norm, words, grid, block, s, (const uint32_t *)dq, (const uint32_t *)dt, words, (const int4 *)buf, n_rows,
+        t_chunk, idx, dist, part);
     hipError_t le = hipGetLastError();
     if (le == hipSuccess && part) {
-        hipLaunchKernelGGL(mt_merge_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, s, part, splits, n_rows, norm == MI_DEGENSAC_NORM_L2 ? 1 : 0, idx, dist);
+        hipLaunchKernelGGL(mt_merge_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, s, part, splits, n_rows, norm != MI_DEGENSAC_NORM_HAMMING ? 1 : 0, idx,
+            dist);
         le = hipGetLastError();
     }
     (void)hipFreeAsync(buf, s);
@@ -489,14 +513,13 @@ extern "C" int mi_degensac_match_knn2_batch_dev(int norm, const void *d_desc1, c
                                                 const int64_t *offsets2_host, int n_pairs, int dim, int device, void *stream, int32_t *d_idx,
                                                 float *d_dist)
 {
-    if ((norm != MI_DEGENSAC_NORM_L2 && norm != MI_DEGENSAC_NORM_HAMMING) || n_pairs < 0 || dim <= 0) { snprintf(mt_err, sizeof mt_err, "bad argument");
-        return MI_DEGENSAC_EINVAL; }
-    const int words = mt_words(norm, dim);
-    if (words < 0) { snprintf(mt_err, sizeof mt_err, "Hamming descriptors must be padded to a multiple of 4 bytes"); return MI_DEGENSAC_EINVAL; }
+    if (n_pairs < 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
+    int rc = mt_check_norm(norm, dim); if (rc) return rc;
+    const int words = mt_row_words(norm, dim);
     if (n_pairs == 0) return 0;
     if (!mt_check_offsets(offsets1_host, n_pairs) || !mt_check_offsets(offsets2_host, n_pairs)) {
         snprintf(mt_err, sizeof mt_err, "offsets must be non-negative and non-decreasing"); return MI_DEGENSAC_EINVAL; }
-    MtDevGuard g; int rc = g.enter(device); if (rc) return rc;
+    MtDevGuard g; rc = g.enter(device); if (rc) return rc;
     std::vector<int64_t> o1(n_pairs + 1), o2(n_pairs + 1);
     for (int p = 0; p <= n_pairs; p++) { o1[p] = offsets1_host[p] - offsets1_host[0]; o2[p] = offsets2_host[p] - offsets2_host[0]; }
     return mt_batch_knn2(norm, words, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words,

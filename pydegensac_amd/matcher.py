@@ -5,14 +5,27 @@
     tentatives = [m for m, n in matches if m.distance < 0.9 * n.distance]     ->  q, t, d = match_snn(descs1, descs2, 0.9)
 
 float32 descriptors use the L2 norm (cv2.BFMatcher's default, what the example runs on AKAZE's KAZE descriptors), uint8
-descriptors the Hamming norm.  No CPU path: without the HIP library / a gfx950 device every call raises."""
+descriptors the Hamming norm.  norm="l2_u8" is the L2 norm on uint8 rows as they are (SIFT / RootSIFT x 512, quantised HardNet /
+SOSNet / SuperPoint; dim <= 256): the squared distance is an exact integer below 2^24, formed on the int8 matrix cores, and idx / dist
+are bit for bit those of norm="l2" on the same rows cast to float32.  No CPU path: without the HIP library / a gfx950 device every
+call raises."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
 
-NORM_L2, NORM_HAMMING = 0, 1
+NORM_L2, NORM_HAMMING, NORM_L2_U8 = 0, 1, 4
+L2_U8_MAX_DIM = 256          # 256 * 255^2 < 2^24: the squared distance stays exact in fp32
+_NORMS = {"l2": NORM_L2, "hamming": NORM_HAMMING, "l2_u8": NORM_L2_U8}
+
+
+def _pad_words(a, b):
+    """uint8 rows padded to whole 32-bit words; zero bytes on both sides add no differing bits and no squared difference"""
+    pad = (-a.shape[1]) % 4
+    if pad:
+        a = np.pad(a, ((0, 0), (0, pad))); b = np.pad(b, ((0, 0), (0, pad)))
+    return a, b
 
 
 def _prep(desc1, desc2, norm):
@@ -21,16 +34,16 @@ def _prep(desc1, desc2, norm):
         raise ValueError("descriptors should be arrays [n1, dim] and [n2, dim] with the same dim")
     if norm is None:
         norm = "hamming" if a.dtype == np.uint8 and b.dtype == np.uint8 else "l2"
-    if norm not in ("l2", "hamming"):
-        raise ValueError("norm should be 'l2' or 'hamming'")
+    if norm not in _NORMS:
+        raise ValueError("norm should be 'l2', 'hamming' or 'l2_u8'")
     if norm == "l2":
         return NORM_L2, np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
     if a.dtype != np.uint8 or b.dtype != np.uint8:
-        raise ValueError("the Hamming norm needs uint8 descriptors")
-    pad = (-a.shape[1]) % 4                                   # whole 32-bit words; zero bytes add no differing bits
-    if pad:
-        a = np.pad(a, ((0, 0), (0, pad))); b = np.pad(b, ((0, 0), (0, pad)))
-    return NORM_HAMMING, np.ascontiguousarray(a), np.ascontiguousarray(b)
+        raise ValueError("the Hamming norm needs uint8 descriptors" if norm == "hamming" else "norm 'l2_u8' needs uint8 descriptors")
+    if norm == "l2_u8" and a.shape[1] > L2_U8_MAX_DIM:
+        raise ValueError(f"norm 'l2_u8' takes dim <= {L2_U8_MAX_DIM}: use float32 descriptors with norm 'l2' beyond that")
+    a, b = _pad_words(a, b)
+    return _NORMS[norm], np.ascontiguousarray(a), np.ascontiguousarray(b)
 
 
 def _run(desc1, desc2, norm, ratio, mutual, want_keep, device):
@@ -112,12 +125,16 @@ def check_match_verify_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2
         raise ValueError("descriptors should both be float32 (L2) or both uint8 (Hamming)")
     if norm is None:
         norm = "hamming" if t1 == "uint8" else "l2"
-    if norm not in ("l2", "hamming"):
-        raise ValueError("norm should be 'l2' or 'hamming'")
+    if norm not in _NORMS:
+        raise ValueError("norm should be 'l2', 'hamming' or 'l2_u8'")
     if norm == "hamming" and t1 != "uint8":
         raise ValueError("the Hamming norm needs uint8 descriptors")
     if norm == "l2" and t1 != "float32":
-        raise ValueError("the L2 norm needs float32 descriptors")
+        raise ValueError("the L2 norm needs float32 descriptors (norm 'l2_u8' takes uint8 rows of dim <= 256 as they are)")
+    if norm == "l2_u8" and t1 != "uint8":
+        raise ValueError("norm 'l2_u8' needs uint8 descriptors")
+    if norm == "l2_u8" and d1_shape[1] > L2_U8_MAX_DIM:
+        raise ValueError(f"norm 'l2_u8' takes dim <= {L2_U8_MAX_DIM}: use float32 descriptors with norm 'l2' beyond that")
     kinds = []
     for shp, dt in ((k1_shape, k1_dtype), (k2_shape, k2_dtype)):
         name = _dtype_name(dt)
@@ -142,7 +159,7 @@ def check_match_verify_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2
     o2 = np.zeros(len(c2) + 1, np.int64); np.cumsum(c2, out=o2[1:])
     if o1[-1] != d1_shape[0] or o2[-1] != d2_shape[0]:
         raise ValueError("counts do not add up to the number of descriptor rows")
-    return (NORM_L2 if norm == "l2" else NORM_HAMMING), kinds[0][0], o1, o2
+    return _NORMS[norm], kinds[0][0], o1, o2
 
 
 def estimator_params(model, px_th=None, conf=None, max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
@@ -188,7 +205,7 @@ def _h_driver_form(M):
 
 def _stack_pairs(kps1_list, kps2_list, desc1_list, desc2_list, model, ratio, norm, device):
     """the per-pair lists of the batched calls -> (norm code, A, B, K1, K2, offsets1, offsets2): descriptors padded to whole 32-bit
-    words for Hamming, keypoints as float64 [n, 2] / [n, 6] rows"""
+    words for uint8 rows, keypoints as float64 [n, 2] / [n, 6] rows"""
     K = len(desc1_list)
     if not (len(kps1_list) == len(kps2_list) == len(desc2_list) == K):
         raise ValueError("kps1_list, kps2_list, desc1_list and desc2_list should hold one entry per pair")
@@ -209,9 +226,8 @@ def _stack_pairs(kps1_list, kps2_list, desc1_list, desc2_list, model, ratio, nor
 
 
 def _finish_pairs(code, kind, A, B, K1, K2, device):
-    if code == NORM_HAMMING and A.shape[1] % 4:
-        pad = (-A.shape[1]) % 4
-        A = np.pad(A, ((0, 0), (0, pad))); B = np.pad(B, ((0, 0), (0, pad)))
+    if code != NORM_L2:
+        A, B = _pad_words(A, B)
     A = np.ascontiguousarray(A); B = np.ascontiguousarray(B)
     if kind == "kpts":
         K1 = kpts_to_xyA(K1, device); K2 = kpts_to_xyA(K2, device)
@@ -271,7 +287,8 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
     """K image pairs from descriptors and keypoints to models in one call: per pair the 2-NN ratio test of match_snn (optionally
     mutual), then findFundamentalMatrix (model "F") or findHomography ("H") on its tentatives, all pairs in one launch.  kps are
     float64 [n, 2] / [n, 6] rows or float32 [n, 4] keypoints (x, y, size, angle -> LAF rows as kpts_to_xyA); descriptors float32
-    (L2) or uint8 (Hamming; padded to whole 32-bit words here).  A pair with fewer than 8 (F) / 4 (H) tentatives gets a zero model
+    (L2) or uint8 (Hamming, or L2 with norm="l2_u8" and dim <= 256; padded to whole 32-bit words here).
+    A pair with fewer than 8 (F) / 4 (H) tentatives gets a zero model
     and no inliers.  seeds default to parallel.pair_seeds(0, K).  Returns (models [K, 3, 3], [match_p], [inlier_p]): match_p[i] =
     the train row of query i or -1, inlier_p[i] = query i is a tentative and an inlier; H is the user-facing inv(H_c^T).
     guided=True runs guided_match_batch after the estimator with the driver-form models it returned (no conversion), this call's
@@ -295,9 +312,8 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
     code, kind, o1, o2 = check_match_verify_args(model, ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape, K2.dtype,
                                                  np.asarray(c1, np.int64), np.asarray(c2, np.int64))
     prm = estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
-    if code == NORM_HAMMING and A.shape[1] % 4:
-        pad = (-A.shape[1]) % 4
-        A = np.pad(A, ((0, 0), (0, pad))); B = np.pad(B, ((0, 0), (0, pad)))
+    if code != NORM_L2:
+        A, B = _pad_words(A, B)
     A = np.ascontiguousarray(A); B = np.ascontiguousarray(B)
     if kind == "kpts":
         K1 = kpts_to_xyA(K1, device); K2 = kpts_to_xyA(K2, device)

@@ -87,21 +87,28 @@ def find_homography_batch_tensors(pts1, pts2, counts, px_th=1.0, conf=0.999, max
 
 
 # ---- the stage in front of the estimators on the device: matcher and keypoint conversion -------------
-def knn_match_tensors(desc1, desc2):
+def knn_match_tensors(desc1, desc2, norm=None):
     """cv2 `BFMatcher().knnMatch(descs1, descs2, k=2)` (examples/simple-example.py:46-47) on device tensors: float32
-    descriptors [n, dim] -> L2, uint8 [n, dim] (dim % 4 == 0) -> Hamming.  Returns (idx [n1, 2] int32, dist [n1, 2] float32)
-    on the device, asynchronous on the current stream."""
+    descriptors [n, dim] -> L2, uint8 [n, dim] (dim % 4 == 0) -> Hamming; norm="l2_u8" takes uint8 rows (dim % 4 == 0, dim <= 256)
+    under L2, bit-identical to the float32 path on the same values (norm None / "l2" / "hamming": the dtype's norm, as before).
+    Returns (idx [n1, 2] int32, dist [n1, 2] float32) on the device, asynchronous on the current stream."""
     import torch
     if not (isinstance(desc1, torch.Tensor) and isinstance(desc2, torch.Tensor)) or desc1.device.type != "cuda" or desc2.device != desc1.device:
         raise ValueError("descriptors must be torch tensors on the same ROCm device")
     if desc1.dim() != 2 or desc2.dim() != 2 or desc1.shape[1] != desc2.shape[1] or desc1.dtype != desc2.dtype:
         raise ValueError("descriptors should be [n1, dim] and [n2, dim] tensors of one dtype")
-    if desc1.dtype == torch.float32:
+    if norm not in (None, "l2", "hamming", "l2_u8"):
+        raise ValueError("norm should be None, 'l2', 'hamming' or 'l2_u8'")
+    if desc1.dtype == torch.float32 and norm in (None, "l2"):
         norm = 0
-    elif desc1.dtype == torch.uint8 and desc1.shape[1] % 4 == 0:
+    elif desc1.dtype == torch.uint8 and desc1.shape[1] % 4 == 0 and norm in (None, "hamming"):
         norm = 1
+    elif desc1.dtype == torch.uint8 and desc1.shape[1] % 4 == 0 and norm == "l2_u8":
+        if desc1.shape[1] > 256:
+            raise ValueError("norm 'l2_u8' takes dim <= 256: use float32 descriptors with norm 'l2' beyond that")
+        norm = 4
     else:
-        raise ValueError("float32 descriptors (L2) or uint8 descriptors with dim % 4 == 0 (Hamming)")
+        raise ValueError("float32 descriptors (L2) or uint8 descriptors with dim % 4 == 0 (Hamming, or L2 with norm='l2_u8')")
     a = desc1.contiguous(); b = desc2.contiguous(); dev = a.device
     # the kernel reads descriptor rows as 32-bit words: a contiguous view into a packed buffer may start at any byte
     if a.data_ptr() % 4: a = a.clone()
@@ -119,15 +126,16 @@ def knn_match_tensors(desc1, desc2):
     return idx, dist
 
 
-def match_snn_tensors(desc1, desc2, ratio=0.9, mutual=False):
+def match_snn_tensors(desc1, desc2, ratio=0.9, mutual=False, norm=None):
     """The ratio test of the example (`m.distance < ratio * n.distance`, simple-example.py:49-53), optionally restricted to
     mutual nearest neighbours, on the device: (query indices, train indices, distances) of the tentative correspondences.
-    The only host synchronisation is the final boolean selection (the number of survivors sizes the outputs)."""
+    norm as for knn_match_tensors.  The only host synchronisation is the final boolean selection (the number of survivors sizes the
+    outputs)."""
     import torch
-    idx, dist = knn_match_tensors(desc1, desc2)
+    idx, dist = knn_match_tensors(desc1, desc2, norm)
     dev = idx.device; n1 = idx.shape[0]
     keep = torch.zeros(n1, dtype=torch.uint8, device=dev)
-    back = knn_match_tensors(desc2, desc1)[0] if mutual and desc2.shape[0] > 0 else None
+    back = knn_match_tensors(desc2, desc1, norm)[0] if mutual and desc2.shape[0] > 0 else None
     stream = torch.cuda.current_stream(dev)
     rc = _lib.lib().mi_degensac_match_filter_dev(idx.data_ptr(), dist.data_ptr(), n1, float(ratio), back.data_ptr() if back is not None else None,
                                                  dev.index or 0, C.c_void_p(stream.cuda_stream), keep.data_ptr())
@@ -166,19 +174,20 @@ def _desc_pair(desc1, desc2):
     if not (isinstance(desc1, torch.Tensor) and isinstance(desc2, torch.Tensor)) or desc1.device.type != "cuda" or desc2.device != desc1.device:
         raise ValueError("descriptors must be torch tensors on the same ROCm device")
     if desc1.dtype == torch.uint8 and desc1.shape[1] % 4:
-        raise ValueError("uint8 descriptors (Hamming) need dim % 4 == 0: pad with zero bytes")
+        raise ValueError("uint8 descriptors (Hamming, L2 with norm='l2_u8') need dim % 4 == 0: pad with zero bytes")
     return _word_aligned(desc1), _word_aligned(desc2)
 
 
-def knn_match_batch_tensors(desc1, desc2, counts1, counts2):
+def knn_match_batch_tensors(desc1, desc2, counts1, counts2, norm=None):
     """knn_match_tensors for K image pairs in one launch: pair p's queries are the next counts1[p] rows of desc1, its train set the
     next counts2[p] rows of desc2.  Returns (idx [N1, 2] int32 with indices LOCAL to the pair, dist [N1, 2] float32) on the device,
-    per pair bit-identical to knn_match_tensors on that pair; asynchronous on the current stream."""
+    per pair bit-identical to knn_match_tensors on that pair; asynchronous on the current stream.  norm: None = the dtype's norm
+    (float32 L2, uint8 Hamming), or "l2" / "hamming" / "l2_u8" (uint8 rows under L2, dim <= 256)."""
     import torch
     from . import matcher
     if not (isinstance(desc1, torch.Tensor) and isinstance(desc2, torch.Tensor)):
         raise ValueError("descriptors must be torch tensors on a ROCm device")
-    code, _, o1, o2 = matcher.check_match_verify_args("F", 1.0, None, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
+    code, _, o1, o2 = matcher.check_match_verify_args("F", 1.0, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
                                                       (desc1.shape[0], 2), np.float64, (desc2.shape[0], 2), np.float64, counts1, counts2)
     a, b = _desc_pair(desc1, desc2)
     dev = a.device; n1 = a.shape[0]; K = len(o1) - 1
@@ -253,12 +262,13 @@ def guided_match_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model
 
 def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
                                    max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
-                                   enable_degeneracy_check=True, seeds=None, guided=False):
+                                   enable_degeneracy_check=True, seeds=None, guided=False, norm=None):
     """K image pairs from descriptors to models with ONE host synchronisation (the read of the per-pair tentative counts): per pair
     the 2-NN ratio test (`m.distance < ratio * n.distance`, optionally mutual) of match_snn_tensors, then the estimator of
     find_fundamental_batch_tensors (model "F") / find_homography_batch_tensors ("H") on its tentatives in query order.
     kps: float64 [N, 2] / [N, 6] rows, or float32 [N, 4] keypoints (x, y, size, angle) that go through kpts_to_xyA_tensors;
-    descriptors float32 (L2) or uint8 with dim % 4 == 0 (Hamming).  Defaults are findFundamentalMatrix's / findHomography's; seeds
+    descriptors float32 (L2) or uint8 with dim % 4 == 0 (Hamming; L2 with norm="l2_u8" and dim <= 256).
+    Defaults are findFundamentalMatrix's / findHomography's; seeds
     default to parallel.pair_seeds(0, K) and belong to the pair, whatever else is in the batch.  A pair with fewer than 8 (F) / 4 (H)
     tentatives is not estimated: zero model, zero stats row, no inliers.
     Returns (model [K, 3, 3] float64 — H as the user-facing inv(H_c^T), zeros where none was found —, match [N1] int32 = pair-local
@@ -271,7 +281,7 @@ def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, m
     ts = (kps1, kps2, desc1, desc2)
     if not all(isinstance(t, torch.Tensor) for t in ts):
         raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
-    code, kind, o1, o2 = matcher.check_match_verify_args(model, ratio, None, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
+    code, kind, o1, o2 = matcher.check_match_verify_args(model, ratio, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
                                                          tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype, counts1, counts2)
     if any(t.device != desc1.device for t in ts):
         raise ValueError("kps1, kps2, desc1 and desc2 must live on the same ROCm device")
