@@ -270,11 +270,16 @@ static void HDs(const double *u, const double *H, double *p, int len)
     int i; for (i = 0; i < len; i++) p[i] = HDs_one(u + 6*i, H);
 }
 
+/* which branch of u2h a driver call took: [0] calls with len == 4, [1] calls with 5 <= len <= 10.  The drivers' entry points
+ * clear them and report them in stats[DG_ST_U2H_4PT] / stats[DG_ST_U2H_SHORT], so that a test can prove it reached the fit. */
+static __thread int g_u2h_cnt[2] = {0, 0};
+
 /* Htools.c:101-133 */
 static void u2h(const double *u, const int *inl, int len, double *H)
 {
     double A1[3], A2[3], V[81], D[9]; int i, j, nb[18];
     if (len < 4) return;
+    if (len == 4) g_u2h_cnt[0]++; else if (len <= 10) g_u2h_cnt[1]++;
     if (len == 4) {
         /* Htools.c:106-114: lin_hg gives a 9(col) x 8(row) block which the reference transposes as
          * if it were 9x9 before nullspace(); the 9 never-written entries are zeroed here */
@@ -1007,8 +1012,10 @@ int dg_oracle_find_fundamental(const double *x1, const double *x2, int n, int di
     ub = (double *)malloc(sizeof(double) * 6 * (size_t)(laf ? n : 1));
     build_u(x1, x2, n, dim, laf && dim == 6, u, ua, ub);
     for (i = 0; i < 9; i++) F[i] = 0;
+    g_u2h_cnt[0] = g_u2h_cnt[1] = 0;
     ret = exp_ransacFcustomLAF(&c, u, ua, ub, n, th, laf_coef, conf, max_iters, F, mask, 1, 0,
                                EXFDS1, FDS1, FDSidx1, sym_th, degen, seed, final_laf_filter, stats);
+    if (stats) { stats[DG_ST_U2H_4PT] = g_u2h_cnt[0]; stats[DG_ST_U2H_SHORT] = g_u2h_cnt[1]; }
     free(u); free(ua); free(ub); free(c.ht);
     return ret;
 }
@@ -1435,7 +1442,9 @@ int dg_oracle_find_homography(const double *x1, const double *x2, int n, int dim
     ub = (double *)malloc(sizeof(double) * 6 * (size_t)(laf ? n : 1));
     build_u(x1, x2, n, dim, laf, u, ua, ub);
     for (i = 0; i < 9; i++) H[i] = 0;
+    g_u2h_cnt[0] = g_u2h_cnt[1] = 0;
     S = exp_ransacHcustomLAF(&c, u, ua, ub, n, th, laf ? laf_coef : 0.0, conf, max_iters, H, mask, 0, error_type, sym_th, seed, stats);
+    if (stats) { stats[DG_ST_U2H_4PT] = g_u2h_cnt[0]; stats[DG_ST_U2H_SHORT] = g_u2h_cnt[1]; }
     free(u); free(ua); free(ub); free(c.ht);
     return (int)S.I;
 }
@@ -1595,7 +1604,9 @@ int dg_oracle_ransacH2el(const double *u10, int n, double th, double conf, int m
     if (n < 2) return -1;
     memset(&c, 0, sizeof c);
     for (i = 0; i < 9; i++) H[i] = 0;
+    g_u2h_cnt[0] = g_u2h_cnt[1] = 0;
     S = ransacH2el(&c, u10, n, th, conf, max_iters, H, mask, do_lo, inl_limit, seed, stats);
+    if (stats) { stats[DG_ST_U2H_4PT] = g_u2h_cnt[0]; stats[DG_ST_U2H_SHORT] = g_u2h_cnt[1]; }
     free(c.ht);
     return (int)S.I;
 }

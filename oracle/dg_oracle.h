@@ -14,7 +14,10 @@ typedef struct {
 
 /* stats[] layout shared with the product's C-ABI (include/mi_degensac.h) */
 enum { DG_ST_SAMPLES = 0, DG_ST_LO_RUNS, DG_ST_REJECTED, DG_ST_I, DG_ST_MODELS, DG_ST_DEGEN,
-       DG_ST_IH, DG_ST_BEST_SAMPLE, DG_ST_COUNT = 16 };
+       DG_ST_IH, DG_ST_BEST_SAMPLE,
+       /* oracle only (the product keeps device ticks in these two slots): u2h calls of the driver with len == 4 and with
+        * 5 <= len <= 10, i.e. the 4-point null-space fit and the short-list least squares */
+       DG_ST_U2H_4PT = 12, DG_ST_U2H_SHORT = 13, DG_ST_COUNT = 16 };
 
 #ifdef __cplusplus
 extern "C" {

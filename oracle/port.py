@@ -59,7 +59,8 @@ def find_fundamental(pts1, pts2, px_th=0.5, conf=0.9999, max_iters=100000, error
                                  mask.ctypes.data_as(C.POINTER(C.c_ubyte)), ip(st))
     stats = dict(samples=int(st[0]), lo_runs=int(st[1]), rejected=int(st[2]), I=int(st[3]), models=int(st[4]),
                  degen=int(st[5]), Ih=int(st[6]), best_sample=int(st[7]), full_passes=int(st[8]),
-                 ex_passes=int(st[9]), hds_passes=int(st[10]), fds_direct=int(st[11]))
+                 ex_passes=int(st[9]), hds_passes=int(st[10]), fds_direct=int(st[11]),
+                 u2h_4pt=int(st[12]), u2h_short=int(st[13]))
     return F.reshape(3, 3), mask.astype(bool), stats
 
 
@@ -72,7 +73,7 @@ def find_homography(pts1, pts2, px_th=1.0, conf=0.999, max_iters=50000, error_ty
     l.dg_oracle_find_homography(dp(a), dp(b), n, dim, px_th, conf, max_iters, error_type, int(sym_check),
                                 max(0.0, laf_coef), seed, dp(H), mask.ctypes.data_as(C.POINTER(C.c_ubyte)), ip(st))
     stats = dict(samples=int(st[0]), lo_runs=int(st[1]), rejected=int(st[2]), I=int(st[3]), models=int(st[4]),
-                 best_sample=int(st[7]))
+                 best_sample=int(st[7]), u2h_4pt=int(st[12]), u2h_short=int(st[13]))
     return H.reshape(3, 3), mask.astype(bool), stats
 
 
@@ -84,4 +85,5 @@ def ransacH2el(u10, th=4.0, conf=0.99, max_iters=10000, do_lo=True, inl_limit=0,
     H = np.zeros(9); mask = np.zeros(n, np.uint8); st = np.zeros(ST_COUNT, np.int32)
     l.dg_oracle_ransacH2el(dp(u), n, C.c_double(th), C.c_double(conf), int(max_iters), int(bool(do_lo)), int(inl_limit), C.c_uint(seed),
                            dp(H), mask.ctypes.data_as(C.POINTER(C.c_ubyte)), ip(st))
-    return H.reshape(3, 3), mask.astype(bool), dict(samples=int(st[0]), lo_runs=int(st[1]), I=int(st[3]), models=int(st[4]))
+    return H.reshape(3, 3), mask.astype(bool), dict(samples=int(st[0]), lo_runs=int(st[1]), I=int(st[3]), models=int(st[4]),
+                                                    u2h_4pt=int(st[12]), u2h_short=int(st[13]))

@@ -294,6 +294,17 @@ def test_two_eigenproblems_per_wave_equal_one_per_wave():
         o1, f1 = run(3, M); o2, f2 = run(5, M)
         assert np.array_equal(f1, f2), trial
         assert np.array_equal(o1, o2, equal_nan=True), (trial, np.flatnonzero((o1 != o2).any(axis=1))[:10])
+    # op 5 against the CPU oracle directly, as the test above does for op 3 (not only through op 3)
+    from oracle import port
+    O = port.lib(); out, flag = run(5, A); bad = []
+    for t in range(N):
+        a = A[t].copy(); w = np.zeros(9)
+        info = O.dg_oracle_eig_sym(dp(a), dp(w), 9)
+        ok = info == flag[t] and out[t, 0] == w[0] and np.array_equal(out[t, 9:18], a.ravel()[:9]) \
+            and np.array_equal(np.sort(out[t, :9]), w)
+        if not ok:
+            bad.append(t)
+    assert not bad, (len(bad), bad[:10], flag[bad[:10]])
 
 
 def test_screening_counts_are_supersets_of_the_exact_band():

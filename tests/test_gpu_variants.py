@@ -191,7 +191,12 @@ def test_sequential_pool_stage_fallback_matches_goldens():
     for path in gu.fixtures("F")[:6] + gu.fixtures("H")[:6]:
         g = gu.load(path); kw = g["call"]
         if g["n"] <= 10:
-            continue
+            # the fixture's outputs came from the uninitialised memory of the reference's 4-point u2h path (Htools.c:108-114) and stay
+            # unused: the restatement, which zero-fills there as the device does, stands in for them on the fixture's inputs and call
+            from oracle import port
+            Mo, mo, so = port.find_homography(g["p1"], g["p2"], kw.get("px_th", 1.0), kw.get("conf", 0.999), kw.get("max_iters", 50000),
+                                              kw.get("error_type", 0), kw.get("sym_check", True), kw.get("laf_coef", 0.0), seed=g["seed"])
+            g = dict(g, samples=so["samples"], lo_runs=so["lo_runs"], model=np.asarray(Mo), mask=mo)
         for variant in (512, 256, 128):
             t = VARIANT[variant] | _lib.TUNE_SEQ_POOL
             if g["kind"] == "F":

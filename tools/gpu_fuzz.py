@@ -154,7 +154,7 @@ def run_batches(N, rng_seed):
             et = int(rng.integers(0, 5)); th = float(rng.choice([1.0, 2.0, 4.0])); lc = 3.0 if laf else 0.0
             fl = int(rng.choice([0, _lib.FLAG_NO_HJOB]))
             for i in range(P):
-                p1, p2, _, _ = syn.homography_pairs(max(ns[i], 12), float(rng.uniform(0.15, 0.8)), float(rng.choice([0.2, 0.5, 1.0])), seed=100000 + 1000 * case + i, laf=laf)
+                p1, p2, _, _ = syn.homography_pairs(ns[i], float(rng.uniform(0.15, 0.8)), float(rng.choice([0.2, 0.5, 1.0])), seed=100000 + 1000 * case + i, laf=laf)
                 A.append(p1); B.append(p2)
             M, masks = api._batch("H", A, B, th, 0.999, mi, et, sym, lc, True, seeds, 0, tn, fl); st = pd.last_stats()
             ref = [port.find_homography(A[i], B[i], th, 0.999, mi, et, sym, lc, seed=seeds[i]) for i in range(P)]
@@ -204,8 +204,7 @@ def run_edges(N, rng_seed):
         kdup = int(rng.integers(2, max(3, n // 2))); lafc = float(rng.choice([1.0, 3.0]))
         if only is not None and case not in only: continue
         if isF: p1, p2, _, _ = syn.two_view_fundamental(n, ir, sg, seed=case, plane_fraction=pf, laf=laf)
-        else:
-            n = max(n, 11)                                   # <= 10: the reference's 4-point u2h path reads uninitialised memory
+        else:                                                # n <= 10 takes u2h's 4-point path: the port zero-fills there as the device does
             p1, p2, _, _ = syn.homography_pairs(n, ir, sg, seed=case, laf=laf)
         if quant: p1[:, :2] = np.round(p1[:, :2]); p2[:, :2] = np.round(p2[:, :2])
         if dup: p1[1:kdup] = p1[0]; p2[1:kdup] = p2[0]

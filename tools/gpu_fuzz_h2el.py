@@ -20,8 +20,6 @@ for b in range(N):
     conf = float(rng.choice([0.95, 0.99, 0.999]))
     H, m = pd.ransacH2el_batch(U, th, conf, mi, do_lo, lim, seeds=seeds, raw=True); st = pd.last_stats()
     for p in range(P):
-        if lim and U[p].shape[0] <= 14:
-            continue                                              # 4-point u2h of the reference reads uninitialised memory (Htools.c:108-114)
         Ho, mo, so = port.ransacH2el(U[p], th, conf, mi, do_lo, lim, seeds[p]); tot += 1
         a = np.asarray(H[p]).ravel(); o = np.asarray(Ho).ravel()
         rel = np.linalg.norm(a - o) / max(np.linalg.norm(o), 1e-300) if np.abs(o).sum() else float(np.abs(a).sum())
