@@ -373,6 +373,25 @@ const char *mi_degensac_match_last_error(void);
 int mi_degensac_match_knn2_batch_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
                                      const int64_t *offsets2_host, int n_pairs, int dim, int device, void *stream,
                                      int32_t *d_idx, float *d_dist);
+/* The batched 2-NN with the first-geometrically-inconsistent-neighbour rule (FGINN, Mishkin et al.) for slot 1.  Detectors emit
+ * several keypoints for one image structure (two orientations, neighbouring scales) with nearly equal descriptors; the second
+ * neighbour of a correct match is then its twin and the ratio test fails.  d_kp2: [offsets2_host[K], kp_dim] float64 keypoints of
+ * the train rows, kp_dim 2 or 6 (only x, y are read).  Per query of a pair, with r = spatial_th:
+ *   slot 0 = (i0, d0) of mi_degensac_match_knn2_batch_dev, unchanged (non-finite rule and tie order included);
+ *   a train row t competes for slot 1 iff t != i0 and dx dx + dy dy >= r r, dx = x2[t] - x2[i0], dy = y2[t] - y2[i0], in fp64 in
+ *            that order without contraction; a NaN makes the comparison false, so a NaN anchor keypoint leaves no competitor (infinite
+ *            coordinates follow the same arithmetic: inf - inf is NaN, inf - finite squares to inf and competes);
+ *   slot 1 = the nearest competing row in the matcher's (distance, index) order, its distance bits those of the dense matcher;
+ *            -1 / inf when nothing competes or i0 = -1.
+ * r = 0 with finite keypoints is mi_degensac_match_knn2_batch_dev bit for bit.  The ratio test on the result is unchanged
+ * (i1 >= 0 && d0 < ratio d1: a query whose every other train row lies inside the radius is not kept); so is the mutual check (the
+ * plain reverse nearest neighbour).  Cost: the plain 2-NN, a pass over its output, and a rescan of the queries whose plain second
+ * neighbour lies inside the radius.  Asynchronous on `stream`, no host synchronisation.  Errors: as
+ * mi_degensac_match_knn2_batch_dev, and MI_DEGENSAC_EINVAL for kp_dim not 2 / 6 or a spatial_th that is negative or not finite
+ * (before a device is looked for); n_pairs == 0 returns 0. */
+int mi_degensac_match_fginn_knn2_batch_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
+                                           const int64_t *offsets2_host, int n_pairs, int dim, const double *d_kp2, int kp_dim,
+                                           double spatial_th, int device, void *stream, int32_t *d_idx, float *d_dist);
 typedef struct mi_degensac_match_params {
     int32_t norm;          /* MI_DEGENSAC_NORM_L2 (float32 rows) / _HAMMING (uint8 rows, dim % 4 == 0) / _L2_U8 (uint8 rows,
                               dim % 4 == 0, dim <= 256)                                                                 */
@@ -381,7 +400,11 @@ typedef struct mi_degensac_match_params {
     int32_t mutual;        /* bool: also require that the query is the nearest neighbour of its nearest train row         */
     int32_t struct_size;   /* sizeof(mi_degensac_match_params) of the caller's header (0 = this layout); fields added later
                               are only read when struct_size covers them                                                  */
-    int32_t reserved;
+    int32_t second_nn;     /* where dist[1] of the ratio test comes from: 0 = the second nearest train row, 1 = FGINN, the nearest
+                              train row whose keypoint lies at least spatial_th from the nearest neighbour's (see
+                              mi_degensac_match_fginn_knn2_batch_dev).  Read only together with spatial_th                   */
+    double  spatial_th;    /* FGINN radius in pixels, finite and >= 0.  Added after the first layout: a caller whose struct_size
+                              is 0 or does not cover it gets second_nn = 0 whatever that field holds                        */
 } mi_degensac_match_params;
 /* Match and verify: per pair the 2-NN search, the ratio test (+ mutual check) of mi_degensac_match, then the estimator of
  * mi_degensac_find_fundamental_batch_dev (homography = 0) or _homography_batch_dev (homography = 1) on the pair's tentatives in
@@ -391,12 +414,15 @@ typedef struct mi_degensac_match_params {
  * pairs of the batch).  Outputs per pair: d_model [K*9] (the driver's form, as the batch entry points), d_stats [K*16] or NULL;
  * per query row of desc1: d_match = train row local to the pair or -1 when the row is not a tentative, d_inlier = 1 when it is a
  * tentative and an inlier of the pair's model.  h_counts (host, [K], nullable): tentatives per pair.
+ * mp->second_nn = 1 (with struct_size covering spatial_th) switches the ratio test to FGINN at mp->spatial_th on this call's d_kp2;
+ * the guided entry points ignore both fields.
  * Synchronisation: the matching is enqueued on `stream`, then the call reads the K tentative counts back (ONE device-to-host copy
  * followed by a wait for `stream`: the only synchronisation; the estimator's launch is sized from them on the host), enqueues the
  * gather, the estimator and the scatter and returns.  Discarded pairs (hand-over time-out) carry bit 10 of stats[15] as with the
  * other *_dev entry points.  Errors: MI_DEGENSAC_EINVAL for a bad norm / dim / kp_dim, uint8 rows with dim % 4 != 0
  * (or dim > 256 under L2_U8), decreasing offsets,
- * a ratio that is not finite and > 0, bad params; n_pairs == 0 returns 0. */
+ * a ratio that is not finite and > 0, a second_nn other than 0 / 1 or a spatial_th that is negative or not finite (when struct_size
+ * covers them), bad params; n_pairs == 0 returns 0. */
 int mi_degensac_match_verify_batch_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
                                        const int64_t *offsets1_host, const int64_t *offsets2_host, const double *d_kp1, const double *d_kp2,
                                        int kp_dim, int n_pairs, const mi_degensac_params *prm, const uint32_t *d_seeds, int device, void *stream,

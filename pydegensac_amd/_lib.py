@@ -54,12 +54,14 @@ class H2elParams(C.Structure):
 
 
 class MatchParams(C.Structure):
-    """mi_degensac_match_params (include/mi_degensac.h) of the batched match-and-verify entry points"""
+    """mi_degensac_match_params (include/mi_degensac.h) of the batched match-and-verify entry points.  fginn_th: None = the plain
+    second neighbour, a number = the FGINN ratio test at that radius (second_nn = 1, spatial_th)"""
     _fields_ = [("norm", C.c_int32), ("dim", C.c_int32), ("ratio", C.c_float), ("mutual", C.c_int32), ("struct_size", C.c_int32),
-                ("reserved", C.c_int32)]
+                ("second_nn", C.c_int32), ("spatial_th", C.c_double)]
 
-    def __init__(self, norm=0, dim=0, ratio=0.9, mutual=False):
-        super().__init__(int(norm), int(dim), float(ratio), int(bool(mutual)), C.sizeof(MatchParams), 0)
+    def __init__(self, norm=0, dim=0, ratio=0.9, mutual=False, fginn_th=None):
+        super().__init__(int(norm), int(dim), float(ratio), int(bool(mutual)), C.sizeof(MatchParams), int(fginn_th is not None),
+                         0.0 if fginn_th is None else float(fginn_th))
 
 
 class GuideParams(C.Structure):
@@ -175,6 +177,10 @@ def lib():
         l.mi_degensac_match_knn2_batch_dev.restype = C.c_int
         l.mi_degensac_match_knn2_batch_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, lp, lp, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                        C.c_void_p]
+        if hasattr(l, "mi_degensac_match_fginn_knn2_batch_dev"):          # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            l.mi_degensac_match_fginn_knn2_batch_dev.restype = C.c_int
+            l.mi_degensac_match_fginn_knn2_batch_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, lp, lp, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                                 C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         mpp = C.POINTER(MatchParams)
         l.mi_degensac_match_verify_batch_dev.restype = C.c_int
         l.mi_degensac_match_verify_batch_dev.argtypes = [C.c_int, mpp, C.c_void_p, C.c_void_p, lp, lp, C.c_void_p, C.c_void_p, C.c_int, C.c_int, pp,

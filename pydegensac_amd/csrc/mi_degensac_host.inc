@@ -1073,6 +1073,7 @@ static int mv_check(int homography, const mi_degensac_match_params *mp, const in
     if (const char *e = mt_norm_dim_error(mp->norm, mp->dim)) { set_err("%s", e); return MI_DEGENSAC_EINVAL; }
     if (!(isfinite(mp->ratio) && mp->ratio > 0.f)) { set_err("ratio must be finite and > 0"); return MI_DEGENSAC_EINVAL; }
     if (kp_dim != 2 && kp_dim != 6) { set_err("keypoint rows must be [n,2] or [n,6]"); return MI_DEGENSAC_EINVAL; }
+    { int fg; double r; if (const char *e = mt_second_nn(mp, &fg, &r)) { set_err("%s", e); return MI_DEGENSAC_EINVAL; } }
     if (n_pairs < 0) { set_err("n_pairs < 0"); return MI_DEGENSAC_EINVAL; }
     if (n_pairs == 0) return 0;
     for (const int64_t *o : {off1, off2}) {
@@ -1126,6 +1127,8 @@ static int match_verify_dev(int homography, const mi_degensac_match_params *mp, 
     uint8_t *keep = (uint8_t *)(A + a_keep);
     rc = match_rc(mt_batch_upload(device, s, o32.data(), o32.size() * 4, A)); if (rc) return rc;
     rc = match_rc(mt_batch_knn2(mp->norm, words, q1, q2, o1.data(), o2.data(), K, device, s, idx, dist)); if (rc) return rc;
+    int fginn; double fginn_r; (void)mt_second_nn(mp, &fginn, &fginn_r);
+    if (fginn) { rc = match_rc(mt_batch_fginn(mp->norm, words, q1, q2, kp2, kd, o1.data(), o2.data(), K, fginn_r, device, s, idx, dist)); if (rc) return rc; }
     if (mutual) { rc = match_rc(mt_batch_knn2(mp->norm, words, q2, q1, o2.data(), o1.data(), K, device, s, bidx, bdist)); if (rc) return rc; }
     rc = match_rc(mt_batch_filter_rank(idx, dist, d_o1, d_o2, K, mp->ratio, bidx, s, keep, rank, cnt)); if (rc) return rc;
 

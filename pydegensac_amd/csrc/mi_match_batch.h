@@ -7,6 +7,7 @@
 #ifndef MI_MATCH_BATCH_H
 #define MI_MATCH_BATCH_H
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "../../include/mi_degensac.h"
 
@@ -41,6 +42,21 @@ static inline const char *mt_norm_dim_error(int norm, int dim)
 static inline int mt_row_words(int norm, int dim) { return norm == MI_DEGENSAC_NORM_L2 ? dim : dim / 4; }
 static inline size_t mt_row_bytes(int norm, int dim) { return (size_t)dim * (norm == MI_DEGENSAC_NORM_L2 ? 4 : 1); }
 
+/* what is wrong with an FGINN radius, or null: finite and >= 0 */
+static inline const char *mt_spatial_th_error(double r) { return r >= 0 && r <= 1.7976931348623157e308 ? nullptr : "spatial_th must be finite and >= 0"; }
+/* the second-neighbour rule of a match_params: *fginn = the mode (0 plain, 1 FGINN at radius *r).  A caller with the layout before
+ * spatial_th (struct_size 0, or one that does not cover the field) gets the plain rule whatever its last field holds.  Returns what
+ * is wrong, or null. */
+static inline const char *mt_second_nn(const mi_degensac_match_params *mp, int *fginn, double *r)
+{
+    *fginn = 0; *r = 0.0;
+    if ((size_t)mp->struct_size < offsetof(mi_degensac_match_params, spatial_th) + sizeof(double)) return nullptr;
+    if (mp->second_nn != 0 && mp->second_nn != 1) return "second_nn must be 0 (plain) or 1 (FGINN)";
+    if (mp->second_nn == 0) return nullptr;
+    *fginn = 1; *r = mp->spatial_th;
+    return mt_spatial_th_error(mp->spatial_th);
+}
+
 /* the message mi_degensac_match_last_error() returns for the calling thread */
 MT_HIDDEN void mt_set_error(const char *msg);
 
@@ -50,6 +66,10 @@ MT_HIDDEN int mt_batch_upload(int device, hipStream_t s, const void *h, size_t b
  * indices local to the pair.  words = 32-bit words per descriptor row. */
 MT_HIDDEN int mt_batch_knn2(int norm, int words, const void *dq, const void *dt, const int64_t *oq, const int64_t *ot, int n_pairs, int device,
                             hipStream_t s, int32_t *idx, float *dist);
+/* FGINN (mi_fginn.h): after mt_batch_knn2 with the same arguments on s, slot 1 of idx / dist becomes the nearest train row whose
+ * keypoint (kt: [rows, kd] of the train side) lies at least r from the keypoint of slot 0; no host synchronisation */
+MT_HIDDEN int mt_batch_fginn(int norm, int words, const void *dq, const void *dt, const double *kt, int kd, const int64_t *oq, const int64_t *ot,
+                             int n_pairs, double r, int device, hipStream_t s, int32_t *idx, float *dist);
 /* ratio test (+ mutual check when d_back is set) and the rank of every kept query among its pair's kept queries; one
  * workgroup per pair.  d_off1 / d_off2: [K + 1] relative int32 row offsets on the device. */
 MT_HIDDEN int mt_batch_filter_rank(const int32_t *d_idx, const float *d_dist, const int32_t *d_off1, const int32_t *d_off2, int n_pairs, float ratio,

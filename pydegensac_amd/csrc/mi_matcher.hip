@@ -32,32 +32,68 @@
 /* mt_best / mt_push (the running top-2 and its tie rule): mi_match_batch.h */
 #include "mi_matcher_u8.h"
 
+/* acc + the dot product of the four unsigned bytes of a and b */
+__device__ __forceinline__ unsigned mt_udot4(uint32_t a, uint32_t b, unsigned acc) { return __builtin_amdgcn_udot4(a, b, acc, false); }
+
+/* What the FGINN rescan (mi_fginn.h) adds to the tile body below.  mf_ctx: the pair's needy list (global query rows at the list
+ * positions q0 .. q_end - 1), the plain 2-NN's idx (slot 0 is the anchor), the train keypoints and r * r.  mf_lds: the tile's train
+ * keypoints next to the descriptor tile (16 bytes per row), every query's anchor keypoint and row, read once per workgroup. */
+struct mf_ctx { const int32_t *list, *idx; const double *kt; int kd; double rr; };
+struct mf_lds { double2 tk[MT_T], ak[MT_Q]; int ai[MT_Q], row[MT_Q]; };
+
 /* One workgroup's tile: queries q0 .. q_end - 1 (at most 64) of q against train rows t_lo .. t_hi - 1 of t, candidates
  * indexed from t_base (0 for a single pair, the pair's first train row in a batch).  NORM: 0 = L2 over float words,
  * 1 = Hamming over 32-bit words of packed bytes; q, t: [n, words] row-major.  Returns true in the threads tid < 64 whose
- * query exists, with that query's merged top-2 (squared distances for L2) in m. */
-template <int NORM>
+ * query exists, with that query's merged top-2 (squared distances for L2) in m.
+ * FG (the FGINN rescan): q0 .. q_end - 1 are positions of fg->list, whose entries are the query rows, and a train row is pushed only
+ * when it competes with the query's anchor i0 = fg->idx[row][0]: t != i0 and dx dx + dy dy >= rr in fp64 (false for a NaN).  NORM 2
+ * (uint8 rows under L2, FG only: the dense form is mu_knn2_tile) forms the exact integer S = |a|^2 + |b|^2 - 2 a.b with unsigned byte
+ * dot products on the vector unit. */
+template <int NORM, bool FG = false>
 __device__ __forceinline__ bool mt_knn2_tile(const uint32_t *q, int q0, int q_end, const uint32_t *t, int t_lo, int t_hi, int t_base, int words,
-                                             uint32_t (&qs)[MT_DC][MT_Q + 1], uint32_t (&ts)[MT_DC][MT_T + 1], mt_best (&merge)[MT_Q][16], mt_best &m)
+                                             uint32_t (&qs)[MT_DC][MT_Q + 1], uint32_t (&ts)[MT_DC][MT_T + 1], mt_best (&merge)[MT_Q][16], mt_best &m,
+                                             const mf_ctx *fg = nullptr, mf_lds *fl = nullptr)
 {
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     mt_best best[4];
 #pragma unroll
     for (int a = 0; a < 4; a++) { best[a].d0 = best[a].d1 = __builtin_inff(); best[a].i0 = best[a].i1 = -1; }
-    for (int t0 = t_lo; t0 < t_hi; t0 += MT_T) {
-        float acc[4][4]; unsigned hacc[4][4];
+    double ax[4], ay[4]; int ai[4];
+    if constexpr (FG) {
+        if (tid < MT_Q) {
+            const bool in = q0 + tid < q_end;
+            const int row = in ? fg->list[q0 + tid] : 0, i0 = in ? fg->idx[2 * (size_t)row] : -1;
+            const double *k = fg->kt + (size_t)(t_base + (i0 >= 0 ? i0 : 0)) * fg->kd;
+            fl->row[tid] = row; fl->ai[tid] = i0;
+            fl->ak[tid] = i0 >= 0 ? make_double2(k[0], k[1]) : make_double2(__builtin_nan(""), __builtin_nan(""));
+        }
+        __syncthreads();
 #pragma unroll
-        for (int a = 0; a < 4; a++)
+        for (int a = 0; a < 4; a++) { const double2 k = fl->ak[4 * ty + a]; ax[a] = k.x; ay[a] = k.y; ai[a] = fl->ai[4 * ty + a]; }
+    }
+    for (int t0 = t_lo; t0 < t_hi; t0 += MT_T) {
+        float acc[4][4]; unsigned hacc[4][4], hq[4], ht[4];
+#pragma unroll
+        for (int a = 0; a < 4; a++) {
+            hq[a] = ht[a] = 0u;
 #pragma unroll
             for (int b = 0; b < 4; b++) { acc[a][b] = 0.f; hacc[a][b] = 0u; }
+        }
         for (int w0 = 0; w0 < words; w0 += MT_DC) {
             __syncthreads();
             /* stage both tiles dimension-major: thread r loads row (r / 4), a quarter of the chunk's words, coalesced per row */
             for (int e = tid; e < MT_Q * MT_DC; e += 256) {
                 const int r = e / MT_DC, w = e - r * MT_DC;
                 const bool okq = q0 + r < q_end && w0 + w < words, okt = t0 + r < t_hi && w0 + w < words;
-                qs[w][r] = okq ? q[(size_t)(q0 + r) * words + w0 + w] : 0u;
+                const int qr = FG ? fl->row[r] : q0 + r;
+                qs[w][r] = okq ? q[(size_t)qr * words + w0 + w] : 0u;
                 ts[w][r] = okt ? t[(size_t)(t0 + r) * words + w0 + w] : 0u;
+            }
+            if constexpr (FG) {
+                if (w0 == 0 && tid < MT_T) {
+                    const double *k = fg->kt + (size_t)(t0 + tid < t_hi ? t0 + tid : t_lo) * fg->kd;
+                    fl->tk[tid] = make_double2(k[0], k[1]);
+                }
             }
             __syncthreads();
             const int wn = words - w0 < MT_DC ? words - w0 : MT_DC;
@@ -67,21 +103,36 @@ __device__ __forceinline__ bool mt_knn2_tile(const uint32_t *q, int q0, int q_en
                 for (int a = 0; a < 4; a++) qa[a] = qs[w][4 * ty + a];
 #pragma unroll
                 for (int b = 0; b < 4; b++) tb[b] = ts[w][tx + 16 * b];
+                if constexpr (NORM == 2) {
+#pragma unroll
+                    for (int a = 0; a < 4; a++) { hq[a] = mt_udot4(qa[a], qa[a], hq[a]); ht[a] = mt_udot4(tb[a], tb[a], ht[a]); }
+                }
 #pragma unroll
                 for (int a = 0; a < 4; a++)
 #pragma unroll
                     for (int b = 0; b < 4; b++) {
                         if (NORM == 0) { const float df = __uint_as_float(qa[a]) - __uint_as_float(tb[b]); acc[a][b] = acc[a][b] + df * df; }
-                        else hacc[a][b] += (unsigned)__popc(qa[a] ^ tb[b]);
+                        else if (NORM == 1) hacc[a][b] += (unsigned)__popc(qa[a] ^ tb[b]);
+                        else hacc[a][b] = mt_udot4(qa[a], tb[b], hacc[a][b]);
                     }
             }
+        }
+        double2 tk[4];
+        if constexpr (FG) {
+#pragma unroll
+            for (int b = 0; b < 4; b++) tk[b] = fl->tk[tx + 16 * b];
         }
 #pragma unroll
         for (int a = 0; a < 4; a++)
 #pragma unroll
             for (int b = 0; b < 4; b++) {
                 const int ti = t0 + tx + 16 * b;
-                if (ti < t_hi) mt_push(best[a], NORM == 0 ? acc[a][b] : (float)hacc[a][b], ti - t_base);
+                bool ok = ti < t_hi;
+                if constexpr (FG) {
+                    const double dx = tk[b].x - ax[a], dy = tk[b].y - ay[a];
+                    ok = ok && ti - t_base != ai[a] && dx * dx + dy * dy >= fg->rr;
+                }
+                if (ok) mt_push(best[a], NORM == 0 ? acc[a][b] : NORM == 1 ? (float)hacc[a][b] : (float)(hq[a] + ht[b] - 2u * hacc[a][b]), ti - t_base);
             }
     }
     /* the 16 threads of a query row merge their candidates (lane order does not matter: mt_push orders by (d, i)) */
@@ -431,6 +482,16 @@ int mt_batch_upload(int device, hipStream_t s, const void *h, size_t bytes, void
     return 0;
 }
 
+/* the train-split rule of the batched launches: (rows per split, splits) from the batch's query tiles and its largest train set */
+static void mt_batch_split(int qtiles, int max_n2, int device, int *t_chunk, int *n_splits)
+{
+    const int ttiles = max_n2 > 0 ? (max_n2 + MT_T - 1) / MT_T : 1, cus = mt_cus(device);
+    int splits = qtiles >= 2 * cus ? 1 : (2 * cus + qtiles - 1) / qtiles;
+    if (splits > ttiles) splits = ttiles; if (splits < 1) splits = 1; if (splits > 256) splits = 256;
+    *t_chunk = max_n2 > 0 ? ((ttiles + splits - 1) / splits) * MT_T : MT_T;
+    *n_splits = max_n2 > 0 ? (max_n2 + *t_chunk - 1) / *t_chunk : 1;
+}
+
 /* One launch over the 64-query tiles of every pair.  The train set is split over blockIdx.y only when the batch's tiles do not
  * cover the CUs about twice (as in mi_degensac_match_knn2_dev, with the largest pair's train set deciding the chunk). */
 int mt_batch_knn2(int norm, int words, const void *dq, const void *dt, const int64_t *oq, const int64_t *ot, int n_pairs, int device, hipStream_t s,
@@ -445,11 +506,8 @@ int mt_batch_knn2(int norm, int words, const void *dq, const void *dt, const int
         if (t_e - t_b > max_n2) max_n2 = t_e - t_b;
         for (int q0 = (int)oq[p]; q0 < q_end; q0 += MT_Q) tiles.push_back(make_int4(q0, q_end, t_b, t_e));
     }
-    const int qtiles = (int)tiles.size(), ttiles = max_n2 > 0 ? (max_n2 + MT_T - 1) / MT_T : 1, cus = mt_cus(device);
-    int splits = qtiles >= 2 * cus ? 1 : (2 * cus + qtiles - 1) / qtiles;
-    if (splits > ttiles) splits = ttiles; if (splits < 1) splits = 1; if (splits > 256) splits = 256;
-    const int t_chunk = max_n2 > 0 ? ((ttiles + splits - 1) / splits) * MT_T : MT_T;
-    splits = max_n2 > 0 ? (max_n2 + t_chunk - 1) / t_chunk : 1;
+    const int qtiles = (int)tiles.size();
+    int t_chunk, splits; mt_batch_split(qtiles, max_n2, device, &t_chunk, &splits);
     const size_t b_tiles = ((size_t)qtiles * sizeof(int4) + 255) / 256 * 256, b_part = splits > 1 ? (size_t)splits * n_rows * sizeof(mt_best) : 0;
     char *buf = nullptr;
     MTCHK(hipMallocAsync((void **)&buf, b_tiles + b_part, s));
@@ -525,3 +583,5 @@ extern "C" int mi_degensac_match_knn2_batch_dev(int norm, const void *d_desc1, c
     return mt_batch_knn2(norm, words, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words,
                          (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words, o1.data(), o2.data(), n_pairs, device, (hipStream_t)stream, d_idx + 2 * offsets1_host[0], d_dist + 2 * offsets1_host[0]);
 }
+
+#include "mi_fginn.h"

@@ -78,6 +78,33 @@ def match_snn(desc1, desc2, ratio=0.9, mutual=False, norm=None, device=0):
     return sel.astype(np.int64), idx[sel, 0].astype(np.int64), dist[sel, 0]
 
 
+def match_fginn(desc1, desc2, kps2, ratio=0.9, spatial_th=10.0, mutual=False, norm=None, device=0):
+    """match_snn with the FGINN ratio test (first geometrically inconsistent neighbour, Mishkin et al.): the second distance of
+    `m.distance < ratio * n.distance` comes from the nearest row of desc2 whose keypoint (kps2 [n2, >= 2]: x, y, ...) lies at least
+    spatial_th pixels from the nearest neighbour's keypoint, so that the twin keypoints a detector emits for one structure (a second
+    orientation, a neighbouring scale) do not veto a correct match.  A query whose every other train row lies inside the radius is
+    not kept; the mutual check is the plain one.  Returns (query indices, train indices, distances) in query order."""
+    code, a, b = _prep(desc1, desc2, norm)
+    r = check_fginn_th(spatial_th, "spatial_th")
+    k2 = np.asarray(kps2, np.float64)
+    if k2.ndim != 2 or k2.shape[1] < 2 or k2.shape[0] != b.shape[0]:
+        raise ValueError("kps2 should hold one keypoint row (x, y, ...) per row of desc2")
+    k2 = np.ascontiguousarray(k2[:, :2])
+    import torch
+    from . import tensor_api
+    if not torch.cuda.is_available():
+        raise _lib.MiDegensacError("no HIP device: this library has no CPU path")
+    dev = torch.device("cuda", int(device))
+    name = {NORM_L2: "l2", NORM_HAMMING: "hamming", NORM_L2_U8: "l2_u8"}[code]
+    ta, tb = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
+    idx, dist = tensor_api.knn_match_fginn_batch_tensors(ta, tb, torch.from_numpy(k2).to(dev), [a.shape[0]], [b.shape[0]], r, name)
+    back = tensor_api.knn_match_tensors(tb, ta, name)[0] if mutual and b.shape[0] > 0 else None
+    keep = tensor_api.match_filter_tensors(idx, dist, ratio, back)
+    idx = idx.cpu().numpy(); dist = dist.cpu().numpy()
+    sel = np.flatnonzero(keep.cpu().numpy())
+    return sel.astype(np.int64), idx[sel, 0].astype(np.int64), dist[sel, 0]
+
+
 def tentative_points(kps1, kps2, desc1, desc2, ratio=0.9, mutual=False, norm=None, device=0):
     """Matched coordinates ready for findHomography / findFundamentalMatrix: kps are [n, >=2] arrays (x, y, ...)"""
     q, t, _ = match_snn(desc1, desc2, ratio, mutual, norm, device)
@@ -107,9 +134,13 @@ def _dtype_name(dt):
     return s[6:] if s.startswith("torch.") else np.dtype(dt).name
 
 
-def check_match_verify_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype, counts1, counts2):
+def check_match_verify_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype, counts1, counts2,
+                            fginn_th=None):
     """The argument checks of the batched match-and-verify calls, on shapes and dtype names only (numpy or torch).  Returns
-    (norm code, "xy" for float64 rows [n, 2] / [n, 6] or "kpts" for float32 keypoints [n, 4], offsets1, offsets2); raises ValueError."""
+    (norm code, "xy" for float64 rows [n, 2] / [n, 6] or "kpts" for float32 keypoints [n, 4], offsets1, offsets2); raises ValueError.
+    fginn_th: None, or the FGINN radius (finite and >= 0)."""
+    if fginn_th is not None:
+        check_fginn_th(fginn_th)
     if model not in ("F", "H"):
         raise ValueError("model should be 'F' or 'H'")
     try:
@@ -160,6 +191,17 @@ def check_match_verify_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2
     if o1[-1] != d1_shape[0] or o2[-1] != d2_shape[0]:
         raise ValueError("counts do not add up to the number of descriptor rows")
     return _NORMS[norm], kinds[0][0], o1, o2
+
+
+def check_fginn_th(fginn_th, name="fginn_th"):
+    """the FGINN radius of the matcher calls: a finite number >= 0; raises ValueError"""
+    try:
+        r = float(fginn_th)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} should be a number")
+    if not (np.isfinite(r) and r >= 0):
+        raise ValueError(f"{name} should be finite and >= 0")
+    return r
 
 
 def estimator_params(model, px_th=None, conf=None, max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
@@ -283,7 +325,7 @@ def guided_match(kps1, kps2, desc1, desc2, M, model="F", ratio=0.9, mutual=False
 
 def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
                            max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
-                           enable_degeneracy_check=True, seeds=None, norm=None, device=0, guided=False):
+                           enable_degeneracy_check=True, seeds=None, norm=None, device=0, guided=False, fginn_th=None):
     """K image pairs from descriptors and keypoints to models in one call: per pair the 2-NN ratio test of match_snn (optionally
     mutual), then findFundamentalMatrix (model "F") or findHomography ("H") on its tentatives, all pairs in one launch.  kps are
     float64 [n, 2] / [n, 6] rows or float32 [n, 4] keypoints (x, y, size, angle -> LAF rows as kpts_to_xyA); descriptors float32
@@ -293,6 +335,8 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
     the train row of query i or -1, inlier_p[i] = query i is a tentative and an inlier; H is the user-facing inv(H_c^T).
     guided=True runs guided_match_batch after the estimator with the driver-form models it returned (no conversion), this call's
     px_th / error_type / ratio / mutual, and adds a fourth element [guided_p]: the guided match of every query or -1.
+    fginn_th: None = the plain ratio test; a number switches it to the FGINN ratio test of match_fginn at that radius in pixels of
+    kps2 (the guided stage keeps its own gate and decision).
     last_stats() holds the per-pair statistics, with "tentatives"."""
     from . import api, parallel
     K = len(desc1_list)
@@ -310,7 +354,7 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
         raise ValueError("one keypoint row per descriptor row")
     A = np.concatenate(a); B = np.concatenate(b); K1 = np.concatenate(k1); K2 = np.concatenate(k2)
     code, kind, o1, o2 = check_match_verify_args(model, ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape, K2.dtype,
-                                                 np.asarray(c1, np.int64), np.asarray(c2, np.int64))
+                                                 np.asarray(c1, np.int64), np.asarray(c2, np.int64), fginn_th)
     prm = estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
     if code != NORM_L2:
         A, B = _pad_words(A, B)
@@ -323,7 +367,7 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
     sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
     if sd.shape != (K,):
         raise ValueError("one seed per pair")
-    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual)
+    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual, fginn_th)
     n1 = A.shape[0]
     M = np.zeros((K, 9)); match = np.full(n1, -1, np.int32); inl = np.zeros(n1, np.uint8)
     st = np.zeros((K, 16), np.int32); cnt = np.zeros(K, np.int32)

@@ -126,6 +126,21 @@ def knn_match_tensors(desc1, desc2, norm=None):
     return idx, dist
 
 
+def match_filter_tensors(idx, dist, ratio=0.9, back=None):
+    """The ratio test `dist[:, 0] < ratio * dist[:, 1]` (a query without a second neighbour is not kept) on a 2-NN result, and with
+    back (the idx of the reverse search) the mutual check; returns keep [n1] uint8 on the device, asynchronous on the current stream."""
+    import torch
+    dev = idx.device; n1 = idx.shape[0]
+    keep = torch.zeros(n1, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    rc = _lib.lib().mi_degensac_match_filter_dev(idx.data_ptr(), dist.data_ptr(), n1, float(ratio), back.data_ptr() if back is not None else None,
+                                                 dev.index or 0, C.c_void_p(stream.cuda_stream), keep.data_ptr())
+    _lib.check_match(rc)
+    for t in (idx, dist) + ((back,) if back is not None else ()):
+        t.record_stream(stream)
+    return keep
+
+
 def match_snn_tensors(desc1, desc2, ratio=0.9, mutual=False, norm=None):
     """The ratio test of the example (`m.distance < ratio * n.distance`, simple-example.py:49-53), optionally restricted to
     mutual nearest neighbours, on the device: (query indices, train indices, distances) of the tentative correspondences.
@@ -204,6 +219,40 @@ def knn_match_batch_tensors(desc1, desc2, counts1, counts2, norm=None):
     return idx, dist
 
 
+def knn_match_fginn_batch_tensors(desc1, desc2, kps2, counts1, counts2, spatial_th=10.0, norm=None):
+    """knn_match_batch_tensors with the FGINN rule for the second neighbour (include/mi_degensac.h
+    mi_degensac_match_fginn_knn2_batch_dev): slot 0 is the nearest train row as before; slot 1 is the nearest train row of the pair
+    whose keypoint (kps2: float64 [N2, 2] / [N2, 6] on the device, only x, y are read) lies at least spatial_th from the keypoint of
+    slot 0 (dx*dx + dy*dy >= spatial_th**2 in float64; NaN never competes), -1 / inf when there is none.  spatial_th=0 with finite
+    keypoints gives knn_match_batch_tensors bit for bit.  Returns (idx [N1, 2] int32, dist [N1, 2] float32) on the device,
+    asynchronous on the current stream (no host synchronisation)."""
+    import torch
+    from . import matcher
+    if not all(isinstance(t, torch.Tensor) for t in (desc1, desc2, kps2)):
+        raise ValueError("desc1, desc2 and kps2 must be torch tensors on a ROCm device")
+    r = matcher.check_fginn_th(spatial_th, "spatial_th")
+    if kps2.dim() != 2 or kps2.dtype != torch.float64 or kps2.shape[1] not in (2, 6):
+        raise ValueError("keypoints should be float64 [n, 2] / [n, 6] rows")
+    code, _, o1, o2 = matcher.check_match_verify_args("F", 1.0, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
+                                                      (desc1.shape[0], kps2.shape[1]), np.float64, tuple(kps2.shape), kps2.dtype, counts1, counts2)
+    if kps2.device != desc1.device:
+        raise ValueError("desc1, desc2 and kps2 must live on the same ROCm device")
+    a, b = _desc_pair(desc1, desc2)
+    k2 = kps2.contiguous()
+    dev = a.device; n1 = a.shape[0]; K = len(o1) - 1
+    idx = torch.full((n1, 2), -1, dtype=torch.int32, device=dev)
+    dist = torch.full((n1, 2), float("inf"), dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    lp = C.POINTER(C.c_int64)
+    rc = _lib.lib().mi_degensac_match_fginn_knn2_batch_dev(code, a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(lp), o2.ctypes.data_as(lp), K,
+                                                           int(a.shape[1]), k2.data_ptr(), int(k2.shape[1]), r, dev.index or 0,
+                                                           C.c_void_p(stream.cuda_stream), idx.data_ptr(), dist.data_ptr())
+    _lib.check_match(rc)
+    for t in (a, b, k2):
+        t.record_stream(stream)
+    return idx, dist
+
+
 def _guided_dev(code, a, b, k1, k2, o1, o2, Md, model, ratio, mutual, px, et):
     """mi_degensac_match_guided_batch_dev on prepared device tensors (Md: [K, 9] driver-form models), asynchronous on the current
     stream.  Returns (match [N1] int32, idx [N1, 2] int32, dist [N1, 2] float32)."""
@@ -262,7 +311,7 @@ def guided_match_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model
 
 def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
                                    max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
-                                   enable_degeneracy_check=True, seeds=None, guided=False, norm=None):
+                                   enable_degeneracy_check=True, seeds=None, guided=False, norm=None, fginn_th=None):
     """K image pairs from descriptors to models with ONE host synchronisation (the read of the per-pair tentative counts): per pair
     the 2-NN ratio test (`m.distance < ratio * n.distance`, optionally mutual) of match_snn_tensors, then the estimator of
     find_fundamental_batch_tensors (model "F") / find_homography_batch_tensors ("H") on its tentatives in query order.
@@ -275,14 +324,16 @@ def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, m
     train row or -1, inlier [N1] bool, stats [K, 16] int32, n_tentatives [K] numpy int64); all but the last on the device.
     guided=True then runs guided_match_batch_tensors on the same stream with the estimator's driver-form models straight from device
     memory (no conversion) and this call's px_th / error_type / ratio / mutual, and appends its match [N1] int32 (the guided match of
-    every query or -1); the call still synchronises exactly once."""
+    every query or -1); the call still synchronises exactly once.
+    fginn_th: None = the plain ratio test; a number switches it to the FGINN ratio test (knn_match_fginn_batch_tensors at that radius
+    on kps2's x, y).  Only the tentatives in front of the estimator change: the guided stage keeps its own gate and decision."""
     import torch
     from . import matcher, parallel
     ts = (kps1, kps2, desc1, desc2)
     if not all(isinstance(t, torch.Tensor) for t in ts):
         raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
     code, kind, o1, o2 = matcher.check_match_verify_args(model, ratio, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
-                                                         tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype, counts1, counts2)
+                                                         tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype, counts1, counts2, fginn_th)
     if any(t.device != desc1.device for t in ts):
         raise ValueError("kps1, kps2, desc1 and desc2 must live on the same ROCm device")
     prm = matcher.estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
@@ -304,7 +355,7 @@ def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, m
     inlier = torch.zeros(n1, dtype=torch.uint8, device=dev)
     stats = torch.zeros((K, 16), dtype=torch.int32, device=dev)
     cnt = np.zeros(K, np.int32)
-    mp = _lib.MatchParams(code, a.shape[1], ratio, mutual)
+    mp = _lib.MatchParams(code, a.shape[1], ratio, mutual, fginn_th)
     stream = torch.cuda.current_stream(dev)
     rc = _lib.lib().mi_degensac_match_verify_batch_dev(1 if model == "H" else 0, C.byref(mp), a.data_ptr(), b.data_ptr(),
                                                        o1.ctypes.data_as(C.POINTER(C.c_int64)), o2.ctypes.data_as(C.POINTER(C.c_int64)),
