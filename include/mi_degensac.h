@@ -434,6 +434,42 @@ int mi_degensac_match_verify_batch(int homography, const mi_degensac_match_param
                                    int n_pairs, const mi_degensac_params *prm, const uint32_t *seeds, int device,
                                    double *model, int32_t *match, uint8_t *inlier, int32_t *stats /*nullable*/, int32_t *counts /*nullable*/);
 
+/* ---- the pair-list form: image stores + a list of (i, j) image indices ------------------------------------------------------
+ * An image collection matched against itself, or queries against a database: every image takes part in many pairs, so its rows are
+ * stored ONCE.  Store 1 holds n_images1 images, image i owning the rows offsets1_host[i] .. offsets1_host[i+1] of desc1 / kp1; store
+ * 2 likewise with offsets2_host [n_images2 + 1] (offsets: non-negative, non-decreasing, a non-zero first offset allowed; the two
+ * stores may be the same memory).  pairs_host: [2 * n_pairs] int32 on the host, entry p = (i, j): the queries are image i of store
+ * 1, the train set image j of store 2.  Any list is allowed: self pairs, repeated pairs, (i, j) next to (j, i), unused and empty
+ * images, any order.  Per-query results are laid out pair after pair in list order from row 0: pair p owns the output rows
+ * out[p] .. out[p+1], out[p+1] - out[p] = the rows of image pairs[p][0]; train indices are local to image j.
+ * Every output is bit for bit what the batched entry point of the same name (knn2_batch_dev / verify_batch_dev / verify_batch)
+ * returns when pair p's rows are copied out of the stores and the seeds are the same; no descriptor row is copied on the device.
+ * The forward search runs once per list entry, and with mutual the reverse search too (image j's rows against image i, into a block
+ * of sum_p rows(image pairs[p][1]) rows): nothing is shared between (i, j) and (j, i).
+ * Errors, before a device is looked for: MI_DEGENSAC_EINVAL for an image index outside its store, n_pairs < 0, bad offsets, and
+ * output or reverse-search rows beyond 0x3fffffff (the row limit of the batched entry points); n_pairs == 0 returns 0 and touches
+ * nothing.  mi_degensac_match_knn2_pairs_dev: asynchronous on `stream`, no host synchronisation; d_idx / d_dist [out[K], 2]. */
+int mi_degensac_match_knn2_pairs_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host, int n_images1,
+                                     const int64_t *offsets2_host, int n_images2, const int32_t *pairs_host, int n_pairs, int dim,
+                                     int device, void *stream, int32_t *d_idx, float *d_dist);
+/* mi_degensac_match_verify_batch_dev on a pair list: d_kp1 / d_kp2 are the stores' keypoint rows, d_seeds [K] one seed per list
+ * entry, d_model [K*9], d_stats [K*16] or NULL, d_match / d_inlier [out[K]] in output-row order, h_counts [K] (host, nullable).  One
+ * synchronisation, as there: the read of the K tentative counts.  The FGINN rule is not part of the pair-list form: a match_params
+ * that asks for it (second_nn = 1 with struct_size covering it) is MI_DEGENSAC_EINVAL. */
+int mi_degensac_match_verify_pairs_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
+                                       const int64_t *offsets1_host, int n_images1, const int64_t *offsets2_host, int n_images2,
+                                       const double *d_kp1, const double *d_kp2, int kp_dim, const int32_t *pairs_host, int n_pairs,
+                                       const mi_degensac_params *prm, const uint32_t *d_seeds, int device, void *stream, double *d_model,
+                                       int32_t *d_match, uint8_t *d_inlier, int32_t *d_stats, int32_t *h_counts /*nullable*/);
+/* the same on host pointers (blocking; seeds[K] on the host): each store is uploaded once (one upload when both sides name the same
+ * arrays).  Pairs discarded after a hand-over time-out are run again as in mi_degensac_match_verify_batch, their tentatives'
+ * keypoints picked out of the stores through the pair's image rows (bit 11 of stats[15]). */
+int mi_degensac_match_verify_pairs(int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2,
+                                   const int64_t *offsets1, int n_images1, const int64_t *offsets2, int n_images2, const double *kp1,
+                                   const double *kp2, int kp_dim, const int32_t *pairs, int n_pairs, const mi_degensac_params *prm,
+                                   const uint32_t *seeds, int device, double *model, int32_t *match, uint8_t *inlier,
+                                   int32_t *stats /*nullable*/, int32_t *counts /*nullable*/);
+
 /* ---- guided matching: the batched 2-NN restricted to each pair's model inlier band (mi_guided.hip) ------------------------
  * Same ragged batch as mi_degensac_match_knn2_batch_dev (host offsets of K + 1 values, pair-local indices), plus keypoints
  * kp1 / kp2 [rows, kp_dim] float64 (kp_dim 2 or 6; only x, y are read) and one model per pair, d_models [K*9] in the driver's form

@@ -188,6 +188,17 @@ def lib():
         l.mi_degensac_match_verify_batch.restype = C.c_int
         l.mi_degensac_match_verify_batch.argtypes = [C.c_int, mpp, C.c_void_p, C.c_void_p, lp, lp, dp, dp, C.c_int, C.c_int, pp, up, C.c_int,
                                                      dp, ip, bp, ip, ip]
+        if hasattr(l, "mi_degensac_match_knn2_pairs_dev"):                # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            l.mi_degensac_match_knn2_pairs_dev.restype = C.c_int
+            l.mi_degensac_match_knn2_pairs_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, lp, C.c_int, lp, C.c_int, ip, C.c_int, C.c_int, C.c_int,
+                                                           C.c_void_p, C.c_void_p, C.c_void_p]
+            l.mi_degensac_match_verify_pairs_dev.restype = C.c_int
+            l.mi_degensac_match_verify_pairs_dev.argtypes = [C.c_int, mpp, C.c_void_p, C.c_void_p, lp, C.c_int, lp, C.c_int, C.c_void_p, C.c_void_p,
+                                                             C.c_int, ip, C.c_int, pp, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                             C.c_void_p, C.c_void_p, ip]
+            l.mi_degensac_match_verify_pairs.restype = C.c_int
+            l.mi_degensac_match_verify_pairs.argtypes = [C.c_int, mpp, C.c_void_p, C.c_void_p, lp, C.c_int, lp, C.c_int, dp, dp, C.c_int, ip, C.c_int,
+                                                         pp, up, C.c_int, dp, ip, bp, ip, ip]
         gpp = C.POINTER(GuideParams)
         l.mi_degensac_match_guided_knn2_batch_dev.restype = C.c_int
         l.mi_degensac_match_guided_knn2_batch_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, lp, lp, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,

@@ -1065,7 +1065,8 @@ extern "C" int mi_degensac_find_fundamental_hist(const double *pts1, const doubl
  * tentatives -> launch_batch -> scatter back to pair / query order.  Scratch: two stream-ordered blocks per call. */
 static int match_rc(int rc) { if (rc) set_err("%s", mi_degensac_match_last_error()); return rc; }
 
-static int mv_check(int homography, const mi_degensac_match_params *mp, const int64_t *off1, const int64_t *off2, int kp_dim, int n_pairs)
+/* everything of a match-and-verify call but its row layout */
+static int mv_check_params(int homography, const mi_degensac_match_params *mp, int kp_dim, int n_pairs)
 {
     if (homography != 0 && homography != 1) { set_err("homography must be 0 or 1"); return MI_DEGENSAC_EINVAL; }
     if (!mp) { set_err("match params are NULL"); return MI_DEGENSAC_EINVAL; }
@@ -1075,6 +1076,12 @@ static int mv_check(int homography, const mi_degensac_match_params *mp, const in
     if (kp_dim != 2 && kp_dim != 6) { set_err("keypoint rows must be [n,2] or [n,6]"); return MI_DEGENSAC_EINVAL; }
     { int fg; double r; if (const char *e = mt_second_nn(mp, &fg, &r)) { set_err("%s", e); return MI_DEGENSAC_EINVAL; } }
     if (n_pairs < 0) { set_err("n_pairs < 0"); return MI_DEGENSAC_EINVAL; }
+    return 0;
+}
+
+static int mv_check(int homography, const mi_degensac_match_params *mp, const int64_t *off1, const int64_t *off2, int kp_dim, int n_pairs)
+{
+    int rc = mv_check_params(homography, mp, kp_dim, n_pairs); if (rc) return rc;
     if (n_pairs == 0) return 0;
     for (const int64_t *o : {off1, off2}) {
         if (!o || o[0] < 0) { set_err("offsets must be given and start at >= 0"); return MI_DEGENSAC_EINVAL; }
@@ -1089,6 +1096,52 @@ struct MvBlocks {
     hipStream_t s; char *a = nullptr, *b = nullptr;
     ~MvBlocks() { if (a) (void)hipFreeAsync(a, s); if (b) (void)hipFreeAsync(b, s); }
 };
+
+/* Where pair p's rows are, as int32 tables on the device.  out [K + 1]: its rows of idx / dist / keep / rank / match / inlier.  The
+ * ragged batch keeps its keypoints at those same rows and its train rows from t2[p] (q1 = null); a pair list reads the query image's
+ * keypoints from row q1[p] of kp1 and the train image's from row t2[p] of kp2. */
+struct MvRows { const int32_t *out, *q1, *t2; };
+
+/* the second half of a match-and-verify call, after the filter has written keep / rank / cnt on s */
+static int mv_estimate(int homography, int K, int kd, const mi_degensac_params *prm, const MvRows &R, const int32_t *cnt, const uint8_t *keep,
+                       const int32_t *rank, const int32_t *idx, const double *kp1, const double *kp2, const uint32_t *d_seeds, int device,
+                       hipStream_t s, MvBlocks &blk, double *d_model, int32_t *d_stats, int32_t *match, uint8_t *inlier, int32_t *h_counts)
+{
+    int rc;
+    /* the one synchronisation: the estimator's launch is sized and configured from the tentative counts on the host */
+    std::vector<int32_t> counts(K);
+    HIPCHK(hipMemcpyAsync(counts.data(), cnt, (size_t)K * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h_counts) memcpy(h_counts, counts.data(), (size_t)K * 4);
+    const int min_pts = homography ? 4 : 8;
+    std::vector<int64_t> est_off(1, 0); std::vector<int32_t> e_of_p(K, -1), pair_of_e;
+    for (int p = 0; p < K; p++)
+        if (counts[p] >= min_pts) { e_of_p[p] = (int32_t)pair_of_e.size(); pair_of_e.push_back(p); est_off.push_back(est_off.back() + counts[p]); }
+    const int E = (int)pair_of_e.size(); const int64_t T = est_off.back();
+
+    /* block B: est_off | e_of_p | pair_of_e (one upload), seeds, models, stats, the estimator's input rows and masks */
+    const size_t c_eoff = 0, c_eop = (size_t)(E + 1) * 8, c_poe = c_eop + (size_t)K * 4, c_all = c_poe + (size_t)E * 4;
+    std::vector<char> tab(c_all);
+    memcpy(tab.data() + c_eoff, est_off.data(), (size_t)(E + 1) * 8); memcpy(tab.data() + c_eop, e_of_p.data(), (size_t)K * 4);
+    if (E) memcpy(tab.data() + c_poe, pair_of_e.data(), (size_t)E * 4);
+    const size_t g_seed = align_up(c_all, 256), g_model = g_seed + align_up((size_t)E * 4, 256), g_stats = g_model + align_up((size_t)E * 72, 256),
+                 g_p1 = g_stats + align_up((size_t)E * 64, 256), g_p2 = g_p1 + align_up((size_t)T * kd * 8, 256),
+                 g_mask = g_p2 + align_up((size_t)T * kd * 8, 256), g_all = g_mask + align_up((size_t)T, 256);
+    HIPCHK(hipMallocAsync((void **)&blk.b, g_all, s));
+    char *B = blk.b;
+    const int64_t *d_eoff = (const int64_t *)(B + c_eoff); const int32_t *d_eop = (const int32_t *)(B + c_eop), *d_poe = (const int32_t *)(B + c_poe);
+    uint32_t *seeds_e = (uint32_t *)(B + g_seed); double *model_e = (double *)(B + g_model), *pts1 = (double *)(B + g_p1), *pts2 = (double *)(B + g_p2);
+    int32_t *stats_e = (int32_t *)(B + g_stats); uint8_t *mask_e = (uint8_t *)(B + g_mask);
+    rc = match_rc(mt_batch_upload(device, s, tab.data(), c_all, B)); if (rc) return rc;
+    if (E > 0) {
+        rc = match_rc(R.q1 ? mt_pairs_gather(E, d_poe, d_eoff, R.out, R.q1, R.t2, keep, rank, idx, kp1, kp2, kd, d_seeds, s, pts1, pts2, seeds_e)
+                           : mt_batch_gather(E, d_poe, d_eoff, R.out, R.t2, keep, rank, idx, kp1, kp2, kd, d_seeds, s, pts1, pts2, seeds_e));
+        if (rc) return rc;
+        rc = launch_batch(homography, pts1, pts2, d_eoff, est_off.data(), E, kd, prm, seeds_e, device, s, model_e, mask_e, stats_e);
+        if (rc) return rc;
+    }
+    return match_rc(mt_batch_scatter(K, d_eop, d_eoff, R.out, keep, rank, idx, model_e, stats_e, mask_e, s, d_model, d_stats, match, inlier));
+}
 
 static int match_verify_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const int64_t *off1,
                             const int64_t *off2, const double *d_kp1, const double *d_kp2, int kd, int K, const mi_degensac_params *prm,
@@ -1132,37 +1185,8 @@ static int match_verify_dev(int homography, const mi_degensac_match_params *mp, 
     if (mutual) { rc = match_rc(mt_batch_knn2(mp->norm, words, q2, q1, o2.data(), o1.data(), K, device, s, bidx, bdist)); if (rc) return rc; }
     rc = match_rc(mt_batch_filter_rank(idx, dist, d_o1, d_o2, K, mp->ratio, bidx, s, keep, rank, cnt)); if (rc) return rc;
 
-    /* the one synchronisation: the estimator's launch is sized and configured from the tentative counts on the host */
-    std::vector<int32_t> counts(K);
-    HIPCHK(hipMemcpyAsync(counts.data(), cnt, (size_t)K * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (h_counts) memcpy(h_counts, counts.data(), (size_t)K * 4);
-    const int min_pts = homography ? 4 : 8;
-    std::vector<int64_t> est_off(1, 0); std::vector<int32_t> e_of_p(K, -1), pair_of_e;
-    for (int p = 0; p < K; p++)
-        if (counts[p] >= min_pts) { e_of_p[p] = (int32_t)pair_of_e.size(); pair_of_e.push_back(p); est_off.push_back(est_off.back() + counts[p]); }
-    const int E = (int)pair_of_e.size(); const int64_t T = est_off.back();
-
-    /* block B: est_off | e_of_p | pair_of_e (one upload), seeds, models, stats, the estimator's input rows and masks */
-    const size_t c_eoff = 0, c_eop = (size_t)(E + 1) * 8, c_poe = c_eop + (size_t)K * 4, c_all = c_poe + (size_t)E * 4;
-    std::vector<char> tab(c_all);
-    memcpy(tab.data() + c_eoff, est_off.data(), (size_t)(E + 1) * 8); memcpy(tab.data() + c_eop, e_of_p.data(), (size_t)K * 4);
-    if (E) memcpy(tab.data() + c_poe, pair_of_e.data(), (size_t)E * 4);
-    const size_t g_seed = align_up(c_all, 256), g_model = g_seed + align_up((size_t)E * 4, 256), g_stats = g_model + align_up((size_t)E * 72, 256),
-                 g_p1 = g_stats + align_up((size_t)E * 64, 256), g_p2 = g_p1 + align_up((size_t)T * kd * 8, 256),
-                 g_mask = g_p2 + align_up((size_t)T * kd * 8, 256), g_all = g_mask + align_up((size_t)T, 256);
-    HIPCHK(hipMallocAsync((void **)&blk.b, g_all, s));
-    char *B = blk.b;
-    const int64_t *d_eoff = (const int64_t *)(B + c_eoff); const int32_t *d_eop = (const int32_t *)(B + c_eop), *d_poe = (const int32_t *)(B + c_poe);
-    uint32_t *seeds_e = (uint32_t *)(B + g_seed); double *model_e = (double *)(B + g_model), *pts1 = (double *)(B + g_p1), *pts2 = (double *)(B + g_p2);
-    int32_t *stats_e = (int32_t *)(B + g_stats); uint8_t *mask_e = (uint8_t *)(B + g_mask);
-    rc = match_rc(mt_batch_upload(device, s, tab.data(), c_all, B)); if (rc) return rc;
-    if (E > 0) {
-        rc = match_rc(mt_batch_gather(E, d_poe, d_eoff, d_o1, d_o2, keep, rank, idx, kp1, kp2, kd, d_seeds, s, pts1, pts2, seeds_e)); if (rc) return rc;
-        rc = launch_batch(homography, pts1, pts2, d_eoff, est_off.data(), E, kd, prm, seeds_e, device, s, model_e, mask_e, stats_e);
-        if (rc) return rc;
-    }
-    return match_rc(mt_batch_scatter(K, d_eop, d_eoff, d_o1, keep, rank, idx, model_e, stats_e, mask_e, s, d_model, d_stats, match, inlier));
+    return mv_estimate(homography, K, kd, prm, MvRows{d_o1, nullptr, d_o2}, cnt, keep, rank, idx, kp1, kp2, d_seeds, device, s, blk, d_model, d_stats,
+                       match, inlier, h_counts);
 }
 
 extern "C" int mi_degensac_match_verify_batch_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
@@ -1172,6 +1196,39 @@ extern "C" int mi_degensac_match_verify_batch_dev(int homography, const mi_degen
 {
     return match_verify_dev(homography, mp, d_desc1, d_desc2, offsets1_host, offsets2_host, d_kp1, d_kp2, kp_dim, n_pairs, prm, d_seeds, device,
                             (hipStream_t)stream, d_model, d_match, d_inlier, d_stats, h_counts);
+}
+
+/* The host-pointer forms' re-run of the pairs discarded after a hand-over time-out (bit 10 of stats[15]): exactly their tentatives,
+ * in the order the device gathered them (query order).  Pair p owns the rows out[p] .. out[p+1] of mt / in; the keypoints of its
+ * query r are row b1[p] + r - out[p] of k1, those of train row t (pair-local) row b2[p] + t of k2. */
+static int mv_rerun(mi_degensac_ctx *c, int homography, int kd, int K, const mi_degensac_params *prm, const uint32_t *seeds, const int64_t *out,
+                    const int64_t *b1, const int64_t *b2, const double *k1, const double *k2, const int32_t *mt, double *model, uint8_t *in,
+                    std::vector<int32_t> &st)
+{
+    std::vector<int> redo;
+    for (int p = 0; p < K; p++) if (st[(size_t)p * 16 + 15] & 1024) redo.push_back(p);
+    if (redo.empty()) return 0;
+    std::vector<double> q1, q2; std::vector<int64_t> qo(1, 0); std::vector<uint32_t> qs;
+    for (int p : redo) {
+        for (int64_t i = out[p]; i < out[p + 1]; i++) if (mt[i] >= 0) {
+            const int64_t a = b1[p] + (i - out[p]), b = b2[p] + mt[i];
+            q1.insert(q1.end(), k1 + a * kd, k1 + (a + 1) * kd);
+            q2.insert(q2.end(), k2 + b * kd, k2 + (b + 1) * kd);
+        }
+        qo.push_back((int64_t)q1.size() / kd); qs.push_back(seeds[p]);
+    }
+    const int R = (int)redo.size();
+    const mi_degensac_params p2s = rerun_params(prm, homography);
+    std::vector<double> qm((size_t)R * 9); std::vector<uint8_t> qk((size_t)qo.back()); std::vector<int32_t> qst((size_t)R * 16);
+    int rc = ctx_batch(c, homography, q1.data(), q2.data(), qo.data(), R, kd, &p2s, qs.data(), qm.data(), qk.data(), qst.data(), 1);
+    if (rc) return rc;
+    for (int r = 0; r < R; r++) {
+        const int p = redo[r]; int64_t k = qo[r];
+        memcpy(model + (size_t)p * 9, qm.data() + (size_t)r * 9, 72);
+        for (int64_t i = out[p]; i < out[p + 1]; i++) if (mt[i] >= 0) in[i] = qk[k++];
+        memcpy(st.data() + (size_t)p * 16, qst.data() + (size_t)r * 16, 64); st[(size_t)p * 16 + 15] |= 2048;     /* bit 11: run again */
+    }
+    return 0;
 }
 
 /* host pointers: stage on the calling thread's context, run the device path on its stream, copy back; pairs discarded after a
@@ -1213,31 +1270,133 @@ extern "C" int mi_degensac_match_verify_batch(int homography, const mi_degensac_
     HIPCHK(hipMemcpy(mt, D + a_ma, (size_t)n1 * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(in, D + a_in, (size_t)n1, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(st.data(), D + a_st, (size_t)K * 64, hipMemcpyDeviceToHost));
-    std::vector<int> redo;
-    for (int p = 0; p < K; p++) if (st[(size_t)p * 16 + 15] & 1024) redo.push_back(p);
-    if (!redo.empty()) {
-        /* exactly the discarded pairs' tentatives, in the order the device gathered them (query order) */
-        const double *k1 = kp1 + offsets1[0] * kd, *k2 = kp2 + offsets2[0] * kd;
-        std::vector<double> q1, q2; std::vector<int64_t> qo(1, 0); std::vector<uint32_t> qs;
-        for (int p : redo) {
-            for (int64_t i = o1[p]; i < o1[p + 1]; i++) if (mt[i] >= 0) {
-                q1.insert(q1.end(), k1 + i * kd, k1 + (i + 1) * kd);
-                q2.insert(q2.end(), k2 + (o2[p] + mt[i]) * kd, k2 + (o2[p] + mt[i] + 1) * kd);
-            }
-            qo.push_back((int64_t)q1.size() / kd); qs.push_back(seeds[p]);
-        }
-        const int R = (int)redo.size();
-        const mi_degensac_params p2s = rerun_params(prm, homography);
-        std::vector<double> qm((size_t)R * 9); std::vector<uint8_t> qk((size_t)qo.back()); std::vector<int32_t> qst((size_t)R * 16);
-        rc = ctx_batch(c, homography, q1.data(), q2.data(), qo.data(), R, kd, &p2s, qs.data(), qm.data(), qk.data(), qst.data(), 1);
-        if (rc) return rc;
-        for (int r = 0; r < R; r++) {
-            const int p = redo[r]; int64_t k = qo[r];
-            memcpy(model + (size_t)p * 9, qm.data() + (size_t)r * 9, 72);
-            for (int64_t i = o1[p]; i < o1[p + 1]; i++) if (mt[i] >= 0) in[i] = qk[k++];
-            memcpy(st.data() + (size_t)p * 16, qst.data() + (size_t)r * 16, 64); st[(size_t)p * 16 + 15] |= 2048;     /* bit 11: run again */
-        }
+    rc = mv_rerun(c, homography, kd, K, prm, seeds, o1.data(), o1.data(), o2.data(), kp1 + offsets1[0] * kd, kp2 + offsets2[0] * kd, mt, model, in, st);
+    if (rc) return rc;
+    if (stats) memcpy(stats, st.data(), (size_t)K * 64);
+    if (counts) memcpy(counts, cnt.data(), (size_t)K * 4);
+    return 0;
+}
+
+/* ---- match-and-verify over a pair list (include/mi_degensac.h mi_degensac_match_verify_pairs[_dev]) --------------------------
+ * The batched path with descriptors and keypoints stored once per image: four per-pair row bases (output rows, query rows in store
+ * 1, train rows in store 2, rows of the reverse search's back block) take the place of the two offset tables that say both "where my
+ * results are" and "where my rows are" in the ragged batch.  The filter and the scatter only ever ask the first question and run
+ * unchanged on the output-row offsets (and the back bases); the 2-NN launch and the gather have pair-list siblings. */
+static int mvp_check(int homography, const mi_degensac_match_params *mp, int kd, const int64_t *off1, int m1, const int64_t *off2, int m2,
+                     const int32_t *pairs, int K, std::vector<mt_pair_rows> &rows, int64_t *n_out, int64_t *n_back)
+{
+    int rc = mv_check_params(homography, mp, kd, K); if (rc) return rc;
+    int fginn; double r; (void)mt_second_nn(mp, &fginn, &r);
+    if (fginn) { set_err("the FGINN rule (second_nn = 1) is not part of the pair-list entry points: use mi_degensac_match_verify_batch*"); return MI_DEGENSAC_EINVAL; }
+    *n_out = *n_back = 0;
+    if (K == 0) return 0;
+    rows.resize(K);
+    return match_rc(mt_pairs_layout(off1, m1, off2, m2, pairs, K, rows.data(), n_out, n_back));
+}
+
+static int match_verify_pairs_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const int64_t *off1,
+                                  const int64_t *off2, const double *d_kp1, const double *d_kp2, int kd, const std::vector<mt_pair_rows> &rows,
+                                  int64_t n_out, int64_t n_back, const mi_degensac_params *prm, const uint32_t *d_seeds, int device, hipStream_t s,
+                                  double *d_model, int32_t *match, uint8_t *inlier, int32_t *d_stats, int32_t *h_counts)
+{
+    const int K = (int)rows.size();
+    dg_params chk; int rc = fill_params(prm, homography, kd, &chk); if (rc) return rc;
+    if (!d_seeds || !d_model || (n_out > 0 && (!d_desc1 || !d_kp1 || !match || !inlier)) || (n_back > 0 && (!d_desc2 || !d_kp2))) {
+        set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
+    if (device < 0 || device >= 64) { set_err("bad device index"); return MI_DEGENSAC_EINVAL; }
+    if (mi_degensac_device_count() == 0) { set_err("no HIP device: this library has no CPU path"); return MI_DEGENSAC_ENODEV; }
+    DevGuard g; rc = g.enter(device); if (rc) return rc;
+    const int words = mt_row_words(mp->norm, mp->dim);
+    const bool mutual = mp->mutual != 0;
+    /* every row pointer moves to its store's first row; the tables: out [K + 1] | q1 [K] | t2 [K] | back [K] */
+    const uint32_t *q1 = (const uint32_t *)d_desc1 + (size_t)off1[0] * words, *q2 = (const uint32_t *)d_desc2 + (size_t)off2[0] * words;
+    const double *kp1 = d_kp1 + (size_t)off1[0] * kd, *kp2 = d_kp2 + (size_t)off2[0] * kd;
+    std::vector<int32_t> tab(4 * (size_t)K + 1);
+    for (int p = 0; p < K; p++) { tab[p] = rows[p].out; tab[K + 1 + p] = rows[p].q; tab[2 * K + 1 + p] = rows[p].t; tab[3 * K + 1 + p] = rows[p].back; }
+    tab[K] = (int32_t)n_out;
+
+    /* block A: tables, forward (and backward) 2-NN, keep / rank / count */
+    const size_t b_tab = align_up(tab.size() * 4, 256), b_idx = align_up((size_t)n_out * 8, 256), b_bidx = mutual ? align_up((size_t)n_back * 8, 256) : 0,
+                 b_keep = align_up((size_t)n_out, 256), b_cnt = align_up((size_t)K * 4, 256);
+    const size_t a_idx = b_tab, a_dist = a_idx + b_idx, a_bidx = a_dist + b_idx, a_bdist = a_bidx + b_bidx, a_keep = a_bdist + b_bidx,
+                 a_rank = a_keep + b_keep, a_cnt = a_rank + b_idx, a_all = a_cnt + b_cnt;
+    MvBlocks blk{s};
+    HIPCHK(hipMallocAsync((void **)&blk.a, a_all, s));
+    char *A = blk.a;
+    const int32_t *d_out = (const int32_t *)A, *d_q1 = d_out + (K + 1), *d_t2 = d_q1 + K, *d_back = d_t2 + K;
+    int32_t *idx = (int32_t *)(A + a_idx), *bidx = mutual ? (int32_t *)(A + a_bidx) : nullptr, *rank = (int32_t *)(A + a_rank), *cnt = (int32_t *)(A + a_cnt);
+    float *dist = (float *)(A + a_dist), *bdist = (float *)(A + a_bdist);
+    uint8_t *keep = (uint8_t *)(A + a_keep);
+    rc = match_rc(mt_batch_upload(device, s, tab.data(), tab.size() * 4, A)); if (rc) return rc;
+    rc = match_rc(mt_pairs_knn2(mp->norm, words, q1, q2, rows.data(), K, (int)n_out, 0, device, s, idx, dist)); if (rc) return rc;
+    if (mutual) { rc = match_rc(mt_pairs_knn2(mp->norm, words, q2, q1, rows.data(), K, (int)n_back, 1, device, s, bidx, bdist)); if (rc) return rc; }
+    rc = match_rc(mt_batch_filter_rank(idx, dist, d_out, d_back, K, mp->ratio, bidx, s, keep, rank, cnt)); if (rc) return rc;
+    return mv_estimate(homography, K, kd, prm, MvRows{d_out, d_q1, d_t2}, cnt, keep, rank, idx, kp1, kp2, d_seeds, device, s, blk, d_model, d_stats,
+                       match, inlier, h_counts);
+}
+
+extern "C" int mi_degensac_match_verify_pairs_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
+        const int64_t *offsets1_host, int n_images1, const int64_t *offsets2_host, int n_images2, const double *d_kp1, const double *d_kp2, int kp_dim,
+        const int32_t *pairs_host, int n_pairs, const mi_degensac_params *prm, const uint32_t *d_seeds, int device, void *stream, double *d_model,
+        int32_t *d_match, uint8_t *d_inlier, int32_t *d_stats, int32_t *h_counts)
+{
+    std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
+    int rc = mvp_check(homography, mp, kp_dim, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, rows, &n_out, &n_back);
+    if (rc || n_pairs == 0) return rc;
+    return match_verify_pairs_dev(homography, mp, d_desc1, d_desc2, offsets1_host, offsets2_host, d_kp1, d_kp2, kp_dim, rows, n_out, n_back, prm, d_seeds,
+                                  device, (hipStream_t)stream, d_model, d_match, d_inlier, d_stats, h_counts);
+}
+
+/* host pointers: each store goes to the device once (one copy when both sides name the same arrays), the device path runs on the
+ * calling thread's stream, the per-pair results come back; discarded pairs go through mv_rerun with the pair's image rows */
+extern "C" int mi_degensac_match_verify_pairs(int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2,
+        const int64_t *offsets1, int n_images1, const int64_t *offsets2, int n_images2, const double *kp1, const double *kp2, int kd,
+        const int32_t *pairs, int K, const mi_degensac_params *prm, const uint32_t *seeds, int device, double *model, int32_t *match,
+        uint8_t *inlier, int32_t *stats, int32_t *counts)
+{
+    std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
+    int rc = mvp_check(homography, mp, kd, offsets1, n_images1, offsets2, n_images2, pairs, K, rows, &n_out, &n_back);
+    if (rc || K == 0) return rc;
+    if (!desc1 || !desc2 || !kp1 || !kp2 || !seeds || !model || !match || !inlier) { set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
+    mi_degensac_ctx *c; rc = thread_ctx(device, &c); if (rc) return rc;
+    DevGuard g; rc = g.enter(device); if (rc) return rc;
+    const int64_t n1 = offsets1[n_images1] - offsets1[0], n2 = offsets2[n_images2] - offsets2[0];
+    const size_t row = mt_row_bytes(mp->norm, mp->dim);
+    const bool same = desc1 == desc2 && kp1 == kp2 && n_images1 == n_images2 && !memcmp(offsets1, offsets2, ((size_t)n_images1 + 1) * 8);
+    const size_t s_d1 = align_up(n1 * row, 256), s_d2 = same ? 0 : align_up(n2 * row, 256), s_k1 = align_up((size_t)n1 * kd * 8, 256),
+                 s_k2 = same ? 0 : align_up((size_t)n2 * kd * 8, 256), s_sd = align_up((size_t)K * 4, 256), s_mo = align_up((size_t)K * 72, 256),
+                 s_ma = align_up((size_t)n_out * 4, 256), s_in = align_up((size_t)n_out, 256), s_st = align_up((size_t)K * 64, 256);
+    const size_t a_d2 = s_d1, a_k1 = a_d2 + s_d2, a_k2 = a_k1 + s_k1, a_sd = a_k2 + s_k2, a_mo = a_sd + s_sd, a_ma = a_mo + s_mo, a_in = a_ma + s_ma,
+                 a_st = a_in + s_in, a_all = a_st + s_st;
+    char *D = nullptr;
+    struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
+    HIPCHK(hipMalloc((void **)&D, a_all));
+    HIPCHK(hipMemcpy(D, (const char *)desc1 + offsets1[0] * row, n1 * row, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(D + a_k1, kp1 + offsets1[0] * kd, (size_t)n1 * kd * 8, hipMemcpyHostToDevice));
+    if (!same) {
+        HIPCHK(hipMemcpy(D + a_d2, (const char *)desc2 + offsets2[0] * row, n2 * row, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(D + a_k2, kp2 + offsets2[0] * kd, (size_t)n2 * kd * 8, hipMemcpyHostToDevice));
     }
+    HIPCHK(hipMemcpy(D + a_sd, seeds, (size_t)K * 4, hipMemcpyHostToDevice));
+    /* the device path takes store pointers with the stores' own offsets: these copies start at each store's first row */
+    std::vector<int64_t> o1(n_images1 + 1), o2(n_images2 + 1);
+    for (int i = 0; i <= n_images1; i++) o1[i] = offsets1[i] - offsets1[0];
+    for (int j = 0; j <= n_images2; j++) o2[j] = offsets2[j] - offsets2[0];
+    std::vector<int32_t> cnt(K), st((size_t)K * 16);
+    rc = match_verify_pairs_dev(homography, mp, D, same ? D : D + a_d2, o1.data(), o2.data(), (const double *)(D + a_k1),
+                                (const double *)(D + (same ? a_k1 : a_k2)), kd, rows, n_out, n_back, prm, (const uint32_t *)(D + a_sd), device, c->stream,
+                                (double *)(D + a_mo), (int32_t *)(D + a_ma), (uint8_t *)(D + a_in), (int32_t *)(D + a_st), cnt.data());
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(model, D + a_mo, (size_t)K * 72, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(match, D + a_ma, (size_t)n_out * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(inlier, D + a_in, (size_t)n_out, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(st.data(), D + a_st, (size_t)K * 64, hipMemcpyDeviceToHost));
+    std::vector<int64_t> out(K + 1), b1(K), b2(K);
+    for (int p = 0; p < K; p++) { out[p] = rows[p].out; b1[p] = rows[p].q; b2[p] = rows[p].t; }
+    out[K] = n_out;
+    rc = mv_rerun(c, homography, kd, K, prm, seeds, out.data(), b1.data(), b2.data(), kp1 + offsets1[0] * kd, kp2 + offsets2[0] * kd, match, model, inlier, st);
+    if (rc) return rc;
     if (stats) memcpy(stats, st.data(), (size_t)K * 64);
     if (counts) memcpy(counts, cnt.data(), (size_t)K * 4);
     return 0;

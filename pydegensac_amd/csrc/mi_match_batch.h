@@ -71,7 +71,9 @@ MT_HIDDEN int mt_batch_knn2(int norm, int words, const void *dq, const void *dt,
 MT_HIDDEN int mt_batch_fginn(int norm, int words, const void *dq, const void *dt, const double *kt, int kd, const int64_t *oq, const int64_t *ot,
                              int n_pairs, double r, int device, hipStream_t s, int32_t *idx, float *dist);
 /* ratio test (+ mutual check when d_back is set) and the rank of every kept query among its pair's kept queries; one
- * workgroup per pair.  d_off1 / d_off2: [K + 1] relative int32 row offsets on the device. */
+ * workgroup per pair.  d_off1 / d_off2: [K + 1] relative int32 row offsets on the device.  d_off1 says where the pair's idx / dist /
+ * keep / rank rows are, d_off2[p] (the only entry read) where its rows of d_back start: the pair-list form passes its output-row
+ * offsets and its back-row bases here. */
 MT_HIDDEN int mt_batch_filter_rank(const int32_t *d_idx, const float *d_dist, const int32_t *d_off1, const int32_t *d_off2, int n_pairs, float ratio,
                                    const int32_t *d_back, hipStream_t s, uint8_t *d_keep, int32_t *d_rank, int32_t *d_count);
 /* the estimator's input rows of the E eligible pairs: pts[est_off[e] + rank[i]] = kp rows of query i and of its nearest train row;
@@ -84,6 +86,26 @@ MT_HIDDEN int mt_batch_gather(int n_eligible, const int32_t *d_pair_of_e, const 
 MT_HIDDEN int mt_batch_scatter(int n_pairs, const int32_t *d_e_of_p, const int64_t *d_est_off, const int32_t *d_off1, const uint8_t *d_keep,
                                const int32_t *d_rank, const int32_t *d_idx, const double *d_model_e, const int32_t *d_stats_e, const uint8_t *d_mask_e,
                                hipStream_t s, double *d_model, int32_t *d_stats /*nullable*/, int32_t *d_match, uint8_t *d_inlier);
+
+/* ---- the pair-list form (include/mi_degensac.h mi_degensac_match_*_pairs*): image stores + (i, j) image indices ---- */
+/* the rows of list entry p, relative to the first row of each store: its first output row, its query rows in store 1 (q, nq), its
+ * train rows in store 2 (t, nt) and its first row in the back block of the mutual check's reverse search */
+struct mt_pair_rows { int32_t out, q, nq, t, nt, back; };
+/* checks the stores' offsets ([m + 1] each) and the list, fills rows [K] and the row totals.  EINVAL (message set) for bad offsets, an
+ * image index outside its store, or output / back rows beyond the batch path's row limit; needs no device */
+MT_HIDDEN int mt_pairs_layout(const int64_t *off1, int m1, const int64_t *off2, int m2, const int32_t *pairs, int n_pairs, mt_pair_rows *rows,
+                              int64_t *n_out, int64_t *n_back);
+/* the batched 2-NN over a pair list, dq / dt at the first row of store 1 / 2.  swap = 0: rows q .. q + nq of dq against t .. t + nt
+ * of dt into the output rows from `out`; swap = 1 (the reverse search): dq / dt are stores 2 / 1, rows t .. t + nt of dq against
+ * q .. q + nq of dt into the rows from `back`.  idx / dist [n_rows, 2] with n_rows the total of the side written */
+MT_HIDDEN int mt_pairs_knn2(int norm, int words, const void *dq, const void *dt, const mt_pair_rows *rows, int n_pairs, int n_rows, int swap, int device,
+                            hipStream_t s, int32_t *idx, float *dist);
+/* mt_batch_gather for a pair list: d_out [K + 1] output-row offsets (where keep / rank / idx live), d_q1 / d_t2 [K] the first keypoint
+ * row of the pair's query image in kp1 and of its train image in kp2 */
+MT_HIDDEN int mt_pairs_gather(int n_eligible, const int32_t *d_pair_of_e, const int64_t *d_est_off, const int32_t *d_out, const int32_t *d_q1,
+                              const int32_t *d_t2, const uint8_t *d_keep, const int32_t *d_rank, const int32_t *d_idx, const double *d_kp1,
+                              const double *d_kp2, int kp_dim, const uint32_t *d_seeds, hipStream_t s, double *d_pts1, double *d_pts2,
+                              uint32_t *d_seeds_e);
 
 /* ---- guided matching (mi_guided.hip) ---- */
 /* the gate of a model kind: th from px_th / error_type as fill_params derives it; EINVAL (message set) for a bad error_type or a

@@ -15,7 +15,8 @@
  * every thread keeps a 4 x 4 block of running sums in registers and its own running top-2 per query; the 16 threads
  * sharing a query merge their candidates at the end.  The train set is additionally split over blockIdx.y (see mt_knn2_kernel).
  * The batched form (mt_knn2_batch_kernel, mi_degensac_match_*_batch*) runs the same tile body over every pair's query tiles in one
- * launch and feeds the match-and-verify path in mi_degensac_host.inc (filter + rank, gather, scatter below). */
+ * launch and feeds the match-and-verify path in mi_degensac_host.inc (filter + rank, gather, scatter below).  The pair-list form
+ * (mt_knn2_pairs_kernel, mi_degensac_match_*_pairs*) runs it over image stores: rows stored once per image, a list of (i, j). */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -204,6 +205,25 @@ __global__ __launch_bounds__(256) void mt_knn2_batch_kernel(const uint32_t *q, c
         mt_store<NORM>(m, tl.x + threadIdx.x, n_rows, blockIdx.y, idx, dist, part);
 }
 
+/* The pair list (include/mi_degensac.h mi_degensac_match_knn2_pairs_dev): descriptors are stored once per image and a tile's answers
+ * no longer belong at its queries' own rows, so the tile record carries the tile's first output row next to the batched record:
+ * queries q0 .. q_end - 1 of the query store against the train rows t_b .. t_e - 1 of the train store, answers at the rows o0 ..
+ * of idx / dist (n_rows of them in all; the per-split partials are indexed by output row too).  The tile bodies, the split rule
+ * and mt_merge_kernel are those of the batch, so neither the split count nor the order of the tiles changes a result. */
+struct mt_ptile { int q0, q_end, t_b, t_e, o0, pad[3]; };
+
+template <int NORM, int NS = 0>
+__global__ __launch_bounds__(256) void mt_knn2_pairs_kernel(const uint32_t *q, const uint32_t *t, int words, const mt_ptile *tiles, int n_rows,
+                                                            int t_chunk, int32_t *idx, float *dist, mt_best *part)
+{
+    __shared__ mt_best merge[MT_Q][16];
+    const mt_ptile tl = tiles[blockIdx.x];
+    const int t_lo = tl.t_b + (int)blockIdx.y * t_chunk, t_hi = t_lo + t_chunk < tl.t_e ? t_lo + t_chunk : tl.t_e;
+    mt_best m;
+    if (mt_tile<NORM, NS>(q, tl.q0, tl.q_end, t, t_lo, t_hi, tl.t_b, words, merge, m))
+        mt_store<NORM>(m, tl.o0 + threadIdx.x, n_rows, blockIdx.y, idx, dist, part);
+}
+
 /* merge the per-split top-2 of every query (any order gives the same result: mt_push orders by (distance, index)) */
 __global__ void mt_merge_kernel(const mt_best *part, int splits, int n1, int l2, int32_t *idx, float *dist)
 {
@@ -284,6 +304,24 @@ __global__ __launch_bounds__(256) void mt_gather_kernel(const int32_t *pair_of_e
         if (!keep[i]) continue;
         const int64_t r = o + rank[i], j = b2 + idx[2 * i];
         for (int c = 0; c < kd; c++) { pts1[r * kd + c] = kp1[(int64_t)i * kd + c]; pts2[r * kd + c] = kp2[j * kd + c]; }
+    }
+}
+
+/* mt_gather_kernel for a pair list: keep / rank / idx live at the pair's output rows out[p] .., its keypoints at the rows q1[p] ..
+ * of store 1 and (train rows, pair-local in idx) t2[p] .. of store 2 */
+__global__ __launch_bounds__(256) void mt_gather_pairs_kernel(const int32_t *pair_of_e, const int64_t *est_off, const int32_t *out, const int32_t *q1,
+                                                              const int32_t *t2, const uint8_t *keep, const int32_t *rank, const int32_t *idx,
+                                                              const double *kp1, const double *kp2, int kd, const uint32_t *seeds, double *pts1,
+                                                              double *pts2, uint32_t *seeds_e)
+{
+    const int e = blockIdx.x, p = pair_of_e[e];
+    const int lo = out[p], hi = out[p + 1];
+    const int64_t o = est_off[e], b1 = (int64_t)q1[p] - lo, b2 = t2[p];
+    if (threadIdx.x == 0) seeds_e[e] = seeds[p];
+    for (int i = lo + (int)threadIdx.x; i < hi; i += 256) {
+        if (!keep[i]) continue;
+        const int64_t r = o + rank[i], a = b1 + i, j = b2 + idx[2 * i];
+        for (int c = 0; c < kd; c++) { pts1[r * kd + c] = kp1[a * kd + c]; pts2[r * kd + c] = kp2[j * kd + c]; }
     }
 }
 
@@ -582,6 +620,95 @@ extern "C" int mi_degensac_match_knn2_batch_dev(int norm, const void *d_desc1, c
     for (int p = 0; p <= n_pairs; p++) { o1[p] = offsets1_host[p] - offsets1_host[0]; o2[p] = offsets2_host[p] - offsets2_host[0]; }
     return mt_batch_knn2(norm, words, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words,
                          (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words, o1.data(), o2.data(), n_pairs, device, (hipStream_t)stream, d_idx + 2 * offsets1_host[0], d_dist + 2 * offsets1_host[0]);
+}
+
+/* ---- the pair-list form: host side ----------------------------------------------------------------------------------- */
+int mt_pairs_layout(const int64_t *off1, int m1, const int64_t *off2, int m2, const int32_t *pairs, int n_pairs, mt_pair_rows *rows,
+                    int64_t *n_out, int64_t *n_back)
+{
+    *n_out = *n_back = 0;
+    if (n_pairs < 0 || m1 < 0 || m2 < 0) { snprintf(mt_err, sizeof mt_err, "n_pairs, n_images1 and n_images2 must be >= 0"); return MI_DEGENSAC_EINVAL; }
+    if (n_pairs == 0) return 0;
+    if (!pairs) { snprintf(mt_err, sizeof mt_err, "the pair list is NULL"); return MI_DEGENSAC_EINVAL; }
+    if (!mt_check_offsets(off1, m1) || !mt_check_offsets(off2, m2)) {
+        snprintf(mt_err, sizeof mt_err, "store offsets must be non-negative and non-decreasing, with at most 0x3fffffff rows in a store"); return MI_DEGENSAC_EINVAL; }
+    int64_t o = 0, b = 0;
+    for (int p = 0; p < n_pairs; p++) {
+        const int i = pairs[2 * p], j = pairs[2 * p + 1];
+        if (i < 0 || i >= m1 || j < 0 || j >= m2) {
+            snprintf(mt_err, sizeof mt_err, "pair %d = (%d, %d): image index outside its store (%d and %d images)", p, i, j, m1, m2); return MI_DEGENSAC_EINVAL; }
+        const int64_t nq = off1[i + 1] - off1[i], nt = off2[j + 1] - off2[j];
+        rows[p] = mt_pair_rows{(int32_t)o, (int32_t)(off1[i] - off1[0]), (int32_t)nq, (int32_t)(off2[j] - off2[0]), (int32_t)nt, (int32_t)b};
+        o += nq; b += nt;
+        if (o > 0x3fffffff || b > 0x3fffffff) {
+            snprintf(mt_err, sizeof mt_err, "too many rows in one pair list: the output rows and the reverse-search rows are limited to 0x3fffffff each");
+            return MI_DEGENSAC_EINVAL; }
+    }
+    *n_out = o; *n_back = b;
+    return 0;
+}
+
+/* mt_batch_knn2 over a pair list: the same tiles per pair (64 queries from the image's first row on), the same split rule */
+int mt_pairs_knn2(int norm, int words, const void *dq, const void *dt, const mt_pair_rows *rows, int n_pairs, int n_rows, int swap, int device,
+                  hipStream_t s, int32_t *idx, float *dist)
+{
+    if (n_rows == 0) return 0;
+    std::vector<mt_ptile> tiles;
+    int max_n2 = 0;
+    for (int p = 0; p < n_pairs; p++) {
+        const mt_pair_rows &r = rows[p];
+        const int qb = swap ? r.t : r.q, nq = swap ? r.nt : r.nq, tb = swap ? r.q : r.t, nt = swap ? r.nq : r.nt, ob = swap ? r.back : r.out;
+        if (nt > max_n2) max_n2 = nt;
+        for (int k = 0; k < nq; k += MT_Q) tiles.push_back(mt_ptile{qb + k, qb + nq, tb, tb + nt, ob + k, {0, 0, 0}});
+    }
+    const int qtiles = (int)tiles.size();
+    int t_chunk, splits; mt_batch_split(qtiles, max_n2, device, &t_chunk, &splits);
+    const size_t b_tiles = ((size_t)qtiles * sizeof(mt_ptile) + 255) / 256 * 256, b_part = splits > 1 ? (size_t)splits * n_rows * sizeof(mt_best) : 0;
+    char *buf = nullptr;
+    MTCHK(hipMallocAsync((void **)&buf, b_tiles + b_part, s));
+    int rc = mt_batch_upload(device, s, tiles.data(), (size_t)qtiles * sizeof(mt_ptile), buf);
+    if (rc) { (void)hipFreeAsync(buf, s); return rc; }
+    mt_best *part = splits > 1 ? (mt_best *)(buf + b_tiles) : nullptr;
+    const dim3 grid(qtiles, splits), block(256);
+    MT_LAUNCH_NORM(mt_knn2_pairs_kernel, norm, words, grid, block, s, (const uint32_t *)dq, (const uint32_t *)dt, words, (const mt_ptile *)buf, n_rows,
+        t_chunk, idx, dist, part);
+    hipError_t le = hipGetLastError();
+    if (le == hipSuccess && part) {
+        hipLaunchKernelGGL(mt_merge_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, s, part, splits, n_rows, norm != MI_DEGENSAC_NORM_HAMMING ? 1 : 0, idx,
+            dist);
+        le = hipGetLastError();
+    }
+    (void)hipFreeAsync(buf, s);
+    MTCHK(le);
+    return 0;
+}
+
+int mt_pairs_gather(int n_eligible, const int32_t *d_pair_of_e, const int64_t *d_est_off, const int32_t *d_out, const int32_t *d_q1, const int32_t *d_t2,
+                    const uint8_t *d_keep, const int32_t *d_rank, const int32_t *d_idx, const double *d_kp1, const double *d_kp2, int kp_dim,
+                    const uint32_t *d_seeds, hipStream_t s, double *d_pts1, double *d_pts2, uint32_t *d_seeds_e)
+{
+    if (n_eligible <= 0) return 0;
+    hipLaunchKernelGGL(mt_gather_pairs_kernel, dim3(n_eligible), dim3(256), 0, s, d_pair_of_e, d_est_off, d_out, d_q1, d_t2, d_keep, d_rank, d_idx, d_kp1,
+        d_kp2, kp_dim, d_seeds, d_pts1, d_pts2, d_seeds_e);
+    MTCHK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mi_degensac_match_knn2_pairs_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host, int n_images1,
+                                                const int64_t *offsets2_host, int n_images2, const int32_t *pairs_host, int n_pairs, int dim,
+                                                int device, void *stream, int32_t *d_idx, float *d_dist)
+{
+    if (n_pairs < 0) { snprintf(mt_err, sizeof mt_err, "n_pairs < 0"); return MI_DEGENSAC_EINVAL; }
+    int rc = mt_check_norm(norm, dim); if (rc) return rc;
+    const int words = mt_row_words(norm, dim);
+    if (n_pairs == 0) return 0;
+    std::vector<mt_pair_rows> rows(n_pairs);
+    int64_t n_out, n_back;
+    rc = mt_pairs_layout(offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, rows.data(), &n_out, &n_back); if (rc) return rc;
+    if ((n_out > 0 && (!d_desc1 || !d_idx || !d_dist)) || (n_out > 0 && n_back > 0 && !d_desc2)) { snprintf(mt_err, sizeof mt_err, "NULL argument"); return MI_DEGENSAC_EINVAL; }
+    MtDevGuard g; rc = g.enter(device); if (rc) return rc;
+    return mt_pairs_knn2(norm, words, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words, (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words,
+                         rows.data(), n_pairs, (int)n_out, 0, device, (hipStream_t)stream, d_idx, d_dist);
 }
 
 #include "mi_fginn.h"

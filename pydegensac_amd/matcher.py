@@ -134,13 +134,8 @@ def _dtype_name(dt):
     return s[6:] if s.startswith("torch.") else np.dtype(dt).name
 
 
-def check_match_verify_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype, counts1, counts2,
-                            fginn_th=None):
-    """The argument checks of the batched match-and-verify calls, on shapes and dtype names only (numpy or torch).  Returns
-    (norm code, "xy" for float64 rows [n, 2] / [n, 6] or "kpts" for float32 keypoints [n, 4], offsets1, offsets2); raises ValueError.
-    fginn_th: None, or the FGINN radius (finite and >= 0)."""
-    if fginn_th is not None:
-        check_fginn_th(fginn_th)
+def _check_sides(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype):
+    """model, ratio, norm and the descriptor / keypoint arrays of the two sides, on shapes and dtype names -> (norm code, "xy" / "kpts")"""
     if model not in ("F", "H"):
         raise ValueError("model should be 'F' or 'H'")
     try:
@@ -179,6 +174,17 @@ def check_match_verify_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2
         raise ValueError("kps1 and kps2 should have the same layout")
     if k1_shape[0] != d1_shape[0] or k2_shape[0] != d2_shape[0]:
         raise ValueError("one keypoint row per descriptor row")
+    return _NORMS[norm], kinds[0][0]
+
+
+def check_match_verify_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype, counts1, counts2,
+                            fginn_th=None):
+    """The argument checks of the batched match-and-verify calls, on shapes and dtype names only (numpy or torch).  Returns
+    (norm code, "xy" for float64 rows [n, 2] / [n, 6] or "kpts" for float32 keypoints [n, 4], offsets1, offsets2); raises ValueError.
+    fginn_th: None, or the FGINN radius (finite and >= 0)."""
+    if fginn_th is not None:
+        check_fginn_th(fginn_th)
+    code, kind = _check_sides(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype)
     c1 = np.asarray(counts1); c2 = np.asarray(counts2)
     if c1.ndim != 1 or c2.ndim != 1 or len(c1) != len(c2):
         raise ValueError("counts1 and counts2 should be 1-D with one entry per pair")
@@ -190,7 +196,64 @@ def check_match_verify_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2
     o2 = np.zeros(len(c2) + 1, np.int64); np.cumsum(c2, out=o2[1:])
     if o1[-1] != d1_shape[0] or o2[-1] != d2_shape[0]:
         raise ValueError("counts do not add up to the number of descriptor rows")
-    return _NORMS[norm], kinds[0][0], o1, o2
+    return code, kind, o1, o2
+
+
+def check_match_pairs_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype, counts1, counts2, pairs,
+                           seeds=None, guided=False, fginn_th=None):
+    """The argument checks of the pair-list calls (knn_match_pairs_tensors, match_and_verify_pairs[_tensors]), on shapes and dtype names
+    (numpy or torch) and on the list itself.  counts1 [M1] / counts2 [M2] are the rows per image of the two stores, pairs an integer
+    array [K, 2] with K >= 1 of (image of store 1, image of store 2); seeds None or one per list entry.  guided and fginn_th are not
+    part of the pair-list calls and are refused.  Returns (norm code, "xy" / "kpts", offsets1 [M1 + 1], offsets2 [M2 + 1], pairs as
+    contiguous int32 [K, 2], pair_offsets int64 [K + 1], seeds as uint32 [K] or None); raises ValueError."""
+    if guided:
+        raise ValueError("guided matching is not part of the pair-list calls: run guided_match_batch on the models they return")
+    if fginn_th is not None:
+        raise ValueError("fginn_th (the FGINN ratio test) is not part of the pair-list calls: use match_and_verify_batch")
+    code, kind = _check_sides(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype)
+    offs = []
+    for c, rows in ((counts1, d1_shape[0]), (counts2, d2_shape[0])):
+        c = np.asarray(c)
+        if c.ndim != 1:
+            raise ValueError("counts1 and counts2 should be 1-D with one entry per image")
+        if c.size and not np.issubdtype(c.dtype, np.integer):
+            raise ValueError("counts should be integers")
+        if (c < 0).any():
+            raise ValueError("counts should be >= 0")
+        o = np.zeros(len(c) + 1, np.int64); np.cumsum(c, out=o[1:])
+        if o[-1] != rows:
+            raise ValueError("counts do not add up to the number of descriptor rows")
+        offs.append(o)
+    pr = np.asarray(pairs)
+    if pr.ndim != 2 or pr.shape[1] != 2 or not np.issubdtype(pr.dtype, np.integer):
+        raise ValueError("pairs should be an integer array [K, 2] of (image of store 1, image of store 2)")
+    K = pr.shape[0]
+    if K == 0:
+        raise ValueError("at least one pair")
+    m1, m2 = len(offs[0]) - 1, len(offs[1]) - 1
+    if (pr < 0).any() or (pr[:, 0] >= m1).any() or (pr[:, 1] >= m2).any():
+        raise ValueError(f"pairs hold an image index outside its store ({m1} and {m2} images)")
+    pr = np.ascontiguousarray(pr, np.int32)
+    po = np.zeros(K + 1, np.int64); np.cumsum(np.diff(offs[0])[pr[:, 0]], out=po[1:])
+    if po[-1] > 0x3fffffff or np.diff(offs[1])[pr[:, 1]].sum() > 0x3fffffff:
+        raise ValueError("too many rows in one pair list")
+    if seeds is not None:
+        sd = np.asarray(seeds)
+        if sd.shape != (K,):
+            raise ValueError("one seed per pair")
+        seeds = np.ascontiguousarray(sd.astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+    return code, kind, offs[0], offs[1], pr, po, seeds
+
+
+def exhaustive_pairs(n, ordered=False):
+    """The pair list of a collection of n images matched exhaustively: every (i, j) with i < j in lexicographic order, [n (n - 1) / 2, 2],
+    or with ordered=True every (i, j) with i != j, [n (n - 1), 2] (the ratio test is not symmetric).  int64."""
+    n = int(n)
+    if n < 0:
+        raise ValueError("n should be >= 0")
+    i, j = np.divmod(np.arange(n * n, dtype=np.int64), max(n, 1))
+    sel = (i != j) if ordered else (i < j)
+    return np.stack([i[sel], j[sel]], axis=1)
 
 
 def check_fginn_th(fginn_th, name="fginn_th"):
@@ -394,3 +457,72 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
         M = out
     res = (M, [match[o1[p]:o1[p + 1]] for p in range(K)], [inl[o1[p]:o1[p + 1]].astype(bool) for p in range(K)])
     return res + ([gm[o1[p]:o1[p + 1]] for p in range(K)],) if guided else res
+
+
+def match_and_verify_pairs(kps_list, desc_list, pairs, model="F", ratio=0.9, mutual=False, px_th=None, conf=None, max_iters=None,
+                           laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True, enable_degeneracy_check=True, seeds=None,
+                           norm=None, device=0, guided=False, fginn_th=None, kps2_list=None, desc2_list=None):
+    """match_and_verify_batch over a pair list: descriptors and keypoints are given ONCE per image (kps_list[i], desc_list[i]) and
+    pairs [K, 2] says which (i, j) to run, queries = image i, train set = image j (exhaustive_pairs(n) for a whole collection).  With
+    kps2_list / desc2_list the train images come from that second store (queries against a database), else from the same one.  The
+    list may hold self pairs, repeats, both orders and any order; images may be empty or unused.  Each store is uploaded once, whatever
+    the number of pairs.  Per pair the results are bit for bit those of match_and_verify_batch on the pair's copied arrays with the
+    same seeds (one per list entry, default parallel.pair_seeds(0, K)).  Returns (models [K, 3, 3], [match_p], [inlier_p]) as
+    match_and_verify_batch; guided and fginn_th are not part of this call (ValueError).  last_stats() holds the per-pair statistics."""
+    from . import api, parallel
+    if (kps2_list is None) != (desc2_list is None):
+        raise ValueError("kps2_list and desc2_list go together")
+    one = desc2_list is None
+    stores = []
+    for kl, dl in ((kps_list, desc_list),) if one else ((kps_list, desc_list), (kps2_list, desc2_list)):
+        if len(kl) != len(dl):
+            raise ValueError("one keypoint array per descriptor array")
+        if len(dl) == 0:
+            raise ValueError("at least one image per store")
+        d = [np.asarray(x) for x in dl]; k = [np.asarray(x) for x in kl]
+        for lst in (d, k):
+            if any(x.ndim != 2 or x.dtype != lst[0].dtype or x.shape[1] != lst[0].shape[1] for x in lst):
+                raise ValueError("every image's arrays should be 2-D with the dtype and width of image 0")
+        c = [x.shape[0] for x in d]
+        if [x.shape[0] for x in k] != c:
+            raise ValueError("one keypoint row per descriptor row")
+        stores.append((np.concatenate(d), np.concatenate(k), np.asarray(c, np.int64)))
+    (A, K1, c1), (B, K2, c2) = stores[0], stores[-1]
+    code, kind, o1, o2, pr, po, sd = check_match_pairs_args(model, ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape,
+                                                            K2.dtype, c1, c2, pairs, seeds, guided, fginn_th)
+    prm = estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
+    K = len(pr)
+    if sd is None:
+        sd = np.ascontiguousarray(np.asarray(parallel.pair_seeds(0, K), dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+
+    def prep(D, Kp):
+        if code != NORM_L2:
+            D = _pad_words(D, D)[0]
+        if kind == "kpts":
+            Kp = kpts_to_xyA(Kp, device)
+        return np.ascontiguousarray(D), np.ascontiguousarray(Kp, np.float64)
+    A, K1 = prep(A, K1)
+    B, K2 = (A, K1) if one else prep(B, K2)              # one store: the same arrays on both sides, uploaded once
+    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual)
+    n = int(po[-1])
+    M = np.zeros((K, 9)); match = np.full(n, -1, np.int32); inl = np.zeros(n, np.uint8)
+    st = np.zeros((K, 16), np.int32); cnt = np.zeros(K, np.int32)
+    lp = C.POINTER(C.c_int64); ip = C.POINTER(C.c_int32)
+    rc = _lib.lib().mi_degensac_match_verify_pairs(1 if model == "H" else 0, C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p),
+                                                   o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, _lib.dptr(K1), _lib.dptr(K2),
+                                                   K1.shape[1], pr.ctypes.data_as(ip), K, C.byref(prm), sd.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                   int(device), _lib.dptr(M), match.ctypes.data_as(ip), inl.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                   st.ctypes.data_as(ip), cnt.ctypes.data_as(ip))
+    _lib.check(rc)
+    stats = [_lib.stats_dict(s) for s in st]
+    for d, c in zip(stats, cnt):
+        d["tentatives"] = int(c)
+    api._tls.stats = stats
+    M = M.reshape(K, 3, 3)
+    if model == "H":
+        out = np.zeros_like(M)
+        for i in range(K):
+            if np.abs(M[i]).sum() != 0:
+                out[i] = np.linalg.inv(M[i].T)
+        M = out
+    return M, [match[po[p]:po[p + 1]] for p in range(K)], [inl[po[p]:po[p + 1]].astype(bool) for p in range(K)]

@@ -134,3 +134,29 @@ def ellipse_pairs(n=1000, inlier_ratio=0.3, sigma=1.0, seed=0, laf_noise=0.05, H
     u = np.stack([x1[:, 0], x1[:, 1], L[:, 0, 0], L[:, 1, 0], L[:, 1, 1], x2[:, 0], x2[:, 1], a, b, c], 1)
     perm = rng.permutation(n)
     return np.ascontiguousarray(u[perm]), lab[perm]
+
+
+def image_collection(m=8, n=500, inlier_ratio=0.5, sigma=0.1, dim=64, seed=0, desc_sigma=0.15):
+    """An image collection for the pair-list calls: m pinhole views on an arc around one random 3-D cloud, n keypoints each.  In
+    every image a share inlier_ratio of the keypoints are projections of cloud points (a different random subset per image, noise
+    sigma px) whose descriptor is the point's own plus desc_sigma noise; the rest are uniform clutter with random descriptors; rows
+    are permuted per image.  Any two images share about inlier_ratio^2 n points and one epipolar geometry.
+    Returns ([kps_i [n, 2] float64], [desc_i [n, dim] float32])."""
+    rng = np.random.default_rng(seed)
+    X = np.stack([rng.uniform(-2, 2, n), rng.uniform(-1.5, 1.5, n), rng.uniform(4, 8, n)], 1)
+    base = rng.normal(size=(n, dim)).astype(np.float32)
+    K = np.array([[FOCAL, 0, IMG_W / 2], [0, FOCAL, IMG_H / 2], [0, 0, 1.0]])
+    n_in = int(round(n * inlier_ratio))
+    kps, descs = [], []
+    for i in range(m):
+        a = 0.5 * (i / max(m - 1, 1) - 0.5)
+        R = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
+        t = np.array([-6.0 * np.sin(a), 0.05 * i / max(m, 1), 6.0 * (1 - np.cos(a))])
+        seen = rng.permutation(n)[:n_in]
+        p = np.stack([rng.uniform(0, IMG_W, n), rng.uniform(0, IMG_H, n)], 1)
+        d = rng.normal(size=(n, dim)).astype(np.float32)
+        p[:n_in] = _project(K, R, t, X[seen]) + rng.normal(0, sigma, (n_in, 2))
+        d[:n_in] = base[seen] + desc_sigma * rng.normal(size=(n_in, dim)).astype(np.float32)
+        perm = rng.permutation(n)
+        kps.append(np.ascontiguousarray(p[perm])); descs.append(np.ascontiguousarray(d[perm]))
+    return kps, descs

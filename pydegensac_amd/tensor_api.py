@@ -376,3 +376,92 @@ def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, m
         M = torch.where(found, inv, torch.zeros_like(M))
     res = (M, match, inlier.to(torch.bool), stats, cnt.astype(np.int64))
     return res + (gm,) if guided else res
+
+
+# ---- the pair-list form: image stores + (i, j) image indices (include/mi_degensac.h mi_degensac_match_*_pairs*) ----
+def knn_match_pairs_tensors(desc1, desc2, counts1, counts2, pairs, norm=None):
+    """knn_match_batch_tensors over a pair list.  desc1 / desc2 are image stores: image i of store 1 is the next counts1[i] rows of desc1,
+    image j of store 2 the next counts2[j] rows of desc2 (the same tensor may be passed twice: a collection against itself).  pairs:
+    integer array [K, 2]; entry p = (i, j) runs image i's rows as queries against image j's rows.  Any list is fine: self pairs,
+    repeats, both orders, any order; images may be empty or unused.  No descriptor row is copied.  Returns (idx [N, 2] int32 with
+    indices LOCAL to image j, dist [N, 2] float32, pair_offsets [K + 1] host int64): pair p owns the rows pair_offsets[p] ..
+    pair_offsets[p + 1], counts1[pairs[p, 0]] of them, and they are bit for bit what knn_match_batch_tensors returns for the pair's
+    copied rows.  Asynchronous on the current stream."""
+    import torch
+    from . import matcher
+    if not (isinstance(desc1, torch.Tensor) and isinstance(desc2, torch.Tensor)):
+        raise ValueError("descriptors must be torch tensors on a ROCm device")
+    code, _, o1, o2, pr, po, _ = matcher.check_match_pairs_args("F", 1.0, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
+                                                                (desc1.shape[0], 2), np.float64, (desc2.shape[0], 2), np.float64, counts1, counts2,
+                                                                pairs)
+    a, b = _desc_pair(desc1, desc2)
+    dev = a.device; n = int(po[-1]); K = len(pr)
+    idx = torch.full((n, 2), -1, dtype=torch.int32, device=dev)
+    dist = torch.full((n, 2), float("inf"), dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    lp = C.POINTER(C.c_int64)
+    rc = _lib.lib().mi_degensac_match_knn2_pairs_dev(code, a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp),
+                                                     len(o2) - 1, pr.ctypes.data_as(C.POINTER(C.c_int32)), K, int(a.shape[1]), dev.index or 0,
+                                                     C.c_void_p(stream.cuda_stream), idx.data_ptr(), dist.data_ptr())
+    _lib.check_match(rc)
+    for t in (a, b):
+        t.record_stream(stream)
+    return idx, dist, po
+
+
+def match_and_verify_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
+                                   max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
+                                   enable_degeneracy_check=True, seeds=None, guided=False, norm=None, fginn_th=None):
+    """match_and_verify_batch_tensors over a pair list: kps / desc are image stores (counts1 / counts2 rows per image, as for
+    knn_match_pairs_tensors; pass the same tensors on both sides for a collection matched against itself) and pairs [K, 2] lists the
+    (i, j) to run, e.g. matcher.exhaustive_pairs(M).  Descriptors and keypoints stay where they are: the device holds M images' rows,
+    not 2 K.  float32 [N, 4] keypoints go through kpts_to_xyA_tensors once per store.  seeds: one per list entry, default
+    parallel.pair_seeds(0, K).  Per pair every output is bit for bit that of match_and_verify_batch_tensors on the pair's copied rows
+    with the same seeds; the call synchronises exactly once (the read of the tentative counts).
+    Returns (model [K, 3, 3], match [N] int32 = train row local to image j or -1, inlier [N] bool, stats [K, 16], n_tentatives [K]
+    numpy int64, pair_offsets [K + 1] host int64) with N = pair_offsets[K]: the per-query outputs lie pair after pair in list order.
+    guided=True and fginn_th are not part of this call (ValueError): both stages keep their batched entry points."""
+    import torch
+    from . import matcher, parallel
+    ts = (kps1, kps2, desc1, desc2)
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
+    code, kind, o1, o2, pr, po, sd = matcher.check_match_pairs_args(model, ratio, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape),
+                                                                    desc2.dtype, tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype,
+                                                                    counts1, counts2, pairs, seeds, guided, fginn_th)
+    if any(t.device != desc1.device for t in ts):
+        raise ValueError("kps1, kps2, desc1 and desc2 must live on the same ROCm device")
+    prm = matcher.estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
+    a, b = _desc_pair(desc1, desc2)
+    dev = a.device; K = len(pr); n = int(po[-1])
+    conv = kpts_to_xyA_tensors if kind == "kpts" else (lambda k: k.contiguous())
+    k1 = conv(kps1); k2 = k1 if kps2 is kps1 else conv(kps2)          # once per store, not per pair
+    if sd is None:
+        sd = (np.asarray(parallel.pair_seeds(0, K), dtype=np.int64) & 0xFFFFFFFF).astype(np.uint32)
+    # pinned + non_blocking: a pageable copy would wait for the stream (the call's one synchronisation is the count read)
+    d_seeds = torch.from_numpy(sd.view(np.int32)).pin_memory().to(dev, non_blocking=True)
+    M = torch.zeros((K, 9), dtype=torch.float64, device=dev)
+    match = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    inlier = torch.zeros(n, dtype=torch.uint8, device=dev)
+    stats = torch.zeros((K, 16), dtype=torch.int32, device=dev)
+    cnt = np.zeros(K, np.int32)
+    mp = _lib.MatchParams(code, a.shape[1], ratio, mutual)
+    stream = torch.cuda.current_stream(dev)
+    lp = C.POINTER(C.c_int64); ip = C.POINTER(C.c_int32)
+    rc = _lib.lib().mi_degensac_match_verify_pairs_dev(1 if model == "H" else 0, C.byref(mp), a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(lp),
+                                                       len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]),
+                                                       pr.ctypes.data_as(ip), K, C.byref(prm), d_seeds.data_ptr(), dev.index or 0,
+                                                       C.c_void_p(stream.cuda_stream), M.data_ptr(), match.data_ptr(), inlier.data_ptr(),
+                                                       stats.data_ptr(), cnt.ctypes.data_as(ip))
+    _lib.check(rc)
+    # the estimator and the scatter read these asynchronously: keep them alive until the stream reaches this point
+    for t in (a, b, k1, k2, d_seeds):
+        t.record_stream(stream)
+    M = M.view(K, 3, 3)
+    if model == "H":
+        # inv(H_c^T) where a model was found, without a host round trip: short / failed pairs invert the identity and are zeroed
+        found = (M.abs().sum(dim=(1, 2)) != 0).view(K, 1, 1)
+        eye = torch.eye(3, dtype=M.dtype, device=dev).expand(K, 3, 3)
+        inv = torch.linalg.inv_ex(torch.where(found, M.transpose(1, 2), eye)).inverse      # inv_ex: no error check, no sync
+        M = torch.where(found, inv, torch.zeros_like(M))
+    return M, match, inlier.to(torch.bool), stats, cnt.astype(np.int64), po
