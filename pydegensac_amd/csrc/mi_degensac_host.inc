@@ -1097,10 +1097,10 @@ struct MvBlocks {
     ~MvBlocks() { if (a) (void)hipFreeAsync(a, s); if (b) (void)hipFreeAsync(b, s); }
 };
 
-/* Where pair p's rows are, as int32 tables on the device.  out [K + 1]: its rows of idx / dist / keep / rank / match / inlier.  The
- * ragged batch keeps its keypoints at those same rows and its train rows from t2[p] (q1 = null); a pair list reads the query image's
- * keypoints from row q1[p] of kp1 and the train image's from row t2[p] of kp2. */
-struct MvRows { const int32_t *out, *q1, *t2; };
+/* Where pair p's rows are, as int32 tables on the device (columns of mt_pair_rows).  out [K + 1]: its rows of idx / dist / keep / rank /
+ * match / inlier; q1 / t2 [K]: the first keypoint row of its query image in kp1 and of its train image in kp2; back [K]: its first row
+ * of the reverse search. */
+struct MvRows { const int32_t *out, *q1, *t2, *back; };
 
 /* the second half of a match-and-verify call, after the filter has written keep / rank / cnt on s */
 static int mv_estimate(int homography, int K, int kd, const mi_degensac_params *prm, const MvRows &R, const int32_t *cnt, const uint8_t *keep,
@@ -1134,8 +1134,7 @@ static int mv_estimate(int homography, int K, int kd, const mi_degensac_params *
     int32_t *stats_e = (int32_t *)(B + g_stats); uint8_t *mask_e = (uint8_t *)(B + g_mask);
     rc = match_rc(mt_batch_upload(device, s, tab.data(), c_all, B)); if (rc) return rc;
     if (E > 0) {
-        rc = match_rc(R.q1 ? mt_pairs_gather(E, d_poe, d_eoff, R.out, R.q1, R.t2, keep, rank, idx, kp1, kp2, kd, d_seeds, s, pts1, pts2, seeds_e)
-                           : mt_batch_gather(E, d_poe, d_eoff, R.out, R.t2, keep, rank, idx, kp1, kp2, kd, d_seeds, s, pts1, pts2, seeds_e));
+        rc = match_rc(mt_batch_gather(E, d_poe, d_eoff, R.out, R.q1, R.t2, keep, rank, idx, kp1, kp2, kd, d_seeds, s, pts1, pts2, seeds_e));
         if (rc) return rc;
         rc = launch_batch(homography, pts1, pts2, d_eoff, est_off.data(), E, kd, prm, seeds_e, device, s, model_e, mask_e, stats_e);
         if (rc) return rc;
@@ -1143,50 +1142,73 @@ static int mv_estimate(int homography, int K, int kd, const mi_degensac_params *
     return match_rc(mt_batch_scatter(K, d_eop, d_eoff, R.out, keep, rank, idx, model_e, stats_e, mask_e, s, d_model, d_stats, match, inlier));
 }
 
-static int match_verify_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const int64_t *off1,
-                            const int64_t *off2, const double *d_kp1, const double *d_kp2, int kd, int K, const mi_degensac_params *prm,
-                            const uint32_t *d_seeds, int device, hipStream_t s, double *d_model, int32_t *d_match, uint8_t *d_inlier,
-                            int32_t *d_stats, int32_t *h_counts)
+/* the pair list's refusals and its rows (see the pair-list section below) */
+static int mvp_check(int homography, const mi_degensac_match_params *mp, int kd, const int64_t *off1, int m1, const int64_t *off2, int m2,
+                     const int32_t *pairs, int K, std::vector<mt_pair_rows> &rows, int64_t *n_out, int64_t *n_back)
 {
-    int rc = mv_check(homography, mp, off1, off2, kd, K); if (rc) return rc;
+    int rc = mv_check_params(homography, mp, kd, K); if (rc) return rc;
+    int fginn; double r; (void)mt_second_nn(mp, &fginn, &r);
+    if (fginn) { set_err("the FGINN rule (second_nn = 1) is not part of the pair-list entry points: use mi_degensac_match_verify_batch*"); return MI_DEGENSAC_EINVAL; }
+    *n_out = *n_back = 0;
     if (K == 0) return 0;
-    dg_params chk; rc = fill_params(prm, homography, kd, &chk); if (rc) return rc;
+    rows.resize(K);
+    return match_rc(mt_pairs_layout(off1, m1, off2, m2, pairs, K, rows.data(), n_out, n_back));
+}
+
+static int mv_check_prm(const mi_degensac_params *prm, int homography, int kd) { dg_params chk; return fill_params(prm, homography, kd, &chk); }
+static int mv_check_device(int device)
+{
     if (device < 0 || device >= 64) { set_err("bad device index"); return MI_DEGENSAC_EINVAL; }
     if (mi_degensac_device_count() == 0) { set_err("no HIP device: this library has no CPU path"); return MI_DEGENSAC_ENODEV; }
-    const int64_t n1 = off1[K] - off1[0], n2 = off2[K] - off2[0];
-    if (!d_seeds || !d_model || (n1 > 0 && (!d_desc1 || !d_kp1 || !d_match || !d_inlier)) || (n2 > 0 && (!d_desc2 || !d_kp2))) {
+    return 0;
+}
+static int mv_check_null(const void *d_desc1, const void *d_desc2, const double *d_kp1, const double *d_kp2, int64_t n_out, int64_t n_back,
+                         const uint32_t *d_seeds, const double *d_model, const int32_t *d_match, const uint8_t *d_inlier)
+{
+    if (!d_seeds || !d_model || (n_out > 0 && (!d_desc1 || !d_kp1 || !d_match || !d_inlier)) || (n_back > 0 && (!d_desc2 || !d_kp2))) {
         set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
-    DevGuard g; rc = g.enter(device); if (rc) return rc;
+    return 0;
+}
+
+/* The device path of both forms, arguments checked: pair p's rows are rows[p], n_out output rows and n_back rows of the reverse search
+ * in all; side 1 / 2 (descriptors and keypoints) start at row r1 / r2 of the arrays passed; match / inlier are at the first output row.
+ * fg_o1 / fg_o2: the relative offsets of a ragged batch, which the FGINN step takes (a pair list has refused FGINN before it gets here). */
+static int match_verify_rows(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const double *d_kp1,
+                             const double *d_kp2, int64_t r1, int64_t r2, int kd, const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t n_back,
+                             const int64_t *fg_o1, const int64_t *fg_o2, const mi_degensac_params *prm, const uint32_t *d_seeds, int device,
+                             hipStream_t s, double *d_model, int32_t *match, uint8_t *inlier, int32_t *d_stats, int32_t *h_counts)
+{
+    const int K = (int)rows.size();
+    DevGuard g; int rc = g.enter(device); if (rc) return rc;
     const int words = mt_row_words(mp->norm, mp->dim);
     const bool mutual = mp->mutual != 0;
-    /* relative offsets; every row pointer moves to the batch's first row */
-    std::vector<int64_t> o1(K + 1), o2(K + 1); std::vector<int32_t> o32(2 * (size_t)(K + 1));
-    for (int p = 0; p <= K; p++) { o1[p] = off1[p] - off1[0]; o2[p] = off2[p] - off2[0]; o32[p] = (int32_t)o1[p]; o32[K + 1 + p] = (int32_t)o2[p]; }
-    const uint32_t *q1 = (const uint32_t *)d_desc1 + (size_t)off1[0] * words, *q2 = (const uint32_t *)d_desc2 + (size_t)off2[0] * words;
-    const double *kp1 = d_kp1 + (size_t)off1[0] * kd, *kp2 = d_kp2 + (size_t)off2[0] * kd;
-    int32_t *match = d_match + off1[0]; uint8_t *inlier = d_inlier + off1[0];
+    /* every row pointer moves to its side's first row; the tables: out [K + 1] | q1 [K] | t2 [K] | back [K] */
+    const uint32_t *q1 = (const uint32_t *)d_desc1 + (size_t)r1 * words, *q2 = (const uint32_t *)d_desc2 + (size_t)r2 * words;
+    const double *kp1 = d_kp1 + (size_t)r1 * kd, *kp2 = d_kp2 + (size_t)r2 * kd;
+    std::vector<int32_t> tab(4 * (size_t)K + 1);
+    for (int p = 0; p < K; p++) { tab[p] = rows[p].out; tab[K + 1 + p] = rows[p].q; tab[2 * K + 1 + p] = rows[p].t; tab[3 * K + 1 + p] = rows[p].back; }
+    tab[K] = (int32_t)n_out;
 
-    /* block A: offsets, forward (and backward) 2-NN, keep / rank / count */
-    const size_t b_off = align_up(o32.size() * 4, 256), b_idx = align_up((size_t)n1 * 8, 256), b_bidx = mutual ? align_up((size_t)n2 * 8, 256) : 0,
-                 b_keep = align_up((size_t)n1, 256), b_cnt = align_up((size_t)K * 4, 256);
-    const size_t a_idx = b_off, a_dist = a_idx + b_idx, a_bidx = a_dist + b_idx, a_bdist = a_bidx + b_bidx, a_keep = a_bdist + b_bidx,
+    /* block A: tables, forward (and backward) 2-NN, keep / rank / count */
+    const size_t b_tab = align_up(tab.size() * 4, 256), b_idx = align_up((size_t)n_out * 8, 256), b_bidx = mutual ? align_up((size_t)n_back * 8, 256) : 0,
+                 b_keep = align_up((size_t)n_out, 256), b_cnt = align_up((size_t)K * 4, 256);
+    const size_t a_idx = b_tab, a_dist = a_idx + b_idx, a_bidx = a_dist + b_idx, a_bdist = a_bidx + b_bidx, a_keep = a_bdist + b_bidx,
                  a_rank = a_keep + b_keep, a_cnt = a_rank + b_idx, a_all = a_cnt + b_cnt;
     MvBlocks blk{s};
     HIPCHK(hipMallocAsync((void **)&blk.a, a_all, s));
     char *A = blk.a;
-    const int32_t *d_o1 = (const int32_t *)A, *d_o2 = d_o1 + (K + 1);
+    const int32_t *d_out = (const int32_t *)A;
+    const MvRows R{d_out, d_out + (K + 1), d_out + (2 * K + 1), d_out + (3 * K + 1)};
     int32_t *idx = (int32_t *)(A + a_idx), *bidx = mutual ? (int32_t *)(A + a_bidx) : nullptr, *rank = (int32_t *)(A + a_rank), *cnt = (int32_t *)(A + a_cnt);
     float *dist = (float *)(A + a_dist), *bdist = (float *)(A + a_bdist);
     uint8_t *keep = (uint8_t *)(A + a_keep);
-    rc = match_rc(mt_batch_upload(device, s, o32.data(), o32.size() * 4, A)); if (rc) return rc;
-    rc = match_rc(mt_batch_knn2(mp->norm, words, q1, q2, o1.data(), o2.data(), K, device, s, idx, dist)); if (rc) return rc;
+    rc = match_rc(mt_batch_upload(device, s, tab.data(), tab.size() * 4, A)); if (rc) return rc;
+    rc = match_rc(mt_batch_knn2(mp->norm, words, q1, q2, rows.data(), K, (int)n_out, 0, device, s, idx, dist)); if (rc) return rc;
     int fginn; double fginn_r; (void)mt_second_nn(mp, &fginn, &fginn_r);
-    if (fginn) { rc = match_rc(mt_batch_fginn(mp->norm, words, q1, q2, kp2, kd, o1.data(), o2.data(), K, fginn_r, device, s, idx, dist)); if (rc) return rc; }
-    if (mutual) { rc = match_rc(mt_batch_knn2(mp->norm, words, q2, q1, o2.data(), o1.data(), K, device, s, bidx, bdist)); if (rc) return rc; }
-    rc = match_rc(mt_batch_filter_rank(idx, dist, d_o1, d_o2, K, mp->ratio, bidx, s, keep, rank, cnt)); if (rc) return rc;
-
-    return mv_estimate(homography, K, kd, prm, MvRows{d_o1, nullptr, d_o2}, cnt, keep, rank, idx, kp1, kp2, d_seeds, device, s, blk, d_model, d_stats,
-                       match, inlier, h_counts);
+    if (fginn) { rc = match_rc(mt_batch_fginn(mp->norm, words, q1, q2, kp2, kd, fg_o1, fg_o2, K, fginn_r, device, s, idx, dist)); if (rc) return rc; }
+    if (mutual) { rc = match_rc(mt_batch_knn2(mp->norm, words, q2, q1, rows.data(), K, (int)n_back, 1, device, s, bidx, bdist)); if (rc) return rc; }
+    rc = match_rc(mt_batch_filter_rank(idx, dist, R.out, R.back, K, mp->ratio, bidx, s, keep, rank, cnt)); if (rc) return rc;
+    return mv_estimate(homography, K, kd, prm, R, cnt, keep, rank, idx, kp1, kp2, d_seeds, device, s, blk, d_model, d_stats, match, inlier, h_counts);
 }
 
 extern "C" int mi_degensac_match_verify_batch_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
@@ -1194,8 +1216,16 @@ extern "C" int mi_degensac_match_verify_batch_dev(int homography, const mi_degen
         const mi_degensac_params *prm, const uint32_t *d_seeds, int device, void *stream, double *d_model, int32_t *d_match, uint8_t *d_inlier,
         int32_t *d_stats, int32_t *h_counts)
 {
-    return match_verify_dev(homography, mp, d_desc1, d_desc2, offsets1_host, offsets2_host, d_kp1, d_kp2, kp_dim, n_pairs, prm, d_seeds, device,
-                            (hipStream_t)stream, d_model, d_match, d_inlier, d_stats, h_counts);
+    int rc = mv_check(homography, mp, offsets1_host, offsets2_host, kp_dim, n_pairs);
+    if (rc || n_pairs == 0) return rc;
+    std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
+    mt_ragged_rows(offsets1_host, offsets2_host, n_pairs, o1, o2, rows);
+    const int64_t n1 = o1[n_pairs], n2 = o2[n_pairs];
+    if ((rc = mv_check_prm(prm, homography, kp_dim)) || (rc = mv_check_device(device)) ||
+        (rc = mv_check_null(d_desc1, d_desc2, d_kp1, d_kp2, n1, n2, d_seeds, d_model, d_match, d_inlier))) return rc;
+    return match_verify_rows(homography, mp, d_desc1, d_desc2, d_kp1, d_kp2, offsets1_host[0], offsets2_host[0], kp_dim, rows, n1, n2, o1.data(),
+                             o2.data(), prm, d_seeds, device, (hipStream_t)stream, d_model, d_match + offsets1_host[0], d_inlier + offsets1_host[0],
+                             d_stats, h_counts);
 }
 
 /* The host-pointer forms' re-run of the pairs discarded after a hand-over time-out (bit 10 of stats[15]): exactly their tentatives,
@@ -1231,161 +1261,41 @@ static int mv_rerun(mi_degensac_ctx *c, int homography, int kd, int K, const mi_
     return 0;
 }
 
-/* host pointers: stage on the calling thread's context, run the device path on its stream, copy back; pairs discarded after a
- * hand-over time-out go through ctx_batch's re-run (depth 1) on exactly their gathered tentatives */
-extern "C" int mi_degensac_match_verify_batch(int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2,
-        const int64_t *offsets1, const int64_t *offsets2, const double *kp1, const double *kp2, int kd, int K, const mi_degensac_params *prm,
-        const uint32_t *seeds, int device, double *model, int32_t *match, uint8_t *inlier, int32_t *stats, int32_t *counts)
-{
-    int rc = mv_check(homography, mp, offsets1, offsets2, kd, K); if (rc) return rc;
-    if (K == 0) return 0;
-    if (!desc1 || !desc2 || !kp1 || !kp2 || !seeds || !model || !match || !inlier) { set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
-    mi_degensac_ctx *c; rc = thread_ctx(device, &c); if (rc) return rc;
-    DevGuard g; rc = g.enter(device); if (rc) return rc;
-    const int64_t n1 = offsets1[K] - offsets1[0], n2 = offsets2[K] - offsets2[0];
-    const size_t row = mt_row_bytes(mp->norm, mp->dim);
-    std::vector<int64_t> o1(K + 1), o2(K + 1);
-    for (int p = 0; p <= K; p++) { o1[p] = offsets1[p] - offsets1[0]; o2[p] = offsets2[p] - offsets2[0]; }
-    const size_t s_d1 = align_up(n1 * row, 256), s_d2 = align_up(n2 * row, 256), s_k1 = align_up((size_t)n1 * kd * 8, 256),
-                 s_k2 = align_up((size_t)n2 * kd * 8, 256), s_sd = align_up((size_t)K * 4, 256), s_mo = align_up((size_t)K * 72, 256),
-                 s_ma = align_up((size_t)n1 * 4, 256), s_in = align_up((size_t)n1, 256), s_st = align_up((size_t)K * 64, 256);
-    const size_t a_d2 = s_d1, a_k1 = a_d2 + s_d2, a_k2 = a_k1 + s_k1, a_sd = a_k2 + s_k2, a_mo = a_sd + s_sd, a_ma = a_mo + s_mo, a_in = a_ma + s_ma,
-                 a_st = a_in + s_in, a_all = a_st + s_st;
-    char *D = nullptr;
-    struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
-    HIPCHK(hipMalloc((void **)&D, a_all));
-    HIPCHK(hipMemcpy(D, (const char *)desc1 + offsets1[0] * row, n1 * row, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(D + a_d2, (const char *)desc2 + offsets2[0] * row, n2 * row, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(D + a_k1, kp1 + offsets1[0] * kd, (size_t)n1 * kd * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(D + a_k2, kp2 + offsets2[0] * kd, (size_t)n2 * kd * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(D + a_sd, seeds, (size_t)K * 4, hipMemcpyHostToDevice));
-    std::vector<int32_t> cnt(K), st((size_t)K * 16);
-    rc = match_verify_dev(homography, mp, D, D + a_d2, o1.data(), o2.data(), (const double *)(D + a_k1), (const double *)(D + a_k2), kd, K, prm,
-                          (const uint32_t *)(D + a_sd), device, c->stream, (double *)(D + a_mo), (int32_t *)(D + a_ma), (uint8_t *)(D + a_in),
-                          (int32_t *)(D + a_st), cnt.data());
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    int32_t *mt = match + offsets1[0]; uint8_t *in = inlier + offsets1[0];
-    HIPCHK(hipMemcpy(model, D + a_mo, (size_t)K * 72, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(mt, D + a_ma, (size_t)n1 * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(in, D + a_in, (size_t)n1, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(st.data(), D + a_st, (size_t)K * 64, hipMemcpyDeviceToHost));
-    rc = mv_rerun(c, homography, kd, K, prm, seeds, o1.data(), o1.data(), o2.data(), kp1 + offsets1[0] * kd, kp2 + offsets2[0] * kd, mt, model, in, st);
-    if (rc) return rc;
-    if (stats) memcpy(stats, st.data(), (size_t)K * 64);
-    if (counts) memcpy(counts, cnt.data(), (size_t)K * 4);
-    return 0;
-}
-
-/* ---- match-and-verify over a pair list (include/mi_degensac.h mi_degensac_match_verify_pairs[_dev]) --------------------------
- * The batched path with descriptors and keypoints stored once per image: four per-pair row bases (output rows, query rows in store
- * 1, train rows in store 2, rows of the reverse search's back block) take the place of the two offset tables that say both "where my
- * results are" and "where my rows are" in the ragged batch.  The filter and the scatter only ever ask the first question and run
- * unchanged on the output-row offsets (and the back bases); the 2-NN launch and the gather have pair-list siblings. */
-static int mvp_check(int homography, const mi_degensac_match_params *mp, int kd, const int64_t *off1, int m1, const int64_t *off2, int m2,
-                     const int32_t *pairs, int K, std::vector<mt_pair_rows> &rows, int64_t *n_out, int64_t *n_back)
-{
-    int rc = mv_check_params(homography, mp, kd, K); if (rc) return rc;
-    int fginn; double r; (void)mt_second_nn(mp, &fginn, &r);
-    if (fginn) { set_err("the FGINN rule (second_nn = 1) is not part of the pair-list entry points: use mi_degensac_match_verify_batch*"); return MI_DEGENSAC_EINVAL; }
-    *n_out = *n_back = 0;
-    if (K == 0) return 0;
-    rows.resize(K);
-    return match_rc(mt_pairs_layout(off1, m1, off2, m2, pairs, K, rows.data(), n_out, n_back));
-}
-
-static int match_verify_pairs_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const int64_t *off1,
-                                  const int64_t *off2, const double *d_kp1, const double *d_kp2, int kd, const std::vector<mt_pair_rows> &rows,
-                                  int64_t n_out, int64_t n_back, const mi_degensac_params *prm, const uint32_t *d_seeds, int device, hipStream_t s,
-                                  double *d_model, int32_t *match, uint8_t *inlier, int32_t *d_stats, int32_t *h_counts)
+/* The host-pointer forms: side 1 (rows off1[0] .. off1[m1] of desc1 / kp1) goes to the device, side 2 too unless `same` says both sides
+ * name the same arrays, then the seeds; the device path runs on the calling thread's stream, the per-pair results come back (match /
+ * inlier: at the first output row); pairs discarded after a hand-over time-out go through mv_rerun (ctx_batch's re-run, depth 1) on
+ * exactly their gathered tentatives. */
+static int match_verify_host(int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *off1, int m1,
+                             const int64_t *off2, int m2, const double *kp1, const double *kp2, int kd, bool same, const std::vector<mt_pair_rows> &rows,
+                             int64_t n_out, int64_t n_back, const int64_t *fg_o1, const int64_t *fg_o2, const mi_degensac_params *prm,
+                             const uint32_t *seeds, int device, double *model, int32_t *match, uint8_t *inlier, int32_t *stats, int32_t *counts)
 {
     const int K = (int)rows.size();
-    dg_params chk; int rc = fill_params(prm, homography, kd, &chk); if (rc) return rc;
-    if (!d_seeds || !d_model || (n_out > 0 && (!d_desc1 || !d_kp1 || !match || !inlier)) || (n_back > 0 && (!d_desc2 || !d_kp2))) {
-        set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
-    if (device < 0 || device >= 64) { set_err("bad device index"); return MI_DEGENSAC_EINVAL; }
-    if (mi_degensac_device_count() == 0) { set_err("no HIP device: this library has no CPU path"); return MI_DEGENSAC_ENODEV; }
+    mi_degensac_ctx *c; int rc = thread_ctx(device, &c); if (rc) return rc;
     DevGuard g; rc = g.enter(device); if (rc) return rc;
-    const int words = mt_row_words(mp->norm, mp->dim);
-    const bool mutual = mp->mutual != 0;
-    /* every row pointer moves to its store's first row; the tables: out [K + 1] | q1 [K] | t2 [K] | back [K] */
-    const uint32_t *q1 = (const uint32_t *)d_desc1 + (size_t)off1[0] * words, *q2 = (const uint32_t *)d_desc2 + (size_t)off2[0] * words;
-    const double *kp1 = d_kp1 + (size_t)off1[0] * kd, *kp2 = d_kp2 + (size_t)off2[0] * kd;
-    std::vector<int32_t> tab(4 * (size_t)K + 1);
-    for (int p = 0; p < K; p++) { tab[p] = rows[p].out; tab[K + 1 + p] = rows[p].q; tab[2 * K + 1 + p] = rows[p].t; tab[3 * K + 1 + p] = rows[p].back; }
-    tab[K] = (int32_t)n_out;
-
-    /* block A: tables, forward (and backward) 2-NN, keep / rank / count */
-    const size_t b_tab = align_up(tab.size() * 4, 256), b_idx = align_up((size_t)n_out * 8, 256), b_bidx = mutual ? align_up((size_t)n_back * 8, 256) : 0,
-                 b_keep = align_up((size_t)n_out, 256), b_cnt = align_up((size_t)K * 4, 256);
-    const size_t a_idx = b_tab, a_dist = a_idx + b_idx, a_bidx = a_dist + b_idx, a_bdist = a_bidx + b_bidx, a_keep = a_bdist + b_bidx,
-                 a_rank = a_keep + b_keep, a_cnt = a_rank + b_idx, a_all = a_cnt + b_cnt;
-    MvBlocks blk{s};
-    HIPCHK(hipMallocAsync((void **)&blk.a, a_all, s));
-    char *A = blk.a;
-    const int32_t *d_out = (const int32_t *)A, *d_q1 = d_out + (K + 1), *d_t2 = d_q1 + K, *d_back = d_t2 + K;
-    int32_t *idx = (int32_t *)(A + a_idx), *bidx = mutual ? (int32_t *)(A + a_bidx) : nullptr, *rank = (int32_t *)(A + a_rank), *cnt = (int32_t *)(A + a_cnt);
-    float *dist = (float *)(A + a_dist), *bdist = (float *)(A + a_bdist);
-    uint8_t *keep = (uint8_t *)(A + a_keep);
-    rc = match_rc(mt_batch_upload(device, s, tab.data(), tab.size() * 4, A)); if (rc) return rc;
-    rc = match_rc(mt_pairs_knn2(mp->norm, words, q1, q2, rows.data(), K, (int)n_out, 0, device, s, idx, dist)); if (rc) return rc;
-    if (mutual) { rc = match_rc(mt_pairs_knn2(mp->norm, words, q2, q1, rows.data(), K, (int)n_back, 1, device, s, bidx, bdist)); if (rc) return rc; }
-    rc = match_rc(mt_batch_filter_rank(idx, dist, d_out, d_back, K, mp->ratio, bidx, s, keep, rank, cnt)); if (rc) return rc;
-    return mv_estimate(homography, K, kd, prm, MvRows{d_out, d_q1, d_t2}, cnt, keep, rank, idx, kp1, kp2, d_seeds, device, s, blk, d_model, d_stats,
-                       match, inlier, h_counts);
-}
-
-extern "C" int mi_degensac_match_verify_pairs_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
-        const int64_t *offsets1_host, int n_images1, const int64_t *offsets2_host, int n_images2, const double *d_kp1, const double *d_kp2, int kp_dim,
-        const int32_t *pairs_host, int n_pairs, const mi_degensac_params *prm, const uint32_t *d_seeds, int device, void *stream, double *d_model,
-        int32_t *d_match, uint8_t *d_inlier, int32_t *d_stats, int32_t *h_counts)
-{
-    std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
-    int rc = mvp_check(homography, mp, kp_dim, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, rows, &n_out, &n_back);
-    if (rc || n_pairs == 0) return rc;
-    return match_verify_pairs_dev(homography, mp, d_desc1, d_desc2, offsets1_host, offsets2_host, d_kp1, d_kp2, kp_dim, rows, n_out, n_back, prm, d_seeds,
-                                  device, (hipStream_t)stream, d_model, d_match, d_inlier, d_stats, h_counts);
-}
-
-/* host pointers: each store goes to the device once (one copy when both sides name the same arrays), the device path runs on the
- * calling thread's stream, the per-pair results come back; discarded pairs go through mv_rerun with the pair's image rows */
-extern "C" int mi_degensac_match_verify_pairs(int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2,
-        const int64_t *offsets1, int n_images1, const int64_t *offsets2, int n_images2, const double *kp1, const double *kp2, int kd,
-        const int32_t *pairs, int K, const mi_degensac_params *prm, const uint32_t *seeds, int device, double *model, int32_t *match,
-        uint8_t *inlier, int32_t *stats, int32_t *counts)
-{
-    std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
-    int rc = mvp_check(homography, mp, kd, offsets1, n_images1, offsets2, n_images2, pairs, K, rows, &n_out, &n_back);
-    if (rc || K == 0) return rc;
-    if (!desc1 || !desc2 || !kp1 || !kp2 || !seeds || !model || !match || !inlier) { set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
-    mi_degensac_ctx *c; rc = thread_ctx(device, &c); if (rc) return rc;
-    DevGuard g; rc = g.enter(device); if (rc) return rc;
-    const int64_t n1 = offsets1[n_images1] - offsets1[0], n2 = offsets2[n_images2] - offsets2[0];
+    const int64_t n1 = off1[m1] - off1[0], n2 = off2[m2] - off2[0];
     const size_t row = mt_row_bytes(mp->norm, mp->dim);
-    const bool same = desc1 == desc2 && kp1 == kp2 && n_images1 == n_images2 && !memcmp(offsets1, offsets2, ((size_t)n_images1 + 1) * 8);
     const size_t s_d1 = align_up(n1 * row, 256), s_d2 = same ? 0 : align_up(n2 * row, 256), s_k1 = align_up((size_t)n1 * kd * 8, 256),
                  s_k2 = same ? 0 : align_up((size_t)n2 * kd * 8, 256), s_sd = align_up((size_t)K * 4, 256), s_mo = align_up((size_t)K * 72, 256),
                  s_ma = align_up((size_t)n_out * 4, 256), s_in = align_up((size_t)n_out, 256), s_st = align_up((size_t)K * 64, 256);
     const size_t a_d2 = s_d1, a_k1 = a_d2 + s_d2, a_k2 = a_k1 + s_k1, a_sd = a_k2 + s_k2, a_mo = a_sd + s_sd, a_ma = a_mo + s_mo, a_in = a_ma + s_ma,
                  a_st = a_in + s_in, a_all = a_st + s_st;
+    const double *h_k1 = kp1 + off1[0] * kd, *h_k2 = kp2 + off2[0] * kd;
     char *D = nullptr;
     struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
     HIPCHK(hipMalloc((void **)&D, a_all));
-    HIPCHK(hipMemcpy(D, (const char *)desc1 + offsets1[0] * row, n1 * row, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(D + a_k1, kp1 + offsets1[0] * kd, (size_t)n1 * kd * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(D, (const char *)desc1 + off1[0] * row, n1 * row, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(D + a_k1, h_k1, (size_t)n1 * kd * 8, hipMemcpyHostToDevice));
     if (!same) {
-        HIPCHK(hipMemcpy(D + a_d2, (const char *)desc2 + offsets2[0] * row, n2 * row, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(D + a_k2, kp2 + offsets2[0] * kd, (size_t)n2 * kd * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(D + a_d2, (const char *)desc2 + off2[0] * row, n2 * row, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(D + a_k2, h_k2, (size_t)n2 * kd * 8, hipMemcpyHostToDevice));
     }
     HIPCHK(hipMemcpy(D + a_sd, seeds, (size_t)K * 4, hipMemcpyHostToDevice));
-    /* the device path takes store pointers with the stores' own offsets: these copies start at each store's first row */
-    std::vector<int64_t> o1(n_images1 + 1), o2(n_images2 + 1);
-    for (int i = 0; i <= n_images1; i++) o1[i] = offsets1[i] - offsets1[0];
-    for (int j = 0; j <= n_images2; j++) o2[j] = offsets2[j] - offsets2[0];
     std::vector<int32_t> cnt(K), st((size_t)K * 16);
-    rc = match_verify_pairs_dev(homography, mp, D, same ? D : D + a_d2, o1.data(), o2.data(), (const double *)(D + a_k1),
-                                (const double *)(D + (same ? a_k1 : a_k2)), kd, rows, n_out, n_back, prm, (const uint32_t *)(D + a_sd), device, c->stream,
-                                (double *)(D + a_mo), (int32_t *)(D + a_ma), (uint8_t *)(D + a_in), (int32_t *)(D + a_st), cnt.data());
+    if ((rc = mv_check_prm(prm, homography, kd))) return rc;
+    rc = match_verify_rows(homography, mp, D, same ? D : D + a_d2, (const double *)(D + a_k1), (const double *)(D + (same ? a_k1 : a_k2)), 0, 0, kd, rows,
+                           n_out, n_back, fg_o1, fg_o2, prm, (const uint32_t *)(D + a_sd), device, c->stream, (double *)(D + a_mo), (int32_t *)(D + a_ma),
+                           (uint8_t *)(D + a_in), (int32_t *)(D + a_st), cnt.data());
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(model, D + a_mo, (size_t)K * 72, hipMemcpyDeviceToHost));
@@ -1395,9 +1305,55 @@ extern "C" int mi_degensac_match_verify_pairs(int homography, const mi_degensac_
     std::vector<int64_t> out(K + 1), b1(K), b2(K);
     for (int p = 0; p < K; p++) { out[p] = rows[p].out; b1[p] = rows[p].q; b2[p] = rows[p].t; }
     out[K] = n_out;
-    rc = mv_rerun(c, homography, kd, K, prm, seeds, out.data(), b1.data(), b2.data(), kp1 + offsets1[0] * kd, kp2 + offsets2[0] * kd, match, model, inlier, st);
+    rc = mv_rerun(c, homography, kd, K, prm, seeds, out.data(), b1.data(), b2.data(), h_k1, h_k2, match, model, inlier, st);
     if (rc) return rc;
     if (stats) memcpy(stats, st.data(), (size_t)K * 64);
     if (counts) memcpy(counts, cnt.data(), (size_t)K * 4);
     return 0;
+}
+
+/* the ragged batch never asks whether its two sides are the same arrays: both are uploaded */
+extern "C" int mi_degensac_match_verify_batch(int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2,
+        const int64_t *offsets1, const int64_t *offsets2, const double *kp1, const double *kp2, int kd, int K, const mi_degensac_params *prm,
+        const uint32_t *seeds, int device, double *model, int32_t *match, uint8_t *inlier, int32_t *stats, int32_t *counts)
+{
+    int rc = mv_check(homography, mp, offsets1, offsets2, kd, K);
+    if (rc || K == 0) return rc;
+    if (!desc1 || !desc2 || !kp1 || !kp2 || !seeds || !model || !match || !inlier) { set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
+    std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
+    mt_ragged_rows(offsets1, offsets2, K, o1, o2, rows);
+    return match_verify_host(homography, mp, desc1, desc2, offsets1, K, offsets2, K, kp1, kp2, kd, false, rows, o1[K], o2[K], o1.data(), o2.data(),
+                             prm, seeds, device, model, match + offsets1[0], inlier + offsets1[0], stats, counts);
+}
+
+/* ---- match-and-verify over a pair list (include/mi_degensac.h mi_degensac_match_verify_pairs[_dev]) --------------------------
+ * The same path with descriptors and keypoints stored once per image: mt_pairs_layout fills the rows from the stores' offsets and the
+ * (i, j) list, where the ragged batch takes the identity list over its own offsets; everything after the layout step is shared. */
+extern "C" int mi_degensac_match_verify_pairs_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
+        const int64_t *offsets1_host, int n_images1, const int64_t *offsets2_host, int n_images2, const double *d_kp1, const double *d_kp2, int kp_dim,
+        const int32_t *pairs_host, int n_pairs, const mi_degensac_params *prm, const uint32_t *d_seeds, int device, void *stream, double *d_model,
+        int32_t *d_match, uint8_t *d_inlier, int32_t *d_stats, int32_t *h_counts)
+{
+    std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
+    int rc = mvp_check(homography, mp, kp_dim, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, rows, &n_out, &n_back);
+    if (rc || n_pairs == 0) return rc;
+    if ((rc = mv_check_prm(prm, homography, kp_dim)) ||
+        (rc = mv_check_null(d_desc1, d_desc2, d_kp1, d_kp2, n_out, n_back, d_seeds, d_model, d_match, d_inlier)) || (rc = mv_check_device(device))) return rc;
+    return match_verify_rows(homography, mp, d_desc1, d_desc2, d_kp1, d_kp2, offsets1_host[0], offsets2_host[0], kp_dim, rows, n_out, n_back, nullptr,
+                             nullptr, prm, d_seeds, device, (hipStream_t)stream, d_model, d_match, d_inlier, d_stats, h_counts);
+}
+
+/* each store goes to the device once: one copy when both sides name the same arrays */
+extern "C" int mi_degensac_match_verify_pairs(int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2,
+        const int64_t *offsets1, int n_images1, const int64_t *offsets2, int n_images2, const double *kp1, const double *kp2, int kd,
+        const int32_t *pairs, int K, const mi_degensac_params *prm, const uint32_t *seeds, int device, double *model, int32_t *match,
+        uint8_t *inlier, int32_t *stats, int32_t *counts)
+{
+    std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
+    int rc = mvp_check(homography, mp, kd, offsets1, n_images1, offsets2, n_images2, pairs, K, rows, &n_out, &n_back);
+    if (rc || K == 0) return rc;
+    if (!desc1 || !desc2 || !kp1 || !kp2 || !seeds || !model || !match || !inlier) { set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
+    const bool same = desc1 == desc2 && kp1 == kp2 && n_images1 == n_images2 && !memcmp(offsets1, offsets2, ((size_t)n_images1 + 1) * 8);
+    return match_verify_host(homography, mp, desc1, desc2, offsets1, n_images1, offsets2, n_images2, kp1, kp2, kd, same, rows, n_out, n_back, nullptr,
+                             nullptr, prm, seeds, device, model, match, inlier, stats, counts);
 }

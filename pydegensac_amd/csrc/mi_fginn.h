@@ -156,11 +156,11 @@ extern "C" int mi_degensac_match_fginn_knn2_batch_dev(int norm, const void *d_de
     if ((n1 > 0 && (!d_desc1 || !d_idx || !d_dist)) || (n2 > 0 && (!d_desc2 || !d_kp2))) { snprintf(mt_err, sizeof mt_err, "NULL argument");
         return MI_DEGENSAC_EINVAL; }
     MtDevGuard g; rc = g.enter(device); if (rc) return rc;
-    std::vector<int64_t> o1(n_pairs + 1), o2(n_pairs + 1);
-    for (int p = 0; p <= n_pairs; p++) { o1[p] = offsets1_host[p] - offsets1_host[0]; o2[p] = offsets2_host[p] - offsets2_host[0]; }
+    std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
+    mt_ragged_rows(offsets1_host, offsets2_host, n_pairs, o1, o2, rows);
     const uint32_t *q1 = (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words, *q2 = (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words;
     int32_t *idx = d_idx + 2 * offsets1_host[0]; float *dist = d_dist + 2 * offsets1_host[0];
-    rc = mt_batch_knn2(norm, words, q1, q2, o1.data(), o2.data(), n_pairs, device, (hipStream_t)stream, idx, dist); if (rc) return rc;
+    rc = mt_batch_knn2(norm, words, q1, q2, rows.data(), n_pairs, (int)n1, 0, device, (hipStream_t)stream, idx, dist); if (rc) return rc;
     return mt_batch_fginn(norm, words, q1, q2, d_kp2 + (size_t)offsets2_host[0] * kp_dim, kp_dim, o1.data(), o2.data(), n_pairs, spatial_th, device,
                           (hipStream_t)stream, idx, dist);
 }

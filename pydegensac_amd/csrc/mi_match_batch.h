@@ -1,7 +1,8 @@
 /* Internal interface between the batched matcher stages (mi_matcher.hip) and the match-and-verify orchestration in
  * mi_degensac_host.inc, which needs launch_batch.  Not part of the C-ABI: hidden symbols of libmi_degensac.so.
  *
- * Row offsets passed here are relative (offs[0] = 0) and every device pointer is already moved to the batch's first row.
+ * The batched stages have one row layout, mt_pair_rows, for the ragged batch and for a pair list over image stores.  Rows and row
+ * offsets passed here are relative (offs[0] = 0) and every device pointer is already moved to its side's first row.
  * All functions enqueue on `s` and never synchronise; the device must be current.  Errors: a MI_DEGENSAC_E* code, message in
  * mi_degensac_match_last_error(). */
 #ifndef MI_MATCH_BATCH_H
@@ -9,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <vector>
 #include "../../include/mi_degensac.h"
 
 #define MT_HIDDEN __attribute__((visibility("hidden")))
@@ -62,58 +64,67 @@ MT_HIDDEN void mt_set_error(const char *msg);
 
 /* host -> device copy of `bytes` through a pinned staging block: asynchronous, the host block may be reused at once */
 MT_HIDDEN int mt_batch_upload(int device, hipStream_t s, const void *h, size_t bytes, void *d);
-/* batched 2-NN: every row of pair p in q (rows oq[p] .. oq[p+1]) against the rows ot[p] .. ot[p+1] of t; idx / dist [oq[K], 2],
- * indices local to the pair.  words = 32-bit words per descriptor row. */
-MT_HIDDEN int mt_batch_knn2(int norm, int words, const void *dq, const void *dt, const int64_t *oq, const int64_t *ot, int n_pairs, int device,
+/* Where the rows of pair p are, relative to the first row of each side: its first output row (idx / dist / keep / rank / match /
+ * inlier), its query rows on side 1 (q, nq), its train rows on side 2 (t, nt) and its first row in the back block of the mutual check's
+ * reverse search.  The one layout of every batched stage below; mt_identity_rows and mt_pairs_layout fill it. */
+struct mt_pair_rows { int32_t out, q, nq, t, nt, back; };
+/* the ragged batch, from its relative offsets o1 / o2 [K + 1]: the list whose entry p is (image p of side 1, image p of side 2), with
+ * the answers at the queries' own rows and the back block at the train rows */
+static inline void mt_identity_rows(const int64_t *o1, const int64_t *o2, int n_pairs, mt_pair_rows *rows)
+{
+    for (int p = 0; p < n_pairs; p++)
+        rows[p] = mt_pair_rows{(int32_t)o1[p], (int32_t)o1[p], (int32_t)(o1[p + 1] - o1[p]), (int32_t)o2[p], (int32_t)(o2[p + 1] - o2[p]), (int32_t)o2[p]};
+}
+/* the same from the offsets as a caller passes them (off[0] >= 0): o1 / o2 = the relative offsets, rows = the identity list over them */
+static inline void mt_ragged_rows(const int64_t *off1, const int64_t *off2, int n_pairs, std::vector<int64_t> &o1, std::vector<int64_t> &o2,
+                                  std::vector<mt_pair_rows> &rows)
+{
+    o1.resize(n_pairs + 1); o2.resize(n_pairs + 1); rows.resize(n_pairs);
+    for (int p = 0; p <= n_pairs; p++) { o1[p] = off1[p] - off1[0]; o2[p] = off2[p] - off2[0]; }
+    mt_identity_rows(o1.data(), o2.data(), n_pairs, rows.data());
+}
+/* a pair list over image stores (include/mi_degensac.h mi_degensac_match_*_pairs*): checks the stores' offsets ([m + 1] each) and the
+ * (i, j) image indices, fills rows [K] and the row totals.  EINVAL (message set) for bad offsets, an image index outside its store, or
+ * output / back rows beyond the batch path's row limit; needs no device */
+MT_HIDDEN int mt_pairs_layout(const int64_t *off1, int m1, const int64_t *off2, int m2, const int32_t *pairs, int n_pairs, mt_pair_rows *rows,
+                              int64_t *n_out, int64_t *n_back);
+/* batched 2-NN, dq / dt at the first row of side 1 / 2.  swap = 0: rows q .. q + nq of dq against t .. t + nt of dt into the output
+ * rows from `out`; swap = 1 (the reverse search): dq / dt are sides 2 / 1, rows t .. t + nt of dq against q .. q + nq of dt into the
+ * rows from `back`.  idx / dist [n_rows, 2] with n_rows the total of the side written, indices local to the pair.  words = 32-bit
+ * words per descriptor row. */
+MT_HIDDEN int mt_batch_knn2(int norm, int words, const void *dq, const void *dt, const mt_pair_rows *rows, int n_pairs, int n_rows, int swap, int device,
                             hipStream_t s, int32_t *idx, float *dist);
-/* FGINN (mi_fginn.h): after mt_batch_knn2 with the same arguments on s, slot 1 of idx / dist becomes the nearest train row whose
- * keypoint (kt: [rows, kd] of the train side) lies at least r from the keypoint of slot 0; no host synchronisation */
+/* FGINN (mi_fginn.h), ragged batches only (oq / ot: relative offsets [K + 1]): after mt_batch_knn2 over their identity rows on s, slot 1
+ * of idx / dist becomes the nearest train row whose keypoint (kt: [rows, kd] of the train side) lies at least r from the keypoint of
+ * slot 0; no host synchronisation */
 MT_HIDDEN int mt_batch_fginn(int norm, int words, const void *dq, const void *dt, const double *kt, int kd, const int64_t *oq, const int64_t *ot,
                              int n_pairs, double r, int device, hipStream_t s, int32_t *idx, float *dist);
 /* ratio test (+ mutual check when d_back is set) and the rank of every kept query among its pair's kept queries; one
  * workgroup per pair.  d_off1 / d_off2: [K + 1] relative int32 row offsets on the device.  d_off1 says where the pair's idx / dist /
- * keep / rank rows are, d_off2[p] (the only entry read) where its rows of d_back start: the pair-list form passes its output-row
- * offsets and its back-row bases here. */
+ * keep / rank rows are (the `out` column and the total), d_off2[p] (the only entry read) where its rows of d_back start (the `back`
+ * column). */
 MT_HIDDEN int mt_batch_filter_rank(const int32_t *d_idx, const float *d_dist, const int32_t *d_off1, const int32_t *d_off2, int n_pairs, float ratio,
                                    const int32_t *d_back, hipStream_t s, uint8_t *d_keep, int32_t *d_rank, int32_t *d_count);
 /* the estimator's input rows of the E eligible pairs: pts[est_off[e] + rank[i]] = kp rows of query i and of its nearest train row;
- * seeds_e[e] = seeds[pair_of_e[e]] */
-MT_HIDDEN int mt_batch_gather(int n_eligible, const int32_t *d_pair_of_e, const int64_t *d_est_off, const int32_t *d_off1, const int32_t *d_off2,
-                              const uint8_t *d_keep, const int32_t *d_rank, const int32_t *d_idx, const double *d_kp1, const double *d_kp2, int kp_dim,
-                              const uint32_t *d_seeds, hipStream_t s, double *d_pts1, double *d_pts2, uint32_t *d_seeds_e);
+ * seeds_e[e] = seeds[pair_of_e[e]].  d_out [K + 1]: output-row offsets (where keep / rank / idx live), d_q1 / d_t2 [K]: the first
+ * keypoint row of the pair's query image in kp1 and of its train image in kp2 */
+MT_HIDDEN int mt_batch_gather(int n_eligible, const int32_t *d_pair_of_e, const int64_t *d_est_off, const int32_t *d_out, const int32_t *d_q1,
+                              const int32_t *d_t2, const uint8_t *d_keep, const int32_t *d_rank, const int32_t *d_idx, const double *d_kp1,
+                              const double *d_kp2, int kp_dim, const uint32_t *d_seeds, hipStream_t s, double *d_pts1, double *d_pts2,
+                              uint32_t *d_seeds_e);
 /* results back to pair order: model / stats of eligible index e_of_p[p] (zeros for short pairs, e_of_p[p] = -1), match[i] = the
  * pair-local train row of a tentative or -1, inlier[i] = tentative and inlier of the pair's model */
 MT_HIDDEN int mt_batch_scatter(int n_pairs, const int32_t *d_e_of_p, const int64_t *d_est_off, const int32_t *d_off1, const uint8_t *d_keep,
                                const int32_t *d_rank, const int32_t *d_idx, const double *d_model_e, const int32_t *d_stats_e, const uint8_t *d_mask_e,
                                hipStream_t s, double *d_model, int32_t *d_stats /*nullable*/, int32_t *d_match, uint8_t *d_inlier);
 
-/* ---- the pair-list form (include/mi_degensac.h mi_degensac_match_*_pairs*): image stores + (i, j) image indices ---- */
-/* the rows of list entry p, relative to the first row of each store: its first output row, its query rows in store 1 (q, nq), its
- * train rows in store 2 (t, nt) and its first row in the back block of the mutual check's reverse search */
-struct mt_pair_rows { int32_t out, q, nq, t, nt, back; };
-/* checks the stores' offsets ([m + 1] each) and the list, fills rows [K] and the row totals.  EINVAL (message set) for bad offsets, an
- * image index outside its store, or output / back rows beyond the batch path's row limit; needs no device */
-MT_HIDDEN int mt_pairs_layout(const int64_t *off1, int m1, const int64_t *off2, int m2, const int32_t *pairs, int n_pairs, mt_pair_rows *rows,
-                              int64_t *n_out, int64_t *n_back);
-/* the batched 2-NN over a pair list, dq / dt at the first row of store 1 / 2.  swap = 0: rows q .. q + nq of dq against t .. t + nt
- * of dt into the output rows from `out`; swap = 1 (the reverse search): dq / dt are stores 2 / 1, rows t .. t + nt of dq against
- * q .. q + nq of dt into the rows from `back`.  idx / dist [n_rows, 2] with n_rows the total of the side written */
-MT_HIDDEN int mt_pairs_knn2(int norm, int words, const void *dq, const void *dt, const mt_pair_rows *rows, int n_pairs, int n_rows, int swap, int device,
-                            hipStream_t s, int32_t *idx, float *dist);
-/* mt_batch_gather for a pair list: d_out [K + 1] output-row offsets (where keep / rank / idx live), d_q1 / d_t2 [K] the first keypoint
- * row of the pair's query image in kp1 and of its train image in kp2 */
-MT_HIDDEN int mt_pairs_gather(int n_eligible, const int32_t *d_pair_of_e, const int64_t *d_est_off, const int32_t *d_out, const int32_t *d_q1,
-                              const int32_t *d_t2, const uint8_t *d_keep, const int32_t *d_rank, const int32_t *d_idx, const double *d_kp1,
-                              const double *d_kp2, int kp_dim, const uint32_t *d_seeds, hipStream_t s, double *d_pts1, double *d_pts2,
-                              uint32_t *d_seeds_e);
-
 /* ---- guided matching (mi_guided.hip) ---- */
 /* the gate of a model kind: th from px_th / error_type as fill_params derives it; EINVAL (message set) for a bad error_type or a
  * px_th that is negative or NaN */
 struct mt_gate { int gk, hk; double th, tb; int screen; };
 MT_HIDDEN int mt_guided_gate(int homography, int error_type, double px_th, mt_gate *g);
-/* guided 2-NN: every row of pair p in q against the rows of t that pass the gate of model d_models[9 p ..]; same layout and index
- * convention as mt_batch_knn2.  kq / kt: keypoint rows [rows, kd] of the two sides.  swap = 0: q is side 1 (queries), gate(q, t);
+/* guided 2-NN: every row of pair p in q against the rows of t that pass the gate of model d_models[9 p ..]; offsets oq / ot [K + 1], indices
+ * local to the pair as in mt_batch_knn2.  kq / kt: keypoint rows [rows, kd] of the two sides.  swap = 0: q is side 1 (queries), gate(q, t);
  * swap = 1: q is side 2 (the reverse search of the mutual check), gate(t, q). */
 MT_HIDDEN int mt_batch_guided_knn2(int norm, int words, const void *dq, const void *dt, const double *kq, const double *kt, int kd, const int64_t *oq,
                                    const int64_t *ot, int n_pairs, const double *d_models, const mt_gate &g, int swap, int device, hipStream_t s,

@@ -14,9 +14,11 @@
  * LDS 64 rows at a time (both tiles stored dimension-major, so a wave reads consecutive words / one broadcast word),
  * every thread keeps a 4 x 4 block of running sums in registers and its own running top-2 per query; the 16 threads
  * sharing a query merge their candidates at the end.  The train set is additionally split over blockIdx.y (see mt_knn2_kernel).
- * The batched form (mt_knn2_batch_kernel, mi_degensac_match_*_batch*) runs the same tile body over every pair's query tiles in one
- * launch and feeds the match-and-verify path in mi_degensac_host.inc (filter + rank, gather, scatter below).  The pair-list form
- * (mt_knn2_pairs_kernel, mi_degensac_match_*_pairs*) runs it over image stores: rows stored once per image, a list of (i, j). */
+ * The batched form (mt_knn2_batch_kernel) runs the same tile body over every pair's query tiles in one launch and feeds the match-and-
+ * verify path in mi_degensac_host.inc (filter + rank, gather, scatter below).  It has one row layout, mt_pair_rows (mi_match_batch.h),
+ * and two ways to fill it: a pair list over image stores (mi_degensac_match_*_pairs*: rows stored once per image, a list of (i, j);
+ * mt_pairs_layout) and the ragged batch (mi_degensac_match_*_batch*), which is the list whose entry p is (image p, image p) with its
+ * answers at its queries' own rows (mt_identity_rows). */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -189,39 +191,27 @@ __global__ __launch_bounds__(256) void mt_knn2_kernel(const uint32_t *q, int n1,
         mt_store<NORM>(m, q0 + threadIdx.x, n1, blockIdx.y, idx, dist, part);
 }
 
-/* The ragged batch (include/mi_degensac.h mi_degensac_match_knn2_batch_dev): one launch over every pair's 64-query tiles.
- * tiles[blockIdx.x] = (first query row, end of the pair's query rows, first train row of the pair, end of its train rows), built on
- * the host from the host offsets; rows are global over the batch, the indices written are local to the pair.  Split y takes
- * the pair's train rows t_begin + y t_chunk .. + t_chunk (possibly none: the partial then stays at (inf, -1)). */
+/* The batched launch: one workgroup per 64-query tile of every pair, from a tile table built on the host (mt_batch_knn2).  A tile's
+ * queries q0 .. q_end - 1 of the query rows meet the train rows t_b .. t_e - 1 of the train rows; the indices written are local to
+ * the pair (from t_b), the answers go to the rows o0 .. of idx / dist (n_rows of them in all; the per-split partials are indexed by
+ * output row too).  In a ragged batch o0 = q0; in a pair list, where descriptors are stored once per image, it is not.  Split y takes
+ * the pair's train rows t_b + y t_chunk .. + t_chunk (possibly none: the partial then stays at (inf, -1)).  Tile bodies and the merge
+ * are those of the dense kernel, so neither the split count nor the order of the tiles changes a result.
+ * The record is read in two parts: the 16 bytes the tile body needs up front, o0 where it is used, after the body.  Measured: with
+ * all five fields loaded up front the instruction stream is the same but for that load, the inner loop lies elsewhere and the fp32
+ * kernel runs 1.2 % slower (profiles/matcher_one_path_ab.log). */
+struct mt_ptile { int4 r /* q0, q_end, t_b, t_e */; int o0, pad[3]; };
+
 template <int NORM, int NS = 0>
-__global__ __launch_bounds__(256) void mt_knn2_batch_kernel(const uint32_t *q, const uint32_t *t, int words, const int4 *tiles, int n_rows,
+__global__ __launch_bounds__(256) void mt_knn2_batch_kernel(const uint32_t *q, const uint32_t *t, int words, const mt_ptile *tiles, int n_rows,
                                                             int t_chunk, int32_t *idx, float *dist, mt_best *part)
 {
     __shared__ mt_best merge[MT_Q][16];
-    const int4 tl = tiles[blockIdx.x];
+    const int4 tl = tiles[blockIdx.x].r;
     const int t_lo = tl.z + (int)blockIdx.y * t_chunk, t_hi = t_lo + t_chunk < tl.w ? t_lo + t_chunk : tl.w;
     mt_best m;
     if (mt_tile<NORM, NS>(q, tl.x, tl.y, t, t_lo, t_hi, tl.z, words, merge, m))
-        mt_store<NORM>(m, tl.x + threadIdx.x, n_rows, blockIdx.y, idx, dist, part);
-}
-
-/* The pair list (include/mi_degensac.h mi_degensac_match_knn2_pairs_dev): descriptors are stored once per image and a tile's answers
- * no longer belong at its queries' own rows, so the tile record carries the tile's first output row next to the batched record:
- * queries q0 .. q_end - 1 of the query store against the train rows t_b .. t_e - 1 of the train store, answers at the rows o0 ..
- * of idx / dist (n_rows of them in all; the per-split partials are indexed by output row too).  The tile bodies, the split rule
- * and mt_merge_kernel are those of the batch, so neither the split count nor the order of the tiles changes a result. */
-struct mt_ptile { int q0, q_end, t_b, t_e, o0, pad[3]; };
-
-template <int NORM, int NS = 0>
-__global__ __launch_bounds__(256) void mt_knn2_pairs_kernel(const uint32_t *q, const uint32_t *t, int words, const mt_ptile *tiles, int n_rows,
-                                                            int t_chunk, int32_t *idx, float *dist, mt_best *part)
-{
-    __shared__ mt_best merge[MT_Q][16];
-    const mt_ptile tl = tiles[blockIdx.x];
-    const int t_lo = tl.t_b + (int)blockIdx.y * t_chunk, t_hi = t_lo + t_chunk < tl.t_e ? t_lo + t_chunk : tl.t_e;
-    mt_best m;
-    if (mt_tile<NORM, NS>(q, tl.q0, tl.q_end, t, t_lo, t_hi, tl.t_b, words, merge, m))
-        mt_store<NORM>(m, tl.o0 + threadIdx.x, n_rows, blockIdx.y, idx, dist, part);
+        mt_store<NORM>(m, tiles[blockIdx.x].o0 + threadIdx.x, n_rows, blockIdx.y, idx, dist, part);
 }
 
 /* merge the per-split top-2 of every query (any order gives the same result: mt_push orders by (distance, index)) */
@@ -291,28 +281,13 @@ __global__ __launch_bounds__(256) void mt_filter_rank_kernel(const int32_t *idx,
     if (tid == 0) count[p] = base;
 }
 
-/* one workgroup per eligible pair: its tentatives in query order become rows est_off[e] .. of the estimator's input */
-__global__ __launch_bounds__(256) void mt_gather_kernel(const int32_t *pair_of_e, const int64_t *est_off, const int32_t *off1, const int32_t *off2,
-                                                        const uint8_t *keep, const int32_t *rank, const int32_t *idx, const double *kp1,
-                                                        const double *kp2, int kd, const uint32_t *seeds, double *pts1, double *pts2, uint32_t *seeds_e)
-{
-    const int e = blockIdx.x, p = pair_of_e[e];
-    const int lo = off1[p], hi = off1[p + 1];
-    const int64_t o = est_off[e], b2 = off2[p];
-    if (threadIdx.x == 0) seeds_e[e] = seeds[p];
-    for (int i = lo + (int)threadIdx.x; i < hi; i += 256) {
-        if (!keep[i]) continue;
-        const int64_t r = o + rank[i], j = b2 + idx[2 * i];
-        for (int c = 0; c < kd; c++) { pts1[r * kd + c] = kp1[(int64_t)i * kd + c]; pts2[r * kd + c] = kp2[j * kd + c]; }
-    }
-}
-
-/* mt_gather_kernel for a pair list: keep / rank / idx live at the pair's output rows out[p] .., its keypoints at the rows q1[p] ..
- * of store 1 and (train rows, pair-local in idx) t2[p] .. of store 2 */
-__global__ __launch_bounds__(256) void mt_gather_pairs_kernel(const int32_t *pair_of_e, const int64_t *est_off, const int32_t *out, const int32_t *q1,
-                                                              const int32_t *t2, const uint8_t *keep, const int32_t *rank, const int32_t *idx,
-                                                              const double *kp1, const double *kp2, int kd, const uint32_t *seeds, double *pts1,
-                                                              double *pts2, uint32_t *seeds_e)
+/* one workgroup per eligible pair: its tentatives in query order become rows est_off[e] .. of the estimator's input.  keep / rank /
+ * idx live at the pair's output rows out[p] .., its keypoints at the rows q1[p] .. of kp1 and (train rows, pair-local in idx)
+ * t2[p] .. of kp2 */
+__global__ __launch_bounds__(256) void mt_gather_kernel(const int32_t *pair_of_e, const int64_t *est_off, const int32_t *out, const int32_t *q1,
+                                                        const int32_t *t2, const uint8_t *keep, const int32_t *rank, const int32_t *idx,
+                                                        const double *kp1, const double *kp2, int kd, const uint32_t *seeds, double *pts1,
+                                                        double *pts2, uint32_t *seeds_e)
 {
     const int e = blockIdx.x, p = pair_of_e[e];
     const int lo = out[p], hi = out[p + 1];
@@ -530,30 +505,31 @@ static void mt_batch_split(int qtiles, int max_n2, int device, int *t_chunk, int
     *n_splits = max_n2 > 0 ? (max_n2 + *t_chunk - 1) / *t_chunk : 1;
 }
 
-/* One launch over the 64-query tiles of every pair.  The train set is split over blockIdx.y only when the batch's tiles do not
- * cover the CUs about twice (as in mi_degensac_match_knn2_dev, with the largest pair's train set deciding the chunk). */
-int mt_batch_knn2(int norm, int words, const void *dq, const void *dt, const int64_t *oq, const int64_t *ot, int n_pairs, int device, hipStream_t s,
-                  int32_t *idx, float *dist)
+/* One launch over the 64-query tiles of every pair (from the pair's first row on).  The train set is split over blockIdx.y only when
+ * the batch's tiles do not cover the CUs about twice (as in mi_degensac_match_knn2_dev, with the largest pair's train set deciding
+ * the chunk). */
+int mt_batch_knn2(int norm, int words, const void *dq, const void *dt, const mt_pair_rows *rows, int n_pairs, int n_rows, int swap, int device,
+                  hipStream_t s, int32_t *idx, float *dist)
 {
-    const int n_rows = (int)oq[n_pairs];
     if (n_rows == 0) return 0;
-    std::vector<int4> tiles;
+    std::vector<mt_ptile> tiles;
     int max_n2 = 0;
     for (int p = 0; p < n_pairs; p++) {
-        const int q_end = (int)oq[p + 1], t_b = (int)ot[p], t_e = (int)ot[p + 1];
-        if (t_e - t_b > max_n2) max_n2 = t_e - t_b;
-        for (int q0 = (int)oq[p]; q0 < q_end; q0 += MT_Q) tiles.push_back(make_int4(q0, q_end, t_b, t_e));
+        const mt_pair_rows &r = rows[p];
+        const int qb = swap ? r.t : r.q, nq = swap ? r.nt : r.nq, tb = swap ? r.q : r.t, nt = swap ? r.nq : r.nt, ob = swap ? r.back : r.out;
+        if (nt > max_n2) max_n2 = nt;
+        for (int k = 0; k < nq; k += MT_Q) tiles.push_back(mt_ptile{make_int4(qb + k, qb + nq, tb, tb + nt), ob + k, {0, 0, 0}});
     }
     const int qtiles = (int)tiles.size();
     int t_chunk, splits; mt_batch_split(qtiles, max_n2, device, &t_chunk, &splits);
-    const size_t b_tiles = ((size_t)qtiles * sizeof(int4) + 255) / 256 * 256, b_part = splits > 1 ? (size_t)splits * n_rows * sizeof(mt_best) : 0;
+    const size_t b_tiles = ((size_t)qtiles * sizeof(mt_ptile) + 255) / 256 * 256, b_part = splits > 1 ? (size_t)splits * n_rows * sizeof(mt_best) : 0;
     char *buf = nullptr;
     MTCHK(hipMallocAsync((void **)&buf, b_tiles + b_part, s));
-    int rc = mt_batch_upload(device, s, tiles.data(), (size_t)qtiles * sizeof(int4), buf);
+    int rc = mt_batch_upload(device, s, tiles.data(), (size_t)qtiles * sizeof(mt_ptile), buf);
     if (rc) { (void)hipFreeAsync(buf, s); return rc; }
     mt_best *part = splits > 1 ? (mt_best *)(buf + b_tiles) : nullptr;
     const dim3 grid(qtiles, splits), block(256);
-    MT_LAUNCH_NORM(mt_knn2_batch_kernel, norm, words, grid, block, s, (const uint32_t *)dq, (const uint32_t *)dt, words, (const int4 *)buf, n_rows,
+    MT_LAUNCH_NORM(mt_knn2_batch_kernel, norm, words, grid, block, s, (const uint32_t *)dq, (const uint32_t *)dt, words, (const mt_ptile *)buf, n_rows,
         t_chunk, idx, dist, part);
     hipError_t le = hipGetLastError();
     if (le == hipSuccess && part) {
@@ -575,13 +551,13 @@ int mt_batch_filter_rank(const int32_t *d_idx, const float *d_dist, const int32_
     return 0;
 }
 
-int mt_batch_gather(int n_eligible, const int32_t *d_pair_of_e, const int64_t *d_est_off, const int32_t *d_off1, const int32_t *d_off2,
+int mt_batch_gather(int n_eligible, const int32_t *d_pair_of_e, const int64_t *d_est_off, const int32_t *d_out, const int32_t *d_q1, const int32_t *d_t2,
                     const uint8_t *d_keep, const int32_t *d_rank, const int32_t *d_idx, const double *d_kp1, const double *d_kp2, int kp_dim,
                     const uint32_t *d_seeds, hipStream_t s, double *d_pts1, double *d_pts2, uint32_t *d_seeds_e)
 {
     if (n_eligible <= 0) return 0;
-    hipLaunchKernelGGL(mt_gather_kernel, dim3(n_eligible), dim3(256), 0, s, d_pair_of_e, d_est_off, d_off1, d_off2, d_keep, d_rank, d_idx, d_kp1, d_kp2,
-        kp_dim, d_seeds, d_pts1, d_pts2, d_seeds_e);
+    hipLaunchKernelGGL(mt_gather_kernel, dim3(n_eligible), dim3(256), 0, s, d_pair_of_e, d_est_off, d_out, d_q1, d_t2, d_keep, d_rank, d_idx, d_kp1,
+        d_kp2, kp_dim, d_seeds, d_pts1, d_pts2, d_seeds_e);
     MTCHK(hipGetLastError());
     return 0;
 }
@@ -616,13 +592,14 @@ extern "C" int mi_degensac_match_knn2_batch_dev(int norm, const void *d_desc1, c
     if (!mt_check_offsets(offsets1_host, n_pairs) || !mt_check_offsets(offsets2_host, n_pairs)) {
         snprintf(mt_err, sizeof mt_err, "offsets must be non-negative and non-decreasing"); return MI_DEGENSAC_EINVAL; }
     MtDevGuard g; rc = g.enter(device); if (rc) return rc;
-    std::vector<int64_t> o1(n_pairs + 1), o2(n_pairs + 1);
-    for (int p = 0; p <= n_pairs; p++) { o1[p] = offsets1_host[p] - offsets1_host[0]; o2[p] = offsets2_host[p] - offsets2_host[0]; }
+    std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
+    mt_ragged_rows(offsets1_host, offsets2_host, n_pairs, o1, o2, rows);
     return mt_batch_knn2(norm, words, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words,
-                         (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words, o1.data(), o2.data(), n_pairs, device, (hipStream_t)stream, d_idx + 2 * offsets1_host[0], d_dist + 2 * offsets1_host[0]);
+                         (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words, rows.data(), n_pairs, (int)o1[n_pairs], 0, device,
+                         (hipStream_t)stream, d_idx + 2 * offsets1_host[0], d_dist + 2 * offsets1_host[0]);
 }
 
-/* ---- the pair-list form: host side ----------------------------------------------------------------------------------- */
+/* ---- the pair list's row layout ------------------------------------------------------------------------------------------ */
 int mt_pairs_layout(const int64_t *off1, int m1, const int64_t *off2, int m2, const int32_t *pairs, int n_pairs, mt_pair_rows *rows,
                     int64_t *n_out, int64_t *n_back)
 {
@@ -648,52 +625,6 @@ int mt_pairs_layout(const int64_t *off1, int m1, const int64_t *off2, int m2, co
     return 0;
 }
 
-/* mt_batch_knn2 over a pair list: the same tiles per pair (64 queries from the image's first row on), the same split rule */
-int mt_pairs_knn2(int norm, int words, const void *dq, const void *dt, const mt_pair_rows *rows, int n_pairs, int n_rows, int swap, int device,
-                  hipStream_t s, int32_t *idx, float *dist)
-{
-    if (n_rows == 0) return 0;
-    std::vector<mt_ptile> tiles;
-    int max_n2 = 0;
-    for (int p = 0; p < n_pairs; p++) {
-        const mt_pair_rows &r = rows[p];
-        const int qb = swap ? r.t : r.q, nq = swap ? r.nt : r.nq, tb = swap ? r.q : r.t, nt = swap ? r.nq : r.nt, ob = swap ? r.back : r.out;
-        if (nt > max_n2) max_n2 = nt;
-        for (int k = 0; k < nq; k += MT_Q) tiles.push_back(mt_ptile{qb + k, qb + nq, tb, tb + nt, ob + k, {0, 0, 0}});
-    }
-    const int qtiles = (int)tiles.size();
-    int t_chunk, splits; mt_batch_split(qtiles, max_n2, device, &t_chunk, &splits);
-    const size_t b_tiles = ((size_t)qtiles * sizeof(mt_ptile) + 255) / 256 * 256, b_part = splits > 1 ? (size_t)splits * n_rows * sizeof(mt_best) : 0;
-    char *buf = nullptr;
-    MTCHK(hipMallocAsync((void **)&buf, b_tiles + b_part, s));
-    int rc = mt_batch_upload(device, s, tiles.data(), (size_t)qtiles * sizeof(mt_ptile), buf);
-    if (rc) { (void)hipFreeAsync(buf, s); return rc; }
-    mt_best *part = splits > 1 ? (mt_best *)(buf + b_tiles) : nullptr;
-    const dim3 grid(qtiles, splits), block(256);
-    MT_LAUNCH_NORM(mt_knn2_pairs_kernel, norm, words, grid, block, s, (const uint32_t *)dq, (const uint32_t *)dt, words, (const mt_ptile *)buf, n_rows,
-        t_chunk, idx, dist, part);
-    hipError_t le = hipGetLastError();
-    if (le == hipSuccess && part) {
-        hipLaunchKernelGGL(mt_merge_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, s, part, splits, n_rows, norm != MI_DEGENSAC_NORM_HAMMING ? 1 : 0, idx,
-            dist);
-        le = hipGetLastError();
-    }
-    (void)hipFreeAsync(buf, s);
-    MTCHK(le);
-    return 0;
-}
-
-int mt_pairs_gather(int n_eligible, const int32_t *d_pair_of_e, const int64_t *d_est_off, const int32_t *d_out, const int32_t *d_q1, const int32_t *d_t2,
-                    const uint8_t *d_keep, const int32_t *d_rank, const int32_t *d_idx, const double *d_kp1, const double *d_kp2, int kp_dim,
-                    const uint32_t *d_seeds, hipStream_t s, double *d_pts1, double *d_pts2, uint32_t *d_seeds_e)
-{
-    if (n_eligible <= 0) return 0;
-    hipLaunchKernelGGL(mt_gather_pairs_kernel, dim3(n_eligible), dim3(256), 0, s, d_pair_of_e, d_est_off, d_out, d_q1, d_t2, d_keep, d_rank, d_idx, d_kp1,
-        d_kp2, kp_dim, d_seeds, d_pts1, d_pts2, d_seeds_e);
-    MTCHK(hipGetLastError());
-    return 0;
-}
-
 extern "C" int mi_degensac_match_knn2_pairs_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host, int n_images1,
                                                 const int64_t *offsets2_host, int n_images2, const int32_t *pairs_host, int n_pairs, int dim,
                                                 int device, void *stream, int32_t *d_idx, float *d_dist)
@@ -707,7 +638,8 @@ extern "C" int mi_degensac_match_knn2_pairs_dev(int norm, const void *d_desc1, c
     rc = mt_pairs_layout(offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, rows.data(), &n_out, &n_back); if (rc) return rc;
     if ((n_out > 0 && (!d_desc1 || !d_idx || !d_dist)) || (n_out > 0 && n_back > 0 && !d_desc2)) { snprintf(mt_err, sizeof mt_err, "NULL argument"); return MI_DEGENSAC_EINVAL; }
     MtDevGuard g; rc = g.enter(device); if (rc) return rc;
-    return mt_pairs_knn2(norm, words, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words, (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words,
+    return mt_batch_knn2(norm, words, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words,
+                         (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words,
                          rows.data(), n_pairs, (int)n_out, 0, device, (hipStream_t)stream, d_idx, d_dist);
 }
 

@@ -177,6 +177,39 @@ def _check_sides(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_
     return _NORMS[norm], kinds[0][0]
 
 
+def _counts_to_offsets(counts, n_rows, per, side_by_side):
+    """rows per pair / per image of the two sides, counts = (counts1, counts2) against n_rows = (rows1, rows2) -> [offsets1, offsets2],
+    int64 [len + 1] each; raises ValueError.  side_by_side: every check on side 1 before any on side 2 (the pair-list calls), else every
+    side under one check before the next check (the ragged calls): which text a call raises for two different defects is pinned."""
+    checks = [(lambda c, n: c.ndim != 1, f"counts1 and counts2 should be 1-D with one entry per {per}"),
+              (lambda c, n: c.size and not np.issubdtype(c.dtype, np.integer), "counts should be integers"),
+              (lambda c, n: (c < 0).any(), "counts should be >= 0"),
+              (lambda c, n: c.sum() != n, "counts do not add up to the number of descriptor rows")]
+    sides = [(np.asarray(c), n) for c, n in zip(counts, n_rows)]
+    if side_by_side:
+        order = [(side, check) for side in sides for check in checks]
+    else:
+        order = [(side, check) for check in checks for side in sides]
+    for (c, n), (bad, msg) in order:
+        if bad(c, n):
+            raise ValueError(msg)
+    offs = []
+    for c, _ in sides:
+        o = np.zeros(len(c) + 1, np.int64); np.cumsum(c, out=o[1:]); offs.append(o)
+    return offs
+
+
+def _seeds_u32(seeds, K):
+    """one seed per pair as contiguous uint32 [K] (any integer, taken modulo 2^32); None = parallel.pair_seeds(0, K); raises ValueError"""
+    if seeds is None:
+        from . import parallel
+        seeds = parallel.pair_seeds(0, K)
+    sd = np.asarray(seeds)
+    if sd.shape != (K,):
+        raise ValueError("one seed per pair")
+    return np.ascontiguousarray(sd.astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+
+
 def check_match_verify_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype, counts1, counts2,
                             fginn_th=None):
     """The argument checks of the batched match-and-verify calls, on shapes and dtype names only (numpy or torch).  Returns
@@ -185,17 +218,9 @@ def check_match_verify_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2
     if fginn_th is not None:
         check_fginn_th(fginn_th)
     code, kind = _check_sides(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype)
-    c1 = np.asarray(counts1); c2 = np.asarray(counts2)
-    if c1.ndim != 1 or c2.ndim != 1 or len(c1) != len(c2):
+    if np.ndim(counts1) == 1 and np.ndim(counts2) == 1 and len(counts1) != len(counts2):
         raise ValueError("counts1 and counts2 should be 1-D with one entry per pair")
-    if (c1.size and not np.issubdtype(c1.dtype, np.integer)) or (c2.size and not np.issubdtype(c2.dtype, np.integer)):
-        raise ValueError("counts should be integers")
-    if (c1 < 0).any() or (c2 < 0).any():
-        raise ValueError("counts should be >= 0")
-    o1 = np.zeros(len(c1) + 1, np.int64); np.cumsum(c1, out=o1[1:])
-    o2 = np.zeros(len(c2) + 1, np.int64); np.cumsum(c2, out=o2[1:])
-    if o1[-1] != d1_shape[0] or o2[-1] != d2_shape[0]:
-        raise ValueError("counts do not add up to the number of descriptor rows")
+    o1, o2 = _counts_to_offsets((counts1, counts2), (d1_shape[0], d2_shape[0]), "pair", False)
     return code, kind, o1, o2
 
 
@@ -211,19 +236,7 @@ def check_match_pairs_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_
     if fginn_th is not None:
         raise ValueError("fginn_th (the FGINN ratio test) is not part of the pair-list calls: use match_and_verify_batch")
     code, kind = _check_sides(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype)
-    offs = []
-    for c, rows in ((counts1, d1_shape[0]), (counts2, d2_shape[0])):
-        c = np.asarray(c)
-        if c.ndim != 1:
-            raise ValueError("counts1 and counts2 should be 1-D with one entry per image")
-        if c.size and not np.issubdtype(c.dtype, np.integer):
-            raise ValueError("counts should be integers")
-        if (c < 0).any():
-            raise ValueError("counts should be >= 0")
-        o = np.zeros(len(c) + 1, np.int64); np.cumsum(c, out=o[1:])
-        if o[-1] != rows:
-            raise ValueError("counts do not add up to the number of descriptor rows")
-        offs.append(o)
+    offs = _counts_to_offsets((counts1, counts2), (d1_shape[0], d2_shape[0]), "image", True)
     pr = np.asarray(pairs)
     if pr.ndim != 2 or pr.shape[1] != 2 or not np.issubdtype(pr.dtype, np.integer):
         raise ValueError("pairs should be an integer array [K, 2] of (image of store 1, image of store 2)")
@@ -237,12 +250,7 @@ def check_match_pairs_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_
     po = np.zeros(K + 1, np.int64); np.cumsum(np.diff(offs[0])[pr[:, 0]], out=po[1:])
     if po[-1] > 0x3fffffff or np.diff(offs[1])[pr[:, 1]].sum() > 0x3fffffff:
         raise ValueError("too many rows in one pair list")
-    if seeds is not None:
-        sd = np.asarray(seeds)
-        if sd.shape != (K,):
-            raise ValueError("one seed per pair")
-        seeds = np.ascontiguousarray(sd.astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
-    return code, kind, offs[0], offs[1], pr, po, seeds
+    return code, kind, offs[0], offs[1], pr, po, None if seeds is None else _seeds_u32(seeds, K)
 
 
 def exhaustive_pairs(n, ordered=False):
@@ -308,7 +316,25 @@ def _h_driver_form(M):
     return out
 
 
-def _stack_pairs(kps1_list, kps2_list, desc1_list, desc2_list, model, ratio, norm, device):
+def _h_user_form(M):
+    """the driver's H_c -> the user-facing H = inv(H_c^T) (utils.py:108); zero models stay zero"""
+    out = np.zeros_like(M)
+    for i in range(M.shape[0]):
+        if np.abs(M[i]).sum() != 0:
+            out[i] = np.linalg.inv(M[i].T)
+    return out
+
+
+def _set_last_stats(st, cnt):
+    """the per-pair stats rows [K, 16] and tentative counts [K] of a match-and-verify call -> last_stats()"""
+    from . import api
+    stats = [_lib.stats_dict(s) for s in st]
+    for d, c in zip(stats, cnt):
+        d["tentatives"] = int(c)
+    api._tls.stats = stats
+
+
+def _stack_pairs(kps1_list, kps2_list, desc1_list, desc2_list, model, ratio, norm, device, fginn_th=None):
     """the per-pair lists of the batched calls -> (norm code, A, B, K1, K2, offsets1, offsets2): descriptors padded to whole 32-bit
     words for uint8 rows, keypoints as float64 [n, 2] / [n, 6] rows"""
     K = len(desc1_list)
@@ -326,7 +352,7 @@ def _stack_pairs(kps1_list, kps2_list, desc1_list, desc2_list, model, ratio, nor
         raise ValueError("one keypoint row per descriptor row")
     A = np.concatenate(a); B = np.concatenate(b); K1 = np.concatenate(k1); K2 = np.concatenate(k2)
     code, kind, o1, o2 = check_match_verify_args(model, ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape, K2.dtype,
-                                                 np.asarray(c1, np.int64), np.asarray(c2, np.int64))
+                                                 np.asarray(c1, np.int64), np.asarray(c2, np.int64), fginn_th)
     return code, kind, A, B, K1, K2, o1, o2
 
 
@@ -401,35 +427,11 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
     fginn_th: None = the plain ratio test; a number switches it to the FGINN ratio test of match_fginn at that radius in pixels of
     kps2 (the guided stage keeps its own gate and decision).
     last_stats() holds the per-pair statistics, with "tentatives"."""
-    from . import api, parallel
-    K = len(desc1_list)
-    if not (len(kps1_list) == len(kps2_list) == len(desc2_list) == K):
-        raise ValueError("kps1_list, kps2_list, desc1_list and desc2_list should hold one entry per pair")
-    a = [np.asarray(x) for x in desc1_list]; b = [np.asarray(x) for x in desc2_list]
-    k1 = [np.asarray(x) for x in kps1_list]; k2 = [np.asarray(x) for x in kps2_list]
-    if K == 0:
-        raise ValueError("at least one pair")
-    for lst in (a, b, k1, k2):
-        if any(x.ndim != 2 or x.dtype != lst[0].dtype or x.shape[1] != lst[0].shape[1] for x in lst):
-            raise ValueError("every pair's arrays should be 2-D with the dtype and width of pair 0")
-    c1 = [x.shape[0] for x in a]; c2 = [x.shape[0] for x in b]
-    if [x.shape[0] for x in k1] != c1 or [x.shape[0] for x in k2] != c2:
-        raise ValueError("one keypoint row per descriptor row")
-    A = np.concatenate(a); B = np.concatenate(b); K1 = np.concatenate(k1); K2 = np.concatenate(k2)
-    code, kind, o1, o2 = check_match_verify_args(model, ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape, K2.dtype,
-                                                 np.asarray(c1, np.int64), np.asarray(c2, np.int64), fginn_th)
+    code, kind, A, B, K1, K2, o1, o2 = _stack_pairs(kps1_list, kps2_list, desc1_list, desc2_list, model, ratio, norm, device, fginn_th)
+    K = len(o1) - 1
     prm = estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
-    if code != NORM_L2:
-        A, B = _pad_words(A, B)
-    A = np.ascontiguousarray(A); B = np.ascontiguousarray(B)
-    if kind == "kpts":
-        K1 = kpts_to_xyA(K1, device); K2 = kpts_to_xyA(K2, device)
-    K1 = np.ascontiguousarray(K1, np.float64); K2 = np.ascontiguousarray(K2, np.float64)
-    if seeds is None:
-        seeds = parallel.pair_seeds(0, K)
-    sd = np.ascontiguousarray(np.asarray(seeds, dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
-    if sd.shape != (K,):
-        raise ValueError("one seed per pair")
+    A, B, K1, K2 = _finish_pairs(code, kind, A, B, K1, K2, device)
+    sd = _seeds_u32(seeds, K)
     mp = _lib.MatchParams(code, A.shape[1], ratio, mutual, fginn_th)
     n1 = A.shape[0]
     M = np.zeros((K, 9)); match = np.full(n1, -1, np.int32); inl = np.zeros(n1, np.uint8)
@@ -441,20 +443,13 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
                                                    match.ctypes.data_as(C.POINTER(C.c_int32)), inl.ctypes.data_as(C.POINTER(C.c_uint8)),
                                                    st.ctypes.data_as(C.POINTER(C.c_int32)), cnt.ctypes.data_as(C.POINTER(C.c_int32)))
     _lib.check(rc)
-    stats = [_lib.stats_dict(s) for s in st]
-    for d, c in zip(stats, cnt):
-        d["tentatives"] = int(c)
-    api._tls.stats = stats
+    _set_last_stats(st, cnt)
     gm = None
     if guided:                  # the driver-form models as the library wrote them, before the inversion below
         gm = _guided_host(code, A, B, K1, K2, o1, o2, M, model, ratio, mutual, prm.px_th, prm.error_type, device)[0]
     M = M.reshape(K, 3, 3)
     if model == "H":
-        out = np.zeros_like(M)
-        for i in range(K):
-            if np.abs(M[i]).sum() != 0:
-                out[i] = np.linalg.inv(M[i].T)
-        M = out
+        M = _h_user_form(M)
     res = (M, [match[o1[p]:o1[p + 1]] for p in range(K)], [inl[o1[p]:o1[p + 1]].astype(bool) for p in range(K)])
     return res + ([gm[o1[p]:o1[p + 1]] for p in range(K)],) if guided else res
 
@@ -469,7 +464,6 @@ def match_and_verify_pairs(kps_list, desc_list, pairs, model="F", ratio=0.9, mut
     the number of pairs.  Per pair the results are bit for bit those of match_and_verify_batch on the pair's copied arrays with the
     same seeds (one per list entry, default parallel.pair_seeds(0, K)).  Returns (models [K, 3, 3], [match_p], [inlier_p]) as
     match_and_verify_batch; guided and fginn_th are not part of this call (ValueError).  last_stats() holds the per-pair statistics."""
-    from . import api, parallel
     if (kps2_list is None) != (desc2_list is None):
         raise ValueError("kps2_list and desc2_list go together")
     one = desc2_list is None
@@ -493,7 +487,7 @@ def match_and_verify_pairs(kps_list, desc_list, pairs, model="F", ratio=0.9, mut
     prm = estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
     K = len(pr)
     if sd is None:
-        sd = np.ascontiguousarray(np.asarray(parallel.pair_seeds(0, K), dtype=np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+        sd = _seeds_u32(None, K)
 
     def prep(D, Kp):
         if code != NORM_L2:
@@ -514,15 +508,8 @@ def match_and_verify_pairs(kps_list, desc_list, pairs, model="F", ratio=0.9, mut
                                                    int(device), _lib.dptr(M), match.ctypes.data_as(ip), inl.ctypes.data_as(C.POINTER(C.c_uint8)),
                                                    st.ctypes.data_as(ip), cnt.ctypes.data_as(ip))
     _lib.check(rc)
-    stats = [_lib.stats_dict(s) for s in st]
-    for d, c in zip(stats, cnt):
-        d["tentatives"] = int(c)
-    api._tls.stats = stats
+    _set_last_stats(st, cnt)
     M = M.reshape(K, 3, 3)
     if model == "H":
-        out = np.zeros_like(M)
-        for i in range(K):
-            if np.abs(M[i]).sum() != 0:
-                out[i] = np.linalg.inv(M[i].T)
-        M = out
+        M = _h_user_form(M)
     return M, [match[po[p]:po[p + 1]] for p in range(K)], [inl[po[p]:po[p + 1]].astype(bool) for p in range(K)]

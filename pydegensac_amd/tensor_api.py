@@ -309,6 +309,44 @@ def guided_match_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model
     return _guided_dev(code, a, b, k1, k2, o1, o2, M.reshape(K, 9).contiguous(), model, ratio, mutual, px, et)
 
 
+def _h_user_form(M):
+    """the driver's H_c [K, 3, 3] -> the user-facing inv(H_c^T) where a model was found, without a host round trip: short / failed
+    pairs invert the identity and stay zero"""
+    import torch
+    K = M.shape[0]
+    found = (M.abs().sum(dim=(1, 2)) != 0).view(K, 1, 1)
+    eye = torch.eye(3, dtype=M.dtype, device=M.device).expand(K, 3, 3)
+    inv = torch.linalg.inv_ex(torch.where(found, M.transpose(1, 2), eye)).inverse      # inv_ex: no error check, no sync
+    return torch.where(found, inv, torch.zeros_like(M))
+
+
+def _match_verify_dev(entry, layout, model, mp, prm, a, b, k1, k2, sd, K, n, guide=None):
+    """The match-and-verify call of both layouts after the argument checks: entry = the *_dev entry point, layout = its arguments
+    between the descriptors and the estimator's params, sd = uint32 seeds [K], n = output rows.  guide (nullable) gets the driver-form
+    models [K, 9] as the library wrote them, on the same stream.  Returns (model [K, 3, 3] — H as the user-facing form —, match [n],
+    inlier [n] bool, stats [K, 16], n_tentatives [K] numpy int64, what guide returned)."""
+    import torch
+    dev = a.device
+    # pinned + non_blocking: a pageable copy would wait for the stream (the call's one synchronisation is the count read)
+    d_seeds = torch.from_numpy(sd.view(np.int32)).pin_memory().to(dev, non_blocking=True)
+    M = torch.zeros((K, 9), dtype=torch.float64, device=dev)
+    match = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    inlier = torch.zeros(n, dtype=torch.uint8, device=dev)
+    stats = torch.zeros((K, 16), dtype=torch.int32, device=dev)
+    cnt = np.zeros(K, np.int32)
+    stream = torch.cuda.current_stream(dev)
+    rc = entry(1 if model == "H" else 0, C.byref(mp), a.data_ptr(), b.data_ptr(), *layout, C.byref(prm), d_seeds.data_ptr(), dev.index or 0,
+               C.c_void_p(stream.cuda_stream), M.data_ptr(), match.data_ptr(), inlier.data_ptr(), stats.data_ptr(),
+               cnt.ctypes.data_as(C.POINTER(C.c_int32)))
+    _lib.check(rc)
+    # the estimator and the scatter read these asynchronously: keep them alive until the stream reaches this point
+    for t in (a, b, k1, k2, d_seeds):
+        t.record_stream(stream)
+    gm = guide(M) if guide else None
+    M = M.view(K, 3, 3)
+    return _h_user_form(M) if model == "H" else M, match, inlier.to(torch.bool), stats, cnt.astype(np.int64), gm
+
+
 def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
                                    max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
                                    enable_degeneracy_check=True, seeds=None, guided=False, norm=None, fginn_th=None):
@@ -328,7 +366,7 @@ def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, m
     fginn_th: None = the plain ratio test; a number switches it to the FGINN ratio test (knn_match_fginn_batch_tensors at that radius
     on kps2's x, y).  Only the tentatives in front of the estimator change: the guided stage keeps its own gate and decision."""
     import torch
-    from . import matcher, parallel
+    from . import matcher
     ts = (kps1, kps2, desc1, desc2)
     if not all(isinstance(t, torch.Tensor) for t in ts):
         raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
@@ -338,44 +376,18 @@ def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, m
         raise ValueError("kps1, kps2, desc1 and desc2 must live on the same ROCm device")
     prm = matcher.estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
     a, b = _desc_pair(desc1, desc2)
-    dev = a.device; K = len(o1) - 1; n1 = a.shape[0]
+    K = len(o1) - 1; n1 = a.shape[0]
     if kind == "kpts":
         k1 = kpts_to_xyA_tensors(kps1); k2 = kpts_to_xyA_tensors(kps2)
     else:
         k1 = kps1.contiguous(); k2 = kps2.contiguous()
-    if seeds is None:
-        seeds = parallel.pair_seeds(0, K)
-    seeds = np.asarray(seeds, dtype=np.int64).ravel()
-    if seeds.shape != (K,):
-        raise ValueError("one seed per pair")
-    # pinned + non_blocking: a pageable copy would wait for the stream (the call's one synchronisation is the count read)
-    d_seeds = torch.from_numpy((seeds & 0xFFFFFFFF).astype(np.uint32).view(np.int32)).pin_memory().to(dev, non_blocking=True)
-    M = torch.zeros((K, 9), dtype=torch.float64, device=dev)
-    match = torch.full((n1,), -1, dtype=torch.int32, device=dev)
-    inlier = torch.zeros(n1, dtype=torch.uint8, device=dev)
-    stats = torch.zeros((K, 16), dtype=torch.int32, device=dev)
-    cnt = np.zeros(K, np.int32)
-    mp = _lib.MatchParams(code, a.shape[1], ratio, mutual, fginn_th)
-    stream = torch.cuda.current_stream(dev)
-    rc = _lib.lib().mi_degensac_match_verify_batch_dev(1 if model == "H" else 0, C.byref(mp), a.data_ptr(), b.data_ptr(),
-                                                       o1.ctypes.data_as(C.POINTER(C.c_int64)), o2.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                       k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]), K, C.byref(prm), d_seeds.data_ptr(),
-                                                       dev.index or 0, C.c_void_p(stream.cuda_stream), M.data_ptr(), match.data_ptr(),
-                                                       inlier.data_ptr(), stats.data_ptr(), cnt.ctypes.data_as(C.POINTER(C.c_int32)))
-    _lib.check(rc)
-    # the estimator and the scatter read these asynchronously: keep them alive until the stream reaches this point
-    for t in (a, b, k1, k2, d_seeds):
-        t.record_stream(stream)
-    gm = _guided_dev(code, a, b, k1, k2, o1, o2, M, model, ratio, mutual, prm.px_th, prm.error_type)[0] if guided else None
-    M = M.view(K, 3, 3)
-    if model == "H":
-        # inv(H_c^T) where a model was found, without a host round trip: short / failed pairs invert the identity and are zeroed
-        found = (M.abs().sum(dim=(1, 2)) != 0).view(K, 1, 1)
-        eye = torch.eye(3, dtype=M.dtype, device=dev).expand(K, 3, 3)
-        inv = torch.linalg.inv_ex(torch.where(found, M.transpose(1, 2), eye)).inverse      # inv_ex: no error check, no sync
-        M = torch.where(found, inv, torch.zeros_like(M))
-    res = (M, match, inlier.to(torch.bool), stats, cnt.astype(np.int64))
-    return res + (gm,) if guided else res
+    sd = matcher._seeds_u32(None if seeds is None else np.asarray(seeds).ravel(), K)
+    lp = C.POINTER(C.c_int64)
+    guide = (lambda M: _guided_dev(code, a, b, k1, k2, o1, o2, M, model, ratio, mutual, prm.px_th, prm.error_type)[0]) if guided else None
+    res = _match_verify_dev(_lib.lib().mi_degensac_match_verify_batch_dev, (o1.ctypes.data_as(lp), o2.ctypes.data_as(lp), k1.data_ptr(), k2.data_ptr(),
+                                                                          int(k1.shape[1]), K),
+                            model, _lib.MatchParams(code, a.shape[1], ratio, mutual, fginn_th), prm, a, b, k1, k2, sd, K, n1, guide)
+    return res if guided else res[:5]
 
 
 # ---- the pair-list form: image stores + (i, j) image indices (include/mi_degensac.h mi_degensac_match_*_pairs*) ----
@@ -422,7 +434,7 @@ def match_and_verify_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, p
     numpy int64, pair_offsets [K + 1] host int64) with N = pair_offsets[K]: the per-query outputs lie pair after pair in list order.
     guided=True and fginn_th are not part of this call (ValueError): both stages keep their batched entry points."""
     import torch
-    from . import matcher, parallel
+    from . import matcher
     ts = (kps1, kps2, desc1, desc2)
     if not all(isinstance(t, torch.Tensor) for t in ts):
         raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
@@ -433,35 +445,13 @@ def match_and_verify_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, p
         raise ValueError("kps1, kps2, desc1 and desc2 must live on the same ROCm device")
     prm = matcher.estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
     a, b = _desc_pair(desc1, desc2)
-    dev = a.device; K = len(pr); n = int(po[-1])
+    K = len(pr); n = int(po[-1])
     conv = kpts_to_xyA_tensors if kind == "kpts" else (lambda k: k.contiguous())
     k1 = conv(kps1); k2 = k1 if kps2 is kps1 else conv(kps2)          # once per store, not per pair
     if sd is None:
-        sd = (np.asarray(parallel.pair_seeds(0, K), dtype=np.int64) & 0xFFFFFFFF).astype(np.uint32)
-    # pinned + non_blocking: a pageable copy would wait for the stream (the call's one synchronisation is the count read)
-    d_seeds = torch.from_numpy(sd.view(np.int32)).pin_memory().to(dev, non_blocking=True)
-    M = torch.zeros((K, 9), dtype=torch.float64, device=dev)
-    match = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    inlier = torch.zeros(n, dtype=torch.uint8, device=dev)
-    stats = torch.zeros((K, 16), dtype=torch.int32, device=dev)
-    cnt = np.zeros(K, np.int32)
-    mp = _lib.MatchParams(code, a.shape[1], ratio, mutual)
-    stream = torch.cuda.current_stream(dev)
-    lp = C.POINTER(C.c_int64); ip = C.POINTER(C.c_int32)
-    rc = _lib.lib().mi_degensac_match_verify_pairs_dev(1 if model == "H" else 0, C.byref(mp), a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(lp),
-                                                       len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]),
-                                                       pr.ctypes.data_as(ip), K, C.byref(prm), d_seeds.data_ptr(), dev.index or 0,
-                                                       C.c_void_p(stream.cuda_stream), M.data_ptr(), match.data_ptr(), inlier.data_ptr(),
-                                                       stats.data_ptr(), cnt.ctypes.data_as(ip))
-    _lib.check(rc)
-    # the estimator and the scatter read these asynchronously: keep them alive until the stream reaches this point
-    for t in (a, b, k1, k2, d_seeds):
-        t.record_stream(stream)
-    M = M.view(K, 3, 3)
-    if model == "H":
-        # inv(H_c^T) where a model was found, without a host round trip: short / failed pairs invert the identity and are zeroed
-        found = (M.abs().sum(dim=(1, 2)) != 0).view(K, 1, 1)
-        eye = torch.eye(3, dtype=M.dtype, device=dev).expand(K, 3, 3)
-        inv = torch.linalg.inv_ex(torch.where(found, M.transpose(1, 2), eye)).inverse      # inv_ex: no error check, no sync
-        M = torch.where(found, inv, torch.zeros_like(M))
-    return M, match, inlier.to(torch.bool), stats, cnt.astype(np.int64), po
+        sd = matcher._seeds_u32(None, K)
+    lp = C.POINTER(C.c_int64)
+    layout = (o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]),
+              pr.ctypes.data_as(C.POINTER(C.c_int32)), K)
+    return _match_verify_dev(_lib.lib().mi_degensac_match_verify_pairs_dev, layout, model, _lib.MatchParams(code, a.shape[1], ratio, mutual), prm, a, b,
+                             k1, k2, sd, K, n)[:5] + (po,)

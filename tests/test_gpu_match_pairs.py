@@ -1,12 +1,14 @@
 """GPU: the pair-list calls (include/mi_degensac.h mi_degensac_match_*_pairs*): descriptors and keypoints stored once per image, a
-list of (i, j) image indices.  Equality only: every case compares the pair-list call with the existing batched call on the expansion
-of tests/pairs_ref.py (pair p's rows copied out of the stores), bit for bit."""
+list of (i, j) image indices.  Equality only: every case compares the pair-list call with the batched call on the expansion of
+tests/pairs_ref.py (pair p's rows copied out of the stores), bit for bit.  Both run one kernel under two row tables, so those cases check
+the tables; the kernel itself is anchored against the dense single-pair kernel and the numpy oracle, entry by entry."""
 import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
+from oracle import matcher_np as mo
 from pydegensac_amd import _lib, matcher, synthetic as syn, tensor_api
 from tests import matcher_ref as mr, pairs_ref as pr
 
@@ -102,6 +104,46 @@ def test_knn2_many_pairs_take_no_train_split(norm, dim):
     _, _, (k1, k2) = _knn_both(d, sizes, d, sizes, pairs, norm)
     assert sum((c + 63) // 64 for c in k1) >= 2 * _cus()
     assert mr.batch_split(list(k1), list(k2), _cus())[1] == 1            # the tiles cover the CUs twice: one split
+
+
+def _entries_equal_dense_kernel_and_oracle(d, sizes, pairs, entries, norm):
+    """list entries `entries` of the pair-list 2-NN over the one store d against knn_match_tensors (the dense single-pair kernel) and the
+    numpy oracle on the entry's two images: idx equal, dist equal by bits"""
+    import torch
+    a = _t(d)
+    idx, dist, po = tensor_api.knn_match_pairs_tensors(a, a, sizes, sizes, pairs, norm)
+    torch.cuda.synchronize()
+    idx = idx.cpu().numpy(); dist = dist.cpu().numpy().view(np.uint32)
+    o = pr.offsets(sizes)
+    for p in entries:
+        i, j = pairs[p]
+        q, t = d[o[i]:o[i + 1]], d[o[j]:o[j + 1]]
+        gi, gd = idx[po[p]:po[p + 1]], dist[po[p]:po[p + 1]]
+        assert gi.shape == (sizes[i], 2)
+        di, dd = tensor_api.knn_match_tensors(_t(q), _t(t), norm)
+        assert np.array_equal(gi, di.cpu().numpy()) and np.array_equal(gd, dd.cpu().numpy().view(np.uint32)), (p, i, j)
+        oi, od = mo.knn2(q, t, "l2" if norm == "l2_u8" else norm)       # uint8 rows under L2: the float32 path on the same values
+        assert np.array_equal(gi, oi) and np.array_equal(gd, od.view(np.uint32)), (p, i, j)
+
+
+ANCHOR_WIDTHS = [("l2", 65), ("hamming", 8), ("l2_u8", 128)]
+
+
+@pytest.mark.parametrize("norm,dim", ANCHOR_WIDTHS)
+def test_knn2_split_list_equals_the_dense_kernel_and_the_oracle(norm, dim):
+    k1 = [SIZES[i] for i, _ in PAIRS]; k2 = [SIZES[j] for _, j in PAIRS]
+    assert mr.batch_split(k1, k2, _cus())[1] > 1                         # the train split is taken
+    _entries_equal_dense_kernel_and_oracle(_descs(11, sum(SIZES), dim, norm), SIZES, PAIRS, range(len(PAIRS)), norm)
+
+
+@pytest.mark.parametrize("norm,dim", ANCHOR_WIDTHS)
+def test_knn2_unsplit_list_equals_the_dense_kernel_and_the_oracle(norm, dim):
+    sizes = [129, 65, 200]
+    pairs = np.random.default_rng(7).integers(0, 3, (300, 2))            # the list of test_knn2_many_pairs_take_no_train_split
+    k1 = [sizes[i] for i, _ in pairs]; k2 = [sizes[j] for _, j in pairs]
+    assert mr.batch_split(k1, k2, _cus())[1] == 1
+    sample = np.random.default_rng(8).choice(len(pairs), 20, replace=False)
+    _entries_equal_dense_kernel_and_oracle(_descs(12, sum(sizes), dim, norm), sizes, pairs, sample, norm)
 
 
 @pytest.mark.parametrize("norm,dim", [("l2", 33), ("hamming", 32), ("l2_u8", 32)])
@@ -242,6 +284,43 @@ def test_numpy_entry_point_equals_the_tensor_one():
     match = match.cpu().numpy(); inl = inl.cpu().numpy()
     for p in range(4):
         assert np.array_equal(match[po[p]:po[p + 1]], mh[p]) and np.array_equal(inl[po[p]:po[p + 1]], ih[p]), p
+
+
+def _stats_rows(dicts):
+    """last_stats() back to the stats columns (column 15 with its flag bits)"""
+    rows = np.array([[d[k] for k in _lib.STAT_NAMES] for d in dicts])
+    rows[:, 15] += np.array([d["set_aside"] << 8 | d["streamed"] << 9 | d["discarded"] << 10 | d["rerun"] << 11 for d in dicts])
+    return rows
+
+
+@pytest.mark.parametrize("mutual", [False, True])
+def test_host_forms_with_both_sides_naming_one_store(mutual):
+    """the host-pointer forms share their staging: the ragged batch uploads both sides whatever they are, the list uploads a store named
+    twice only once.  Both equal the tensor forms: models, match, inlier and every stats column but the clock readings."""
+    import pydegensac_amd as pd
+    xy, k4, k6, desc, counts = _scene("F")
+    o = pr.offsets(counts)
+    kl = [xy[o[i]:o[i + 1]] for i in range(4)]; dl = [desc[o[i]:o[i + 1]] for i in range(4)]
+    kw = dict(model="F", mutual=mutual, max_iters=2000)
+    tk, td = _t(xy), _t(desc)
+
+    def same(host, stats, M, match, inl, st, po):
+        assert np.array_equal(M.cpu().numpy(), host[0])
+        match = match.cpu().numpy(); inl = inl.cpu().numpy()
+        for p in range(len(po) - 1):
+            assert np.array_equal(match[po[p]:po[p + 1]], host[1][p]) and np.array_equal(inl[po[p]:po[p + 1]], host[2][p]), p
+        assert np.array_equal(_stats_rows(stats)[:, DET], st.cpu().numpy()[:, DET])
+
+    # the ragged batch: pair p = (image p, image p), one list object on both sides
+    M, match, inl, st, cnt = tensor_api.match_and_verify_batch_tensors(tk, tk, td, td, counts, counts, seeds=SEEDS[:4], **kw)
+    host = matcher.match_and_verify_batch(kl, kl, dl, dl, seeds=SEEDS[:4], **kw)
+    same(host, pd.last_stats(), M, match, inl, st, o)
+    assert list(cnt) == counts                                           # every row matches itself
+    # the list: one store, then the same store given again as the second one
+    M, match, inl, st, cnt, po = tensor_api.match_and_verify_pairs_tensors(tk, tk, td, td, counts, counts, SCENE_PAIRS, seeds=SEEDS, **kw)
+    for second in (dict(), dict(kps2_list=kl, desc2_list=dl)):
+        host = matcher.match_and_verify_pairs(kl, dl, SCENE_PAIRS, seeds=SEEDS, **second, **kw)
+        same(host, pd.last_stats(), M, match, inl, st, po)
 
 
 def test_non_default_stream_and_one_synchronisation():

@@ -2,12 +2,15 @@
 Every stage equals its single-pair counterpart bit for bit: the batched 2-NN equals matcher.knn_match and the numpy oracle, the
 tentatives equal match_snn, and the models / masks / counters equal findFundamentalMatrixBatch / findHomographyBatch on those
 tentatives, whatever else is in the batch."""
+import ctypes as C
+import functools
+
 import numpy as np
 import pytest
 
 import pydegensac_amd as pd
 from oracle import matcher_np as mo
-from pydegensac_amd import matcher, parallel, synthetic as syn, tensor_api
+from pydegensac_amd import _lib, matcher, parallel, synthetic as syn, tensor_api
 
 pytestmark = pytest.mark.gpu
 
@@ -220,3 +223,135 @@ def test_host_pointer_form_equals_tensor_form():
             assert np.array_equal(match[p], mh[p]) and np.array_equal(inl[p], ih[p]), p
             assert [sth[p][k] for k in ("samples", "lo_runs", "I")] == list(st[p, [MI_ST_SAMPLES, MI_ST_LO_RUNS, MI_ST_I]]), p
             assert sth[p]["tentatives"] == cnt[p]
+
+
+# ---- the two sides of a ragged batch with different layouts -------------------------------------------------------------------------
+# a partly filled second query tile against a train set shorter than a tile, an empty side on either side, a full tile against a train
+# set longer than two: no two offsets of the two sides agree after pair 0
+UNEVEN1, UNEVEN2 = [65, 0, 1, 64], [2, 70, 0, 129]
+DET = [c for c in range(16) if c not in (12, 13)]                         # every stats column but the two device clock readings
+
+
+def _uneven_descs(norm, dim, seed):
+    rng = np.random.default_rng(seed)
+    n1, n2 = sum(UNEVEN1), sum(UNEVEN2)
+    if norm == "l2":
+        a = rng.normal(size=(n1, dim)).astype(np.float32); b = rng.normal(size=(n2, dim)).astype(np.float32)
+        b[72:72 + 64:2] = a[66:66 + 32] + 0.05 * rng.normal(size=(32, dim)).astype(np.float32)
+    else:
+        a = rng.integers(0, 256, (n1, dim), dtype=np.uint8); b = rng.integers(0, 256, (n2, dim), dtype=np.uint8)
+        b[72:72 + 64:2] = a[66:66 + 32] ^ (rng.random((32, dim)) < 0.03).astype(np.uint8)
+    b[80] = b[76]                                                       # a tie inside pair 3's train set
+    return a, b
+
+
+@functools.lru_cache(maxsize=None)
+def _uneven_scene():
+    """(K1 [130, 2], K2 [201, 2], D1, D2 float32 [., 32]) under UNEVEN1 / UNEVEN2: pair 3 is a two-view scene (64 queries; their 64
+    second views, 21 twins 1.5 px from a second view with a near-equal descriptor and 44 unrelated rows as train set, shuffled), the
+    other pairs random rows"""
+    rng = np.random.default_rng(31)
+    n1, n2, dim = sum(UNEVEN1), sum(UNEVEN2), 32
+    K1 = rng.uniform(0, 500, (n1, 2)); K2 = rng.uniform(0, 500, (n2, 2))
+    D1 = rng.normal(size=(n1, dim)).astype(np.float32); D2 = rng.normal(size=(n2, dim)).astype(np.float32)
+    p1, p2, lab, _ = syn.two_view_fundamental(64, 0.8, 0.1, seed=32)
+    d2 = D1[66:] + 0.15 * rng.normal(size=(64, dim)).astype(np.float32)
+    d2[~lab] = rng.normal(size=((~lab).sum(), dim)).astype(np.float32)
+    tw = rng.permutation(64)[:21]
+    perm = rng.permutation(129)
+    K1[66:] = p1[:, :2]
+    K2[72:] = np.r_[p2[:, :2], p2[tw, :2] + [1.5, 0.0], K2[72 + 85:]][perm]
+    D2[72:] = np.r_[d2, d2[tw] + 0.002 * rng.normal(size=(21, dim)).astype(np.float32), D2[72 + 85:]][perm]
+    return K1, K2, D1, D2
+
+
+@pytest.mark.parametrize("norm,dim", [("l2", 65), ("hamming", 8), ("l2_u8", 128)])
+def test_knn2_batch_whose_first_offsets_are_above_zero(norm, dim):
+    """the C ABI takes batch offsets that do not start at 0: the rows in front of offsets[0] are never read, the output rows outside
+    [offsets1[0], offsets1[K]) never written"""
+    import torch
+    code = {"l2": 0, "hamming": 1, "l2_u8": 4}[norm]
+    a, b = _uneven_descs(norm, dim, 41)
+    want_idx, want_dist = tensor_api.knn_match_batch_tensors(_t(a), _t(b), UNEVEN1, UNEVEN2, norm)
+    ja, jb = _uneven_descs(norm, dim, 42)
+    A = _t(np.concatenate([ja[:5], a, ja[5:8]])); B = _t(np.concatenate([jb[:12], b, jb[12:14]]))
+    o1 = np.r_[0, np.cumsum(UNEVEN1)].astype(np.int64) + 5; o2 = np.r_[0, np.cumsum(UNEVEN2)].astype(np.int64) + 12
+    n = A.shape[0]
+    idx = torch.full((n, 2), -7, dtype=torch.int32, device=_dev()); dist = torch.full((n, 2), -7.0, dtype=torch.float32, device=_dev())
+    lp = C.POINTER(C.c_int64)
+    rc = _lib.lib().mi_degensac_match_knn2_batch_dev(code, A.data_ptr(), B.data_ptr(), o1.ctypes.data_as(lp), o2.ctypes.data_as(lp), len(UNEVEN1), dim, 0,
+                                                     C.c_void_p(torch.cuda.current_stream().cuda_stream), idx.data_ptr(), dist.data_ptr())
+    assert rc == 0, _lib.lib().mi_degensac_match_last_error()
+    torch.cuda.synchronize()
+    own = slice(int(o1[0]), int(o1[-1]))
+    assert torch.equal(idx[own], want_idx) and torch.equal(dist[own].view(torch.int32), want_dist.view(torch.int32))
+    assert (idx[:own.start] == -7).all() and (idx[own.stop:] == -7).all() and (dist[:own.start] == -7).all() and (dist[own.stop:] == -7).all()
+    assert (want_idx[:65, 1] >= 0).all() and (want_idx[66:, 0] >= 0).all()
+
+
+def test_match_verify_batch_whose_first_offsets_are_above_zero():
+    """the same through mi_degensac_match_verify_batch_dev with the mutual check: the identity rows are relative, every pointer (both
+    descriptor and keypoint arrays, match, inlier) moves by its side's first offset"""
+    import torch
+    K1, K2, D1, D2 = _uneven_scene()
+    K = len(UNEVEN1); seeds = [3, 5, 7, 4000000000]
+    want = tensor_api.match_and_verify_batch_tensors(_t(K1), _t(K2), _t(D1), _t(D2), UNEVEN1, UNEVEN2, model="F", mutual=True, max_iters=2000, seeds=seeds)
+    rng = np.random.default_rng(43)
+    junk = lambda n, like: rng.normal(size=(n,) + like.shape[1:]).astype(like.dtype)
+    a = _t(np.concatenate([junk(5, D1), D1, junk(3, D1)])); b = _t(np.concatenate([junk(12, D2), D2, junk(2, D2)]))
+    k1 = _t(np.concatenate([junk(5, K1), K1, junk(3, K1)])); k2 = _t(np.concatenate([junk(12, K2), K2, junk(2, K2)]))
+    o1 = np.r_[0, np.cumsum(UNEVEN1)].astype(np.int64) + 5; o2 = np.r_[0, np.cumsum(UNEVEN2)].astype(np.int64) + 12
+    n = a.shape[0]; dev = _dev()
+    M = torch.zeros((K, 9), dtype=torch.float64, device=dev); st = torch.zeros((K, 16), dtype=torch.int32, device=dev)
+    match = torch.full((n,), -7, dtype=torch.int32, device=dev); inl = torch.full((n,), 7, dtype=torch.uint8, device=dev)
+    d_seeds = _t(np.asarray(seeds, np.uint32).view(np.int32)); cnt = np.zeros(K, np.int32)
+    mp = _lib.MatchParams(0, D1.shape[1], 0.9, True); prm = matcher.estimator_params("F", max_iters=2000)
+    lp = C.POINTER(C.c_int64)
+    rc = _lib.lib().mi_degensac_match_verify_batch_dev(0, C.byref(mp), a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(lp), o2.ctypes.data_as(lp),
+                                                       k1.data_ptr(), k2.data_ptr(), 2, K, C.byref(prm), d_seeds.data_ptr(), 0,
+                                                       C.c_void_p(torch.cuda.current_stream().cuda_stream), M.data_ptr(), match.data_ptr(),
+                                                       inl.data_ptr(), st.data_ptr(), cnt.ctypes.data_as(C.POINTER(C.c_int32)))
+    assert rc == 0, _lib.lib().mi_degensac_last_error()
+    torch.cuda.synchronize()
+    own = slice(int(o1[0]), int(o1[-1]))
+    assert torch.equal(M.view(K, 3, 3), want[0]) and torch.equal(match[own], want[1]) and torch.equal(inl[own].to(torch.bool), want[2])
+    assert torch.equal(st[:, DET], want[3][:, DET]) and np.array_equal(cnt, want[4])
+    assert (match[:own.start] == -7).all() and (match[own.stop:] == -7).all() and (inl[:own.start] == 7).all() and (inl[own.stop:] == 7).all()
+    assert cnt[3] >= 8 and bool(want[0][3].any()) and int(want[2].sum()) >= 8      # the planted pair is estimated
+
+
+@pytest.mark.parametrize("mutual", [False, True])
+def test_uneven_sides_with_fginn_equal_the_composed_calls(mutual):
+    """match_and_verify_batch_tensors with fginn_th on the uneven batch = the FGINN 2-NN, the reverse plain 2-NN, the filter per pair
+    and the batch estimator on the tentatives"""
+    import torch
+    K1, K2, D1, D2 = _uneven_scene()
+    K = len(UNEVEN1); seeds = [3, 5, 7, 4000000000]; r = 3.0
+    o1 = np.r_[0, np.cumsum(UNEVEN1)]; o2 = np.r_[0, np.cumsum(UNEVEN2)]
+    k1, k2, a, b = _t(K1), _t(K2), _t(D1), _t(D2)
+    M, match, inl, st, cnt = tensor_api.match_and_verify_batch_tensors(k1, k2, a, b, UNEVEN1, UNEVEN2, model="F", mutual=mutual, max_iters=2000,
+                                                                       seeds=seeds, fginn_th=r)
+    idx, dist = tensor_api.knn_match_fginn_batch_tensors(a, b, k2, UNEVEN1, UNEVEN2, r)
+    back = tensor_api.knn_match_batch_tensors(b, a, UNEVEN2, UNEVEN1)[0] if mutual else None
+    P1, P2, elig = [], [], []
+    for p in range(K):
+        q = slice(int(o1[p]), int(o1[p + 1]))
+        bk = back[o2[p]:o2[p + 1]] if mutual and UNEVEN2[p] > 0 else None
+        keep = tensor_api.match_filter_tensors(idx[q], dist[q], 0.9, bk).to(torch.bool)
+        want = torch.where(keep, idx[q, 0], torch.full_like(idx[q, 0], -1))
+        assert torch.equal(match[q], want) and cnt[p] == int(keep.sum()), p
+        if cnt[p] >= 8:
+            elig.append(p); P1.append(k1[q][keep]); P2.append(k2[o2[p]:o2[p + 1]][want[keep].long()])
+        else:
+            assert not bool(M[p].any()) and not bool(st[p].any()) and not bool(inl[q].any()), p
+    assert 3 in elig                                                    # >= 8 planted matches in the one pair that can hold them
+    Fe, me, ste, oe = tensor_api.find_fundamental_batch_tensors(torch.cat(P1), torch.cat(P2), [len(x) for x in P1], max_iters=2000,
+                                                                seeds=[seeds[p] for p in elig])
+    cols = [MI_ST_SAMPLES, MI_ST_LO_RUNS, MI_ST_I]                      # the other columns follow the launch the pair ran in
+    for e, p in enumerate(elig):
+        q = slice(int(o1[p]), int(o1[p + 1]))
+        assert torch.equal(M[p], Fe[e]) and torch.equal(inl[q][match[q] >= 0], me[oe[e]:oe[e + 1]]) and not bool(inl[q][match[q] < 0].any()), p
+        assert torch.equal(st[p, cols], ste[e, cols]), p
+    assert int(inl[int(o1[3]):].sum()) >= 8
+    plain = tensor_api.match_and_verify_batch_tensors(k1, k2, a, b, UNEVEN1, UNEVEN2, model="F", mutual=mutual, max_iters=2000, seeds=seeds)
+    assert cnt[3] > plain[4][3]                                         # the twins veto matches under the plain rule only
