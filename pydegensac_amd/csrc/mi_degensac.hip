@@ -220,7 +220,8 @@ extern "C" int mi_degensac_sample_stream_ex(uint32_t seed, int n, int sample_siz
 {
     DG_UNIT_ENTER(device);
     if (!g_dev[device].pool_par_ok) seq_pool = 1;
-    if ((sample_size != 4 && sample_size != 7) || n < sample_size + 1) { set_err("bad sample size"); return MI_DEGENSAC_EINVAL; }
+    /* n == sample_size is a valid input of the drivers (a homography on 4 rows): the last draw is rand() % 1 */
+    if ((sample_size != 4 && sample_size != 7) || n < sample_size || iters < 0 || !samples) { set_err("bad sample size"); return MI_DEGENSAC_EINVAL; }
     DevBuf<int> dpool, dout;
     if (dpool.alloc(n) || dout.alloc((size_t)iters * sample_size)) { set_err("device allocation failed"); return MI_DEGENSAC_ENOMEM; }
     hipLaunchKernelGGL(dg_sample_stream_kernel, dim3(1), dim3(64), 0, 0, seed, n, sample_size, iters, seq_pool, dpool.p, dout.p);

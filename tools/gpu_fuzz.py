@@ -50,7 +50,7 @@ def run(N, rng_seed, verbose=True):
             tn = {512: 1, 256: 2, 128: 3}[variant] | ((mode + 1) << 2)          # params.tuning: variant, placement (include/mi_degensac.h)
             if os.environ.get("FUZZ_TUNING"):                   # debugging: this kernel variant / placement instead of the drawn one
                 variant, mode = (int(x) for x in os.environ["FUZZ_TUNING"].split(",")); tn = {512: 1, 256: 2, 128: 3}[variant] | ((mode + 1) << 2)
-            seed = int(rng.integers(1, 2**31 - 1)); n = int(rng.choice([8, 20, 64, 150, 400, 1000, 2000, 3000]))
+            seed = int(rng.integers(1, 2**31 - 1)); n = int(rng.choice([8, 20, 64, 150, 255, 256, 257, 400, 1000, 1025, 2000, 3000]))
             mi = int(rng.choice([500, 3000, 20000]))
             if rng.random() < 0.6:
                 ir = float(rng.uniform(0.1, 0.8)); sg = float(rng.choice([0.05, 0.1, 0.5, 1.0])); pf = float(rng.choice([0.0, 0.0, 0.6, 0.9]))
