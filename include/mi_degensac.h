@@ -512,6 +512,38 @@ int mi_degensac_match_guided_batch(const mi_degensac_match_params *mp, const voi
                                    const mi_degensac_guide_params *gp, int device, int32_t *idx, float *dist, int32_t *match,
                                    int32_t *counts /*nullable*/);
 
+/* ---- guided matching over a pair list: image stores + (i, j) image indices + one model per list entry ------------------------
+ * The guided entry points above on the layout of the pair-list form (stores, offsets [n_images + 1], pairs_host [2 * n_pairs]; see "the
+ * pair-list form").  Entry p = (i, j) with model M_p = d_models[9 p ..] (driver form): the queries are the rows of image i of store 1,
+ * the candidates the rows of image j of store 2 that pass gate(q, t) under M_p; its answers are the output rows out[p] .. out[p+1] (list
+ * order from row 0, out[p+1] - out[p] = the rows of image i), indices local to image j.  The model and the zero-model rule belong to
+ * the list entry, not to an image: the same (i, j) twice with two models gives two results.  With mp->mutual the reverse guided search
+ * (image j's rows against image i's under the same gate(q, t)) runs per entry into a block of 16 bytes per back row (sum_p rows(image
+ * pairs[p][1]) rows), which the call allocates stream-ordered and frees.  No descriptor or keypoint row is gathered or copied on the
+ * device.  Every output is bit for bit what the batched entry point of the same name (guided_knn2_batch_dev / guided_batch_dev /
+ * guided_batch) returns when entry p's rows are copied out of the stores and the models are the same.  mp->second_nn is ignored, as
+ * there.
+ * Errors, before a device is looked for: MI_DEGENSAC_EINVAL for a bad norm / dim / kp_dim / guide params / ratio, then n_pairs < 0,
+ * then (n_pairs > 0) bad offsets, an image index outside its store, output or back rows beyond 0x3fffffff, NULL pointers.
+ * n_pairs == 0 with good params returns 0 and looks at nothing else. */
+/* the guided 2-NN alone: d_idx / d_dist [out[K], 2]; asynchronous on `stream`, no host synchronisation */
+int mi_degensac_match_guided_knn2_pairs_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host, int n_images1,
+                                            const int64_t *offsets2_host, int n_images2, const int32_t *pairs_host, int n_pairs, int dim,
+                                            const double *d_kp1, const double *d_kp2, int kp_dim, const double *d_models /* [K*9] */,
+                                            const mi_degensac_guide_params *gp, int device, void *stream, int32_t *d_idx, float *d_dist);
+/* the guided 2-NN + the decision: d_match [out[K]] = train row local to image j or -1, d_counts [K] (nullable) guided matches per entry
+ * on the device.  Asynchronous; it synchronises (once) only when h_counts [K] (host) is given. */
+int mi_degensac_match_guided_pairs_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
+                                       int n_images1, const int64_t *offsets2_host, int n_images2, const int32_t *pairs_host, int n_pairs,
+                                       const double *d_kp1, const double *d_kp2, int kp_dim, const double *d_models,
+                                       const mi_degensac_guide_params *gp, int device, void *stream, int32_t *d_idx, float *d_dist,
+                                       int32_t *d_match, int32_t *d_counts /*nullable*/, int32_t *h_counts /*nullable*/);
+/* the same on host pointers (blocking): each store is uploaded once (one upload when both sides name the same arrays) */
+int mi_degensac_match_guided_pairs(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
+                                   int n_images1, const int64_t *offsets2, int n_images2, const int32_t *pairs, int n_pairs, const double *kp1,
+                                   const double *kp2, int kp_dim, const double *models, const mi_degensac_guide_params *gp, int device,
+                                   int32_t *idx, float *dist, int32_t *match, int32_t *counts /*nullable*/);
+
 /* ---- unit-level device entry points (parity tests of the kernels' building blocks) ------------ */
 /* score n_models fundamental (kind 0: Sampson, 1: symmetric epipolar) or homography (kind 10..14:
  * H Sampson, symm_sq_max, symm_max, symm_sq_sum, symm_sum) models against all n points: I (<= th)

@@ -209,6 +209,18 @@ def lib():
         l.mi_degensac_match_guided_batch.restype = C.c_int
         l.mi_degensac_match_guided_batch.argtypes = [mpp, C.c_void_p, C.c_void_p, lp, lp, dp, dp, C.c_int, C.c_int, dp, gpp, C.c_int, ip,
                                                      C.POINTER(C.c_float), ip, ip]
+        if hasattr(l, "mi_degensac_match_guided_pairs_dev"):              # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            l.mi_degensac_match_guided_knn2_pairs_dev.restype = C.c_int
+            l.mi_degensac_match_guided_knn2_pairs_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, lp, C.c_int, lp, C.c_int, ip, C.c_int, C.c_int,
+                                                                  C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, gpp, C.c_int, C.c_void_p, C.c_void_p,
+                                                                  C.c_void_p]
+            l.mi_degensac_match_guided_pairs_dev.restype = C.c_int
+            l.mi_degensac_match_guided_pairs_dev.argtypes = [mpp, C.c_void_p, C.c_void_p, lp, C.c_int, lp, C.c_int, ip, C.c_int, C.c_void_p, C.c_void_p,
+                                                             C.c_int, C.c_void_p, gpp, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                             C.c_void_p, ip]
+            l.mi_degensac_match_guided_pairs.restype = C.c_int
+            l.mi_degensac_match_guided_pairs.argtypes = [mpp, C.c_void_p, C.c_void_p, lp, C.c_int, lp, C.c_int, ip, C.c_int, dp, dp, C.c_int, dp, gpp,
+                                                         C.c_int, ip, C.POINTER(C.c_float), ip, ip]
         l.mi_degensac_kpts_to_xyA.restype = C.c_int
         l.mi_degensac_kpts_to_xyA.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, dp]
         l.mi_degensac_kpts_to_xyA_dev.restype = C.c_int

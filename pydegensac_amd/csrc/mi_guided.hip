@@ -22,7 +22,12 @@
  * Whenever a list holds 64 rows, and once at the end, the 64 lanes each take one candidate, form its distance in the matcher's
  * order (the query row is wave-uniform) and push it into a lane-local top-2; a butterfly over the wave merges the 64 top-2s.
  * Memory is bounded (two fixed LDS blocks per workgroup) whatever the gate passes.  A gate that passes everything is correct,
- * and slower than the dense matcher (one distance per lane instead of a 4 x 4 register block over LDS tiles). */
+ * and slower than the dense matcher (one distance per lane instead of a 4 x 4 register block over LDS tiles).
+ *
+ * One path for two layouts, as in mi_matcher.hip: a "pair" is an entry of a list over image stores (mi_degensac_match_guided_*_pairs*,
+ * rows from mt_pairs_layout: descriptors and keypoints stored once per image, one model per ENTRY, answers pair after pair in list
+ * order) or of the ragged batch (mi_degensac_match_guided_*_batch*), which is the list whose entry p is (image p, image p) with its
+ * answers at its queries' own rows (mt_identity_rows).  No row is gathered or copied for either. */
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -99,28 +104,35 @@ __device__ __forceinline__ void mg_flush(const uint32_t *qrow, const uint32_t *d
     __builtin_amdgcn_wave_barrier();
 }
 
-/* grid = one workgroup per tile of MG_Q queries of one pair.  tab = [toff | oq | ot], each [K + 1] int32: pair p owns tiles
- * toff[p] .. toff[p+1] - 1, query rows oq[p] .. oq[p+1] - 1 and train rows ot[p] .. ot[p+1] - 1 (relative, global over the batch).
+/* grid = one workgroup per tile of MG_Q queries of one list entry.  toff [K + 1]: entry p owns tiles toff[p] .. toff[p+1] - 1; rows [K]: its
+ * record (mi_match_batch.h).  swap = 0: the queries are rows q .. q + nq of dq / kq (side 1), the candidates rows t .. t + nt of dt / kt
+ * (side 2), the answers go to the rows out .. out + nq of idx / dist; swap = 1 (the reverse search): dq / kq are side 2 and dt / kt side 1,
+ * the queries are rows t .. t + nt, the candidates rows q .. q + nq, the answers go to the rows back .. back + nt.  In a ragged batch the
+ * answers lie at the queries' own rows; in a pair list, where an image is stored once and queried by many entries, they do not.  The
+ * model is that of the entry, models[9 p ..].  The record is wave-uniform (it follows blockIdx), so it costs scalar loads only.
  * Every branch around a barrier or a ballot is uniform: the chunk loop over the workgroup, query slots and list counts over the wave. */
 template <int NORM, int GK>
 __global__ __launch_bounds__(256) void mg_guided_kernel(const uint32_t *dq, const uint32_t *dt, int words, const double *kq, const double *kt, int kd,
-                                                        const int32_t *tab, int n_pairs, const double *models, int hk, double th, double tb, int screen,
-                                                        int swap, int32_t *idx, float *dist)
+                                                        const int32_t *toff, const mt_pair_rows *rows, int n_pairs, const double *models, int hk,
+                                                        double th, double tb, int screen, int swap, int32_t *idx, float *dist)
 {
     __shared__ double2 ts[MG_TC];
     __shared__ int lists[MG_W][MG_QPW][MG_LIST];
-    const int32_t *toff = tab, *oq = tab + (n_pairs + 1), *ot = tab + 2 * (n_pairs + 1);
     const int b = (int)blockIdx.x;
-    int lo = 0, hi = n_pairs - 1;                                    /* the last pair p with toff[p] <= b (empty pairs own no tile) */
+    int lo = 0, hi = n_pairs - 1;                                    /* the last entry p with toff[p] <= b (an entry without queries owns no tile) */
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (toff[mid] <= b) lo = mid; else hi = mid - 1; }
-    const int pair = lo, q0 = oq[pair] + (b - toff[pair]) * MG_Q, q_end = oq[pair + 1], t_b = ot[pair];
+    const int pair = lo;
+    const mt_pair_rows r = rows[pair];
+    const int q_b = swap ? r.t : r.q, n_q = swap ? r.nt : r.nq, t_b = swap ? r.q : r.t, n_t = swap ? r.nq : r.nt;
+    const int q0 = q_b + (b - toff[pair]) * MG_Q, q_end = q_b + n_q;
+    const int o_d = (swap ? r.back : r.out) - q_b;                   /* query row q answers at row q + o_d */
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     double M[9], Hinv[9], H1[9];
     bool any = false;
 #pragma unroll
     for (int i = 0; i < 9; i++) { M[i] = models[(size_t)pair * 9 + i]; any = any || M[i] != 0.0; }
     if (GK == MG_H_SYM) dg_hsym_prepare(M, Hinv, H1);
-    const int t_e = any ? ot[pair + 1] : t_b;                        /* a zero model has no candidates */
+    const int t_e = any ? t_b + n_t : t_b;                           /* a zero model has no candidates */
     double qx[MG_QPW], qy[MG_QPW]; int cnt[MG_QPW]; mt_best best[MG_QPW];
 #pragma unroll
     for (int j = 0; j < MG_QPW; j++) {
@@ -169,8 +181,9 @@ __global__ __launch_bounds__(256) void mg_guided_kernel(const uint32_t *dq, cons
             if (i1 >= 0) mt_push(m, d1, i1);
         }
         if (lane == 0) {
-            idx[2 * (size_t)q] = m.i0; idx[2 * (size_t)q + 1] = m.i1;
-            dist[2 * (size_t)q] = NORM != 1 ? sqrtf(m.d0) : m.d0; dist[2 * (size_t)q + 1] = NORM != 1 ? sqrtf(m.d1) : m.d1;
+            const size_t o = (size_t)(q + o_d);
+            idx[2 * o] = m.i0; idx[2 * o + 1] = m.i1;
+            dist[2 * o] = NORM != 1 ? sqrtf(m.d0) : m.d0; dist[2 * o + 1] = NORM != 1 ? sqrtf(m.d1) : m.d1;
         }
     }
 }
@@ -232,24 +245,28 @@ int mt_guided_gate(int homography, int error_type, double px_th, mt_gate *g)
     return 0;
 }
 
-int mt_batch_guided_knn2(int norm, int words, const void *dq, const void *dt, const double *kq, const double *kt, int kd, const int64_t *oq,
-                         const int64_t *ot, int n_pairs, const double *d_models, const mt_gate &g, int swap, int device, hipStream_t s,
-                         int32_t *idx, float *dist)
+int mt_batch_guided_knn2(int norm, int words, const void *dq, const void *dt, const double *kq, const double *kt, int kd, const mt_pair_rows *rows,
+                         int n_pairs, int n_rows, const double *d_models, const mt_gate &g, int swap, int device, hipStream_t s, int32_t *idx,
+                         float *dist)
 {
-    if (n_pairs <= 0 || oq[n_pairs] == 0) return 0;
-    std::vector<int32_t> tab(3 * (size_t)(n_pairs + 1));
+    if (n_pairs <= 0 || n_rows == 0) return 0;
+    /* one upload: the tile starts [K + 1], then (16-byte aligned) the entries' records as they are */
+    const size_t a_rows = ((size_t)(n_pairs + 1) * 4 + 15) / 16 * 16, bytes = a_rows + (size_t)n_pairs * sizeof(mt_pair_rows);
+    std::vector<char> tab(bytes);
+    int32_t *toff = (int32_t *)tab.data();
     int64_t tiles = 0;
     for (int p = 0; p <= n_pairs; p++) {
-        tab[p] = (int32_t)tiles; tab[n_pairs + 1 + p] = (int32_t)oq[p]; tab[2 * (n_pairs + 1) + p] = (int32_t)ot[p];
-        if (p < n_pairs) tiles += (oq[p + 1] - oq[p] + MG_Q - 1) / MG_Q;
+        toff[p] = (int32_t)tiles;
+        if (p < n_pairs) tiles += ((swap ? rows[p].nt : rows[p].nq) + MG_Q - 1) / MG_Q;
     }
-    int32_t *d_tab = nullptr;
-    MGCHK(hipMallocAsync((void **)&d_tab, tab.size() * 4, s));
-    int rc = mt_batch_upload(device, s, tab.data(), tab.size() * 4, d_tab);
+    memcpy(tab.data() + a_rows, rows, (size_t)n_pairs * sizeof(mt_pair_rows));
+    char *d_tab = nullptr;
+    MGCHK(hipMallocAsync((void **)&d_tab, bytes, s));
+    int rc = mt_batch_upload(device, s, tab.data(), bytes, d_tab);
     if (rc) { (void)hipFreeAsync(d_tab, s); return rc; }
     const dim3 grid((unsigned)tiles), block(256);
 #define MG_LAUNCH(N, G) hipLaunchKernelGGL((mg_guided_kernel<N, G>), grid, block, 0, s, (const uint32_t *)dq, (const uint32_t *)dt, words, kq, kt, kd, \
-        d_tab, n_pairs, d_models, g.hk, g.th, g.tb, g.screen, swap, idx, dist)
+        (const int32_t *)d_tab, (const mt_pair_rows *)(d_tab + a_rows), n_pairs, d_models, g.hk, g.th, g.tb, g.screen, swap, idx, dist)
     switch (4 * mt_norm_index(norm) + g.gk) {
     case 0: MG_LAUNCH(0, MG_F_SAMPSON); break;
     case 1: MG_LAUNCH(0, MG_F_SYM); break;
@@ -281,7 +298,8 @@ int mt_batch_guided_decide(const int32_t *d_idx, const float *d_dist, const int3
 }
 
 /* ---- C-ABI ----------------------------------------------------------------------------------------------------------- */
-static int mg_check(int norm, int dim, int kp_dim, const mi_degensac_guide_params *gp, const int64_t *o1, const int64_t *o2, int n_pairs, mt_gate *g)
+/* norm, dim, keypoint width and the gate: what both layouts refuse before they look at offsets or a list */
+static int mg_check_gate(int norm, int dim, int kp_dim, const mi_degensac_guide_params *gp, mt_gate *g)
 {
     if (!mt_norm_known(norm) || dim <= 0) return mg_einval("bad norm or descriptor dim");
     if (const char *e = mt_norm_dim_error(norm, dim)) return mg_einval(e);
@@ -289,7 +307,20 @@ static int mg_check(int norm, int dim, int kp_dim, const mi_degensac_guide_param
     if (!gp) return mg_einval("guide params are NULL");
     if (gp->struct_size != 0 && gp->struct_size < (int32_t)sizeof(mi_degensac_guide_params)) return mg_einval("guide params: struct_size too small");
     if (gp->homography != 0 && gp->homography != 1) return mg_einval("homography must be 0 or 1");
-    int rc = mt_guided_gate(gp->homography, gp->error_type, gp->px_th, g); if (rc) return rc;
+    return mt_guided_gate(gp->homography, gp->error_type, gp->px_th, g);
+}
+
+static int mg_check_ratio(const mi_degensac_match_params *mp)
+{
+    if (!mp) return mg_einval("match params are NULL");
+    if (!(isfinite(mp->ratio) && mp->ratio > 0.f)) return mg_einval("ratio must be finite and > 0");
+    return 0;
+}
+
+/* the ragged batch */
+static int mg_check(int norm, int dim, int kp_dim, const mi_degensac_guide_params *gp, const int64_t *o1, const int64_t *o2, int n_pairs, mt_gate *g)
+{
+    int rc = mg_check_gate(norm, dim, kp_dim, gp, g); if (rc) return rc;
     if (n_pairs < 0) return mg_einval("n_pairs < 0");
     if (n_pairs == 0) return 0;
     for (const int64_t *o : {o1, o2}) {
@@ -298,6 +329,18 @@ static int mg_check(int norm, int dim, int kp_dim, const mi_degensac_guide_param
         if (o[n_pairs] - o[0] > 0x3fffffff) return mg_einval("too many descriptor rows in one batch");
     }
     return 0;
+}
+
+/* the pair list: the gate, then the list (mt_pairs_layout: n_pairs < 0, offsets, image indices, the row limits) */
+static int mg_check_pairs(int norm, int dim, int kp_dim, const mi_degensac_guide_params *gp, const int64_t *off1, int m1, const int64_t *off2, int m2,
+                          const int32_t *pairs, int n_pairs, mt_gate *g, std::vector<mt_pair_rows> &rows, int64_t *n_out, int64_t *n_back)
+{
+    *n_out = *n_back = 0;
+    int rc = mg_check_gate(norm, dim, kp_dim, gp, g); if (rc) return rc;
+    if (n_pairs < 0) return mg_einval("n_pairs < 0");
+    if (n_pairs == 0) return 0;
+    rows.resize(n_pairs);
+    return mt_pairs_layout(off1, m1, off2, m2, pairs, n_pairs, rows.data(), n_out, n_back);
 }
 
 static int mg_words(int norm, int dim) { return mt_row_words(norm, dim); }
@@ -313,52 +356,65 @@ extern "C" int mi_degensac_match_guided_knn2_batch_dev(int norm, const void *d_d
     if (!d_models || (n1 > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist)) || (n2 > 0 && (!d_desc2 || !d_kp2))) return mg_einval("NULL argument");
     MgDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     const int words = mg_words(norm, dim);
-    std::vector<int64_t> o1(n_pairs + 1), o2(n_pairs + 1);
-    for (int p = 0; p <= n_pairs; p++) { o1[p] = offsets1_host[p] - offsets1_host[0]; o2[p] = offsets2_host[p] - offsets2_host[0]; }
+    std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
+    mt_ragged_rows(offsets1_host, offsets2_host, n_pairs, o1, o2, rows);
     return mt_batch_guided_knn2(norm, words, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words,
                                 (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words, d_kp1 + (size_t)offsets1_host[0] * kp_dim,
-                                d_kp2 + (size_t)offsets2_host[0] * kp_dim, kp_dim, o1.data(), o2.data(), n_pairs, d_models, g, 0, device,
+                                d_kp2 + (size_t)offsets2_host[0] * kp_dim, kp_dim, rows.data(), n_pairs, (int)n1, d_models, g, 0, device,
                                 (hipStream_t)stream, d_idx + 2 * offsets1_host[0], d_dist + 2 * offsets1_host[0]);
+}
+
+/* The device path of both layouts, arguments checked and the device current: entry p's rows are rows[p], n_out output rows and n_back
+ * rows of the reverse search in all; every pointer is already at its side's first row, idx / dist / match at the first output row. */
+static int mg_rows_dev(const mi_degensac_match_params *mp, const uint32_t *q1, const uint32_t *q2, const double *kp1, const double *kp2, int kd,
+                       const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t n_back, const double *d_models, const mt_gate &g, int device,
+                       hipStream_t s, int32_t *idx, float *dist, int32_t *match, int32_t *d_counts, int32_t *h_counts)
+{
+    const int K = (int)rows.size();
+    const int words = mg_words(mp->norm, mp->dim);
+    const bool mutual = mp->mutual != 0;
+    /* the decision's tables: out [K + 1] (where the entry's idx / dist / match rows are) | back [K] (where its reverse-search rows start) */
+    std::vector<int32_t> o32(2 * (size_t)(K + 1));
+    for (int p = 0; p < K; p++) { o32[p] = rows[p].out; o32[K + 1 + p] = rows[p].back; }
+    o32[K] = (int32_t)n_out; o32[2 * K + 1] = (int32_t)n_back;
+    /* one stream-ordered block: tables | reverse idx | reverse dist | counts (when the caller gives none on the device) */
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t a_bidx = up(o32.size() * 4), a_bdist = a_bidx + (mutual ? up((size_t)n_back * 8) : 0),
+                 a_cnt = a_bdist + (mutual ? up((size_t)n_back * 8) : 0), a_all = a_cnt + up((size_t)K * 4);
+    char *blk = nullptr;
+    MGCHK(hipMallocAsync((void **)&blk, a_all, s));
+    struct Free { char *p; hipStream_t s; ~Free() { (void)hipFreeAsync(p, s); } } fr{blk, s};
+    const int32_t *d_out = (const int32_t *)blk, *d_back = d_out + (K + 1);
+    int32_t *bidx = mutual ? (int32_t *)(blk + a_bidx) : nullptr, *cnt = d_counts ? d_counts : (int32_t *)(blk + a_cnt);
+    float *bdist = (float *)(blk + a_bdist);
+    int rc = mt_batch_upload(device, s, o32.data(), o32.size() * 4, blk); if (rc) return rc;
+    rc = mt_batch_guided_knn2(mp->norm, words, q1, q2, kp1, kp2, kd, rows.data(), K, (int)n_out, d_models, g, 0, device, s, idx, dist); if (rc) return rc;
+    if (mutual) { rc = mt_batch_guided_knn2(mp->norm, words, q2, q1, kp2, kp1, kd, rows.data(), K, (int)n_back, d_models, g, 1, device, s, bidx, bdist);
+        if (rc) return rc; }
+    rc = mt_batch_guided_decide(idx, dist, d_out, d_back, K, mp->ratio, bidx, s, match, cnt); if (rc) return rc;
+    if (h_counts) {                                                  /* the only synchronisation, and only when asked for */
+        MGCHK(hipMemcpyAsync(h_counts, cnt, (size_t)K * 4, hipMemcpyDeviceToHost, s));
+        MGCHK(hipStreamSynchronize(s));
+    }
+    return 0;
 }
 
 static int mg_batch_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const int64_t *off1, const int64_t *off2,
                         const double *d_kp1, const double *d_kp2, int kd, int K, const double *d_models, const mi_degensac_guide_params *gp, int device,
                         hipStream_t s, int32_t *d_idx, float *d_dist, int32_t *d_match, int32_t *d_counts, int32_t *h_counts)
 {
-    if (!mp) return mg_einval("match params are NULL");
-    if (!(isfinite(mp->ratio) && mp->ratio > 0.f)) return mg_einval("ratio must be finite and > 0");
-    mt_gate g; int rc = mg_check(mp->norm, mp->dim, kd, gp, off1, off2, K, &g); if (rc) return rc;
+    int rc = mg_check_ratio(mp); if (rc) return rc;
+    mt_gate g; rc = mg_check(mp->norm, mp->dim, kd, gp, off1, off2, K, &g); if (rc) return rc;
     if (K == 0) return 0;
     const int64_t n1 = off1[K] - off1[0], n2 = off2[K] - off2[0];
     if (!d_models || (n1 > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist || !d_match)) || (n2 > 0 && (!d_desc2 || !d_kp2))) return mg_einval("NULL argument");
     MgDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     const int words = mg_words(mp->norm, mp->dim);
-    const bool mutual = mp->mutual != 0;
-    std::vector<int64_t> o1(K + 1), o2(K + 1); std::vector<int32_t> o32(2 * (size_t)(K + 1));
-    for (int p = 0; p <= K; p++) { o1[p] = off1[p] - off1[0]; o2[p] = off2[p] - off2[0]; o32[p] = (int32_t)o1[p]; o32[K + 1 + p] = (int32_t)o2[p]; }
-    const uint32_t *q1 = (const uint32_t *)d_desc1 + (size_t)off1[0] * words, *q2 = (const uint32_t *)d_desc2 + (size_t)off2[0] * words;
-    const double *kp1 = d_kp1 + (size_t)off1[0] * kd, *kp2 = d_kp2 + (size_t)off2[0] * kd;
-    int32_t *idx = d_idx + 2 * off1[0], *match = d_match + off1[0]; float *dist = d_dist + 2 * off1[0];
-    /* one stream-ordered block: offsets | reverse idx | reverse dist | counts (when the caller gives none on the device) */
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t a_bidx = up(o32.size() * 4), a_bdist = a_bidx + (mutual ? up((size_t)n2 * 8) : 0), a_cnt = a_bdist + (mutual ? up((size_t)n2 * 8) : 0),
-                 a_all = a_cnt + up((size_t)K * 4);
-    char *blk = nullptr;
-    MGCHK(hipMallocAsync((void **)&blk, a_all, s));
-    struct Free { char *p; hipStream_t s; ~Free() { (void)hipFreeAsync(p, s); } } fr{blk, s};
-    const int32_t *d_o1 = (const int32_t *)blk, *d_o2 = d_o1 + (K + 1);
-    int32_t *bidx = mutual ? (int32_t *)(blk + a_bidx) : nullptr, *cnt = d_counts ? d_counts : (int32_t *)(blk + a_cnt);
-    float *bdist = (float *)(blk + a_bdist);
-    rc = mt_batch_upload(device, s, o32.data(), o32.size() * 4, blk); if (rc) return rc;
-    rc = mt_batch_guided_knn2(mp->norm, words, q1, q2, kp1, kp2, kd, o1.data(), o2.data(), K, d_models, g, 0, device, s, idx, dist); if (rc) return rc;
-    if (mutual) { rc = mt_batch_guided_knn2(mp->norm, words, q2, q1, kp2, kp1, kd, o2.data(), o1.data(), K, d_models, g, 1, device, s, bidx, bdist);
-        if (rc) return rc; }
-    rc = mt_batch_guided_decide(idx, dist, d_o1, d_o2, K, mp->ratio, bidx, s, match, cnt); if (rc) return rc;
-    if (h_counts) {                                                  /* the only synchronisation, and only when asked for */
-        MGCHK(hipMemcpyAsync(h_counts, cnt, (size_t)K * 4, hipMemcpyDeviceToHost, s));
-        MGCHK(hipStreamSynchronize(s));
-    }
-    return 0;
+    std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
+    mt_ragged_rows(off1, off2, K, o1, o2, rows);
+    return mg_rows_dev(mp, (const uint32_t *)d_desc1 + (size_t)off1[0] * words, (const uint32_t *)d_desc2 + (size_t)off2[0] * words,
+                       d_kp1 + (size_t)off1[0] * kd, d_kp2 + (size_t)off2[0] * kd, kd, rows, n1, n2, d_models, g, device, s, d_idx + 2 * off1[0],
+                       d_dist + 2 * off1[0], d_match + off1[0], d_counts, h_counts);
 }
 
 extern "C" int mi_degensac_match_guided_batch_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
@@ -370,41 +426,112 @@ extern "C" int mi_degensac_match_guided_batch_dev(const mi_degensac_match_params
                         d_idx, d_dist, d_match, d_counts, h_counts);
 }
 
-/* host pointers: stage, run the device path on the null stream, copy back */
+/* The host-pointer forms, arguments checked: side 1 (rows off1[0] .. off1[m1] of desc1 / kp1) goes to the device, side 2 too unless `same`
+ * says both sides name the same arrays, then the models; the device path runs on the null stream and idx / dist / match (at the first
+ * output row) come back. */
+static int mg_rows_host(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *off1, int m1, const int64_t *off2,
+                        int m2, const double *kp1, const double *kp2, int kd, bool same, const std::vector<mt_pair_rows> &rows, int64_t n_out,
+                        int64_t n_back, const double *models, const mt_gate &g, int device, int32_t *idx, float *dist, int32_t *match, int32_t *counts)
+{
+    const int K = (int)rows.size();
+    MgDevGuard dg; int rc = dg.enter(device); if (rc) return rc;
+    const int64_t n1 = off1[m1] - off1[0], n2 = off2[m2] - off2[0];
+    const size_t row = mt_row_bytes(mp->norm, mp->dim);
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t a_d2 = up(n1 * row), a_k1 = a_d2 + (same ? 0 : up(n2 * row)), a_k2 = a_k1 + up((size_t)n1 * kd * 8),
+                 a_mo = a_k2 + (same ? 0 : up((size_t)n2 * kd * 8)), a_ix = a_mo + up((size_t)K * 72), a_ds = a_ix + up((size_t)n_out * 8),
+                 a_ma = a_ds + up((size_t)n_out * 8), a_all = a_ma + up((size_t)n_out * 4);
+    char *D = nullptr;
+    struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
+    MGCHK(hipMalloc((void **)&D, a_all));
+    MGCHK(hipMemcpy(D, (const char *)desc1 + off1[0] * row, n1 * row, hipMemcpyHostToDevice));
+    MGCHK(hipMemcpy(D + a_k1, kp1 + off1[0] * kd, (size_t)n1 * kd * 8, hipMemcpyHostToDevice));
+    if (!same) {
+        MGCHK(hipMemcpy(D + a_d2, (const char *)desc2 + off2[0] * row, n2 * row, hipMemcpyHostToDevice));
+        MGCHK(hipMemcpy(D + a_k2, kp2 + off2[0] * kd, (size_t)n2 * kd * 8, hipMemcpyHostToDevice));
+    }
+    MGCHK(hipMemcpy(D + a_mo, models, (size_t)K * 72, hipMemcpyHostToDevice));
+    std::vector<int32_t> cnt(K);
+    rc = mg_rows_dev(mp, (const uint32_t *)D, (const uint32_t *)(same ? D : D + a_d2), (const double *)(D + a_k1), (const double *)(D + (same ? a_k1 : a_k2)),
+                     kd, rows, n_out, n_back, (const double *)(D + a_mo), g, device, nullptr, (int32_t *)(D + a_ix), (float *)(D + a_ds),
+                     (int32_t *)(D + a_ma), nullptr, cnt.data());
+    if (rc) return rc;
+    MGCHK(hipStreamSynchronize(nullptr));
+    MGCHK(hipMemcpy(idx, D + a_ix, (size_t)n_out * 8, hipMemcpyDeviceToHost));
+    MGCHK(hipMemcpy(dist, D + a_ds, (size_t)n_out * 8, hipMemcpyDeviceToHost));
+    MGCHK(hipMemcpy(match, D + a_ma, (size_t)n_out * 4, hipMemcpyDeviceToHost));
+    if (counts) memcpy(counts, cnt.data(), (size_t)K * 4);
+    return 0;
+}
+
+/* host pointers: stage, run the device path on the null stream, copy back.  The ragged batch never asks whether its two sides are the
+ * same arrays: both are uploaded */
 extern "C" int mi_degensac_match_guided_batch(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
                                               const int64_t *offsets2, const double *kp1, const double *kp2, int kp_dim, int n_pairs, const double *models,
                                               const mi_degensac_guide_params *gp, int device, int32_t *idx, float *dist, int32_t *match, int32_t *counts)
 {
-    if (!mp) return mg_einval("match params are NULL");
-    if (!(isfinite(mp->ratio) && mp->ratio > 0.f)) return mg_einval("ratio must be finite and > 0");
-    mt_gate g; int rc = mg_check(mp->norm, mp->dim, kp_dim, gp, offsets1, offsets2, n_pairs, &g); if (rc) return rc;
+    int rc = mg_check_ratio(mp); if (rc) return rc;
+    mt_gate g; rc = mg_check(mp->norm, mp->dim, kp_dim, gp, offsets1, offsets2, n_pairs, &g); if (rc) return rc;
     const int K = n_pairs;
     if (K == 0) return 0;
     if (!desc1 || !desc2 || !kp1 || !kp2 || !models || !idx || !dist || !match) return mg_einval("NULL argument");
+    std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
+    mt_ragged_rows(offsets1, offsets2, K, o1, o2, rows);
+    return mg_rows_host(mp, desc1, desc2, offsets1, K, offsets2, K, kp1, kp2, kp_dim, false, rows, o1[K], o2[K], models, g, device,
+                        idx + 2 * offsets1[0], dist + 2 * offsets1[0], match + offsets1[0], counts);
+}
+
+/* ---- guided matching over a pair list (include/mi_degensac.h mi_degensac_match_guided_*_pairs*) -------------------------------
+ * The same path with descriptors and keypoints stored once per image: mt_pairs_layout fills the rows from the stores' offsets and the
+ * (i, j) list, where the ragged batch takes the identity list over its own offsets; everything after the layout step is shared. */
+extern "C" int mi_degensac_match_guided_knn2_pairs_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host, int n_images1,
+                                                       const int64_t *offsets2_host, int n_images2, const int32_t *pairs_host, int n_pairs, int dim,
+                                                       const double *d_kp1, const double *d_kp2, int kp_dim, const double *d_models,
+                                                       const mi_degensac_guide_params *gp, int device, void *stream, int32_t *d_idx, float *d_dist)
+{
+    mt_gate g; std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
+    int rc = mg_check_pairs(norm, dim, kp_dim, gp, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, &g, rows, &n_out, &n_back);
+    if (rc || n_pairs == 0) return rc;
+    if (!d_models || (n_out > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist)) || (n_back > 0 && (!d_desc2 || !d_kp2))) return mg_einval("NULL argument");
     MgDevGuard dg; rc = dg.enter(device); if (rc) return rc;
-    const int64_t n1 = offsets1[K] - offsets1[0], n2 = offsets2[K] - offsets2[0];
-    const size_t row = mt_row_bytes(mp->norm, mp->dim);
-    std::vector<int64_t> o1(K + 1), o2(K + 1);
-    for (int p = 0; p <= K; p++) { o1[p] = offsets1[p] - offsets1[0]; o2[p] = offsets2[p] - offsets2[0]; }
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t a_d2 = up(n1 * row), a_k1 = a_d2 + up(n2 * row), a_k2 = a_k1 + up((size_t)n1 * kp_dim * 8), a_mo = a_k2 + up((size_t)n2 * kp_dim * 8),
-                 a_ix = a_mo + up((size_t)K * 72), a_ds = a_ix + up((size_t)n1 * 8), a_ma = a_ds + up((size_t)n1 * 8), a_all = a_ma + up((size_t)n1 * 4);
-    char *D = nullptr;
-    struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
-    MGCHK(hipMalloc((void **)&D, a_all));
-    MGCHK(hipMemcpy(D, (const char *)desc1 + offsets1[0] * row, n1 * row, hipMemcpyHostToDevice));
-    MGCHK(hipMemcpy(D + a_d2, (const char *)desc2 + offsets2[0] * row, n2 * row, hipMemcpyHostToDevice));
-    MGCHK(hipMemcpy(D + a_k1, kp1 + offsets1[0] * kp_dim, (size_t)n1 * kp_dim * 8, hipMemcpyHostToDevice));
-    MGCHK(hipMemcpy(D + a_k2, kp2 + offsets2[0] * kp_dim, (size_t)n2 * kp_dim * 8, hipMemcpyHostToDevice));
-    MGCHK(hipMemcpy(D + a_mo, models, (size_t)K * 72, hipMemcpyHostToDevice));
-    std::vector<int32_t> cnt(K);
-    rc = mg_batch_dev(mp, D, D + a_d2, o1.data(), o2.data(), (const double *)(D + a_k1), (const double *)(D + a_k2), kp_dim, K, (const double *)(D + a_mo),
-                      gp, device, nullptr, (int32_t *)(D + a_ix), (float *)(D + a_ds), (int32_t *)(D + a_ma), nullptr, cnt.data());
-    if (rc) return rc;
-    MGCHK(hipStreamSynchronize(nullptr));
-    MGCHK(hipMemcpy(idx + 2 * offsets1[0], D + a_ix, (size_t)n1 * 8, hipMemcpyDeviceToHost));
-    MGCHK(hipMemcpy(dist + 2 * offsets1[0], D + a_ds, (size_t)n1 * 8, hipMemcpyDeviceToHost));
-    MGCHK(hipMemcpy(match + offsets1[0], D + a_ma, (size_t)n1 * 4, hipMemcpyDeviceToHost));
-    if (counts) memcpy(counts, cnt.data(), (size_t)K * 4);
-    return 0;
+    const int words = mg_words(norm, dim);
+    return mt_batch_guided_knn2(norm, words, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words,
+                                (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words, d_kp1 + (size_t)offsets1_host[0] * kp_dim,
+                                d_kp2 + (size_t)offsets2_host[0] * kp_dim, kp_dim, rows.data(), n_pairs, (int)n_out, d_models, g, 0, device,
+                                (hipStream_t)stream, d_idx, d_dist);
+}
+
+extern "C" int mi_degensac_match_guided_pairs_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
+                                                  const int64_t *offsets1_host, int n_images1, const int64_t *offsets2_host, int n_images2,
+                                                  const int32_t *pairs_host, int n_pairs, const double *d_kp1, const double *d_kp2, int kp_dim,
+                                                  const double *d_models, const mi_degensac_guide_params *gp, int device, void *stream, int32_t *d_idx,
+                                                  float *d_dist, int32_t *d_match, int32_t *d_counts, int32_t *h_counts)
+{
+    int rc = mg_check_ratio(mp); if (rc) return rc;
+    mt_gate g; std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
+    rc = mg_check_pairs(mp->norm, mp->dim, kp_dim, gp, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, &g, rows, &n_out, &n_back);
+    if (rc || n_pairs == 0) return rc;
+    if (!d_models || (n_out > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist || !d_match)) || (n_back > 0 && (!d_desc2 || !d_kp2)))
+        return mg_einval("NULL argument");
+    MgDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+    const int words = mg_words(mp->norm, mp->dim);
+    return mg_rows_dev(mp, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words, (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words,
+                       d_kp1 + (size_t)offsets1_host[0] * kp_dim, d_kp2 + (size_t)offsets2_host[0] * kp_dim, kp_dim, rows, n_out, n_back, d_models, g,
+                       device, (hipStream_t)stream, d_idx, d_dist, d_match, d_counts, h_counts);
+}
+
+/* each store goes to the device once: one copy when both sides name the same arrays */
+extern "C" int mi_degensac_match_guided_pairs(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
+                                              int n_images1, const int64_t *offsets2, int n_images2, const int32_t *pairs, int n_pairs, const double *kp1,
+                                              const double *kp2, int kp_dim, const double *models, const mi_degensac_guide_params *gp, int device,
+                                              int32_t *idx, float *dist, int32_t *match, int32_t *counts)
+{
+    int rc = mg_check_ratio(mp); if (rc) return rc;
+    mt_gate g; std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
+    rc = mg_check_pairs(mp->norm, mp->dim, kp_dim, gp, offsets1, n_images1, offsets2, n_images2, pairs, n_pairs, &g, rows, &n_out, &n_back);
+    if (rc || n_pairs == 0) return rc;
+    if (!desc1 || !desc2 || !kp1 || !kp2 || !models || !idx || !dist || !match) return mg_einval("NULL argument");
+    const bool same = desc1 == desc2 && kp1 == kp2 && n_images1 == n_images2 && !memcmp(offsets1, offsets2, ((size_t)n_images1 + 1) * 8);
+    return mg_rows_host(mp, desc1, desc2, offsets1, n_images1, offsets2, n_images2, kp1, kp2, kp_dim, same, rows, n_out, n_back, models, g, device,
+                        idx, dist, match, counts);
 }

@@ -123,14 +123,18 @@ MT_HIDDEN int mt_batch_scatter(int n_pairs, const int32_t *d_e_of_p, const int64
  * px_th that is negative or NaN */
 struct mt_gate { int gk, hk; double th, tb; int screen; };
 MT_HIDDEN int mt_guided_gate(int homography, int error_type, double px_th, mt_gate *g);
-/* guided 2-NN: every row of pair p in q against the rows of t that pass the gate of model d_models[9 p ..]; offsets oq / ot [K + 1], indices
- * local to the pair as in mt_batch_knn2.  kq / kt: keypoint rows [rows, kd] of the two sides.  swap = 0: q is side 1 (queries), gate(q, t);
- * swap = 1: q is side 2 (the reverse search of the mutual check), gate(t, q). */
-MT_HIDDEN int mt_batch_guided_knn2(int norm, int words, const void *dq, const void *dt, const double *kq, const double *kt, int kd, const int64_t *oq,
-                                   const int64_t *ot, int n_pairs, const double *d_models, const mt_gate &g, int swap, int device, hipStream_t s,
-                                   int32_t *idx, float *dist);
+/* guided 2-NN over the same rows as mt_batch_knn2 (dq / dt, kq / kt [rows, kd] at the first row of their side): every query row of
+ * entry p against the candidate rows that pass the gate of ITS model d_models[9 p ..] (the model belongs to the list entry, not to an
+ * image).  swap = 0: dq / kq are side 1, rows q .. q + nq against t .. t + nt of dt / kt, gate(query, candidate), into the output rows from
+ * `out`; swap = 1 (the reverse search of the mutual check): dq / kq are side 2, rows t .. t + nt against q .. q + nq of dt / kt,
+ * gate(candidate, query), into the rows from `back`.  idx / dist [n_rows, 2] with n_rows the total of the side written, indices local to
+ * the entry's candidate image.  No row is gathered or copied. */
+MT_HIDDEN int mt_batch_guided_knn2(int norm, int words, const void *dq, const void *dt, const double *kq, const double *kt, int kd,
+                                   const mt_pair_rows *rows, int n_pairs, int n_rows, const double *d_models, const mt_gate &g, int swap, int device,
+                                   hipStream_t s, int32_t *idx, float *dist);
 /* the decision: match[i] = idx[i][0] when it exists and dist[i][0] < ratio * dist[i][1] (and back[b2 + idx[i][0]][0] == i - lo when
- * d_back is set), else -1; count[p] (nullable) = guided matches of pair p.  d_off1 / d_off2: [K + 1] relative int32 row offsets */
+ * d_back is set), else -1; count[p] (nullable) = guided matches of pair p.  d_off1 [K + 1]: the output-row offsets (the `out` column and
+ * the total), d_off2[p] (the only entry read): where the pair's rows of d_back start (the `back` column), as for mt_batch_filter_rank */
 MT_HIDDEN int mt_batch_guided_decide(const int32_t *d_idx, const float *d_dist, const int32_t *d_off1, const int32_t *d_off2, int n_pairs, float ratio,
                                      const int32_t *d_back, hipStream_t s, int32_t *d_match, int32_t *d_count);
 #endif /* MI_MATCH_BATCH_H */

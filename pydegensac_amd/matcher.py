@@ -226,13 +226,15 @@ def check_match_verify_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2
 
 def check_match_pairs_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype, counts1, counts2, pairs,
                            seeds=None, guided=False, fginn_th=None):
-    """The argument checks of the pair-list calls (knn_match_pairs_tensors, match_and_verify_pairs[_tensors]), on shapes and dtype names
-    (numpy or torch) and on the list itself.  counts1 [M1] / counts2 [M2] are the rows per image of the two stores, pairs an integer
-    array [K, 2] with K >= 1 of (image of store 1, image of store 2); seeds None or one per list entry.  guided and fginn_th are not
-    part of the pair-list calls and are refused.  Returns (norm code, "xy" / "kpts", offsets1 [M1 + 1], offsets2 [M2 + 1], pairs as
+    """The argument checks of the pair-list calls (knn_match_pairs_tensors, match_and_verify_pairs[_tensors], guided_match_pairs[_tensors]),
+    on shapes and dtype names (numpy or torch) and on the list itself.  counts1 [M1] / counts2 [M2] are the rows per image of the two
+    stores, pairs an integer array [K, 2] with K >= 1 of (image of store 1, image of store 2); seeds None or one per list entry.  guided
+    and fginn_th are refused: the calls that have them as arguments do not run those stages (guided matching over a list is a call of
+    its own, guided_match_pairs[_tensors]).  Returns (norm code, "xy" / "kpts", offsets1 [M1 + 1], offsets2 [M2 + 1], pairs as
     contiguous int32 [K, 2], pair_offsets int64 [K + 1], seeds as uint32 [K] or None); raises ValueError."""
     if guided:
-        raise ValueError("guided matching is not part of the pair-list calls: run guided_match_batch on the models they return")
+        raise ValueError("guided matching is not part of this pair-list call: pass the models it returns to guided_match_pairs / "
+                         "guided_match_pairs_tensors")
     if fginn_th is not None:
         raise ValueError("fginn_th (the FGINN ratio test) is not part of the pair-list calls: use match_and_verify_batch")
     code, kind = _check_sides(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype)
@@ -454,16 +456,9 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
     return res + ([gm[o1[p]:o1[p + 1]] for p in range(K)],) if guided else res
 
 
-def match_and_verify_pairs(kps_list, desc_list, pairs, model="F", ratio=0.9, mutual=False, px_th=None, conf=None, max_iters=None,
-                           laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True, enable_degeneracy_check=True, seeds=None,
-                           norm=None, device=0, guided=False, fginn_th=None, kps2_list=None, desc2_list=None):
-    """match_and_verify_batch over a pair list: descriptors and keypoints are given ONCE per image (kps_list[i], desc_list[i]) and
-    pairs [K, 2] says which (i, j) to run, queries = image i, train set = image j (exhaustive_pairs(n) for a whole collection).  With
-    kps2_list / desc2_list the train images come from that second store (queries against a database), else from the same one.  The
-    list may hold self pairs, repeats, both orders and any order; images may be empty or unused.  Each store is uploaded once, whatever
-    the number of pairs.  Per pair the results are bit for bit those of match_and_verify_batch on the pair's copied arrays with the
-    same seeds (one per list entry, default parallel.pair_seeds(0, K)).  Returns (models [K, 3, 3], [match_p], [inlier_p]) as
-    match_and_verify_batch; guided and fginn_th are not part of this call (ValueError).  last_stats() holds the per-pair statistics."""
+def _stack_stores(kps_list, desc_list, kps2_list, desc2_list):
+    """the per-image lists of the pair-list calls -> ((A, K1, counts1), (B, K2, counts2), one): the concatenated descriptor and keypoint
+    rows of each store with its rows per image; one = no second store was given (both sides are then the same tuple)"""
     if (kps2_list is None) != (desc2_list is None):
         raise ValueError("kps2_list and desc2_list go together")
     one = desc2_list is None
@@ -481,14 +476,12 @@ def match_and_verify_pairs(kps_list, desc_list, pairs, model="F", ratio=0.9, mut
         if [x.shape[0] for x in k] != c:
             raise ValueError("one keypoint row per descriptor row")
         stores.append((np.concatenate(d), np.concatenate(k), np.asarray(c, np.int64)))
-    (A, K1, c1), (B, K2, c2) = stores[0], stores[-1]
-    code, kind, o1, o2, pr, po, sd = check_match_pairs_args(model, ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape,
-                                                            K2.dtype, c1, c2, pairs, seeds, guided, fginn_th)
-    prm = estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
-    K = len(pr)
-    if sd is None:
-        sd = _seeds_u32(None, K)
+    return stores[0], stores[-1], one
 
+
+def _finish_stores(code, kind, A, K1, B, K2, one, device):
+    """the stores as the library takes them: uint8 rows padded to whole words, keypoints as float64 rows; one store = the same arrays
+    on both sides, which the host-pointer entry points upload once"""
     def prep(D, Kp):
         if code != NORM_L2:
             D = _pad_words(D, D)[0]
@@ -496,7 +489,29 @@ def match_and_verify_pairs(kps_list, desc_list, pairs, model="F", ratio=0.9, mut
             Kp = kpts_to_xyA(Kp, device)
         return np.ascontiguousarray(D), np.ascontiguousarray(Kp, np.float64)
     A, K1 = prep(A, K1)
-    B, K2 = (A, K1) if one else prep(B, K2)              # one store: the same arrays on both sides, uploaded once
+    B, K2 = (A, K1) if one else prep(B, K2)
+    return A, K1, B, K2
+
+
+def match_and_verify_pairs(kps_list, desc_list, pairs, model="F", ratio=0.9, mutual=False, px_th=None, conf=None, max_iters=None,
+                           laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True, enable_degeneracy_check=True, seeds=None,
+                           norm=None, device=0, guided=False, fginn_th=None, kps2_list=None, desc2_list=None):
+    """match_and_verify_batch over a pair list: descriptors and keypoints are given ONCE per image (kps_list[i], desc_list[i]) and
+    pairs [K, 2] says which (i, j) to run, queries = image i, train set = image j (exhaustive_pairs(n) for a whole collection).  With
+    kps2_list / desc2_list the train images come from that second store (queries against a database), else from the same one.  The
+    list may hold self pairs, repeats, both orders and any order; images may be empty or unused.  Each store is uploaded once, whatever
+    the number of pairs.  Per pair the results are bit for bit those of match_and_verify_batch on the pair's copied arrays with the
+    same seeds (one per list entry, default parallel.pair_seeds(0, K)).  Returns (models [K, 3, 3], [match_p], [inlier_p]) as
+    match_and_verify_batch; guided and fginn_th are not part of this call (ValueError): guided_match_pairs takes the models it returns.
+    last_stats() holds the per-pair statistics."""
+    (A, K1, c1), (B, K2, c2), one = _stack_stores(kps_list, desc_list, kps2_list, desc2_list)
+    code, kind, o1, o2, pr, po, sd = check_match_pairs_args(model, ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape,
+                                                            K2.dtype, c1, c2, pairs, seeds, guided, fginn_th)
+    prm = estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
+    K = len(pr)
+    if sd is None:
+        sd = _seeds_u32(None, K)
+    A, K1, B, K2 = _finish_stores(code, kind, A, K1, B, K2, one, device)              # one store: uploaded once
     mp = _lib.MatchParams(code, A.shape[1], ratio, mutual)
     n = int(po[-1])
     M = np.zeros((K, 9)); match = np.full(n, -1, np.int32); inl = np.zeros(n, np.uint8)
@@ -513,3 +528,37 @@ def match_and_verify_pairs(kps_list, desc_list, pairs, model="F", ratio=0.9, mut
     if model == "H":
         M = _h_user_form(M)
     return M, [match[po[p]:po[p + 1]] for p in range(K)], [inl[po[p]:po[p + 1]].astype(bool) for p in range(K)]
+
+
+def guided_match_pairs(kps_list, desc_list, pairs, models, model="F", ratio=0.9, mutual=False, px_th=None, error_type="sampson", norm=None,
+                       driver_form=False, device=0, kps2_list=None, desc2_list=None):
+    """guided_match_batch over a pair list: descriptors and keypoints are given ONCE per image, pairs [K, 2] says which (i, j) to run and
+    models [K, 3, 3] float64 holds one model per LIST ENTRY (the same (i, j) may appear twice with two models) — what
+    match_and_verify_pairs returned for the same list goes in as it is: F, or the user-facing H (driver_form=True: H_c = inv(H)^T).  Stores
+    as for match_and_verify_pairs: kps2_list / desc2_list name a second store for the train images, each store is uploaded once and no
+    row is copied per pair.  Per entry the result is bit for bit that of guided_match_batch on the entry's copied arrays.  Returns per
+    list entry (query indices, train indices, distances) in query order; train indices are local to image j."""
+    (A, K1, c1), (B, K2, c2), one = _stack_stores(kps_list, desc_list, kps2_list, desc2_list)
+    code, kind, o1, o2, pr, po, _ = check_match_pairs_args(model, ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape,
+                                                           K2.dtype, c1, c2, pairs)
+    K = len(pr)
+    M = np.asarray(models)
+    px, et = check_guided_args(model, px_th, error_type, M.shape, M.dtype, K)
+    A, K1, B, K2 = _finish_stores(code, kind, A, K1, B, K2, one, device)
+    Md = np.ascontiguousarray(M if (model == "F" or driver_form) else _h_driver_form(M), np.float64).reshape(K, 9)
+    n = int(po[-1])
+    idx = np.full((n, 2), -1, np.int32); dist = np.full((n, 2), np.inf, np.float32); match = np.full(n, -1, np.int32)
+    cnt = np.zeros(K, np.int32)
+    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual); gp = _lib.GuideParams(model == "H", et, px)
+    lp = C.POINTER(C.c_int64); ip = C.POINTER(C.c_int32)
+    rc = _lib.lib().mi_degensac_match_guided_pairs(C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), o1.ctypes.data_as(lp),
+                                                   len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, pr.ctypes.data_as(ip), K, _lib.dptr(K1),
+                                                   _lib.dptr(K2), K1.shape[1], _lib.dptr(Md), C.byref(gp), int(device), idx.ctypes.data_as(ip),
+                                                   dist.ctypes.data_as(C.POINTER(C.c_float)), match.ctypes.data_as(ip), cnt.ctypes.data_as(ip))
+    _lib.check_match(rc)
+    out = []
+    for p in range(K):
+        m = match[po[p]:po[p + 1]]
+        q = np.flatnonzero(m >= 0)
+        out.append((q.astype(np.int64), m[q].astype(np.int64), dist[po[p]:po[p + 1]][q, 0]))
+    return out

@@ -273,6 +273,16 @@ def _guided_dev(code, a, b, k1, k2, o1, o2, Md, model, ratio, mutual, px, et):
     return match, idx, dist
 
 
+def _h_driver_form(M):
+    """the user-facing H [K, 3, 3] -> the driver's H_c = inv(H)^T where the model is not zero, without a host round trip (inv_ex: no error
+    check, no sync); zero models stay zero"""
+    import torch
+    K = M.shape[0]
+    found = (M.abs().sum(dim=(1, 2)) != 0).view(K, 1, 1)
+    eye = torch.eye(3, dtype=M.dtype, device=M.device).expand(K, 3, 3)
+    return torch.where(found, torch.linalg.inv_ex(torch.where(found, M, eye)).inverse.transpose(1, 2), torch.zeros_like(M))
+
+
 def guided_match_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, models, model="F", ratio=0.9, mutual=False, px_th=None,
                                error_type="sampson", norm=None, driver_form=False):
     """Guided matching on the device (include/mi_degensac.h mi_degensac_match_guided_batch_dev): per pair the 2-NN search of
@@ -302,10 +312,7 @@ def guided_match_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model
         k1 = kps1.contiguous(); k2 = kps2.contiguous()
     M = models.contiguous()
     if model == "H" and not driver_form:
-        # H_c = inv(H)^T where the model is not zero, without a host round trip (inv_ex: no error check, no sync)
-        found = (M.abs().sum(dim=(1, 2)) != 0).view(K, 1, 1)
-        eye = torch.eye(3, dtype=M.dtype, device=M.device).expand(K, 3, 3)
-        M = torch.where(found, torch.linalg.inv_ex(torch.where(found, M, eye)).inverse.transpose(1, 2), torch.zeros_like(M))
+        M = _h_driver_form(M)
     return _guided_dev(code, a, b, k1, k2, o1, o2, M.reshape(K, 9).contiguous(), model, ratio, mutual, px, et)
 
 
@@ -432,7 +439,8 @@ def match_and_verify_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, p
     with the same seeds; the call synchronises exactly once (the read of the tentative counts).
     Returns (model [K, 3, 3], match [N] int32 = train row local to image j or -1, inlier [N] bool, stats [K, 16], n_tentatives [K]
     numpy int64, pair_offsets [K + 1] host int64) with N = pair_offsets[K]: the per-query outputs lie pair after pair in list order.
-    guided=True and fginn_th are not part of this call (ValueError): both stages keep their batched entry points."""
+    guided=True and fginn_th are not part of this call (ValueError): guided matching over the list is guided_match_pairs_tensors, which
+    takes the models returned here as they are; FGINN keeps its batched entry points."""
     import torch
     from . import matcher
     ts = (kps1, kps2, desc1, desc2)
@@ -455,3 +463,51 @@ def match_and_verify_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, p
               pr.ctypes.data_as(C.POINTER(C.c_int32)), K)
     return _match_verify_dev(_lib.lib().mi_degensac_match_verify_pairs_dev, layout, model, _lib.MatchParams(code, a.shape[1], ratio, mutual), prm, a, b,
                              k1, k2, sd, K, n)[:5] + (po,)
+
+
+def guided_match_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs, models, model="F", ratio=0.9, mutual=False, px_th=None,
+                               error_type="sampson", norm=None, driver_form=False):
+    """guided_match_batch_tensors over a pair list (include/mi_degensac.h mi_degensac_match_guided_pairs_dev): kps / desc are image stores
+    (counts1 / counts2 rows per image; pass the same tensors on both sides for a collection matched against itself), pairs [K, 2] lists
+    the (i, j) to run and models [K, 3, 3] float64 on the device holds one model per LIST ENTRY — what match_and_verify_pairs_tensors
+    returned for the same list goes in as it is: F, or the user-facing H (converted here on the device; driver_form=True takes
+    H_c = inv(H)^T).  The same (i, j) may appear twice with two models.  Descriptors and keypoints stay where they are: no row is copied
+    per pair, float32 [N, 4] keypoints go through kpts_to_xyA_tensors once per store, and with mutual the reverse search takes 16 bytes
+    per train row of the list.  Gate, decision and the zero-model rule as in guided_match_batch_tensors; per entry every output is bit for
+    bit what that call returns on the entry's copied rows.  Returns (match [N] int32 = train row local to image j or -1, idx [N, 2]
+    int32, dist [N, 2] float32, pair_offsets [K + 1] host int64) with N = pair_offsets[K]: entry p owns the rows pair_offsets[p] ..
+    pair_offsets[p + 1].  Asynchronous on the current stream (no host synchronisation)."""
+    import torch
+    from . import matcher
+    ts = (kps1, kps2, desc1, desc2, models)
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        raise ValueError("kps1, kps2, desc1, desc2 and models must be torch tensors on a ROCm device")
+    code, kind, o1, o2, pr, po, _ = matcher.check_match_pairs_args(model, ratio, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape),
+                                                                   desc2.dtype, tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype,
+                                                                   counts1, counts2, pairs)
+    K = len(pr); n = int(po[-1])
+    px, et = matcher.check_guided_args(model, px_th, error_type, tuple(models.shape), models.dtype, K)
+    if any(t.device != desc1.device for t in ts) or desc1.device.type != "cuda":
+        raise ValueError("kps1, kps2, desc1, desc2 and models must live on the same ROCm device")
+    a, b = _desc_pair(desc1, desc2)
+    conv = kpts_to_xyA_tensors if kind == "kpts" else (lambda k: k.contiguous())
+    k1 = conv(kps1); k2 = k1 if kps2 is kps1 else conv(kps2)          # once per store, not per pair
+    M = models.contiguous()
+    if model == "H" and not driver_form:
+        M = _h_driver_form(M)
+    M = M.reshape(K, 9).contiguous()
+    dev = a.device
+    idx = torch.full((n, 2), -1, dtype=torch.int32, device=dev)
+    dist = torch.full((n, 2), float("inf"), dtype=torch.float32, device=dev)
+    match = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    mp = _lib.MatchParams(code, a.shape[1], ratio, mutual); gp = _lib.GuideParams(model == "H", et, px)
+    stream = torch.cuda.current_stream(dev)
+    lp = C.POINTER(C.c_int64)
+    rc = _lib.lib().mi_degensac_match_guided_pairs_dev(C.byref(mp), a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(lp), len(o1) - 1,
+                                                       o2.ctypes.data_as(lp), len(o2) - 1, pr.ctypes.data_as(C.POINTER(C.c_int32)), K, k1.data_ptr(),
+                                                       k2.data_ptr(), int(k1.shape[1]), M.data_ptr(), C.byref(gp), dev.index or 0,
+                                                       C.c_void_p(stream.cuda_stream), idx.data_ptr(), dist.data_ptr(), match.data_ptr(), None, None)
+    _lib.check_match(rc)
+    for t in (a, b, k1, k2, M):
+        t.record_stream(stream)
+    return match, idx, dist, po
