@@ -454,8 +454,9 @@ int mi_degensac_match_knn2_pairs_dev(int norm, const void *d_desc1, const void *
                                      int device, void *stream, int32_t *d_idx, float *d_dist);
 /* mi_degensac_match_verify_batch_dev on a pair list: d_kp1 / d_kp2 are the stores' keypoint rows, d_seeds [K] one seed per list
  * entry, d_model [K*9], d_stats [K*16] or NULL, d_match / d_inlier [out[K]] in output-row order, h_counts [K] (host, nullable).  One
- * synchronisation, as there: the read of the K tentative counts.  The FGINN rule is not part of the pair-list form: a match_params
- * that asks for it (second_nn = 1 with struct_size covering it) is MI_DEGENSAC_EINVAL. */
+ * synchronisation, as there: the read of the K tentative counts.  The FGINN rule is not part of this call: a match_params
+ * that asks for it (second_nn = 1 with struct_size covering it) is MI_DEGENSAC_EINVAL; mi_degensac_match_verify_fginn_pairs[_dev]
+ * below runs it. */
 int mi_degensac_match_verify_pairs_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
                                        const int64_t *offsets1_host, int n_images1, const int64_t *offsets2_host, int n_images2,
                                        const double *d_kp1, const double *d_kp2, int kp_dim, const int32_t *pairs_host, int n_pairs,
@@ -469,6 +470,34 @@ int mi_degensac_match_verify_pairs(int homography, const mi_degensac_match_param
                                    const double *kp2, int kp_dim, const int32_t *pairs, int n_pairs, const mi_degensac_params *prm,
                                    const uint32_t *seeds, int device, double *model, int32_t *match, uint8_t *inlier,
                                    int32_t *stats /*nullable*/, int32_t *counts /*nullable*/);
+
+/* FGINN over a pair list.  The plain pair-list calls above keep refusing it; these are the calls that run it.
+ * mi_degensac_match_fginn_knn2_pairs_dev = mi_degensac_match_knn2_pairs_dev followed by the FGINN rule of
+ * mi_degensac_match_fginn_knn2_batch_dev for slot 1: d_kp2 is the keypoint store of side 2, one [kp_dim] float64 row per row of
+ * desc2 (kp_dim 2 or 6, only x, y are read; indexed like desc2, so a non-zero first offset skips keypoint rows too).  Entry p's
+ * anchors and competitors are the keypoints of image pairs[p][1]; d_idx / d_dist [out[K], 2] in list order, train indices local to
+ * image j; bit for bit mi_degensac_match_fginn_knn2_batch_dev on the entries' copied rows.  A needy query is rescanned through its
+ * image's rows in the store: no descriptor or keypoint row is copied.  Asynchronous on `stream`, no host synchronisation.  Errors,
+ * before a device is looked for: those of mi_degensac_match_knn2_pairs_dev, and MI_DEGENSAC_EINVAL for kp_dim not 2 / 6 or a
+ * spatial_th that is negative or not finite; n_pairs == 0 returns 0. */
+int mi_degensac_match_fginn_knn2_pairs_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host, int n_images1,
+                                           const int64_t *offsets2_host, int n_images2, const int32_t *pairs_host, int n_pairs, int dim,
+                                           const double *d_kp2, int kp_dim, double spatial_th, int device, void *stream, int32_t *d_idx,
+                                           float *d_dist);
+/* mi_degensac_match_verify_pairs_dev / _pairs that honour mp->second_nn / mp->spatial_th (FGINN at that radius on the keypoints of
+ * store 2) instead of refusing them; everything else, the one synchronisation included, is that call.  With second_nn = 0, or a
+ * struct_size that does not cover spatial_th, they ARE the plain pair-list calls.  Per entry bit for bit
+ * mi_degensac_match_verify_batch[_dev] with the same match_params on the entry's copied rows and the same seeds. */
+int mi_degensac_match_verify_fginn_pairs_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
+                                             const int64_t *offsets1_host, int n_images1, const int64_t *offsets2_host, int n_images2,
+                                             const double *d_kp1, const double *d_kp2, int kp_dim, const int32_t *pairs_host, int n_pairs,
+                                             const mi_degensac_params *prm, const uint32_t *d_seeds, int device, void *stream, double *d_model,
+                                             int32_t *d_match, uint8_t *d_inlier, int32_t *d_stats, int32_t *h_counts /*nullable*/);
+int mi_degensac_match_verify_fginn_pairs(int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2,
+                                         const int64_t *offsets1, int n_images1, const int64_t *offsets2, int n_images2, const double *kp1,
+                                         const double *kp2, int kp_dim, const int32_t *pairs, int n_pairs, const mi_degensac_params *prm,
+                                         const uint32_t *seeds, int device, double *model, int32_t *match, uint8_t *inlier,
+                                         int32_t *stats /*nullable*/, int32_t *counts /*nullable*/);
 
 /* ---- guided matching: the batched 2-NN restricted to each pair's model inlier band (mi_guided.hip) ------------------------
  * Same ragged batch as mi_degensac_match_knn2_batch_dev (host offsets of K + 1 values, pair-local indices), plus keypoints

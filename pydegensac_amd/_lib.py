@@ -71,6 +71,9 @@ class GuideParams(C.Structure):
     def __init__(self, homography=0, error_type=0, px_th=0.5):
         super().__init__(int(bool(homography)), int(error_type), float(px_th), C.sizeof(GuideParams), 0)
 
+    def __repr__(self):                 # the fields, not the object's address: stable in logs and in parametrised test ids
+        return f"GuideParams(homography={self.homography}, error_type={self.error_type}, px_th={self.px_th!r}, struct_size={self.struct_size})"
+
 
 class MiDegensacError(RuntimeError):
     pass
@@ -199,6 +202,14 @@ def lib():
             l.mi_degensac_match_verify_pairs.restype = C.c_int
             l.mi_degensac_match_verify_pairs.argtypes = [C.c_int, mpp, C.c_void_p, C.c_void_p, lp, C.c_int, lp, C.c_int, dp, dp, C.c_int, ip, C.c_int,
                                                          pp, up, C.c_int, dp, ip, bp, ip, ip]
+        if hasattr(l, "mi_degensac_match_fginn_knn2_pairs_dev"):          # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            l.mi_degensac_match_fginn_knn2_pairs_dev.restype = C.c_int
+            l.mi_degensac_match_fginn_knn2_pairs_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, lp, C.c_int, lp, C.c_int, ip, C.c_int, C.c_int,
+                                                                 C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.mi_degensac_match_verify_fginn_pairs_dev.restype = C.c_int
+            l.mi_degensac_match_verify_fginn_pairs_dev.argtypes = l.mi_degensac_match_verify_pairs_dev.argtypes
+            l.mi_degensac_match_verify_fginn_pairs.restype = C.c_int
+            l.mi_degensac_match_verify_fginn_pairs.argtypes = l.mi_degensac_match_verify_pairs.argtypes
         gpp = C.POINTER(GuideParams)
         l.mi_degensac_match_guided_knn2_batch_dev.restype = C.c_int
         l.mi_degensac_match_guided_knn2_batch_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, lp, lp, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,

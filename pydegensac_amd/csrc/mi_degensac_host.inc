@@ -1142,13 +1142,15 @@ static int mv_estimate(int homography, int K, int kd, const mi_degensac_params *
     return match_rc(mt_batch_scatter(K, d_eop, d_eoff, R.out, keep, rank, idx, model_e, stats_e, mask_e, s, d_model, d_stats, match, inlier));
 }
 
-/* the pair list's refusals and its rows (see the pair-list section below) */
+/* the pair list's refusals and its rows (see the pair-list section below); with_fginn: the *_fginn_pairs* entry points, which honour
+ * second_nn / spatial_th where the plain ones refuse them */
 static int mvp_check(int homography, const mi_degensac_match_params *mp, int kd, const int64_t *off1, int m1, const int64_t *off2, int m2,
-                     const int32_t *pairs, int K, std::vector<mt_pair_rows> &rows, int64_t *n_out, int64_t *n_back)
+                     const int32_t *pairs, int K, bool with_fginn, std::vector<mt_pair_rows> &rows, int64_t *n_out, int64_t *n_back)
 {
     int rc = mv_check_params(homography, mp, kd, K); if (rc) return rc;
     int fginn; double r; (void)mt_second_nn(mp, &fginn, &r);
-    if (fginn) { set_err("the FGINN rule (second_nn = 1) is not part of the pair-list entry points: use mi_degensac_match_verify_batch*"); return MI_DEGENSAC_EINVAL; }
+    if (fginn && !with_fginn) { set_err("the FGINN rule (second_nn = 1) is not part of the pair-list entry points: use mi_degensac_match_verify_batch*"
+                                        " or, over a pair list, mi_degensac_match_verify_fginn_pairs*"); return MI_DEGENSAC_EINVAL; }
     *n_out = *n_back = 0;
     if (K == 0) return 0;
     rows.resize(K);
@@ -1172,11 +1174,10 @@ static int mv_check_null(const void *d_desc1, const void *d_desc2, const double 
 
 /* The device path of both forms, arguments checked: pair p's rows are rows[p], n_out output rows and n_back rows of the reverse search
  * in all; side 1 / 2 (descriptors and keypoints) start at row r1 / r2 of the arrays passed; match / inlier are at the first output row.
- * fg_o1 / fg_o2: the relative offsets of a ragged batch, which the FGINN step takes (a pair list has refused FGINN before it gets here). */
+ * The FGINN step (mp->second_nn) takes the same rows as the 2-NN in front of it. */
 static int match_verify_rows(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const double *d_kp1,
                              const double *d_kp2, int64_t r1, int64_t r2, int kd, const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t n_back,
-                             const int64_t *fg_o1, const int64_t *fg_o2, const mi_degensac_params *prm, const uint32_t *d_seeds, int device,
-                             hipStream_t s, double *d_model, int32_t *match, uint8_t *inlier, int32_t *d_stats, int32_t *h_counts)
+                             const mi_degensac_params *prm, const uint32_t *d_seeds, int device, hipStream_t s, double *d_model, int32_t *match, uint8_t *inlier, int32_t *d_stats, int32_t *h_counts)
 {
     const int K = (int)rows.size();
     DevGuard g; int rc = g.enter(device); if (rc) return rc;
@@ -1205,7 +1206,7 @@ static int match_verify_rows(int homography, const mi_degensac_match_params *mp,
     rc = match_rc(mt_batch_upload(device, s, tab.data(), tab.size() * 4, A)); if (rc) return rc;
     rc = match_rc(mt_batch_knn2(mp->norm, words, q1, q2, rows.data(), K, (int)n_out, 0, device, s, idx, dist)); if (rc) return rc;
     int fginn; double fginn_r; (void)mt_second_nn(mp, &fginn, &fginn_r);
-    if (fginn) { rc = match_rc(mt_batch_fginn(mp->norm, words, q1, q2, kp2, kd, fg_o1, fg_o2, K, fginn_r, device, s, idx, dist)); if (rc) return rc; }
+    if (fginn) { rc = match_rc(mt_batch_fginn(mp->norm, words, q1, q2, kp2, kd, rows.data(), K, (int)n_out, fginn_r, device, s, idx, dist)); if (rc) return rc; }
     if (mutual) { rc = match_rc(mt_batch_knn2(mp->norm, words, q2, q1, rows.data(), K, (int)n_back, 1, device, s, bidx, bdist)); if (rc) return rc; }
     rc = match_rc(mt_batch_filter_rank(idx, dist, R.out, R.back, K, mp->ratio, bidx, s, keep, rank, cnt)); if (rc) return rc;
     return mv_estimate(homography, K, kd, prm, R, cnt, keep, rank, idx, kp1, kp2, d_seeds, device, s, blk, d_model, d_stats, match, inlier, h_counts);
@@ -1223,8 +1224,7 @@ extern "C" int mi_degensac_match_verify_batch_dev(int homography, const mi_degen
     const int64_t n1 = o1[n_pairs], n2 = o2[n_pairs];
     if ((rc = mv_check_prm(prm, homography, kp_dim)) || (rc = mv_check_device(device)) ||
         (rc = mv_check_null(d_desc1, d_desc2, d_kp1, d_kp2, n1, n2, d_seeds, d_model, d_match, d_inlier))) return rc;
-    return match_verify_rows(homography, mp, d_desc1, d_desc2, d_kp1, d_kp2, offsets1_host[0], offsets2_host[0], kp_dim, rows, n1, n2, o1.data(),
-                             o2.data(), prm, d_seeds, device, (hipStream_t)stream, d_model, d_match + offsets1_host[0], d_inlier + offsets1_host[0],
+    return match_verify_rows(homography, mp, d_desc1, d_desc2, d_kp1, d_kp2, offsets1_host[0], offsets2_host[0], kp_dim, rows, n1, n2, prm, d_seeds, device, (hipStream_t)stream, d_model, d_match + offsets1_host[0], d_inlier + offsets1_host[0],
                              d_stats, h_counts);
 }
 
@@ -1267,8 +1267,7 @@ static int mv_rerun(mi_degensac_ctx *c, int homography, int kd, int K, const mi_
  * exactly their gathered tentatives. */
 static int match_verify_host(int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *off1, int m1,
                              const int64_t *off2, int m2, const double *kp1, const double *kp2, int kd, bool same, const std::vector<mt_pair_rows> &rows,
-                             int64_t n_out, int64_t n_back, const int64_t *fg_o1, const int64_t *fg_o2, const mi_degensac_params *prm,
-                             const uint32_t *seeds, int device, double *model, int32_t *match, uint8_t *inlier, int32_t *stats, int32_t *counts)
+                             int64_t n_out, int64_t n_back, const mi_degensac_params *prm, const uint32_t *seeds, int device, double *model, int32_t *match, uint8_t *inlier, int32_t *stats, int32_t *counts)
 {
     const int K = (int)rows.size();
     mi_degensac_ctx *c; int rc = thread_ctx(device, &c); if (rc) return rc;
@@ -1294,7 +1293,7 @@ static int match_verify_host(int homography, const mi_degensac_match_params *mp,
     std::vector<int32_t> cnt(K), st((size_t)K * 16);
     if ((rc = mv_check_prm(prm, homography, kd))) return rc;
     rc = match_verify_rows(homography, mp, D, same ? D : D + a_d2, (const double *)(D + a_k1), (const double *)(D + (same ? a_k1 : a_k2)), 0, 0, kd, rows,
-                           n_out, n_back, fg_o1, fg_o2, prm, (const uint32_t *)(D + a_sd), device, c->stream, (double *)(D + a_mo), (int32_t *)(D + a_ma),
+                           n_out, n_back, prm, (const uint32_t *)(D + a_sd), device, c->stream, (double *)(D + a_mo), (int32_t *)(D + a_ma),
                            (uint8_t *)(D + a_in), (int32_t *)(D + a_st), cnt.data());
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1322,38 +1321,58 @@ extern "C" int mi_degensac_match_verify_batch(int homography, const mi_degensac_
     if (!desc1 || !desc2 || !kp1 || !kp2 || !seeds || !model || !match || !inlier) { set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
     std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
     mt_ragged_rows(offsets1, offsets2, K, o1, o2, rows);
-    return match_verify_host(homography, mp, desc1, desc2, offsets1, K, offsets2, K, kp1, kp2, kd, false, rows, o1[K], o2[K], o1.data(), o2.data(),
-                             prm, seeds, device, model, match + offsets1[0], inlier + offsets1[0], stats, counts);
+    return match_verify_host(homography, mp, desc1, desc2, offsets1, K, offsets2, K, kp1, kp2, kd, false, rows, o1[K], o2[K], prm, seeds, device, model, match + offsets1[0], inlier + offsets1[0], stats, counts);
 }
 
 /* ---- match-and-verify over a pair list (include/mi_degensac.h mi_degensac_match_verify_pairs[_dev]) --------------------------
  * The same path with descriptors and keypoints stored once per image: mt_pairs_layout fills the rows from the stores' offsets and the
  * (i, j) list, where the ragged batch takes the identity list over its own offsets; everything after the layout step is shared. */
-extern "C" int mi_degensac_match_verify_pairs_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
+static int match_verify_pairs_dev(bool with_fginn, int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
         const int64_t *offsets1_host, int n_images1, const int64_t *offsets2_host, int n_images2, const double *d_kp1, const double *d_kp2, int kp_dim,
         const int32_t *pairs_host, int n_pairs, const mi_degensac_params *prm, const uint32_t *d_seeds, int device, void *stream, double *d_model,
         int32_t *d_match, uint8_t *d_inlier, int32_t *d_stats, int32_t *h_counts)
 {
     std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
-    int rc = mvp_check(homography, mp, kp_dim, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, rows, &n_out, &n_back);
+    int rc = mvp_check(homography, mp, kp_dim, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, with_fginn, rows, &n_out, &n_back);
     if (rc || n_pairs == 0) return rc;
     if ((rc = mv_check_prm(prm, homography, kp_dim)) ||
         (rc = mv_check_null(d_desc1, d_desc2, d_kp1, d_kp2, n_out, n_back, d_seeds, d_model, d_match, d_inlier)) || (rc = mv_check_device(device))) return rc;
-    return match_verify_rows(homography, mp, d_desc1, d_desc2, d_kp1, d_kp2, offsets1_host[0], offsets2_host[0], kp_dim, rows, n_out, n_back, nullptr,
-                             nullptr, prm, d_seeds, device, (hipStream_t)stream, d_model, d_match, d_inlier, d_stats, h_counts);
+    return match_verify_rows(homography, mp, d_desc1, d_desc2, d_kp1, d_kp2, offsets1_host[0], offsets2_host[0], kp_dim, rows, n_out, n_back, prm, d_seeds,
+                             device, (hipStream_t)stream, d_model, d_match, d_inlier, d_stats, h_counts);
 }
 
 /* each store goes to the device once: one copy when both sides name the same arrays */
-extern "C" int mi_degensac_match_verify_pairs(int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2,
+static int match_verify_pairs(bool with_fginn, int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2,
         const int64_t *offsets1, int n_images1, const int64_t *offsets2, int n_images2, const double *kp1, const double *kp2, int kd,
         const int32_t *pairs, int K, const mi_degensac_params *prm, const uint32_t *seeds, int device, double *model, int32_t *match,
         uint8_t *inlier, int32_t *stats, int32_t *counts)
 {
     std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
-    int rc = mvp_check(homography, mp, kd, offsets1, n_images1, offsets2, n_images2, pairs, K, rows, &n_out, &n_back);
+    int rc = mvp_check(homography, mp, kd, offsets1, n_images1, offsets2, n_images2, pairs, K, with_fginn, rows, &n_out, &n_back);
     if (rc || K == 0) return rc;
     if (!desc1 || !desc2 || !kp1 || !kp2 || !seeds || !model || !match || !inlier) { set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
     const bool same = desc1 == desc2 && kp1 == kp2 && n_images1 == n_images2 && !memcmp(offsets1, offsets2, ((size_t)n_images1 + 1) * 8);
-    return match_verify_host(homography, mp, desc1, desc2, offsets1, n_images1, offsets2, n_images2, kp1, kp2, kd, same, rows, n_out, n_back, nullptr,
-                             nullptr, prm, seeds, device, model, match, inlier, stats, counts);
+    return match_verify_host(homography, mp, desc1, desc2, offsets1, n_images1, offsets2, n_images2, kp1, kp2, kd, same, rows, n_out, n_back, prm, seeds,
+                             device, model, match, inlier, stats, counts);
 }
+
+#define MVP_DEV_ARGS int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host, \
+        int n_images1, const int64_t *offsets2_host, int n_images2, const double *d_kp1, const double *d_kp2, int kp_dim, const int32_t *pairs_host, \
+        int n_pairs, const mi_degensac_params *prm, const uint32_t *d_seeds, int device, void *stream, double *d_model, int32_t *d_match, \
+        uint8_t *d_inlier, int32_t *d_stats, int32_t *h_counts
+#define MVP_DEV_PASS homography, mp, d_desc1, d_desc2, offsets1_host, n_images1, offsets2_host, n_images2, d_kp1, d_kp2, kp_dim, pairs_host, n_pairs, prm, \
+        d_seeds, device, stream, d_model, d_match, d_inlier, d_stats, h_counts
+#define MVP_HOST_ARGS int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1, int n_images1, \
+        const int64_t *offsets2, int n_images2, const double *kp1, const double *kp2, int kd, const int32_t *pairs, int K, \
+        const mi_degensac_params *prm, const uint32_t *seeds, int device, double *model, int32_t *match, uint8_t *inlier, int32_t *stats, int32_t *counts
+#define MVP_HOST_PASS homography, mp, desc1, desc2, offsets1, n_images1, offsets2, n_images2, kp1, kp2, kd, pairs, K, prm, seeds, device, model, match, \
+        inlier, stats, counts
+extern "C" int mi_degensac_match_verify_pairs_dev(MVP_DEV_ARGS) { return match_verify_pairs_dev(false, MVP_DEV_PASS); }
+extern "C" int mi_degensac_match_verify_pairs(MVP_HOST_ARGS) { return match_verify_pairs(false, MVP_HOST_PASS); }
+/* the FGINN forms: the same calls without the refusal of second_nn = 1 (second_nn = 0 or the layout before spatial_th: the plain calls) */
+extern "C" int mi_degensac_match_verify_fginn_pairs_dev(MVP_DEV_ARGS) { return match_verify_pairs_dev(true, MVP_DEV_PASS); }
+extern "C" int mi_degensac_match_verify_fginn_pairs(MVP_HOST_ARGS) { return match_verify_pairs(true, MVP_HOST_PASS); }
+#undef MVP_DEV_ARGS
+#undef MVP_DEV_PASS
+#undef MVP_HOST_ARGS
+#undef MVP_HOST_PASS

@@ -94,11 +94,11 @@ MT_HIDDEN int mt_pairs_layout(const int64_t *off1, int m1, const int64_t *off2, 
  * words per descriptor row. */
 MT_HIDDEN int mt_batch_knn2(int norm, int words, const void *dq, const void *dt, const mt_pair_rows *rows, int n_pairs, int n_rows, int swap, int device,
                             hipStream_t s, int32_t *idx, float *dist);
-/* FGINN (mi_fginn.h), ragged batches only (oq / ot: relative offsets [K + 1]): after mt_batch_knn2 over their identity rows on s, slot 1
- * of idx / dist becomes the nearest train row whose keypoint (kt: [rows, kd] of the train side) lies at least r from the keypoint of
- * slot 0; no host synchronisation */
-MT_HIDDEN int mt_batch_fginn(int norm, int words, const void *dq, const void *dt, const double *kt, int kd, const int64_t *oq, const int64_t *ot,
-                             int n_pairs, double r, int device, hipStream_t s, int32_t *idx, float *dist);
+/* FGINN (mi_fginn.h): after mt_batch_knn2 (swap = 0) over the same rows on s, slot 1 of idx / dist [n_rows, 2] becomes the nearest
+ * train row whose keypoint (kt: [rows, kd] of side 2, at its first row) lies at least r from the keypoint of slot 0; no host
+ * synchronisation */
+MT_HIDDEN int mt_batch_fginn(int norm, int words, const void *dq, const void *dt, const double *kt, int kd, const mt_pair_rows *rows, int n_pairs,
+                             int n_rows, double r, int device, hipStream_t s, int32_t *idx, float *dist);
 /* ratio test (+ mutual check when d_back is set) and the rank of every kept query among its pair's kept queries; one
  * workgroup per pair.  d_off1 / d_off2: [K + 1] relative int32 row offsets on the device.  d_off1 says where the pair's idx / dist /
  * keep / rank rows are (the `out` column and the total), d_off2[p] (the only entry read) where its rows of d_back start (the `back`

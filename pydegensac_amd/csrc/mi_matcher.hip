@@ -38,25 +38,29 @@
 /* acc + the dot product of the four unsigned bytes of a and b */
 __device__ __forceinline__ unsigned mt_udot4(uint32_t a, uint32_t b, unsigned acc) { return __builtin_amdgcn_udot4(a, b, acc, false); }
 
-/* What the FGINN rescan (mi_fginn.h) adds to the tile body below.  mf_ctx: the pair's needy list (global query rows at the list
- * positions q0 .. q_end - 1), the plain 2-NN's idx (slot 0 is the anchor), the train keypoints and r * r.  mf_lds: the tile's train
- * keypoints next to the descriptor tile (16 bytes per row), every query's anchor keypoint and row, read once per workgroup. */
-struct mf_ctx { const int32_t *list, *idx; const double *kt; int kd; double rr; };
+/* What the FGINN rescan (mi_fginn.h) adds to the tile body below.  mf_ctx: the entry's needy list (OUTPUT rows at the list
+ * positions q0 .. q_end - 1), the plain 2-NN's idx (slot 0 is the anchor, at the output row), the train keypoints, r * r and qd = the
+ * entry's first query row in q minus its first output row: a needy query's descriptor row is its output row + qd (0 only in a ragged
+ * batch; of either sign in a pair list).  mf_lds: the tile's train keypoints next to the descriptor tile (16 bytes per row), every
+ * query's anchor keypoint and output row, read once per workgroup. */
+struct mf_ctx { const int32_t *list, *idx; const double *kt; int kd; double rr; int qd; };
 struct mf_lds { double2 tk[MT_T], ak[MT_Q]; int ai[MT_Q], row[MT_Q]; };
 
 /* One workgroup's tile: queries q0 .. q_end - 1 (at most 64) of q against train rows t_lo .. t_hi - 1 of t, candidates
  * indexed from t_base (0 for a single pair, the pair's first train row in a batch).  NORM: 0 = L2 over float words,
  * 1 = Hamming over 32-bit words of packed bytes; q, t: [n, words] row-major.  Returns true in the threads tid < 64 whose
  * query exists, with that query's merged top-2 (squared distances for L2) in m.
- * FG (the FGINN rescan): q0 .. q_end - 1 are positions of fg->list, whose entries are the query rows, and a train row is pushed only
- * when it competes with the query's anchor i0 = fg->idx[row][0]: t != i0 and dx dx + dy dy >= rr in fp64 (false for a NaN).  NORM 2
- * (uint8 rows under L2, FG only: the dense form is mu_knn2_tile) forms the exact integer S = |a|^2 + |b|^2 - 2 a.b with unsigned byte
+ * FGM != 0 (the FGINN rescan): q0 .. q_end - 1 are positions of fg->list, whose entries are the queries' output rows.  FGM 1 is the
+ * ragged batch, where the output row is the descriptor row too (the instantiation of before the pair list, kept as it was); FGM 2 is
+ * the pair list, descriptor row = output row + fg->qd.  A train row is pushed only when it competes with the query's anchor i0 = fg->idx[output row][0]: t != i0 and dx dx + dy dy >= rr in fp64 (false for a NaN).  NORM 2
+ * (uint8 rows under L2, FGM != 0 only: the dense form is mu_knn2_tile) forms the exact integer S = |a|^2 + |b|^2 - 2 a.b with unsigned byte
  * dot products on the vector unit. */
-template <int NORM, bool FG = false>
+template <int NORM, int FGM = 0>
 __device__ __forceinline__ bool mt_knn2_tile(const uint32_t *q, int q0, int q_end, const uint32_t *t, int t_lo, int t_hi, int t_base, int words,
                                              uint32_t (&qs)[MT_DC][MT_Q + 1], uint32_t (&ts)[MT_DC][MT_T + 1], mt_best (&merge)[MT_Q][16], mt_best &m,
                                              const mf_ctx *fg = nullptr, mf_lds *fl = nullptr)
 {
+    constexpr bool FG = FGM != 0;
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     mt_best best[4];
 #pragma unroll
@@ -88,7 +92,7 @@ __device__ __forceinline__ bool mt_knn2_tile(const uint32_t *q, int q0, int q_en
             for (int e = tid; e < MT_Q * MT_DC; e += 256) {
                 const int r = e / MT_DC, w = e - r * MT_DC;
                 const bool okq = q0 + r < q_end && w0 + w < words, okt = t0 + r < t_hi && w0 + w < words;
-                const int qr = FG ? fl->row[r] : q0 + r;
+                const int qr = FGM == 2 ? fl->row[r] + fg->qd : FG ? fl->row[r] : q0 + r;
                 qs[w][r] = okq ? q[(size_t)qr * words + w0 + w] : 0u;
                 ts[w][r] = okt ? t[(size_t)(t0 + r) * words + w0 + w] : 0u;
             }

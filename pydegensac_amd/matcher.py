@@ -236,7 +236,8 @@ def check_match_pairs_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_
         raise ValueError("guided matching is not part of this pair-list call: pass the models it returns to guided_match_pairs / "
                          "guided_match_pairs_tensors")
     if fginn_th is not None:
-        raise ValueError("fginn_th (the FGINN ratio test) is not part of the pair-list calls: use match_and_verify_batch")
+        raise ValueError("fginn_th (the FGINN ratio test) is not part of the pair-list calls: use match_and_verify_batch, or "
+                         "match_and_verify_fginn_pairs / match_and_verify_fginn_pairs_tensors over a pair list")
     code, kind = _check_sides(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype)
     offs = _counts_to_offsets((counts1, counts2), (d1_shape[0], d2_shape[0]), "image", True)
     pr = np.asarray(pairs)
@@ -502,8 +503,30 @@ def match_and_verify_pairs(kps_list, desc_list, pairs, model="F", ratio=0.9, mut
     list may hold self pairs, repeats, both orders and any order; images may be empty or unused.  Each store is uploaded once, whatever
     the number of pairs.  Per pair the results are bit for bit those of match_and_verify_batch on the pair's copied arrays with the
     same seeds (one per list entry, default parallel.pair_seeds(0, K)).  Returns (models [K, 3, 3], [match_p], [inlier_p]) as
-    match_and_verify_batch; guided and fginn_th are not part of this call (ValueError): guided_match_pairs takes the models it returns.
+    match_and_verify_batch; guided and fginn_th are not part of this call (ValueError): guided_match_pairs takes the models it returns,
+    match_and_verify_fginn_pairs runs the FGINN ratio test over a list.
     last_stats() holds the per-pair statistics."""
+    return _match_verify_pairs(None, kps_list, desc_list, pairs, model, ratio, mutual, px_th, conf, max_iters, laf_consistensy_coef, error_type,
+                               symmetric_error_check, enable_degeneracy_check, seeds, norm, device, guided, fginn_th, kps2_list, desc2_list)
+
+
+def match_and_verify_fginn_pairs(kps_list, desc_list, pairs, fginn_th, model="F", ratio=0.9, mutual=False, px_th=None, conf=None, max_iters=None,
+                                 laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True, enable_degeneracy_check=True,
+                                 seeds=None, norm=None, device=0, guided=False, kps2_list=None, desc2_list=None):
+    """match_and_verify_pairs with the FGINN ratio test of match_fginn in front of the estimator: fginn_th is the radius in pixels of the
+    train image's keypoints, a finite number >= 0.  Stores (one, or two with kps2_list / desc2_list; a store named on both sides is
+    uploaded once), list, seeds and the returned tuple are those of match_and_verify_pairs; per entry the results are bit for bit those
+    of match_and_verify_batch(fginn_th=) on the entry's copied arrays with the same seeds.  guided=True is refused here as well:
+    guided_match_pairs takes the models this call returns.  last_stats() holds the per-pair statistics."""
+    r = check_fginn_th(fginn_th)
+    return _match_verify_pairs(r, kps_list, desc_list, pairs, model, ratio, mutual, px_th, conf, max_iters, laf_consistensy_coef, error_type,
+                               symmetric_error_check, enable_degeneracy_check, seeds, norm, device, guided, None, kps2_list, desc2_list)
+
+
+def _match_verify_pairs(fginn_r, kps_list, desc_list, pairs, model, ratio, mutual, px_th, conf, max_iters, laf_consistensy_coef, error_type,
+                        symmetric_error_check, enable_degeneracy_check, seeds, norm, device, guided, fginn_th, kps2_list, desc2_list):
+    """the body of the two pair-list match-and-verify calls: fginn_r None = the plain call (which refuses fginn_th), a checked radius =
+    the FGINN call and its entry point"""
     (A, K1, c1), (B, K2, c2), one = _stack_stores(kps_list, desc_list, kps2_list, desc2_list)
     code, kind, o1, o2, pr, po, sd = check_match_pairs_args(model, ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape,
                                                             K2.dtype, c1, c2, pairs, seeds, guided, fginn_th)
@@ -512,16 +535,16 @@ def match_and_verify_pairs(kps_list, desc_list, pairs, model="F", ratio=0.9, mut
     if sd is None:
         sd = _seeds_u32(None, K)
     A, K1, B, K2 = _finish_stores(code, kind, A, K1, B, K2, one, device)              # one store: uploaded once
-    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual)
+    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual, fginn_r)
     n = int(po[-1])
     M = np.zeros((K, 9)); match = np.full(n, -1, np.int32); inl = np.zeros(n, np.uint8)
     st = np.zeros((K, 16), np.int32); cnt = np.zeros(K, np.int32)
     lp = C.POINTER(C.c_int64); ip = C.POINTER(C.c_int32)
-    rc = _lib.lib().mi_degensac_match_verify_pairs(1 if model == "H" else 0, C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p),
-                                                   o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, _lib.dptr(K1), _lib.dptr(K2),
-                                                   K1.shape[1], pr.ctypes.data_as(ip), K, C.byref(prm), sd.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                   int(device), _lib.dptr(M), match.ctypes.data_as(ip), inl.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                   st.ctypes.data_as(ip), cnt.ctypes.data_as(ip))
+    entry = _lib.lib().mi_degensac_match_verify_pairs if fginn_r is None else _lib.lib().mi_degensac_match_verify_fginn_pairs
+    rc = entry(1 if model == "H" else 0, C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), o1.ctypes.data_as(lp), len(o1) - 1,
+               o2.ctypes.data_as(lp), len(o2) - 1, _lib.dptr(K1), _lib.dptr(K2), K1.shape[1], pr.ctypes.data_as(ip), K, C.byref(prm),
+               sd.ctypes.data_as(C.POINTER(C.c_uint32)), int(device), _lib.dptr(M), match.ctypes.data_as(ip), inl.ctypes.data_as(C.POINTER(C.c_uint8)),
+               st.ctypes.data_as(ip), cnt.ctypes.data_as(ip))
     _lib.check(rc)
     _set_last_stats(st, cnt)
     M = M.reshape(K, 3, 3)

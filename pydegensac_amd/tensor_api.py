@@ -428,6 +428,43 @@ def knn_match_pairs_tensors(desc1, desc2, counts1, counts2, pairs, norm=None):
     return idx, dist, po
 
 
+def knn_match_fginn_pairs_tensors(desc1, desc2, kps2, counts1, counts2, pairs, spatial_th=10.0, norm=None):
+    """knn_match_pairs_tensors with the FGINN rule of knn_match_fginn_batch_tensors for the second neighbour (include/mi_degensac.h
+    mi_degensac_match_fginn_knn2_pairs_dev).  kps2 is the keypoint store of side 2: float64 [N2, 2] / [N2, 6] on the device, one row
+    per row of desc2 (only x, y are read).  For entry p = (i, j) slot 1 is the nearest row of image j whose keypoint lies at least
+    spatial_th from the keypoint of slot 0.  Stores, list and layout as for knn_match_pairs_tensors: no descriptor or keypoint row is
+    copied, and per entry the rows are bit for bit what knn_match_fginn_batch_tensors returns for the entry's copied rows.  Returns
+    (idx [N, 2] int32 with indices LOCAL to image j, dist [N, 2] float32, pair_offsets [K + 1] host int64); asynchronous on the current
+    stream (no host synchronisation)."""
+    import torch
+    from . import matcher
+    if not all(isinstance(t, torch.Tensor) for t in (desc1, desc2, kps2)):
+        raise ValueError("desc1, desc2 and kps2 must be torch tensors on a ROCm device")
+    r = matcher.check_fginn_th(spatial_th, "spatial_th")
+    if kps2.dim() != 2 or kps2.dtype != torch.float64 or kps2.shape[1] not in (2, 6):
+        raise ValueError("keypoints should be float64 [n, 2] / [n, 6] rows")
+    code, _, o1, o2, pr, po, _ = matcher.check_match_pairs_args("F", 1.0, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
+                                                                (desc1.shape[0], kps2.shape[1]), np.float64, tuple(kps2.shape), kps2.dtype,
+                                                                counts1, counts2, pairs)
+    if kps2.device != desc1.device:
+        raise ValueError("desc1, desc2 and kps2 must live on the same ROCm device")
+    a, b = _desc_pair(desc1, desc2)
+    k2 = kps2.contiguous()
+    dev = a.device; n = int(po[-1]); K = len(pr)
+    idx = torch.full((n, 2), -1, dtype=torch.int32, device=dev)
+    dist = torch.full((n, 2), float("inf"), dtype=torch.float32, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    lp = C.POINTER(C.c_int64)
+    rc = _lib.lib().mi_degensac_match_fginn_knn2_pairs_dev(code, a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(lp), len(o1) - 1,
+                                                           o2.ctypes.data_as(lp), len(o2) - 1, pr.ctypes.data_as(C.POINTER(C.c_int32)), K,
+                                                           int(a.shape[1]), k2.data_ptr(), int(k2.shape[1]), r, dev.index or 0,
+                                                           C.c_void_p(stream.cuda_stream), idx.data_ptr(), dist.data_ptr())
+    _lib.check_match(rc)
+    for t in (a, b, k2):
+        t.record_stream(stream)
+    return idx, dist, po
+
+
 def match_and_verify_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
                                    max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
                                    enable_degeneracy_check=True, seeds=None, guided=False, norm=None, fginn_th=None):
@@ -440,7 +477,30 @@ def match_and_verify_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, p
     Returns (model [K, 3, 3], match [N] int32 = train row local to image j or -1, inlier [N] bool, stats [K, 16], n_tentatives [K]
     numpy int64, pair_offsets [K + 1] host int64) with N = pair_offsets[K]: the per-query outputs lie pair after pair in list order.
     guided=True and fginn_th are not part of this call (ValueError): guided matching over the list is guided_match_pairs_tensors, which
-    takes the models returned here as they are; FGINN keeps its batched entry points."""
+    takes the models returned here as they are; the FGINN ratio test over a list is match_and_verify_fginn_pairs_tensors."""
+    return _match_verify_pairs_tensors(None, kps1, kps2, desc1, desc2, counts1, counts2, pairs, model, ratio, mutual, px_th, conf, max_iters,
+                                       laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check, seeds, guided, norm, fginn_th)
+
+
+def match_and_verify_fginn_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs, fginn_th, model="F", ratio=0.9, mutual=False, px_th=None,
+                                         conf=None, max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
+                                         enable_degeneracy_check=True, seeds=None, guided=False, norm=None):
+    """match_and_verify_pairs_tensors with the FGINN ratio test in front of the estimator (include/mi_degensac.h
+    mi_degensac_match_verify_fginn_pairs_dev): fginn_th is the radius in pixels of kps2 (knn_match_fginn_pairs_tensors at that radius on
+    the x, y of store 2's keypoints), a finite number >= 0.  Stores, list, seeds, the returned tuple and the single synchronisation are
+    those of match_and_verify_pairs_tensors; per entry every output is bit for bit that of match_and_verify_batch_tensors(fginn_th=) on
+    the entry's copied rows with the same seeds.  guided=True is refused here as well: guided_match_pairs_tensors takes the returned
+    models as they are."""
+    from . import matcher
+    r = matcher.check_fginn_th(fginn_th)
+    return _match_verify_pairs_tensors(r, kps1, kps2, desc1, desc2, counts1, counts2, pairs, model, ratio, mutual, px_th, conf, max_iters,
+                                       laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check, seeds, guided, norm, None)
+
+
+def _match_verify_pairs_tensors(fginn_r, kps1, kps2, desc1, desc2, counts1, counts2, pairs, model, ratio, mutual, px_th, conf, max_iters,
+                                laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check, seeds, guided, norm, fginn_th):
+    """the body of the two pair-list match-and-verify calls: fginn_r None = the plain call (which refuses fginn_th), a checked radius =
+    the FGINN call and its entry point"""
     import torch
     from . import matcher
     ts = (kps1, kps2, desc1, desc2)
@@ -461,8 +521,8 @@ def match_and_verify_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, p
     lp = C.POINTER(C.c_int64)
     layout = (o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]),
               pr.ctypes.data_as(C.POINTER(C.c_int32)), K)
-    return _match_verify_dev(_lib.lib().mi_degensac_match_verify_pairs_dev, layout, model, _lib.MatchParams(code, a.shape[1], ratio, mutual), prm, a, b,
-                             k1, k2, sd, K, n)[:5] + (po,)
+    entry = _lib.lib().mi_degensac_match_verify_pairs_dev if fginn_r is None else _lib.lib().mi_degensac_match_verify_fginn_pairs_dev
+    return _match_verify_dev(entry, layout, model, _lib.MatchParams(code, a.shape[1], ratio, mutual, fginn_r), prm, a, b, k1, k2, sd, K, n)[:5] + (po,)
 
 
 def guided_match_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs, models, model="F", ratio=0.9, mutual=False, px_th=None,
