@@ -415,7 +415,7 @@ typedef struct mi_degensac_match_params {
  * per query row of desc1: d_match = train row local to the pair or -1 when the row is not a tentative, d_inlier = 1 when it is a
  * tentative and an inlier of the pair's model.  h_counts (host, [K], nullable): tentatives per pair.
  * mp->second_nn = 1 (with struct_size covering spatial_th) switches the ratio test to FGINN at mp->spatial_th on this call's d_kp2;
- * the guided entry points ignore both fields.
+ * the plain guided entry points ignore both fields (mi_degensac_match_guided_fginn_* below are the guided calls that read them).
  * Synchronisation: the matching is enqueued on `stream`, then the call reads the K tentative counts back (ONE device-to-host copy
  * followed by a wait for `stream`: the only synchronisation; the estimator's launch is sized from them on the host), enqueues the
  * gather, the estimator and the scatter and returns.  Discarded pairs (hand-over time-out) carry bit 10 of stats[15] as with the
@@ -551,7 +551,7 @@ int mi_degensac_match_guided_batch(const mi_degensac_match_params *mp, const voi
  * pairs[p][1]) rows), which the call allocates stream-ordered and frees.  No descriptor or keypoint row is gathered or copied on the
  * device.  Every output is bit for bit what the batched entry point of the same name (guided_knn2_batch_dev / guided_batch_dev /
  * guided_batch) returns when entry p's rows are copied out of the stores and the models are the same.  mp->second_nn is ignored, as
- * there.
+ * there (mi_degensac_match_guided_fginn_pairs* reads it).
  * Errors, before a device is looked for: MI_DEGENSAC_EINVAL for a bad norm / dim / kp_dim / guide params / ratio, then n_pairs < 0,
  * then (n_pairs > 0) bad offsets, an image index outside its store, output or back rows beyond 0x3fffffff, NULL pointers.
  * n_pairs == 0 with good params returns 0 and looks at nothing else. */
@@ -572,6 +572,66 @@ int mi_degensac_match_guided_pairs(const mi_degensac_match_params *mp, const voi
                                    int n_images1, const int64_t *offsets2, int n_images2, const int32_t *pairs, int n_pairs, const double *kp1,
                                    const double *kp2, int kp_dim, const double *models, const mi_degensac_guide_params *gp, int device,
                                    int32_t *idx, float *dist, int32_t *match, int32_t *counts /*nullable*/);
+
+/* ---- guided matching with the FGINN second neighbour INSIDE the gate (mi_guided.hip) --------------------------------------------
+ * The two remedies for tentatives the ratio test drops, composed.  The gate takes the look-alikes elsewhere in the image away and leaves
+ * a keypoint's own twin (a second orientation, a neighbouring scale a pixel away) as its only second neighbour: the twin lies inside the
+ * band too, d1 ~ d0, and the plain guided decision drops exactly the multi-orientation, multi-scale keypoints.  Here, per list entry p
+ * with model M_p, the train keypoints kp2 of the entry and r = spatial_th (finite, >= 0):
+ *   gate(q, t)  exactly as above (the same residual, `<=`, a NaN fails, a zero model passes nothing);
+ *   slot 0      (i0, d0) = the nearest gated train row, unchanged from the plain guided 2-NN;
+ *   a train row t competes for slot 1 iff gate(q, t) passes and t != i0 and dx dx + dy dy >= r r, dx = x2[t] - x2[i0], dy = y2[t] -
+ *               y2[i0], in fp64 in that order without contraction; a NaN makes the comparison false (the rule of
+ *               mi_degensac_match_fginn_knn2_batch_dev word for word, applied after the gate and anchored at the GATED nearest row);
+ *   slot 1      the nearest competing row in the matcher's (distance, index) order, distances formed as the guided 2-NN forms them;
+ *               -1 / inf when nothing competes or i0 = -1;
+ *   decision    the guided one, unchanged: match = i0 when i0 >= 0 && dist0 < ratio * dist1.  A query whose only gated companions lie
+ *               inside the radius has dist1 = inf and is KEPT: nothing competes with it.  This is the guided rule, not the unguided
+ *               FGINN rule (which needs a second row), and it is the case these calls exist for;
+ *   mutual      the reverse guided search and the mutual check stay the plain ones (slot 0 only).
+ * r = 0 with finite keypoints is the plain guided 2-NN and decision bit for bit.
+ * Cost: the plain guided pass (the same kernels, unchanged), one pass over its output that lists per entry the NEEDY queries (slot 1
+ * exists and does not compete), and a rescan of those only, in the guided kernel's shape with the exclusion test in the gate's place in
+ * the pass predicate.  A needy query has two rows, its output row and its query row in store 1 (equal only in a ragged batch); both are
+ * found through the entry's record and no descriptor or keypoint row is copied.  The rescan's grid is sized on the host for the worst
+ * case: no host synchronisation.  Memory: 4 bytes per output row and per entry next to the plain call's, stream-ordered and freed.
+ *
+ * mi_degensac_match_guided_fginn_knn2_batch_dev / _pairs_dev: mi_degensac_match_guided_knn2_batch_dev / _pairs_dev with spatial_th after
+ * the guide params; asynchronous on `stream`, no host synchronisation.
+ * mi_degensac_match_guided_fginn_batch_dev / _batch / _pairs_dev / _pairs: the signatures of the plain guided calls; they honour
+ * mp->second_nn / mp->spatial_th when mp->struct_size covers spatial_th.  With second_nn = 0, or a struct_size that does not cover it
+ * (0 included), they ARE the plain guided calls.
+ * Errors, before a device is looked for: those of the plain guided call of the same layout in its order (params, gate, n_pairs < 0, then
+ * for n_pairs > 0 the offsets and the list), then MI_DEGENSAC_EINVAL for a spatial_th that is negative or not finite or a second_nn
+ * other than 0 / 1, then (n_pairs > 0) NULL pointers.  n_pairs == 0 with good params returns 0. */
+int mi_degensac_match_guided_fginn_knn2_batch_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
+                                                  const int64_t *offsets2_host, int n_pairs, int dim, const double *d_kp1, const double *d_kp2,
+                                                  int kp_dim, const double *d_models, const mi_degensac_guide_params *gp, double spatial_th,
+                                                  int device, void *stream, int32_t *d_idx, float *d_dist);
+int mi_degensac_match_guided_fginn_knn2_pairs_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host, int n_images1,
+                                                  const int64_t *offsets2_host, int n_images2, const int32_t *pairs_host, int n_pairs, int dim,
+                                                  const double *d_kp1, const double *d_kp2, int kp_dim, const double *d_models /* [K*9] */,
+                                                  const mi_degensac_guide_params *gp, double spatial_th, int device, void *stream, int32_t *d_idx,
+                                                  float *d_dist);
+int mi_degensac_match_guided_fginn_batch_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
+                                             const int64_t *offsets1_host, const int64_t *offsets2_host, const double *d_kp1, const double *d_kp2,
+                                             int kp_dim, int n_pairs, const double *d_models, const mi_degensac_guide_params *gp, int device,
+                                             void *stream, int32_t *d_idx, float *d_dist, int32_t *d_match, int32_t *d_counts /*nullable*/,
+                                             int32_t *h_counts /*nullable*/);
+int mi_degensac_match_guided_fginn_batch(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
+                                         const int64_t *offsets2, const double *kp1, const double *kp2, int kp_dim, int n_pairs,
+                                         const double *models, const mi_degensac_guide_params *gp, int device, int32_t *idx, float *dist,
+                                         int32_t *match, int32_t *counts /*nullable*/);
+int mi_degensac_match_guided_fginn_pairs_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
+                                             const int64_t *offsets1_host, int n_images1, const int64_t *offsets2_host, int n_images2,
+                                             const int32_t *pairs_host, int n_pairs, const double *d_kp1, const double *d_kp2, int kp_dim,
+                                             const double *d_models, const mi_degensac_guide_params *gp, int device, void *stream, int32_t *d_idx,
+                                             float *d_dist, int32_t *d_match, int32_t *d_counts /*nullable*/, int32_t *h_counts /*nullable*/);
+int mi_degensac_match_guided_fginn_pairs(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
+                                         int n_images1, const int64_t *offsets2, int n_images2, const int32_t *pairs, int n_pairs,
+                                         const double *kp1, const double *kp2, int kp_dim, const double *models,
+                                         const mi_degensac_guide_params *gp, int device, int32_t *idx, float *dist, int32_t *match,
+                                         int32_t *counts /*nullable*/);
 
 /* ---- unit-level device entry points (parity tests of the kernels' building blocks) ------------ */
 /* score n_models fundamental (kind 0: Sampson, 1: symmetric epipolar) or homography (kind 10..14:

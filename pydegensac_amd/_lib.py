@@ -232,6 +232,15 @@ def lib():
             l.mi_degensac_match_guided_pairs.restype = C.c_int
             l.mi_degensac_match_guided_pairs.argtypes = [mpp, C.c_void_p, C.c_void_p, lp, C.c_int, lp, C.c_int, ip, C.c_int, dp, dp, C.c_int, dp, gpp,
                                                          C.c_int, ip, C.POINTER(C.c_float), ip, ip]
+        if hasattr(l, "mi_degensac_match_guided_fginn_pairs_dev"):        # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            # FGINN inside the gate: the knn2 forms take the radius after the guide params, the others read it from the match params
+            for lay in ("batch", "pairs"):
+                f = getattr(l, f"mi_degensac_match_guided_fginn_knn2_{lay}_dev"); f.restype = C.c_int
+                at = list(getattr(l, f"mi_degensac_match_guided_knn2_{lay}_dev").argtypes)
+                f.argtypes = at[:at.index(gpp) + 1] + [C.c_double] + at[at.index(gpp) + 1:]
+                for tail in ("_dev", ""):
+                    f = getattr(l, f"mi_degensac_match_guided_fginn_{lay}{tail}"); f.restype = C.c_int
+                    f.argtypes = getattr(l, f"mi_degensac_match_guided_{lay}{tail}").argtypes
         l.mi_degensac_kpts_to_xyA.restype = C.c_int
         l.mi_degensac_kpts_to_xyA.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, dp]
         l.mi_degensac_kpts_to_xyA_dev.restype = C.c_int

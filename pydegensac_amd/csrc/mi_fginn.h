@@ -103,6 +103,16 @@ __global__ __launch_bounds__(256) void mf_merge_kernel(const mt_best *part, int 
     }
 }
 
+/* mf_mark_kernel for another stage's result lists (the guided stage, mi_guided.hip, whose slot 1 is judged by the same rule) */
+int mt_batch_fginn_mark(const int32_t *idx, const mt_pair_rows *d_rows, int n_pairs, const double *kt, int kd, double rr, hipStream_t s, int32_t *list,
+                        int32_t *count)
+{
+    if (n_pairs <= 0) return 0;
+    hipLaunchKernelGGL(mf_mark_kernel, dim3(n_pairs), dim3(256), 0, s, idx, d_rows, kt, kd, rr, list, count);
+    MTCHK(hipGetLastError());
+    return 0;
+}
+
 /* slot 1 of idx / dist (the plain batched 2-NN of the same rows, already enqueued on s) becomes the FGINN second neighbour */
 int mt_batch_fginn(int norm, int words, const void *dq, const void *dt, const double *kt, int kd, const mt_pair_rows *rows, int n_pairs, int n_rows,
                    double r, int device, hipStream_t s, int32_t *idx, float *dist)

@@ -188,6 +188,99 @@ __global__ __launch_bounds__(256) void mg_guided_kernel(const uint32_t *dq, cons
     }
 }
 
+/* FGINN inside the gate (include/mi_degensac.h mi_degensac_match_guided_fginn_*): the second distance of a guided query comes from the
+ * nearest GATED train row whose keypoint lies at least r from the keypoint of the nearest gated row (the anchor, slot 0).  The gate takes
+ * the look-alikes elsewhere in the image away and leaves a keypoint's own twin (a second orientation, a neighbouring scale) as its only
+ * second neighbour; the twin lies inside the band too, so the plain guided rule drops exactly those queries.  A gated row t competes for
+ * slot 1 iff t != i0 and dx dx + dy dy >= r r (dx = x2[t] - x2[i0], dy = y2[t] - y2[i0], fp64 in that order, a NaN is false): the rule of
+ * mi_fginn.h word for word, applied after the gate.  The decision stays the guided one: a query whose only gated companions lie inside
+ * the radius has dist1 = inf and is KEPT (nothing competes with it), where the unguided FGINN filter needs a second row.
+ *
+ * mg_guided_kernel runs unchanged; mf_mark_kernel (mi_fginn.h, through mt_batch_fginn_mark) lists per entry, in ascending query order,
+ * the NEEDY queries (slot 1 exists and does not compete) as OUTPUT rows.  This kernel rescans only those, in the guided kernel's shape:
+ * the grid is the forward search's tile table (the worst case, every query needy; no host synchronisation), tile k of an entry owns the
+ * list positions MG_Q k .. of that entry and returns at once when they lie at or beyond the entry's needy count (uniform over the
+ * workgroup, before any barrier).  A needy query has TWO rows: its output row o (the list's value; the anchor idx[o][0] is read and
+ * slot 1 written there) and its query row in store 1, r.q + (o - r.out); only a ragged batch has them equal.  The anchor's x, y are
+ * wave-uniform per query and the exclusion test is part of the pass predicate, so the candidate lists, their flushes at 64 with a carry
+ * and the distances are those of the forward search; of the top-2 only slot 0 is merged and written, to slot 1 of the output row. */
+template <int NORM, int GK>
+__global__ __launch_bounds__(256) void mg_rescan_kernel(const uint32_t *dq, const uint32_t *dt, int words, const double *kq, const double *kt, int kd,
+                                                        const int32_t *toff, const mt_pair_rows *rows, int n_pairs, const double *models, int hk,
+                                                        double th, double tb, int screen, const int32_t *list, const int32_t *count, double rr,
+                                                        int32_t *idx, float *dist)
+{
+    __shared__ double2 ts[MG_TC];
+    __shared__ int lists[MG_W][MG_QPW][MG_LIST];
+    const int b = (int)blockIdx.x;
+    int lo = 0, hi = n_pairs - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (toff[mid] <= b) lo = mid; else hi = mid - 1; }
+    const int pair = lo;
+    const mt_pair_rows r = rows[pair];
+    const int k0 = (b - toff[pair]) * MG_Q, k_end = count[pair];     /* list positions of this tile, the entry's needy count (<= r.nq) */
+    if (k0 >= k_end) return;                                         /* uniform over the workgroup */
+    const int t_b = r.t, n_t = r.nt;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double M[9], Hinv[9], H1[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) M[i] = models[(size_t)pair * 9 + i];  /* a needy query has two gated rows: the model is not zero */
+    if (GK == MG_H_SYM) dg_hsym_prepare(M, Hinv, H1);
+    const int t_e = t_b + n_t;
+    double qx[MG_QPW], qy[MG_QPW], ax[MG_QPW], ay[MG_QPW]; int cnt[MG_QPW], orow[MG_QPW], anc[MG_QPW]; mt_best best[MG_QPW];
+#pragma unroll
+    for (int j = 0; j < MG_QPW; j++) {
+        const int k = k0 + wv + MG_W * j;
+        const bool on = k < k_end;                                   /* wave-uniform */
+        orow[j] = on ? list[r.out + k] : r.out;
+        anc[j] = on ? idx[2 * (size_t)orow[j]] : -1;
+        const size_t q = (size_t)(r.q + (orow[j] - r.out));
+        qx[j] = on ? kq[q * kd] : 0.0; qy[j] = on ? kq[q * kd + 1] : 0.0;
+        ax[j] = anc[j] >= 0 ? kt[(size_t)(t_b + anc[j]) * kd] : 0.0; ay[j] = anc[j] >= 0 ? kt[(size_t)(t_b + anc[j]) * kd + 1] : 0.0;
+        cnt[j] = 0; best[j].d0 = best[j].d1 = __builtin_inff(); best[j].i0 = best[j].i1 = -1;
+    }
+    for (int c0 = t_b; c0 < t_e; c0 += MG_TC) {
+        const int c_end = c0 + MG_TC < t_e ? c0 + MG_TC : t_e;
+        __syncthreads();
+        for (int i = threadIdx.x; i < c_end - c0; i += 256) ts[i] = make_double2(kt[(size_t)(c0 + i) * kd], kt[(size_t)(c0 + i) * kd + 1]);
+        __syncthreads();
+        for (int s0 = c0; s0 < c_end; s0 += 64) {
+            const int t = s0 + lane;
+            const bool in = t < c_end;
+            const double2 p = ts[in ? t - c0 : 0];
+#pragma unroll
+            for (int j = 0; j < MG_QPW; j++) {
+                if (k0 + wv + MG_W * j >= k_end) continue;                         /* wave-uniform */
+                const double dx = p.x - ax[j], dy = p.y - ay[j];
+                const bool pass = in && t - t_b != anc[j] && dx * dx + dy * dy >= rr
+                                  && mg_gate<GK>(M, Hinv, H1, hk, th, tb, screen, qx[j], qy[j], p.x, p.y);
+                const unsigned long long bal = __ballot(pass);
+                int *lst = lists[wv][j];
+                if (pass) lst[cnt[j] + __popcll(bal & ((1ull << lane) - 1ull))] = t - t_b;
+                cnt[j] += __popcll(bal);
+                if (cnt[j] >= 64) {                                                /* wave-uniform */
+                    mg_flush<NORM>(dq + (size_t)(r.q + (orow[j] - r.out)) * words, dt, words, t_b, lst, 64, lane, best[j]);
+                    if (lane < cnt[j] - 64) lst[lane] = lst[64 + lane];
+                    cnt[j] -= 64;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < MG_QPW; j++) {
+        if (k0 + wv + MG_W * j >= k_end) continue;
+        if (cnt[j] > 0) mg_flush<NORM>(dq + (size_t)(r.q + (orow[j] - r.out)) * words, dt, words, t_b, lists[wv][j], cnt[j], lane, best[j]);
+        float d = best[j].d0; int i = best[j].i0;
+        for (int k = 1; k < 64; k <<= 1) {                                         /* the minimum in (distance, index) order */
+            const float d2 = __shfl_xor(d, k); const int i2 = __shfl_xor(i, k);
+            if (i2 >= 0 && (i < 0 || d2 < d || (d2 == d && i2 < i))) { d = d2; i = i2; }
+        }
+        if (lane == 0) {
+            const size_t o = (size_t)orow[j] * 2 + 1;
+            idx[o] = i; dist[o] = NORM != 1 ? sqrtf(d) : d;
+        }
+    }
+}
+
 /* one workgroup per pair: every query's decision and the pair's number of guided matches */
 __global__ __launch_bounds__(256) void mg_decide_kernel(const int32_t *idx, const float *dist, const int32_t *off1, const int32_t *off2, float ratio,
                                                         const int32_t *back, int32_t *match, int32_t *count)
@@ -245,21 +338,36 @@ int mt_guided_gate(int homography, int error_type, double px_th, mt_gate *g)
     return 0;
 }
 
-int mt_batch_guided_knn2(int norm, int words, const void *dq, const void *dt, const double *kq, const double *kt, int kd, const mt_pair_rows *rows,
-                         int n_pairs, int n_rows, const double *d_models, const mt_gate &g, int swap, int device, hipStream_t s, int32_t *idx,
-                         float *dist)
+/* the forward / reverse search's tile table, one upload: the tile starts [K + 1], then (16-byte aligned, at *a_rows) the entries' records
+ * as they are; returns the number of tiles */
+static int64_t mg_tile_table(const mt_pair_rows *rows, int n_pairs, int swap, std::vector<char> &tab, size_t *a_rows)
 {
-    if (n_pairs <= 0 || n_rows == 0) return 0;
-    /* one upload: the tile starts [K + 1], then (16-byte aligned) the entries' records as they are */
-    const size_t a_rows = ((size_t)(n_pairs + 1) * 4 + 15) / 16 * 16, bytes = a_rows + (size_t)n_pairs * sizeof(mt_pair_rows);
-    std::vector<char> tab(bytes);
+    *a_rows = ((size_t)(n_pairs + 1) * 4 + 15) / 16 * 16;
+    tab.resize(*a_rows + (size_t)n_pairs * sizeof(mt_pair_rows));
     int32_t *toff = (int32_t *)tab.data();
     int64_t tiles = 0;
     for (int p = 0; p <= n_pairs; p++) {
         toff[p] = (int32_t)tiles;
         if (p < n_pairs) tiles += ((swap ? rows[p].nt : rows[p].nq) + MG_Q - 1) / MG_Q;
     }
-    memcpy(tab.data() + a_rows, rows, (size_t)n_pairs * sizeof(mt_pair_rows));
+    memcpy(tab.data() + *a_rows, rows, (size_t)n_pairs * sizeof(mt_pair_rows));
+    return tiles;
+}
+
+/* one launch per (norm, gate kind): KERNEL<N, G> with the arguments after it */
+#define MG_DISPATCH(norm, gk, LAUNCH) switch (4 * mt_norm_index(norm) + (gk)) { \
+    case 0: LAUNCH(0, MG_F_SAMPSON); break;  case 1: LAUNCH(0, MG_F_SYM); break;  case 2: LAUNCH(0, MG_H_SAMPSON); break;  case 3: LAUNCH(0, MG_H_SYM); break; \
+    case 4: LAUNCH(1, MG_F_SAMPSON); break;  case 5: LAUNCH(1, MG_F_SYM); break;  case 6: LAUNCH(1, MG_H_SAMPSON); break;  case 7: LAUNCH(1, MG_H_SYM); break; \
+    case 8: LAUNCH(2, MG_F_SAMPSON); break;  case 9: LAUNCH(2, MG_F_SYM); break;  case 10: LAUNCH(2, MG_H_SAMPSON); break; default: LAUNCH(2, MG_H_SYM); break; }
+
+int mt_batch_guided_knn2(int norm, int words, const void *dq, const void *dt, const double *kq, const double *kt, int kd, const mt_pair_rows *rows,
+                         int n_pairs, int n_rows, const double *d_models, const mt_gate &g, int swap, int device, hipStream_t s, int32_t *idx,
+                         float *dist)
+{
+    if (n_pairs <= 0 || n_rows == 0) return 0;
+    std::vector<char> tab; size_t a_rows;
+    const int64_t tiles = mg_tile_table(rows, n_pairs, swap, tab, &a_rows);
+    const size_t bytes = tab.size();
     char *d_tab = nullptr;
     MGCHK(hipMallocAsync((void **)&d_tab, bytes, s));
     int rc = mt_batch_upload(device, s, tab.data(), bytes, d_tab);
@@ -267,24 +375,38 @@ int mt_batch_guided_knn2(int norm, int words, const void *dq, const void *dt, co
     const dim3 grid((unsigned)tiles), block(256);
 #define MG_LAUNCH(N, G) hipLaunchKernelGGL((mg_guided_kernel<N, G>), grid, block, 0, s, (const uint32_t *)dq, (const uint32_t *)dt, words, kq, kt, kd, \
         (const int32_t *)d_tab, (const mt_pair_rows *)(d_tab + a_rows), n_pairs, d_models, g.hk, g.th, g.tb, g.screen, swap, idx, dist)
-    switch (4 * mt_norm_index(norm) + g.gk) {
-    case 0: MG_LAUNCH(0, MG_F_SAMPSON); break;
-    case 1: MG_LAUNCH(0, MG_F_SYM); break;
-    case 2: MG_LAUNCH(0, MG_H_SAMPSON); break;
-    case 3: MG_LAUNCH(0, MG_H_SYM); break;
-    case 4: MG_LAUNCH(1, MG_F_SAMPSON); break;
-    case 5: MG_LAUNCH(1, MG_F_SYM); break;
-    case 6: MG_LAUNCH(1, MG_H_SAMPSON); break;
-    case 7: MG_LAUNCH(1, MG_H_SYM); break;
-    case 8: MG_LAUNCH(2, MG_F_SAMPSON); break;
-    case 9: MG_LAUNCH(2, MG_F_SYM); break;
-    case 10: MG_LAUNCH(2, MG_H_SAMPSON); break;
-    default: MG_LAUNCH(2, MG_H_SYM); break;
-    }
+    MG_DISPATCH(norm, g.gk, MG_LAUNCH)
 #undef MG_LAUNCH
     const hipError_t le = hipGetLastError();
     (void)hipFreeAsync(d_tab, s);
     MGCHK(le);
+    return 0;
+}
+
+/* one stream-ordered block: the tile table | the needy lists (one int32 per output row) | the needy counts [K] */
+int mt_batch_guided_fginn(int norm, int words, const void *dq, const void *dt, const double *kq, const double *kt, int kd, const mt_pair_rows *rows,
+                          int n_pairs, int n_rows, const double *d_models, const mt_gate &g, double r, int device, hipStream_t s, int32_t *idx,
+                          float *dist)
+{
+    if (n_pairs <= 0 || n_rows == 0) return 0;
+    std::vector<char> tab; size_t a_rows;
+    const int64_t tiles = mg_tile_table(rows, n_pairs, 0, tab, &a_rows);
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t a_list = up(tab.size()), a_cnt = a_list + up((size_t)n_rows * 4), a_all = a_cnt + up((size_t)n_pairs * 4);
+    char *blk = nullptr;
+    MGCHK(hipMallocAsync((void **)&blk, a_all, s));
+    struct Free { char *p; hipStream_t s; ~Free() { (void)hipFreeAsync(p, s); } } fr{blk, s};
+    int rc = mt_batch_upload(device, s, tab.data(), tab.size(), blk); if (rc) return rc;
+    const mt_pair_rows *d_rows = (const mt_pair_rows *)(blk + a_rows);
+    int32_t *list = (int32_t *)(blk + a_list), *cnt = (int32_t *)(blk + a_cnt);
+    const double rr = r * r;
+    rc = mt_batch_fginn_mark(idx, d_rows, n_pairs, kt, kd, rr, s, list, cnt); if (rc) return rc;
+    const dim3 grid((unsigned)tiles), block(256);
+#define MG_LAUNCH(N, G) hipLaunchKernelGGL((mg_rescan_kernel<N, G>), grid, block, 0, s, (const uint32_t *)dq, (const uint32_t *)dt, words, kq, kt, kd, \
+        (const int32_t *)blk, d_rows, n_pairs, d_models, g.hk, g.th, g.tb, g.screen, list, cnt, rr, idx, dist)
+    MG_DISPATCH(norm, g.gk, MG_LAUNCH)
+#undef MG_LAUNCH
+    MGCHK(hipGetLastError());
     return 0;
 }
 
@@ -317,6 +439,23 @@ static int mg_check_ratio(const mi_degensac_match_params *mp)
     return 0;
 }
 
+/* the second-neighbour rule of a guided call.  honour = 0 (the plain entry points): second_nn / spatial_th are not read.  honour = 1 (the
+ * guided_fginn entry points): mt_second_nn, so a struct_size that does not cover spatial_th, or second_nn = 0, is the plain call */
+struct mg_second { int fginn; double r; };
+static int mg_check_second(const mi_degensac_match_params *mp, int honour, mg_second *sn)
+{
+    sn->fginn = 0; sn->r = 0.0;
+    if (!honour) return 0;
+    if (const char *e = mt_second_nn(mp, &sn->fginn, &sn->r)) return mg_einval(e);
+    return 0;
+}
+/* the radius of the guided_fginn_knn2 entry points */
+static int mg_check_radius(double spatial_th)
+{
+    if (const char *e = mt_spatial_th_error(spatial_th)) return mg_einval(e);
+    return 0;
+}
+
 /* the ragged batch */
 static int mg_check(int norm, int dim, int kp_dim, const mi_degensac_guide_params *gp, const int64_t *o1, const int64_t *o2, int n_pairs, mt_gate *g)
 {
@@ -345,12 +484,13 @@ static int mg_check_pairs(int norm, int dim, int kp_dim, const mi_degensac_guide
 
 static int mg_words(int norm, int dim) { return mt_row_words(norm, dim); }
 
-extern "C" int mi_degensac_match_guided_knn2_batch_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
-                                                       const int64_t *offsets2_host, int n_pairs, int dim, const double *d_kp1, const double *d_kp2,
-                                                       int kp_dim, const double *d_models, const mi_degensac_guide_params *gp, int device, void *stream,
-                                                       int32_t *d_idx, float *d_dist)
+/* the guided 2-NN of a ragged batch; fginn: then slot 1 by the FGINN rule at radius r */
+static int mg_knn2_batch_dev(int fginn, double r, int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
+                             const int64_t *offsets2_host, int n_pairs, int dim, const double *d_kp1, const double *d_kp2, int kp_dim,
+                             const double *d_models, const mi_degensac_guide_params *gp, int device, hipStream_t s, int32_t *d_idx, float *d_dist)
 {
     mt_gate g; int rc = mg_check(norm, dim, kp_dim, gp, offsets1_host, offsets2_host, n_pairs, &g); if (rc) return rc;
+    if (fginn) { rc = mg_check_radius(r); if (rc) return rc; }
     if (n_pairs == 0) return 0;
     const int64_t n1 = offsets1_host[n_pairs] - offsets1_host[0], n2 = offsets2_host[n_pairs] - offsets2_host[0];
     if (!d_models || (n1 > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist)) || (n2 > 0 && (!d_desc2 || !d_kp2))) return mg_einval("NULL argument");
@@ -358,17 +498,38 @@ extern "C" int mi_degensac_match_guided_knn2_batch_dev(int norm, const void *d_d
     const int words = mg_words(norm, dim);
     std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
     mt_ragged_rows(offsets1_host, offsets2_host, n_pairs, o1, o2, rows);
-    return mt_batch_guided_knn2(norm, words, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words,
-                                (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words, d_kp1 + (size_t)offsets1_host[0] * kp_dim,
-                                d_kp2 + (size_t)offsets2_host[0] * kp_dim, kp_dim, rows.data(), n_pairs, (int)n1, d_models, g, 0, device,
-                                (hipStream_t)stream, d_idx + 2 * offsets1_host[0], d_dist + 2 * offsets1_host[0]);
+    const uint32_t *q1 = (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words, *q2 = (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words;
+    const double *k1 = d_kp1 + (size_t)offsets1_host[0] * kp_dim, *k2 = d_kp2 + (size_t)offsets2_host[0] * kp_dim;
+    int32_t *idx = d_idx + 2 * offsets1_host[0]; float *dist = d_dist + 2 * offsets1_host[0];
+    rc = mt_batch_guided_knn2(norm, words, q1, q2, k1, k2, kp_dim, rows.data(), n_pairs, (int)n1, d_models, g, 0, device, s, idx, dist);
+    if (rc || !fginn) return rc;
+    return mt_batch_guided_fginn(norm, words, q1, q2, k1, k2, kp_dim, rows.data(), n_pairs, (int)n1, d_models, g, r, device, s, idx, dist);
+}
+
+extern "C" int mi_degensac_match_guided_knn2_batch_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
+                                                       const int64_t *offsets2_host, int n_pairs, int dim, const double *d_kp1, const double *d_kp2,
+                                                       int kp_dim, const double *d_models, const mi_degensac_guide_params *gp, int device, void *stream,
+                                                       int32_t *d_idx, float *d_dist)
+{
+    return mg_knn2_batch_dev(0, 0.0, norm, d_desc1, d_desc2, offsets1_host, offsets2_host, n_pairs, dim, d_kp1, d_kp2, kp_dim, d_models, gp, device,
+                             (hipStream_t)stream, d_idx, d_dist);
+}
+
+extern "C" int mi_degensac_match_guided_fginn_knn2_batch_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
+                                                             const int64_t *offsets2_host, int n_pairs, int dim, const double *d_kp1,
+                                                             const double *d_kp2, int kp_dim, const double *d_models,
+                                                             const mi_degensac_guide_params *gp, double spatial_th, int device, void *stream,
+                                                             int32_t *d_idx, float *d_dist)
+{
+    return mg_knn2_batch_dev(1, spatial_th, norm, d_desc1, d_desc2, offsets1_host, offsets2_host, n_pairs, dim, d_kp1, d_kp2, kp_dim, d_models, gp,
+                             device, (hipStream_t)stream, d_idx, d_dist);
 }
 
 /* The device path of both layouts, arguments checked and the device current: entry p's rows are rows[p], n_out output rows and n_back
  * rows of the reverse search in all; every pointer is already at its side's first row, idx / dist / match at the first output row. */
 static int mg_rows_dev(const mi_degensac_match_params *mp, const uint32_t *q1, const uint32_t *q2, const double *kp1, const double *kp2, int kd,
-                       const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t n_back, const double *d_models, const mt_gate &g, int device,
-                       hipStream_t s, int32_t *idx, float *dist, int32_t *match, int32_t *d_counts, int32_t *h_counts)
+                       const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t n_back, const double *d_models, const mt_gate &g,
+                       const mg_second &sn, int device, hipStream_t s, int32_t *idx, float *dist, int32_t *match, int32_t *d_counts, int32_t *h_counts)
 {
     const int K = (int)rows.size();
     const int words = mg_words(mp->norm, mp->dim);
@@ -389,6 +550,9 @@ static int mg_rows_dev(const mi_degensac_match_params *mp, const uint32_t *q1, c
     float *bdist = (float *)(blk + a_bdist);
     int rc = mt_batch_upload(device, s, o32.data(), o32.size() * 4, blk); if (rc) return rc;
     rc = mt_batch_guided_knn2(mp->norm, words, q1, q2, kp1, kp2, kd, rows.data(), K, (int)n_out, d_models, g, 0, device, s, idx, dist); if (rc) return rc;
+    /* FGINN inside the gate judges the forward search only: the reverse search and the mutual check stay the plain ones (slot 0) */
+    if (sn.fginn) { rc = mt_batch_guided_fginn(mp->norm, words, q1, q2, kp1, kp2, kd, rows.data(), K, (int)n_out, d_models, g, sn.r, device, s, idx, dist);
+        if (rc) return rc; }
     if (mutual) { rc = mt_batch_guided_knn2(mp->norm, words, q2, q1, kp2, kp1, kd, rows.data(), K, (int)n_back, d_models, g, 1, device, s, bidx, bdist);
         if (rc) return rc; }
     rc = mt_batch_guided_decide(idx, dist, d_out, d_back, K, mp->ratio, bidx, s, match, cnt); if (rc) return rc;
@@ -399,12 +563,13 @@ static int mg_rows_dev(const mi_degensac_match_params *mp, const uint32_t *q1, c
     return 0;
 }
 
-static int mg_batch_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const int64_t *off1, const int64_t *off2,
+static int mg_batch_dev(int honour, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const int64_t *off1, const int64_t *off2,
                         const double *d_kp1, const double *d_kp2, int kd, int K, const double *d_models, const mi_degensac_guide_params *gp, int device,
                         hipStream_t s, int32_t *d_idx, float *d_dist, int32_t *d_match, int32_t *d_counts, int32_t *h_counts)
 {
     int rc = mg_check_ratio(mp); if (rc) return rc;
     mt_gate g; rc = mg_check(mp->norm, mp->dim, kd, gp, off1, off2, K, &g); if (rc) return rc;
+    mg_second sn; rc = mg_check_second(mp, honour, &sn); if (rc) return rc;
     if (K == 0) return 0;
     const int64_t n1 = off1[K] - off1[0], n2 = off2[K] - off2[0];
     if (!d_models || (n1 > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist || !d_match)) || (n2 > 0 && (!d_desc2 || !d_kp2))) return mg_einval("NULL argument");
@@ -413,7 +578,7 @@ static int mg_batch_dev(const mi_degensac_match_params *mp, const void *d_desc1,
     std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
     mt_ragged_rows(off1, off2, K, o1, o2, rows);
     return mg_rows_dev(mp, (const uint32_t *)d_desc1 + (size_t)off1[0] * words, (const uint32_t *)d_desc2 + (size_t)off2[0] * words,
-                       d_kp1 + (size_t)off1[0] * kd, d_kp2 + (size_t)off2[0] * kd, kd, rows, n1, n2, d_models, g, device, s, d_idx + 2 * off1[0],
+                       d_kp1 + (size_t)off1[0] * kd, d_kp2 + (size_t)off2[0] * kd, kd, rows, n1, n2, d_models, g, sn, device, s, d_idx + 2 * off1[0],
                        d_dist + 2 * off1[0], d_match + off1[0], d_counts, h_counts);
 }
 
@@ -422,7 +587,17 @@ extern "C" int mi_degensac_match_guided_batch_dev(const mi_degensac_match_params
                                                   const double *d_models, const mi_degensac_guide_params *gp, int device, void *stream, int32_t *d_idx,
                                                   float *d_dist, int32_t *d_match, int32_t *d_counts, int32_t *h_counts)
 {
-    return mg_batch_dev(mp, d_desc1, d_desc2, offsets1_host, offsets2_host, d_kp1, d_kp2, kp_dim, n_pairs, d_models, gp, device, (hipStream_t)stream,
+    return mg_batch_dev(0, mp, d_desc1, d_desc2, offsets1_host, offsets2_host, d_kp1, d_kp2, kp_dim, n_pairs, d_models, gp, device, (hipStream_t)stream,
+                        d_idx, d_dist, d_match, d_counts, h_counts);
+}
+
+extern "C" int mi_degensac_match_guided_fginn_batch_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
+                                                        const int64_t *offsets1_host, const int64_t *offsets2_host, const double *d_kp1,
+                                                        const double *d_kp2, int kp_dim, int n_pairs, const double *d_models,
+                                                        const mi_degensac_guide_params *gp, int device, void *stream, int32_t *d_idx, float *d_dist,
+                                                        int32_t *d_match, int32_t *d_counts, int32_t *h_counts)
+{
+    return mg_batch_dev(1, mp, d_desc1, d_desc2, offsets1_host, offsets2_host, d_kp1, d_kp2, kp_dim, n_pairs, d_models, gp, device, (hipStream_t)stream,
                         d_idx, d_dist, d_match, d_counts, h_counts);
 }
 
@@ -431,7 +606,8 @@ extern "C" int mi_degensac_match_guided_batch_dev(const mi_degensac_match_params
  * output row) come back. */
 static int mg_rows_host(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *off1, int m1, const int64_t *off2,
                         int m2, const double *kp1, const double *kp2, int kd, bool same, const std::vector<mt_pair_rows> &rows, int64_t n_out,
-                        int64_t n_back, const double *models, const mt_gate &g, int device, int32_t *idx, float *dist, int32_t *match, int32_t *counts)
+                        int64_t n_back, const double *models, const mt_gate &g, const mg_second &sn, int device, int32_t *idx, float *dist, int32_t *match,
+                        int32_t *counts)
 {
     const int K = (int)rows.size();
     MgDevGuard dg; int rc = dg.enter(device); if (rc) return rc;
@@ -453,7 +629,7 @@ static int mg_rows_host(const mi_degensac_match_params *mp, const void *desc1, c
     MGCHK(hipMemcpy(D + a_mo, models, (size_t)K * 72, hipMemcpyHostToDevice));
     std::vector<int32_t> cnt(K);
     rc = mg_rows_dev(mp, (const uint32_t *)D, (const uint32_t *)(same ? D : D + a_d2), (const double *)(D + a_k1), (const double *)(D + (same ? a_k1 : a_k2)),
-                     kd, rows, n_out, n_back, (const double *)(D + a_mo), g, device, nullptr, (int32_t *)(D + a_ix), (float *)(D + a_ds),
+                     kd, rows, n_out, n_back, (const double *)(D + a_mo), g, sn, device, nullptr, (int32_t *)(D + a_ix), (float *)(D + a_ds),
                      (int32_t *)(D + a_ma), nullptr, cnt.data());
     if (rc) return rc;
     MGCHK(hipStreamSynchronize(nullptr));
@@ -466,72 +642,129 @@ static int mg_rows_host(const mi_degensac_match_params *mp, const void *desc1, c
 
 /* host pointers: stage, run the device path on the null stream, copy back.  The ragged batch never asks whether its two sides are the
  * same arrays: both are uploaded */
-extern "C" int mi_degensac_match_guided_batch(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
-                                              const int64_t *offsets2, const double *kp1, const double *kp2, int kp_dim, int n_pairs, const double *models,
-                                              const mi_degensac_guide_params *gp, int device, int32_t *idx, float *dist, int32_t *match, int32_t *counts)
+static int mg_batch_host(int honour, const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
+                         const int64_t *offsets2, const double *kp1, const double *kp2, int kp_dim, int n_pairs, const double *models,
+                         const mi_degensac_guide_params *gp, int device, int32_t *idx, float *dist, int32_t *match, int32_t *counts)
 {
     int rc = mg_check_ratio(mp); if (rc) return rc;
     mt_gate g; rc = mg_check(mp->norm, mp->dim, kp_dim, gp, offsets1, offsets2, n_pairs, &g); if (rc) return rc;
+    mg_second sn; rc = mg_check_second(mp, honour, &sn); if (rc) return rc;
     const int K = n_pairs;
     if (K == 0) return 0;
     if (!desc1 || !desc2 || !kp1 || !kp2 || !models || !idx || !dist || !match) return mg_einval("NULL argument");
     std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
     mt_ragged_rows(offsets1, offsets2, K, o1, o2, rows);
-    return mg_rows_host(mp, desc1, desc2, offsets1, K, offsets2, K, kp1, kp2, kp_dim, false, rows, o1[K], o2[K], models, g, device,
+    return mg_rows_host(mp, desc1, desc2, offsets1, K, offsets2, K, kp1, kp2, kp_dim, false, rows, o1[K], o2[K], models, g, sn, device,
                         idx + 2 * offsets1[0], dist + 2 * offsets1[0], match + offsets1[0], counts);
+}
+
+extern "C" int mi_degensac_match_guided_batch(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
+                                              const int64_t *offsets2, const double *kp1, const double *kp2, int kp_dim, int n_pairs, const double *models,
+                                              const mi_degensac_guide_params *gp, int device, int32_t *idx, float *dist, int32_t *match, int32_t *counts)
+{
+    return mg_batch_host(0, mp, desc1, desc2, offsets1, offsets2, kp1, kp2, kp_dim, n_pairs, models, gp, device, idx, dist, match, counts);
+}
+
+extern "C" int mi_degensac_match_guided_fginn_batch(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
+                                                    const int64_t *offsets2, const double *kp1, const double *kp2, int kp_dim, int n_pairs,
+                                                    const double *models, const mi_degensac_guide_params *gp, int device, int32_t *idx, float *dist,
+                                                    int32_t *match, int32_t *counts)
+{
+    return mg_batch_host(1, mp, desc1, desc2, offsets1, offsets2, kp1, kp2, kp_dim, n_pairs, models, gp, device, idx, dist, match, counts);
 }
 
 /* ---- guided matching over a pair list (include/mi_degensac.h mi_degensac_match_guided_*_pairs*) -------------------------------
  * The same path with descriptors and keypoints stored once per image: mt_pairs_layout fills the rows from the stores' offsets and the
  * (i, j) list, where the ragged batch takes the identity list over its own offsets; everything after the layout step is shared. */
+static int mg_knn2_pairs_dev(int fginn, double r, int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host, int n_images1,
+                             const int64_t *offsets2_host, int n_images2, const int32_t *pairs_host, int n_pairs, int dim, const double *d_kp1,
+                             const double *d_kp2, int kp_dim, const double *d_models, const mi_degensac_guide_params *gp, int device, hipStream_t s,
+                             int32_t *d_idx, float *d_dist)
+{
+    mt_gate g; std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
+    int rc = mg_check_pairs(norm, dim, kp_dim, gp, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, &g, rows, &n_out, &n_back);
+    if (rc) return rc;
+    if (fginn) { rc = mg_check_radius(r); if (rc) return rc; }
+    if (n_pairs == 0) return 0;
+    if (!d_models || (n_out > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist)) || (n_back > 0 && (!d_desc2 || !d_kp2))) return mg_einval("NULL argument");
+    MgDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+    const int words = mg_words(norm, dim);
+    const uint32_t *q1 = (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words, *q2 = (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words;
+    const double *k1 = d_kp1 + (size_t)offsets1_host[0] * kp_dim, *k2 = d_kp2 + (size_t)offsets2_host[0] * kp_dim;
+    rc = mt_batch_guided_knn2(norm, words, q1, q2, k1, k2, kp_dim, rows.data(), n_pairs, (int)n_out, d_models, g, 0, device, s, d_idx, d_dist);
+    if (rc || !fginn) return rc;
+    return mt_batch_guided_fginn(norm, words, q1, q2, k1, k2, kp_dim, rows.data(), n_pairs, (int)n_out, d_models, g, r, device, s, d_idx, d_dist);
+}
+
 extern "C" int mi_degensac_match_guided_knn2_pairs_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host, int n_images1,
                                                        const int64_t *offsets2_host, int n_images2, const int32_t *pairs_host, int n_pairs, int dim,
                                                        const double *d_kp1, const double *d_kp2, int kp_dim, const double *d_models,
                                                        const mi_degensac_guide_params *gp, int device, void *stream, int32_t *d_idx, float *d_dist)
 {
-    mt_gate g; std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
-    int rc = mg_check_pairs(norm, dim, kp_dim, gp, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, &g, rows, &n_out, &n_back);
-    if (rc || n_pairs == 0) return rc;
-    if (!d_models || (n_out > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist)) || (n_back > 0 && (!d_desc2 || !d_kp2))) return mg_einval("NULL argument");
-    MgDevGuard dg; rc = dg.enter(device); if (rc) return rc;
-    const int words = mg_words(norm, dim);
-    return mt_batch_guided_knn2(norm, words, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words,
-                                (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words, d_kp1 + (size_t)offsets1_host[0] * kp_dim,
-                                d_kp2 + (size_t)offsets2_host[0] * kp_dim, kp_dim, rows.data(), n_pairs, (int)n_out, d_models, g, 0, device,
-                                (hipStream_t)stream, d_idx, d_dist);
+    return mg_knn2_pairs_dev(0, 0.0, norm, d_desc1, d_desc2, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, dim, d_kp1, d_kp2,
+                             kp_dim, d_models, gp, device, (hipStream_t)stream, d_idx, d_dist);
 }
 
-extern "C" int mi_degensac_match_guided_pairs_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
-                                                  const int64_t *offsets1_host, int n_images1, const int64_t *offsets2_host, int n_images2,
-                                                  const int32_t *pairs_host, int n_pairs, const double *d_kp1, const double *d_kp2, int kp_dim,
-                                                  const double *d_models, const mi_degensac_guide_params *gp, int device, void *stream, int32_t *d_idx,
-                                                  float *d_dist, int32_t *d_match, int32_t *d_counts, int32_t *h_counts)
+extern "C" int mi_degensac_match_guided_fginn_knn2_pairs_dev(int norm, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
+                                                             int n_images1, const int64_t *offsets2_host, int n_images2, const int32_t *pairs_host,
+                                                             int n_pairs, int dim, const double *d_kp1, const double *d_kp2, int kp_dim,
+                                                             const double *d_models, const mi_degensac_guide_params *gp, double spatial_th, int device,
+                                                             void *stream, int32_t *d_idx, float *d_dist)
+{
+    return mg_knn2_pairs_dev(1, spatial_th, norm, d_desc1, d_desc2, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, dim, d_kp1,
+                             d_kp2, kp_dim, d_models, gp, device, (hipStream_t)stream, d_idx, d_dist);
+}
+
+static int mg_pairs_dev(int honour, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host,
+                        int n_images1, const int64_t *offsets2_host, int n_images2, const int32_t *pairs_host, int n_pairs, const double *d_kp1,
+                        const double *d_kp2, int kp_dim, const double *d_models, const mi_degensac_guide_params *gp, int device, hipStream_t s,
+                        int32_t *d_idx, float *d_dist, int32_t *d_match, int32_t *d_counts, int32_t *h_counts)
 {
     int rc = mg_check_ratio(mp); if (rc) return rc;
     mt_gate g; std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
     rc = mg_check_pairs(mp->norm, mp->dim, kp_dim, gp, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, &g, rows, &n_out, &n_back);
-    if (rc || n_pairs == 0) return rc;
+    if (rc) return rc;
+    mg_second sn; rc = mg_check_second(mp, honour, &sn); if (rc) return rc;
+    if (n_pairs == 0) return 0;
     if (!d_models || (n_out > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist || !d_match)) || (n_back > 0 && (!d_desc2 || !d_kp2)))
         return mg_einval("NULL argument");
     MgDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     const int words = mg_words(mp->norm, mp->dim);
     return mg_rows_dev(mp, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words, (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words,
-                       d_kp1 + (size_t)offsets1_host[0] * kp_dim, d_kp2 + (size_t)offsets2_host[0] * kp_dim, kp_dim, rows, n_out, n_back, d_models, g,
-                       device, (hipStream_t)stream, d_idx, d_dist, d_match, d_counts, h_counts);
+                       d_kp1 + (size_t)offsets1_host[0] * kp_dim, d_kp2 + (size_t)offsets2_host[0] * kp_dim, kp_dim, rows, n_out, n_back, d_models, g, sn,
+                       device, s, d_idx, d_dist, d_match, d_counts, h_counts);
 }
 
 /* each store goes to the device once: one copy when both sides name the same arrays */
-extern "C" int mi_degensac_match_guided_pairs(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
-                                              int n_images1, const int64_t *offsets2, int n_images2, const int32_t *pairs, int n_pairs, const double *kp1,
-                                              const double *kp2, int kp_dim, const double *models, const mi_degensac_guide_params *gp, int device,
-                                              int32_t *idx, float *dist, int32_t *match, int32_t *counts)
+static int mg_pairs_host(int honour, const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1, int n_images1,
+                         const int64_t *offsets2, int n_images2, const int32_t *pairs, int n_pairs, const double *kp1, const double *kp2, int kp_dim,
+                         const double *models, const mi_degensac_guide_params *gp, int device, int32_t *idx, float *dist, int32_t *match, int32_t *counts)
 {
     int rc = mg_check_ratio(mp); if (rc) return rc;
     mt_gate g; std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
     rc = mg_check_pairs(mp->norm, mp->dim, kp_dim, gp, offsets1, n_images1, offsets2, n_images2, pairs, n_pairs, &g, rows, &n_out, &n_back);
-    if (rc || n_pairs == 0) return rc;
+    if (rc) return rc;
+    mg_second sn; rc = mg_check_second(mp, honour, &sn); if (rc) return rc;
+    if (n_pairs == 0) return 0;
     if (!desc1 || !desc2 || !kp1 || !kp2 || !models || !idx || !dist || !match) return mg_einval("NULL argument");
     const bool same = desc1 == desc2 && kp1 == kp2 && n_images1 == n_images2 && !memcmp(offsets1, offsets2, ((size_t)n_images1 + 1) * 8);
-    return mg_rows_host(mp, desc1, desc2, offsets1, n_images1, offsets2, n_images2, kp1, kp2, kp_dim, same, rows, n_out, n_back, models, g, device,
+    return mg_rows_host(mp, desc1, desc2, offsets1, n_images1, offsets2, n_images2, kp1, kp2, kp_dim, same, rows, n_out, n_back, models, g, sn, device,
                         idx, dist, match, counts);
 }
+
+#define MG_PAIRS_DEV_ARGS const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host, int n_images1, \
+    const int64_t *offsets2_host, int n_images2, const int32_t *pairs_host, int n_pairs, const double *d_kp1, const double *d_kp2, int kp_dim, \
+    const double *d_models, const mi_degensac_guide_params *gp, int device, void *stream, int32_t *d_idx, float *d_dist, int32_t *d_match, \
+    int32_t *d_counts, int32_t *h_counts
+#define MG_PAIRS_DEV_PASS mp, d_desc1, d_desc2, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, d_kp1, d_kp2, kp_dim, d_models, gp, \
+    device, (hipStream_t)stream, d_idx, d_dist, d_match, d_counts, h_counts
+extern "C" int mi_degensac_match_guided_pairs_dev(MG_PAIRS_DEV_ARGS) { return mg_pairs_dev(0, MG_PAIRS_DEV_PASS); }
+extern "C" int mi_degensac_match_guided_fginn_pairs_dev(MG_PAIRS_DEV_ARGS) { return mg_pairs_dev(1, MG_PAIRS_DEV_PASS); }
+
+#define MG_PAIRS_HOST_ARGS const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1, int n_images1, \
+    const int64_t *offsets2, int n_images2, const int32_t *pairs, int n_pairs, const double *kp1, const double *kp2, int kp_dim, const double *models, \
+    const mi_degensac_guide_params *gp, int device, int32_t *idx, float *dist, int32_t *match, int32_t *counts
+#define MG_PAIRS_HOST_PASS mp, desc1, desc2, offsets1, n_images1, offsets2, n_images2, pairs, n_pairs, kp1, kp2, kp_dim, models, gp, device, idx, dist, match, \
+    counts
+extern "C" int mi_degensac_match_guided_pairs(MG_PAIRS_HOST_ARGS) { return mg_pairs_host(0, MG_PAIRS_HOST_PASS); }
+extern "C" int mi_degensac_match_guided_fginn_pairs(MG_PAIRS_HOST_ARGS) { return mg_pairs_host(1, MG_PAIRS_HOST_PASS); }

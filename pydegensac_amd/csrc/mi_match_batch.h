@@ -99,6 +99,11 @@ MT_HIDDEN int mt_batch_knn2(int norm, int words, const void *dq, const void *dt,
  * synchronisation */
 MT_HIDDEN int mt_batch_fginn(int norm, int words, const void *dq, const void *dt, const double *kt, int kd, const mt_pair_rows *rows, int n_pairs,
                              int n_rows, double r, int device, hipStream_t s, int32_t *idx, float *dist);
+/* the mark pass of FGINN alone, for any stage whose result lists have the matcher's layout: per entry (d_rows [K] on the device) the
+ * queries whose slot 1 exists and does not compete with slot 0 at squared radius rr, as OUTPUT rows in ascending order to
+ * list[out ..], their number to count[p]; no host synchronisation */
+MT_HIDDEN int mt_batch_fginn_mark(const int32_t *idx, const mt_pair_rows *d_rows, int n_pairs, const double *kt, int kd, double rr, hipStream_t s,
+                                  int32_t *list, int32_t *count);
 /* ratio test (+ mutual check when d_back is set) and the rank of every kept query among its pair's kept queries; one
  * workgroup per pair.  d_off1 / d_off2: [K + 1] relative int32 row offsets on the device.  d_off1 says where the pair's idx / dist /
  * keep / rank rows are (the `out` column and the total), d_off2[p] (the only entry read) where its rows of d_back start (the `back`
@@ -132,6 +137,11 @@ MT_HIDDEN int mt_guided_gate(int homography, int error_type, double px_th, mt_ga
 MT_HIDDEN int mt_batch_guided_knn2(int norm, int words, const void *dq, const void *dt, const double *kq, const double *kt, int kd,
                                    const mt_pair_rows *rows, int n_pairs, int n_rows, const double *d_models, const mt_gate &g, int swap, int device,
                                    hipStream_t s, int32_t *idx, float *dist);
+/* FGINN inside the gate: after mt_batch_guided_knn2 (swap = 0) over the same rows, models and gate on s, slot 1 of idx / dist becomes the
+ * nearest GATED train row whose keypoint lies at least r from the keypoint of slot 0 (-1 / inf when none does); no host synchronisation */
+MT_HIDDEN int mt_batch_guided_fginn(int norm, int words, const void *dq, const void *dt, const double *kq, const double *kt, int kd,
+                                    const mt_pair_rows *rows, int n_pairs, int n_rows, const double *d_models, const mt_gate &g, double r, int device,
+                                    hipStream_t s, int32_t *idx, float *dist);
 /* the decision: match[i] = idx[i][0] when it exists and dist[i][0] < ratio * dist[i][1] (and back[b2 + idx[i][0]][0] == i - lo when
  * d_back is set), else -1; count[p] (nullable) = guided matches of pair p.  d_off1 [K + 1]: the output-row offsets (the `out` column and
  * the total), d_off2[p] (the only entry read): where the pair's rows of d_back start (the `back` column), as for mt_batch_filter_rank */

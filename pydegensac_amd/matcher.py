@@ -278,6 +278,12 @@ def check_fginn_th(fginn_th, name="fginn_th"):
     return r
 
 
+def guided_entry(layout, fginn_r):
+    """the guided entry point of a layout ("batch_dev", "batch", "pairs_dev", "pairs"): fginn_r None = the plain call, a checked radius =
+    the call that honours second_nn / spatial_th of its match params (FGINN inside the gate)"""
+    return getattr(_lib.lib(), f"mi_degensac_match_guided_{'' if fginn_r is None else 'fginn_'}{layout}")
+
+
 def estimator_params(model, px_th=None, conf=None, max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
                      enable_degeneracy_check=True):
     """mi_degensac_params of findFundamentalMatrix / findHomography with their defaults where an argument is None"""
@@ -286,6 +292,16 @@ def estimator_params(model, px_th=None, conf=None, max_iters=None, laf_consisten
     et = _error_type(error_type_dict_fundamental if model == "F" else error_type_dict_homography, error_type)
     return _lib.make_params(d[0] if px_th is None else px_th, d[1] if conf is None else conf, d[2] if max_iters is None else max_iters, et,
                             symmetric_error_check, max(0.0, laf_consistensy_coef), enable_degeneracy_check if model == "F" else True)
+
+
+def check_guided_fginn_th(guided, guided_fginn_th):
+    """guided_fginn_th of the match-and-verify calls: None, or (only with guided=True) the checked radius; raises ValueError"""
+    if guided_fginn_th is None:
+        return None
+    if not guided:
+        raise ValueError("guided_fginn_th is the FGINN radius of the guided stage: pass guided=True with it (fginn_th is the radius of "
+                         "the tentatives in front of the estimator)")
+    return check_fginn_th(guided_fginn_th, "guided_fginn_th")
 
 
 def check_guided_args(model, px_th, error_type, models_shape, models_dtype, K):
@@ -368,38 +384,44 @@ def _finish_pairs(code, kind, A, B, K1, K2, device):
     return A, B, np.ascontiguousarray(K1, np.float64), np.ascontiguousarray(K2, np.float64)
 
 
-def _guided_host(code, A, B, K1, K2, o1, o2, Md, model, ratio, mutual, px, et, device):
-    """mi_degensac_match_guided_batch on prepared host arrays; Md = [K, 9] driver-form models.  Returns (match, idx, dist, counts)."""
+def _guided_host(code, A, B, K1, K2, o1, o2, Md, model, ratio, mutual, px, et, device, fginn_r=None):
+    """mi_degensac_match_guided_batch (fginn_r, a checked radius: mi_degensac_match_guided_fginn_batch) on prepared host arrays; Md =
+    [K, 9] driver-form models.  Returns (match, idx, dist, counts)."""
     K = len(o1) - 1; n1 = A.shape[0]
     idx = np.full((n1, 2), -1, np.int32); dist = np.full((n1, 2), np.inf, np.float32); match = np.full(n1, -1, np.int32)
     cnt = np.zeros(K, np.int32)
     Md = np.ascontiguousarray(Md, np.float64).reshape(K, 9)
-    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual); gp = _lib.GuideParams(model == "H", et, px)
-    rc = _lib.lib().mi_degensac_match_guided_batch(C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p),
-                                                   o1.ctypes.data_as(C.POINTER(C.c_int64)), o2.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                   _lib.dptr(K1), _lib.dptr(K2), K1.shape[1], K, _lib.dptr(Md), C.byref(gp), int(device),
-                                                   idx.ctypes.data_as(C.POINTER(C.c_int32)), dist.ctypes.data_as(C.POINTER(C.c_float)),
-                                                   match.ctypes.data_as(C.POINTER(C.c_int32)), cnt.ctypes.data_as(C.POINTER(C.c_int32)))
+    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual, fginn_r); gp = _lib.GuideParams(model == "H", et, px)
+    rc = guided_entry("batch", fginn_r)(C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p),
+                                        o1.ctypes.data_as(C.POINTER(C.c_int64)), o2.ctypes.data_as(C.POINTER(C.c_int64)),
+                                        _lib.dptr(K1), _lib.dptr(K2), K1.shape[1], K, _lib.dptr(Md), C.byref(gp), int(device),
+                                        idx.ctypes.data_as(C.POINTER(C.c_int32)), dist.ctypes.data_as(C.POINTER(C.c_float)),
+                                        match.ctypes.data_as(C.POINTER(C.c_int32)), cnt.ctypes.data_as(C.POINTER(C.c_int32)))
     _lib.check_match(rc)
     return match, idx, dist, cnt
 
 
 def guided_match_batch(kps1_list, kps2_list, desc1_list, desc2_list, models, model="F", ratio=0.9, mutual=False, px_th=None,
-                       error_type="sampson", norm=None, driver_form=False, device=0):
+                       error_type="sampson", norm=None, driver_form=False, device=0, fginn_th=None):
     """Guided matching of K image pairs in one call: per pair the 2-NN search restricted to the train keypoints that are inliers of
     the pair's model (models [K, 3, 3] float64: F, or the user-facing H that findHomography returns; driver_form=True takes them in the
     driver's form, H_c = inv(H)^T), with the estimator's residual for error_type and its threshold from px_th (None = the model's
     default, 0.5 for F, 1.0 for H).  The ratio test then keeps a query whose nearest gated row is closer than ratio times the second;
     a query with a single gated row passes (nothing competes with it).  A zero model gives its pair no matches.  Arrays as for
     match_and_verify_batch.  Returns per pair (query indices, train indices, distances) in query order, like match_snn.
-    A gate that lets everything through (a huge px_th) is correct but slower than the unguided matcher."""
+    A gate that lets everything through (a huge px_th) is correct but slower than the unguided matcher.
+    fginn_th: None = the second gated row decides; a number (pixels of kps2, finite and >= 0) takes the second distance from the nearest
+    GATED row whose keypoint lies at least that far from the nearest gated row's (FGINN inside the gate), so a keypoint's own twin (a
+    second orientation, a neighbouring scale), which lies inside the band too, no longer fails the ratio test.  A query whose only gated
+    companions lie inside the radius is KEPT (dist1 = inf: nothing competes with it), unlike match_fginn, which needs a second row."""
     code, kind, A, B, K1, K2, o1, o2 = _stack_pairs(kps1_list, kps2_list, desc1_list, desc2_list, model, ratio, norm, device)
     K = len(o1) - 1
     M = np.asarray(models)
     px, et = check_guided_args(model, px_th, error_type, M.shape, M.dtype, K)
+    fr = None if fginn_th is None else check_fginn_th(fginn_th)
     A, B, K1, K2 = _finish_pairs(code, kind, A, B, K1, K2, device)
     Md = M if (model == "F" or driver_form) else _h_driver_form(M)
-    match, _, dist, _ = _guided_host(code, A, B, K1, K2, o1, o2, Md, model, ratio, mutual, px, et, device)
+    match, _, dist, _ = _guided_host(code, A, B, K1, K2, o1, o2, Md, model, ratio, mutual, px, et, device, fr)
     out = []
     for p in range(K):
         m = match[o1[p]:o1[p + 1]]
@@ -409,15 +431,16 @@ def guided_match_batch(kps1_list, kps2_list, desc1_list, desc2_list, models, mod
 
 
 def guided_match(kps1, kps2, desc1, desc2, M, model="F", ratio=0.9, mutual=False, px_th=None, error_type="sampson", norm=None,
-                 driver_form=False, device=0):
-    """guided_match_batch for one pair: (query indices, train indices, distances) of the guided matches under model M [3, 3]"""
+                 driver_form=False, device=0, fginn_th=None):
+    """guided_match_batch for one pair: (query indices, train indices, distances) of the guided matches under model M [3, 3];
+    fginn_th as there (FGINN inside the gate; a query whose only gated companions are its twins is kept)"""
     return guided_match_batch([kps1], [kps2], [desc1], [desc2], np.asarray(M)[None], model, ratio, mutual, px_th, error_type, norm,
-                              driver_form, device)[0]
+                              driver_form, device, fginn_th)[0]
 
 
 def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
                            max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
-                           enable_degeneracy_check=True, seeds=None, norm=None, device=0, guided=False, fginn_th=None):
+                           enable_degeneracy_check=True, seeds=None, norm=None, device=0, guided=False, fginn_th=None, guided_fginn_th=None):
     """K image pairs from descriptors and keypoints to models in one call: per pair the 2-NN ratio test of match_snn (optionally
     mutual), then findFundamentalMatrix (model "F") or findHomography ("H") on its tentatives, all pairs in one launch.  kps are
     float64 [n, 2] / [n, 6] rows or float32 [n, 4] keypoints (x, y, size, angle -> LAF rows as kpts_to_xyA); descriptors float32
@@ -429,7 +452,9 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
     px_th / error_type / ratio / mutual, and adds a fourth element [guided_p]: the guided match of every query or -1.
     fginn_th: None = the plain ratio test; a number switches it to the FGINN ratio test of match_fginn at that radius in pixels of
     kps2 (the guided stage keeps its own gate and decision).
+    guided_fginn_th: None, or the radius of guided_match_batch(fginn_th=) for the guided stage; only with guided=True (ValueError else).
     last_stats() holds the per-pair statistics, with "tentatives"."""
+    gfr = check_guided_fginn_th(guided, guided_fginn_th)
     code, kind, A, B, K1, K2, o1, o2 = _stack_pairs(kps1_list, kps2_list, desc1_list, desc2_list, model, ratio, norm, device, fginn_th)
     K = len(o1) - 1
     prm = estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
@@ -449,7 +474,7 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
     _set_last_stats(st, cnt)
     gm = None
     if guided:                  # the driver-form models as the library wrote them, before the inversion below
-        gm = _guided_host(code, A, B, K1, K2, o1, o2, M, model, ratio, mutual, prm.px_th, prm.error_type, device)[0]
+        gm = _guided_host(code, A, B, K1, K2, o1, o2, M, model, ratio, mutual, prm.px_th, prm.error_type, device, gfr)[0]
     M = M.reshape(K, 3, 3)
     if model == "H":
         M = _h_user_form(M)
@@ -554,30 +579,33 @@ def _match_verify_pairs(fginn_r, kps_list, desc_list, pairs, model, ratio, mutua
 
 
 def guided_match_pairs(kps_list, desc_list, pairs, models, model="F", ratio=0.9, mutual=False, px_th=None, error_type="sampson", norm=None,
-                       driver_form=False, device=0, kps2_list=None, desc2_list=None):
+                       driver_form=False, device=0, kps2_list=None, desc2_list=None, fginn_th=None):
     """guided_match_batch over a pair list: descriptors and keypoints are given ONCE per image, pairs [K, 2] says which (i, j) to run and
     models [K, 3, 3] float64 holds one model per LIST ENTRY (the same (i, j) may appear twice with two models) — what
     match_and_verify_pairs returned for the same list goes in as it is: F, or the user-facing H (driver_form=True: H_c = inv(H)^T).  Stores
     as for match_and_verify_pairs: kps2_list / desc2_list name a second store for the train images, each store is uploaded once and no
     row is copied per pair.  Per entry the result is bit for bit that of guided_match_batch on the entry's copied arrays.  Returns per
-    list entry (query indices, train indices, distances) in query order; train indices are local to image j."""
+    list entry (query indices, train indices, distances) in query order; train indices are local to image j.
+    fginn_th as in guided_match_batch (FGINN inside the gate on the keypoints of the entry's train image; a query whose only gated
+    companions lie inside the radius is kept)."""
     (A, K1, c1), (B, K2, c2), one = _stack_stores(kps_list, desc_list, kps2_list, desc2_list)
     code, kind, o1, o2, pr, po, _ = check_match_pairs_args(model, ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape,
                                                            K2.dtype, c1, c2, pairs)
     K = len(pr)
     M = np.asarray(models)
     px, et = check_guided_args(model, px_th, error_type, M.shape, M.dtype, K)
+    fr = None if fginn_th is None else check_fginn_th(fginn_th)
     A, K1, B, K2 = _finish_stores(code, kind, A, K1, B, K2, one, device)
     Md = np.ascontiguousarray(M if (model == "F" or driver_form) else _h_driver_form(M), np.float64).reshape(K, 9)
     n = int(po[-1])
     idx = np.full((n, 2), -1, np.int32); dist = np.full((n, 2), np.inf, np.float32); match = np.full(n, -1, np.int32)
     cnt = np.zeros(K, np.int32)
-    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual); gp = _lib.GuideParams(model == "H", et, px)
+    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual, fr); gp = _lib.GuideParams(model == "H", et, px)
     lp = C.POINTER(C.c_int64); ip = C.POINTER(C.c_int32)
-    rc = _lib.lib().mi_degensac_match_guided_pairs(C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), o1.ctypes.data_as(lp),
-                                                   len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, pr.ctypes.data_as(ip), K, _lib.dptr(K1),
-                                                   _lib.dptr(K2), K1.shape[1], _lib.dptr(Md), C.byref(gp), int(device), idx.ctypes.data_as(ip),
-                                                   dist.ctypes.data_as(C.POINTER(C.c_float)), match.ctypes.data_as(ip), cnt.ctypes.data_as(ip))
+    rc = guided_entry("pairs", fr)(C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), o1.ctypes.data_as(lp),
+                                   len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, pr.ctypes.data_as(ip), K, _lib.dptr(K1),
+                                   _lib.dptr(K2), K1.shape[1], _lib.dptr(Md), C.byref(gp), int(device), idx.ctypes.data_as(ip),
+                                   dist.ctypes.data_as(C.POINTER(C.c_float)), match.ctypes.data_as(ip), cnt.ctypes.data_as(ip))
     _lib.check_match(rc)
     out = []
     for p in range(K):

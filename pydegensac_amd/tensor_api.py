@@ -253,20 +253,22 @@ def knn_match_fginn_batch_tensors(desc1, desc2, kps2, counts1, counts2, spatial_
     return idx, dist
 
 
-def _guided_dev(code, a, b, k1, k2, o1, o2, Md, model, ratio, mutual, px, et):
-    """mi_degensac_match_guided_batch_dev on prepared device tensors (Md: [K, 9] driver-form models), asynchronous on the current
-    stream.  Returns (match [N1] int32, idx [N1, 2] int32, dist [N1, 2] float32)."""
+def _guided_dev(code, a, b, k1, k2, o1, o2, Md, model, ratio, mutual, px, et, fginn_r=None):
+    """mi_degensac_match_guided_batch_dev (fginn_r, a checked radius: mi_degensac_match_guided_fginn_batch_dev) on prepared device
+    tensors (Md: [K, 9] driver-form models), asynchronous on the current stream.  Returns (match [N1] int32, idx [N1, 2] int32,
+    dist [N1, 2] float32)."""
     import torch
+    from . import matcher
     dev = a.device; n1 = a.shape[0]; K = len(o1) - 1
     idx = torch.full((n1, 2), -1, dtype=torch.int32, device=dev)
     dist = torch.full((n1, 2), float("inf"), dtype=torch.float32, device=dev)
     match = torch.full((n1,), -1, dtype=torch.int32, device=dev)
-    mp = _lib.MatchParams(code, a.shape[1], ratio, mutual); gp = _lib.GuideParams(model == "H", et, px)
+    mp = _lib.MatchParams(code, a.shape[1], ratio, mutual, fginn_r); gp = _lib.GuideParams(model == "H", et, px)
     stream = torch.cuda.current_stream(dev)
-    rc = _lib.lib().mi_degensac_match_guided_batch_dev(C.byref(mp), a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                       o2.ctypes.data_as(C.POINTER(C.c_int64)), k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]), K,
-                                                       Md.data_ptr(), C.byref(gp), dev.index or 0, C.c_void_p(stream.cuda_stream), idx.data_ptr(),
-                                                       dist.data_ptr(), match.data_ptr(), None, None)
+    rc = matcher.guided_entry("batch_dev", fginn_r)(C.byref(mp), a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                    o2.ctypes.data_as(C.POINTER(C.c_int64)), k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]), K,
+                                                    Md.data_ptr(), C.byref(gp), dev.index or 0, C.c_void_p(stream.cuda_stream), idx.data_ptr(),
+                                                    dist.data_ptr(), match.data_ptr(), None, None)
     _lib.check_match(rc)
     for t in (a, b, k1, k2, Md):
         t.record_stream(stream)
@@ -284,7 +286,7 @@ def _h_driver_form(M):
 
 
 def guided_match_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, models, model="F", ratio=0.9, mutual=False, px_th=None,
-                               error_type="sampson", norm=None, driver_form=False):
+                               error_type="sampson", norm=None, driver_form=False, fginn_th=None):
     """Guided matching on the device (include/mi_degensac.h mi_degensac_match_guided_batch_dev): per pair the 2-NN search of
     knn_match_batch_tensors restricted to the train keypoints that are inliers of the pair's model under the estimator's own residual
     for error_type and its threshold from px_th (None = the model's default: 0.5 for F, 1.0 for H), then the ratio test (and, with
@@ -293,7 +295,13 @@ def guided_match_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model
     driver's form H_c = inv(H)^T without a host round trip); driver_form=True takes them as the *_batch_dev entry points write them.
     Keypoints and descriptors as for match_and_verify_batch_tensors.  Cost follows the rows that pass the gate; a gate that passes
     everything (a huge px_th) is correct but slower than the unguided matcher.  Returns (match [N1] int32 = pair-local train row or -1,
-    idx [N1, 2] int32, dist [N1, 2] float32) on the device, asynchronous on the current stream (no host synchronisation)."""
+    idx [N1, 2] int32, dist [N1, 2] float32) on the device, asynchronous on the current stream (no host synchronisation).
+    fginn_th: None = this call through mi_degensac_match_guided_batch_dev; a number (pixels of kps2, finite and >= 0) goes to
+    mi_degensac_match_guided_fginn_batch_dev: slot 1 of idx / dist becomes the nearest GATED train row whose keypoint lies at least that
+    far from the keypoint of slot 0 (FGINN inside the gate), so a keypoint's own twin inside the band (a second orientation, a
+    neighbouring scale) no longer fails the ratio test.  A query whose only gated companions lie inside the radius has dist1 = inf and
+    is KEPT (nothing competes with it) — not the rule of knn_match_fginn_batch_tensors, which needs a second row.  The reverse search
+    of mutual stays the plain one."""
     import torch
     from . import matcher
     ts = (kps1, kps2, desc1, desc2, models)
@@ -303,6 +311,7 @@ def guided_match_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model
                                                          tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype, counts1, counts2)
     K = len(o1) - 1
     px, et = matcher.check_guided_args(model, px_th, error_type, tuple(models.shape), models.dtype, K)
+    fr = None if fginn_th is None else matcher.check_fginn_th(fginn_th)
     if any(t.device != desc1.device for t in ts) or desc1.device.type != "cuda":
         raise ValueError("kps1, kps2, desc1, desc2 and models must live on the same ROCm device")
     a, b = _desc_pair(desc1, desc2)
@@ -313,7 +322,7 @@ def guided_match_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model
     M = models.contiguous()
     if model == "H" and not driver_form:
         M = _h_driver_form(M)
-    return _guided_dev(code, a, b, k1, k2, o1, o2, M.reshape(K, 9).contiguous(), model, ratio, mutual, px, et)
+    return _guided_dev(code, a, b, k1, k2, o1, o2, M.reshape(K, 9).contiguous(), model, ratio, mutual, px, et, fr)
 
 
 def _h_user_form(M):
@@ -356,7 +365,7 @@ def _match_verify_dev(entry, layout, model, mp, prm, a, b, k1, k2, sd, K, n, gui
 
 def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
                                    max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
-                                   enable_degeneracy_check=True, seeds=None, guided=False, norm=None, fginn_th=None):
+                                   enable_degeneracy_check=True, seeds=None, guided=False, norm=None, fginn_th=None, guided_fginn_th=None):
     """K image pairs from descriptors to models with ONE host synchronisation (the read of the per-pair tentative counts): per pair
     the 2-NN ratio test (`m.distance < ratio * n.distance`, optionally mutual) of match_snn_tensors, then the estimator of
     find_fundamental_batch_tensors (model "F") / find_homography_batch_tensors ("H") on its tentatives in query order.
@@ -371,9 +380,12 @@ def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, m
     memory (no conversion) and this call's px_th / error_type / ratio / mutual, and appends its match [N1] int32 (the guided match of
     every query or -1); the call still synchronises exactly once.
     fginn_th: None = the plain ratio test; a number switches it to the FGINN ratio test (knn_match_fginn_batch_tensors at that radius
-    on kps2's x, y).  Only the tentatives in front of the estimator change: the guided stage keeps its own gate and decision."""
+    on kps2's x, y).  Only the tentatives in front of the estimator change: the guided stage keeps its own gate and decision.
+    guided_fginn_th: None, or the radius of guided_match_batch_tensors(fginn_th=) for the guided stage (FGINN inside the gate; a query
+    whose only gated companions lie inside the radius is kept).  It is passed on only with guided=True and is a ValueError without it."""
     import torch
     from . import matcher
+    gfr = matcher.check_guided_fginn_th(guided, guided_fginn_th)
     ts = (kps1, kps2, desc1, desc2)
     if not all(isinstance(t, torch.Tensor) for t in ts):
         raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
@@ -390,7 +402,7 @@ def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, m
         k1 = kps1.contiguous(); k2 = kps2.contiguous()
     sd = matcher._seeds_u32(None if seeds is None else np.asarray(seeds).ravel(), K)
     lp = C.POINTER(C.c_int64)
-    guide = (lambda M: _guided_dev(code, a, b, k1, k2, o1, o2, M, model, ratio, mutual, prm.px_th, prm.error_type)[0]) if guided else None
+    guide = (lambda M: _guided_dev(code, a, b, k1, k2, o1, o2, M, model, ratio, mutual, prm.px_th, prm.error_type, gfr)[0]) if guided else None
     res = _match_verify_dev(_lib.lib().mi_degensac_match_verify_batch_dev, (o1.ctypes.data_as(lp), o2.ctypes.data_as(lp), k1.data_ptr(), k2.data_ptr(),
                                                                           int(k1.shape[1]), K),
                             model, _lib.MatchParams(code, a.shape[1], ratio, mutual, fginn_th), prm, a, b, k1, k2, sd, K, n1, guide)
@@ -526,7 +538,7 @@ def _match_verify_pairs_tensors(fginn_r, kps1, kps2, desc1, desc2, counts1, coun
 
 
 def guided_match_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs, models, model="F", ratio=0.9, mutual=False, px_th=None,
-                               error_type="sampson", norm=None, driver_form=False):
+                               error_type="sampson", norm=None, driver_form=False, fginn_th=None):
     """guided_match_batch_tensors over a pair list (include/mi_degensac.h mi_degensac_match_guided_pairs_dev): kps / desc are image stores
     (counts1 / counts2 rows per image; pass the same tensors on both sides for a collection matched against itself), pairs [K, 2] lists
     the (i, j) to run and models [K, 3, 3] float64 on the device holds one model per LIST ENTRY — what match_and_verify_pairs_tensors
@@ -536,7 +548,10 @@ def guided_match_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs
     per train row of the list.  Gate, decision and the zero-model rule as in guided_match_batch_tensors; per entry every output is bit for
     bit what that call returns on the entry's copied rows.  Returns (match [N] int32 = train row local to image j or -1, idx [N, 2]
     int32, dist [N, 2] float32, pair_offsets [K + 1] host int64) with N = pair_offsets[K]: entry p owns the rows pair_offsets[p] ..
-    pair_offsets[p + 1].  Asynchronous on the current stream (no host synchronisation)."""
+    pair_offsets[p + 1].  Asynchronous on the current stream (no host synchronisation).
+    fginn_th as in guided_match_batch_tensors, through mi_degensac_match_guided_fginn_pairs_dev: anchors and competitors are the
+    keypoints of the entry's train image in store 2; a needy query is rescanned through its image's rows in store 1 and answered at
+    its output row (two different rows in a list), nothing is copied.  A query whose only gated companions lie inside the radius is kept."""
     import torch
     from . import matcher
     ts = (kps1, kps2, desc1, desc2, models)
@@ -547,6 +562,7 @@ def guided_match_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs
                                                                    counts1, counts2, pairs)
     K = len(pr); n = int(po[-1])
     px, et = matcher.check_guided_args(model, px_th, error_type, tuple(models.shape), models.dtype, K)
+    fr = None if fginn_th is None else matcher.check_fginn_th(fginn_th)
     if any(t.device != desc1.device for t in ts) or desc1.device.type != "cuda":
         raise ValueError("kps1, kps2, desc1, desc2 and models must live on the same ROCm device")
     a, b = _desc_pair(desc1, desc2)
@@ -560,13 +576,13 @@ def guided_match_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs
     idx = torch.full((n, 2), -1, dtype=torch.int32, device=dev)
     dist = torch.full((n, 2), float("inf"), dtype=torch.float32, device=dev)
     match = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    mp = _lib.MatchParams(code, a.shape[1], ratio, mutual); gp = _lib.GuideParams(model == "H", et, px)
+    mp = _lib.MatchParams(code, a.shape[1], ratio, mutual, fr); gp = _lib.GuideParams(model == "H", et, px)
     stream = torch.cuda.current_stream(dev)
     lp = C.POINTER(C.c_int64)
-    rc = _lib.lib().mi_degensac_match_guided_pairs_dev(C.byref(mp), a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(lp), len(o1) - 1,
-                                                       o2.ctypes.data_as(lp), len(o2) - 1, pr.ctypes.data_as(C.POINTER(C.c_int32)), K, k1.data_ptr(),
-                                                       k2.data_ptr(), int(k1.shape[1]), M.data_ptr(), C.byref(gp), dev.index or 0,
-                                                       C.c_void_p(stream.cuda_stream), idx.data_ptr(), dist.data_ptr(), match.data_ptr(), None, None)
+    rc = matcher.guided_entry("pairs_dev", fr)(C.byref(mp), a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(lp), len(o1) - 1,
+                                               o2.ctypes.data_as(lp), len(o2) - 1, pr.ctypes.data_as(C.POINTER(C.c_int32)), K, k1.data_ptr(),
+                                               k2.data_ptr(), int(k1.shape[1]), M.data_ptr(), C.byref(gp), dev.index or 0,
+                                               C.c_void_p(stream.cuda_stream), idx.data_ptr(), dist.data_ptr(), match.data_ptr(), None, None)
     _lib.check_match(rc)
     for t in (a, b, k1, k2, M):
         t.record_stream(stream)
