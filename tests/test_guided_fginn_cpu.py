@@ -215,7 +215,7 @@ def test_abi_refuses_a_bad_second_nn(layout):
     dict(mp=_lib.MatchParams(0, 0, 0.9, False, R)), dict(kp_dim=3), dict(kp_dim=0),
     dict(gp=_lib.GuideParams(0, 2, 0.5)), dict(gp=_lib.GuideParams(1, 5, 0.5)), dict(gp=_lib.GuideParams(0, 0, -0.1)),
     dict(gp=_lib.GuideParams(1, 2, float("nan"))),
-], ids=repr)
+], ids=lambda c: f"mp-norm{c['mp'].norm}-dim{c['mp'].dim}" if "mp" in c else repr(c))     # MatchParams' repr holds the object's address
 def test_abi_keeps_the_refusals_of_the_plain_guided_calls_whatever_the_list_holds(layout, case):
     assert _abi(layout, **case)[0] == ALL
     assert _abi(layout, n_pairs=0, **case)[0] == ALL
