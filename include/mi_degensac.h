@@ -499,6 +499,55 @@ int mi_degensac_match_verify_fginn_pairs(int homography, const mi_degensac_match
                                          const uint32_t *seeds, int device, double *model, int32_t *match, uint8_t *inlier,
                                          int32_t *stats /*nullable*/, int32_t *counts /*nullable*/);
 
+/* ---- match once, verify F and H: both models on the same tentatives ---------------------------------------------------------
+ * A pipeline that classifies its pairs (general scene: keep F; planar or panoramic: H explains what F explains; rejected) needs both
+ * models on the SAME tentatives, the two inlier sets and their overlap.  These calls run the matching half of
+ * mi_degensac_match_verify_batch_dev ONCE (2-NN, FGINN step, reverse search, ratio test, ranks), read the K tentative counts back ONCE
+ * (the only synchronisation), then run the fundamental-matrix estimator with prm_f and the homography estimator with prm_h one after
+ * the other on `stream`, and one scatter stage writes everything.  Arguments as mi_degensac_match_verify_batch_dev without
+ * `homography`; d_seeds[p] seeds BOTH estimators of pair p.
+ * Per pair, d_model_f / d_inlier_f / d_stats_f are bit for bit those of mi_degensac_match_verify_batch_dev with homography = 0 and
+ * prm_f, d_model_h / d_inlier_h / d_stats_h those of the call with homography = 1 and prm_h, d_match and h_counts those of either, on
+ * the same inputs, seeds and mp.  So a pair with 4 .. 7 tentatives has an H and a zero F; below 4 both are zero.
+ * Outputs: d_model_f / d_model_h [K*9] in the driver's form, d_stats_f / d_stats_h [K*16] or NULL, d_match / d_inlier_f / d_inlier_h one
+ * entry per query row, d_summary [K*4] int32 (not nullable): per pair (tentatives, nF, nH, nFH) = its tentatives, its rows with
+ * inlier_f = 1, with inlier_h = 1, and with both; h_counts (host, [K], nullable).  Discarded pairs carry bit 10 of stats[15] in the
+ * stats row of the model that was discarded.
+ * Errors, all before a device is looked for: those of mi_degensac_match_verify_batch_dev, with prm_f checked as a fundamental-matrix
+ * and prm_h as a homography parameter block; n_pairs == 0 returns 0. */
+int mi_degensac_match_verify_fh_batch_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
+                                          const int64_t *offsets1_host, const int64_t *offsets2_host, const double *d_kp1, const double *d_kp2,
+                                          int kp_dim, int n_pairs, const mi_degensac_params *prm_f, const mi_degensac_params *prm_h,
+                                          const uint32_t *d_seeds, int device, void *stream, double *d_model_f, double *d_model_h,
+                                          int32_t *d_match, uint8_t *d_inlier_f, uint8_t *d_inlier_h, int32_t *d_stats_f /*nullable*/,
+                                          int32_t *d_stats_h /*nullable*/, int32_t *d_summary, int32_t *h_counts /*nullable*/);
+/* the same on host pointers (blocking; seeds[K] on the host; summary nullable): one upload, the device path, and per model the re-run of
+ * the pairs whose stats row of THAT model carries bit 10 (bit 11 afterwards, as in mi_degensac_match_verify_batch); the summary of such
+ * a pair is counted again from its masks. */
+int mi_degensac_match_verify_fh_batch(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
+                                      const int64_t *offsets2, const double *kp1, const double *kp2, int kp_dim, int n_pairs,
+                                      const mi_degensac_params *prm_f, const mi_degensac_params *prm_h, const uint32_t *seeds, int device,
+                                      double *model_f, double *model_h, int32_t *match, uint8_t *inlier_f, uint8_t *inlier_h,
+                                      int32_t *stats_f /*nullable*/, int32_t *stats_h /*nullable*/, int32_t *summary /*nullable*/,
+                                      int32_t *counts /*nullable*/);
+/* mi_degensac_match_verify_fh_batch_dev on a pair list over image stores (arguments and layout as mi_degensac_match_verify_pairs_dev).
+ * mp->second_nn / mp->spatial_th are honoured as by mi_degensac_match_verify_fginn_pairs_dev: there is no separate FGINN twin.  Per
+ * entry and model bit for bit mi_degensac_match_verify_fginn_pairs_dev with that model's homography flag and parameter block. */
+int mi_degensac_match_verify_fh_pairs_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
+                                          const int64_t *offsets1_host, int n_images1, const int64_t *offsets2_host, int n_images2,
+                                          const double *d_kp1, const double *d_kp2, int kp_dim, const int32_t *pairs_host, int n_pairs,
+                                          const mi_degensac_params *prm_f, const mi_degensac_params *prm_h, const uint32_t *d_seeds, int device,
+                                          void *stream, double *d_model_f, double *d_model_h, int32_t *d_match, uint8_t *d_inlier_f,
+                                          uint8_t *d_inlier_h, int32_t *d_stats_f /*nullable*/, int32_t *d_stats_h /*nullable*/,
+                                          int32_t *d_summary, int32_t *h_counts /*nullable*/);
+/* the same on host pointers (blocking): each store is uploaded once, re-runs per model as in mi_degensac_match_verify_fh_batch */
+int mi_degensac_match_verify_fh_pairs(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
+                                      int n_images1, const int64_t *offsets2, int n_images2, const double *kp1, const double *kp2, int kp_dim,
+                                      const int32_t *pairs, int n_pairs, const mi_degensac_params *prm_f, const mi_degensac_params *prm_h,
+                                      const uint32_t *seeds, int device, double *model_f, double *model_h, int32_t *match, uint8_t *inlier_f,
+                                      uint8_t *inlier_h, int32_t *stats_f /*nullable*/, int32_t *stats_h /*nullable*/,
+                                      int32_t *summary /*nullable*/, int32_t *counts /*nullable*/);
+
 /* ---- guided matching: the batched 2-NN restricted to each pair's model inlier band (mi_guided.hip) ------------------------
  * Same ragged batch as mi_degensac_match_knn2_batch_dev (host offsets of K + 1 values, pair-local indices), plus keypoints
  * kp1 / kp2 [rows, kp_dim] float64 (kp_dim 2 or 6; only x, y are read) and one model per pair, d_models [K*9] in the driver's form

@@ -210,6 +210,22 @@ def lib():
             l.mi_degensac_match_verify_fginn_pairs_dev.argtypes = l.mi_degensac_match_verify_pairs_dev.argtypes
             l.mi_degensac_match_verify_fginn_pairs.restype = C.c_int
             l.mi_degensac_match_verify_fginn_pairs.argtypes = l.mi_degensac_match_verify_pairs.argtypes
+        if hasattr(l, "mi_degensac_match_verify_fh_pairs_dev"):           # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            # both models on the same tentatives: no homography flag, two parameter blocks, and after the stream (_dev) / the device
+            # model_f, model_h, match, inlier_f, inlier_h, stats_f, stats_h, summary, counts
+            vp = C.c_void_p
+            l.mi_degensac_match_verify_fh_batch_dev.restype = C.c_int
+            l.mi_degensac_match_verify_fh_batch_dev.argtypes = [mpp, vp, vp, lp, lp, vp, vp, C.c_int, C.c_int, pp, pp, vp, C.c_int, vp,
+                                                                vp, vp, vp, vp, vp, vp, vp, vp, ip]
+            l.mi_degensac_match_verify_fh_batch.restype = C.c_int
+            l.mi_degensac_match_verify_fh_batch.argtypes = [mpp, vp, vp, lp, lp, dp, dp, C.c_int, C.c_int, pp, pp, up, C.c_int,
+                                                            dp, dp, ip, bp, bp, ip, ip, ip, ip]
+            l.mi_degensac_match_verify_fh_pairs_dev.restype = C.c_int
+            l.mi_degensac_match_verify_fh_pairs_dev.argtypes = [mpp, vp, vp, lp, C.c_int, lp, C.c_int, vp, vp, C.c_int, ip, C.c_int, pp, pp, vp,
+                                                                C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, ip]
+            l.mi_degensac_match_verify_fh_pairs.restype = C.c_int
+            l.mi_degensac_match_verify_fh_pairs.argtypes = [mpp, vp, vp, lp, C.c_int, lp, C.c_int, dp, dp, C.c_int, ip, C.c_int, pp, pp, up,
+                                                            C.c_int, dp, dp, ip, bp, bp, ip, ip, ip, ip]
         gpp = C.POINTER(GuideParams)
         l.mi_degensac_match_guided_knn2_batch_dev.restype = C.c_int
         l.mi_degensac_match_guided_knn2_batch_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, lp, lp, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,

@@ -1091,10 +1091,11 @@ static int mv_check(int homography, const mi_degensac_match_params *mp, const in
     return 0;
 }
 
-/* stream-ordered device blocks freed (on the stream) when the call returns, whichever way */
+/* stream-ordered device blocks freed (on the stream) when the call returns, whichever way: block A (the matching half) and one block B
+ * per estimator run on its tentatives (b2: the second model of the *_fh_* calls) */
 struct MvBlocks {
-    hipStream_t s; char *a = nullptr, *b = nullptr;
-    ~MvBlocks() { if (a) (void)hipFreeAsync(a, s); if (b) (void)hipFreeAsync(b, s); }
+    hipStream_t s; char *a = nullptr, *b = nullptr, *b2 = nullptr;
+    ~MvBlocks() { if (a) (void)hipFreeAsync(a, s); if (b) (void)hipFreeAsync(b, s); if (b2) (void)hipFreeAsync(b2, s); }
 };
 
 /* Where pair p's rows are, as int32 tables on the device (columns of mt_pair_rows).  out [K + 1]: its rows of idx / dist / keep / rank /
@@ -1102,17 +1103,26 @@ struct MvBlocks {
  * of the reverse search. */
 struct MvRows { const int32_t *out, *q1, *t2, *back; };
 
-/* the second half of a match-and-verify call, after the filter has written keep / rank / cnt on s */
-static int mv_estimate(int homography, int K, int kd, const mi_degensac_params *prm, const MvRows &R, const int32_t *cnt, const uint8_t *keep,
-                       const int32_t *rank, const int32_t *idx, const double *kp1, const double *kp2, const uint32_t *d_seeds, int device,
-                       hipStream_t s, MvBlocks &blk, double *d_model, int32_t *d_stats, int32_t *match, uint8_t *inlier, int32_t *h_counts)
+/* what the matching half leaves on s (in block A) for the estimating half: nothing of it depends on the model */
+struct MvMatched { MvRows R; const int32_t *cnt, *rank, *idx; const uint8_t *keep; const double *kp1, *kp2; };
+
+/* the second half of a match-and-verify call, after the filter has written keep / rank / cnt on s: (a) the read of the counts */
+static int mv_counts(int K, const int32_t *cnt, hipStream_t s, std::vector<int32_t> &counts, int32_t *h_counts)
 {
-    int rc;
     /* the one synchronisation: the estimator's launch is sized and configured from the tentative counts on the host */
-    std::vector<int32_t> counts(K);
+    counts.resize(K);
     HIPCHK(hipMemcpyAsync(counts.data(), cnt, (size_t)K * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (h_counts) memcpy(h_counts, counts.data(), (size_t)K * 4);
+    return 0;
+}
+
+/* (b) one model on the counted tentatives: its eligible list, block B (into b), gather and estimator on s; `half` says where the results
+ * lie for the scatter stage */
+static int mv_half(int homography, int K, int kd, const mi_degensac_params *prm, const MvMatched &m, const std::vector<int32_t> &counts,
+                   const uint32_t *d_seeds, int device, hipStream_t s, char *&b, mt_half &half)
+{
+    int rc;
     const int min_pts = homography ? 4 : 8;
     std::vector<int64_t> est_off(1, 0); std::vector<int32_t> e_of_p(K, -1), pair_of_e;
     for (int p = 0; p < K; p++)
@@ -1127,19 +1137,47 @@ static int mv_estimate(int homography, int K, int kd, const mi_degensac_params *
     const size_t g_seed = align_up(c_all, 256), g_model = g_seed + align_up((size_t)E * 4, 256), g_stats = g_model + align_up((size_t)E * 72, 256),
                  g_p1 = g_stats + align_up((size_t)E * 64, 256), g_p2 = g_p1 + align_up((size_t)T * kd * 8, 256),
                  g_mask = g_p2 + align_up((size_t)T * kd * 8, 256), g_all = g_mask + align_up((size_t)T, 256);
-    HIPCHK(hipMallocAsync((void **)&blk.b, g_all, s));
-    char *B = blk.b;
+    HIPCHK(hipMallocAsync((void **)&b, g_all, s));
+    char *B = b;
     const int64_t *d_eoff = (const int64_t *)(B + c_eoff); const int32_t *d_eop = (const int32_t *)(B + c_eop), *d_poe = (const int32_t *)(B + c_poe);
     uint32_t *seeds_e = (uint32_t *)(B + g_seed); double *model_e = (double *)(B + g_model), *pts1 = (double *)(B + g_p1), *pts2 = (double *)(B + g_p2);
     int32_t *stats_e = (int32_t *)(B + g_stats); uint8_t *mask_e = (uint8_t *)(B + g_mask);
+    half = mt_half{d_eop, d_eoff, model_e, stats_e, mask_e};
     rc = match_rc(mt_batch_upload(device, s, tab.data(), c_all, B)); if (rc) return rc;
     if (E > 0) {
-        rc = match_rc(mt_batch_gather(E, d_poe, d_eoff, R.out, R.q1, R.t2, keep, rank, idx, kp1, kp2, kd, d_seeds, s, pts1, pts2, seeds_e));
+        rc = match_rc(mt_batch_gather(E, d_poe, d_eoff, m.R.out, m.R.q1, m.R.t2, m.keep, m.rank, m.idx, m.kp1, m.kp2, kd, d_seeds, s, pts1, pts2, seeds_e));
         if (rc) return rc;
         rc = launch_batch(homography, pts1, pts2, d_eoff, est_off.data(), E, kd, prm, seeds_e, device, s, model_e, mask_e, stats_e);
         if (rc) return rc;
     }
-    return match_rc(mt_batch_scatter(K, d_eop, d_eoff, R.out, keep, rank, idx, model_e, stats_e, mask_e, s, d_model, d_stats, match, inlier));
+    return 0;
+}
+
+/* one model: counts, its half, the scatter back to pair / query order */
+static int mv_estimate(int homography, int K, int kd, const mi_degensac_params *prm, const MvMatched &m, const uint32_t *d_seeds, int device,
+                       hipStream_t s, MvBlocks &blk, double *d_model, int32_t *d_stats, int32_t *match, uint8_t *inlier, int32_t *h_counts)
+{
+    std::vector<int32_t> counts; mt_half h;
+    int rc = mv_counts(K, m.cnt, s, counts, h_counts); if (rc) return rc;
+    if ((rc = mv_half(homography, K, kd, prm, m, counts, d_seeds, device, s, blk.b, h))) return rc;
+    return match_rc(mt_batch_scatter(K, h.e_of_p, h.est_off, m.R.out, m.keep, m.rank, m.idx, h.model_e, h.stats_e, h.mask_e, s, d_model, d_stats, match, inlier));
+}
+
+/* the outputs of the two-model calls (include/mi_degensac.h mi_degensac_match_verify_fh_*), on the device; match / inlier_* at the first
+ * output row */
+struct MvOutFH { double *model_f, *model_h; int32_t *match; uint8_t *inlier_f, *inlier_h; int32_t *stats_f, *stats_h, *summary; };
+
+/* both models on the same tentatives: the counts are read ONCE, then the fundamental matrix's half and the homography's half run one
+ * after the other on s (each persistent estimator fills the device), and one scatter writes both and the per-pair summary */
+static int mv_estimate_fh(int K, int kd, const mi_degensac_params *prm_f, const mi_degensac_params *prm_h, const MvMatched &m, const uint32_t *d_seeds,
+                          int device, hipStream_t s, MvBlocks &blk, const MvOutFH &o, int32_t *h_counts)
+{
+    std::vector<int32_t> counts; mt_half f, h;
+    int rc = mv_counts(K, m.cnt, s, counts, h_counts); if (rc) return rc;
+    if ((rc = mv_half(0, K, kd, prm_f, m, counts, d_seeds, device, s, blk.b, f))) return rc;
+    if ((rc = mv_half(1, K, kd, prm_h, m, counts, d_seeds, device, s, blk.b2, h))) return rc;
+    return match_rc(mt_batch_scatter_fh(K, f, h, m.R.out, m.keep, m.rank, m.idx, s, o.model_f, o.stats_f, o.model_h, o.stats_h, o.match, o.inlier_f,
+                                        o.inlier_h, o.summary));
 }
 
 /* the pair list's refusals and its rows (see the pair-list section below); with_fginn: the *_fginn_pairs* entry points, which honour
@@ -1172,15 +1210,15 @@ static int mv_check_null(const void *d_desc1, const void *d_desc2, const double 
     return 0;
 }
 
-/* The device path of both forms, arguments checked: pair p's rows are rows[p], n_out output rows and n_back rows of the reverse search
- * in all; side 1 / 2 (descriptors and keypoints) start at row r1 / r2 of the arrays passed; match / inlier are at the first output row.
- * The FGINN step (mp->second_nn) takes the same rows as the 2-NN in front of it. */
-static int match_verify_rows(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const double *d_kp1,
-                             const double *d_kp2, int64_t r1, int64_t r2, int kd, const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t n_back,
-                             const mi_degensac_params *prm, const uint32_t *d_seeds, int device, hipStream_t s, double *d_model, int32_t *match, uint8_t *inlier, int32_t *d_stats, int32_t *h_counts)
+/* The matching half of the device path, arguments checked and the device current: pair p's rows are rows[p], n_out output rows and
+ * n_back rows of the reverse search in all; side 1 / 2 (descriptors and keypoints) start at row r1 / r2 of the arrays passed.  The FGINN
+ * step (mp->second_nn) takes the same rows as the 2-NN in front of it.  Everything is enqueued on s into block A; m says where it lies. */
+static int mv_match(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const double *d_kp1, const double *d_kp2, int64_t r1,
+                    int64_t r2, int kd, const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t n_back, int device, hipStream_t s, MvBlocks &blk,
+                    MvMatched &m)
 {
     const int K = (int)rows.size();
-    DevGuard g; int rc = g.enter(device); if (rc) return rc;
+    int rc;
     const int words = mt_row_words(mp->norm, mp->dim);
     const bool mutual = mp->mutual != 0;
     /* every row pointer moves to its side's first row; the tables: out [K + 1] | q1 [K] | t2 [K] | back [K] */
@@ -1195,7 +1233,6 @@ static int match_verify_rows(int homography, const mi_degensac_match_params *mp,
                  b_keep = align_up((size_t)n_out, 256), b_cnt = align_up((size_t)K * 4, 256);
     const size_t a_idx = b_tab, a_dist = a_idx + b_idx, a_bidx = a_dist + b_idx, a_bdist = a_bidx + b_bidx, a_keep = a_bdist + b_bidx,
                  a_rank = a_keep + b_keep, a_cnt = a_rank + b_idx, a_all = a_cnt + b_cnt;
-    MvBlocks blk{s};
     HIPCHK(hipMallocAsync((void **)&blk.a, a_all, s));
     char *A = blk.a;
     const int32_t *d_out = (const int32_t *)A;
@@ -1203,13 +1240,37 @@ static int match_verify_rows(int homography, const mi_degensac_match_params *mp,
     int32_t *idx = (int32_t *)(A + a_idx), *bidx = mutual ? (int32_t *)(A + a_bidx) : nullptr, *rank = (int32_t *)(A + a_rank), *cnt = (int32_t *)(A + a_cnt);
     float *dist = (float *)(A + a_dist), *bdist = (float *)(A + a_bdist);
     uint8_t *keep = (uint8_t *)(A + a_keep);
+    m = MvMatched{R, cnt, rank, idx, keep, kp1, kp2};
     rc = match_rc(mt_batch_upload(device, s, tab.data(), tab.size() * 4, A)); if (rc) return rc;
     rc = match_rc(mt_batch_knn2(mp->norm, words, q1, q2, rows.data(), K, (int)n_out, 0, device, s, idx, dist)); if (rc) return rc;
     int fginn; double fginn_r; (void)mt_second_nn(mp, &fginn, &fginn_r);
     if (fginn) { rc = match_rc(mt_batch_fginn(mp->norm, words, q1, q2, kp2, kd, rows.data(), K, (int)n_out, fginn_r, device, s, idx, dist)); if (rc) return rc; }
     if (mutual) { rc = match_rc(mt_batch_knn2(mp->norm, words, q2, q1, rows.data(), K, (int)n_back, 1, device, s, bidx, bdist)); if (rc) return rc; }
-    rc = match_rc(mt_batch_filter_rank(idx, dist, R.out, R.back, K, mp->ratio, bidx, s, keep, rank, cnt)); if (rc) return rc;
-    return mv_estimate(homography, K, kd, prm, R, cnt, keep, rank, idx, kp1, kp2, d_seeds, device, s, blk, d_model, d_stats, match, inlier, h_counts);
+    return match_rc(mt_batch_filter_rank(idx, dist, R.out, R.back, K, mp->ratio, bidx, s, keep, rank, cnt));
+}
+
+/* The device path of both forms, arguments checked: the matching half, then the estimating half; match / inlier are at the first output
+ * row. */
+static int match_verify_rows(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const double *d_kp1,
+                             const double *d_kp2, int64_t r1, int64_t r2, int kd, const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t n_back,
+                             const mi_degensac_params *prm, const uint32_t *d_seeds, int device, hipStream_t s, double *d_model, int32_t *match, uint8_t *inlier, int32_t *d_stats, int32_t *h_counts)
+{
+    DevGuard g; int rc = g.enter(device); if (rc) return rc;
+    MvBlocks blk{s}; MvMatched m;
+    if ((rc = mv_match(mp, d_desc1, d_desc2, d_kp1, d_kp2, r1, r2, kd, rows, n_out, n_back, device, s, blk, m))) return rc;
+    return mv_estimate(homography, (int)rows.size(), kd, prm, m, d_seeds, device, s, blk, d_model, d_stats, match, inlier, h_counts);
+}
+
+/* the same with both models (mi_degensac_match_verify_fh_*): one matching half, one read of the counts */
+static int match_verify_fh_rows(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const double *d_kp1, const double *d_kp2,
+                                int64_t r1, int64_t r2, int kd, const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t n_back,
+                                const mi_degensac_params *prm_f, const mi_degensac_params *prm_h, const uint32_t *d_seeds, int device, hipStream_t s,
+                                const MvOutFH &o, int32_t *h_counts)
+{
+    DevGuard g; int rc = g.enter(device); if (rc) return rc;
+    MvBlocks blk{s}; MvMatched m;
+    if ((rc = mv_match(mp, d_desc1, d_desc2, d_kp1, d_kp2, r1, r2, kd, rows, n_out, n_back, device, s, blk, m))) return rc;
+    return mv_estimate_fh((int)rows.size(), kd, prm_f, prm_h, m, d_seeds, device, s, blk, o, h_counts);
 }
 
 extern "C" int mi_degensac_match_verify_batch_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
@@ -1376,3 +1437,160 @@ extern "C" int mi_degensac_match_verify_fginn_pairs(MVP_HOST_ARGS) { return matc
 #undef MVP_DEV_PASS
 #undef MVP_HOST_ARGS
 #undef MVP_HOST_PASS
+
+/* ---- match once, verify F and H (include/mi_degensac.h mi_degensac_match_verify_fh_*) -----------------------------------------
+ * The matching half of the calls above once, then both estimators on its tentatives: mv_match -> mv_counts (the one synchronisation)
+ * -> mv_half for F (pairs with >= 8 tentatives) -> mv_half for H (>= 4) -> mt_batch_scatter_fh.  Every refusal comes before a device is
+ * looked for. */
+static int mvfh_check_prm(const mi_degensac_params *prm_f, const mi_degensac_params *prm_h, int kd)
+{
+    int rc = mv_check_prm(prm_f, 0, kd); if (rc) return rc;
+    return mv_check_prm(prm_h, 1, kd);
+}
+static int mvfh_check_null(const void *d_desc1, const void *d_desc2, const double *d_kp1, const double *d_kp2, int64_t n_out, int64_t n_back,
+                           const uint32_t *d_seeds, const MvOutFH &o, bool need_summary)
+{
+    if (!d_seeds || !o.model_f || !o.model_h || (need_summary && !o.summary) ||
+        (n_out > 0 && (!d_desc1 || !d_kp1 || !o.match || !o.inlier_f || !o.inlier_h)) || (n_back > 0 && (!d_desc2 || !d_kp2))) {
+        set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
+    return 0;
+}
+
+extern "C" int mi_degensac_match_verify_fh_batch_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
+        const int64_t *offsets1_host, const int64_t *offsets2_host, const double *d_kp1, const double *d_kp2, int kp_dim, int n_pairs,
+        const mi_degensac_params *prm_f, const mi_degensac_params *prm_h, const uint32_t *d_seeds, int device, void *stream, double *d_model_f,
+        double *d_model_h, int32_t *d_match, uint8_t *d_inlier_f, uint8_t *d_inlier_h, int32_t *d_stats_f, int32_t *d_stats_h, int32_t *d_summary,
+        int32_t *h_counts)
+{
+    int rc = mv_check(0, mp, offsets1_host, offsets2_host, kp_dim, n_pairs);
+    if (rc || n_pairs == 0) return rc;
+    std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
+    mt_ragged_rows(offsets1_host, offsets2_host, n_pairs, o1, o2, rows);
+    const int64_t n1 = o1[n_pairs], n2 = o2[n_pairs], r1 = offsets1_host[0];
+    const MvOutFH o{d_model_f, d_model_h, d_match ? d_match + r1 : nullptr, d_inlier_f ? d_inlier_f + r1 : nullptr, d_inlier_h ? d_inlier_h + r1 : nullptr,
+                    d_stats_f, d_stats_h, d_summary};
+    if ((rc = mvfh_check_prm(prm_f, prm_h, kp_dim)) || (rc = mvfh_check_null(d_desc1, d_desc2, d_kp1, d_kp2, n1, n2, d_seeds, o, true)) ||
+        (rc = mv_check_device(device))) return rc;
+    return match_verify_fh_rows(mp, d_desc1, d_desc2, d_kp1, d_kp2, r1, offsets2_host[0], kp_dim, rows, n1, n2, prm_f, prm_h, d_seeds, device,
+                                (hipStream_t)stream, o, h_counts);
+}
+
+extern "C" int mi_degensac_match_verify_fh_pairs_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
+        const int64_t *offsets1_host, int n_images1, const int64_t *offsets2_host, int n_images2, const double *d_kp1, const double *d_kp2, int kp_dim,
+        const int32_t *pairs_host, int n_pairs, const mi_degensac_params *prm_f, const mi_degensac_params *prm_h, const uint32_t *d_seeds, int device,
+        void *stream, double *d_model_f, double *d_model_h, int32_t *d_match, uint8_t *d_inlier_f, uint8_t *d_inlier_h, int32_t *d_stats_f,
+        int32_t *d_stats_h, int32_t *d_summary, int32_t *h_counts)
+{
+    std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
+    int rc = mvp_check(0, mp, kp_dim, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, true, rows, &n_out, &n_back);
+    if (rc || n_pairs == 0) return rc;
+    const MvOutFH o{d_model_f, d_model_h, d_match, d_inlier_f, d_inlier_h, d_stats_f, d_stats_h, d_summary};
+    if ((rc = mvfh_check_prm(prm_f, prm_h, kp_dim)) || (rc = mvfh_check_null(d_desc1, d_desc2, d_kp1, d_kp2, n_out, n_back, d_seeds, o, true)) ||
+        (rc = mv_check_device(device))) return rc;
+    return match_verify_fh_rows(mp, d_desc1, d_desc2, d_kp1, d_kp2, offsets1_host[0], offsets2_host[0], kp_dim, rows, n_out, n_back, prm_f, prm_h,
+                                d_seeds, device, (hipStream_t)stream, o, h_counts);
+}
+
+/* the host outputs of the two-model calls; match / inlier_* at the first output row */
+struct MvHostFH { double *model_f, *model_h; int32_t *match; uint8_t *inlier_f, *inlier_h; int32_t *stats_f, *stats_h, *summary, *counts; };
+
+/* The host-pointer forms, as match_verify_host: one upload, the device path, the results back, then mv_rerun per model for the pairs
+ * whose stats row OF THAT MODEL carries bit 10; the summary of a pair run again is counted again from its masks. */
+static int match_verify_fh_host(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *off1, int m1,
+                                const int64_t *off2, int m2, const double *kp1, const double *kp2, int kd, bool same,
+                                const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t n_back, const mi_degensac_params *prm_f,
+                                const mi_degensac_params *prm_h, const uint32_t *seeds, int device, const MvHostFH &h)
+{
+    const int K = (int)rows.size();
+    mi_degensac_ctx *c; int rc = thread_ctx(device, &c); if (rc) return rc;
+    DevGuard g; rc = g.enter(device); if (rc) return rc;
+    const int64_t n1 = off1[m1] - off1[0], n2 = off2[m2] - off2[0];
+    const size_t row = mt_row_bytes(mp->norm, mp->dim);
+    const size_t s_d1 = align_up(n1 * row, 256), s_d2 = same ? 0 : align_up(n2 * row, 256), s_k1 = align_up((size_t)n1 * kd * 8, 256),
+                 s_k2 = same ? 0 : align_up((size_t)n2 * kd * 8, 256), s_sd = align_up((size_t)K * 4, 256), s_mo = align_up((size_t)K * 72, 256),
+                 s_ma = align_up((size_t)n_out * 4, 256), s_in = align_up((size_t)n_out, 256), s_st = align_up((size_t)K * 64, 256),
+                 s_su = align_up((size_t)K * 16, 256);
+    const size_t a_d2 = s_d1, a_k1 = a_d2 + s_d2, a_k2 = a_k1 + s_k1, a_sd = a_k2 + s_k2, a_mf = a_sd + s_sd, a_mh = a_mf + s_mo, a_ma = a_mh + s_mo,
+                 a_if = a_ma + s_ma, a_ih = a_if + s_in, a_sf = a_ih + s_in, a_sh = a_sf + s_st, a_su = a_sh + s_st, a_all = a_su + s_su;
+    const double *h_k1 = kp1 + off1[0] * kd, *h_k2 = kp2 + off2[0] * kd;
+    char *D = nullptr;
+    struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
+    HIPCHK(hipMalloc((void **)&D, a_all));
+    HIPCHK(hipMemcpy(D, (const char *)desc1 + off1[0] * row, n1 * row, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(D + a_k1, h_k1, (size_t)n1 * kd * 8, hipMemcpyHostToDevice));
+    if (!same) {
+        HIPCHK(hipMemcpy(D + a_d2, (const char *)desc2 + off2[0] * row, n2 * row, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(D + a_k2, h_k2, (size_t)n2 * kd * 8, hipMemcpyHostToDevice));
+    }
+    HIPCHK(hipMemcpy(D + a_sd, seeds, (size_t)K * 4, hipMemcpyHostToDevice));
+    std::vector<int32_t> cnt(K), stf((size_t)K * 16), sth((size_t)K * 16), sum((size_t)K * 4);
+    const MvOutFH o{(double *)(D + a_mf), (double *)(D + a_mh), (int32_t *)(D + a_ma), (uint8_t *)(D + a_if), (uint8_t *)(D + a_ih),
+                    (int32_t *)(D + a_sf), (int32_t *)(D + a_sh), (int32_t *)(D + a_su)};
+    rc = match_verify_fh_rows(mp, D, same ? D : D + a_d2, (const double *)(D + a_k1), (const double *)(D + (same ? a_k1 : a_k2)), 0, 0, kd, rows, n_out,
+                              n_back, prm_f, prm_h, (const uint32_t *)(D + a_sd), device, c->stream, o, cnt.data());
+    if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(h.model_f, o.model_f, (size_t)K * 72, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.model_h, o.model_h, (size_t)K * 72, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.match, o.match, (size_t)n_out * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.inlier_f, o.inlier_f, (size_t)n_out, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.inlier_h, o.inlier_h, (size_t)n_out, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(stf.data(), o.stats_f, (size_t)K * 64, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sth.data(), o.stats_h, (size_t)K * 64, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(sum.data(), o.summary, (size_t)K * 16, hipMemcpyDeviceToHost));
+    std::vector<int64_t> out(K + 1), b1(K), b2(K);
+    for (int p = 0; p < K; p++) { out[p] = rows[p].out; b1[p] = rows[p].q; b2[p] = rows[p].t; }
+    out[K] = n_out;
+    std::vector<uint8_t> redo(K, 0);
+    for (int p = 0; p < K; p++) redo[p] = ((stf[(size_t)p * 16 + 15] | sth[(size_t)p * 16 + 15]) & 1024) != 0;
+    rc = mv_rerun(c, 0, kd, K, prm_f, seeds, out.data(), b1.data(), b2.data(), h_k1, h_k2, h.match, h.model_f, h.inlier_f, stf); if (rc) return rc;
+    rc = mv_rerun(c, 1, kd, K, prm_h, seeds, out.data(), b1.data(), b2.data(), h_k1, h_k2, h.match, h.model_h, h.inlier_h, sth); if (rc) return rc;
+    for (int p = 0; p < K; p++) if (redo[p]) {
+        int32_t nf = 0, nh = 0, nfh = 0;
+        for (int64_t i = out[p]; i < out[p + 1]; i++) { nf += h.inlier_f[i] != 0; nh += h.inlier_h[i] != 0; nfh += h.inlier_f[i] && h.inlier_h[i]; }
+        sum[(size_t)p * 4 + 1] = nf; sum[(size_t)p * 4 + 2] = nh; sum[(size_t)p * 4 + 3] = nfh;
+    }
+    if (h.stats_f) memcpy(h.stats_f, stf.data(), (size_t)K * 64);
+    if (h.stats_h) memcpy(h.stats_h, sth.data(), (size_t)K * 64);
+    if (h.summary) memcpy(h.summary, sum.data(), (size_t)K * 16);
+    if (h.counts) memcpy(h.counts, cnt.data(), (size_t)K * 4);
+    return 0;
+}
+
+static int mvfh_check_host_null(const void *desc1, const void *desc2, const double *kp1, const double *kp2, const uint32_t *seeds, const MvHostFH &h)
+{
+    if (!desc1 || !desc2 || !kp1 || !kp2 || !seeds || !h.model_f || !h.model_h || !h.match || !h.inlier_f || !h.inlier_h) {
+        set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
+    return 0;
+}
+
+extern "C" int mi_degensac_match_verify_fh_batch(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
+        const int64_t *offsets2, const double *kp1, const double *kp2, int kd, int K, const mi_degensac_params *prm_f, const mi_degensac_params *prm_h,
+        const uint32_t *seeds, int device, double *model_f, double *model_h, int32_t *match, uint8_t *inlier_f, uint8_t *inlier_h, int32_t *stats_f,
+        int32_t *stats_h, int32_t *summary, int32_t *counts)
+{
+    int rc = mv_check(0, mp, offsets1, offsets2, kd, K);
+    if (rc || K == 0) return rc;
+    const int64_t r1 = offsets1[0];
+    const MvHostFH h{model_f, model_h, match ? match + r1 : nullptr, inlier_f ? inlier_f + r1 : nullptr, inlier_h ? inlier_h + r1 : nullptr, stats_f,
+                     stats_h, summary, counts};
+    if ((rc = mvfh_check_prm(prm_f, prm_h, kd)) || (rc = mvfh_check_host_null(desc1, desc2, kp1, kp2, seeds, h))) return rc;
+    std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
+    mt_ragged_rows(offsets1, offsets2, K, o1, o2, rows);
+    return match_verify_fh_host(mp, desc1, desc2, offsets1, K, offsets2, K, kp1, kp2, kd, false, rows, o1[K], o2[K], prm_f, prm_h, seeds, device, h);
+}
+
+extern "C" int mi_degensac_match_verify_fh_pairs(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
+        int n_images1, const int64_t *offsets2, int n_images2, const double *kp1, const double *kp2, int kd, const int32_t *pairs, int K,
+        const mi_degensac_params *prm_f, const mi_degensac_params *prm_h, const uint32_t *seeds, int device, double *model_f, double *model_h,
+        int32_t *match, uint8_t *inlier_f, uint8_t *inlier_h, int32_t *stats_f, int32_t *stats_h, int32_t *summary, int32_t *counts)
+{
+    std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
+    int rc = mvp_check(0, mp, kd, offsets1, n_images1, offsets2, n_images2, pairs, K, true, rows, &n_out, &n_back);
+    if (rc || K == 0) return rc;
+    const MvHostFH h{model_f, model_h, match, inlier_f, inlier_h, stats_f, stats_h, summary, counts};
+    if ((rc = mvfh_check_prm(prm_f, prm_h, kd)) || (rc = mvfh_check_host_null(desc1, desc2, kp1, kp2, seeds, h))) return rc;
+    const bool same = desc1 == desc2 && kp1 == kp2 && n_images1 == n_images2 && !memcmp(offsets1, offsets2, ((size_t)n_images1 + 1) * 8);
+    return match_verify_fh_host(mp, desc1, desc2, offsets1, n_images1, offsets2, n_images2, kp1, kp2, kd, same, rows, n_out, n_back, prm_f, prm_h, seeds,
+                                device, h);
+}

@@ -122,6 +122,16 @@ MT_HIDDEN int mt_batch_gather(int n_eligible, const int32_t *d_pair_of_e, const 
 MT_HIDDEN int mt_batch_scatter(int n_pairs, const int32_t *d_e_of_p, const int64_t *d_est_off, const int32_t *d_off1, const uint8_t *d_keep,
                                const int32_t *d_rank, const int32_t *d_idx, const double *d_model_e, const int32_t *d_stats_e, const uint8_t *d_mask_e,
                                hipStream_t s, double *d_model, int32_t *d_stats /*nullable*/, int32_t *d_match, uint8_t *d_inlier);
+/* one estimator's results over its eligible pairs, as mt_batch_scatter takes them: e_of_p [K] (-1 = short pair), est_off [E + 1], and
+ * model [E*9] / stats [E*16] / mask [est_off[E]] in eligible order; all on the device */
+struct mt_half { const int32_t *e_of_p; const int64_t *est_off; const double *model_e; const int32_t *stats_e; const uint8_t *mask_e; };
+/* mt_batch_scatter for two estimators run on the same tentatives (f: fundamental matrix, h: homography; each half has its own eligible
+ * list and row base) in one launch: both models / stats rows (d_stats_* nullable), one match, inlier_f / inlier_h per query, and
+ * d_summary [K*4] = per pair (tentatives, rows with inlier_f, rows with inlier_h, rows with both), counted without atomics */
+MT_HIDDEN int mt_batch_scatter_fh(int n_pairs, const mt_half &f, const mt_half &h, const int32_t *d_off1, const uint8_t *d_keep,
+                                  const int32_t *d_rank, const int32_t *d_idx, hipStream_t s, double *d_model_f, int32_t *d_stats_f /*nullable*/,
+                                  double *d_model_h, int32_t *d_stats_h /*nullable*/, int32_t *d_match, uint8_t *d_inlier_f, uint8_t *d_inlier_h,
+                                  int32_t *d_summary);
 
 /* ---- guided matching (mi_guided.hip) ---- */
 /* the gate of a model kind: th from px_th / error_type as fill_params derives it; EINVAL (message set) for a bad error_type or a

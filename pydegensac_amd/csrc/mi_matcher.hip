@@ -321,6 +321,48 @@ __global__ __launch_bounds__(256) void mt_scatter_kernel(const int32_t *e_of_p, 
     }
 }
 
+/* mt_scatter_kernel for two models on the same tentatives (F, then H): one workgroup per pair writes both models / stats rows from the
+ * pair's eligible index of each half (ef / eh, each with its own est_off base; zeros where the index is -1), match and both inlier rows
+ * per query, and summary[p] = (tentatives, nF, nH, nFH).  The counts come from wave ballots, summed per wave over the sweep, and a
+ * four-entry LDS table per count that thread 0 adds up: no atomics, nothing depends on scheduling. */
+__global__ __launch_bounds__(256) void mt_scatter_fh_kernel(const int32_t *e_of_p_f, const int64_t *est_off_f, const int32_t *e_of_p_h,
+                                                            const int64_t *est_off_h, const int32_t *off1, const uint8_t *keep, const int32_t *rank,
+                                                            const int32_t *idx, const double *model_ef, const int32_t *stats_ef,
+                                                            const uint8_t *mask_ef, const double *model_eh, const int32_t *stats_eh,
+                                                            const uint8_t *mask_eh, double *model_f, int32_t *stats_f, double *model_h,
+                                                            int32_t *stats_h, int32_t *match, uint8_t *inlier_f, uint8_t *inlier_h, int32_t *summary)
+{
+    __shared__ int wsum[4][4];
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int ef = e_of_p_f[p], eh = e_of_p_h[p];
+    if (tid < 9) {
+        model_f[(int64_t)p * 9 + tid] = ef >= 0 ? model_ef[(int64_t)ef * 9 + tid] : 0.0;
+        model_h[(int64_t)p * 9 + tid] = eh >= 0 ? model_eh[(int64_t)eh * 9 + tid] : 0.0;
+    }
+    if (tid < MI_DEGENSAC_STATS_LEN) {
+        if (stats_f) stats_f[(int64_t)p * MI_DEGENSAC_STATS_LEN + tid] = ef >= 0 ? stats_ef[(int64_t)ef * MI_DEGENSAC_STATS_LEN + tid] : 0;
+        if (stats_h) stats_h[(int64_t)p * MI_DEGENSAC_STATS_LEN + tid] = eh >= 0 ? stats_eh[(int64_t)eh * MI_DEGENSAC_STATS_LEN + tid] : 0;
+    }
+    const int64_t of = ef >= 0 ? est_off_f[ef] : 0, oh = eh >= 0 ? est_off_h[eh] : 0;
+    const int lo = off1[p], hi = off1[p + 1];
+    int nt = 0, nf = 0, nh = 0, nfh = 0;                /* this wave's counts (the same in all its lanes) */
+    for (int i0 = lo; i0 < hi; i0 += 256) {
+        const int i = i0 + tid;
+        bool k = false; uint8_t f = 0, h = 0;
+        if (i < hi) {
+            k = keep[i] != 0;
+            if (k) { const int r = rank[i]; f = ef >= 0 ? mask_ef[of + r] : 0; h = eh >= 0 ? mask_eh[oh + r] : 0; }
+            match[i] = k ? idx[2 * i] : -1;
+            inlier_f[i] = f; inlier_h[i] = h;
+        }
+        nt += __popcll(__ballot(k)); nf += __popcll(__ballot(f != 0)); nh += __popcll(__ballot(h != 0)); nfh += __popcll(__ballot(f != 0 && h != 0));
+    }
+    if (lane == 0) { wsum[wv][0] = nt; wsum[wv][1] = nf; wsum[wv][2] = nh; wsum[wv][3] = nfh; }
+    __syncthreads();
+    if (tid == 0)
+        for (int c = 0; c < 4; c++) summary[(int64_t)p * 4 + c] = wsum[0][c] + wsum[1][c] + wsum[2][c] + wsum[3][c];
+}
+
 static thread_local char mt_err[256] = "";
 extern "C" const char *mi_degensac_match_last_error(void) { return mt_err; }
 void mt_set_error(const char *msg) { snprintf(mt_err, sizeof mt_err, "%s", msg); }
@@ -573,6 +615,18 @@ int mt_batch_scatter(int n_pairs, const int32_t *d_e_of_p, const int64_t *d_est_
     if (n_pairs <= 0) return 0;
     hipLaunchKernelGGL(mt_scatter_kernel, dim3(n_pairs), dim3(256), 0, s, d_e_of_p, d_est_off, d_off1, d_keep, d_rank, d_idx, d_model_e, d_stats_e,
         d_mask_e, d_model, d_stats, d_match, d_inlier);
+    MTCHK(hipGetLastError());
+    return 0;
+}
+
+int mt_batch_scatter_fh(int n_pairs, const mt_half &f, const mt_half &h, const int32_t *d_off1, const uint8_t *d_keep, const int32_t *d_rank,
+                        const int32_t *d_idx, hipStream_t s, double *d_model_f, int32_t *d_stats_f, double *d_model_h, int32_t *d_stats_h,
+                        int32_t *d_match, uint8_t *d_inlier_f, uint8_t *d_inlier_h, int32_t *d_summary)
+{
+    if (n_pairs <= 0) return 0;
+    hipLaunchKernelGGL(mt_scatter_fh_kernel, dim3(n_pairs), dim3(256), 0, s, f.e_of_p, f.est_off, h.e_of_p, h.est_off, d_off1, d_keep, d_rank, d_idx,
+        f.model_e, f.stats_e, f.mask_e, h.model_e, h.stats_e, h.mask_e, d_model_f, d_stats_f, d_model_h, d_stats_h, d_match, d_inlier_f, d_inlier_h,
+        d_summary);
     MTCHK(hipGetLastError());
     return 0;
 }

@@ -578,6 +578,113 @@ def _match_verify_pairs(fginn_r, kps_list, desc_list, pairs, model, ratio, mutua
     return M, [match[po[p]:po[p + 1]] for p in range(K)], [inl[po[p]:po[p + 1]].astype(bool) for p in range(K)]
 
 
+# ---- match once, verify F and H (include/mi_degensac.h mi_degensac_match_verify_fh_*) ----
+_ESTIMATOR_KEYS = ("px_th", "conf", "max_iters", "laf_consistensy_coef", "error_type", "symmetric_error_check")
+
+
+def two_view_params(f_params=None, h_params=None):
+    """f_params / h_params of the match_and_verify_fh_* calls -> (mi_degensac_params for F, for H).  Each is None or a dict of the estimator
+    keywords estimator_params takes (px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, and for F
+    enable_degeneracy_check); missing keys take findFundamentalMatrix's / findHomography's defaults.  An unknown key is a ValueError."""
+    out = []
+    for model, d, name in (("F", f_params, "f_params"), ("H", h_params, "h_params")):
+        d = {} if d is None else d
+        if not isinstance(d, dict):
+            raise ValueError(f"{name} should be a dict of estimator keywords, or None")
+        allowed = _ESTIMATOR_KEYS + (("enable_degeneracy_check",) if model == "F" else ())
+        bad = sorted(str(k) for k in d if k not in allowed)
+        if bad:
+            raise ValueError(f"{name}: unknown key {', '.join(bad)} (known: {', '.join(allowed)})")
+        out.append(estimator_params(model, **d))
+    return tuple(out)
+
+
+def two_view_config(summary, min_inliers=15, max_h_ratio=0.8):
+    """The class of every pair from the summary [K, 4] = (tentatives, nF, nH, nFH) of a match_and_verify_fh_* call (numpy, or a tensor,
+    which is copied to the host): int8 [K] with 0 = rejected (max(nF, nH) < min_inliers), 2 = planar or panoramic (nH > max_h_ratio * nF,
+    compared in float64: the homography explains what the fundamental matrix explains), 1 = general.  This is COLMAP's H/F inlier-ratio
+    test of its two-view geometry estimation; the thresholds are the caller's business (the defaults are COLMAP's min_num_inliers and
+    max_H_inlier_ratio), and so is what to do with each class."""
+    s = summary.detach().cpu().numpy() if hasattr(summary, "detach") else np.asarray(summary)
+    if s.ndim != 2 or s.shape[1] != 4 or (s.size and not np.issubdtype(s.dtype, np.integer)):
+        raise ValueError("summary should be an integer array [K, 4] = (tentatives, nF, nH, nFH)")
+    nF = s[:, 1].astype(np.float64); nH = s[:, 2].astype(np.float64)
+    out = np.ones(s.shape[0], np.int8)
+    out[nH > float(max_h_ratio) * nF] = 2
+    out[np.maximum(nF, nH) < min_inliers] = 0
+    return out
+
+
+def _set_last_stats_fh(stf, sth, cnt):
+    """last_stats() of a two-model call: per pair the F row's dict with "tentatives", and the H row's dict under "homography" """
+    from . import api
+    stats = [_lib.stats_dict(s) for s in stf]
+    for d, h, c in zip(stats, sth, cnt):
+        d["tentatives"] = int(c); d["homography"] = _lib.stats_dict(h)
+    api._tls.stats = stats
+
+
+def _fh_host(entry, mp, A, B, layout, prm_f, prm_h, sd, device, K, n):
+    """a host-pointer mi_degensac_match_verify_fh_* call on prepared arrays; layout = its arguments between the descriptors and the
+    parameter blocks.  Returns (F [K, 3, 3], H [K, 3, 3] user-facing, match [n], inlier_f [n], inlier_h [n], summary [K, 4])."""
+    F = np.zeros((K, 9)); H = np.zeros((K, 9)); match = np.full(n, -1, np.int32); inf = np.zeros(n, np.uint8); inh = np.zeros(n, np.uint8)
+    stf = np.zeros((K, 16), np.int32); sth = np.zeros((K, 16), np.int32); summ = np.zeros((K, 4), np.int32); cnt = np.zeros(K, np.int32)
+    ip = C.POINTER(C.c_int32); bp = C.POINTER(C.c_uint8)
+    rc = entry(C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), *layout, C.byref(prm_f), C.byref(prm_h),
+               sd.ctypes.data_as(C.POINTER(C.c_uint32)), int(device), _lib.dptr(F), _lib.dptr(H), match.ctypes.data_as(ip), inf.ctypes.data_as(bp),
+               inh.ctypes.data_as(bp), stf.ctypes.data_as(ip), sth.ctypes.data_as(ip), summ.ctypes.data_as(ip), cnt.ctypes.data_as(ip))
+    _lib.check(rc)
+    _set_last_stats_fh(stf, sth, cnt)
+    return F.reshape(K, 3, 3), _h_user_form(H.reshape(K, 3, 3)), match, inf, inh, summ
+
+
+def match_and_verify_fh_batch(kps1_list, kps2_list, desc1_list, desc2_list, ratio=0.9, mutual=False, norm=None, fginn_th=None, seeds=None,
+                              f_params=None, h_params=None, device=0):
+    """match_and_verify_batch with BOTH models on the same tentatives: the matching runs once, then findFundamentalMatrix (f_params) and
+    findHomography (h_params) on every pair's tentatives, each seeded with the pair's seed.  Arrays, ratio, mutual, norm, fginn_th and
+    seeds as for match_and_verify_batch; f_params / h_params as for two_view_params.  Per pair F / inlier_f are bit for bit those of
+    match_and_verify_batch(model="F", **f_params), H / inlier_h those of model="H" with h_params; a pair with 4 .. 7 tentatives has an H
+    and a zero F, below 4 both are zero.  Returns (F [K, 3, 3], H [K, 3, 3] user-facing, [match_p], [inlier_f_p], [inlier_h_p],
+    summary [K, 4] int32 = per pair (tentatives, nF, nH, nFH): its tentatives and its queries that are inliers of F, of H, of both);
+    two_view_config(summary) classifies the pairs.  The guided stage is not part of this call: guided_match_batch takes either returned
+    model as it is.  last_stats() holds per pair the F statistics with "tentatives", and the H statistics under "homography"."""
+    code, kind, A, B, K1, K2, o1, o2 = _stack_pairs(kps1_list, kps2_list, desc1_list, desc2_list, "H", ratio, norm, device, fginn_th)
+    K = len(o1) - 1
+    prm_f, prm_h = two_view_params(f_params, h_params)
+    A, B, K1, K2 = _finish_pairs(code, kind, A, B, K1, K2, device)
+    sd = _seeds_u32(seeds, K)
+    lp = C.POINTER(C.c_int64)
+    F, H, match, inf, inh, summ = _fh_host(_lib.lib().mi_degensac_match_verify_fh_batch, _lib.MatchParams(code, A.shape[1], ratio, mutual, fginn_th), A, B,
+                                           (o1.ctypes.data_as(lp), o2.ctypes.data_as(lp), _lib.dptr(K1), _lib.dptr(K2), K1.shape[1], K), prm_f, prm_h,
+                                           sd, device, K, A.shape[0])
+    cut = lambda x, t=None: [x[o1[p]:o1[p + 1]] if t is None else x[o1[p]:o1[p + 1]].astype(t) for p in range(K)]          # noqa: E731
+    return F, H, cut(match), cut(inf, bool), cut(inh, bool), summ
+
+
+def match_and_verify_fh_pairs(kps_list, desc_list, pairs, ratio=0.9, mutual=False, norm=None, fginn_th=None, seeds=None, f_params=None,
+                              h_params=None, device=0, kps2_list=None, desc2_list=None):
+    """match_and_verify_fh_batch over a pair list: descriptors and keypoints once per image, pairs [K, 2] the (i, j) to run (stores, list
+    and seeds as for match_and_verify_pairs).  fginn_th is part of this call (None = the plain ratio test): there is no separate FGINN
+    form.  Per entry and model the results are bit for bit those of match_and_verify_pairs / match_and_verify_fginn_pairs with that model
+    and its parameters.  Returns (F [K, 3, 3], H [K, 3, 3] user-facing, [match_p], [inlier_f_p], [inlier_h_p], summary [K, 4] int32) as
+    match_and_verify_fh_batch.  The guided stage is not part of this call: guided_match_pairs takes either returned model as it is."""
+    fr = None if fginn_th is None else check_fginn_th(fginn_th)
+    (A, K1, c1), (B, K2, c2), one = _stack_stores(kps_list, desc_list, kps2_list, desc2_list)
+    code, kind, o1, o2, pr, po, sd = check_match_pairs_args("H", ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape,
+                                                            K2.dtype, c1, c2, pairs, seeds)
+    prm_f, prm_h = two_view_params(f_params, h_params)
+    K = len(pr)
+    if sd is None:
+        sd = _seeds_u32(None, K)
+    A, K1, B, K2 = _finish_stores(code, kind, A, K1, B, K2, one, device)              # one store: uploaded once
+    lp = C.POINTER(C.c_int64)
+    F, H, match, inf, inh, summ = _fh_host(_lib.lib().mi_degensac_match_verify_fh_pairs, _lib.MatchParams(code, A.shape[1], ratio, mutual, fr), A, B,
+                                           (o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, _lib.dptr(K1), _lib.dptr(K2),
+                                            K1.shape[1], pr.ctypes.data_as(C.POINTER(C.c_int32)), K), prm_f, prm_h, sd, device, K, int(po[-1]))
+    cut = lambda x, t=None: [x[po[p]:po[p + 1]] if t is None else x[po[p]:po[p + 1]].astype(t) for p in range(K)]          # noqa: E731
+    return F, H, cut(match), cut(inf, bool), cut(inh, bool), summ
+
+
 def guided_match_pairs(kps_list, desc_list, pairs, models, model="F", ratio=0.9, mutual=False, px_th=None, error_type="sampson", norm=None,
                        driver_form=False, device=0, kps2_list=None, desc2_list=None, fginn_th=None):
     """guided_match_batch over a pair list: descriptors and keypoints are given ONCE per image, pairs [K, 2] says which (i, j) to run and

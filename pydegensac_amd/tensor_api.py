@@ -537,6 +537,114 @@ def _match_verify_pairs_tensors(fginn_r, kps1, kps2, desc1, desc2, counts1, coun
     return _match_verify_dev(entry, layout, model, _lib.MatchParams(code, a.shape[1], ratio, mutual, fginn_r), prm, a, b, k1, k2, sd, K, n)[:5] + (po,)
 
 
+# ---- match once, verify F and H (include/mi_degensac.h mi_degensac_match_verify_fh_*) ----
+def _match_verify_fh_dev(entry, layout, mp, prm_f, prm_h, a, b, k1, k2, sd, K, n):
+    """_match_verify_dev for the two-model entry points: one call, both estimators on the same tentatives.  Returns (F [K, 3, 3],
+    H [K, 3, 3] user-facing, match [n], inlier_f [n] bool, inlier_h [n] bool, stats_f [K, 16], stats_h [K, 16], summary [K, 4],
+    n_tentatives [K] numpy int64)."""
+    import torch
+    dev = a.device
+    # pinned + non_blocking: a pageable copy would wait for the stream (the call's one synchronisation is the count read)
+    d_seeds = torch.from_numpy(sd.view(np.int32)).pin_memory().to(dev, non_blocking=True)
+    MF = torch.zeros((K, 9), dtype=torch.float64, device=dev); MH = torch.zeros((K, 9), dtype=torch.float64, device=dev)
+    match = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    inf = torch.zeros(n, dtype=torch.uint8, device=dev); inh = torch.zeros(n, dtype=torch.uint8, device=dev)
+    stf = torch.zeros((K, 16), dtype=torch.int32, device=dev); sth = torch.zeros((K, 16), dtype=torch.int32, device=dev)
+    summ = torch.zeros((K, 4), dtype=torch.int32, device=dev)
+    cnt = np.zeros(K, np.int32)
+    stream = torch.cuda.current_stream(dev)
+    rc = entry(C.byref(mp), a.data_ptr(), b.data_ptr(), *layout, C.byref(prm_f), C.byref(prm_h), d_seeds.data_ptr(), dev.index or 0,
+               C.c_void_p(stream.cuda_stream), MF.data_ptr(), MH.data_ptr(), match.data_ptr(), inf.data_ptr(), inh.data_ptr(), stf.data_ptr(),
+               sth.data_ptr(), summ.data_ptr(), cnt.ctypes.data_as(C.POINTER(C.c_int32)))
+    _lib.check(rc)
+    # the estimators and the scatter read these asynchronously: keep them alive until the stream reaches this point
+    for t in (a, b, k1, k2, d_seeds):
+        t.record_stream(stream)
+    return MF.view(K, 3, 3), _h_user_form(MH.view(K, 3, 3)), match, inf.to(torch.bool), inh.to(torch.bool), stf, sth, summ, cnt.astype(np.int64)
+
+
+def match_and_verify_fh_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, ratio=0.9, mutual=False, norm=None, fginn_th=None, seeds=None,
+                                      f_params=None, h_params=None):
+    """match_and_verify_batch_tensors with BOTH models on the same tentatives (include/mi_degensac.h mi_degensac_match_verify_fh_batch_dev):
+    the 2-NN search, the FGINN step, the reverse search of mutual and the ratio test run ONCE, the tentative counts are read ONCE (the
+    call's one host synchronisation), then the fundamental-matrix and the homography estimator run one after the other on every pair's
+    tentatives, both seeded with the pair's seed.  A pipeline that has to decide per pair between a general scene, a planar / panoramic
+    one and a rejected pair gets both models, both inlier sets and their overlap for about the price of one matching phase less than two
+    match_and_verify_batch_tensors calls.  Tensors, ratio, mutual, norm, fginn_th and seeds as there.  f_params / h_params: None or a dict
+    of estimator keywords (px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, and for F
+    enable_degeneracy_check); missing keys take findFundamentalMatrix's / findHomography's defaults, an unknown key is a ValueError.
+    Per pair F / inlier_f / stats_f are bit for bit those of match_and_verify_batch_tensors(model="F", **f_params), H / inlier_h / stats_h
+    those of model="H" with h_params, match and n_tentatives those of either.  A pair with 4 .. 7 tentatives has an H and a zero F; below
+    4 both are zero.
+    Returns (F [K, 3, 3], H [K, 3, 3] — the user-facing inv(H_c^T) —, match [N1] int32, inlier_f [N1] bool, inlier_h [N1] bool,
+    stats_f [K, 16], stats_h [K, 16], summary [K, 4] int32 = per pair (tentatives, nF, nH, nFH): its tentatives and its queries that are
+    inliers of F, of H, of both; n_tentatives [K] numpy int64); all but the last on the device.  matcher.two_view_config(summary)
+    classifies the pairs.
+    The guided stage is not part of this call (there is no guided= keyword): guided_match_batch_tensors / guided_match_pairs_tensors take
+    either returned model as it is."""
+    import torch
+    from . import matcher
+    ts = (kps1, kps2, desc1, desc2)
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
+    code, kind, o1, o2 = matcher.check_match_verify_args("H", ratio, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
+                                                         tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype, counts1, counts2, fginn_th)
+    K = len(o1) - 1
+    sd = matcher._seeds_u32(None if seeds is None else np.asarray(seeds).ravel(), K)
+    prm_f, prm_h = matcher.two_view_params(f_params, h_params)
+    if any(t.device != desc1.device for t in ts):
+        raise ValueError("kps1, kps2, desc1 and desc2 must live on the same ROCm device")
+    a, b = _desc_pair(desc1, desc2)
+    n1 = a.shape[0]
+    if kind == "kpts":
+        k1 = kpts_to_xyA_tensors(kps1); k2 = kpts_to_xyA_tensors(kps2)
+    else:
+        k1 = kps1.contiguous(); k2 = kps2.contiguous()
+    lp = C.POINTER(C.c_int64)
+    return _match_verify_fh_dev(_lib.lib().mi_degensac_match_verify_fh_batch_dev,
+                                (o1.ctypes.data_as(lp), o2.ctypes.data_as(lp), k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]), K),
+                                _lib.MatchParams(code, a.shape[1], ratio, mutual, fginn_th), prm_f, prm_h, a, b, k1, k2, sd, K, n1)
+
+
+def match_and_verify_fh_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs, ratio=0.9, mutual=False, norm=None, fginn_th=None,
+                                      seeds=None, f_params=None, h_params=None):
+    """match_and_verify_fh_batch_tensors over a pair list (include/mi_degensac.h mi_degensac_match_verify_fh_pairs_dev): kps / desc are
+    image stores (counts1 / counts2 rows per image; pass the same tensors on both sides for a collection matched against itself) and
+    pairs [K, 2] lists the (i, j) to run, as for match_and_verify_pairs_tensors.  fginn_th IS part of this call (None = the plain ratio
+    test, a number = the FGINN ratio test of match_and_verify_fginn_pairs_tensors): there is no separate FGINN form.  seeds: one per list
+    entry, for both estimators.  Per entry F / inlier_f / stats_f are bit for bit those of match_and_verify_pairs_tensors (with fginn_th:
+    match_and_verify_fginn_pairs_tensors) with model="F" and f_params, H / inlier_h / stats_h those with model="H" and h_params; the call
+    synchronises exactly once.
+    Returns (F [K, 3, 3], H [K, 3, 3] user-facing, match [N] int32 = train row local to image j or -1, inlier_f [N] bool, inlier_h [N]
+    bool, stats_f [K, 16], stats_h [K, 16], summary [K, 4] int32 = (tentatives, nF, nH, nFH), n_tentatives [K] numpy int64,
+    pair_offsets [K + 1] host int64) with N = pair_offsets[K].
+    The guided stage is not part of this call (there is no guided= keyword): guided_match_pairs_tensors / guided_match_batch_tensors take
+    either returned model as it is."""
+    import torch
+    from . import matcher
+    ts = (kps1, kps2, desc1, desc2)
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
+    fr = None if fginn_th is None else matcher.check_fginn_th(fginn_th)
+    code, kind, o1, o2, pr, po, sd = matcher.check_match_pairs_args("H", ratio, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape),
+                                                                    desc2.dtype, tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype,
+                                                                    counts1, counts2, pairs, seeds)
+    prm_f, prm_h = matcher.two_view_params(f_params, h_params)
+    if any(t.device != desc1.device for t in ts):
+        raise ValueError("kps1, kps2, desc1 and desc2 must live on the same ROCm device")
+    a, b = _desc_pair(desc1, desc2)
+    K = len(pr); n = int(po[-1])
+    conv = kpts_to_xyA_tensors if kind == "kpts" else (lambda k: k.contiguous())
+    k1 = conv(kps1); k2 = k1 if kps2 is kps1 else conv(kps2)          # once per store, not per pair
+    if sd is None:
+        sd = matcher._seeds_u32(None, K)
+    lp = C.POINTER(C.c_int64)
+    layout = (o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]),
+              pr.ctypes.data_as(C.POINTER(C.c_int32)), K)
+    return _match_verify_fh_dev(_lib.lib().mi_degensac_match_verify_fh_pairs_dev, layout, _lib.MatchParams(code, a.shape[1], ratio, mutual, fr),
+                                prm_f, prm_h, a, b, k1, k2, sd, K, n) + (po,)
+
+
 def guided_match_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs, models, model="F", ratio=0.9, mutual=False, px_th=None,
                                error_type="sampson", norm=None, driver_form=False, fginn_th=None):
     """guided_match_batch_tensors over a pair list (include/mi_degensac.h mi_degensac_match_guided_pairs_dev): kps / desc are image stores
