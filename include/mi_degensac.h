@@ -405,7 +405,45 @@ typedef struct mi_degensac_match_params {
                               mi_degensac_match_fginn_knn2_batch_dev).  Read only together with spatial_th                   */
     double  spatial_th;    /* FGINN radius in pixels, finite and >= 0.  Added after the first layout: a caller whose struct_size
                               is 0 or does not cover it gets second_nn = 0 whatever that field holds                        */
+    int32_t decide;        /* the decision rule, MI_DEGENSAC_DECIDE_* bit flags (below); 0 = the ratio test above.  Read, with
+                              max_dist, only when struct_size covers both (40): a caller whose struct_size is 0, 24 or 32 gets
+                              the rule above whatever these bytes hold                                                      */
+    float   max_dist;      /* with MI_DEGENSAC_DECIDE_MAX_DIST: the largest dist[0] of a tentative, finite and >= 0; not read
+                              without that bit                                                                              */
 } mi_degensac_match_params;
+/* The decision rule: which queries of a 2-NN result become tentatives.  Every entry point that reads mp->ratio reads it from the same
+ * struct (no twins); the data is what the searches already leave on the device: idx / dist of the forward 2-NN and, with mutual, bidx /
+ * bdist of the reverse one (16 bytes per train row).  With j = idx[i][0], query i is a tentative when ALL of these hold:
+ *   slot 0 exists                 j >= 0
+ *   the forward ratio test        idx[i][1] >= 0 && dist[i][0] < ratio * dist[i][1]   (fp32 product, strict), unless NO_RATIO.  In the
+ *                                 guided entry points a missing slot 1 has dist = inf and passes: nothing competes
+ *   the mutual check              bidx[j][0] == i, when mp->mutual != 0
+ *   the reverse ratio test        bidx[j][1] >= 0 && bdist[j][0] < ratio * bdist[j][1]  (the same fp32 product and strict <, at the
+ *                                 train row's own reverse search), with BACK_RATIO.  Guided form as above: a missing slot 1 passes
+ *   the distance threshold        dist[i][0] <= max_dist  (fp32, NOT strict, in the unit of the returned dist: the square-rooted L2
+ *                                 distance, or Hamming bits), with MAX_DIST
+ * NO_RATIO: no ratio test at all; a second train row is not needed, so a pair with exactly one train row can match, and mp->ratio is
+ *   not read.  NO_RATIO alone is nearest-neighbour matching, with mutual it is mutual-nearest-neighbour matching.
+ * BACK_RATIO needs mutual != 0 (the reverse search is the mutual check's); with it the ratio test holds in both directions.
+ * Refused with MI_DEGENSAC_EINVAL and a message, before a device is looked for: a bit other than these three; NO_RATIO | BACK_RATIO;
+ * BACK_RATIO without mutual; NO_RATIO or BACK_RATIO together with an honoured second_nn = 1 (FGINN defines a second neighbour for the
+ * forward test only; MAX_DIST with FGINN is allowed); with MAX_DIST a max_dist that is negative or not finite.  A zero-initialised
+ * struct of this size is the rule of decide = 0, and with decide = 0 every output of every call is bit for bit what it was. */
+#define MI_DEGENSAC_DECIDE_NO_RATIO   1
+#define MI_DEGENSAC_DECIDE_BACK_RATIO 2
+#define MI_DEGENSAC_DECIDE_MAX_DIST   4
+/* The dense calls under a rule (mi_degensac_match / mi_degensac_match_filter_dev take scalars and stay as they are).
+ * mi_degensac_match_decide_dev: d_keep[i] = the decision above on a 2-NN result on the device; mp->norm / dim / second_nn are not read
+ * (the rule judges whatever slot 1 holds, so MAX_DIST on an FGINN result is fine).  The mutual check runs when mp->mutual != 0 and
+ * then needs d_back_idx ([n2, 2]: the 2-NN of desc2 in desc1), BACK_RATIO needs d_back_dist too: a NULL one is MI_DEGENSAC_EINVAL;
+ * without mutual both are ignored and may be NULL.  Asynchronous on `stream`.
+ * mi_degensac_match_ex: mi_degensac_match with the rule of mp (norm, dim, ratio, mutual, decide, max_dist; second_nn must be 0: there
+ * are no keypoints here); the reverse search runs when mp->mutual != 0 and keep is asked for. */
+int mi_degensac_match_decide_dev(const mi_degensac_match_params *mp, const int32_t *d_idx, const float *d_dist, int n1,
+                                 const int32_t *d_back_idx /*nullable*/, const float *d_back_dist /*nullable*/, int device, void *stream,
+                                 uint8_t *d_keep);
+int mi_degensac_match_ex(const mi_degensac_match_params *mp, const void *desc1, int n1, const void *desc2, int n2, int device,
+                         int32_t *idx /*[n1,2]*/, float *dist /*[n1,2]*/, uint8_t *keep /*[n1], nullable*/);
 /* Match and verify: per pair the 2-NN search, the ratio test (+ mutual check) of mi_degensac_match, then the estimator of
  * mi_degensac_find_fundamental_batch_dev (homography = 0) or _homography_batch_dev (homography = 1) on the pair's tentatives in
  * query order — exactly the rows mi_degensac_match + the per-pair gather would hand it.  kp1 / kp2: [rows, kp_dim] float64,

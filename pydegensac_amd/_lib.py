@@ -64,6 +64,27 @@ class MatchParams(C.Structure):
                          0.0 if fginn_th is None else float(fginn_th))
 
 
+DECIDE_NO_RATIO, DECIDE_BACK_RATIO, DECIDE_MAX_DIST = 1, 2, 4        # include/mi_degensac.h MI_DEGENSAC_DECIDE_*
+
+
+class MatchParamsEx(MatchParams):
+    """mi_degensac_match_params with the decision rule behind spatial_th (40 bytes): decide = DECIDE_* bit flags, max_dist read with
+    DECIDE_MAX_DIST.  MatchParams keeps the 32-byte layout, which the library reads as decide = 0."""
+    _fields_ = [("decide", C.c_int32), ("max_dist", C.c_float)]
+
+    def __init__(self, norm=0, dim=0, ratio=0.9, mutual=False, fginn_th=None, decide=0, max_dist=0.0):
+        super().__init__(norm, dim, ratio, mutual, fginn_th)
+        self.struct_size = C.sizeof(MatchParamsEx); self.decide = int(decide); self.max_dist = float(max_dist)
+
+
+def match_params(norm, dim, rule, fginn_th=None):
+    """the match params of a checked rule (matcher.check_rule): the 32-byte struct for the plain ratio test, the extended one as soon as
+    a new option is given"""
+    if rule.decide == 0:
+        return MatchParams(norm, dim, rule.ratio, rule.mutual, fginn_th)
+    return MatchParamsEx(norm, dim, rule.ratio, rule.mutual, fginn_th, rule.decide, rule.max_dist)
+
+
 class GuideParams(C.Structure):
     """mi_degensac_guide_params (include/mi_degensac.h): the gate of the guided-matching entry points"""
     _fields_ = [("homography", C.c_int32), ("error_type", C.c_int32), ("px_th", C.c_double), ("struct_size", C.c_int32), ("reserved", C.c_int32)]
@@ -177,6 +198,12 @@ def lib():
         l.mi_degensac_match_knn2_dev.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         l.mi_degensac_match_filter_dev.restype = C.c_int
         l.mi_degensac_match_filter_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        mpp = C.POINTER(MatchParams)
+        if hasattr(l, "mi_degensac_match_decide_dev"):                    # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            l.mi_degensac_match_decide_dev.restype = C.c_int
+            l.mi_degensac_match_decide_dev.argtypes = [mpp, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+            l.mi_degensac_match_ex.restype = C.c_int
+            l.mi_degensac_match_ex.argtypes = [mpp, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, ip, C.POINTER(C.c_float), bp]
         l.mi_degensac_match_knn2_batch_dev.restype = C.c_int
         l.mi_degensac_match_knn2_batch_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, lp, lp, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                        C.c_void_p]
@@ -184,7 +211,6 @@ def lib():
             l.mi_degensac_match_fginn_knn2_batch_dev.restype = C.c_int
             l.mi_degensac_match_fginn_knn2_batch_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, lp, lp, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                                                  C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        mpp = C.POINTER(MatchParams)
         l.mi_degensac_match_verify_batch_dev.restype = C.c_int
         l.mi_degensac_match_verify_batch_dev.argtypes = [C.c_int, mpp, C.c_void_p, C.c_void_p, lp, lp, C.c_void_p, C.c_void_p, C.c_int, C.c_int, pp,
                                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, ip]

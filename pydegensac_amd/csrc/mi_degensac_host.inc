@@ -1072,7 +1072,7 @@ static int mv_check_params(int homography, const mi_degensac_match_params *mp, i
     if (!mp) { set_err("match params are NULL"); return MI_DEGENSAC_EINVAL; }
     if (!mt_norm_known(mp->norm) || mp->dim <= 0) { set_err("bad norm or descriptor dim"); return MI_DEGENSAC_EINVAL; }
     if (const char *e = mt_norm_dim_error(mp->norm, mp->dim)) { set_err("%s", e); return MI_DEGENSAC_EINVAL; }
-    if (!(isfinite(mp->ratio) && mp->ratio > 0.f)) { set_err("ratio must be finite and > 0"); return MI_DEGENSAC_EINVAL; }
+    { mt_rule rule; if (const char *e = mt_decide_rule(mp, 1, &rule)) { set_err("%s", e); return MI_DEGENSAC_EINVAL; } }   /* the ratio too */
     if (kp_dim != 2 && kp_dim != 6) { set_err("keypoint rows must be [n,2] or [n,6]"); return MI_DEGENSAC_EINVAL; }
     { int fg; double r; if (const char *e = mt_second_nn(mp, &fg, &r)) { set_err("%s", e); return MI_DEGENSAC_EINVAL; } }
     if (n_pairs < 0) { set_err("n_pairs < 0"); return MI_DEGENSAC_EINVAL; }
@@ -1246,7 +1246,8 @@ static int mv_match(const mi_degensac_match_params *mp, const void *d_desc1, con
     int fginn; double fginn_r; (void)mt_second_nn(mp, &fginn, &fginn_r);
     if (fginn) { rc = match_rc(mt_batch_fginn(mp->norm, words, q1, q2, kp2, kd, rows.data(), K, (int)n_out, fginn_r, device, s, idx, dist)); if (rc) return rc; }
     if (mutual) { rc = match_rc(mt_batch_knn2(mp->norm, words, q2, q1, rows.data(), K, (int)n_back, 1, device, s, bidx, bdist)); if (rc) return rc; }
-    return match_rc(mt_batch_filter_rank(idx, dist, R.out, R.back, K, mp->ratio, bidx, s, keep, rank, cnt));
+    mt_rule rule; (void)mt_decide_rule(mp, 1, &rule);
+    return match_rc(mt_batch_filter_rank(idx, dist, R.out, R.back, K, rule, bidx, mutual ? bdist : nullptr, s, keep, rank, cnt));
 }
 
 /* The device path of both forms, arguments checked: the matching half, then the estimating half; match / inlier are at the first output

@@ -282,17 +282,15 @@ __global__ __launch_bounds__(256) void mg_rescan_kernel(const uint32_t *dq, cons
 }
 
 /* one workgroup per pair: every query's decision and the pair's number of guided matches */
-__global__ __launch_bounds__(256) void mg_decide_kernel(const int32_t *idx, const float *dist, const int32_t *off1, const int32_t *off2, float ratio,
-                                                        const int32_t *back, int32_t *match, int32_t *count)
+__global__ __launch_bounds__(256) void mg_decide_kernel(const int32_t *idx, const float *dist, const int32_t *off1, const int32_t *off2, mt_rule rule,
+                                                        const int32_t *back, const float *bdist, int32_t *match, int32_t *count)
 {
     __shared__ int wsum[4];
     const int p = blockIdx.x, lo = off1[p], hi = off1[p + 1], b2 = off2[p];
     int c = 0;
     for (int i = lo + (int)threadIdx.x; i < hi; i += 256) {
-        const int j = idx[2 * i];
-        bool ok = j >= 0 && dist[2 * i] < ratio * dist[2 * i + 1];     /* one candidate: dist[1] = inf, the query passes */
-        if (ok && back) ok = back[2 * (b2 + j)] == i - lo;
-        match[i] = ok ? j : -1;
+        const bool ok = mt_decide<true>(rule, idx, dist, i, i - lo, back, bdist, b2);     /* one candidate: dist[1] = inf, the query passes */
+        match[i] = ok ? idx[2 * i] : -1;
         c += ok ? 1 : 0;
     }
     for (int k = 32; k >= 1; k >>= 1) c += __shfl_xor(c, k);
@@ -410,11 +408,11 @@ int mt_batch_guided_fginn(int norm, int words, const void *dq, const void *dt, c
     return 0;
 }
 
-int mt_batch_guided_decide(const int32_t *d_idx, const float *d_dist, const int32_t *d_off1, const int32_t *d_off2, int n_pairs, float ratio,
-                           const int32_t *d_back, hipStream_t s, int32_t *d_match, int32_t *d_count)
+int mt_batch_guided_decide(const int32_t *d_idx, const float *d_dist, const int32_t *d_off1, const int32_t *d_off2, int n_pairs, const mt_rule &rule,
+                           const int32_t *d_back, const float *d_bdist, hipStream_t s, int32_t *d_match, int32_t *d_count)
 {
     if (n_pairs <= 0) return 0;
-    hipLaunchKernelGGL(mg_decide_kernel, dim3(n_pairs), dim3(256), 0, s, d_idx, d_dist, d_off1, d_off2, ratio, d_back, d_match, d_count);
+    hipLaunchKernelGGL(mg_decide_kernel, dim3(n_pairs), dim3(256), 0, s, d_idx, d_dist, d_off1, d_off2, rule, d_back, d_bdist, d_match, d_count);
     MGCHK(hipGetLastError());
     return 0;
 }
@@ -432,10 +430,11 @@ static int mg_check_gate(int norm, int dim, int kp_dim, const mi_degensac_guide_
     return mt_guided_gate(gp->homography, gp->error_type, gp->px_th, g);
 }
 
-static int mg_check_ratio(const mi_degensac_match_params *mp)
+/* the ratio and the decision rule (mt_decide_rule); honour: the entry point reads second_nn, which NO_RATIO / BACK_RATIO exclude */
+static int mg_check_ratio(const mi_degensac_match_params *mp, int honour, mt_rule *rule)
 {
     if (!mp) return mg_einval("match params are NULL");
-    if (!(isfinite(mp->ratio) && mp->ratio > 0.f)) return mg_einval("ratio must be finite and > 0");
+    if (const char *e = mt_decide_rule(mp, honour, rule)) return mg_einval(e);
     return 0;
 }
 
@@ -527,7 +526,7 @@ extern "C" int mi_degensac_match_guided_fginn_knn2_batch_dev(int norm, const voi
 
 /* The device path of both layouts, arguments checked and the device current: entry p's rows are rows[p], n_out output rows and n_back
  * rows of the reverse search in all; every pointer is already at its side's first row, idx / dist / match at the first output row. */
-static int mg_rows_dev(const mi_degensac_match_params *mp, const uint32_t *q1, const uint32_t *q2, const double *kp1, const double *kp2, int kd,
+static int mg_rows_dev(const mi_degensac_match_params *mp, const mt_rule &rule, const uint32_t *q1, const uint32_t *q2, const double *kp1, const double *kp2, int kd,
                        const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t n_back, const double *d_models, const mt_gate &g,
                        const mg_second &sn, int device, hipStream_t s, int32_t *idx, float *dist, int32_t *match, int32_t *d_counts, int32_t *h_counts)
 {
@@ -555,7 +554,7 @@ static int mg_rows_dev(const mi_degensac_match_params *mp, const uint32_t *q1, c
         if (rc) return rc; }
     if (mutual) { rc = mt_batch_guided_knn2(mp->norm, words, q2, q1, kp2, kp1, kd, rows.data(), K, (int)n_back, d_models, g, 1, device, s, bidx, bdist);
         if (rc) return rc; }
-    rc = mt_batch_guided_decide(idx, dist, d_out, d_back, K, mp->ratio, bidx, s, match, cnt); if (rc) return rc;
+    rc = mt_batch_guided_decide(idx, dist, d_out, d_back, K, rule, bidx, mutual ? bdist : nullptr, s, match, cnt); if (rc) return rc;
     if (h_counts) {                                                  /* the only synchronisation, and only when asked for */
         MGCHK(hipMemcpyAsync(h_counts, cnt, (size_t)K * 4, hipMemcpyDeviceToHost, s));
         MGCHK(hipStreamSynchronize(s));
@@ -567,7 +566,7 @@ static int mg_batch_dev(int honour, const mi_degensac_match_params *mp, const vo
                         const double *d_kp1, const double *d_kp2, int kd, int K, const double *d_models, const mi_degensac_guide_params *gp, int device,
                         hipStream_t s, int32_t *d_idx, float *d_dist, int32_t *d_match, int32_t *d_counts, int32_t *h_counts)
 {
-    int rc = mg_check_ratio(mp); if (rc) return rc;
+    mt_rule rule; int rc = mg_check_ratio(mp, honour, &rule); if (rc) return rc;
     mt_gate g; rc = mg_check(mp->norm, mp->dim, kd, gp, off1, off2, K, &g); if (rc) return rc;
     mg_second sn; rc = mg_check_second(mp, honour, &sn); if (rc) return rc;
     if (K == 0) return 0;
@@ -577,7 +576,7 @@ static int mg_batch_dev(int honour, const mi_degensac_match_params *mp, const vo
     const int words = mg_words(mp->norm, mp->dim);
     std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
     mt_ragged_rows(off1, off2, K, o1, o2, rows);
-    return mg_rows_dev(mp, (const uint32_t *)d_desc1 + (size_t)off1[0] * words, (const uint32_t *)d_desc2 + (size_t)off2[0] * words,
+    return mg_rows_dev(mp, rule, (const uint32_t *)d_desc1 + (size_t)off1[0] * words, (const uint32_t *)d_desc2 + (size_t)off2[0] * words,
                        d_kp1 + (size_t)off1[0] * kd, d_kp2 + (size_t)off2[0] * kd, kd, rows, n1, n2, d_models, g, sn, device, s, d_idx + 2 * off1[0],
                        d_dist + 2 * off1[0], d_match + off1[0], d_counts, h_counts);
 }
@@ -604,7 +603,7 @@ extern "C" int mi_degensac_match_guided_fginn_batch_dev(const mi_degensac_match_
 /* The host-pointer forms, arguments checked: side 1 (rows off1[0] .. off1[m1] of desc1 / kp1) goes to the device, side 2 too unless `same`
  * says both sides name the same arrays, then the models; the device path runs on the null stream and idx / dist / match (at the first
  * output row) come back. */
-static int mg_rows_host(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *off1, int m1, const int64_t *off2,
+static int mg_rows_host(const mi_degensac_match_params *mp, const mt_rule &rule, const void *desc1, const void *desc2, const int64_t *off1, int m1, const int64_t *off2,
                         int m2, const double *kp1, const double *kp2, int kd, bool same, const std::vector<mt_pair_rows> &rows, int64_t n_out,
                         int64_t n_back, const double *models, const mt_gate &g, const mg_second &sn, int device, int32_t *idx, float *dist, int32_t *match,
                         int32_t *counts)
@@ -628,7 +627,7 @@ static int mg_rows_host(const mi_degensac_match_params *mp, const void *desc1, c
     }
     MGCHK(hipMemcpy(D + a_mo, models, (size_t)K * 72, hipMemcpyHostToDevice));
     std::vector<int32_t> cnt(K);
-    rc = mg_rows_dev(mp, (const uint32_t *)D, (const uint32_t *)(same ? D : D + a_d2), (const double *)(D + a_k1), (const double *)(D + (same ? a_k1 : a_k2)),
+    rc = mg_rows_dev(mp, rule, (const uint32_t *)D, (const uint32_t *)(same ? D : D + a_d2), (const double *)(D + a_k1), (const double *)(D + (same ? a_k1 : a_k2)),
                      kd, rows, n_out, n_back, (const double *)(D + a_mo), g, sn, device, nullptr, (int32_t *)(D + a_ix), (float *)(D + a_ds),
                      (int32_t *)(D + a_ma), nullptr, cnt.data());
     if (rc) return rc;
@@ -646,7 +645,7 @@ static int mg_batch_host(int honour, const mi_degensac_match_params *mp, const v
                          const int64_t *offsets2, const double *kp1, const double *kp2, int kp_dim, int n_pairs, const double *models,
                          const mi_degensac_guide_params *gp, int device, int32_t *idx, float *dist, int32_t *match, int32_t *counts)
 {
-    int rc = mg_check_ratio(mp); if (rc) return rc;
+    mt_rule rule; int rc = mg_check_ratio(mp, honour, &rule); if (rc) return rc;
     mt_gate g; rc = mg_check(mp->norm, mp->dim, kp_dim, gp, offsets1, offsets2, n_pairs, &g); if (rc) return rc;
     mg_second sn; rc = mg_check_second(mp, honour, &sn); if (rc) return rc;
     const int K = n_pairs;
@@ -654,7 +653,7 @@ static int mg_batch_host(int honour, const mi_degensac_match_params *mp, const v
     if (!desc1 || !desc2 || !kp1 || !kp2 || !models || !idx || !dist || !match) return mg_einval("NULL argument");
     std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
     mt_ragged_rows(offsets1, offsets2, K, o1, o2, rows);
-    return mg_rows_host(mp, desc1, desc2, offsets1, K, offsets2, K, kp1, kp2, kp_dim, false, rows, o1[K], o2[K], models, g, sn, device,
+    return mg_rows_host(mp, rule, desc1, desc2, offsets1, K, offsets2, K, kp1, kp2, kp_dim, false, rows, o1[K], o2[K], models, g, sn, device,
                         idx + 2 * offsets1[0], dist + 2 * offsets1[0], match + offsets1[0], counts);
 }
 
@@ -720,7 +719,7 @@ static int mg_pairs_dev(int honour, const mi_degensac_match_params *mp, const vo
                         const double *d_kp2, int kp_dim, const double *d_models, const mi_degensac_guide_params *gp, int device, hipStream_t s,
                         int32_t *d_idx, float *d_dist, int32_t *d_match, int32_t *d_counts, int32_t *h_counts)
 {
-    int rc = mg_check_ratio(mp); if (rc) return rc;
+    mt_rule rule; int rc = mg_check_ratio(mp, honour, &rule); if (rc) return rc;
     mt_gate g; std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
     rc = mg_check_pairs(mp->norm, mp->dim, kp_dim, gp, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, &g, rows, &n_out, &n_back);
     if (rc) return rc;
@@ -730,7 +729,7 @@ static int mg_pairs_dev(int honour, const mi_degensac_match_params *mp, const vo
         return mg_einval("NULL argument");
     MgDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     const int words = mg_words(mp->norm, mp->dim);
-    return mg_rows_dev(mp, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words, (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words,
+    return mg_rows_dev(mp, rule, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words, (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words,
                        d_kp1 + (size_t)offsets1_host[0] * kp_dim, d_kp2 + (size_t)offsets2_host[0] * kp_dim, kp_dim, rows, n_out, n_back, d_models, g, sn,
                        device, s, d_idx, d_dist, d_match, d_counts, h_counts);
 }
@@ -740,7 +739,7 @@ static int mg_pairs_host(int honour, const mi_degensac_match_params *mp, const v
                          const int64_t *offsets2, int n_images2, const int32_t *pairs, int n_pairs, const double *kp1, const double *kp2, int kp_dim,
                          const double *models, const mi_degensac_guide_params *gp, int device, int32_t *idx, float *dist, int32_t *match, int32_t *counts)
 {
-    int rc = mg_check_ratio(mp); if (rc) return rc;
+    mt_rule rule; int rc = mg_check_ratio(mp, honour, &rule); if (rc) return rc;
     mt_gate g; std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
     rc = mg_check_pairs(mp->norm, mp->dim, kp_dim, gp, offsets1, n_images1, offsets2, n_images2, pairs, n_pairs, &g, rows, &n_out, &n_back);
     if (rc) return rc;
@@ -748,7 +747,7 @@ static int mg_pairs_host(int honour, const mi_degensac_match_params *mp, const v
     if (n_pairs == 0) return 0;
     if (!desc1 || !desc2 || !kp1 || !kp2 || !models || !idx || !dist || !match) return mg_einval("NULL argument");
     const bool same = desc1 == desc2 && kp1 == kp2 && n_images1 == n_images2 && !memcmp(offsets1, offsets2, ((size_t)n_images1 + 1) * 8);
-    return mg_rows_host(mp, desc1, desc2, offsets1, n_images1, offsets2, n_images2, kp1, kp2, kp_dim, same, rows, n_out, n_back, models, g, sn, device,
+    return mg_rows_host(mp, rule, desc1, desc2, offsets1, n_images1, offsets2, n_images2, kp1, kp2, kp_dim, same, rows, n_out, n_back, models, g, sn, device,
                         idx, dist, match, counts);
 }
 

@@ -59,6 +59,58 @@ static inline const char *mt_second_nn(const mi_degensac_match_params *mp, int *
     return mt_spatial_th_error(mp->spatial_th);
 }
 
+/* ---- the decision rule (include/mi_degensac.h MI_DEGENSAC_DECIDE_*): parsed once on the host, evaluated once on the device ---- */
+/* what the three decision kernels take by value */
+struct mt_rule { float ratio; int32_t flags; float max_dist; };
+/* the rule of a match_params.  A caller whose struct_size does not cover decide / max_dist gets flags = 0 whatever those bytes hold.
+ * honour_second_nn: the entry point reads second_nn (an FGINN second neighbour goes with MAX_DIST only).  The ratio is checked here too
+ * (not read under NO_RATIO).  Returns what is wrong, or null; needs no device. */
+static inline const char *mt_decide_rule(const mi_degensac_match_params *mp, int honour_second_nn, mt_rule *r)
+{
+    r->ratio = mp->ratio; r->flags = 0; r->max_dist = 0.f;
+    if (mp->struct_size > 0 && (size_t)mp->struct_size >= offsetof(mi_degensac_match_params, max_dist) + sizeof(float) && mp->decide != 0) {
+        const int d = mp->decide;
+        if (d & ~(MI_DEGENSAC_DECIDE_NO_RATIO | MI_DEGENSAC_DECIDE_BACK_RATIO | MI_DEGENSAC_DECIDE_MAX_DIST))
+            return "decide: unknown bit (MI_DEGENSAC_DECIDE_NO_RATIO = 1, _BACK_RATIO = 2, _MAX_DIST = 4)";
+        if ((d & MI_DEGENSAC_DECIDE_NO_RATIO) && (d & MI_DEGENSAC_DECIDE_BACK_RATIO))
+            return "decide: NO_RATIO and BACK_RATIO exclude each other";
+        if ((d & MI_DEGENSAC_DECIDE_BACK_RATIO) && !mp->mutual)
+            return "decide: BACK_RATIO needs mutual != 0 (it reads the reverse search of the mutual check)";
+        int fginn = 0; double rad;
+        if (honour_second_nn) (void)mt_second_nn(mp, &fginn, &rad);
+        if (fginn && (d & (MI_DEGENSAC_DECIDE_NO_RATIO | MI_DEGENSAC_DECIDE_BACK_RATIO)))
+            return "decide: NO_RATIO and BACK_RATIO do not go with second_nn = 1 (FGINN defines a second neighbour for the forward test only)";
+        if ((d & MI_DEGENSAC_DECIDE_MAX_DIST) && !(mp->max_dist >= 0.f && mp->max_dist <= 3.402823466e+38f))
+            return "max_dist must be finite and >= 0";
+        r->flags = d;
+        if (d & MI_DEGENSAC_DECIDE_MAX_DIST) r->max_dist = mp->max_dist;
+    }
+    if (!(r->flags & MI_DEGENSAC_DECIDE_NO_RATIO) && !(mp->ratio > 0.f && mp->ratio <= 3.402823466e+38f)) return "ratio must be finite and > 0";
+    return nullptr;
+}
+
+/* THE decision of query row i (local index qi in its pair) from the forward 2-NN idx / dist and, when back is set, the reverse one
+ * back / bdist whose rows of this pair start at b2.  GUIDED: the guided form of both ratio tests, where a missing slot 1 (dist = inf)
+ * passes because nothing competes.  With flags = 0 this is the ratio test and mutual check as they always were, load for load. */
+template <bool GUIDED>
+__device__ __forceinline__ bool mt_decide(const mt_rule &r, const int32_t *idx, const float *dist, int i, int qi, const int32_t *back,
+                                          const float *bdist, int b2)
+{
+    const int j = idx[2 * i];
+    bool ok = j >= 0;
+    if (!(r.flags & MI_DEGENSAC_DECIDE_NO_RATIO)) {
+        if (!GUIDED) ok = ok && idx[2 * i + 1] >= 0;
+        ok = ok && dist[2 * i] < r.ratio * dist[2 * i + 1];
+    }
+    if ((r.flags & MI_DEGENSAC_DECIDE_MAX_DIST) && ok) ok = dist[2 * i] <= r.max_dist;
+    if (ok && back) ok = back[2 * (b2 + j)] == qi;
+    if ((r.flags & MI_DEGENSAC_DECIDE_BACK_RATIO) && ok) {
+        const size_t o = 2 * (size_t)(b2 + j);
+        ok = (GUIDED || back[o + 1] >= 0) && bdist[o] < r.ratio * bdist[o + 1];
+    }
+    return ok;
+}
+
 /* the message mi_degensac_match_last_error() returns for the calling thread */
 MT_HIDDEN void mt_set_error(const char *msg);
 
@@ -104,12 +156,14 @@ MT_HIDDEN int mt_batch_fginn(int norm, int words, const void *dq, const void *dt
  * list[out ..], their number to count[p]; no host synchronisation */
 MT_HIDDEN int mt_batch_fginn_mark(const int32_t *idx, const mt_pair_rows *d_rows, int n_pairs, const double *kt, int kd, double rr, hipStream_t s,
                                   int32_t *list, int32_t *count);
-/* ratio test (+ mutual check when d_back is set) and the rank of every kept query among its pair's kept queries; one
+/* the decision rule (mt_decide: ratio test, + mutual check when d_back is set, + what rule.flags adds; d_bdist, the reverse search's
+ * distances next to d_back, is read only under BACK_RATIO) and the rank of every kept query among its pair's kept queries; one
  * workgroup per pair.  d_off1 / d_off2: [K + 1] relative int32 row offsets on the device.  d_off1 says where the pair's idx / dist /
  * keep / rank rows are (the `out` column and the total), d_off2[p] (the only entry read) where its rows of d_back start (the `back`
  * column). */
-MT_HIDDEN int mt_batch_filter_rank(const int32_t *d_idx, const float *d_dist, const int32_t *d_off1, const int32_t *d_off2, int n_pairs, float ratio,
-                                   const int32_t *d_back, hipStream_t s, uint8_t *d_keep, int32_t *d_rank, int32_t *d_count);
+MT_HIDDEN int mt_batch_filter_rank(const int32_t *d_idx, const float *d_dist, const int32_t *d_off1, const int32_t *d_off2, int n_pairs,
+                                   const mt_rule &rule, const int32_t *d_back, const float *d_bdist, hipStream_t s, uint8_t *d_keep, int32_t *d_rank,
+                                   int32_t *d_count);
 /* the estimator's input rows of the E eligible pairs: pts[est_off[e] + rank[i]] = kp rows of query i and of its nearest train row;
  * seeds_e[e] = seeds[pair_of_e[e]].  d_out [K + 1]: output-row offsets (where keep / rank / idx live), d_q1 / d_t2 [K]: the first
  * keypoint row of the pair's query image in kp1 and of its train image in kp2 */
@@ -153,8 +207,9 @@ MT_HIDDEN int mt_batch_guided_fginn(int norm, int words, const void *dq, const v
                                     const mt_pair_rows *rows, int n_pairs, int n_rows, const double *d_models, const mt_gate &g, double r, int device,
                                     hipStream_t s, int32_t *idx, float *dist);
 /* the decision: match[i] = idx[i][0] when it exists and dist[i][0] < ratio * dist[i][1] (and back[b2 + idx[i][0]][0] == i - lo when
- * d_back is set), else -1; count[p] (nullable) = guided matches of pair p.  d_off1 [K + 1]: the output-row offsets (the `out` column and
+ * d_back is set; the guided form of mt_decide under rule.flags, d_bdist as for mt_batch_filter_rank), else -1; count[p] (nullable) = guided matches of pair p.  d_off1 [K + 1]: the output-row offsets (the `out` column and
  * the total), d_off2[p] (the only entry read): where the pair's rows of d_back start (the `back` column), as for mt_batch_filter_rank */
-MT_HIDDEN int mt_batch_guided_decide(const int32_t *d_idx, const float *d_dist, const int32_t *d_off1, const int32_t *d_off2, int n_pairs, float ratio,
-                                     const int32_t *d_back, hipStream_t s, int32_t *d_match, int32_t *d_count);
+MT_HIDDEN int mt_batch_guided_decide(const int32_t *d_idx, const float *d_dist, const int32_t *d_off1, const int32_t *d_off2, int n_pairs,
+                                     const mt_rule &rule, const int32_t *d_back, const float *d_bdist, hipStream_t s, int32_t *d_match,
+                                     int32_t *d_count);
 #endif /* MI_MATCH_BATCH_H */

@@ -230,16 +230,14 @@ __global__ void mt_merge_kernel(const mt_best *part, int splits, int n1, int l2,
     dist[2 * i] = l2 ? sqrtf(m.d0) : m.d0; dist[2 * i + 1] = l2 ? sqrtf(m.d1) : m.d1;
 }
 
-/* keep[i] = second-nearest-neighbour ratio test (strict, as the example's `m.distance < ratio * n.distance`; a query with
- * fewer than two train rows never passes) and, when back != 0, the mutual check back[idx[i][0]][0] == i */
-__global__ void mt_filter_kernel(const int32_t *idx, const float *dist, int n1, float ratio, const int32_t *back, uint8_t *keep)
+/* keep[i] = the decision rule (mt_decide, mi_match_batch.h).  With rule.flags = 0: the second-nearest-neighbour ratio test (strict, as
+ * the example's `m.distance < ratio * n.distance`; a query with fewer than two train rows never passes) and, when back != 0, the
+ * mutual check back[idx[i][0]][0] == i */
+__global__ void mt_filter_kernel(const int32_t *idx, const float *dist, int n1, mt_rule rule, const int32_t *back, const float *bdist, uint8_t *keep)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n1) return;
-    const int j = idx[2 * i], j2 = idx[2 * i + 1];
-    bool ok = j >= 0 && j2 >= 0 && dist[2 * i] < ratio * dist[2 * i + 1];
-    if (ok && back) ok = back[2 * j] == i;
-    keep[i] = ok ? 1 : 0;
+    keep[i] = mt_decide<false>(rule, idx, dist, i, i, back, bdist, 0) ? 1 : 0;
 }
 
 /* utils.py:24-41 convert_cv2_kpts_to_xyA on the device: (x, y, size, angle in degrees) -> (x, y, s cos a, s sin a,
@@ -259,7 +257,8 @@ __global__ void mt_kpts_to_xyA_kernel(const float *kp, int n, double *out)
  * among the pair's kept queries in ascending query order (-1 when not kept), count[p] their number.  Positions come from
  * wave ballots and a four-entry prefix over the waves, so they do not depend on scheduling. */
 __global__ __launch_bounds__(256) void mt_filter_rank_kernel(const int32_t *idx, const float *dist, const int32_t *off1, const int32_t *off2,
-                                                             float ratio, const int32_t *back, uint8_t *keep, int32_t *rank, int32_t *count)
+                                                             mt_rule rule, const int32_t *back, const float *bdist, uint8_t *keep, int32_t *rank,
+                                                             int32_t *count)
 {
     __shared__ int wsum[4];
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -268,11 +267,7 @@ __global__ __launch_bounds__(256) void mt_filter_rank_kernel(const int32_t *idx,
     for (int i0 = lo; i0 < hi; i0 += 256) {
         const int i = i0 + tid;
         bool ok = false;
-        if (i < hi) {
-            const int j = idx[2 * i], j2 = idx[2 * i + 1];
-            ok = j >= 0 && j2 >= 0 && dist[2 * i] < ratio * dist[2 * i + 1];
-            if (ok && back) ok = back[2 * (b2 + j)] == i - lo;
-        }
+        if (i < hi) ok = mt_decide<false>(rule, idx, dist, i, i - lo, back, bdist, b2);
         const unsigned long long bal = __ballot(ok);
         if (lane == 0) wsum[wv] = __popcll(bal);
         __syncthreads();
@@ -437,14 +432,61 @@ extern "C" int mi_degensac_match_filter_dev(const int32_t *d_idx, const float *d
     if (n1 < 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
     MtDevGuard g; int rc = g.enter(device); if (rc) return rc;
     if (n1 == 0) return 0;
-    hipLaunchKernelGGL(mt_filter_kernel, dim3((n1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_idx, d_dist, n1, ratio, d_back_idx_or_null, d_keep);
+    hipLaunchKernelGGL(mt_filter_kernel, dim3((n1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_idx, d_dist, n1, mt_rule{ratio, 0, 0.f},
+        d_back_idx_or_null, (const float *)nullptr, d_keep);
     MTCHK(hipGetLastError());
     return 0;
 }
 
-/* host pointers: stage, search both directions when the mutual check is asked for, filter, copy back */
+/* the rule of a dense call: no keypoints here, so an FGINN request can only be refused */
+static int mt_dense_rule(const mi_degensac_match_params *mp, int honour_second_nn, mt_rule *rule)
+{
+    if (!mp) { snprintf(mt_err, sizeof mt_err, "match params are NULL"); return MI_DEGENSAC_EINVAL; }
+    if (const char *e = mt_decide_rule(mp, honour_second_nn, rule)) { snprintf(mt_err, sizeof mt_err, "%s", e); return MI_DEGENSAC_EINVAL; }
+    return 0;
+}
+
+extern "C" int mi_degensac_match_decide_dev(const mi_degensac_match_params *mp, const int32_t *d_idx, const float *d_dist, int n1,
+                                            const int32_t *d_back_idx, const float *d_back_dist, int device, void *stream, uint8_t *d_keep)
+{
+    mt_rule rule; int rc = mt_dense_rule(mp, 0, &rule); if (rc) return rc;
+    if (n1 < 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
+    const bool mutual = mp->mutual != 0;
+    if (n1 > 0 && (!d_idx || !d_dist || !d_keep)) { snprintf(mt_err, sizeof mt_err, "NULL argument"); return MI_DEGENSAC_EINVAL; }
+    if (n1 > 0 && mutual && !d_back_idx) { snprintf(mt_err, sizeof mt_err, "mutual needs d_back_idx, the reverse search's idx"); return MI_DEGENSAC_EINVAL; }
+    if (n1 > 0 && (rule.flags & MI_DEGENSAC_DECIDE_BACK_RATIO) && !d_back_dist) {
+        snprintf(mt_err, sizeof mt_err, "BACK_RATIO needs d_back_dist, the reverse search's dist"); return MI_DEGENSAC_EINVAL; }
+    MtDevGuard g; rc = g.enter(device); if (rc) return rc;
+    if (n1 == 0) return 0;
+    hipLaunchKernelGGL(mt_filter_kernel, dim3((n1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_idx, d_dist, n1, rule,
+        mutual ? d_back_idx : (const int32_t *)nullptr, mutual ? d_back_dist : (const float *)nullptr, d_keep);
+    MTCHK(hipGetLastError());
+    return 0;
+}
+
+/* host pointers: stage, search both directions when the mutual check is asked for, decide, copy back; rule = null: the scalar call's
+ * ratio test through mi_degensac_match_filter_dev, as it always ran */
+static int mt_match_host(int norm, const void *desc1, int n1, const void *desc2, int n2, int dim, float ratio, int mutual, const mt_rule *rule,
+                         int device, int32_t *idx, float *dist, uint8_t *keep);
+
 extern "C" int mi_degensac_match(int norm, const void *desc1, int n1, const void *desc2, int n2, int dim, float ratio, int mutual, int device,
                                  int32_t *idx /* [n1,2] */, float *dist /* [n1,2] */, uint8_t *keep /* [n1] or NULL */)
+{
+    return mt_match_host(norm, desc1, n1, desc2, n2, dim, ratio, mutual, nullptr, device, idx, dist, keep);
+}
+
+extern "C" int mi_degensac_match_ex(const mi_degensac_match_params *mp, const void *desc1, int n1, const void *desc2, int n2, int device,
+                                    int32_t *idx, float *dist, uint8_t *keep)
+{
+    mt_rule rule; int rc = mt_dense_rule(mp, 1, &rule); if (rc) return rc;
+    int fginn; double r;
+    if (const char *e = mt_second_nn(mp, &fginn, &r)) { snprintf(mt_err, sizeof mt_err, "%s", e); return MI_DEGENSAC_EINVAL; }
+    if (fginn) { snprintf(mt_err, sizeof mt_err, "the FGINN rule (second_nn = 1) is not part of the dense call: it has no keypoints"); return MI_DEGENSAC_EINVAL; }
+    return mt_match_host(mp->norm, desc1, n1, desc2, n2, mp->dim, mp->ratio, mp->mutual, &rule, device, idx, dist, keep);
+}
+
+static int mt_match_host(int norm, const void *desc1, int n1, const void *desc2, int n2, int dim, float ratio, int mutual, const mt_rule *rule,
+                         int device, int32_t *idx, float *dist, uint8_t *keep)
 {
     if (!desc1 || !desc2 || !idx || !dist || n1 < 0 || n2 < 0 || dim <= 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
     int rc = mt_check_norm(norm, dim); if (rc) return rc;
@@ -465,7 +507,11 @@ extern "C" int mi_degensac_match(int norm, const void *desc1, int n1, const void
             MTCHK(hipMalloc((void **)&dbi, (size_t)n2 * 8)); MTCHK(hipMalloc((void **)&dbd, (size_t)n2 * 8));
             rc = mi_degensac_match_knn2_dev(norm, d2, n2, d1, n1, dim, device, nullptr, dbi, dbd); if (rc) return rc;
         }
-        rc = mi_degensac_match_filter_dev(di, dd, n1, ratio, dbi, device, nullptr, dk); if (rc) return rc;
+        if (!rule) { rc = mi_degensac_match_filter_dev(di, dd, n1, ratio, dbi, device, nullptr, dk); if (rc) return rc; }
+        else {
+            hipLaunchKernelGGL(mt_filter_kernel, dim3((n1 + 255) / 256), dim3(256), 0, (hipStream_t) nullptr, di, dd, n1, *rule, dbi, dbd, dk);
+            MTCHK(hipGetLastError());
+        }
     }
     MTCHK(hipDeviceSynchronize());
     MTCHK(hipMemcpy(idx, di, (size_t)n1 * 8, hipMemcpyDeviceToHost)); MTCHK(hipMemcpy(dist, dd, (size_t)n1 * 8, hipMemcpyDeviceToHost));
@@ -588,11 +634,12 @@ int mt_batch_knn2(int norm, int words, const void *dq, const void *dt, const mt_
     return 0;
 }
 
-int mt_batch_filter_rank(const int32_t *d_idx, const float *d_dist, const int32_t *d_off1, const int32_t *d_off2, int n_pairs, float ratio,
-                         const int32_t *d_back, hipStream_t s, uint8_t *d_keep, int32_t *d_rank, int32_t *d_count)
+int mt_batch_filter_rank(const int32_t *d_idx, const float *d_dist, const int32_t *d_off1, const int32_t *d_off2, int n_pairs, const mt_rule &rule,
+                         const int32_t *d_back, const float *d_bdist, hipStream_t s, uint8_t *d_keep, int32_t *d_rank, int32_t *d_count)
 {
     if (n_pairs <= 0) return 0;
-    hipLaunchKernelGGL(mt_filter_rank_kernel, dim3(n_pairs), dim3(256), 0, s, d_idx, d_dist, d_off1, d_off2, ratio, d_back, d_keep, d_rank, d_count);
+    hipLaunchKernelGGL(mt_filter_rank_kernel, dim3(n_pairs), dim3(256), 0, s, d_idx, d_dist, d_off1, d_off2, rule, d_back, d_bdist, d_keep, d_rank,
+        d_count);
     MTCHK(hipGetLastError());
     return 0;
 }

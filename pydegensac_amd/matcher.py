@@ -9,6 +9,7 @@ descriptors the Hamming norm.  norm="l2_u8" is the L2 norm on uint8 rows as they
 SOSNet / SuperPoint; dim <= 256): the squared distance is an exact integer below 2^24, formed on the int8 matrix cores, and idx / dist
 are bit for bit those of norm="l2" on the same rows cast to float32.  No CPU path: without the HIP library / a gfx950 device every
 call raises."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -46,15 +47,61 @@ def _prep(desc1, desc2, norm):
     return _NORMS[norm], np.ascontiguousarray(a), np.ascontiguousarray(b)
 
 
-def _run(desc1, desc2, norm, ratio, mutual, want_keep, device):
+# the decision rule of a matcher call (include/mi_degensac.h MI_DEGENSAC_DECIDE_*): ratio as a float (1.0 where it is not read), mutual as
+# a bool, decide = the bit flags, max_dist as a float (0.0 where it is not read)
+Rule = collections.namedtuple("Rule", "ratio mutual decide max_dist")
+
+
+def check_rule(ratio, mutual=False, max_dist=None, fginn=False):
+    """The shared check of ratio / mutual / max_dist of every matcher call -> Rule; raises ValueError.
+    ratio: a finite number > 0, or None = no ratio test (a query is a tentative when it has a nearest neighbour; one train row is enough).
+    mutual: False, True, or "ratio" = mutual nearest neighbours whose ratio test also holds at the train row's own reverse search.
+    max_dist: None, or a finite number >= 0: also require dist[0] <= max_dist (the returned L2 distance, or Hamming bits).
+    fginn: the call runs the FGINN second neighbour, which is defined for the forward ratio test only (max_dist goes with it)."""
+    decide = 0
+    if ratio is None:
+        decide |= _lib.DECIDE_NO_RATIO; r = 1.0
+    else:
+        try:
+            r = float(ratio)
+        except (TypeError, ValueError):
+            raise ValueError("ratio should be a number, or None for no ratio test")
+        if not np.isfinite(r) or r <= 0:
+            raise ValueError("ratio should be finite and > 0")
+    if isinstance(mutual, str):
+        if mutual != "ratio":
+            raise ValueError('mutual should be False, True or "ratio"')
+        if ratio is None:
+            raise ValueError('mutual="ratio" needs a ratio: ratio=None is no ratio test in either direction')
+        decide |= _lib.DECIDE_BACK_RATIO
+    md = 0.0
+    if max_dist is not None:
+        try:
+            md = float(max_dist)
+        except (TypeError, ValueError):
+            raise ValueError("max_dist should be a number")
+        if not (np.isfinite(md) and md >= 0 and md <= float(np.finfo(np.float32).max)):
+            raise ValueError("max_dist should be finite and >= 0")
+        decide |= _lib.DECIDE_MAX_DIST
+    if fginn and decide & (_lib.DECIDE_NO_RATIO | _lib.DECIDE_BACK_RATIO):
+        raise ValueError('the FGINN second neighbour belongs to the forward ratio test: it goes with max_dist, not with ratio=None or mutual="ratio"')
+    return Rule(r, bool(mutual), decide, md)
+
+
+def _run(desc1, desc2, norm, ratio, mutual, want_keep, device, max_dist=None):
+    rule = check_rule(ratio, mutual, max_dist)
     code, a, b = _prep(desc1, desc2, norm)
     n1, n2, dim = a.shape[0], b.shape[0], a.shape[1]
     idx = np.full((n1, 2), -1, np.int32); dist = np.full((n1, 2), np.inf, np.float32)
     keep = np.zeros(n1, np.uint8) if want_keep else None
-    rc = _lib.lib().mi_degensac_match(code, a.ctypes.data_as(C.c_void_p), n1, b.ctypes.data_as(C.c_void_p), n2, dim, float(ratio),
-                                      int(bool(mutual)), int(device), idx.ctypes.data_as(C.POINTER(C.c_int32)),
-                                      dist.ctypes.data_as(C.POINTER(C.c_float)),
-                                      keep.ctypes.data_as(C.POINTER(C.c_uint8)) if want_keep else None)
+    out = (idx.ctypes.data_as(C.POINTER(C.c_int32)), dist.ctypes.data_as(C.POINTER(C.c_float)),
+           keep.ctypes.data_as(C.POINTER(C.c_uint8)) if want_keep else None)
+    if rule.decide == 0:
+        rc = _lib.lib().mi_degensac_match(code, a.ctypes.data_as(C.c_void_p), n1, b.ctypes.data_as(C.c_void_p), n2, dim, rule.ratio,
+                                          int(rule.mutual), int(device), *out)
+    else:
+        mp = _lib.match_params(code, dim, rule)
+        rc = _lib.lib().mi_degensac_match_ex(C.byref(mp), a.ctypes.data_as(C.c_void_p), n1, b.ctypes.data_as(C.c_void_p), n2, int(device), *out)
     if rc != 0:
         msg = _lib.lib().mi_degensac_match_last_error().decode()
         if rc == -1:
@@ -70,20 +117,43 @@ def knn_match(desc1, desc2, norm=None, device=0):
     return idx, dist
 
 
-def match_snn(desc1, desc2, ratio=0.9, mutual=False, norm=None, device=0):
+def match_snn(desc1, desc2, ratio=0.9, mutual=False, norm=None, device=0, *, max_dist=None):
     """Second-nearest-neighbour ratio test (`m.distance < ratio * n.distance`), optionally restricted to mutual nearest
-    neighbours: (query indices, train indices, distances) of the tentative correspondences, in query order."""
-    idx, dist, keep = _run(desc1, desc2, norm, ratio, mutual, True, device)
+    neighbours: (query indices, train indices, distances) of the tentative correspondences, in query order.
+    ratio=None, mutual="ratio" and max_dist: the decision rule of check_rule (match_nn / match_mnn / match_smnn name its usual forms)."""
+    idx, dist, keep = _run(desc1, desc2, norm, ratio, mutual, True, device, max_dist)
     sel = np.flatnonzero(keep)
     return sel.astype(np.int64), idx[sel, 0].astype(np.int64), dist[sel, 0]
 
 
-def match_fginn(desc1, desc2, kps2, ratio=0.9, spatial_th=10.0, mutual=False, norm=None, device=0):
+def match_nn(desc1, desc2, max_dist=None, norm=None, device=0):
+    """Nearest-neighbour matching, the rule of learned descriptors without a ratio test: every row of desc1 with a nearest row in desc2
+    (one train row is enough), optionally only at distance <= max_dist.  Returns the triple of match_snn."""
+    return match_snn(desc1, desc2, None, False, norm, device, max_dist=max_dist)
+
+
+def match_mnn(desc1, desc2, max_dist=None, norm=None, device=0):
+    """Mutual-nearest-neighbour matching: match_nn restricted to the pairs that are each other's nearest neighbour, optionally only at
+    distance <= max_dist (SuperPoint / DISK / ALIKED style).  Returns the triple of match_snn."""
+    return match_snn(desc1, desc2, None, True, norm, device, max_dist=max_dist)
+
+
+def match_smnn(desc1, desc2, ratio=0.9, max_dist=None, norm=None, device=0):
+    """Mutual nearest neighbours whose ratio test holds in BOTH directions: `d0 < ratio * d1` at the query and at its train row's own
+    reverse search (a train row with a single query row has no second distance and is dropped), optionally only at distance <= max_dist.
+    Returns the triple of match_snn."""
+    if ratio is None:
+        raise ValueError("match_smnn is the ratio test in both directions: ratio should be a number (match_mnn has none)")
+    return match_snn(desc1, desc2, ratio, "ratio", norm, device, max_dist=max_dist)
+
+
+def match_fginn(desc1, desc2, kps2, ratio=0.9, spatial_th=10.0, mutual=False, norm=None, device=0, *, max_dist=None):
     """match_snn with the FGINN ratio test (first geometrically inconsistent neighbour, Mishkin et al.): the second distance of
     `m.distance < ratio * n.distance` comes from the nearest row of desc2 whose keypoint (kps2 [n2, >= 2]: x, y, ...) lies at least
     spatial_th pixels from the nearest neighbour's keypoint, so that the twin keypoints a detector emits for one structure (a second
     orientation, a neighbouring scale) do not veto a correct match.  A query whose every other train row lies inside the radius is
     not kept; the mutual check is the plain one.  Returns (query indices, train indices, distances) in query order."""
+    rule = check_rule(ratio, mutual, max_dist, fginn=True)
     code, a, b = _prep(desc1, desc2, norm)
     r = check_fginn_th(spatial_th, "spatial_th")
     k2 = np.asarray(kps2, np.float64)
@@ -99,15 +169,17 @@ def match_fginn(desc1, desc2, kps2, ratio=0.9, spatial_th=10.0, mutual=False, no
     ta, tb = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
     idx, dist = tensor_api.knn_match_fginn_batch_tensors(ta, tb, torch.from_numpy(k2).to(dev), [a.shape[0]], [b.shape[0]], r, name)
     back = tensor_api.knn_match_tensors(tb, ta, name)[0] if mutual and b.shape[0] > 0 else None
-    keep = tensor_api.match_filter_tensors(idx, dist, ratio, back)
+    keep = tensor_api.match_filter_tensors(idx, dist, ratio, back) if rule.decide == 0 else \
+        tensor_api.match_decide_tensors(idx, dist, ratio, back, None, max_dist)
     idx = idx.cpu().numpy(); dist = dist.cpu().numpy()
     sel = np.flatnonzero(keep.cpu().numpy())
     return sel.astype(np.int64), idx[sel, 0].astype(np.int64), dist[sel, 0]
 
 
-def tentative_points(kps1, kps2, desc1, desc2, ratio=0.9, mutual=False, norm=None, device=0):
-    """Matched coordinates ready for findHomography / findFundamentalMatrix: kps are [n, >=2] arrays (x, y, ...)"""
-    q, t, _ = match_snn(desc1, desc2, ratio, mutual, norm, device)
+def tentative_points(kps1, kps2, desc1, desc2, ratio=0.9, mutual=False, norm=None, device=0, *, max_dist=None):
+    """Matched coordinates ready for findHomography / findFundamentalMatrix: kps are [n, >=2] arrays (x, y, ...); ratio / mutual /
+    max_dist as for match_snn"""
+    q, t, _ = match_snn(desc1, desc2, ratio, mutual, norm, device, max_dist=max_dist)
     a = np.asarray(kps1, np.float64); b = np.asarray(kps2, np.float64)
     return a[q], b[t]
 
@@ -138,12 +210,13 @@ def _check_sides(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_
     """model, ratio, norm and the descriptor / keypoint arrays of the two sides, on shapes and dtype names -> (norm code, "xy" / "kpts")"""
     if model not in ("F", "H"):
         raise ValueError("model should be 'F' or 'H'")
-    try:
-        r = float(ratio)
-    except (TypeError, ValueError):
-        raise ValueError("ratio should be a number")
-    if not np.isfinite(r) or r <= 0:
-        raise ValueError("ratio should be finite and > 0")
+    if ratio is not None:                       # None = no ratio test (check_rule)
+        try:
+            r = float(ratio)
+        except (TypeError, ValueError):
+            raise ValueError("ratio should be a number")
+        if not np.isfinite(r) or r <= 0:
+            raise ValueError("ratio should be finite and > 0")
     if len(d1_shape) != 2 or len(d2_shape) != 2 or d1_shape[1] != d2_shape[1] or d1_shape[1] == 0:
         raise ValueError("descriptors should be [N1, dim] and [N2, dim] with the same dim")
     t1, t2 = _dtype_name(d1_dtype), _dtype_name(d2_dtype)
@@ -384,14 +457,14 @@ def _finish_pairs(code, kind, A, B, K1, K2, device):
     return A, B, np.ascontiguousarray(K1, np.float64), np.ascontiguousarray(K2, np.float64)
 
 
-def _guided_host(code, A, B, K1, K2, o1, o2, Md, model, ratio, mutual, px, et, device, fginn_r=None):
+def _guided_host(code, A, B, K1, K2, o1, o2, Md, model, rule, px, et, device, fginn_r=None):
     """mi_degensac_match_guided_batch (fginn_r, a checked radius: mi_degensac_match_guided_fginn_batch) on prepared host arrays; Md =
     [K, 9] driver-form models.  Returns (match, idx, dist, counts)."""
     K = len(o1) - 1; n1 = A.shape[0]
     idx = np.full((n1, 2), -1, np.int32); dist = np.full((n1, 2), np.inf, np.float32); match = np.full(n1, -1, np.int32)
     cnt = np.zeros(K, np.int32)
     Md = np.ascontiguousarray(Md, np.float64).reshape(K, 9)
-    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual, fginn_r); gp = _lib.GuideParams(model == "H", et, px)
+    mp = _lib.match_params(code, A.shape[1], rule, fginn_r); gp = _lib.GuideParams(model == "H", et, px)
     rc = guided_entry("batch", fginn_r)(C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p),
                                         o1.ctypes.data_as(C.POINTER(C.c_int64)), o2.ctypes.data_as(C.POINTER(C.c_int64)),
                                         _lib.dptr(K1), _lib.dptr(K2), K1.shape[1], K, _lib.dptr(Md), C.byref(gp), int(device),
@@ -402,7 +475,7 @@ def _guided_host(code, A, B, K1, K2, o1, o2, Md, model, ratio, mutual, px, et, d
 
 
 def guided_match_batch(kps1_list, kps2_list, desc1_list, desc2_list, models, model="F", ratio=0.9, mutual=False, px_th=None,
-                       error_type="sampson", norm=None, driver_form=False, device=0, fginn_th=None):
+                       error_type="sampson", norm=None, driver_form=False, device=0, fginn_th=None, *, max_dist=None):
     """Guided matching of K image pairs in one call: per pair the 2-NN search restricted to the train keypoints that are inliers of
     the pair's model (models [K, 3, 3] float64: F, or the user-facing H that findHomography returns; driver_form=True takes them in the
     driver's form, H_c = inv(H)^T), with the estimator's residual for error_type and its threshold from px_th (None = the model's
@@ -413,7 +486,10 @@ def guided_match_batch(kps1_list, kps2_list, desc1_list, desc2_list, models, mod
     fginn_th: None = the second gated row decides; a number (pixels of kps2, finite and >= 0) takes the second distance from the nearest
     GATED row whose keypoint lies at least that far from the nearest gated row's (FGINN inside the gate), so a keypoint's own twin (a
     second orientation, a neighbouring scale), which lies inside the band too, no longer fails the ratio test.  A query whose only gated
-    companions lie inside the radius is KEPT (dist1 = inf: nothing competes with it), unlike match_fginn, which needs a second row."""
+    companions lie inside the radius is KEPT (dist1 = inf: nothing competes with it), unlike match_fginn, which needs a second row.
+    ratio=None, mutual="ratio" and max_dist: the rule of check_rule; the reverse ratio test takes the guided form too (a train row with a
+    single gated query row passes)."""
+    rule = check_rule(ratio, mutual, max_dist, fginn=fginn_th is not None)
     code, kind, A, B, K1, K2, o1, o2 = _stack_pairs(kps1_list, kps2_list, desc1_list, desc2_list, model, ratio, norm, device)
     K = len(o1) - 1
     M = np.asarray(models)
@@ -421,7 +497,7 @@ def guided_match_batch(kps1_list, kps2_list, desc1_list, desc2_list, models, mod
     fr = None if fginn_th is None else check_fginn_th(fginn_th)
     A, B, K1, K2 = _finish_pairs(code, kind, A, B, K1, K2, device)
     Md = M if (model == "F" or driver_form) else _h_driver_form(M)
-    match, _, dist, _ = _guided_host(code, A, B, K1, K2, o1, o2, Md, model, ratio, mutual, px, et, device, fr)
+    match, _, dist, _ = _guided_host(code, A, B, K1, K2, o1, o2, Md, model, rule, px, et, device, fr)
     out = []
     for p in range(K):
         m = match[o1[p]:o1[p + 1]]
@@ -431,16 +507,17 @@ def guided_match_batch(kps1_list, kps2_list, desc1_list, desc2_list, models, mod
 
 
 def guided_match(kps1, kps2, desc1, desc2, M, model="F", ratio=0.9, mutual=False, px_th=None, error_type="sampson", norm=None,
-                 driver_form=False, device=0, fginn_th=None):
+                 driver_form=False, device=0, fginn_th=None, *, max_dist=None):
     """guided_match_batch for one pair: (query indices, train indices, distances) of the guided matches under model M [3, 3];
     fginn_th as there (FGINN inside the gate; a query whose only gated companions are its twins is kept)"""
     return guided_match_batch([kps1], [kps2], [desc1], [desc2], np.asarray(M)[None], model, ratio, mutual, px_th, error_type, norm,
-                              driver_form, device, fginn_th)[0]
+                              driver_form, device, fginn_th, max_dist=max_dist)[0]
 
 
 def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
                            max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
-                           enable_degeneracy_check=True, seeds=None, norm=None, device=0, guided=False, fginn_th=None, guided_fginn_th=None):
+                           enable_degeneracy_check=True, seeds=None, norm=None, device=0, guided=False, fginn_th=None, guided_fginn_th=None, *,
+                           max_dist=None):
     """K image pairs from descriptors and keypoints to models in one call: per pair the 2-NN ratio test of match_snn (optionally
     mutual), then findFundamentalMatrix (model "F") or findHomography ("H") on its tentatives, all pairs in one launch.  kps are
     float64 [n, 2] / [n, 6] rows or float32 [n, 4] keypoints (x, y, size, angle -> LAF rows as kpts_to_xyA); descriptors float32
@@ -453,14 +530,18 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
     fginn_th: None = the plain ratio test; a number switches it to the FGINN ratio test of match_fginn at that radius in pixels of
     kps2 (the guided stage keeps its own gate and decision).
     guided_fginn_th: None, or the radius of guided_match_batch(fginn_th=) for the guided stage; only with guided=True (ValueError else).
+    ratio=None, mutual="ratio" and max_dist: the rule of check_rule, for the tentatives and (guided form) for the guided stage.
     last_stats() holds the per-pair statistics, with "tentatives"."""
     gfr = check_guided_fginn_th(guided, guided_fginn_th)
+    rule = check_rule(ratio, mutual, max_dist, fginn=fginn_th is not None)
+    if gfr is not None:
+        check_rule(ratio, mutual, max_dist, fginn=True)
     code, kind, A, B, K1, K2, o1, o2 = _stack_pairs(kps1_list, kps2_list, desc1_list, desc2_list, model, ratio, norm, device, fginn_th)
     K = len(o1) - 1
     prm = estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
     A, B, K1, K2 = _finish_pairs(code, kind, A, B, K1, K2, device)
     sd = _seeds_u32(seeds, K)
-    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual, fginn_th)
+    mp = _lib.match_params(code, A.shape[1], rule, fginn_th)
     n1 = A.shape[0]
     M = np.zeros((K, 9)); match = np.full(n1, -1, np.int32); inl = np.zeros(n1, np.uint8)
     st = np.zeros((K, 16), np.int32); cnt = np.zeros(K, np.int32)
@@ -474,7 +555,7 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
     _set_last_stats(st, cnt)
     gm = None
     if guided:                  # the driver-form models as the library wrote them, before the inversion below
-        gm = _guided_host(code, A, B, K1, K2, o1, o2, M, model, ratio, mutual, prm.px_th, prm.error_type, device, gfr)[0]
+        gm = _guided_host(code, A, B, K1, K2, o1, o2, M, model, rule, prm.px_th, prm.error_type, device, gfr)[0]
     M = M.reshape(K, 3, 3)
     if model == "H":
         M = _h_user_form(M)
@@ -521,7 +602,7 @@ def _finish_stores(code, kind, A, K1, B, K2, one, device):
 
 def match_and_verify_pairs(kps_list, desc_list, pairs, model="F", ratio=0.9, mutual=False, px_th=None, conf=None, max_iters=None,
                            laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True, enable_degeneracy_check=True, seeds=None,
-                           norm=None, device=0, guided=False, fginn_th=None, kps2_list=None, desc2_list=None):
+                           norm=None, device=0, guided=False, fginn_th=None, kps2_list=None, desc2_list=None, *, max_dist=None):
     """match_and_verify_batch over a pair list: descriptors and keypoints are given ONCE per image (kps_list[i], desc_list[i]) and
     pairs [K, 2] says which (i, j) to run, queries = image i, train set = image j (exhaustive_pairs(n) for a whole collection).  With
     kps2_list / desc2_list the train images come from that second store (queries against a database), else from the same one.  The
@@ -532,12 +613,12 @@ def match_and_verify_pairs(kps_list, desc_list, pairs, model="F", ratio=0.9, mut
     match_and_verify_fginn_pairs runs the FGINN ratio test over a list.
     last_stats() holds the per-pair statistics."""
     return _match_verify_pairs(None, kps_list, desc_list, pairs, model, ratio, mutual, px_th, conf, max_iters, laf_consistensy_coef, error_type,
-                               symmetric_error_check, enable_degeneracy_check, seeds, norm, device, guided, fginn_th, kps2_list, desc2_list)
+                               symmetric_error_check, enable_degeneracy_check, seeds, norm, device, guided, fginn_th, kps2_list, desc2_list, max_dist)
 
 
 def match_and_verify_fginn_pairs(kps_list, desc_list, pairs, fginn_th, model="F", ratio=0.9, mutual=False, px_th=None, conf=None, max_iters=None,
                                  laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True, enable_degeneracy_check=True,
-                                 seeds=None, norm=None, device=0, guided=False, kps2_list=None, desc2_list=None):
+                                 seeds=None, norm=None, device=0, guided=False, kps2_list=None, desc2_list=None, *, max_dist=None):
     """match_and_verify_pairs with the FGINN ratio test of match_fginn in front of the estimator: fginn_th is the radius in pixels of the
     train image's keypoints, a finite number >= 0.  Stores (one, or two with kps2_list / desc2_list; a store named on both sides is
     uploaded once), list, seeds and the returned tuple are those of match_and_verify_pairs; per entry the results are bit for bit those
@@ -545,13 +626,14 @@ def match_and_verify_fginn_pairs(kps_list, desc_list, pairs, fginn_th, model="F"
     guided_match_pairs takes the models this call returns.  last_stats() holds the per-pair statistics."""
     r = check_fginn_th(fginn_th)
     return _match_verify_pairs(r, kps_list, desc_list, pairs, model, ratio, mutual, px_th, conf, max_iters, laf_consistensy_coef, error_type,
-                               symmetric_error_check, enable_degeneracy_check, seeds, norm, device, guided, None, kps2_list, desc2_list)
+                               symmetric_error_check, enable_degeneracy_check, seeds, norm, device, guided, None, kps2_list, desc2_list, max_dist)
 
 
 def _match_verify_pairs(fginn_r, kps_list, desc_list, pairs, model, ratio, mutual, px_th, conf, max_iters, laf_consistensy_coef, error_type,
-                        symmetric_error_check, enable_degeneracy_check, seeds, norm, device, guided, fginn_th, kps2_list, desc2_list):
+                        symmetric_error_check, enable_degeneracy_check, seeds, norm, device, guided, fginn_th, kps2_list, desc2_list, max_dist=None):
     """the body of the two pair-list match-and-verify calls: fginn_r None = the plain call (which refuses fginn_th), a checked radius =
-    the FGINN call and its entry point"""
+    the FGINN call and its entry point; ratio / mutual / max_dist: the rule of check_rule"""
+    rule = check_rule(ratio, mutual, max_dist, fginn=fginn_r is not None)
     (A, K1, c1), (B, K2, c2), one = _stack_stores(kps_list, desc_list, kps2_list, desc2_list)
     code, kind, o1, o2, pr, po, sd = check_match_pairs_args(model, ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape,
                                                             K2.dtype, c1, c2, pairs, seeds, guided, fginn_th)
@@ -560,7 +642,7 @@ def _match_verify_pairs(fginn_r, kps_list, desc_list, pairs, model, ratio, mutua
     if sd is None:
         sd = _seeds_u32(None, K)
     A, K1, B, K2 = _finish_stores(code, kind, A, K1, B, K2, one, device)              # one store: uploaded once
-    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual, fginn_r)
+    mp = _lib.match_params(code, A.shape[1], rule, fginn_r)
     n = int(po[-1])
     M = np.zeros((K, 9)); match = np.full(n, -1, np.int32); inl = np.zeros(n, np.uint8)
     st = np.zeros((K, 16), np.int32); cnt = np.zeros(K, np.int32)
@@ -639,7 +721,7 @@ def _fh_host(entry, mp, A, B, layout, prm_f, prm_h, sd, device, K, n):
 
 
 def match_and_verify_fh_batch(kps1_list, kps2_list, desc1_list, desc2_list, ratio=0.9, mutual=False, norm=None, fginn_th=None, seeds=None,
-                              f_params=None, h_params=None, device=0):
+                              f_params=None, h_params=None, device=0, *, max_dist=None):
     """match_and_verify_batch with BOTH models on the same tentatives: the matching runs once, then findFundamentalMatrix (f_params) and
     findHomography (h_params) on every pair's tentatives, each seeded with the pair's seed.  Arrays, ratio, mutual, norm, fginn_th and
     seeds as for match_and_verify_batch; f_params / h_params as for two_view_params.  Per pair F / inlier_f are bit for bit those of
@@ -648,13 +730,14 @@ def match_and_verify_fh_batch(kps1_list, kps2_list, desc1_list, desc2_list, rati
     summary [K, 4] int32 = per pair (tentatives, nF, nH, nFH): its tentatives and its queries that are inliers of F, of H, of both);
     two_view_config(summary) classifies the pairs.  The guided stage is not part of this call: guided_match_batch takes either returned
     model as it is.  last_stats() holds per pair the F statistics with "tentatives", and the H statistics under "homography"."""
+    rule = check_rule(ratio, mutual, max_dist, fginn=fginn_th is not None)
     code, kind, A, B, K1, K2, o1, o2 = _stack_pairs(kps1_list, kps2_list, desc1_list, desc2_list, "H", ratio, norm, device, fginn_th)
     K = len(o1) - 1
     prm_f, prm_h = two_view_params(f_params, h_params)
     A, B, K1, K2 = _finish_pairs(code, kind, A, B, K1, K2, device)
     sd = _seeds_u32(seeds, K)
     lp = C.POINTER(C.c_int64)
-    F, H, match, inf, inh, summ = _fh_host(_lib.lib().mi_degensac_match_verify_fh_batch, _lib.MatchParams(code, A.shape[1], ratio, mutual, fginn_th), A, B,
+    F, H, match, inf, inh, summ = _fh_host(_lib.lib().mi_degensac_match_verify_fh_batch, _lib.match_params(code, A.shape[1], rule, fginn_th), A, B,
                                            (o1.ctypes.data_as(lp), o2.ctypes.data_as(lp), _lib.dptr(K1), _lib.dptr(K2), K1.shape[1], K), prm_f, prm_h,
                                            sd, device, K, A.shape[0])
     cut = lambda x, t=None: [x[o1[p]:o1[p + 1]] if t is None else x[o1[p]:o1[p + 1]].astype(t) for p in range(K)]          # noqa: E731
@@ -662,13 +745,14 @@ def match_and_verify_fh_batch(kps1_list, kps2_list, desc1_list, desc2_list, rati
 
 
 def match_and_verify_fh_pairs(kps_list, desc_list, pairs, ratio=0.9, mutual=False, norm=None, fginn_th=None, seeds=None, f_params=None,
-                              h_params=None, device=0, kps2_list=None, desc2_list=None):
+                              h_params=None, device=0, kps2_list=None, desc2_list=None, *, max_dist=None):
     """match_and_verify_fh_batch over a pair list: descriptors and keypoints once per image, pairs [K, 2] the (i, j) to run (stores, list
     and seeds as for match_and_verify_pairs).  fginn_th is part of this call (None = the plain ratio test): there is no separate FGINN
     form.  Per entry and model the results are bit for bit those of match_and_verify_pairs / match_and_verify_fginn_pairs with that model
     and its parameters.  Returns (F [K, 3, 3], H [K, 3, 3] user-facing, [match_p], [inlier_f_p], [inlier_h_p], summary [K, 4] int32) as
     match_and_verify_fh_batch.  The guided stage is not part of this call: guided_match_pairs takes either returned model as it is."""
     fr = None if fginn_th is None else check_fginn_th(fginn_th)
+    rule = check_rule(ratio, mutual, max_dist, fginn=fr is not None)
     (A, K1, c1), (B, K2, c2), one = _stack_stores(kps_list, desc_list, kps2_list, desc2_list)
     code, kind, o1, o2, pr, po, sd = check_match_pairs_args("H", ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape,
                                                             K2.dtype, c1, c2, pairs, seeds)
@@ -678,7 +762,7 @@ def match_and_verify_fh_pairs(kps_list, desc_list, pairs, ratio=0.9, mutual=Fals
         sd = _seeds_u32(None, K)
     A, K1, B, K2 = _finish_stores(code, kind, A, K1, B, K2, one, device)              # one store: uploaded once
     lp = C.POINTER(C.c_int64)
-    F, H, match, inf, inh, summ = _fh_host(_lib.lib().mi_degensac_match_verify_fh_pairs, _lib.MatchParams(code, A.shape[1], ratio, mutual, fr), A, B,
+    F, H, match, inf, inh, summ = _fh_host(_lib.lib().mi_degensac_match_verify_fh_pairs, _lib.match_params(code, A.shape[1], rule, fr), A, B,
                                            (o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, _lib.dptr(K1), _lib.dptr(K2),
                                             K1.shape[1], pr.ctypes.data_as(C.POINTER(C.c_int32)), K), prm_f, prm_h, sd, device, K, int(po[-1]))
     cut = lambda x, t=None: [x[po[p]:po[p + 1]] if t is None else x[po[p]:po[p + 1]].astype(t) for p in range(K)]          # noqa: E731
@@ -686,7 +770,7 @@ def match_and_verify_fh_pairs(kps_list, desc_list, pairs, ratio=0.9, mutual=Fals
 
 
 def guided_match_pairs(kps_list, desc_list, pairs, models, model="F", ratio=0.9, mutual=False, px_th=None, error_type="sampson", norm=None,
-                       driver_form=False, device=0, kps2_list=None, desc2_list=None, fginn_th=None):
+                       driver_form=False, device=0, kps2_list=None, desc2_list=None, fginn_th=None, *, max_dist=None):
     """guided_match_batch over a pair list: descriptors and keypoints are given ONCE per image, pairs [K, 2] says which (i, j) to run and
     models [K, 3, 3] float64 holds one model per LIST ENTRY (the same (i, j) may appear twice with two models) — what
     match_and_verify_pairs returned for the same list goes in as it is: F, or the user-facing H (driver_form=True: H_c = inv(H)^T).  Stores
@@ -694,7 +778,8 @@ def guided_match_pairs(kps_list, desc_list, pairs, models, model="F", ratio=0.9,
     row is copied per pair.  Per entry the result is bit for bit that of guided_match_batch on the entry's copied arrays.  Returns per
     list entry (query indices, train indices, distances) in query order; train indices are local to image j.
     fginn_th as in guided_match_batch (FGINN inside the gate on the keypoints of the entry's train image; a query whose only gated
-    companions lie inside the radius is kept)."""
+    companions lie inside the radius is kept).  ratio=None, mutual="ratio" and max_dist as in guided_match_batch."""
+    rule = check_rule(ratio, mutual, max_dist, fginn=fginn_th is not None)
     (A, K1, c1), (B, K2, c2), one = _stack_stores(kps_list, desc_list, kps2_list, desc2_list)
     code, kind, o1, o2, pr, po, _ = check_match_pairs_args(model, ratio, norm, A.shape, A.dtype, B.shape, B.dtype, K1.shape, K1.dtype, K2.shape,
                                                            K2.dtype, c1, c2, pairs)
@@ -707,7 +792,7 @@ def guided_match_pairs(kps_list, desc_list, pairs, models, model="F", ratio=0.9,
     n = int(po[-1])
     idx = np.full((n, 2), -1, np.int32); dist = np.full((n, 2), np.inf, np.float32); match = np.full(n, -1, np.int32)
     cnt = np.zeros(K, np.int32)
-    mp = _lib.MatchParams(code, A.shape[1], ratio, mutual, fr); gp = _lib.GuideParams(model == "H", et, px)
+    mp = _lib.match_params(code, A.shape[1], rule, fr); gp = _lib.GuideParams(model == "H", et, px)
     lp = C.POINTER(C.c_int64); ip = C.POINTER(C.c_int32)
     rc = guided_entry("pairs", fr)(C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), o1.ctypes.data_as(lp),
                                    len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, pr.ctypes.data_as(ip), K, _lib.dptr(K1),

@@ -141,13 +141,47 @@ def match_filter_tensors(idx, dist, ratio=0.9, back=None):
     return keep
 
 
-def match_snn_tensors(desc1, desc2, ratio=0.9, mutual=False, norm=None):
+def match_decide_tensors(idx, dist, ratio=0.9, back=None, back_dist=None, max_dist=None, back_ratio=False):
+    """match_filter_tensors under the decision rule (include/mi_degensac.h mi_degensac_match_decide_dev): ratio=None drops the ratio test
+    (a query with a nearest neighbour is kept, a second train row is not needed), back (the idx of the reverse search) adds the mutual
+    check, back_ratio=True (with back and back_dist, the reverse search's idx and dist) the ratio test at the train row's own reverse
+    search, max_dist the threshold dist[:, 0] <= max_dist.  Returns keep [n1] uint8 on the device, asynchronous on the current stream."""
+    import torch
+    from . import matcher
+    if back_ratio and (back is None or back_dist is None):
+        raise ValueError("back_ratio=True needs back and back_dist, the idx and dist of the reverse search")
+    rule = matcher.check_rule(ratio, "ratio" if back_ratio else back is not None, max_dist)
+    dev = idx.device; n1 = idx.shape[0]
+    keep = torch.zeros(n1, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    mp = _lib.MatchParamsEx(0, 0, rule.ratio, rule.mutual, None, rule.decide, rule.max_dist)
+    rc = _lib.lib().mi_degensac_match_decide_dev(C.byref(mp), idx.data_ptr(), dist.data_ptr(), n1, back.data_ptr() if back is not None else None,
+                                                 back_dist.data_ptr() if back_dist is not None else None, dev.index or 0,
+                                                 C.c_void_p(stream.cuda_stream), keep.data_ptr())
+    _lib.check_match(rc)
+    for t in (idx, dist, back, back_dist):
+        if t is not None:
+            t.record_stream(stream)
+    return keep
+
+
+def match_snn_tensors(desc1, desc2, ratio=0.9, mutual=False, norm=None, *, max_dist=None):
     """The ratio test of the example (`m.distance < ratio * n.distance`, simple-example.py:49-53), optionally restricted to
     mutual nearest neighbours, on the device: (query indices, train indices, distances) of the tentative correspondences.
     norm as for knn_match_tensors.  The only host synchronisation is the final boolean selection (the number of survivors sizes the
-    outputs)."""
+    outputs).  ratio=None, mutual="ratio" and max_dist: the decision rule of matcher.check_rule, through match_decide_tensors."""
     import torch
+    from . import matcher
+    rule = matcher.check_rule(ratio, mutual, max_dist)
     idx, dist = knn_match_tensors(desc1, desc2, norm)
+    if rule.decide:
+        back, bdist = knn_match_tensors(desc2, desc1, norm) if rule.mutual and desc2.shape[0] > 0 else (None, None)
+        if rule.mutual and back is None:                     # no train row: nothing to keep, and no reverse search to read
+            keep = torch.zeros(idx.shape[0], dtype=torch.uint8, device=idx.device)
+        else:
+            keep = match_decide_tensors(idx, dist, ratio, back, bdist, max_dist, bool(rule.decide & _lib.DECIDE_BACK_RATIO))
+        sel = torch.nonzero(keep, as_tuple=False).flatten()
+        return sel, idx[sel, 0].to(torch.int64), dist[sel, 0]
     dev = idx.device; n1 = idx.shape[0]
     keep = torch.zeros(n1, dtype=torch.uint8, device=dev)
     back = knn_match_tensors(desc2, desc1, norm)[0] if mutual and desc2.shape[0] > 0 else None
@@ -253,7 +287,7 @@ def knn_match_fginn_batch_tensors(desc1, desc2, kps2, counts1, counts2, spatial_
     return idx, dist
 
 
-def _guided_dev(code, a, b, k1, k2, o1, o2, Md, model, ratio, mutual, px, et, fginn_r=None):
+def _guided_dev(code, a, b, k1, k2, o1, o2, Md, model, rule, px, et, fginn_r=None):
     """mi_degensac_match_guided_batch_dev (fginn_r, a checked radius: mi_degensac_match_guided_fginn_batch_dev) on prepared device
     tensors (Md: [K, 9] driver-form models), asynchronous on the current stream.  Returns (match [N1] int32, idx [N1, 2] int32,
     dist [N1, 2] float32)."""
@@ -263,7 +297,7 @@ def _guided_dev(code, a, b, k1, k2, o1, o2, Md, model, ratio, mutual, px, et, fg
     idx = torch.full((n1, 2), -1, dtype=torch.int32, device=dev)
     dist = torch.full((n1, 2), float("inf"), dtype=torch.float32, device=dev)
     match = torch.full((n1,), -1, dtype=torch.int32, device=dev)
-    mp = _lib.MatchParams(code, a.shape[1], ratio, mutual, fginn_r); gp = _lib.GuideParams(model == "H", et, px)
+    mp = _lib.match_params(code, a.shape[1], rule, fginn_r); gp = _lib.GuideParams(model == "H", et, px)
     stream = torch.cuda.current_stream(dev)
     rc = matcher.guided_entry("batch_dev", fginn_r)(C.byref(mp), a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(C.POINTER(C.c_int64)),
                                                     o2.ctypes.data_as(C.POINTER(C.c_int64)), k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]), K,
@@ -286,7 +320,7 @@ def _h_driver_form(M):
 
 
 def guided_match_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, models, model="F", ratio=0.9, mutual=False, px_th=None,
-                               error_type="sampson", norm=None, driver_form=False, fginn_th=None):
+                               error_type="sampson", norm=None, driver_form=False, fginn_th=None, *, max_dist=None):
     """Guided matching on the device (include/mi_degensac.h mi_degensac_match_guided_batch_dev): per pair the 2-NN search of
     knn_match_batch_tensors restricted to the train keypoints that are inliers of the pair's model under the estimator's own residual
     for error_type and its threshold from px_th (None = the model's default: 0.5 for F, 1.0 for H), then the ratio test (and, with
@@ -301,9 +335,12 @@ def guided_match_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model
     far from the keypoint of slot 0 (FGINN inside the gate), so a keypoint's own twin inside the band (a second orientation, a
     neighbouring scale) no longer fails the ratio test.  A query whose only gated companions lie inside the radius has dist1 = inf and
     is KEPT (nothing competes with it) — not the rule of knn_match_fginn_batch_tensors, which needs a second row.  The reverse search
-    of mutual stays the plain one."""
+    of mutual stays the plain one.
+    ratio=None, mutual="ratio" and max_dist: the rule of matcher.check_rule in its guided form (a missing slot 1 has dist = inf and passes
+    either ratio test)."""
     import torch
     from . import matcher
+    rule = matcher.check_rule(ratio, mutual, max_dist, fginn=fginn_th is not None)
     ts = (kps1, kps2, desc1, desc2, models)
     if not all(isinstance(t, torch.Tensor) for t in ts):
         raise ValueError("kps1, kps2, desc1, desc2 and models must be torch tensors on a ROCm device")
@@ -322,7 +359,7 @@ def guided_match_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model
     M = models.contiguous()
     if model == "H" and not driver_form:
         M = _h_driver_form(M)
-    return _guided_dev(code, a, b, k1, k2, o1, o2, M.reshape(K, 9).contiguous(), model, ratio, mutual, px, et, fr)
+    return _guided_dev(code, a, b, k1, k2, o1, o2, M.reshape(K, 9).contiguous(), model, rule, px, et, fr)
 
 
 def _h_user_form(M):
@@ -365,7 +402,8 @@ def _match_verify_dev(entry, layout, model, mp, prm, a, b, k1, k2, sd, K, n, gui
 
 def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
                                    max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
-                                   enable_degeneracy_check=True, seeds=None, guided=False, norm=None, fginn_th=None, guided_fginn_th=None):
+                                   enable_degeneracy_check=True, seeds=None, guided=False, norm=None, fginn_th=None, guided_fginn_th=None, *,
+                                   max_dist=None):
     """K image pairs from descriptors to models with ONE host synchronisation (the read of the per-pair tentative counts): per pair
     the 2-NN ratio test (`m.distance < ratio * n.distance`, optionally mutual) of match_snn_tensors, then the estimator of
     find_fundamental_batch_tensors (model "F") / find_homography_batch_tensors ("H") on its tentatives in query order.
@@ -382,10 +420,14 @@ def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, m
     fginn_th: None = the plain ratio test; a number switches it to the FGINN ratio test (knn_match_fginn_batch_tensors at that radius
     on kps2's x, y).  Only the tentatives in front of the estimator change: the guided stage keeps its own gate and decision.
     guided_fginn_th: None, or the radius of guided_match_batch_tensors(fginn_th=) for the guided stage (FGINN inside the gate; a query
-    whose only gated companions lie inside the radius is kept).  It is passed on only with guided=True and is a ValueError without it."""
+    whose only gated companions lie inside the radius is kept).  It is passed on only with guided=True and is a ValueError without it.
+    ratio=None, mutual="ratio" and max_dist: the rule of matcher.check_rule, for the tentatives and (guided form) the guided stage."""
     import torch
     from . import matcher
     gfr = matcher.check_guided_fginn_th(guided, guided_fginn_th)
+    rule = matcher.check_rule(ratio, mutual, max_dist, fginn=fginn_th is not None)
+    if gfr is not None:
+        matcher.check_rule(ratio, mutual, max_dist, fginn=True)
     ts = (kps1, kps2, desc1, desc2)
     if not all(isinstance(t, torch.Tensor) for t in ts):
         raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
@@ -402,10 +444,10 @@ def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, m
         k1 = kps1.contiguous(); k2 = kps2.contiguous()
     sd = matcher._seeds_u32(None if seeds is None else np.asarray(seeds).ravel(), K)
     lp = C.POINTER(C.c_int64)
-    guide = (lambda M: _guided_dev(code, a, b, k1, k2, o1, o2, M, model, ratio, mutual, prm.px_th, prm.error_type, gfr)[0]) if guided else None
+    guide = (lambda M: _guided_dev(code, a, b, k1, k2, o1, o2, M, model, rule, prm.px_th, prm.error_type, gfr)[0]) if guided else None
     res = _match_verify_dev(_lib.lib().mi_degensac_match_verify_batch_dev, (o1.ctypes.data_as(lp), o2.ctypes.data_as(lp), k1.data_ptr(), k2.data_ptr(),
                                                                           int(k1.shape[1]), K),
-                            model, _lib.MatchParams(code, a.shape[1], ratio, mutual, fginn_th), prm, a, b, k1, k2, sd, K, n1, guide)
+                            model, _lib.match_params(code, a.shape[1], rule, fginn_th), prm, a, b, k1, k2, sd, K, n1, guide)
     return res if guided else res[:5]
 
 
@@ -479,7 +521,7 @@ def knn_match_fginn_pairs_tensors(desc1, desc2, kps2, counts1, counts2, pairs, s
 
 def match_and_verify_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
                                    max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
-                                   enable_degeneracy_check=True, seeds=None, guided=False, norm=None, fginn_th=None):
+                                   enable_degeneracy_check=True, seeds=None, guided=False, norm=None, fginn_th=None, *, max_dist=None):
     """match_and_verify_batch_tensors over a pair list: kps / desc are image stores (counts1 / counts2 rows per image, as for
     knn_match_pairs_tensors; pass the same tensors on both sides for a collection matched against itself) and pairs [K, 2] lists the
     (i, j) to run, e.g. matcher.exhaustive_pairs(M).  Descriptors and keypoints stay where they are: the device holds M images' rows,
@@ -491,12 +533,13 @@ def match_and_verify_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, p
     guided=True and fginn_th are not part of this call (ValueError): guided matching over the list is guided_match_pairs_tensors, which
     takes the models returned here as they are; the FGINN ratio test over a list is match_and_verify_fginn_pairs_tensors."""
     return _match_verify_pairs_tensors(None, kps1, kps2, desc1, desc2, counts1, counts2, pairs, model, ratio, mutual, px_th, conf, max_iters,
-                                       laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check, seeds, guided, norm, fginn_th)
+                                       laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check, seeds, guided, norm, fginn_th,
+                                       max_dist)
 
 
 def match_and_verify_fginn_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs, fginn_th, model="F", ratio=0.9, mutual=False, px_th=None,
                                          conf=None, max_iters=None, laf_consistensy_coef=-1.0, error_type="sampson", symmetric_error_check=True,
-                                         enable_degeneracy_check=True, seeds=None, guided=False, norm=None):
+                                         enable_degeneracy_check=True, seeds=None, guided=False, norm=None, *, max_dist=None):
     """match_and_verify_pairs_tensors with the FGINN ratio test in front of the estimator (include/mi_degensac.h
     mi_degensac_match_verify_fginn_pairs_dev): fginn_th is the radius in pixels of kps2 (knn_match_fginn_pairs_tensors at that radius on
     the x, y of store 2's keypoints), a finite number >= 0.  Stores, list, seeds, the returned tuple and the single synchronisation are
@@ -506,15 +549,18 @@ def match_and_verify_fginn_pairs_tensors(kps1, kps2, desc1, desc2, counts1, coun
     from . import matcher
     r = matcher.check_fginn_th(fginn_th)
     return _match_verify_pairs_tensors(r, kps1, kps2, desc1, desc2, counts1, counts2, pairs, model, ratio, mutual, px_th, conf, max_iters,
-                                       laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check, seeds, guided, norm, None)
+                                       laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check, seeds, guided, norm, None,
+                                       max_dist)
 
 
 def _match_verify_pairs_tensors(fginn_r, kps1, kps2, desc1, desc2, counts1, counts2, pairs, model, ratio, mutual, px_th, conf, max_iters,
-                                laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check, seeds, guided, norm, fginn_th):
+                                laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check, seeds, guided, norm, fginn_th,
+                                max_dist=None):
     """the body of the two pair-list match-and-verify calls: fginn_r None = the plain call (which refuses fginn_th), a checked radius =
-    the FGINN call and its entry point"""
+    the FGINN call and its entry point; ratio / mutual / max_dist: the rule of matcher.check_rule"""
     import torch
     from . import matcher
+    rule = matcher.check_rule(ratio, mutual, max_dist, fginn=fginn_r is not None)
     ts = (kps1, kps2, desc1, desc2)
     if not all(isinstance(t, torch.Tensor) for t in ts):
         raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
@@ -534,7 +580,7 @@ def _match_verify_pairs_tensors(fginn_r, kps1, kps2, desc1, desc2, counts1, coun
     layout = (o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]),
               pr.ctypes.data_as(C.POINTER(C.c_int32)), K)
     entry = _lib.lib().mi_degensac_match_verify_pairs_dev if fginn_r is None else _lib.lib().mi_degensac_match_verify_fginn_pairs_dev
-    return _match_verify_dev(entry, layout, model, _lib.MatchParams(code, a.shape[1], ratio, mutual, fginn_r), prm, a, b, k1, k2, sd, K, n)[:5] + (po,)
+    return _match_verify_dev(entry, layout, model, _lib.match_params(code, a.shape[1], rule, fginn_r), prm, a, b, k1, k2, sd, K, n)[:5] + (po,)
 
 
 # ---- match once, verify F and H (include/mi_degensac.h mi_degensac_match_verify_fh_*) ----
@@ -564,7 +610,7 @@ def _match_verify_fh_dev(entry, layout, mp, prm_f, prm_h, a, b, k1, k2, sd, K, n
 
 
 def match_and_verify_fh_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, ratio=0.9, mutual=False, norm=None, fginn_th=None, seeds=None,
-                                      f_params=None, h_params=None):
+                                      f_params=None, h_params=None, *, max_dist=None):
     """match_and_verify_batch_tensors with BOTH models on the same tentatives (include/mi_degensac.h mi_degensac_match_verify_fh_batch_dev):
     the 2-NN search, the FGINN step, the reverse search of mutual and the ratio test run ONCE, the tentative counts are read ONCE (the
     call's one host synchronisation), then the fundamental-matrix and the homography estimator run one after the other on every pair's
@@ -581,9 +627,10 @@ def match_and_verify_fh_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2
     inliers of F, of H, of both; n_tentatives [K] numpy int64); all but the last on the device.  matcher.two_view_config(summary)
     classifies the pairs.
     The guided stage is not part of this call (there is no guided= keyword): guided_match_batch_tensors / guided_match_pairs_tensors take
-    either returned model as it is."""
+    either returned model as it is.  ratio=None, mutual="ratio" and max_dist: the rule of matcher.check_rule."""
     import torch
     from . import matcher
+    rule = matcher.check_rule(ratio, mutual, max_dist, fginn=fginn_th is not None)
     ts = (kps1, kps2, desc1, desc2)
     if not all(isinstance(t, torch.Tensor) for t in ts):
         raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
@@ -603,11 +650,11 @@ def match_and_verify_fh_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2
     lp = C.POINTER(C.c_int64)
     return _match_verify_fh_dev(_lib.lib().mi_degensac_match_verify_fh_batch_dev,
                                 (o1.ctypes.data_as(lp), o2.ctypes.data_as(lp), k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]), K),
-                                _lib.MatchParams(code, a.shape[1], ratio, mutual, fginn_th), prm_f, prm_h, a, b, k1, k2, sd, K, n1)
+                                _lib.match_params(code, a.shape[1], rule, fginn_th), prm_f, prm_h, a, b, k1, k2, sd, K, n1)
 
 
 def match_and_verify_fh_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs, ratio=0.9, mutual=False, norm=None, fginn_th=None,
-                                      seeds=None, f_params=None, h_params=None):
+                                      seeds=None, f_params=None, h_params=None, *, max_dist=None):
     """match_and_verify_fh_batch_tensors over a pair list (include/mi_degensac.h mi_degensac_match_verify_fh_pairs_dev): kps / desc are
     image stores (counts1 / counts2 rows per image; pass the same tensors on both sides for a collection matched against itself) and
     pairs [K, 2] lists the (i, j) to run, as for match_and_verify_pairs_tensors.  fginn_th IS part of this call (None = the plain ratio
@@ -622,6 +669,7 @@ def match_and_verify_fh_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2
     either returned model as it is."""
     import torch
     from . import matcher
+    rule = matcher.check_rule(ratio, mutual, max_dist, fginn=fginn_th is not None)
     ts = (kps1, kps2, desc1, desc2)
     if not all(isinstance(t, torch.Tensor) for t in ts):
         raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
@@ -641,12 +689,12 @@ def match_and_verify_fh_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2
     lp = C.POINTER(C.c_int64)
     layout = (o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]),
               pr.ctypes.data_as(C.POINTER(C.c_int32)), K)
-    return _match_verify_fh_dev(_lib.lib().mi_degensac_match_verify_fh_pairs_dev, layout, _lib.MatchParams(code, a.shape[1], ratio, mutual, fr),
+    return _match_verify_fh_dev(_lib.lib().mi_degensac_match_verify_fh_pairs_dev, layout, _lib.match_params(code, a.shape[1], rule, fr),
                                 prm_f, prm_h, a, b, k1, k2, sd, K, n) + (po,)
 
 
 def guided_match_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs, models, model="F", ratio=0.9, mutual=False, px_th=None,
-                               error_type="sampson", norm=None, driver_form=False, fginn_th=None):
+                               error_type="sampson", norm=None, driver_form=False, fginn_th=None, *, max_dist=None):
     """guided_match_batch_tensors over a pair list (include/mi_degensac.h mi_degensac_match_guided_pairs_dev): kps / desc are image stores
     (counts1 / counts2 rows per image; pass the same tensors on both sides for a collection matched against itself), pairs [K, 2] lists
     the (i, j) to run and models [K, 3, 3] float64 on the device holds one model per LIST ENTRY — what match_and_verify_pairs_tensors
@@ -659,9 +707,11 @@ def guided_match_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs
     pair_offsets[p + 1].  Asynchronous on the current stream (no host synchronisation).
     fginn_th as in guided_match_batch_tensors, through mi_degensac_match_guided_fginn_pairs_dev: anchors and competitors are the
     keypoints of the entry's train image in store 2; a needy query is rescanned through its image's rows in store 1 and answered at
-    its output row (two different rows in a list), nothing is copied.  A query whose only gated companions lie inside the radius is kept."""
+    its output row (two different rows in a list), nothing is copied.  A query whose only gated companions lie inside the radius is kept.
+    ratio=None, mutual="ratio" and max_dist as in guided_match_batch_tensors."""
     import torch
     from . import matcher
+    rule = matcher.check_rule(ratio, mutual, max_dist, fginn=fginn_th is not None)
     ts = (kps1, kps2, desc1, desc2, models)
     if not all(isinstance(t, torch.Tensor) for t in ts):
         raise ValueError("kps1, kps2, desc1, desc2 and models must be torch tensors on a ROCm device")
@@ -684,7 +734,7 @@ def guided_match_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs
     idx = torch.full((n, 2), -1, dtype=torch.int32, device=dev)
     dist = torch.full((n, 2), float("inf"), dtype=torch.float32, device=dev)
     match = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    mp = _lib.MatchParams(code, a.shape[1], ratio, mutual, fr); gp = _lib.GuideParams(model == "H", et, px)
+    mp = _lib.match_params(code, a.shape[1], rule, fr); gp = _lib.GuideParams(model == "H", et, px)
     stream = torch.cuda.current_stream(dev)
     lp = C.POINTER(C.c_int64)
     rc = matcher.guided_entry("pairs_dev", fr)(C.byref(mp), a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(lp), len(o1) - 1,
