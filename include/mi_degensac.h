@@ -362,6 +362,47 @@ int mi_degensac_kpts_to_xyA(const float *kpts, int n, int device, double *out);
 int mi_degensac_kpts_to_xyA_dev(const float *d_kpts, int n, int device, void *stream, double *d_out);
 const char *mi_degensac_match_last_error(void);
 
+/* ---- float descriptors -> the uint8 rows of MI_DEGENSAC_NORM_L2_U8, on the device ---------------------------------------
+ * Every extractor emits float32 descriptors; norm L2_U8 takes bytes.  This is the conversion, with its rounding, clamping, padding
+ * and its zero / NaN rows fixed here.  in: float32 [n, dim], 1 <= dim <= MI_DEGENSAC_L2_U8_MAX_DIM, rows dim floats apart;
+ * out: uint8 [n, out_dim] with out_dim = (dim + 3) & ~3, the width the L2_U8 entry points take.
+ * The arithmetic is fp64 throughout, one IEEE operation per step and no FMA contraction.  Per row, x_k = (double)in[k]:
+ *   normalize 0 (none):     y_k = x_k
+ *   normalize 1 (L2):       s = sum_k x_k^2,  y_k = x_k / sqrt(s)                      (a division, not a reciprocal multiply)
+ *   normalize 2 (L1-root):  s = sum_k |x_k|,  y_k = copysign(sqrt(|x_k| / s), x_k)     (RootSIFT)
+ *   v_k = rint(scale * y_k) + offset   (round half to even, no + 0.5),   q_k = v_k clamped to 0 .. 255
+ * Summation order of s: think of 64 lanes, lane i owning columns 4 i .. 4 i + 3.  Each lane adds the terms of its own columns below
+ * dim in ascending order, starting from +0.0 (a lane without columns holds +0.0); then, for m = 32, 16, 8, 4, 2, 1 in this order,
+ * every lane i replaces its value by (its value) + (the value lane i ^ m held before the step).  All lanes end with the same s.
+ * Pad columns dim .. out_dim - 1 are written as 0 (zero bytes on both sides add nothing to the distance).
+ * clipped [n] int32 (optional): the number of columns of the row whose v_k lay outside 0 .. 255.
+ * Dead rows: a row with a non-finite x_k, or with normalize != 0 and s == 0, gets `offset` in every column below dim and
+ * clipped = -1: a constant descriptor.  No NaN is ever cast to an integer.
+ * Distances: an L2_U8 distance between two quantised rows is about `scale` times the float distance of the normalised rows (each
+ * byte is within 1/2 of scale * y_k, clamping apart; a common offset cancels in every difference), so a max_dist stated in float
+ * units is multiplied by scale.
+ * Errors, with a message in mi_degensac_match_last_error() and before a device is looked for: MI_DEGENSAC_EINVAL for dim < 1 or
+ * dim > 256, n < 0, NULL qp / input / output when n > 0, normalize outside 0 .. 2, a scale that is not finite or <= 0, an offset
+ * outside 0 .. 255, a struct_size that does not cover offset, and (_dev) a device pointer that is not 4-byte aligned (a row's output
+ * is written as 32-bit words).  n == 0 succeeds and touches nothing.  The _dev form is asynchronous on `stream`, allocates nothing
+ * and never synchronises; it reads 16 bytes per lane when dim % 4 == 0 and d_desc is 16-byte aligned, single floats otherwise. */
+#define MI_DEGENSAC_QUANT_NONE   0
+#define MI_DEGENSAC_QUANT_L2     1
+#define MI_DEGENSAC_QUANT_L1ROOT 2
+typedef struct {
+    int    struct_size;    /* sizeof(mi_degensac_quant_params) of the caller's header; has to cover offset */
+    int    normalize;      /* MI_DEGENSAC_QUANT_* */
+    double scale;          /* finite and > 0: 512 for SIFT / RootSIFT, 256 with offset 128 for signed unit-norm descriptors */
+    int    offset;         /* 0 .. 255 */
+} mi_degensac_quant_params;
+int mi_degensac_desc_quantize_dev(const mi_degensac_quant_params *qp, const float *d_desc, int64_t n, int dim, int device,
+                                  void *stream, uint8_t *d_out /*[n, out_dim]*/, int32_t *d_clipped_or_null /*[n]*/);
+int mi_degensac_desc_quantize(const mi_degensac_quant_params *qp, const float *desc, int64_t n, int dim, int device,
+                              uint8_t *out /*[n, out_dim]*/, int32_t *clipped_or_null /*[n]*/);
+/* the rows one pass of the largest grid of mi_degensac_desc_quantize_dev covers at this width (more rows are reached by its
+ * grid-stride loop; tests size a case just beyond it); 0 for a dim outside 1 .. 256 */
+int64_t mi_degensac_desc_quantize_pass_rows(int dim);
+
 /* ---- batched match-and-verify: many image pairs from descriptors to F / H -------------------------------------------
  * A ragged batch of K image pairs: pair p owns the rows offsets1_host[p] .. offsets1_host[p+1] of desc1 / kp1 (its queries) and
  * offsets2_host[p] .. offsets2_host[p+1] of desc2 / kp2 (its train set); offsets are host arrays of K + 1 non-decreasing values.

@@ -85,6 +85,14 @@ def match_params(norm, dim, rule, fginn_th=None):
     return MatchParamsEx(norm, dim, rule.ratio, rule.mutual, fginn_th, rule.decide, rule.max_dist)
 
 
+class QuantParams(C.Structure):
+    """mi_degensac_quant_params (include/mi_degensac.h): normalize 0 none / 1 L2 / 2 L1-root, scale, offset of mi_degensac_desc_quantize*"""
+    _fields_ = [("struct_size", C.c_int), ("normalize", C.c_int), ("scale", C.c_double), ("offset", C.c_int)]
+
+    def __init__(self, normalize=0, scale=1.0, offset=0):
+        super().__init__(C.sizeof(QuantParams), int(normalize), float(scale), int(offset))
+
+
 class GuideParams(C.Structure):
     """mi_degensac_guide_params (include/mi_degensac.h): the gate of the guided-matching entry points"""
     _fields_ = [("homography", C.c_int32), ("error_type", C.c_int32), ("px_th", C.c_double), ("struct_size", C.c_int32), ("reserved", C.c_int32)]
@@ -283,6 +291,14 @@ def lib():
                 for tail in ("_dev", ""):
                     f = getattr(l, f"mi_degensac_match_guided_fginn_{lay}{tail}"); f.restype = C.c_int
                     f.argtypes = getattr(l, f"mi_degensac_match_guided_{lay}{tail}").argtypes
+        if hasattr(l, "mi_degensac_desc_quantize_dev"):                   # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            qpp = C.POINTER(QuantParams)
+            l.mi_degensac_desc_quantize_dev.restype = C.c_int
+            l.mi_degensac_desc_quantize_dev.argtypes = [qpp, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            l.mi_degensac_desc_quantize.restype = C.c_int
+            l.mi_degensac_desc_quantize.argtypes = [qpp, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+            l.mi_degensac_desc_quantize_pass_rows.restype = C.c_int64
+            l.mi_degensac_desc_quantize_pass_rows.argtypes = [C.c_int]
         l.mi_degensac_kpts_to_xyA.restype = C.c_int
         l.mi_degensac_kpts_to_xyA.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, dp]
         l.mi_degensac_kpts_to_xyA_dev.restype = C.c_int

@@ -749,3 +749,4 @@ extern "C" int mi_degensac_match_knn2_pairs_dev(int norm, const void *d_desc1, c
 }
 
 #include "mi_fginn.h"
+#include "mi_quantize.h"

@@ -197,6 +197,74 @@ def kpts_to_xyA(kpts, device=0):
     return out
 
 
+# ---- float descriptors -> the uint8 rows of norm="l2_u8" (include/mi_degensac.h mi_degensac_desc_quantize*) ----
+QUANT_NONE, QUANT_L2, QUANT_L1ROOT = 0, 1, 2
+_QUANT_NORMALIZE = {None: QUANT_NONE, "none": QUANT_NONE, "l2": QUANT_L2, "l1root": QUANT_L1ROOT}
+# preset -> (normalize, scale, offset).  "sift" and "rootsift" are the x 512 bytes of the SIFT convention; "unit" puts a signed
+# unit-norm learned descriptor (HardNet, SOSNet, SuperPoint) around 128: a common offset cancels in every difference
+QUANT_PRESETS = {"sift": ("l2", 512.0, 0), "rootsift": ("l1root", 512.0, 0), "unit": ("l2", 256.0, 128)}
+
+
+def quant_params(preset="rootsift", normalize=None, scale=None, offset=None):
+    """preset and the keywords that override it -> (normalize code, scale, offset), checked; raises ValueError.  normalize: "none", "l2",
+    "l1root" (or the codes 0, 1, 2); scale: finite and > 0; offset: an integer 0 .. 255."""
+    if preset not in QUANT_PRESETS:
+        raise ValueError(f"preset should be one of {', '.join(sorted(QUANT_PRESETS))}")
+    nz, sc, of = QUANT_PRESETS[preset]
+    if normalize is not None:
+        nz = normalize
+    if isinstance(nz, str) and nz in _QUANT_NORMALIZE:
+        nz = _QUANT_NORMALIZE[nz]
+    elif isinstance(nz, bool) or nz not in (QUANT_NONE, QUANT_L2, QUANT_L1ROOT):
+        raise ValueError('normalize should be "none", "l2" or "l1root"')
+    if scale is not None:
+        try:
+            sc = float(scale)
+        except (TypeError, ValueError):
+            raise ValueError("scale should be a number")
+    if not (np.isfinite(sc) and sc > 0):
+        raise ValueError("scale should be finite and > 0")
+    if offset is not None:
+        if isinstance(offset, bool) or not isinstance(offset, (int, np.integer)):
+            raise ValueError("offset should be an integer 0 .. 255")
+        of = int(offset)
+    if not 0 <= of <= 255:
+        raise ValueError("offset should be an integer 0 .. 255")
+    return int(nz), float(sc), of
+
+
+def check_quantize_input(shape, dtype):
+    """shape and dtype name of the float descriptors of the quantise calls (numpy or torch); raises ValueError"""
+    if _dtype_name(dtype) != "float32":
+        raise ValueError("descriptors to quantise should be float32")
+    if len(shape) != 2 or not 1 <= shape[1] <= L2_U8_MAX_DIM:
+        raise ValueError(f"descriptors to quantise should be [n, dim] with 1 <= dim <= {L2_U8_MAX_DIM}")
+
+
+def quantize_descriptors(desc, preset="rootsift", *, normalize=None, scale=None, offset=None, device=0, return_clipped=False):
+    """float32 descriptors [n, dim] (dim <= 256) -> the uint8 rows [n, dim] that norm="l2_u8" takes, computed on the GPU
+    (include/mi_degensac.h mi_degensac_desc_quantize states the arithmetic: fp64, q = clamp(rint(scale * y) + offset, 0, 255) with y the
+    row as it is, L2-normalised, or the signed square root of the L1-normalised row).  preset: a key of QUANT_PRESETS — "sift" (L2, 512, 0),
+    "rootsift" (L1-root, 512, 0), "unit" (L2, 256, 128: signed learned descriptors); normalize / scale / offset override it.
+    A row with a NaN or an infinity, or one that cannot be normalised (all zero), becomes the constant row `offset`.
+    return_clipped=True adds clipped [n] int32: the columns of each row that left 0 .. 255 before the clamp, -1 for such a dead row.
+    Distances: an "l2_u8" distance between quantised rows is about scale x the float distance of the normalised rows, so a max_dist
+    meant in float units is multiplied by scale.  The pad to whole 32-bit words is trimmed here (the matcher calls pad again)."""
+    a = np.asarray(desc)
+    check_quantize_input(a.shape, a.dtype)
+    nz, sc, of = quant_params(preset, normalize, scale, offset)
+    a = np.ascontiguousarray(a)
+    n, dim = a.shape
+    out = np.zeros((n, (dim + 3) & ~3), np.uint8)
+    clipped = np.zeros(n, np.int32) if return_clipped else None
+    qp = _lib.QuantParams(nz, sc, of)
+    _lib.check_match(_lib.lib().mi_degensac_desc_quantize(C.byref(qp), a.ctypes.data_as(C.c_void_p), n, dim, int(device),
+                                                          out.ctypes.data_as(C.c_void_p),
+                                                          clipped.ctypes.data_as(C.c_void_p) if return_clipped else None))
+    out = np.ascontiguousarray(out[:, :dim])
+    return (out, clipped) if return_clipped else out
+
+
 # ---- many image pairs at once: descriptors + keypoints -> tentatives -> F / H (include/mi_degensac.h mi_degensac_match_verify_batch*) ----
 _MODEL_DEFAULTS = {"F": (0.5, 0.9999, 100000), "H": (1.0, 0.999, 50000)}          # findFundamentalMatrix / findHomography
 

@@ -211,6 +211,35 @@ def kpts_to_xyA_tensors(kpts):
     return out
 
 
+def quantize_descriptors_tensors(desc, preset="rootsift", *, normalize=None, scale=None, offset=None, out=None, return_clipped=False):
+    """matcher.quantize_descriptors on a device tensor (include/mi_degensac.h mi_degensac_desc_quantize_dev): float32 [n, dim] with
+    dim <= 256 -> uint8 [n, out_dim], out_dim = dim rounded up to a multiple of 4 with zero pad bytes: the width the norm="l2_u8"
+    tensor calls take.  preset / normalize / scale / offset as there.  out: None, or a contiguous uint8 tensor [n, out_dim] on the same
+    device to write into.  return_clipped=True adds clipped [n] int32 (-1 for a dead row).  Asynchronous on the current stream; an
+    "l2_u8" distance between quantised rows is about scale x the float distance of the normalised rows."""
+    import torch
+    from . import matcher
+    if not isinstance(desc, torch.Tensor) or desc.device.type != "cuda":
+        raise ValueError("descriptors must be a torch tensor on a ROCm device")
+    matcher.check_quantize_input(tuple(desc.shape), desc.dtype)
+    nz, sc, of = matcher.quant_params(preset, normalize, scale, offset)
+    a = desc.contiguous(); dev = a.device
+    n, dim = a.shape; out_dim = (dim + 3) & ~3
+    if out is None:
+        out = torch.empty((n, out_dim), dtype=torch.uint8, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.uint8 and tuple(out.shape) == (n, out_dim)
+              and out.is_contiguous() and out.data_ptr() % 4 == 0):
+        raise ValueError(f"out should be a contiguous, 4-byte aligned uint8 tensor [{n}, {out_dim}] on the descriptors' device")
+    clipped = torch.empty(n, dtype=torch.int32, device=dev) if return_clipped else None
+    stream = torch.cuda.current_stream(dev)
+    qp = _lib.QuantParams(nz, sc, of)
+    rc = _lib.lib().mi_degensac_desc_quantize_dev(C.byref(qp), a.data_ptr(), n, dim, dev.index or 0, C.c_void_p(stream.cuda_stream), out.data_ptr(),
+                                                  clipped.data_ptr() if return_clipped else None)
+    _lib.check_match(rc)
+    a.record_stream(stream)
+    return (out, clipped) if return_clipped else out
+
+
 # ---- many image pairs: descriptors + keypoints -> tentatives -> F / H on the device (include/mi_degensac.h mi_degensac_match_*_batch*) ----
 def _word_aligned(t):
     # the kernels read descriptor rows as 32-bit words: a contiguous view into a packed buffer may start at any byte
