@@ -761,6 +761,73 @@ int mi_degensac_match_guided_fginn_pairs(const mi_degensac_match_params *mp, con
                                          const mi_degensac_guide_params *gp, int device, int32_t *idx, float *dist, int32_t *match,
                                          int32_t *counts /*nullable*/);
 
+/* ---- verified matches as compact per-entry lists with coordinates and residuals (mi_correspond.hip) ---------------------------
+ * Every call above answers per query row: match [N] (train row local to image j, or -1) and a per-row mask.  What follows the library
+ * (a two-view database, triangulation, track building) wants, per list entry, the (row in image i, row in image j) that survived, the
+ * four coordinates and the residual under the entry's model.  These calls make that list on the device, without a host synchronisation.
+ * Inputs, all device arrays on one device:
+ *   the layout    of the pair-list form (offsets1_host [n_images1 + 1], offsets2_host [n_images2 + 1], pairs_host [2 * n_pairs]): entry
+ *                 p = (i, j) owns the N = out[K] output rows out[p] .. out[p+1] in list order, out[p+1] - out[p] = rows(image i).  The
+ *                 batch form is the identity list: entry p = (image p, image p) of offsets1_host / offsets2_host [K + 1].
+ *   d_match [N]   int32, d_keep [N] uint8 or NULL: at output row 0 in the pair-list form; in the batch form indexed like the batch's
+ *                 other per-query arrays (row offsets1_host[0] is entry 0's first row).
+ * Selection: row r of entry p = (i, j), query q = r - out[p], is selected iff 0 <= d_match[r] < rows(image j) and (d_keep == NULL or
+ * d_keep[r] != 0).  A match value outside that range means "not selected": it is no error and is never used as an index.
+ * Outputs: the selected rows in row order (list order, query order inside an entry) at positions 0, 1, ...; with total = their number
+ * and capacity = the length of the per-correspondence arrays, the correspondence at position pos < capacity is written, the others are
+ * dropped, and no element at a position >= min(total, capacity) is written.  d_total and d_corr_offsets are exact whatever capacity
+ * is, so an overflow shows as total > capacity.
+ *   d_corr_offsets [K + 1] int64   the selected rows that lie before out[p]; [K] = total; an empty entry repeats its successor's value
+ *   d_total [1] int64
+ *   d_rows [capacity, 2] int32     (q, d_match[r]), local to images i and j; with MI_DEGENSAC_CORR_STORE_ROWS in flags
+ *                                  (offsets1_host[i] + q, offsets2_host[j] + d_match[r]), the rows of the stores
+ *   d_entry [capacity] int32       p (nullable)
+ *   d_pts [capacity, 4] float64    x1, y1 of row offsets1_host[i] + q of d_kp1 and x2, y2 of row offsets2_host[j] + d_match[r] of d_kp2
+ *                                  ([rows, kp_dim] float64, kp_dim 2 or 6, only x, y are read; nullable)
+ *   d_resid [capacity] float64     r(M_p; x1, y1, x2, y2), M_p = d_models[9 p ..] in the driver's form, the estimator's own residual
+ *                                  for gp->homography / gp->error_type (F: 0 dg_FDs, 1 dg_FDsSym; H: 0 dg_HDs, 1..4 dg_Hsym on
+ *                                  dg_hsym_prepare(M_p)) exactly as the gate of the guided calls forms it: fp64 without contraction,
+ *                                  no screen, a zero or non-finite model gives whatever the function gives; gp->px_th is not read
+ *                                  (nullable; needs d_models and gp)
+ * Asynchronous on `stream`, no host synchronisation; temporaries (8 bytes per 1024 rows, 28 bytes per entry, 144 more per entry for
+ * the symmetric H errors) are allocated and freed stream-ordered.  Deterministic: no atomics, the same bits on every call.
+ * Refused with MI_DEGENSAC_EINVAL and a message in mi_degensac_match_last_error(), before a device is looked for and in this order:
+ * a flag bit other than MI_DEGENSAC_CORR_STORE_ROWS; kp_dim not 2 / 6 when d_pts or d_resid is given; d_resid without d_models or
+ * without gp, a gp whose struct_size does not cover the fields, homography other than 0 / 1, an error_type of the other model kind;
+ * capacity < 0; n_pairs < 0; then for n_pairs > 0 what the layout refuses (offsets, image indices, more than 0x3fffffff rows); under
+ * MI_DEGENSAC_CORR_STORE_ROWS store offsets beyond 0x7fffffff; NULL d_corr_offsets or d_total, and for N > 0 NULL d_match, NULL d_rows
+ * with capacity > 0, NULL d_kp1 / d_kp2 with d_pts or d_resid.  n_pairs == 0 with good parameters writes d_total = 0 and
+ * d_corr_offsets[0] = 0 (asynchronously) and looks at nothing else; N == 0 with K > 0 writes K + 1 zeros. */
+#define MI_DEGENSAC_CORR_STORE_ROWS 1u
+int mi_degensac_correspondences_pairs_dev(const int64_t *offsets1_host, int n_images1, const int64_t *offsets2_host, int n_images2,
+                                          const int32_t *pairs_host, int n_pairs, const int32_t *d_match, const uint8_t *d_keep /*nullable*/,
+                                          uint32_t flags, const double *d_kp1, const double *d_kp2,
+                                          int kp_dim /* all three unused when d_pts and d_resid are NULL */, const double *d_models /*nullable*/,
+                                          const mi_degensac_guide_params *gp /*nullable*/, int64_t capacity, int device, void *stream,
+                                          int64_t *d_corr_offsets, int64_t *d_total, int32_t *d_rows, int32_t *d_entry /*nullable*/,
+                                          double *d_pts /*nullable*/, double *d_resid /*nullable*/);
+int mi_degensac_correspondences_batch_dev(const int64_t *offsets1_host, const int64_t *offsets2_host, int n_pairs, const int32_t *d_match,
+                                          const uint8_t *d_keep /*nullable*/, uint32_t flags, const double *d_kp1, const double *d_kp2, int kp_dim,
+                                          const double *d_models /*nullable*/, const mi_degensac_guide_params *gp /*nullable*/, int64_t capacity,
+                                          int device, void *stream, int64_t *d_corr_offsets, int64_t *d_total, int32_t *d_rows,
+                                          int32_t *d_entry /*nullable*/, double *d_pts /*nullable*/, double *d_resid /*nullable*/);
+/* the same on host pointers (blocking): match / keep, the keypoint rows of each store (one upload when both sides name the same arrays)
+ * and the models go to the device once; corr_offsets [K + 1], total [1] and the first min(total, capacity) elements of rows / entry /
+ * pts / resid come back, capacity = what the caller allocated.  n_pairs == 0 writes total = 0 and corr_offsets[0] = 0 without a device. */
+int mi_degensac_correspondences_pairs(const int64_t *offsets1, int n_images1, const int64_t *offsets2, int n_images2, const int32_t *pairs,
+                                      int n_pairs, const int32_t *match, const uint8_t *keep /*nullable*/, uint32_t flags, const double *kp1,
+                                      const double *kp2, int kp_dim, const double *models /*nullable*/,
+                                      const mi_degensac_guide_params *gp /*nullable*/, int64_t capacity, int device, int64_t *corr_offsets,
+                                      int64_t *total, int32_t *rows, int32_t *entry /*nullable*/, double *pts /*nullable*/,
+                                      double *resid /*nullable*/);
+int mi_degensac_correspondences_batch(const int64_t *offsets1, const int64_t *offsets2, int n_pairs, const int32_t *match,
+                                      const uint8_t *keep /*nullable*/, uint32_t flags, const double *kp1, const double *kp2, int kp_dim,
+                                      const double *models /*nullable*/, const mi_degensac_guide_params *gp /*nullable*/, int64_t capacity,
+                                      int device, int64_t *corr_offsets, int64_t *total, int32_t *rows, int32_t *entry /*nullable*/,
+                                      double *pts /*nullable*/, double *resid /*nullable*/);
+/* the tile constants of the compaction: which = 0 rows per workgroup, 1 workgroup counts per scan step (-1 for any other value) */
+int mi_degensac_correspondences_tile(int which);
+
 /* ---- unit-level device entry points (parity tests of the kernels' building blocks) ------------ */
 /* score n_models fundamental (kind 0: Sampson, 1: symmetric epipolar) or homography (kind 10..14:
  * H Sampson, symm_sq_max, symm_max, symm_sq_sum, symm_sum) models against all n points: I (<= th)

@@ -31,6 +31,10 @@ def TUNE_GRID_CAP(g): return (int(g) & 31) << 24         # noqa: E704  cap on re
 def TUNE_LONG_SHIFT(l): return (int(l) & 7) << 29        # noqa: E704,E741  "many samples left" = threshold << l
 # bits 8-15: cooperative helper workgroups per pair (0 auto, 255 off); bits 16-23: samples after which a running pair is
 # set aside while unstarted pairs remain, in units of 256 (0 auto, 255 off); bits 24-31: cap on resident workgroups (tests)
+# the correspondence export (csrc/mi_correspond.hip MX_ROWS / MX_SCAN, mi_degensac_correspondences_tile): rows per workgroup of the
+# compaction and workgroup counts per step of its scan; MI_DEGENSAC_CORR_STORE_ROWS
+CORR_ROWS, CORR_SCAN = 1024, 256
+CORR_STORE_ROWS = 1
 
 
 class Params(C.Structure):
@@ -299,6 +303,18 @@ def lib():
             l.mi_degensac_desc_quantize.argtypes = [qpp, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
             l.mi_degensac_desc_quantize_pass_rows.restype = C.c_int64
             l.mi_degensac_desc_quantize_pass_rows.argtypes = [C.c_int]
+        if hasattr(l, "mi_degensac_correspondences_pairs_dev"):           # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            # layout | match, keep, flags, kp1, kp2, kp_dim, models, gp, capacity, device[, stream] | corr_offsets, total, rows, entry, pts, resid
+            vp = C.c_void_p
+            mid = [vp, vp, C.c_uint32, vp, vp, C.c_int, vp, gpp, C.c_int64, C.c_int]
+            outs = [vp, vp, vp, vp, vp, vp]
+            for name, lay in (("pairs", [lp, C.c_int, lp, C.c_int, ip, C.c_int]), ("batch", [lp, lp, C.c_int])):
+                f = getattr(l, f"mi_degensac_correspondences_{name}_dev"); f.restype = C.c_int
+                f.argtypes = lay + mid + [vp] + outs
+                f = getattr(l, f"mi_degensac_correspondences_{name}"); f.restype = C.c_int
+                f.argtypes = lay + mid + outs
+            l.mi_degensac_correspondences_tile.restype = C.c_int
+            l.mi_degensac_correspondences_tile.argtypes = [C.c_int]
         l.mi_degensac_kpts_to_xyA.restype = C.c_int
         l.mi_degensac_kpts_to_xyA.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, dp]
         l.mi_degensac_kpts_to_xyA_dev.restype = C.c_int

@@ -873,3 +873,154 @@ def guided_match_pairs(kps_list, desc_list, pairs, models, model="F", ratio=0.9,
         q = np.flatnonzero(m >= 0)
         out.append((q.astype(np.int64), m[q].astype(np.int64), dist[po[p]:po[p + 1]][q, 0]))
     return out
+
+
+def check_correspond_args(match_shape, match_dtype, counts1, counts2, pairs, keep=None, kps1=None, kps2=None, models=None, model="F",
+                          error_type="sampson", capacity=None):
+    """The argument checks of the correspondence export (correspondences_pairs / _batch and their _tensors forms), on shapes and dtype names
+    (numpy or torch).  pairs None = the ragged batch (entry p = pair p, counts1 / counts2 rows per pair), else an integer [K, 2] list over
+    stores of counts1 / counts2 rows per image.  keep / kps1 / kps2 / models: None or (shape, dtype).  Returns (offsets1, offsets2, pairs
+    as contiguous int32 [K, 2] or None, pair_offsets int64 [K + 1], "xy" / "kpts" / None, error_type code, capacity); raises ValueError."""
+    from .api import _error_type, error_type_dict_fundamental, error_type_dict_homography
+    if model not in ("F", "H"):
+        raise ValueError("model should be 'F' or 'H'")
+    et = _error_type(error_type_dict_fundamental if model == "F" else error_type_dict_homography, error_type)
+    cs = [np.asarray(c) for c in (counts1, counts2)]
+    for c in cs:
+        if c.ndim != 1 or (c.size and not np.issubdtype(c.dtype, np.integer)) or (c < 0).any():
+            raise ValueError("counts1 and counts2 should be 1-D arrays of integers >= 0")
+    o1, o2 = (np.concatenate([[0], np.cumsum(c, dtype=np.int64)]).astype(np.int64) for c in cs)
+    if pairs is None:
+        if len(cs[0]) != len(cs[1]):
+            raise ValueError("counts1 and counts2 should have one entry per pair")
+        pr = None; K = len(cs[0]); po = o1.copy(); nt_rows = o2[-1]
+    else:
+        pr = np.asarray(pairs)
+        if pr.ndim != 2 or pr.shape[1] != 2 or not np.issubdtype(pr.dtype, np.integer):
+            raise ValueError("pairs should be an integer array [K, 2] of (image of store 1, image of store 2)")
+        K = pr.shape[0]
+        if K == 0:
+            raise ValueError("at least one pair")
+        m1, m2 = len(o1) - 1, len(o2) - 1
+        if (pr < 0).any() or (pr[:, 0] >= m1).any() or (pr[:, 1] >= m2).any():
+            raise ValueError(f"pairs hold an image index outside its store ({m1} and {m2} images)")
+        pr = np.ascontiguousarray(pr, np.int32)
+        po = np.zeros(K + 1, np.int64); np.cumsum(np.diff(o1)[pr[:, 0]], out=po[1:])
+        nt_rows = np.diff(o2)[pr[:, 1]].sum()
+    if po[-1] > 0x3fffffff or nt_rows > 0x3fffffff:
+        raise ValueError("too many rows in one pair list")
+    N = int(po[-1])
+    if tuple(match_shape) != (N,) or _dtype_name(match_dtype) != "int32":
+        raise ValueError(f"match should be int32 [N] = [{N}], one value per output row of the list")
+    if keep is not None and (tuple(keep[0]) != (N,) or _dtype_name(keep[1]) not in ("bool", "uint8")):
+        raise ValueError(f"keep should be bool or uint8 [N] = [{N}]")
+    if (kps1 is None) != (kps2 is None):
+        raise ValueError("kps1 and kps2 go together")
+    kind = None
+    if kps1 is not None:
+        kinds = []
+        for shp, dt in (kps1, kps2):
+            name = _dtype_name(dt)
+            if len(shp) == 2 and name == "float64" and shp[1] in (2, 6):
+                kinds.append(("xy", shp[1]))
+            elif len(shp) == 2 and name == "float32" and shp[1] == 4:
+                kinds.append(("kpts", 4))
+            else:
+                raise ValueError("keypoints should be float64 [n, 2] / [n, 6] rows or float32 [n, 4] = (x, y, size, angle)")
+        if kinds[0] != kinds[1]:
+            raise ValueError("kps1 and kps2 should have the same layout")
+        if kps1[0][0] != o1[-1] or kps2[0][0] != o2[-1]:
+            raise ValueError("counts do not add up to the number of keypoint rows")
+        kind = kinds[0][0]
+    if models is not None:
+        if kps1 is None:
+            raise ValueError("models (the residuals) need kps1 and kps2")
+        if tuple(models[0]) != (K, 3, 3):
+            raise ValueError(f"models should be [K, 3, 3] = [{K}, 3, 3], one model per list entry")
+        if _dtype_name(models[1]) != "float64":
+            raise ValueError("models should be float64")
+    if capacity is None:
+        cap = N
+    else:
+        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 0:
+            raise ValueError("capacity should be an integer >= 0 (or None = one position per output row)")
+        cap = int(capacity)
+    return o1, o2, pr, po, kind, et, cap
+
+
+def correspond_layout(o1, o2, pr):
+    """the layout arguments of the mi_degensac_correspondences_* entry points: (layout name, ctypes arguments, K)"""
+    lp = C.POINTER(C.c_int64)
+    if pr is None:
+        return "batch", (o1.ctypes.data_as(lp), o2.ctypes.data_as(lp), len(o1) - 1), len(o1) - 1
+    return "pairs", (o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, pr.ctypes.data_as(C.POINTER(C.c_int32)), len(pr)), len(pr)
+
+
+def _correspondences(match, counts1, counts2, pairs, keep, kps_list, kps2_list, models, model, error_type, driver_form, store_rows, device):
+    match = np.asarray(match)
+    kp = None if keep is None else np.asarray(keep)
+    if (kps_list is None) and (kps2_list is not None):
+        raise ValueError("kps2_list names a second store: give kps_list too")
+    K1 = K2 = None
+    if kps_list is not None:
+        stores = []
+        for kl in (kps_list,) if kps2_list is None else (kps_list, kps2_list):
+            k = [np.asarray(x) for x in kl]
+            if len(k) == 0 or any(x.ndim != 2 or x.dtype != k[0].dtype or x.shape[1] != k[0].shape[1] for x in k):
+                raise ValueError("every image's keypoints should be 2-D with the dtype and width of image 0 (at least one image per store)")
+            stores.append(np.concatenate(k))
+        K1, K2 = stores[0], stores[-1]
+    M = None if models is None else np.asarray(models)
+    sd = lambda x: None if x is None else (x.shape, x.dtype)          # noqa: E731
+    o1, o2, pr, po, kind, et, cap = check_correspond_args(match.shape, match.dtype, counts1, counts2, pairs, sd(kp), sd(K1), sd(K2), sd(M), model,
+                                                          error_type, None)
+    name, layout, K = correspond_layout(o1, o2, pr)
+    match = np.ascontiguousarray(match)
+    if kp is not None:
+        kp = np.ascontiguousarray(kp).view(np.uint8)
+    if K1 is not None:
+        same = K2 is K1
+        K1 = np.ascontiguousarray(kpts_to_xyA(K1, device) if kind == "kpts" else K1, np.float64)
+        K2 = K1 if same else np.ascontiguousarray(kpts_to_xyA(K2, device) if kind == "kpts" else K2, np.float64)
+    Md = None
+    if M is not None:
+        Md = np.ascontiguousarray(M if (model == "F" or driver_form) else _h_driver_form(M), np.float64).reshape(K, 9)
+    co = np.zeros(K + 1, np.int64); total = np.zeros(1, np.int64)
+    rows = np.full((cap, 2), -1, np.int32)
+    pts = None if K1 is None else np.full((cap, 4), np.nan)
+    resid = None if Md is None else np.full(cap, np.nan)
+    gp = _lib.GuideParams(model == "H", et, 0.0)
+    vp = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)          # noqa: E731
+    rc = getattr(_lib.lib(), f"mi_degensac_correspondences_{name}")(*layout, vp(match), vp(kp), _lib.CORR_STORE_ROWS if store_rows else 0, vp(K1),
+                                                                   vp(K2), 0 if K1 is None else K1.shape[1], vp(Md), C.byref(gp), cap, int(device),
+                                                                   vp(co), vp(total), vp(rows), None, vp(pts), vp(resid))
+    _lib.check_match(rc)
+    cut = lambda x, p: None if x is None else x[co[p]:co[p + 1]]          # noqa: E731
+    return [{"rows": cut(rows, p), "pts": cut(pts, p), "resid": cut(resid, p)} for p in range(K)]
+
+
+def correspondences_pairs(match, counts1, counts2, pairs, keep=None, kps_list=None, kps2_list=None, models=None, model="F", error_type="sampson",
+                          driver_form=False, store_rows=False, device=0):
+    """The verified matches of a pair list as one compact list per entry (include/mi_degensac.h mi_degensac_correspondences_pairs, blocking,
+    numpy).  match [N] int32 is what a pair-list call returned per output row (train row local to image j, or -1), counts1 / counts2 the
+    rows per image of the two stores and pairs [K, 2] the list.  What goes in as it is: `match` and `keep=inlier` of match_and_verify_pairs
+    (concatenated in list order); `match` of guided_match_pairs' tensor form with keep=None; `keep = inlier_f & inlier_h` of the F+H call.
+    A row is selected when 0 <= match < rows(image j) and (keep is None or keep != 0).  kps_list (one [n, 2] / [n, 6] float64 or [n, 4]
+    float32 array per image; kps2_list for a second store) adds the coordinates, models [K, 3, 3] (F, or the user-facing H;
+    driver_form=True: H_c = inv(H)^T) the estimator's own residual of error_type, the function the gate of guided matching uses.
+    Returns a list of K dicts: rows [n_p, 2] int32 = (query row in image i, train row in image j) in query order — with store_rows=True
+    (row of store 1, row of store 2) —, pts [n_p, 4] = x1, y1, x2, y2 or None, resid [n_p] or None."""
+    if pairs is None:
+        raise ValueError("pairs should be an integer array [K, 2] of (image of store 1, image of store 2)")
+    return _correspondences(match, counts1, counts2, pairs, keep, kps_list, kps2_list, models, model, error_type, driver_form, store_rows, device)
+
+
+def correspondences_batch(match, counts1, counts2, keep=None, kps1_list=None, kps2_list=None, models=None, model="F", error_type="sampson",
+                          driver_form=False, store_rows=False, device=0):
+    """correspondences_pairs on the ragged batch (mi_degensac_correspondences_batch): entry p is pair p with counts1[p] query and counts2[p]
+    train rows, match [sum(counts1)] int32 the concatenated `match` of match_and_verify_batch / guided_match_batch, keep likewise (the
+    concatenated `inlier`), kps1_list[p] / kps2_list[p] the pair's keypoints (both or none).  store_rows=True gives rows of the two
+    concatenations."""
+    if (kps1_list is None) != (kps2_list is None):
+        raise ValueError("kps1_list and kps2_list go together")
+    return _correspondences(match, counts1, counts2, None, keep, kps1_list, kps2_list, models, model, error_type, driver_form, store_rows, device)

@@ -774,3 +774,82 @@ def guided_match_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs
     for t in (a, b, k1, k2, M):
         t.record_stream(stream)
     return match, idx, dist, po
+
+
+def _correspondences_tensors(match, counts1, counts2, pairs, keep, kps1, kps2, models, model, error_type, driver_form, store_rows, with_entry,
+                             capacity):
+    import torch
+    from . import matcher
+    ts = [t for t in (match, keep, kps1, kps2, models) if t is not None]
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        raise ValueError("match, keep, kps1, kps2 and models must be torch tensors on a ROCm device")
+    sd = lambda t: None if t is None else (tuple(t.shape), t.dtype)          # noqa: E731
+    o1, o2, pr, po, kind, et, cap = matcher.check_correspond_args(tuple(match.shape), match.dtype, counts1, counts2, pairs, sd(keep), sd(kps1),
+                                                                  sd(kps2), sd(models), model, error_type, capacity)
+    if any(t.device != match.device for t in ts) or match.device.type != "cuda":
+        raise ValueError("match, keep, kps1, kps2 and models must live on the same ROCm device")
+    name, layout, K = matcher.correspond_layout(o1, o2, pr)
+    dev = match.device
+    m = match.contiguous()
+    kp = None if keep is None else keep.contiguous().view(torch.uint8)
+    k1 = k2 = M = None
+    if kps1 is not None:
+        conv = kpts_to_xyA_tensors if kind == "kpts" else (lambda k: k.contiguous())
+        k1 = conv(kps1); k2 = k1 if kps2 is kps1 else conv(kps2)          # once per store
+    if models is not None:
+        M = models.contiguous()
+        if model == "H" and not driver_form:
+            M = _h_driver_form(M)
+        M = M.reshape(K, 9).contiguous()
+    rows = torch.full((cap, 2), -1, dtype=torch.int32, device=dev)
+    co = torch.empty(K + 1, dtype=torch.int64, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    entry = torch.full((cap,), -1, dtype=torch.int32, device=dev) if with_entry else None
+    pts = None if k1 is None else torch.full((cap, 4), float("nan"), dtype=torch.float64, device=dev)
+    resid = None if M is None else torch.full((cap,), float("nan"), dtype=torch.float64, device=dev)
+    gp = _lib.GuideParams(model == "H", et, 0.0)
+    stream = torch.cuda.current_stream(dev)
+    p = lambda t: None if t is None else t.data_ptr()          # noqa: E731
+    rc = getattr(_lib.lib(), f"mi_degensac_correspondences_{name}_dev")(*layout, p(m), p(kp), _lib.CORR_STORE_ROWS if store_rows else 0, p(k1), p(k2),
+                                                                       0 if k1 is None else int(k1.shape[1]), p(M), C.byref(gp), cap,
+                                                                       dev.index or 0, C.c_void_p(stream.cuda_stream), co.data_ptr(),
+                                                                       total.data_ptr(), p(rows), p(entry), p(pts), p(resid))
+    _lib.check_match(rc)
+    for t in (m, kp, k1, k2, M):
+        if t is not None:
+            t.record_stream(stream)
+    return rows, co, total, entry, pts, resid
+
+
+def correspondences_pairs_tensors(match, counts1, counts2, pairs, keep=None, kps1=None, kps2=None, models=None, model="F", error_type="sampson",
+                                  driver_form=False, store_rows=False, with_entry=False, capacity=None):
+    """The verified matches of a pair list as compact per-entry lists, on the device and without a host synchronisation (include/mi_degensac.h
+    mi_degensac_correspondences_pairs_dev): what a two-view database, triangulation or a track builder takes.  match [N] int32 (train row
+    local to image j, or -1) with N the output rows of the list, counts1 / counts2 the rows per image of the two stores, pairs [K, 2].
+    What goes in as it is: `match` and `keep=inlier` of match_and_verify_pairs_tensors (and of the batch form, with
+    correspondences_batch_tensors); `match` of guided_match_pairs_tensors with keep=None; `keep = inlier_f & inlier_h` of
+    match_and_verify_fh_pairs_tensors.  A row is selected when 0 <= match < rows(image j) and (keep is None or keep != 0, bool or uint8);
+    any other match value means "not selected".  kps1 / kps2 (the stores' keypoints, [n, 2] / [n, 6] float64, or [n, 4] float32 through
+    kpts_to_xyA_tensors) add pts; models [K, 3, 3] float64 (what the verify calls return: F, or the user-facing H, converted on the device;
+    driver_form=True takes H_c = inv(H)^T) add resid = the estimator's own residual of error_type on every exported correspondence, the
+    function the gate of guided matching calls (so resid <= th holds for every correspondence of a guided call with that threshold).
+    Returns (rows [cap, 2] int32, corr_offsets [K + 1] int64 on the device, total [1] int64 on the device, entry [cap] int32 or None,
+    pts [cap, 4] float64 = x1, y1, x2, y2 or None, resid [cap] float64 or None).  The selected rows stand in list order, query order
+    inside an entry; entry p owns the positions corr_offsets[p] .. corr_offsets[p + 1].  rows = (query row in image i, train row in image
+    j), with store_rows=True (row of store 1, row of store 2).  cap = capacity, or N when capacity is None; positions >= total keep their
+    fill (rows / entry -1, pts / resid NaN).  corr_offsets and total are exact whatever capacity is: total > cap says that the tail was
+    dropped.  capacity=int(n_tentatives.sum()) is a safe bound after a verify call (inliers are tentatives) and saves the memory of
+    the rows that were never matched."""
+    if pairs is None:
+        raise ValueError("pairs should be an integer array [K, 2] of (image of store 1, image of store 2)")
+    return _correspondences_tensors(match, counts1, counts2, pairs, keep, kps1, kps2, models, model, error_type, driver_form, store_rows, with_entry,
+                                    capacity)
+
+
+def correspondences_batch_tensors(match, counts1, counts2, keep=None, kps1=None, kps2=None, models=None, model="F", error_type="sampson",
+                                  driver_form=False, store_rows=False, with_entry=False, capacity=None):
+    """correspondences_pairs_tensors on the ragged batch (mi_degensac_correspondences_batch_dev): entry p is pair p with counts1[p] query rows
+    and counts2[p] train rows; match [sum(counts1)] and keep are `match` / `inlier` of match_and_verify_batch_tensors (or `match` of
+    guided_match_batch_tensors), kps1 / kps2 that call's keypoints.  The same result as the pair-list call on the identity list."""
+    return _correspondences_tensors(match, counts1, counts2, None, keep, kps1, kps2, models, model, error_type, driver_form, store_rows, with_entry,
+                                    capacity)
