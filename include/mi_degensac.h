@@ -828,6 +828,49 @@ int mi_degensac_correspondences_batch(const int64_t *offsets1, const int64_t *of
 /* the tile constants of the compaction: which = 0 rows per workgroup, 1 workgroup counts per scan step (-1 for any other value) */
 int mi_degensac_correspondences_tile(int which);
 
+/* ---- tracks: the connected components of exported matches over one image store (mi_tracks.hip) ---------------------------------
+ * A track is a set of keypoints across the images of a collection that are transitively matched.  The input is exactly what the
+ * correspondence export writes for a collection matched against itself with MI_DEGENSAC_CORR_STORE_ROWS: d_rows [n_edges, 2] int32 of
+ * store rows and its device total.  Both columns index ONE store, described by offsets_host [n_images + 1] (the two-store form of a
+ * pair list has no tracks): R = offsets_host[n_images] - offsets_host[0] nodes, node k = store row offsets_host[0] + k.
+ * Edges: only the first min(*d_total, n_edges) count (d_total NULL: all n_edges; a negative total: none).  An edge with either end
+ * outside [offsets_host[0], offsets_host[n_images]) is ignored and never used as an index, which covers the export's -1 fill; self
+ * edges and repeated edges are legal and change nothing.
+ * Outputs, all device arrays, each a pure function of the input (the same bits on every call, whatever the scheduling):
+ *   d_label [R] int32                 the smallest node of k's connected component; an isolated node has itself (nullable)
+ *   d_track [R] int32                 a track is a component of at least two nodes, numbered 0, 1, ... in ascending order of their
+ *                                     label: the node's track, or -1
+ *   d_n_tracks [1], d_n_obs [1] int64 the tracks and their members in all
+ *   d_track_offsets [R/2 + 1] int64   track t owns d_obs[d_track_offsets[t] .. d_track_offsets[t + 1]); the elements after [n_tracks]
+ *                                     equal n_obs, so every prefix is a valid table
+ *   d_obs [R] int32                   the store rows of all track members, track after track, ascending inside a track; -1 at
+ *                                     positions >= n_obs (nullable)
+ *   d_obs_image [R] int32             their image: the last i with offsets_host[i] <= row, which skips empty images; -1 at positions
+ *                                     >= n_obs (nullable; needs d_obs)
+ *   d_track_images [R/2] int32        the distinct images of the track; -1 at positions >= n_tracks.  A track is consistent (at most
+ *                                     one keypoint per image) iff d_track_images[t] == d_track_offsets[t + 1] - d_track_offsets[t]
+ *                                     (nullable; needs d_obs)
+ * R == 0 writes n_tracks = n_obs = 0 and track_offsets[0] = 0; n_edges == 0 gives label[k] = k, track = -1 and zero tracks.
+ * Asynchronous on `stream`, no host synchronisation; temporaries (up to 25 bytes per node, 4 per image, 8 per 1024 nodes and the sort's
+ * own) are allocated and freed stream-ordered.  The components come from a lock-free link (hook the larger root under the smaller by
+ * compare-and-swap) whose result does not depend on the schedule: the smallest node of a component always ends as its root; the
+ * grouping is a stable radix sort, the track numbers a scan, and track_images integer sums.  No pass waits for another workgroup.
+ * Refused with MI_DEGENSAC_EINVAL and a message in mi_degensac_match_last_error(), before a device is looked for and in this order:
+ * n_images < 0; NULL offsets_host; decreasing or negative offsets, or offsets beyond 0x7fffffff; n_edges < 0 or > 0x3fffffff; NULL d_rows
+ * with n_edges > 0; NULL d_track, d_n_tracks, d_n_obs or d_track_offsets; d_obs_image or d_track_images without d_obs; a d_rows that is
+ * not 4-byte aligned (an 8-byte-aligned d_rows is read as int2). */
+int mi_degensac_tracks_dev(const int64_t *offsets_host, int n_images, const int32_t *d_rows, int64_t n_edges, const int64_t *d_total /*nullable*/,
+                           int device, void *stream, int32_t *d_label /*nullable*/, int32_t *d_track, int64_t *d_n_tracks, int64_t *d_n_obs,
+                           int64_t *d_track_offsets, int32_t *d_obs /*nullable*/, int32_t *d_obs_image /*nullable*/,
+                           int32_t *d_track_images /*nullable*/);
+/* the same on host pointers (blocking): the edges go to the device once and every array comes back whole, fills included; total is
+ * passed by value, < 0 = all n_edges */
+int mi_degensac_tracks(const int64_t *offsets, int n_images, const int32_t *rows, int64_t n_edges, int64_t total, int device,
+                       int32_t *label /*nullable*/, int32_t *track, int64_t *n_tracks, int64_t *n_obs, int64_t *track_offsets,
+                       int32_t *obs /*nullable*/, int32_t *obs_image /*nullable*/, int32_t *track_images /*nullable*/);
+/* the tile constants of the boundary passes: which = 0 sorted positions per workgroup, 1 workgroup counts per scan step (-1 else) */
+int mi_degensac_tracks_tile(int which);
+
 /* ---- unit-level device entry points (parity tests of the kernels' building blocks) ------------ */
 /* score n_models fundamental (kind 0: Sampson, 1: symmetric epipolar) or homography (kind 10..14:
  * H Sampson, symm_sq_max, symm_max, symm_sq_sum, symm_sum) models against all n points: I (<= th)

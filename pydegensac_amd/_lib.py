@@ -35,6 +35,9 @@ def TUNE_LONG_SHIFT(l): return (int(l) & 7) << 29        # noqa: E704,E741  "man
 # compaction and workgroup counts per step of its scan; MI_DEGENSAC_CORR_STORE_ROWS
 CORR_ROWS, CORR_SCAN = 1024, 256
 CORR_STORE_ROWS = 1
+# the tracks (csrc/mi_tracks.hip TK_ROWS / TK_SCAN, mi_degensac_tracks_tile): sorted positions per workgroup of the boundary passes and
+# workgroup counts per step of their scan
+TRACK_ROWS, TRACK_SCAN = 1024, 256
 
 
 class Params(C.Structure):
@@ -315,6 +318,15 @@ def lib():
                 f.argtypes = lay + mid + outs
             l.mi_degensac_correspondences_tile.restype = C.c_int
             l.mi_degensac_correspondences_tile.argtypes = [C.c_int]
+        if hasattr(l, "mi_degensac_tracks_dev"):                          # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            # offsets, n_images, rows, n_edges, total, device[, stream] | label, track, n_tracks, n_obs, track_offsets, obs, obs_image, track_images
+            vp = C.c_void_p
+            l.mi_degensac_tracks_dev.restype = C.c_int
+            l.mi_degensac_tracks_dev.argtypes = [lp, C.c_int, vp, C.c_int64, vp, C.c_int, vp] + [vp] * 8
+            l.mi_degensac_tracks.restype = C.c_int
+            l.mi_degensac_tracks.argtypes = [lp, C.c_int, vp, C.c_int64, C.c_int64, C.c_int] + [vp] * 8
+            l.mi_degensac_tracks_tile.restype = C.c_int
+            l.mi_degensac_tracks_tile.argtypes = [C.c_int]
         l.mi_degensac_kpts_to_xyA.restype = C.c_int
         l.mi_degensac_kpts_to_xyA.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, dp]
         l.mi_degensac_kpts_to_xyA_dev.restype = C.c_int

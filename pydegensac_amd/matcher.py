@@ -1024,3 +1024,47 @@ def correspondences_batch(match, counts1, counts2, keep=None, kps1_list=None, kp
     if (kps1_list is None) != (kps2_list is None):
         raise ValueError("kps1_list and kps2_list go together")
     return _correspondences(match, counts1, counts2, None, keep, kps1_list, kps2_list, models, model, error_type, driver_form, store_rows, device)
+
+
+def check_tracks_args(rows_shape, rows_dtype, counts, total=None):
+    """The argument checks of tracks / tracks_tensors on a shape and a dtype name (numpy or torch).  counts: the rows per image of the ONE
+    store both columns of `rows` index; total: None, or for the numpy form an integer (< 0 = all edges).  Returns (offsets int64
+    [n_images + 1], R, M); raises ValueError."""
+    c = np.asarray(counts)
+    if c.ndim != 1 or (c.size and not np.issubdtype(c.dtype, np.integer)) or (c < 0).any():
+        raise ValueError("counts should be a 1-D array of integers >= 0, the rows per image of the store")
+    off = np.concatenate([[0], np.cumsum(c, dtype=np.int64)]).astype(np.int64)
+    if off[-1] > 0x7fffffff:
+        raise ValueError("too many rows in the store (its rows must fit int32)")
+    if len(rows_shape) != 2 or rows_shape[1] != 2 or _dtype_name(rows_dtype) != "int32":
+        raise ValueError("rows should be int32 [M, 2] of store rows, as the correspondence export writes them with store_rows=True")
+    if rows_shape[0] > 0x3fffffff:
+        raise ValueError("too many edges in one list")
+    if total is not None and (isinstance(total, bool) or not isinstance(total, (int, np.integer))):
+        raise ValueError("total should be an integer (or None = all edges)")
+    return off, int(off[-1]), int(rows_shape[0])
+
+
+def tracks(rows, counts, total=None, device=0):
+    """Tracks = the connected components of verified matches over one image store (include/mi_degensac.h mi_degensac_tracks, blocking,
+    numpy).  rows [M, 2] int32 holds store rows, as correspondences_pairs(..., store_rows=True) gives them for a collection matched
+    against itself (concatenate the entries' rows); counts are the rows per image of that store; total: only the first min(total, M)
+    edges count (None or < 0: all).  Ends outside the store (the -1 fill) drop their edge; self edges and repeats change nothing.
+    Returns a dict: label [R] (the smallest store row of the keypoint's component), track [R] (its track, or -1), n_tracks, n_obs,
+    track_offsets [n_tracks + 1], obs [n_obs] (the store rows of the members, track after track in ascending order of the tracks' smallest
+    member, ascending inside), obs_image [n_obs] and track_images [n_tracks] (distinct images: a track is consistent iff it equals the
+    track's length)."""
+    rows = np.asarray(rows)
+    off, R, M = check_tracks_args(rows.shape, rows.dtype, counts, total)
+    rows = np.ascontiguousarray(rows)
+    half = R // 2
+    label = np.empty(R, np.int32); track = np.empty(R, np.int32); obs = np.empty(R, np.int32); oi = np.empty(R, np.int32)
+    to = np.empty(half + 1, np.int64); ti = np.empty(half, np.int32); n = np.zeros(2, np.int64)
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)          # noqa: E731
+    rc = _lib.lib().mi_degensac_tracks(off.ctypes.data_as(C.POINTER(C.c_int64)), len(off) - 1, vp(rows) if M else None, M,
+                                       -1 if total is None else int(total), int(device), vp(label), vp(track), vp(n[0:]), vp(n[1:]), vp(to), vp(obs),
+                                       vp(oi), vp(ti))
+    _lib.check_match(rc)
+    nt, no = int(n[0]), int(n[1])
+    return {"label": label, "track": track, "n_tracks": nt, "n_obs": no, "track_offsets": to[:nt + 1], "obs": obs[:no], "obs_image": oi[:no],
+            "track_images": ti[:nt]}

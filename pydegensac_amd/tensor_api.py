@@ -853,3 +853,47 @@ def correspondences_batch_tensors(match, counts1, counts2, keep=None, kps1=None,
     guided_match_batch_tensors), kps1 / kps2 that call's keypoints.  The same result as the pair-list call on the identity list."""
     return _correspondences_tensors(match, counts1, counts2, None, keep, kps1, kps2, models, model, error_type, driver_form, store_rows, with_entry,
                                     capacity)
+
+
+def tracks_tensors(rows, counts, total=None, with_label=False):
+    """Tracks = the connected components of verified matches over one image store, on the device and without a host synchronisation
+    (include/mi_degensac.h mi_degensac_tracks_dev).  rows [M, 2] int32 and total [1] int64 are what
+    correspondences_pairs_tensors(..., store_rows=True) returned for a collection matched against itself (the same tensors on both sides),
+    counts the rows per image of that store.  Only the first min(total, M) edges count (total=None: all M); an edge with an end outside
+    the store (the -1 fill of the export) is ignored, self edges and repeated edges change nothing.
+    Returns (track [R] int32 = the keypoint's track or -1, n_tracks [1] int64, track_offsets [R // 2 + 1] int64, obs [R] int32,
+    obs_image [R] int32, track_images [R // 2] int32, n_obs [1] int64[, label [R] int32 with with_label=True]), all on the device, R the
+    rows of the store.  A track is a component of at least two keypoints; tracks are numbered in ascending order of their smallest store
+    row (label).  Track t owns obs[track_offsets[t] : track_offsets[t + 1]], store rows in ascending order, obs_image their images;
+    track_images[t] is the number of distinct images, so the track is consistent (one keypoint per image at most) iff it equals the
+    track's length.  Tails: track_offsets beyond [n_tracks] repeat n_obs, obs / obs_image beyond n_obs and track_images beyond n_tracks
+    hold -1.  Every output is a pure function of the input: the same bits on every call.  Asynchronous on the current stream."""
+    import torch
+    from . import matcher
+    if not isinstance(rows, torch.Tensor) or (total is not None and not isinstance(total, torch.Tensor)):
+        raise ValueError("rows (and total) must be torch tensors on a ROCm device")
+    off, R, M = matcher.check_tracks_args(tuple(rows.shape), rows.dtype, counts)
+    if not rows.is_contiguous():
+        raise ValueError("rows should be a contiguous int32 [M, 2] tensor")
+    if total is not None and (tuple(total.shape) != (1,) or total.dtype != torch.int64):
+        raise ValueError("total should be int64 [1] on the device, as the correspondence export returns it")
+    if rows.device.type != "cuda" or (total is not None and total.device != rows.device):
+        raise ValueError("rows and total must live on the same ROCm device")
+    dev = rows.device
+    half = R // 2
+    i32 = lambda n: torch.empty(max(n, 1), dtype=torch.int32, device=dev)          # noqa: E731  (an address also where n == 0)
+    track, obs, oi, ti = i32(R), i32(R), i32(R), i32(half)
+    label = i32(R) if with_label else None
+    to = torch.empty(half + 1, dtype=torch.int64, device=dev)
+    nt = torch.empty(1, dtype=torch.int64, device=dev); no = torch.empty(1, dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    p = lambda t: None if t is None else t.data_ptr()          # noqa: E731
+    rc = _lib.lib().mi_degensac_tracks_dev(off.ctypes.data_as(C.POINTER(C.c_int64)), len(off) - 1, p(rows) if M else None, M, p(total),
+                                           dev.index or 0, C.c_void_p(stream.cuda_stream), p(label), p(track), p(nt), p(no), p(to), p(obs), p(oi),
+                                           p(ti))
+    _lib.check_match(rc)
+    for t in (rows, total):
+        if t is not None:
+            t.record_stream(stream)
+    out = (track[:R], nt, to, obs[:R], oi[:R], ti[:half], no)
+    return out + (label[:R],) if with_label else out
