@@ -258,7 +258,11 @@ int mi_degensac_find_homography_batch_dev(const double *d_pts1, const double *d_
  * the entry points above).  u10: [total, 10] doubles, per correspondence x1 y1 a1 b1 c1 | x2 y2 a2 b2 c2 with the local
  * affine frame [a 0; b c] of each image; a sample is TWO correspondences (14 x 15 system of Chum & Matas, ICPR 2012).
  * H (9 doubles per pair, column-wise like the reference's internal H) maps image 2 to image 1; mask[j] = HDs residual of
- * the returned model <= th (ranH2el.c:189-198).  stats as for the other drivers ([0] samples, [1] LO runs, [3] I). */
+ * the returned model <= th (ranH2el.c:189-198).  stats as for the other drivers ([0] samples, [1] LO runs, [3] I).
+ * Device entry: d_offsets holds ABSOLUTE row numbers into d_u10 and d_mask, so with d_offsets[0] > 0 both pointers stay the bases of the
+ * whole store, pair p reads rows d_offsets[p] .. d_offsets[p+1] and writes those mask bytes and nothing outside them, while d_H, d_stats
+ * (may be NULL) and d_seeds are indexed by p from 0; offsets_host must hold the same n_pairs + 1 values as d_offsets (the workspace is
+ * sized from it). */
 typedef struct mi_degensac_h2el_params {
     double   th;          /* threshold on the squared transfer error HDs returns (the reference's `th`)       */
     double   conf;        /* confidence of the sample-count rule (nsamples with sample size 2)                  */
