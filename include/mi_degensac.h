@@ -875,6 +875,61 @@ int mi_degensac_tracks(const int64_t *offsets, int n_images, const int32_t *rows
 /* the tile constants of the boundary passes: which = 0 sorted positions per workgroup, 1 workgroup counts per scan step (-1 else) */
 int mi_degensac_tracks_tile(int which);
 
+/* ---- refit F / H on exported correspondence lists (mi_refit.hip) ---------------------------------------------------------------
+ * The guided stage brings back matches the estimator never saw, and matches may come from elsewhere altogether (a learned matcher, a
+ * previous frame's model).  This call judges such a list against a model and refits the model on what it keeps, per list entry, on the
+ * device and without a host synchronisation: the row ranges are read from device memory, so the host never learns a length.
+ * Inputs per entry p (all device arrays on one device, as mi_degensac_correspondences_* write them):
+ *   its rows     d_pts[o[p] .. o[p + 1]) of d_pts [cap, 4] float64 = x1, y1, x2, y2, with o = d_corr_offsets [K + 1] int64
+ *   M0[p]        d_models[9 p ..], the start model in the driver's form
+ *   th           from gp->px_th and gp->error_type exactly as the guided gate derives it (F: px_th^2; H: px_th^2 for 0, 1, 3 and px_th
+ *                for 2, 4); resid(M; row) is the estimator's own function of that error type, the one the guided gate and the export's
+ *                d_resid use (F: 0 dg_FDs, 1 dg_FDsSym; H: 0 dg_HDs, 1..4 dg_Hsym on dg_hsym_prepare(M)), fp64 without contraction.
+ *   members(M)   the rows with resid(M; row) <= th, in row order.  A NaN residual is not a member; a model of nine zeros, or with an entry
+ *                that is not finite, has no members.
+ * The rule:
+ *   best = M0; I = members(best); n0 = |I|
+ *   repeat at most max_fits times (0 is allowed):
+ *       if |I| < 8 (F) / 4 (H): stop, MI_DEGENSAC_REFIT_SHORT
+ *       M = u2f / u2h on the rows of I in list order: the reference's non-minimal solver, in the variant the drivers use for that length
+ *           (F: <= 16 rows the small solver — 8 rows the 9 x 8 null vector —, beyond the sequential normalised least squares; H: 4 rows
+ *           the DLT null vector, 5 .. 12 the small normalised DLT, beyond the sequential one)
+ *       if M has an entry that is not finite: stop, MI_DEGENSAC_REFIT_BAD_FIT
+ *       I' = members(M)
+ *       if |I'| < |I|: stop, MI_DEGENSAC_REFIT_WORSE (best and I stay)
+ *       best = M; same = (I' == I); I = I'
+ *       if same: stop, MI_DEGENSAC_REFIT_FIXED
+ *   all max_fits rounds used: MI_DEGENSAC_REFIT_MAX_FITS
+ * The estimators' symmetric check and LAF check are not part of it, as in the guided gate: the call judges a list against a model, it
+ * does not choose correspondences.  An entry whose range does not lie wholly inside [0, cap) — a truncated export (total > capacity),
+ * or a decreasing pair of offsets — keeps M0, flags no member and has status MI_DEGENSAC_REFIT_TRUNCATED; d_corr_offsets is device
+ * data and is not validated on the host.  An empty entry keeps M0 (SHORT, or MAX_FITS with max_fits == 0).  Ranges must not overlap.
+ * Outputs:
+ *   d_models_out [K, 9]    best, driver form
+ *   d_inlier [cap] uint8   1 for the members of best; a position no entry owns keeps 0
+ *   d_models_user [K, 9]   (nullable) H: the user-facing inv(H_c^T) of best, nine zeros where best is zero, singular or not finite; F: best
+ *   d_info [K, 4] int32    (nullable) n0, |I| at the end, fits run, status
+ *   d_resid [cap]          (nullable) resid(best; row); a position no entry owns keeps NaN
+ * One workgroup per entry, no atomics, every sum in list order: the same bits on every call.  Asynchronous on `stream`; temporaries
+ * (68 bytes per row of cap: the fits' staging array and the member lists) are allocated and freed stream-ordered.
+ * Refused with MI_DEGENSAC_EINVAL and a message in mi_degensac_match_last_error(), before a device is looked for and in this order:
+ * n_entries < 0; cap < 0 or > 0x3fffffff; max_fits < 0; NULL gp, a gp whose struct_size does not cover the fields, homography other than
+ * 0 / 1, an error_type of the other model kind, a px_th that is negative or NaN; NULL d_corr_offsets; for n_entries > 0 NULL d_models or
+ * d_models_out; for cap > 0 NULL d_pts or d_inlier.  n_entries == 0 and cap == 0 succeed (with n_entries == 0 the fills are all that
+ * is written). */
+enum { MI_DEGENSAC_REFIT_FIXED = 0, MI_DEGENSAC_REFIT_MAX_FITS = 1, MI_DEGENSAC_REFIT_SHORT = 2, MI_DEGENSAC_REFIT_BAD_FIT = 3,
+       MI_DEGENSAC_REFIT_WORSE = 4, MI_DEGENSAC_REFIT_TRUNCATED = 5 };
+int mi_degensac_refit_lists_dev(const double *d_pts, const int64_t *d_corr_offsets, const double *d_models, int n_entries, int64_t cap,
+                                const mi_degensac_guide_params *gp, int max_fits, int device, void *stream, double *d_models_out,
+                                uint8_t *d_inlier, double *d_models_user /*nullable*/, int32_t *d_info /*nullable*/,
+                                double *d_resid /*nullable*/);
+/* the same on host pointers (blocking): pts, corr_offsets and models go to the device once, every output comes back whole */
+int mi_degensac_refit_lists(const double *pts, const int64_t *corr_offsets, const double *models, int n_entries, int64_t cap,
+                            const mi_degensac_guide_params *gp, int max_fits, int device, double *models_out, uint8_t *inlier,
+                            double *models_user /*nullable*/, int32_t *info /*nullable*/, double *resid /*nullable*/);
+/* the tile constants: which = 0 rows per workgroup and step of a scoring pass, 1 the cap on the grid (-1 for any other value) */
+int mi_degensac_refit_tile(int which);
+
 /* ---- unit-level device entry points (parity tests of the kernels' building blocks) ------------ */
 /* score n_models fundamental (kind 0: Sampson, 1: symmetric epipolar) or homography (kind 10..14:
  * H Sampson, symm_sq_max, symm_max, symm_sq_sum, symm_sum) models against all n points: I (<= th)

@@ -38,6 +38,10 @@ CORR_STORE_ROWS = 1
 # the tracks (csrc/mi_tracks.hip TK_ROWS / TK_SCAN, mi_degensac_tracks_tile): sorted positions per workgroup of the boundary passes and
 # workgroup counts per step of their scan
 TRACK_ROWS, TRACK_SCAN = 1024, 256
+# the refit (csrc/mi_refit.hip RF_STEP / RF_GRID, mi_degensac_refit_tile): rows per workgroup and step of a scoring pass, the cap on the
+# grid; the status column of its info rows (MI_DEGENSAC_REFIT_*)
+REFIT_STEP, REFIT_GRID = 1024, 256
+REFIT_FIXED, REFIT_MAX_FITS, REFIT_SHORT, REFIT_BAD_FIT, REFIT_WORSE, REFIT_TRUNCATED = range(6)
 
 
 class Params(C.Structure):
@@ -327,6 +331,15 @@ def lib():
             l.mi_degensac_tracks.argtypes = [lp, C.c_int, vp, C.c_int64, C.c_int64, C.c_int] + [vp] * 8
             l.mi_degensac_tracks_tile.restype = C.c_int
             l.mi_degensac_tracks_tile.argtypes = [C.c_int]
+        if hasattr(l, "mi_degensac_refit_lists_dev"):                     # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            # pts, corr_offsets, models, K, cap, gp, max_fits, device[, stream] | models_out, inlier, models_user, info, resid
+            vp = C.c_void_p
+            l.mi_degensac_refit_lists_dev.restype = C.c_int
+            l.mi_degensac_refit_lists_dev.argtypes = [vp, vp, vp, C.c_int, C.c_int64, gpp, C.c_int, C.c_int, vp] + [vp] * 5
+            l.mi_degensac_refit_lists.restype = C.c_int
+            l.mi_degensac_refit_lists.argtypes = [vp, vp, vp, C.c_int, C.c_int64, gpp, C.c_int, C.c_int] + [vp] * 5
+            l.mi_degensac_refit_tile.restype = C.c_int
+            l.mi_degensac_refit_tile.argtypes = [C.c_int]
         l.mi_degensac_kpts_to_xyA.restype = C.c_int
         l.mi_degensac_kpts_to_xyA.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, dp]
         l.mi_degensac_kpts_to_xyA_dev.restype = C.c_int

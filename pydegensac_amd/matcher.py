@@ -1068,3 +1068,45 @@ def tracks(rows, counts, total=None, device=0):
     nt, no = int(n[0]), int(n[1])
     return {"label": label, "track": track, "n_tracks": nt, "n_obs": no, "track_offsets": to[:nt + 1], "obs": obs[:no], "obs_image": oi[:no],
             "track_images": ti[:nt]}
+
+
+def check_refit_args(pts_shape, pts_dtype, off_shape, off_dtype, models_shape, models_dtype, model="F", px_th=None, error_type="sampson",
+                     max_fits=4):
+    """The argument checks of refit_correspondences / refit_correspondences_tensors on shapes and dtype names (numpy or torch): pts float64
+    [cap, 4], corr_offsets int64 [K + 1], models float64 [K, 3, 3], px_th >= 0 (None = the model's default), error_type one of the model's
+    names, max_fits an integer >= 0.  Returns (K, cap, px_th, error_type code, max_fits); raises ValueError."""
+    if len(off_shape) != 1 or off_shape[0] < 1 or _dtype_name(off_dtype) != "int64":
+        raise ValueError("corr_offsets should be int64 [K + 1], as the correspondence export returns it")
+    K = int(off_shape[0]) - 1
+    px, et = check_guided_args(model, px_th, error_type, models_shape, models_dtype, K)
+    if len(pts_shape) != 2 or pts_shape[1] != 4 or _dtype_name(pts_dtype) != "float64":
+        raise ValueError("pts should be float64 [cap, 4] = x1, y1, x2, y2, as the correspondence export returns it")
+    if pts_shape[0] > 0x3fffffff:
+        raise ValueError("too many rows in one list")
+    if isinstance(max_fits, bool) or not isinstance(max_fits, (int, np.integer)) or max_fits < 0:
+        raise ValueError("max_fits should be an integer >= 0")
+    return K, int(pts_shape[0]), px, et, int(max_fits)
+
+
+def refit_correspondences(pts, corr_offsets, models, model="F", px_th=None, error_type="sampson", driver_form=False, max_fits=4, with_resid=False,
+                          device=0):
+    """Refit F / H on exported correspondence lists (include/mi_degensac.h mi_degensac_refit_lists, blocking, numpy): per entry p the
+    members of models[p] among the rows pts[corr_offsets[p] : corr_offsets[p + 1]] (resid <= th, the estimator's own residual of
+    error_type and its threshold from px_th, None = the model's default), then at most max_fits rounds of the reference's non-minimal fit
+    on the members followed by the members of the fit; a round that loses members is dropped, a round that keeps the set ends the entry.
+    pts [cap, 4] = x1, y1, x2, y2 and corr_offsets [K + 1] are the concatenated `pts` of correspondences_pairs / _batch and their running
+    lengths; models [K, 3, 3] what a verify call returned (F, or the user-facing H; driver_form=True: H_c = inv(H)^T in and out).
+    Returns (models [K, 3, 3], inlier [cap] bool, info [K, 4] int32 = (members of the start model, members at the end, fits run,
+    _lib.REFIT_* status)[, resid [cap] under the returned model])."""
+    P = np.ascontiguousarray(np.asarray(pts)); o = np.ascontiguousarray(np.asarray(corr_offsets)); M = np.asarray(models)
+    K, cap, px, et, mf = check_refit_args(P.shape, P.dtype, o.shape, o.dtype, M.shape, M.dtype, model, px_th, error_type, max_fits)
+    Md = np.ascontiguousarray(M if (model == "F" or driver_form) else _h_driver_form(M), np.float64).reshape(K, 9)
+    out = np.zeros((K, 9)); user = np.zeros((K, 9)); inl = np.zeros(cap, np.uint8); info = np.zeros((K, 4), np.int32)
+    resid = np.full(cap, np.nan) if with_resid else None
+    gp = _lib.GuideParams(model == "H", et, px)
+    vp = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)          # noqa: E731
+    rc = _lib.lib().mi_degensac_refit_lists(vp(P), vp(o), vp(Md), K, cap, C.byref(gp), mf, int(device), vp(out), vp(inl), vp(user), vp(info),
+                                            vp(resid))
+    _lib.check_match(rc)
+    res = ((out if (model == "F" or driver_form) else user).reshape(K, 3, 3), inl.astype(bool), info)
+    return res + (resid,) if with_resid else res

@@ -897,3 +897,49 @@ def tracks_tensors(rows, counts, total=None, with_label=False):
             t.record_stream(stream)
     out = (track[:R], nt, to, obs[:R], oi[:R], ti[:half], no)
     return out + (label[:R],) if with_label else out
+
+
+def refit_correspondences_tensors(pts, corr_offsets, models, model="F", px_th=None, error_type="sampson", driver_form=False, max_fits=4,
+                                  with_resid=False):
+    """Refit F / H on exported correspondence lists, on the device and without a host synchronisation (include/mi_degensac.h
+    mi_degensac_refit_lists_dev): the model of a verify call has never seen the matches the guided stage brought back, nor matches that
+    come from elsewhere.  pts [cap, 4] float64 and corr_offsets [K + 1] int64 are what correspondences_pairs_tensors / _batch_tensors
+    returned (kps1 / kps2 given), models [K, 3, 3] float64 what any verify call returned: F, or the user-facing H (converted on the device
+    in both directions; driver_form=True takes and returns H_c = inv(H)^T).  Per entry: the members of its model (resid <= th, the
+    estimator's own residual of error_type and its threshold from px_th, None = the model's default, as in the guided calls), then at
+    most max_fits rounds of the reference's non-minimal fit on the members followed by the members of the fit; a round that loses members
+    is dropped, a round that keeps the set ends the entry.  The kernel reads the entries' lengths from corr_offsets itself, so nothing
+    is read back.  An entry that a truncated export (total > capacity) cut keeps its model and flags nothing (status _lib.REFIT_TRUNCATED).
+    Returns (models [K, 3, 3], inlier [cap] bool, info [K, 4] int32 = (members of the start model, members at the end, fits run,
+    _lib.REFIT_* status)[, resid [cap] under the returned model]) on the device, asynchronous on the current stream.  `inlier` goes into
+    correspondences_pairs_tensors as it is only after a scatter to output rows; on the exported list itself it is the mask of the rows."""
+    import torch
+    from . import matcher
+    ts = (pts, corr_offsets, models)
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        raise ValueError("pts, corr_offsets and models must be torch tensors on a ROCm device")
+    K, cap, px, et, mf = matcher.check_refit_args(tuple(pts.shape), pts.dtype, tuple(corr_offsets.shape), corr_offsets.dtype, tuple(models.shape),
+                                                  models.dtype, model, px_th, error_type, max_fits)
+    if any(t.device != pts.device for t in ts) or pts.device.type != "cuda":
+        raise ValueError("pts, corr_offsets and models must live on the same ROCm device")
+    dev = pts.device
+    P = pts.contiguous(); o = corr_offsets.contiguous()
+    M = models.contiguous()
+    if model == "H" and not driver_form:
+        M = _h_driver_form(M)
+    M = M.reshape(K, 9).contiguous()
+    out = torch.empty((K, 9), dtype=torch.float64, device=dev)
+    user = torch.empty((K, 9), dtype=torch.float64, device=dev) if (model == "H" and not driver_form) else None
+    inl = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)          # (an address also where cap == 0)
+    info = torch.empty((K, 4), dtype=torch.int32, device=dev)
+    resid = torch.empty(max(cap, 1), dtype=torch.float64, device=dev) if with_resid else None
+    gp = _lib.GuideParams(model == "H", et, px)
+    stream = torch.cuda.current_stream(dev)
+    p = lambda t: None if t is None else t.data_ptr()          # noqa: E731
+    rc = _lib.lib().mi_degensac_refit_lists_dev(p(P), p(o), p(M), K, cap, C.byref(gp), mf, dev.index or 0, C.c_void_p(stream.cuda_stream), p(out),
+                                                p(inl), p(user), p(info), p(resid))
+    _lib.check_match(rc)
+    for t in (P, o, M):
+        t.record_stream(stream)
+    res = ((out if user is None else user).view(K, 3, 3), inl[:cap].view(torch.bool), info)
+    return res + (resid[:cap],) if with_resid else res
