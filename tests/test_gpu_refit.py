@@ -3,8 +3,14 @@ restatement over the CPU oracle (tests/refit_ref.py).  Equality only: inlier and
 around every output, models to 1e-9 relative Frobenius in driver form (the project's standing bound against its restatement), resid bit
 for bit against the oracle's residual of the device's own output model.  The scenes are refit_ref.gpu_scenes; test_refit_cpu.py asserts
 for each of them that no residual of a visited model lies within 1e-6 th of th, the condition under which the masks can be demanded bit
-for bit.  Entry lengths sit on both sides of the solver switches (F 16 / 17, H 4 / 5 and 12 / 13), of a wave (63 .. 65), of a load of the
-workgroup (255 .. 257) and of a step of the scoring pass (1023 .. 1025, 2049 = a third step)."""
+for bit.  Entry LENGTHS sit at the edges of a wave (63 .. 65), of a load of the workgroup (255 .. 257) and of a step of the scoring pass
+(1023 .. 1025, 2049 = a third step); at 70 % inliers they say little about which solver ran.  MEMBER COUNTS sit at the solver edges: the
+member stores (refit_ref.MEMBER_STORES) hold entries whose members under the start model are known in advance, 8 .. 513 of them for F
+and 4 .. 513 for H, on both sides of the solver switches (F 16 | 17, H 4 | 5 and 12 | 13), of the 8-term unroll of the normal-matrix
+loop, of the wave, of the stride of 256 threads and of 512.  At max_fits = 1 such an entry is "gather these rows, run the driver's solver
+for that count, return the model": there the model is demanded BIT FOR BIT against the oracle's fit (dg_oracle_u2f / dg_oracle_u2h) on
+the same rows, in the pixel frame, in three other frames, under every error type, on rank-deficient sets, and independent of which
+entries the workgroup fitted before."""
 import ctypes as C
 
 import numpy as np
@@ -82,7 +88,7 @@ def _compare(oracle_port, sc, got, ref):
 
 SCENES = ["F_len_0", "F_len_1", "H_len_0", "H_len_1", "H_len_2", "H_len_3", "H_len_4", "F_px2", "F_8_per_wave", "F_8_last_wave", "F_7_of_300",
           "H_4_per_wave", "H_4_last_wave", "H_3_of_200", "F_many", "H_many", "F_offsets", "H_offsets", "F_models", "H_models", "H_models_3",
-          "F_bad_rows", "H_bad_rows"]
+          "F_bad_rows", "H_bad_rows"] + list(R.MEMBER_STORES)
 
 
 def test_scene_list_is_the_catalogue(oracle_port):
@@ -94,7 +100,7 @@ def test_refit_equals_restatement(torch, oracle_port, name):
     """every scene at max_fits = 4: lengths at the tile and solver edges, empty entries first, last and between, a non-zero o[0], unowned
     rows behind, every error type, member counts exactly at 8 / 4 and one below, members in the last wave only and one per wave, 300
     entries on a grid of 256 workgroups, ranges that cross cap / start beyond it / decrease, zero / NaN / inf / 1e+-150 start models,
-    rows that are not finite"""
+    rows that are not finite, the member stores (member counts at the solver edges, other frames, rank-deficient sets)"""
     sc = R.gpu_scenes(oracle_port)[name]
     got, _ = _call(torch, sc, 4)
     _compare(oracle_port, sc, got, R.reference(oracle_port, name, 4))
@@ -111,6 +117,87 @@ def test_max_fits_0_and_1(torch, oracle_port, name, max_fits):
     assert (got["info"][:, 2] <= max_fits).all()
     if max_fits == 0:
         assert np.array_equal(got["models"], sc["models"]) and (got["info"][:, 3] == R.MAX_FITS).all()
+
+
+# ---- the non-minimal fits bit for bit, through max_fits = 1 on entries whose members are known in advance ----
+def _ulps(a, b):
+    """the largest distance of two models in units of the last place, -1 where the two are not comparable that way"""
+    a = np.asarray(a, np.float64); b = np.asarray(b, np.float64)
+    if not (np.isfinite(a).all() and np.isfinite(b).all()) or (np.signbit(a) != np.signbit(b)).any():
+        return -1
+    return int(np.abs(a.view(np.int64) - b.view(np.int64)).max())
+
+
+def _fit_is_the_output(info_row):
+    """one fit was run and kept: its model is models_out (FIXED; MAX_FITS where the one fit gained members)"""
+    return info_row[2] == 1 and info_row[3] in (R.FIXED, R.MAX_FITS)
+
+
+def _bits(torch, oracle_port, name):
+    """the member store at max_fits = 1: the standing comparison, then models_out of every entry whose fit is the output has the bytes of
+    the oracle's fit on the rows at `where`.  Every entry is one (all but H on 4 rows, whose reference fit keeps no member: see
+    test_refit_cpu.test_member_scene_is_a_fixed_point_after_one_fit).  Every differing entry is reported, not the first."""
+    sc = R.gpu_scenes(oracle_port)[name]
+    got, _ = _call(torch, sc, 1)
+    _compare(oracle_port, sc, got, R.reference(oracle_port, name, 1))
+    bad = []; checked = 0
+    for p, where in enumerate(sc["where"]):
+        if not _fit_is_the_output(got["info"][p]):
+            continue
+        want = R.fit(oracle_port, sc["model"], sc["pts"][sc["off"][p]:sc["off"][p + 1]], where)
+        checked += 1
+        if got["models"][p].tobytes() != want.tobytes():
+            bad.append((p, sc["m"][p], _ulps(got["models"][p], want), R.rel_fro(got["models"][p], want)))
+    print(name, "entries checked", checked, "differing (entry, members, ulps, rel)", bad)
+    assert not bad, bad
+    assert checked == len(sc["m"]) - sum(1 for m in sc["m"] if sc["model"] == "H" and m == 4)
+    return got
+
+
+@pytest.mark.parametrize("name", ["F_members_0", "F_members_1", "H_members_0", "H_members_1", "H_members_2", "H_members_3", "H_members_4"])
+def test_fit_carries_the_oracles_bits(torch, oracle_port, name):
+    """dg_u2f_small_w (8 = the 9 x 8 null vector, 9 .. 16), dg_u2f_big (17 .. 513), dg_u2h_small_w (5 .. 12) and dg_u2h_big (13 .. 513) as
+    the refit calls them (no LDS table, the global path of dg_lsq_seq_par with a staging slice of 2 len): every operation is meant to be
+    the reference's IEEE sequence, sums in list order, no contraction, so the model is demanded byte for byte.  Members are never a
+    contiguous range; three entries have them in the second step of the pass only, at rows 0 / 1023 / 1024 / n - 1, and inside the last
+    partly filled wave.  The error type changes which rows are members, not the fit: types other than 0 at the switch counts only."""
+    _bits(torch, oracle_port, name)
+
+
+@pytest.mark.parametrize("name", [f"{k}_frame_{fr}" for k in "FH" for fr in R.MEMBER_FRAMES] + ["F_rankdef", "H_rankdef"])
+def test_fit_carries_the_oracles_bits_in_other_frames_and_on_rank_deficient_sets(torch, oracle_port, name):
+    """the same demand with coordinates x 37 + 5000 / x 37 - 9000, centred x 1e-3 and x 1e4 (px_th and the start model in the frame) at
+    the switch counts, 64 and 257; and on member sets that do not determine the model (3 distinct rows in 9, 6 in 20), where the
+    eigenvector taken among the (near-)zero eigenvalues is the eigen-solver's order, which DESIGN.md section 4 says is the restatement's"""
+    _bits(torch, oracle_port, name)
+
+
+def _entry_bytes(sc, got, p):
+    b, e = int(sc["off"][p]), int(sc["off"][p + 1])
+    return tuple(x.tobytes() for x in (got["models"][p], got["user"][p], got["info"][p], got["inlier"][b:e], got["resid"][b:e]))
+
+
+@pytest.mark.parametrize("name", ["F_members_0", "H_members_0"])
+def test_fit_does_not_depend_on_what_the_workgroup_fitted_before(torch, oracle_port, name):
+    """LDS that survives an entry (rf_shared.lsq, cand, prep, the popcount words): the entries of the store (a) one workgroup each,
+    (b) REFIT_GRID - 1 empty entries between two of them, so that workgroup 0 takes them all one after the other, small fits after big
+    ones, (c) the same in reversed order, so that every fit has another predecessor, (d) each alone in a call of its own.  models,
+    models_user, info and the entry's slices of inlier and resid must be the same bytes in all four."""
+    entries = R.member_entries(oracle_port, name); E = len(entries)
+    sc = R.gpu_scenes(oracle_port)[name]
+    got, _ = _call(torch, sc, 1)
+    want = [_entry_bytes(sc, got, p) for p in range(E)]
+    for order in (list(range(E)), list(range(E))[::-1]):
+        st = R.concat_scenes(entries, order, stride=_lib.REFIT_GRID)
+        assert len(st["off"]) - 1 == (E - 1) * _lib.REFIT_GRID + 1
+        g, _ = _call(torch, st, 1)
+        for k, q in enumerate(order):
+            assert _entry_bytes(st, g, k * _lib.REFIT_GRID) == want[q], (order[0], q, sc["m"][q])
+        empty = np.ones(len(st["m"]), bool); empty[::_lib.REFIT_GRID] = False
+        assert (g["info"][empty] == [0, 0, 0, R.SHORT]).all()
+    for q, one in enumerate(entries):
+        g, _ = _call(torch, one, 1)
+        assert _entry_bytes(one, g, 0) == want[q], ("alone", q, sc["m"][q])
 
 
 def test_grid_takes_a_second_step():

@@ -2,7 +2,8 @@
 matcher.refit_correspondences, tensor_api.refit_correspondences_tensors): every refusal of both C entry points with its message (each comes
 back as EINVAL, not ENODEV, on a machine without a device: it came before a device was looked for), K == 0, the Python keyword and shape
 checks, the restatement tests/refit_ref.py on small lists whose outcome can be told in advance, three broken restatements that these lists
-reject, and the margin that every scene of test_gpu_refit.py must have."""
+reject, the margin that every scene of test_gpu_refit.py must have, and the scenes fixed by member count (refit_ref.MEMBER_STORES): their
+outcome, the oracle's fit against a plain numpy least-squares solution, and the teeth of a comparison of bytes."""
 import ctypes as C
 
 import numpy as np
@@ -190,6 +191,107 @@ def test_broken_restatements_are_rejected(oracle_port):
     assert not np.array_equal(good["info"], small["info"]) and (small["info"][:, 3] != R.WORSE).all()
     allrows = _one(oracle_port, sc, broken="allrows")
     assert not np.array_equal(good["inlier"], allrows["inlier"]) and allrows["info"][:, 1].sum() < good["info"][:, 1].sum()
+
+
+# ---- the scenes fixed by member count: the unit entry of the non-minimal fits ----
+def _entries(oracle_port, name):
+    """(scene, p, m, where, rows of the entry) of every entry of a member store"""
+    sc = R.gpu_scenes(oracle_port)[name]
+    return [(sc, p, sc["m"][p], sc["where"][p], sc["pts"][sc["off"][p]:sc["off"][p + 1]]) for p in range(len(sc["m"]))]
+
+
+def test_member_stores_hold_the_counts_the_solvers_switch_at(oracle_port):
+    """the catalogue of the member stores: every count of both sides of 16 | 17 (F) and 12 | 13 (H), of the 8-term unroll, the wave, the
+    stride of 256 threads and 512, and members that are never a contiguous range of rows"""
+    S = R.gpu_scenes(oracle_port)
+    assert S["F_members_0"]["m"] == list(R.F_COUNTS) + [24] * 3 and S["H_members_0"]["m"] == list(R.H_COUNTS) + [13] * 3
+    assert R.F_COUNTS == (8, 9, 15, 16, 17, 18, 23, 24, 25, 63, 64, 65, 255, 256, 257, 511, 512, 513)
+    assert R.H_COUNTS == (4, 5, 11, 12, 13, 14, 19, 20, 21, 63, 64, 65, 255, 256, 257, 513)
+    assert S["F_members_1"]["m"] == [16, 17] and all(S[f"H_members_{et}"]["m"] == [12, 13] for et in (1, 2, 3, 4))
+    for fr in R.MEMBER_FRAMES:
+        assert S[f"F_frame_{fr}"]["m"] == [16, 17, 64, 257] and S[f"H_frame_{fr}"]["m"] == [12, 13, 64, 257]
+    assert S["F_rankdef"]["m"] == [9, 20] == S["H_rankdef"]["m"]
+    for name in R.MEMBER_STORES:
+        for sc, p, m, where, rows in _entries(oracle_port, name):
+            assert len(where) == m and (np.diff(where) > 0).all() and where[-1] - where[0] >= m           # sorted, not one range
+    late, edges, wave = S["F_members_0"]["where"][-3:]
+    assert late.min() >= 1024 and {0, 1023, 1024, 1099} <= set(edges.tolist()) and wave.min() >= 640 and wave.max() < 700
+    late, edges, wave = S["H_members_0"]["where"][-3:]
+    assert late.min() >= 1024 and {0, 1023, 1024, 1099} <= set(edges.tolist()) and wave.min() >= 640 and wave.max() < 700
+    for k in "FH":                                                     # rank-deficient: 3 distinct rows in 9, 6 in 20
+        for (sc, p, m, where, rows), d in zip(_entries(oracle_port, f"{k}_rankdef"), (3, 6)):
+            assert len(np.unique(rows[where], axis=0)) == d
+
+
+@pytest.mark.parametrize("name", list(R.MEMBER_STORES))
+def test_member_scene_is_a_fixed_point_after_one_fit(oracle_port, name):
+    """at max_fits = 1 every member scene gives info == [m, m, 1, FIXED] and its inlier rows are exactly `where`: the members of the
+    start model are known in advance, the one fit runs on exactly them, and its model is the output.  That holds for the two
+    rank-deficient F sets and the repeated H sets too, at the seeds refit_ref._PICKED names.  The one exception is H on 4 rows: the
+    reference's u2h at len == 4 (Htools.c:106-114, restated in oracle/dg_oracle.c u2h) transposes its 9 x 8 system as if it were 9 x 9
+    and zeroes the last row, so its null vector is (0, ..., 0, 1) for ANY four rows, noise-free ones included; under that model no
+    row is a member, the entry ends WORSE with the start model kept, and the 4-row fit shows in info and the mask only."""
+    sc = R.gpu_scenes(oracle_port)[name]
+    ref = R.reference(oracle_port, name, 1)
+    for _, p, m, where, rows in _entries(oracle_port, name):
+        b = sc["off"][p]
+        if sc["model"] == "H" and m == 4:
+            assert ref["info"][p].tolist() == [4, 4, 1, R.WORSE] and np.array_equal(ref["models"][p], sc["models"][p])
+            assert R.fit(oracle_port, "H", rows, where).tolist() == [0.0] * 8 + [1.0]
+        else:
+            assert ref["info"][p].tolist() == [m, m, 1, R.FIXED], (p, m, ref["info"][p])
+            assert ref["models"][p].tobytes() == R.fit(oracle_port, sc["model"], rows, where).tobytes()
+        assert np.array_equal(np.flatnonzero(ref["inlier"][b:b + len(rows)]), where)
+    assert np.array_equal(R.reference(oracle_port, name, 4)["info"], ref["info"])          # a fixed point stays one
+
+
+K_F, K_H = 360.0, 2.9
+
+
+def test_oracle_fit_is_the_plain_least_squares_model(oracle_port):
+    """The oracle's u2f / u2h (R.fit) on every member set against R.plain_fit, an independent float64 numpy solution (Hartley
+    normalisation, design matrix, np.linalg.svd, rank 2 by a second SVD, denormalisation), as sign-aligned relative Frobenius distance of
+    the unit-norm models.  Oracle against numpy only: the device is never the yardstick.  The bound is k eps |N|_2 / (l8 - l9) of the
+    9 x 9 normal matrix N of the design matrix the solver works on (normalised; raw for F on 8 rows): the first-order change of the
+    eigenvector under a relative perturbation eps of N, and the oracle forms N.  Measured worst distance / (eps |N| / gap) over all scenes:
+    F 45.0 (511 members; 40.1 at 256, 37.1 at 24 in the second step; the rank-2 step and the denormalisation to pixels are not in the
+    first-order term), H 0.351 (257 members, normalised frame; 0.304 in the pixel frame); k is 8 x that, per model kind: 360 and 2.9.
+    Left out: the rank-deficient scenes (the gap is 0 and the model is not determined) and H on 4 rows (the reference's 4-row u2h
+    returns (0, ..., 0, 1), see test_member_scene_is_a_fixed_point_after_one_fit, which is no least-squares model)."""
+    worst = {"F": 0.0, "H": 0.0}
+    for name in R.MEMBER_STORES:
+        if "rankdef" in name:
+            continue
+        for sc, p, m, where, rows in _entries(oracle_port, name):
+            if sc["model"] == "H" and m == 4:
+                continue
+            N, Z = R.plain_fit(sc["model"], rows[where])
+            d = R.aligned_rel_fro(R.fit(oracle_port, sc["model"], rows, where), N); gb = R.gap_bound(Z)
+            worst[sc["model"]] = max(worst[sc["model"]], d / gb)
+            assert d <= (K_F if sc["model"] == "F" else K_H) * gb, (name, p, m, d, gb, d / gb)
+    print("worst distance / (eps |N| / gap):", worst)
+
+
+def test_plain_fit_finds_a_planted_model():
+    """the numpy reference itself: noise-free rows of a known F / H give that model back to 1e-9 (its own conventions are the drivers')"""
+    for model in "FH":
+        rows, _, gt = R._rows(model, 40, 5, ratio=1.0, sigma=0.0)
+        assert R.aligned_rel_fro(R.plain_fit(model, rows)[0], gt) <= 1e-9, model
+
+
+@pytest.mark.parametrize("name", ["F_members_0", "H_members_0"])
+def test_a_wrong_order_or_a_missing_member_changes_the_bits(oracle_port, name):
+    """teeth of the bit-level comparison: for every count of every solver variant (F 8, 9 .. 16, 17 .. 513; H 4, 5 .. 12, 13 .. 513) the
+    oracle's fit on the members in reversed list order, and on the members without the last one, differs from the proper fit in at
+    least one bit: a wrong summation order or an off-by-one gather cannot pass a comparison of bytes"""
+    seen = {}
+    for sc, p, m, where, rows in _entries(oracle_port, name):
+        M = R.fit(oracle_port, sc["model"], rows, where)
+        assert R.fit(oracle_port, sc["model"], rows, where[::-1]).tobytes() != M.tobytes(), (m, "reversed")
+        assert R.fit(oracle_port, sc["model"], rows, where[:-1]).tobytes() != M.tobytes(), (m, "without the last")
+        small = m <= (16 if sc["model"] == "F" else 12)
+        seen[small] = seen.get(small, 0) + 1
+    assert seen[True] >= 3 and seen[False] >= 3
 
 
 def test_every_gpu_scene_keeps_its_margin(oracle_port):
