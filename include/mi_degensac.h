@@ -930,6 +930,81 @@ int mi_degensac_refit_lists(const double *pts, const int64_t *corr_offsets, cons
 /* the tile constants: which = 0 rows per workgroup and step of a scoring pass, 1 the cap on the grid (-1 for any other value) */
 int mi_degensac_refit_tile(int which);
 
+/* ---- relative pose and triangulation on exported correspondence lists --------------------------------------------------------------
+ * What a structure-from-motion front end stores per pair besides F: the relative pose (R, t) under known intrinsics, which of the
+ * exported matches triangulate in front of both cameras, and how much parallax they have.  Per list entry, on the device and without a
+ * host synchronisation: the row ranges are read from device memory, so the host never learns a length.
+ * Inputs per entry p (all device arrays on one device):
+ *   its rows     d_pts[o[p] .. o[p + 1]) of d_pts [cap, 4] float64 = x1, y1, x2, y2, with o = d_corr_offsets [K + 1] int64
+ *   d_keep       (nullable) [cap] uint8: only rows with keep != 0 are USED; the refit's d_inlier goes in as it is.  NULL: every row.
+ *   F[p]         d_F[9 p ..], row-major, x2^T F x1 = 0 as everywhere in this library (any scale)
+ *   cameras      two pinhole cameras (fx, fy, cx, cy): rows i1, i2 of d_cams [n_cams, 4] float64 with (i1, i2) = d_cam_idx[2 p], [2 p + 1]
+ *                (int32 [K, 2]); d_cam_idx NULL: i1 = 2 p, i2 = 2 p + 1.  Camera 1 belongs to x1, y1.
+ * Every step below is ONE IEEE float64 operation per written operator, no contraction; a sum of three terms is (first + second) + third.
+ * Per entry (statuses in their order of precedence):
+ *   range        not 0 <= o[p] <= o[p + 1] <= cap (a truncated export, a decreasing pair): MI_DEGENSAC_POSE_TRUNCATED
+ *   cameras      i1 or i2 outside [0, n_cams), or an fx / fy that is zero or not finite: MI_DEGENSAC_POSE_BAD_CAMERA
+ *   E = K2^T F K1  G = F K1: G[i][0] = F[i][0] fx1, G[i][1] = F[i][1] fy1, G[i][2] = (F[i][0] cx1 + F[i][1] cy1) + F[i][2];
+ *                then E[0][j] = fx2 G[0][j], E[1][j] = fy2 G[1][j], E[2][j] = (cx2 G[0][j] + cy2 G[1][j]) + G[2][j]
+ *                m = the largest |E[i][j]|; an entry that is not finite, or m == 0: MI_DEGENSAC_POSE_BAD_MODEL.  A = E / m.
+ *   V, sigma     the singular value decomposition of A by one-sided Jacobi rotations: V = I, B = A (b_i = column i of A), then six sweeps
+ *                over the column pairs (i j) = (0 1) (0 2) (1 2), a dot product being (first + second) + third:
+ *                al = b_i . b_i, be = b_j . b_j, ga = b_i . b_j; if ga != 0: z = (be - al) / (2 ga), t = sign(z) / (|z| + sqrt(1 + z z))
+ *                (sign(0) = 1), c = 1 / sqrt(1 + t t), s = c t; (b_i, b_j) <- (c b_i - s b_j, s b_i + c b_j), (v_i, v_j) likewise.
+ *                V stays orthogonal to rounding for every A and B = A V throughout; four sweeps converge to 1e-15 on general, rank-2 and
+ *                (near-)essential matrices, six are run.  (The reference's 3 x 3 routine of the DEGENSAC branch, dg_svd3_right, is not
+ *                used here: the pose needs all of V orthogonal and the singular values, which it does not return on every input.)
+ *                sigma_i = sqrt(b_i . b_i); sorted by sigma descending with ties keeping the lower column in front: v1, v2, v3, b1, b2 and
+ *                sigma1 >= sigma2 >= sigma3.  sigma2 not > 0: BAD_MODEL.
+ *   U            u_i = b_i / sigma_i for i = 1, 2;
+ *                u3 = u1 x u2 (each component a difference of two products, (1 2 - 2 1), (2 0 - 0 2), (0 1 - 1 0));
+ *                t = u3 / sqrt((u3[0]^2 + u3[1]^2) + u3[2]^2)
+ *   R            U W V^T and U W^T V^T with W = [0 -1 0; 1 0 0; 0 0 1] and t as the third column of U:
+ *                Ra[r][c] = (u2[r] v1[c] - u1[r] v2[c]) + t[r] v3[c],  Rb[r][c] = (u1[r] v2[c] - u2[r] v1[c]) + t[r] v3[c];
+ *                each is negated when its determinant (R00 (R11 R22 - R12 R21) - R01 (R10 R22 - R12 R20)) + R02 (R10 R21 - R11 R20) is < 0
+ *   candidates   in this order 0: (Ra, t), 1: (Ra, -t), 2: (Rb, t), 3: (Rb, -t); the meaning is X2 = R X1 + t, |t| = 1.
+ *                A candidate with a number that is not finite: BAD_MODEL.
+ *   c2           the centre of camera 2 in the frame of camera 1, per candidate: c2[j] = -((R[0][j] t[0] + R[1][j] t[1]) + R[2][j] t[2])
+ * Per used row and candidate:
+ *   rays         d1 = ((x1 - cx1) / fx1, (y1 - cy1) / fy1, 1), d2 likewise with camera 2; r2 = R^T d2: r2[j] = (R[0][j] d2[0] + R[1][j] d2[1]) + R[2][j]
+ *   midpoint     a = (d1[0]^2 + d1[1]^2) + 1, b = (d1[0] r2[0] + d1[1] r2[1]) + r2[2], c = (r2[0]^2 + r2[1]^2) + r2[2]^2,
+ *                d = (d1[0] c2[0] + d1[1] c2[1]) + c2[2], e = (r2[0] c2[0] + r2[1] c2[1]) + r2[2] c2[2], den = a c - b b,
+ *                lambda1 = (c d - b e) / den, lambda2 = (b d - a e) / den  (the depths along d1 and r2: the closest points of the two rays),
+ *                X[j] = 0.5 ((lambda1 d1[j] + c2[j]) + lambda2 r2[j]) in the frame of camera 1 (j = 2: lambda1 itself for lambda1 d1[2])
+ *   front        lambda1 > 0 and lambda2 > 0; a NaN is not front (den == 0 is not treated apart: it gives what IEEE division gives)
+ *   cosang       b / sqrt(a c), the cosine of the angle between the two rays; a front row is WIDE iff cosang <= cos_min
+ * The chosen pose is the candidate with the most front rows among the used rows; ties go to the first in the order above.  No used row:
+ * MI_DEGENSAC_POSE_EMPTY.  With a status other than OK the pose is twelve zeros, the info row is (0, 0, 0, 0, status) and no row of
+ * the entry is written.  Ranges must not overlap.
+ * Outputs:
+ *   d_pose [K, 12]          R row-major, then t, of the chosen candidate
+ *   d_front [cap] uint8     1 for the used rows that are front under the chosen candidate; every other position keeps 0
+ *   d_info [K, 5] int32     rows used, front rows of the chosen candidate, the largest front count of the other three, wide rows, status
+ *   d_X [cap, 3], d_depth [cap, 2] = lambda1, lambda2, d_cosang [cap]   (each nullable) of the used rows under the chosen candidate;
+ *                           positions that no entry owns, rows that are not used and rows of entries without a pose keep NaN
+ *   d_cand [K, 4, 12], d_cand_front [K, 4] int32   (each nullable) all four candidates (zeros for TRUNCATED, BAD_CAMERA, BAD_MODEL) and
+ *                           their front counts (zeros unless OK)
+ * One workgroup per entry, no atomics, counts by wave ballots and integer adds: the same bits on every call.  Asynchronous on `stream`;
+ * the call needs no temporaries.  d_corr_offsets and d_cam_idx are device data and are checked on the device, not on the host.
+ * Refused with MI_DEGENSAC_EINVAL and a message in mi_degensac_match_last_error(), before a device is looked for and in this order:
+ * n_entries < 0; cap < 0 or > 0x3fffffff; n_cams < 0; a cos_min that is NaN or outside [-1, 1]; NULL d_corr_offsets; for n_entries > 0
+ * NULL d_F or d_cams, then NULL d_pose or d_info; for cap > 0 NULL d_pts or d_front.  n_entries == 0 and cap == 0 succeed (with
+ * n_entries == 0 the fills are all that is written). */
+enum { MI_DEGENSAC_POSE_OK = 0, MI_DEGENSAC_POSE_BAD_MODEL = 1, MI_DEGENSAC_POSE_BAD_CAMERA = 2, MI_DEGENSAC_POSE_TRUNCATED = 3,
+       MI_DEGENSAC_POSE_EMPTY = 4 };
+int mi_degensac_pose_lists_dev(const double *d_pts, const int64_t *d_corr_offsets, const uint8_t *d_keep /*nullable*/, const double *d_F,
+                               const double *d_cams, int n_cams, const int32_t *d_cam_idx /*nullable*/, int n_entries, int64_t cap,
+                               double cos_min, int device, void *stream, double *d_pose, uint8_t *d_front, int32_t *d_info,
+                               double *d_X /*nullable*/, double *d_depth /*nullable*/, double *d_cosang /*nullable*/,
+                               double *d_cand /*nullable*/, int32_t *d_cand_front /*nullable*/);
+/* the same on host pointers (blocking): the inputs go to the device once, every output that is asked for comes back whole */
+int mi_degensac_pose_lists(const double *pts, const int64_t *corr_offsets, const uint8_t *keep /*nullable*/, const double *F,
+                           const double *cams, int n_cams, const int32_t *cam_idx /*nullable*/, int n_entries, int64_t cap, double cos_min,
+                           int device, double *pose, uint8_t *front, int32_t *info, double *X /*nullable*/, double *depth /*nullable*/,
+                           double *cosang /*nullable*/, double *cand /*nullable*/, int32_t *cand_front /*nullable*/);
+/* the tile constants: which = 0 rows per workgroup and step of a row pass, 1 the cap on the grid (-1 for any other value) */
+int mi_degensac_pose_tile(int which);
+
 /* ---- unit-level device entry points (parity tests of the kernels' building blocks) ------------ */
 /* score n_models fundamental (kind 0: Sampson, 1: symmetric epipolar) or homography (kind 10..14:
  * H Sampson, symm_sq_max, symm_max, symm_sq_sum, symm_sum) models against all n points: I (<= th)

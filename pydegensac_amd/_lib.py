@@ -42,6 +42,10 @@ TRACK_ROWS, TRACK_SCAN = 1024, 256
 # grid; the status column of its info rows (MI_DEGENSAC_REFIT_*)
 REFIT_STEP, REFIT_GRID = 1024, 256
 REFIT_FIXED, REFIT_MAX_FITS, REFIT_SHORT, REFIT_BAD_FIT, REFIT_WORSE, REFIT_TRUNCATED = range(6)
+# the relative pose (csrc/mi_pose.hip PS_STEP / PS_GRID, mi_degensac_pose_tile): rows per workgroup and step of a row pass, the cap on the
+# grid; the status column of its info rows (MI_DEGENSAC_POSE_*)
+POSE_STEP, POSE_GRID = 1024, 256
+POSE_OK, POSE_BAD_MODEL, POSE_BAD_CAMERA, POSE_TRUNCATED, POSE_EMPTY = range(5)
 
 
 class Params(C.Structure):
@@ -340,6 +344,17 @@ def lib():
             l.mi_degensac_refit_lists.argtypes = [vp, vp, vp, C.c_int, C.c_int64, gpp, C.c_int, C.c_int] + [vp] * 5
             l.mi_degensac_refit_tile.restype = C.c_int
             l.mi_degensac_refit_tile.argtypes = [C.c_int]
+        if hasattr(l, "mi_degensac_pose_lists_dev"):                      # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            # pts, corr_offsets, keep, F, cams, n_cams, cam_idx, K, cap, cos_min, device[, stream] | pose, front, info, X, depth, cosang, cand,
+            # cand_front
+            vp = C.c_void_p
+            head = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int64, C.c_double, C.c_int]
+            l.mi_degensac_pose_lists_dev.restype = C.c_int
+            l.mi_degensac_pose_lists_dev.argtypes = head + [vp] + [vp] * 8
+            l.mi_degensac_pose_lists.restype = C.c_int
+            l.mi_degensac_pose_lists.argtypes = head + [vp] * 8
+            l.mi_degensac_pose_tile.restype = C.c_int
+            l.mi_degensac_pose_tile.argtypes = [C.c_int]
         l.mi_degensac_kpts_to_xyA.restype = C.c_int
         l.mi_degensac_kpts_to_xyA.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, dp]
         l.mi_degensac_kpts_to_xyA_dev.restype = C.c_int

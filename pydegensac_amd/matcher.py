@@ -1110,3 +1110,112 @@ def refit_correspondences(pts, corr_offsets, models, model="F", px_th=None, erro
     _lib.check_match(rc)
     res = ((out if (model == "F" or driver_form) else user).reshape(K, 3, 3), inl.astype(bool), info)
     return res + (resid,) if with_resid else res
+
+
+def check_pose_args(pts_shape, pts_dtype, off_shape, off_dtype, models_shape, models_dtype, cams1_shape, cams1_dtype, pairs=None, cams2=None, keep=None,
+                    min_parallax_deg=1.5):
+    """The argument checks of relative_pose / relative_pose_tensors on shapes and dtype names (numpy or torch): pts float64 [cap, 4],
+    corr_offsets int64 [K + 1], models float64 [K, 3, 3] (F); pairs, cams2 and keep are None or (shape, dtype): without pairs cams1 is
+    float64 [K, 8] (one row of two cameras fx, fy, cx, cy per entry) and cams2 must be None; with pairs int32 / int64 [K, 2] cams1 is
+    float64 [n_images, 4] and cams2 None (= cams1) or float64 [n_images_2, 4]; keep bool / uint8 [cap]; min_parallax_deg a number in
+    [0, 180].  Returns (K, cap, rows of cams1, rows of cams2 or None, cos_min); raises ValueError."""
+    if len(off_shape) != 1 or off_shape[0] < 1 or _dtype_name(off_dtype) != "int64":
+        raise ValueError("corr_offsets should be int64 [K + 1], as the correspondence export returns it")
+    K = int(off_shape[0]) - 1
+    if tuple(models_shape) != (K, 3, 3) or _dtype_name(models_dtype) != "float64":
+        raise ValueError("models should be float64 [K, 3, 3], one fundamental matrix per entry of corr_offsets")
+    if len(pts_shape) != 2 or pts_shape[1] != 4 or _dtype_name(pts_dtype) != "float64":
+        raise ValueError("pts should be float64 [cap, 4] = x1, y1, x2, y2, as the correspondence export returns it")
+    if pts_shape[0] > 0x3fffffff:
+        raise ValueError("too many rows in one list")
+    cap = int(pts_shape[0])
+    if _dtype_name(cams1_dtype) != "float64":
+        raise ValueError("cams1 should be float64")
+    n2 = None
+    if pairs is None:
+        if tuple(cams1_shape) != (K, 8):
+            raise ValueError("cams1 should be float64 [K, 8] = fx, fy, cx, cy of camera 1 and of camera 2 per entry (or give pairs)")
+        if cams2 is not None:
+            raise ValueError("cams2 names a second store: give pairs too")
+    else:
+        if tuple(pairs[0]) != (K, 2) or _dtype_name(pairs[1]) not in ("int32", "int64"):
+            raise ValueError("pairs should be an integer array [K, 2] of (image of store 1, image of store 2)")
+        if len(cams1_shape) != 2 or cams1_shape[1] != 4:
+            raise ValueError("cams1 should be float64 [n_images, 4] = fx, fy, cx, cy per image of store 1")
+        if cams2 is not None:
+            if len(cams2[0]) != 2 or cams2[0][1] != 4 or _dtype_name(cams2[1]) != "float64":
+                raise ValueError("cams2 should be float64 [n_images, 4] = fx, fy, cx, cy per image of store 2")
+            n2 = int(cams2[0][0])
+        if int(cams1_shape[0]) + (n2 or 0) > 0x7fffffff:
+            raise ValueError("too many cameras")
+    if keep is not None and (tuple(keep[0]) != (cap,) or _dtype_name(keep[1]) not in ("bool", "uint8")):
+        raise ValueError("keep should be bool or uint8 [cap], one flag per row of pts")
+    if isinstance(min_parallax_deg, bool) or not isinstance(min_parallax_deg, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(min_parallax_deg) <= 180.0:
+        raise ValueError("min_parallax_deg should be a number in [0, 180]")
+    return K, cap, int(cams1_shape[0]), n2, float(np.cos(np.deg2rad(float(min_parallax_deg))))
+
+
+def relative_pose(pts, corr_offsets, models, cams1, pairs=None, cams2=None, keep=None, min_parallax_deg=1.5, with_points=False, with_candidates=False,
+                  device=0):
+    """Relative pose and triangulation on exported correspondence lists (include/mi_degensac.h mi_degensac_pose_lists, blocking, numpy):
+    per entry p the essential matrix of models[p] (F, x2^T F x1 = 0) under the entry's two pinhole cameras, its four (R, t) candidates
+    (X2 = R X1 + t, |t| = 1), and the one under which most used rows pts[corr_offsets[p] : corr_offsets[p + 1]] triangulate in front of
+    both cameras (closed-form midpoint of the two rays).  cams1 [K, 8] = fx, fy, cx, cy of both cameras per entry; or, with pairs [K, 2],
+    cams1 [n_images, 4] per image of store 1 and cams2 likewise for store 2 (None = cams1).  keep [cap]: only rows with keep != 0 are
+    used (the refit's `inlier` as it is).  A front row is wide when the angle between its two rays is at least min_parallax_deg.
+    Returns (R [K, 3, 3], t [K, 3], front [cap] bool, info [K, 5] int32 = (rows used, front rows of the chosen candidate, the largest
+    front count of the other three, wide rows, _lib.POSE_* status)[, X [cap, 3] in the frame of camera 1, depth [cap, 2], cosang [cap]]
+    [, cand [K, 4, 12], cand_front [K, 4]])."""
+    P = np.ascontiguousarray(np.asarray(pts)); o = np.ascontiguousarray(np.asarray(corr_offsets)); M = np.asarray(models)
+    c1 = np.asarray(cams1); c2 = None if cams2 is None else np.asarray(cams2)
+    pr = None if pairs is None else np.asarray(pairs)
+    kp = None if keep is None else np.asarray(keep)
+    sd = lambda x: None if x is None else (x.shape, x.dtype)          # noqa: E731
+    K, cap, n1, n2, cos_min = check_pose_args(P.shape, P.dtype, o.shape, o.dtype, M.shape, M.dtype, c1.shape, c1.dtype, sd(pr), sd(c2), sd(kp),
+                                              min_parallax_deg)
+    F = np.ascontiguousarray(M, np.float64).reshape(K, 9)
+    idx = None
+    if pr is None:
+        cams = np.ascontiguousarray(c1).reshape(2 * K, 4)
+    else:
+        cams = np.ascontiguousarray(c1 if c2 is None else np.concatenate([c1, c2]))
+        wide = pr.astype(np.int64) + np.array([0, 0 if c2 is None else n1], np.int64)
+        if c2 is not None:                                            # an image of store 1 must not reach into store 2's rows
+            wide[(pr[:, 0] < 0) | (pr[:, 0] >= n1), 0] = -1
+            wide[pr[:, 1] < 0, 1] = -1
+        idx = np.ascontiguousarray(np.clip(wide, -1, 0x7fffffff).astype(np.int32))
+    if kp is not None:
+        kp = np.ascontiguousarray(kp).view(np.uint8)
+    pose = np.zeros((K, 12)); front = np.zeros(cap, np.uint8); info = np.zeros((K, 5), np.int32)
+    X = np.full((cap, 3), np.nan) if with_points else None
+    depth = np.full((cap, 2), np.nan) if with_points else None
+    cosang = np.full(cap, np.nan) if with_points else None
+    cand = np.zeros((K, 4, 12)) if with_candidates else None
+    cf = np.zeros((K, 4), np.int32) if with_candidates else None
+    vp = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)          # noqa: E731
+    rc = _lib.lib().mi_degensac_pose_lists(vp(P), vp(o), vp(kp), vp(F), vp(cams), len(cams), vp(idx), K, cap, cos_min, int(device), vp(pose),
+                                           vp(front), vp(info), vp(X), vp(depth), vp(cosang), vp(cand), vp(cf))
+    _lib.check_match(rc)
+    res = (pose[:, :9].reshape(K, 3, 3), pose[:, 9:], front.astype(bool), info)
+    if with_points:
+        res += (X, depth, cosang)
+    return res + (cand, cf) if with_candidates else res
+
+
+def pose_config(info, min_front_ratio=0.5, min_wide_ratio=0.0):
+    """What the info rows [K, 5] of relative_pose / relative_pose_tensors (numpy, or a tensor, which is copied to the host) say about a
+    pair that two_view_config put into class 2, "planar or panoramic": int8 [K] with 2 = panoramic (wide <= min_wide_ratio * front,
+    compared in float64: no row, or too few, with parallax, so the pose's baseline is not supported), 1 = planar with a supported pose
+    (not panoramic, and front >= min_front_ratio * used), 0 = undecided (a status other than _lib.POSE_OK, or front < min_front_ratio *
+    used).  COLMAP tells the two apart after its pose decomposition by the triangulation angles; the thresholds are the caller's business
+    (the defaults: any wide row is parallax, half of the used rows in front), and so is what to do with each class."""
+    s = info.detach().cpu().numpy() if hasattr(info, "detach") else np.asarray(info)
+    if s.ndim != 2 or s.shape[1] != 5 or (s.size and not np.issubdtype(s.dtype, np.integer)):
+        raise ValueError("info should be an integer array [K, 5] = (used, front, runner-up, wide, status)")
+    used = s[:, 0].astype(np.float64); front = s[:, 1].astype(np.float64); wide = s[:, 3].astype(np.float64)
+    out = np.ones(s.shape[0], np.int8)
+    out[front < float(min_front_ratio) * used] = 0
+    out[wide <= float(min_wide_ratio) * front] = 2
+    out[s[:, 4] != _lib.POSE_OK] = 0
+    return out

@@ -136,6 +136,20 @@ def ellipse_pairs(n=1000, inlier_ratio=0.3, sigma=1.0, seed=0, laf_noise=0.05, H
     return np.ascontiguousarray(u[perm]), lab[perm]
 
 
+def collection_cameras(m=8):
+    """The cameras image_collection(m, ...) projects with: (K [3, 3], [(R_i [3, 3], t_i [3])] for i < m), x_i ~ K (R_i X + t_i).  Every image
+    has the same pinhole intrinsics fx = fy = FOCAL, cx = IMG_W / 2, cy = IMG_H / 2.  The relative pose of the pair (i, j), X_j = R X_i + t,
+    is R = R_j R_i^T, t = t_j - R t_i."""
+    K = np.array([[FOCAL, 0, IMG_W / 2], [0, FOCAL, IMG_H / 2], [0, 0, 1.0]])
+    poses = []
+    for i in range(m):
+        a = 0.5 * (i / max(m - 1, 1) - 0.5)
+        R = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
+        t = np.array([-6.0 * np.sin(a), 0.05 * i / max(m, 1), 6.0 * (1 - np.cos(a))])
+        poses.append((R, t))
+    return K, poses
+
+
 def image_collection(m=8, n=500, inlier_ratio=0.5, sigma=0.1, dim=64, seed=0, desc_sigma=0.15):
     """An image collection for the pair-list calls: m pinhole views on an arc around one random 3-D cloud, n keypoints each.  In
     every image a share inlier_ratio of the keypoints are projections of cloud points (a different random subset per image, noise

@@ -943,3 +943,68 @@ def refit_correspondences_tensors(pts, corr_offsets, models, model="F", px_th=No
         t.record_stream(stream)
     res = ((out if user is None else user).view(K, 3, 3), inl[:cap].view(torch.bool), info)
     return res + (resid[:cap],) if with_resid else res
+
+
+def relative_pose_tensors(pts, corr_offsets, models, cams1, pairs=None, cams2=None, keep=None, min_parallax_deg=1.5, with_points=False,
+                          with_candidates=False):
+    """Relative pose and triangulation on exported correspondence lists, on the device and without a host synchronisation
+    (include/mi_degensac.h mi_degensac_pose_lists_dev): what a structure-from-motion front end stores per pair besides F.  pts [cap, 4]
+    float64 and corr_offsets [K + 1] int64 are what correspondences_pairs_tensors / _batch_tensors returned (kps1 / kps2 given), models
+    [K, 3, 3] float64 the fundamental matrices of a verify call or of the refit (x2^T F x1 = 0).  Cameras are pinhole (fx, fy, cx, cy),
+    float64: with pairs=None cams1 is [K, 8], the two cameras of every entry; with pairs [K, 2] (the pair list, int32 or int64) cams1 is
+    [n_images, 4] per image of store 1 and cams2 likewise for store 2 (None = cams1).  keep [cap] bool / uint8: only rows with keep != 0
+    are used, so the refit's `inlier` goes in as it is.  Per entry: E = K2^T F K1, its four (R, t) candidates (X2 = R X1 + t, |t| = 1),
+    and the candidate under which most used rows lie in front of both cameras (closed-form midpoint of the two rays; ties go to the first
+    candidate).  A front row is wide when the angle between its rays is at least min_parallax_deg (COLMAP's minimum triangulation angle).
+    The kernel reads the entries' lengths from corr_offsets itself, so nothing is read back.
+    Returns (R [K, 3, 3], t [K, 3], front [cap] bool, info [K, 5] int32 = (rows used, front rows of the chosen candidate, the largest
+    front count of the other three, wide rows, _lib.POSE_* status)[, X [cap, 3] in the frame of camera 1, depth [cap, 2] along the two
+    rays, cosang [cap]][, cand [K, 4, 12], cand_front [K, 4]]) on the device, asynchronous on the current stream.  Rows that are not
+    used, and rows of an entry without a pose (status != POSE_OK: R and t are zeros), keep front = False and NaN."""
+    import torch
+    from . import matcher
+    opt = [t for t in (pairs, cams2, keep) if t is not None]
+    ts = [pts, corr_offsets, models, cams1] + opt
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        raise ValueError("pts, corr_offsets, models, cams1 (and pairs, cams2, keep) must be torch tensors on a ROCm device")
+    sd = lambda t: None if t is None else (tuple(t.shape), t.dtype)          # noqa: E731
+    K, cap, n1, n2, cos_min = matcher.check_pose_args(tuple(pts.shape), pts.dtype, tuple(corr_offsets.shape), corr_offsets.dtype, tuple(models.shape),
+                                                      models.dtype, tuple(cams1.shape), cams1.dtype, sd(pairs), sd(cams2), sd(keep), min_parallax_deg)
+    if any(t.device != pts.device for t in ts) or pts.device.type != "cuda":
+        raise ValueError("pts, corr_offsets, models, cams1 (and pairs, cams2, keep) must live on the same ROCm device")
+    dev = pts.device
+    P = pts.contiguous(); o = corr_offsets.contiguous(); F = models.contiguous()
+    idx = None
+    if pairs is None:
+        cams = cams1.contiguous()
+        n_cams = 2 * K
+    else:
+        cams = cams1.contiguous() if cams2 is None else torch.cat([cams1, cams2])
+        n_cams = n1 + (n2 or 0)
+        wide = pairs.to(torch.int64)
+        if cams2 is not None:                                         # an image of store 1 must not reach into store 2's rows
+            a = torch.where((wide[:, 0] < 0) | (wide[:, 0] >= n1), -1, wide[:, 0])
+            b = torch.where(wide[:, 1] < 0, -1, wide[:, 1] + n1)
+            wide = torch.stack([a, b], 1)
+        idx = wide.clamp(-1, 0x7fffffff).to(torch.int32).contiguous()
+    kp = None if keep is None else keep.contiguous().view(torch.uint8)
+    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
+    rows = max(cap, 1)                                                # (an address also where cap == 0)
+    pose = f64(K, 12); front = torch.empty(rows, dtype=torch.uint8, device=dev); info = torch.empty((K, 5), dtype=torch.int32, device=dev)
+    X = f64(rows, 3) if with_points else None
+    depth = f64(rows, 2) if with_points else None
+    cosang = f64(rows) if with_points else None
+    cand = f64(K, 4, 12) if with_candidates else None
+    cf = torch.empty((K, 4), dtype=torch.int32, device=dev) if with_candidates else None
+    stream = torch.cuda.current_stream(dev)
+    p = lambda t: None if t is None else t.data_ptr()          # noqa: E731
+    rc = _lib.lib().mi_degensac_pose_lists_dev(p(P), p(o), p(kp), p(F), p(cams), n_cams, p(idx), K, cap, cos_min, dev.index or 0,
+                                               C.c_void_p(stream.cuda_stream), p(pose), p(front), p(info), p(X), p(depth), p(cosang), p(cand), p(cf))
+    _lib.check_match(rc)
+    for t in (P, o, F, cams, idx, kp):
+        if t is not None:
+            t.record_stream(stream)
+    res = (pose[:, :9].reshape(K, 3, 3), pose[:, 9:], front[:cap].view(torch.bool), info)
+    if with_points:
+        res += (X[:cap], depth[:cap], cosang[:cap])
+    return res + (cand, cf) if with_candidates else res
