@@ -1005,6 +1005,92 @@ int mi_degensac_pose_lists(const double *pts, const int64_t *corr_offsets, const
 /* the tile constants: which = 0 rows per workgroup and step of a row pass, 1 the cap on the grid (-1 for any other value) */
 int mi_degensac_pose_tile(int which);
 
+/* ---- refinement of relative poses on exported correspondence lists ---------------------------------------------------------------------
+ * The pose call takes (R, t) from E = K2^T F K1 of an uncalibrated F, which is no essential matrix, and snaps it to one without looking
+ * at the rows again.  This call follows it with what every structure-from-motion front end runs next: a Levenberg-Marquardt refinement
+ * of the five degrees of freedom of (R, t / |t|) on the Sampson distance, in pixels, of the used rows.  Per list entry, on the device and
+ * without a host synchronisation; rows, offsets, keep and cameras exactly as mi_degensac_pose_lists_dev takes them (the pose call's
+ * d_front goes in as d_keep as it is), d_pose [K, 12] = R row-major then t as that call writes it.
+ * Every step below is ONE IEEE float64 operation per written operator, no contraction; a sum of three terms is (a + b) + c, one of four
+ * ((a + b) + c) + d.  Only + - * / sqrt, comparisons and |x| occur: no sin, cos, acos or exp.
+ * Statuses, in their order of precedence:
+ *   TRUNCATED    not 0 <= o[p] <= o[p + 1] <= cap
+ *   BAD_CAMERA   i1 or i2 outside [0, n_cams), or an fx / fy that is zero or not finite (as in the pose call)
+ *   BAD_POSE     one of the twelve pose numbers is not finite, or (t[0] t[0] + t[1] t[1]) + t[2] t[2] is not > 0 (the twelve zeros of a
+ *                failed pose entry)
+ *   SHORT        fewer than 5 used rows
+ *   NOT_FINITE   the cost of the start pose is not finite
+ *   CONVERGED, STALLED, MAX_TRIALS   the three ends of a run (below)
+ * With one of the first five the pose is copied through unchanged (BAD_POSE: twelve zeros are written), both costs are NaN, no row of
+ * d_resid is written, the info row is (used, 0, 0, status) with used = 0 for the first three.
+ * Notation: cross(x, y) = (x[1] y[2] - x[2] y[1], x[2] y[0] - x[0] y[2], x[0] y[1] - x[1] y[0]); for a vector x and a matrix M,
+ * [x]x M is the matrix whose column j is cross(x, column j of M); dot(x, x) = (x[0] x[0] + x[1] x[1]) + x[2] x[2].
+ * Model at a pose (R, t) (t is used as it is given; the cost does not depend on its length):
+ *   E = [t]x R
+ *   i = the index of the smallest |t[i]|, ties to the lowest index; c = cross(e_i, t) written out: i = 0: (0, -t[2], t[1]), i = 1:
+ *   (t[2], 0, -t[0]), i = 2: (-t[1], t[0], 0); u = c / sqrt(dot(c, c)) (three divisions); v = cross(t, u)
+ *   five generators: G_0 = (0, E_2, -E_1), G_1 = (-E_2, 0, E_0), G_2 = (E_1, -E_0, 0) by columns (E_j = column j of E: G_k = E [e_k]x, the
+ *   right-hand rotation R <- R C(w)), G_3 = [u]x R, G_4 = [v]x R.  The zero columns are stored as +0.0 and take part like any number.
+ * Per used row, with d1 = ((x1 - cx1) / fx1, (y1 - cy1) / fy1, 1) and d2 likewise with camera 2, for a 3 x 3 matrix M define
+ * epi(M) = (n, a0, a1, b0, b1):
+ *   a[i] = (M[i][0] d1[0] + M[i][1] d1[1]) + M[i][2],  b[j] = (M[0][j] d2[0] + M[1][j] d2[1]) + M[2][j]   (b[2] is not needed)
+ *   n = (d2[0] a[0] + d2[1] a[1]) + a[2];  a0 = a[0] / fx2, a1 = a[1] / fy2, b0 = b[0] / fx1, b1 = b[1] / fy1
+ * With (n, a0, a1, b0, b1) = epi(E):  s = ((a0 a0 + a1 a1) + b0 b0) + b1 b1, q = sqrt(s), r = n / q: the signed Sampson distance of
+ * F = K2^-T E K1^-1 in pixels.  With (n_k, c0, c1, e0, e1) = epi(G_k), k = 0 .. 4:
+ *   h_k = ((a0 c0 + a1 c1) + b0 e0) + b1 e1,  J_k = n_k / q - (n h_k) / (s q)
+ * The 21 sums of a pass, in this order: cost = sum r r; g_k = sum J_k r (k = 0 .. 4); A_kl = sum J_k J_l for k <= l in the order 00 01 02
+ * 03 04 11 12 13 14 22 23 24 33 34 44.  Each sum: thread tau of the 256 adds the terms of the used rows i == tau (mod 256) of the entry
+ * (i counted from the entry's first row) in ascending i into an accumulator that starts as +0.0; a row that is not used adds nothing.
+ * Inside each wave of 64, for m = 32, 16, 8, 4, 2, 1: lane l < m takes v[l] + v[l + m]; lane 0 holds the wave's sum w.  The sum is
+ * ((w0 + w1) + w2) + w3 over the four waves.
+ * The run: lambda = 1e-3; one pass at the start pose gives cost, g, A (cost not finite: NOT_FINITE); the start cost is kept.  Then up to
+ * max_trials trials; before each, if max_trials trials have run the status is MAX_TRIALS.  One trial:
+ *   M[k][k] = A_kk + lambda A_kk, M[k][l] = A_lk for l < k.  Unpivoted Cholesky M = L L^T, for j = 0 .. 4: x = M[j][j], then x = x -
+ *   L[j][k] L[j][k] for k = 0 .. j - 1 in turn; x not > 0 (a NaN included): the trial is REJECTED and has no pass; L[j][j] = sqrt(x); for
+ *   i = j + 1 .. 4: x = M[i][j], x = x - L[i][k] L[j][k] for k = 0 .. j - 1 in turn, L[i][j] = x / L[j][j].
+ *   y: for i = 0 .. 4: x = -g_i, x = x - L[i][k] y[k] for k = 0 .. i - 1 in turn, y[i] = x / L[i][i].
+ *   delta: for i = 4 .. 0: x = y[i], x = x - L[k][i] delta[k] for k = i + 1 .. 4 in turn, delta[i] = x / L[i][i].
+ *   w = delta[0 .. 2], a = 0.5 w, aa = dot(a, a), p = 1 - aa, d = 1 + aa; the Cayley rotation (exact, rational):
+ *   C[i][i] = (p + w[i] a[i]) / d;  C[0][1] = (w[0] a[1] - w[2]) / d, C[0][2] = (w[0] a[2] + w[1]) / d, C[1][0] = (w[1] a[0] + w[2]) / d,
+ *   C[1][2] = (w[1] a[2] - w[0]) / d, C[2][0] = (w[2] a[0] - w[1]) / d, C[2][1] = (w[2] a[1] + w[0]) / d
+ *   R'[i][j] = (R[i][0] C[0][j] + R[i][1] C[1][j]) + R[i][2] C[2][j];  z[j] = (t[j] + delta[3] u[j]) + delta[4] v[j], t' = z /
+ *   sqrt(dot(z, z)) (three divisions)
+ *   one pass at (R', t') gives cost', g', A'.  ACCEPTED iff cost' < cost (a NaN is not), else REJECTED.
+ *   accepted: the pose and its sums become the current ones; lambda = max(lambda / 10, 1e-12); if (cost - cost') <= ftol cost with the
+ *   cost before the step, the status is CONVERGED.  rejected: lambda = 10 lambda; if lambda > 1e12 the status is STALLED.
+ * max_trials = 0 scores only (MAX_TRIALS, end cost = start cost).
+ * Outputs:
+ *   d_pose_out [K, 12]      the final pose; may be d_pose itself (an entry reads its twelve numbers before it writes them), must not
+ *                           overlap it otherwise
+ *   d_cost [K, 2]           cost at the start and at the final pose
+ *   d_info [K, 4] int32     used rows, trials run (rejected ones included), trials accepted, status
+ *   d_resid [cap]           (nullable) r of the used rows under the final pose, from one more pass; every other position keeps NaN
+ *   d_F [K, 9]              (nullable) F = K2^-T E K1^-1 of the final pose (x2^T F x1 = 0, row-major): H[i][0] = E[i][0] / fx1, H[i][1] =
+ *                           E[i][1] / fy1, H[i][2] = (E[i][2] - H[i][0] cx1) - H[i][1] cy1; F[0][j] = H[0][j] / fx2, F[1][j] = H[1][j] /
+ *                           fy2, F[2][j] = (H[2][j] - F[0][j] cx2) - F[1][j] cy2.  Nine zeros for TRUNCATED, BAD_CAMERA and BAD_POSE;
+ *                           for SHORT and NOT_FINITE the F of the pose that was copied through.
+ * One workgroup of 256 threads per entry, no atomics, a fixed order of every sum: the same bits on every call.  Asynchronous on `stream`;
+ * no temporaries.  Ranges must not overlap.
+ * Refused with MI_DEGENSAC_EINVAL and a message in mi_degensac_match_last_error(), before a device is looked for and in this order:
+ * n_entries < 0; cap < 0 or > 0x3fffffff; n_cams < 0; max_trials outside 0 .. 100; an ftol that is NaN or < 0; NULL d_corr_offsets; for
+ * n_entries > 0 NULL d_pose or d_cams, then NULL d_pose_out, d_cost or d_info; for cap > 0 NULL d_pts.  n_entries == 0 and cap == 0
+ * succeed (with n_entries == 0 the NaN fill of d_resid is all that is written). */
+enum { MI_DEGENSAC_REFINE_CONVERGED = 0, MI_DEGENSAC_REFINE_STALLED = 1, MI_DEGENSAC_REFINE_MAX_TRIALS = 2, MI_DEGENSAC_REFINE_SHORT = 3,
+       MI_DEGENSAC_REFINE_NOT_FINITE = 4, MI_DEGENSAC_REFINE_BAD_POSE = 5, MI_DEGENSAC_REFINE_BAD_CAMERA = 6,
+       MI_DEGENSAC_REFINE_TRUNCATED = 7 };
+int mi_degensac_pose_refine_lists_dev(const double *d_pts, const int64_t *d_corr_offsets, const uint8_t *d_keep /*nullable*/,
+                                      const double *d_pose, const double *d_cams, int n_cams, const int32_t *d_cam_idx /*nullable*/,
+                                      int n_entries, int64_t cap, int max_trials, double ftol, int device, void *stream,
+                                      double *d_pose_out, double *d_cost, int32_t *d_info, double *d_resid /*nullable*/,
+                                      double *d_F /*nullable*/);
+/* the same on host pointers (blocking): the inputs go to the device once, every output that is asked for comes back whole */
+int mi_degensac_pose_refine_lists(const double *pts, const int64_t *corr_offsets, const uint8_t *keep /*nullable*/, const double *pose,
+                                  const double *cams, int n_cams, const int32_t *cam_idx /*nullable*/, int n_entries, int64_t cap,
+                                  int max_trials, double ftol, int device, double *pose_out, double *cost, int32_t *info,
+                                  double *resid /*nullable*/, double *F /*nullable*/);
+/* the tile constants: which = 0 rows per workgroup and step of a row pass, 1 the cap on the grid (-1 for any other value) */
+int mi_degensac_pose_refine_tile(int which);
+
 /* ---- unit-level device entry points (parity tests of the kernels' building blocks) ------------ */
 /* score n_models fundamental (kind 0: Sampson, 1: symmetric epipolar) or homography (kind 10..14:
  * H Sampson, symm_sq_max, symm_max, symm_sq_sum, symm_sum) models against all n points: I (<= th)

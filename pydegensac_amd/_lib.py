@@ -46,6 +46,10 @@ REFIT_FIXED, REFIT_MAX_FITS, REFIT_SHORT, REFIT_BAD_FIT, REFIT_WORSE, REFIT_TRUN
 # grid; the status column of its info rows (MI_DEGENSAC_POSE_*)
 POSE_STEP, POSE_GRID = 1024, 256
 POSE_OK, POSE_BAD_MODEL, POSE_BAD_CAMERA, POSE_TRUNCATED, POSE_EMPTY = range(5)
+# the pose refinement (csrc/mi_pose_refine.hip PR_STEP / PR_GRID, mi_degensac_pose_refine_tile): rows per workgroup and step of a row pass,
+# the cap on the grid; the status column of its info rows (MI_DEGENSAC_REFINE_*)
+REFINE_STEP, REFINE_GRID = 1024, 256
+REFINE_CONVERGED, REFINE_STALLED, REFINE_MAX_TRIALS, REFINE_SHORT, REFINE_NOT_FINITE, REFINE_BAD_POSE, REFINE_BAD_CAMERA, REFINE_TRUNCATED = range(8)
 
 
 class Params(C.Structure):
@@ -355,6 +359,16 @@ def lib():
             l.mi_degensac_pose_lists.argtypes = head + [vp] * 8
             l.mi_degensac_pose_tile.restype = C.c_int
             l.mi_degensac_pose_tile.argtypes = [C.c_int]
+        if hasattr(l, "mi_degensac_pose_refine_lists_dev"):               # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            # pts, corr_offsets, keep, pose, cams, n_cams, cam_idx, K, cap, max_trials, ftol, device[, stream] | pose_out, cost, info, resid, F
+            vp = C.c_void_p
+            head = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int64, C.c_int, C.c_double, C.c_int]
+            l.mi_degensac_pose_refine_lists_dev.restype = C.c_int
+            l.mi_degensac_pose_refine_lists_dev.argtypes = head + [vp] + [vp] * 5
+            l.mi_degensac_pose_refine_lists.restype = C.c_int
+            l.mi_degensac_pose_refine_lists.argtypes = head + [vp] * 5
+            l.mi_degensac_pose_refine_tile.restype = C.c_int
+            l.mi_degensac_pose_refine_tile.argtypes = [C.c_int]
         l.mi_degensac_kpts_to_xyA.restype = C.c_int
         l.mi_degensac_kpts_to_xyA.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, dp]
         l.mi_degensac_kpts_to_xyA_dev.restype = C.c_int

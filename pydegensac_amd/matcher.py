@@ -1203,6 +1203,69 @@ def relative_pose(pts, corr_offsets, models, cams1, pairs=None, cams2=None, keep
     return res + (cand, cf) if with_candidates else res
 
 
+def check_refine_args(pts_shape, pts_dtype, off_shape, off_dtype, R_shape, R_dtype, t_shape, t_dtype, cams1_shape, cams1_dtype, pairs=None, cams2=None,
+                      keep=None, max_trials=20, ftol=1e-12):
+    """The argument checks of refine_pose / refine_pose_tensors on shapes and dtype names (numpy or torch): R float64 [K, 3, 3] and t
+    float64 [K, 3] as relative_pose returns them, max_trials an integer in 0 .. 100, ftol a number >= 0; everything else as
+    check_pose_args, which is called for it.  Returns (K, cap, rows of cams1, rows of cams2 or None, max_trials, ftol); raises ValueError."""
+    K = int(off_shape[0]) - 1 if len(off_shape) == 1 else -1
+    if len(R_shape) != 3 or tuple(R_shape[1:]) != (3, 3) or (K >= 0 and R_shape[0] != K) or _dtype_name(R_dtype) != "float64":
+        raise ValueError("R should be float64 [K, 3, 3], one rotation per entry of corr_offsets")
+    if len(t_shape) != 2 or t_shape[1] != 3 or (K >= 0 and t_shape[0] != K) or _dtype_name(t_dtype) != "float64":
+        raise ValueError("t should be float64 [K, 3], one baseline direction per entry of corr_offsets")
+    K, cap, n1, n2, _ = check_pose_args(pts_shape, pts_dtype, off_shape, off_dtype, R_shape, R_dtype, cams1_shape, cams1_dtype, pairs, cams2, keep)
+    if isinstance(max_trials, bool) or not isinstance(max_trials, (int, np.integer)) or not 0 <= int(max_trials) <= 100:
+        raise ValueError("max_trials should be an integer in 0 .. 100")
+    if isinstance(ftol, bool) or not isinstance(ftol, (int, float, np.integer, np.floating)) or not float(ftol) >= 0.0:
+        raise ValueError("ftol should be a number >= 0")
+    return K, cap, n1, n2, int(max_trials), float(ftol)
+
+
+def refine_pose(pts, corr_offsets, R, t, cams1, pairs=None, cams2=None, keep=None, max_trials=20, ftol=1e-12, with_resid=False, with_F=False,
+                device=0, **unknown):
+    """Refine relative poses on exported correspondence lists (include/mi_degensac.h mi_degensac_pose_refine_lists, blocking, numpy): per
+    entry p a Levenberg-Marquardt run over the five degrees of freedom of (R[p], t[p] / |t[p]|) on the Sampson distance, in pixels, of the
+    used rows pts[corr_offsets[p] : corr_offsets[p + 1]] under the entry's two pinhole cameras.  R, t are what relative_pose returned,
+    cameras, pairs and keep as there (its `front` goes in as keep as it is).  At most max_trials trial steps per entry; an accepted step
+    that lowers the cost by no more than ftol times the cost ends the run.
+    Returns (R [K, 3, 3], t [K, 3], cost [K, 2] = (start, end), info [K, 4] int32 = (rows used, trials, trials accepted, _lib.REFINE_*
+    status)[, resid [cap]: the signed Sampson distance of the used rows under the final pose, NaN elsewhere][, F [K, 3, 3] = K2^-T [t]x R
+    K1^-1 of the final pose, x2^T F x1 = 0])."""
+    if unknown:
+        raise ValueError(f"refine_pose: unknown keyword {sorted(unknown)[0]!r}")
+    P = np.ascontiguousarray(np.asarray(pts)); o = np.ascontiguousarray(np.asarray(corr_offsets)); Rm = np.asarray(R); tv = np.asarray(t)
+    c1 = np.asarray(cams1); c2 = None if cams2 is None else np.asarray(cams2)
+    pr = None if pairs is None else np.asarray(pairs)
+    kp = None if keep is None else np.asarray(keep)
+    sd = lambda x: None if x is None else (x.shape, x.dtype)          # noqa: E731
+    K, cap, n1, n2, mt, ft = check_refine_args(P.shape, P.dtype, o.shape, o.dtype, Rm.shape, Rm.dtype, tv.shape, tv.dtype, c1.shape, c1.dtype, sd(pr),
+                                               sd(c2), sd(kp), max_trials, ftol)
+    pose = np.ascontiguousarray(np.concatenate([Rm.reshape(K, 9), tv], 1))
+    idx = None
+    if pr is None:
+        cams = np.ascontiguousarray(c1).reshape(2 * K, 4)
+    else:
+        cams = np.ascontiguousarray(c1 if c2 is None else np.concatenate([c1, c2]))
+        wide = pr.astype(np.int64) + np.array([0, 0 if c2 is None else n1], np.int64)
+        if c2 is not None:                                            # an image of store 1 must not reach into store 2's rows
+            wide[(pr[:, 0] < 0) | (pr[:, 0] >= n1), 0] = -1
+            wide[pr[:, 1] < 0, 1] = -1
+        idx = np.ascontiguousarray(np.clip(wide, -1, 0x7fffffff).astype(np.int32))
+    if kp is not None:
+        kp = np.ascontiguousarray(kp).view(np.uint8)
+    out = np.zeros((K, 12)); cost = np.full((K, 2), np.nan); info = np.zeros((K, 4), np.int32)
+    resid = np.full(cap, np.nan) if with_resid else None
+    F = np.zeros((K, 9)) if with_F else None
+    vp = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)          # noqa: E731
+    rc = _lib.lib().mi_degensac_pose_refine_lists(vp(P), vp(o), vp(kp), vp(pose), vp(cams), len(cams), vp(idx), K, cap, mt, ft, int(device), vp(out),
+                                                  vp(cost), vp(info), vp(resid), vp(F))
+    _lib.check_match(rc)
+    res = (out[:, :9].reshape(K, 3, 3), out[:, 9:], cost, info)
+    if with_resid:
+        res += (resid,)
+    return res + (F.reshape(K, 3, 3),) if with_F else res
+
+
 def pose_config(info, min_front_ratio=0.5, min_wide_ratio=0.0):
     """What the info rows [K, 5] of relative_pose / relative_pose_tensors (numpy, or a tensor, which is copied to the host) say about a
     pair that two_view_config put into class 2, "planar or panoramic": int8 [K] with 2 = panoramic (wide <= min_wide_ratio * front,

@@ -1008,3 +1008,67 @@ def relative_pose_tensors(pts, corr_offsets, models, cams1, pairs=None, cams2=No
     if with_points:
         res += (X[:cap], depth[:cap], cosang[:cap])
     return res + (cand, cf) if with_candidates else res
+
+
+def refine_pose_tensors(pts, corr_offsets, R, t, cams1, pairs=None, cams2=None, keep=None, max_trials=20, ftol=1e-12, with_resid=False,
+                        with_F=False, **unknown):
+    """Refine relative poses on exported correspondence lists, on the device and without a host synchronisation (include/mi_degensac.h
+    mi_degensac_pose_refine_lists_dev): the non-linear step that follows the decomposition of relative_pose_tensors.  pts [cap, 4]
+    float64, corr_offsets [K + 1] int64, cameras, pairs and keep exactly as relative_pose_tensors takes them (its `front` goes in as
+    keep as it is); R [K, 3, 3] and t [K, 3] float64 are what it returned.  Per entry a Levenberg-Marquardt run over the five degrees of
+    freedom of (R, t / |t|) on the Sampson distance, in pixels, of the used rows: at most max_trials trial steps, an accepted step that
+    lowers the cost by no more than ftol times the cost ends the run.  The kernel reads the entries' lengths from corr_offsets itself, so
+    nothing is read back.
+    Returns (R [K, 3, 3], t [K, 3], cost [K, 2] = (start, end), info [K, 4] int32 = (rows used, trials, trials accepted, _lib.REFINE_*
+    status)[, resid [cap]: the signed Sampson distance of the used rows under the final pose, NaN elsewhere][, F [K, 3, 3] = K2^-T [t]x R
+    K1^-1 of the final pose, x2^T F x1 = 0, which guided_match_pairs_tensors, correspondences_pairs_tensors(models=) and
+    relative_pose_tensors take as it is]) on the device, asynchronous on the current stream.  An entry without a usable start (status
+    REFINE_SHORT, NOT_FINITE, BAD_CAMERA, TRUNCATED) keeps its pose and has NaN costs; REFINE_BAD_POSE (the zeros of a failed pose entry)
+    gives zeros."""
+    import torch
+    from . import matcher
+    if unknown:
+        raise ValueError(f"refine_pose_tensors: unknown keyword {sorted(unknown)[0]!r}")
+    opt = [x for x in (pairs, cams2, keep) if x is not None]
+    ts = [pts, corr_offsets, R, t, cams1] + opt
+    if not all(isinstance(x, torch.Tensor) for x in ts):
+        raise ValueError("pts, corr_offsets, R, t, cams1 (and pairs, cams2, keep) must be torch tensors on a ROCm device")
+    sd = lambda x: None if x is None else (tuple(x.shape), x.dtype)          # noqa: E731
+    K, cap, n1, n2, mt, ft = matcher.check_refine_args(tuple(pts.shape), pts.dtype, tuple(corr_offsets.shape), corr_offsets.dtype, tuple(R.shape), R.dtype,
+                                                       tuple(t.shape), t.dtype, tuple(cams1.shape), cams1.dtype, sd(pairs), sd(cams2), sd(keep),
+                                                       max_trials, ftol)
+    if any(x.device != pts.device for x in ts) or pts.device.type != "cuda":
+        raise ValueError("pts, corr_offsets, R, t, cams1 (and pairs, cams2, keep) must live on the same ROCm device")
+    dev = pts.device
+    P = pts.contiguous(); o = corr_offsets.contiguous()
+    pose = torch.cat([R.reshape(K, 9), t], 1).contiguous()
+    idx = None
+    if pairs is None:
+        cams = cams1.contiguous()
+        n_cams = 2 * K
+    else:
+        cams = cams1.contiguous() if cams2 is None else torch.cat([cams1, cams2])
+        n_cams = n1 + (n2 or 0)
+        wide = pairs.to(torch.int64)
+        if cams2 is not None:                                         # an image of store 1 must not reach into store 2's rows
+            a = torch.where((wide[:, 0] < 0) | (wide[:, 0] >= n1), -1, wide[:, 0])
+            b = torch.where(wide[:, 1] < 0, -1, wide[:, 1] + n1)
+            wide = torch.stack([a, b], 1)
+        idx = wide.clamp(-1, 0x7fffffff).to(torch.int32).contiguous()
+    kp = None if keep is None else keep.contiguous().view(torch.uint8)
+    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
+    out = f64(K, 12); cost = f64(K, 2); info = torch.empty((K, 4), dtype=torch.int32, device=dev)
+    resid = f64(max(cap, 1)) if with_resid else None                  # (an address also where cap == 0)
+    F = f64(K, 9) if with_F else None
+    stream = torch.cuda.current_stream(dev)
+    p = lambda x: None if x is None else x.data_ptr()          # noqa: E731
+    rc = _lib.lib().mi_degensac_pose_refine_lists_dev(p(P), p(o), p(kp), p(pose), p(cams), n_cams, p(idx), K, cap, mt, ft, dev.index or 0,
+                                                      C.c_void_p(stream.cuda_stream), p(out), p(cost), p(info), p(resid), p(F))
+    _lib.check_match(rc)
+    for x in (P, o, pose, cams, idx, kp):
+        if x is not None:
+            x.record_stream(stream)
+    res = (out[:, :9].reshape(K, 3, 3), out[:, 9:], cost, info)
+    if with_resid:
+        res += (resid[:cap],)
+    return res + (F.view(K, 3, 3),) if with_F else res
