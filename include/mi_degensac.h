@@ -1091,6 +1091,101 @@ int mi_degensac_pose_refine_lists(const double *pts, const int64_t *corr_offsets
 /* the tile constants: which = 0 rows per workgroup and step of a row pass, 1 the cap on the grid (-1 for any other value) */
 int mi_degensac_pose_refine_tile(int which);
 
+/* ---- triangulation of tracks under known camera poses (mi_triangulate.hip) ------------------------------------------------------------
+ * The tracks call ends the pair-list pipeline with tables nobody consumed.  With poses from elsewhere (a previous reconstruction, a SLAM
+ * front end, a rig, GPS/INS) every track becomes a 3-D point with its reprojection errors: hloc's triangulation.py, COLMAP's
+ * point_triangulator.  Per track, on the device and without a host synchronisation: ranges and the number of tracks are read from
+ * device memory.
+ * Inputs (device arrays on one device), the first four exactly as mi_degensac_tracks_dev writes them, fills included:
+ *   d_track_offsets [T + 1] int64   track k owns the positions o[k] .. o[k + 1] of d_obs / d_obs_image (T = n_tracks_max)
+ *   d_obs [M] int32                 store rows (M = n_obs_max), d_obs_image [M] int32 their images; the -1 of the tails is never an index
+ *   d_n_tracks [1] int64            (nullable: all T) only the first min(max(*d_n_tracks, 0), T) tracks are triangulated; every later one
+ *                                   gets the outputs of an empty track: X, cost, cosang NaN, info (0, 0, 0, 0, SHORT)
+ *   d_kps [rows, 2] float64         x, y per row of the ONE store the tracks were built on
+ *   d_cams [n_images, 4] float64    pinhole fx, fy, cx, cy per image, as the pose call takes them
+ *   d_poses [n_images, 12] float64  R row-major, then t: world to camera, X_cam = R X + t (the layout of d_pose)
+ * Every step below is ONE IEEE float64 operation per written operator, no contraction; a sum of three terms is (a + b) + c, one of four
+ * ((a + b) + c) + d.  Only + - * / sqrt, comparisons and |x| occur on the device.
+ * Statuses, in their order of precedence:
+ *   TRUNCATED    not 0 <= o[k] <= o[k + 1] <= M.  Nothing of the track is read; info (0, 0, 0, 0, TRUNCATED).
+ *   SHORT        fewer than two USED observations.  The observation at position p is used when m = d_obs_image[p] lies in [0, n_images),
+ *                r = d_obs[p] lies in [0, rows), x, y = d_kps[r] are finite, the twelve numbers of d_poses[m] are finite, and fx, fy of
+ *                d_cams[m] are finite and not zero.  Anything else is skipped and never used as an index.  Two keypoints of one image
+ *                are two observations.  info (used, 0, 0, 0, SHORT).
+ *   DEGENERATE   the 3 x 3 system of the linear point is not positive definite, or the linear point is not finite.  info (used, 0, 0, 0,
+ *                DEGENERATE).
+ *   NARROW       a point exists and cosang > cos_min, cos_min = cos(min_angle_deg * (3.141592653589793 / 180.0)) by the C library's cos on
+ *                the host.  Every output is written as for OK.
+ *   OK
+ * With one of the first three X, both costs and cosang are NaN and no position of d_err, d_ok, d_depth is written.
+ * Per used observation: d0 = (x - cx) / fx, d1 = (y - cy) / fy; v[j] = (R[0][j] d0 + R[1][j] d1) + R[2][j] (R^T d with d[2] = 1);
+ *   nn = sqrt((v[0] v[0] + v[1] v[1]) + v[2] v[2]); the unit ray w[j] = v[j] / nn;
+ *   the centre c[j] = -((R[0][j] t[0] + R[1][j] t[1]) + R[2][j] t[2]);
+ *   P = I - w w^T as P00 = 1 - w[0] w[0], P01 = -(w[0] w[1]), P02 = -(w[0] w[2]), P11 = 1 - w[1] w[1], P12 = -(w[1] w[2]), P22 = 1 - w[2] w[2];
+ *   q[0] = (P00 c[0] + P01 c[1]) + P02 c[2], q[1] = (P01 c[0] + P11 c[1]) + P12 c[2], q[2] = (P02 c[0] + P12 c[1]) + P22 c[2].
+ * The linear point (the N-view midpoint): the nine sums A = sum P in the order 00 01 02 11 12 22 and b = sum q; X = solve(A, b).
+ * solve(M, r), M symmetric: the unpivoted Cholesky factor L00 = sqrt(M00), L10 = M01 / L00, L20 = M02 / L00, p = M11 - L10 L10, L11 =
+ *   sqrt(p), L21 = (M12 - L20 L10) / L11, p = M22 - L20 L20, p = p - L21 L21, L22 = sqrt(p); a pivot (M00 and the two p) that is not > 0, a
+ *   NaN included, FAILS the solve.  y0 = r[0] / L00, y1 = (r[1] - L10 y0) / L11, y2 = ((r[2] - L20 y0) - L21 y1) / L22; x[2] = y2 / L22,
+ *   x[1] = (y1 - L21 x[2]) / L11, x[0] = ((y0 - L10 x[1]) - L20 x[2]) / L00.
+ * One pass at a point X, per used observation: Xc = ((R[0][0] X[0] + R[0][1] X[1]) + R[0][2] X[2]) + t[0], Yc and Zc likewise with rows 1
+ *   and 2; u = Xc / Zc, v = Yc / Zc; the residual rx = (fx u + cx) - x, ry = (fy v + cy) - y;
+ *   ax = fx / Zc, ex = (fx u) / Zc, ay = fy / Zc, ey = (fy v) / Zc; the Jacobian with respect to X: Jx[j] = ax R[0][j] - ex R[2][j], Jy[j] =
+ *   ay R[1][j] - ey R[2][j].
+ *   The ten sums of a pass, each term ONE sum of two products: cost = sum (rx rx + ry ry); H_jk = sum (Jx[j] Jx[k] + Jy[j] Jy[k]) in the
+ *   order 00 01 02 11 12 22; g_j = sum (Jx[j] rx + Jy[j] ry).
+ * The run: one pass at the linear point gives cost, H, g; that cost is d_cost[k][0].  Then, while fewer than max_iters trials have been
+ *   made: delta = solve(H, g); a failed solve ends the run (it is no trial).  The trial point is X'[j] = X[j] - delta[j]; one pass at X'
+ *   gives cost', H', g'.  The trial is ACCEPTED iff cost' is finite and cost' < cost; the first trial that is not ends the run and the
+ *   current point stays.  Accepted: X', cost', H', g' become the current ones; if (cost - cost') <= ftol cost with the cost before the
+ *   step, the run ends.  max_iters = 0 returns the linear point.  A run is trials + 1 passes.
+ * At the final point, per used observation: err = sqrt(rx rx + ry ry), depth = Zc, front = Zc > 0 (a NaN is not front), ok = front and
+ *   err <= max_reproj_px.
+ * cosang = the minimum of (w_i[0] w_j[0] + w_i[1] w_j[1]) + w_i[2] w_j[2] over the pairs i != j of used observations: the products
+ *   commute, so it does not depend on an order.
+ * The order of every sum (A, b, cost, H, g), with G = mi_degensac_triangulate_tile(0) lanes per track: lane l adds the terms of the used
+ *   observations at the positions i == l (mod G) of the track (i counted from o[k]) in ascending i into an accumulator that starts as
+ *   +0.0; an observation that is not used adds nothing.  Then for m = G / 2, G / 4, .., 1: every lane l takes v[l] + v[l xor m].  IEEE
+ *   addition commutes, so all lanes hold the same bits: the tree in which lane 0 takes v[0] + v[m] with v[0] and v[m] the sums of the
+ *   step before.  The counts are integer sums.
+ * Outputs (T rows each, M positions each for the last three):
+ *   d_X [T, 3]              the point in the world frame
+ *   d_info [T, 5] int32     used observations, ok observations at the final point, accepted steps, trial steps, status
+ *   d_cost [T, 2]           the cost in px^2 over the used observations at the linear and at the final point
+ *   d_cosang [T]
+ *   d_err [M], d_ok [M] uint8, d_depth [M]   (each nullable) per used observation of a track with a point; every other position, the
+ *                           positions no track owns included, keeps NaN, 0, NaN
+ * A group of G lanes per track, tracks by a grid stride over at most mi_degensac_triangulate_tile(1) workgroups of tile(2) groups; the
+ * pair pass stages tile(3) unit rays at a time in LDS and recomputes them per chunk for a longer track, so a track of any length
+ * works.  The pair pass is quadratic: a track of n observations costs n (n - 1) / 2 products inside its one group and, beyond tile(3)
+ * observations, restages the rays once per pair of chunks, so one very long track holds its workgroup for that long (2049 observations:
+ * 2.1 million products).  No atomics, no group waits for another: the same bits on every call.  Asynchronous on `stream`; no
+ * temporaries.  Ranges must not overlap when d_err, d_ok or d_depth is given.
+ * Refused with MI_DEGENSAC_EINVAL and a message in mi_degensac_match_last_error(), before a device is looked for and in this order:
+ * n_tracks_max < 0 or > 0x3fffffff; n_obs_max < 0 or > 0x3fffffff; rows < 0 or > 0x7fffffff; n_images < 0; a min_angle_deg that is NaN or
+ * outside [0, 180]; a max_reproj_px that is NaN or < 0; max_iters outside 0 .. 100; an ftol that is NaN or < 0; NULL d_track_offsets; for
+ * n_obs_max > 0 NULL d_obs or d_obs_image; for n_tracks_max > 0 NULL d_X, d_info, d_cost or d_cosang; for rows > 0 NULL d_kps; for
+ * n_images > 0 NULL d_cams or d_poses.  n_tracks_max == 0 and n_obs_max == 0 succeed (with n_tracks_max == 0 the fills of d_err, d_ok
+ * and d_depth are all that is written). */
+enum { MI_DEGENSAC_TRI_OK = 0, MI_DEGENSAC_TRI_NARROW = 1, MI_DEGENSAC_TRI_DEGENERATE = 2, MI_DEGENSAC_TRI_SHORT = 3,
+       MI_DEGENSAC_TRI_TRUNCATED = 4 };
+int mi_degensac_triangulate_tracks_dev(const int64_t *d_track_offsets, const int32_t *d_obs, const int32_t *d_obs_image,
+                                       const int64_t *d_n_tracks /*nullable*/, const double *d_kps, int64_t rows, const double *d_cams,
+                                       const double *d_poses, int n_images, int64_t n_tracks_max, int64_t n_obs_max, double min_angle_deg,
+                                       double max_reproj_px, int max_iters, double ftol, int device, void *stream, double *d_X,
+                                       int32_t *d_info, double *d_cost, double *d_cosang, double *d_err /*nullable*/,
+                                       uint8_t *d_ok /*nullable*/, double *d_depth /*nullable*/);
+/* the same on host pointers (blocking): the inputs go to the device once, every output that is asked for comes back whole; n_tracks is
+ * passed by value, < 0 = all n_tracks_max */
+int mi_degensac_triangulate_tracks(const int64_t *track_offsets, const int32_t *obs, const int32_t *obs_image, int64_t n_tracks,
+                                   const double *kps, int64_t rows, const double *cams, const double *poses, int n_images,
+                                   int64_t n_tracks_max, int64_t n_obs_max, double min_angle_deg, double max_reproj_px, int max_iters,
+                                   double ftol, int device, double *X, int32_t *info, double *cost, double *cosang,
+                                   double *err /*nullable*/, uint8_t *ok /*nullable*/, double *depth /*nullable*/);
+/* the tile constants: which = 0 G = lanes per track, 1 the cap on the grid, 2 tracks (groups) per workgroup, 3 rays per staging area of
+ * the pair pass (-1 for any other value) */
+int mi_degensac_triangulate_tile(int which);
+
 /* ---- unit-level device entry points (parity tests of the kernels' building blocks) ------------ */
 /* score n_models fundamental (kind 0: Sampson, 1: symmetric epipolar) or homography (kind 10..14:
  * H Sampson, symm_sq_max, symm_max, symm_sq_sum, symm_sum) models against all n points: I (<= th)

@@ -50,6 +50,11 @@ POSE_OK, POSE_BAD_MODEL, POSE_BAD_CAMERA, POSE_TRUNCATED, POSE_EMPTY = range(5)
 # the cap on the grid; the status column of its info rows (MI_DEGENSAC_REFINE_*)
 REFINE_STEP, REFINE_GRID = 1024, 256
 REFINE_CONVERGED, REFINE_STALLED, REFINE_MAX_TRIALS, REFINE_SHORT, REFINE_NOT_FINITE, REFINE_BAD_POSE, REFINE_BAD_CAMERA, REFINE_TRUNCATED = range(8)
+# the triangulation of tracks (csrc/mi_triangulate.hip TR_GRID / TR_CH, mi_degensac_triangulate_tile): the cap on the grid, rays per staging
+# area of the pair pass; the lanes per track are a build constant (TR_G) that tri_group() reads from the loaded library; the status column
+# of its info rows (MI_DEGENSAC_TRI_*)
+TRI_GRID, TRI_CHUNK = 1024, 64
+TRI_OK, TRI_NARROW, TRI_DEGENERATE, TRI_SHORT, TRI_TRUNCATED = range(5)
 
 
 class Params(C.Structure):
@@ -369,6 +374,17 @@ def lib():
             l.mi_degensac_pose_refine_lists.argtypes = head + [vp] * 5
             l.mi_degensac_pose_refine_tile.restype = C.c_int
             l.mi_degensac_pose_refine_tile.argtypes = [C.c_int]
+        if hasattr(l, "mi_degensac_triangulate_tracks_dev"):              # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            # track_offsets, obs, obs_image, n_tracks, kps, rows, cams, poses, n_images, T, M, min_angle_deg, max_reproj_px, max_iters, ftol,
+            # device[, stream] | X, info, cost, cosang, err, ok, depth
+            vp = C.c_void_p
+            tail = [vp, C.c_int64, vp, vp, C.c_int, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int, C.c_double, C.c_int]
+            l.mi_degensac_triangulate_tracks_dev.restype = C.c_int
+            l.mi_degensac_triangulate_tracks_dev.argtypes = [vp, vp, vp, vp] + tail + [vp] + [vp] * 7
+            l.mi_degensac_triangulate_tracks.restype = C.c_int
+            l.mi_degensac_triangulate_tracks.argtypes = [vp, vp, vp, C.c_int64] + tail + [vp] * 7
+            l.mi_degensac_triangulate_tile.restype = C.c_int
+            l.mi_degensac_triangulate_tile.argtypes = [C.c_int]
         l.mi_degensac_kpts_to_xyA.restype = C.c_int
         l.mi_degensac_kpts_to_xyA.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, dp]
         l.mi_degensac_kpts_to_xyA_dev.restype = C.c_int
@@ -393,6 +409,11 @@ def lib():
         l.mi_degensac_device_count.restype = C.c_int
         _lib = l
     return _lib
+
+
+def tri_group():
+    """lanes per track of the loaded library's triangulation kernel (mi_degensac_triangulate_tile(0)): the order of its sums depends on it"""
+    return int(lib().mi_degensac_triangulate_tile(0))
 
 
 def check(rc):

@@ -1266,6 +1266,81 @@ def refine_pose(pts, corr_offsets, R, t, cams1, pairs=None, cams2=None, keep=Non
     return res + (F.reshape(K, 3, 3),) if with_F else res
 
 
+def check_triangulate_args(off_shape, off_dtype, obs_shape, obs_dtype, img_shape, img_dtype, kps_shape, kps_dtype, cams_shape, cams_dtype, R_shape,
+                           R_dtype, t_shape, t_dtype, n_tracks=None, min_angle_deg=1.5, max_reproj_px=4.0, max_iters=10, ftol=1e-12):
+    """The argument checks of triangulate_tracks / triangulate_tracks_tensors on shapes and dtype names (numpy or torch): track_offsets
+    int64 [T + 1], obs and obs_image int32 [M], kps float64 [rows, >= 2], cams float64 [n_images, 4], R float64 [n_images, 3, 3], t float64
+    [n_images, 3]; n_tracks None or (shape, dtype) = int64 [1]; min_angle_deg a number in [0, 180], max_reproj_px a number >= 0, max_iters
+    an integer in 0 .. 100, ftol a number >= 0.  Returns (T, M, rows, n_images, min_angle_deg, max_reproj_px, max_iters, ftol); raises
+    ValueError."""
+    num = (int, float, np.integer, np.floating)
+    if len(off_shape) != 1 or off_shape[0] < 1 or _dtype_name(off_dtype) != "int64":
+        raise ValueError("track_offsets should be int64 [T + 1], as the tracks call returns it")
+    T = int(off_shape[0]) - 1
+    if len(obs_shape) != 1 or _dtype_name(obs_dtype) != "int32":
+        raise ValueError("obs should be int32 [M] of store rows, as the tracks call returns it")
+    if tuple(img_shape) != tuple(obs_shape) or _dtype_name(img_dtype) != "int32":
+        raise ValueError("obs_image should be int32 [M], one image per element of obs")
+    if T > 0x3fffffff or obs_shape[0] > 0x3fffffff:
+        raise ValueError("too many tracks or observations")
+    if len(kps_shape) != 2 or kps_shape[1] < 2 or _dtype_name(kps_dtype) != "float64" or kps_shape[0] > 0x7fffffff:
+        raise ValueError("kps should be float64 [rows, >= 2] with x, y in front, one row per row of the store")
+    if len(cams_shape) != 2 or cams_shape[1] != 4 or _dtype_name(cams_dtype) != "float64" or cams_shape[0] > 0x7fffffff:
+        raise ValueError("cams should be float64 [n_images, 4] = fx, fy, cx, cy per image")
+    n = int(cams_shape[0])
+    if tuple(R_shape) != (n, 3, 3) or _dtype_name(R_dtype) != "float64":
+        raise ValueError("R should be float64 [n_images, 3, 3], one world-to-camera rotation per row of cams")
+    if tuple(t_shape) != (n, 3) or _dtype_name(t_dtype) != "float64":
+        raise ValueError("t should be float64 [n_images, 3], X_cam = R X + t")
+    if n_tracks is not None and (tuple(n_tracks[0]) != (1,) or _dtype_name(n_tracks[1]) != "int64"):
+        raise ValueError("n_tracks should be int64 [1], as the tracks call returns it (or None = all T)")
+    if isinstance(min_angle_deg, bool) or not isinstance(min_angle_deg, num) or not 0.0 <= float(min_angle_deg) <= 180.0:
+        raise ValueError("min_angle_deg should be a number in [0, 180]")
+    if isinstance(max_reproj_px, bool) or not isinstance(max_reproj_px, num) or not float(max_reproj_px) >= 0.0:
+        raise ValueError("max_reproj_px should be a number >= 0")
+    if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or not 0 <= int(max_iters) <= 100:
+        raise ValueError("max_iters should be an integer in 0 .. 100")
+    if isinstance(ftol, bool) or not isinstance(ftol, num) or not float(ftol) >= 0.0:
+        raise ValueError("ftol should be a number >= 0")
+    return T, int(obs_shape[0]), int(kps_shape[0]), n, float(min_angle_deg), float(max_reproj_px), int(max_iters), float(ftol)
+
+
+def triangulate_tracks(track_offsets, obs, obs_image, kps, cams, R, t, n_tracks=None, min_angle_deg=1.5, max_reproj_px=4.0, max_iters=10, ftol=1e-12,
+                       with_obs=False, device=0, **unknown):
+    """Triangulate tracks under known camera poses (include/mi_degensac.h mi_degensac_triangulate_tracks, blocking, numpy): per track k
+    the N-view midpoint of its used observations obs[track_offsets[k] : track_offsets[k + 1]] (store rows, obs_image their images),
+    refined by at most max_iters Gauss-Newton steps on the reprojection error in pixels.  kps [rows, >= 2] holds x, y per row of the
+    store, cams [n_images, 4] = fx, fy, cx, cy, R [n_images, 3, 3] and t [n_images, 3] the world-to-camera poses X_cam = R X + t (the
+    convention of synthetic.collection_cameras).  n_tracks: an integer, only the first min(n_tracks, T) tracks are triangulated (None:
+    all T).  An observation with an index out of range, or with a keypoint, pose or focal length that is not finite, is skipped.
+    Returns (X [T, 3] in the world frame, info [T, 5] int32 = (observations used, observations in front and within max_reproj_px at
+    the final point, accepted steps, trial steps, _lib.TRI_* status), cost [T, 2] = the summed squared reprojection error at the linear
+    and at the final point, cosang [T] = the smallest cosine between two rays of the track[, err [M] in px, ok [M] bool, depth [M] per
+    used observation]).  TRI_NARROW (no two rays min_angle_deg apart) still has its point; TRI_DEGENERATE, TRI_SHORT and TRI_TRUNCATED
+    have NaN."""
+    if unknown:
+        raise ValueError(f"triangulate_tracks: unknown keyword {sorted(unknown)[0]!r}")
+    o = np.ascontiguousarray(np.asarray(track_offsets)); ob = np.ascontiguousarray(np.asarray(obs)); oi = np.ascontiguousarray(np.asarray(obs_image))
+    kp = np.asarray(kps); cm = np.asarray(cams); Rm = np.asarray(R); tv = np.asarray(t)
+    if n_tracks is not None and (isinstance(n_tracks, bool) or not isinstance(n_tracks, (int, np.integer))):
+        raise ValueError("n_tracks should be an integer (or None = all T)")
+    T, M, rows, n, ang, px, mi, ft = check_triangulate_args(o.shape, o.dtype, ob.shape, ob.dtype, oi.shape, oi.dtype, kp.shape, kp.dtype, cm.shape, cm.dtype,
+                                                            Rm.shape, Rm.dtype, tv.shape, tv.dtype, None, min_angle_deg, max_reproj_px, max_iters, ftol)
+    xy = np.ascontiguousarray(kp[:, :2]); cm = np.ascontiguousarray(cm)
+    poses = np.ascontiguousarray(np.concatenate([Rm.reshape(n, 9), tv], 1))
+    X = np.full((T, 3), np.nan); info = np.zeros((T, 5), np.int32); cost = np.full((T, 2), np.nan); cosang = np.full(T, np.nan)
+    err = np.full(M, np.nan) if with_obs else None
+    ok = np.zeros(M, np.uint8) if with_obs else None
+    depth = np.full(M, np.nan) if with_obs else None
+    vp = lambda x: None if x is None or x.size == 0 else x.ctypes.data_as(C.c_void_p)          # noqa: E731
+    rc = _lib.lib().mi_degensac_triangulate_tracks(vp(o), vp(ob), vp(oi), -1 if n_tracks is None else max(int(n_tracks), 0), vp(xy), rows, vp(cm),
+                                                   vp(poses), n, T, M, ang, px, mi, ft, int(device), vp(X), vp(info), vp(cost), vp(cosang), vp(err),
+                                                   vp(ok), vp(depth))
+    _lib.check_match(rc)
+    res = (X, info, cost, cosang)
+    return res + (err, ok.astype(bool), depth) if with_obs else res
+
+
 def pose_config(info, min_front_ratio=0.5, min_wide_ratio=0.0):
     """What the info rows [K, 5] of relative_pose / relative_pose_tensors (numpy, or a tensor, which is copied to the host) say about a
     pair that two_view_config put into class 2, "planar or panoramic": int8 [K] with 2 = panoramic (wide <= min_wide_ratio * front,

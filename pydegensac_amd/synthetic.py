@@ -174,3 +174,27 @@ def image_collection(m=8, n=500, inlier_ratio=0.5, sigma=0.1, dim=64, seed=0, de
         perm = rng.permutation(n)
         kps.append(np.ascontiguousarray(p[perm])); descs.append(np.ascontiguousarray(d[perm]))
     return kps, descs
+
+
+def collection_truth(m=8, n=500, inlier_ratio=0.5, sigma=0.1, dim=64, seed=0, desc_sigma=0.15):
+    """What image_collection(m, n, inlier_ratio, sigma, dim, seed, desc_sigma) drew: the cloud X [n, 3] and, per image, point [n] int64 = the
+    cloud index of every keypoint, -1 for clutter.  The generator's draws are replayed one for one, so the keypoint i of image k is
+    _project(K, R_k, t_k, X[point[k][i]]) plus its noise (tests/test_triangulate_cpu.py holds the replay to image_collection's keypoints
+    bit for bit).  Returns (X, [point_k], [kps_k])."""
+    rng = np.random.default_rng(seed)
+    X = np.stack([rng.uniform(-2, 2, n), rng.uniform(-1.5, 1.5, n), rng.uniform(4, 8, n)], 1)
+    rng.normal(size=(n, dim))                                             # base
+    K, poses = collection_cameras(m)
+    n_in = int(round(n * inlier_ratio))
+    points, kps = [], []
+    for i in range(m):
+        R, t = poses[i]
+        seen = rng.permutation(n)[:n_in]
+        p = np.stack([rng.uniform(0, IMG_W, n), rng.uniform(0, IMG_H, n)], 1)
+        rng.normal(size=(n, dim))                                         # d
+        p[:n_in] = _project(K, R, t, X[seen]) + rng.normal(0, sigma, (n_in, 2))
+        rng.normal(size=(n_in, dim))                                      # the descriptor noise
+        perm = rng.permutation(n)
+        pt = np.full(n, -1, np.int64); pt[:n_in] = seen
+        points.append(np.ascontiguousarray(pt[perm])); kps.append(np.ascontiguousarray(p[perm]))
+    return X, points, kps

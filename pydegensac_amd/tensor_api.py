@@ -1072,3 +1072,56 @@ def refine_pose_tensors(pts, corr_offsets, R, t, cams1, pairs=None, cams2=None, 
     if with_resid:
         res += (resid[:cap],)
     return res + (F.view(K, 3, 3),) if with_F else res
+
+
+def triangulate_tracks_tensors(track_offsets, obs, obs_image, kps, cams, R, t, n_tracks=None, min_angle_deg=1.5, max_reproj_px=4.0, max_iters=10,
+                               ftol=1e-12, with_obs=False, **unknown):
+    """Triangulate tracks under known camera poses, on the device and without a host synchronisation (include/mi_degensac.h
+    mi_degensac_triangulate_tracks_dev): the step after tracks_tensors when poses come from elsewhere (a previous reconstruction, a SLAM
+    front end, a rig).  track_offsets [T + 1] int64, obs [M] int32, obs_image [M] int32 and n_tracks [1] int64 go in exactly as
+    tracks_tensors returned them, fills included (n_tracks=None: all T tracks); kps [rows, >= 2] float64 holds x, y per row of the store
+    the tracks were built on, cams [n_images, 4] float64 = fx, fy, cx, cy, R [n_images, 3, 3] and t [n_images, 3] float64 the
+    world-to-camera poses X_cam = R X + t (the convention of synthetic.collection_cameras).  Per track: the N-view midpoint of its used
+    observations, then at most max_iters Gauss-Newton steps on the reprojection error in pixels (a step is kept iff it lowers the cost;
+    one that lowers it by no more than ftol times the cost ends the run).  An observation with an index out of range or with a keypoint,
+    pose or focal length that is not finite is skipped.  The kernel reads the ranges and n_tracks itself, so nothing is read back.
+    Returns (X [T, 3] in the world frame, info [T, 5] int32 = (observations used, observations in front and within max_reproj_px at the
+    final point, accepted steps, trial steps, _lib.TRI_* status), cost [T, 2] = the summed squared reprojection error at the linear and
+    at the final point, cosang [T] = the smallest cosine between two rays of the track[, err [M] in px, ok [M] bool, depth [M] per used
+    observation, NaN / False elsewhere]) on the device, asynchronous on the current stream.  TRI_NARROW (no two rays min_angle_deg apart)
+    still has its point; TRI_DEGENERATE, TRI_SHORT, TRI_TRUNCATED and the tracks beyond n_tracks have NaN."""
+    import torch
+    from . import matcher
+    if unknown:
+        raise ValueError(f"triangulate_tracks_tensors: unknown keyword {sorted(unknown)[0]!r}")
+    ts = [track_offsets, obs, obs_image, kps, cams, R, t] + ([] if n_tracks is None else [n_tracks])
+    if not all(isinstance(x, torch.Tensor) for x in ts):
+        raise ValueError("track_offsets, obs, obs_image, kps, cams, R, t (and n_tracks) must be torch tensors on a ROCm device")
+    sd = lambda x: None if x is None else (tuple(x.shape), x.dtype)          # noqa: E731
+    T, M, rows, n, ang, px, mi, ft = matcher.check_triangulate_args(tuple(track_offsets.shape), track_offsets.dtype, tuple(obs.shape), obs.dtype,
+                                                                    tuple(obs_image.shape), obs_image.dtype, tuple(kps.shape), kps.dtype, tuple(cams.shape),
+                                                                    cams.dtype, tuple(R.shape), R.dtype, tuple(t.shape), t.dtype, sd(n_tracks),
+                                                                    min_angle_deg, max_reproj_px, max_iters, ftol)
+    if any(x.device != obs.device for x in ts) or obs.device.type != "cuda":
+        raise ValueError("track_offsets, obs, obs_image, kps, cams, R, t (and n_tracks) must live on the same ROCm device")
+    dev = obs.device
+    o = track_offsets.contiguous(); ob = obs.contiguous(); oi = obs_image.contiguous(); cm = cams.contiguous()
+    xy = kps[:, :2].contiguous()
+    poses = torch.cat([R.reshape(n, 9), t], 1).contiguous()
+    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
+    X = f64(max(T, 1), 3); cost = f64(max(T, 1), 2); cosang = f64(max(T, 1))          # (an address also where T == 0)
+    info = torch.empty((max(T, 1), 5), dtype=torch.int32, device=dev)
+    err = f64(max(M, 1)) if with_obs else None
+    depth = f64(max(M, 1)) if with_obs else None
+    ok = torch.empty(max(M, 1), dtype=torch.uint8, device=dev) if with_obs else None
+    stream = torch.cuda.current_stream(dev)
+    p = lambda x: None if x is None or x.numel() == 0 else x.data_ptr()          # noqa: E731
+    rc = _lib.lib().mi_degensac_triangulate_tracks_dev(p(o), p(ob), p(oi), p(n_tracks), p(xy), rows, p(cm), p(poses), n, T, M, ang, px, mi, ft,
+                                                       dev.index or 0, C.c_void_p(stream.cuda_stream), p(X), p(info), p(cost), p(cosang), p(err), p(ok),
+                                                       p(depth))
+    _lib.check_match(rc)
+    for x in (o, ob, oi, n_tracks, xy, cm, poses):
+        if x is not None:
+            x.record_stream(stream)
+    res = (X[:T], info[:T], cost[:T], cosang[:T])
+    return res + (err[:M], ok[:M].view(torch.bool), depth[:M]) if with_obs else res
