@@ -242,7 +242,13 @@ int mi_degensac_ctx_find_homography_batch(mi_degensac_ctx *ctx, const double *pt
 
 /* ---- device-pointer entry points: everything except `offsets_host` and `prm` lives in HBM ----- */
 /* `stream` is a hipStream_t (NULL = default stream).  Asynchronous: returns after enqueueing; never
- * synchronises the device. */
+ * synchronises the device.
+ * d_offsets holds ABSOLUTE row numbers into d_pts1, d_pts2 and d_mask, so with d_offsets[0] > 0 the three pointers stay the bases of the
+ * whole store, pair p reads rows d_offsets[p] .. d_offsets[p+1] and writes those mask bytes, while d_F / d_H, d_stats and d_seeds are
+ * indexed by p from 0.  Nothing is written outside the owned mask ranges and the n_pairs model and stats blocks.  A pair without a
+ * model leaves a zero model and an all-zero mask whatever the buffers held before the call.  d_stats may be NULL; every other pointer
+ * is required (a NULL one is MI_DEGENSAC_EINVAL when n_pairs > 0; n_pairs <= 0 returns 0 and touches nothing).  offsets_host must hold
+ * the same n_pairs + 1 values as d_offsets (the launch and its workspace are sized from it). */
 int mi_degensac_find_fundamental_batch_dev(const double *d_pts1, const double *d_pts2,
                                            const int64_t *d_offsets, const int64_t *offsets_host,
                                            int n_pairs, int dim, const mi_degensac_params *prm,

@@ -7,6 +7,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI_DEGENSAC_LIB") or os.path.join(_HERE, "libmi_degensac.so")
 STATS_LEN = 16
+OK, EINVAL, ENODEV, EHIP, ENOMEM = 0, -1, -2, -3, -4          # include/mi_degensac.h MI_DEGENSAC_OK / _EINVAL / _ENODEV / _EHIP / _ENOMEM
 STAT_NAMES = ["samples", "lo_runs", "rejected", "I", "models", "degen", "Ih", "best_sample",
               "full_passes", "ex_passes", "h_passes", "aux_passes", "ticks_best", "ticks_total", "threads", "placement"]
 FLAG_FINAL_LAF_FILTER = 1

@@ -367,6 +367,8 @@ static int launch_batch_impl(int homography, const double *d_p1, const double *d
     if (n_pairs <= 0) return 0;
     if (dim != 2 && dim != 6) { set_err("points must be [n,2] or [n,6]"); return MI_DEGENSAC_EINVAL; }
     if (!h_off) { set_err("offsets_host is NULL"); return MI_DEGENSAC_EINVAL; }
+    if (!d_p1 || !d_p2 || !d_off || !d_seeds || !d_model || !d_mask) {
+        set_err("NULL argument (pts1, pts2, offsets, seeds, the model and the mask are required)"); return MI_DEGENSAC_EINVAL; }
     int rc = dev_init(device); if (rc) return rc;
     dg_args A; memset(&A, 0, sizeof A);
     rc = fill_params(prm, homography, dim, &A.prm); if (rc) return rc;
