@@ -23,6 +23,8 @@
 #include <vector>
 #include "../../include/mi_degensac.h"
 #include "mi_match_batch.h"
+#include "mi_host.h"
+#include "mi_dev_util.h"
 #include "dg_geom.h"
 
 #define MX_ROWS 1024              /* rows per workgroup: 256 threads x 4 consecutive rows */
@@ -92,52 +94,21 @@ __device__ __forceinline__ unsigned mx_flags(const mx_args &a, int r0, int (&e)[
     return f;
 }
 
-/* the selected rows of the wave's lower lanes (before this thread's four rows), and of the whole wave */
-__device__ __forceinline__ void mx_wave_prefix(unsigned f, int lane, int *before, int *total)
-{
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int b = 0, t = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const unsigned long long bal = __ballot((f >> j) & 1u);
-        b += __popcll(bal & below); t += __popcll(bal);
-    }
-    *before = b; *total = t;
-}
-
 __global__ __launch_bounds__(256) void mx_count_kernel(mx_args a, int32_t *cnt)
 {
-    __shared__ int wsum[4];
     int e[4], m[4];
     const unsigned f = mx_flags(a, (int)blockIdx.x * MX_ROWS + (int)threadIdx.x * 4, e, m);
     int before, total;
-    mx_wave_prefix(f, threadIdx.x & 63, &before, &total);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = total;
-    __syncthreads();
-    if (threadIdx.x == 0) cnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    mi_wave_prefix(f, threadIdx.x & 63, &before, &total);
+    mi_block_count(total, cnt);
 }
 
 /* one workgroup: base[b] = the counts before workgroup b, *total, and corr_offsets of every entry that starts at row N */
 __global__ __launch_bounds__(MX_SCAN) void mx_scan_kernel(const int32_t *cnt, int nb, int32_t *base, int64_t *total, const int32_t *out, int K, int N,
                                                           int64_t *corr_offsets)
 {
-    __shared__ int wsum[MX_SCAN / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int64_t carry = 0;
-    for (int s = 0; s < nb; s += MX_SCAN) {                           /* uniform over the workgroup */
-        const int i = s + tid;
-        const int c = i < nb ? cnt[i] : 0;
-        int v = c;
-        for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(v, d); if (lane >= d) v += t; }
-        if (lane == 63) wsum[wv] = v;
-        __syncthreads();
-        int wbase = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < MX_SCAN / 64; w++) { if (w < wv) wbase += wsum[w]; all += wsum[w]; }
-        if (i < nb) base[i] = (int32_t)(carry + wbase + v - c);
-        carry += all;
-        __syncthreads();
-    }
+    const int tid = threadIdx.x;
+    const int64_t carry = mi_block_scan<MX_SCAN>(cnt, nb, base);
     if (tid == 0) *total = carry;
     for (int p = tid; p <= K; p += MX_SCAN) if (out[p] >= N) corr_offsets[p] = carry;
 }
@@ -164,7 +135,7 @@ __global__ __launch_bounds__(256) void mx_write_kernel(mx_args a)
     const unsigned f = mx_flags(a, r0, e, m);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     int before, total;
-    mx_wave_prefix(f, lane, &before, &total);
+    mi_wave_prefix(f, lane, &before, &total);
     if (lane == 0) wsum[wv] = total;
     __syncthreads();
     int64_t pos = (int64_t)a.base[blockIdx.x] + before;
@@ -218,25 +189,6 @@ __global__ __launch_bounds__(256) void mx_write_kernel(mx_args a)
 }
 
 /* ---- host side ---------------------------------------------------------------------------------------------------------- */
-#define MXCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { char b_[256]; snprintf(b_, sizeof b_, "%s failed: %s", #x, hipGetErrorString(e_)); \
-    mt_set_error(b_); (void)hipGetLastError(); return MI_DEGENSAC_EHIP; } } while (0)
-static int mx_einval(const char *msg) { mt_set_error(msg); return MI_DEGENSAC_EINVAL; }
-
-struct MxDevGuard {
-    int prev = -1; bool armed = false;
-    int enter(int device)
-    {
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n == 0) { (void)hipGetLastError(); mt_set_error("no HIP device: this library has no CPU path");
-            return MI_DEGENSAC_ENODEV; }
-        if (device < 0 || device >= n) { mt_set_error("device index out of range"); return MI_DEGENSAC_ENODEV; }
-        if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-        if (prev != device) { MXCHK(hipSetDevice(device)); armed = prev >= 0; }
-        return 0;
-    }
-    ~MxDevGuard() { if (armed) (void)hipSetDevice(prev); }
-};
-
 extern "C" int mi_degensac_correspondences_tile(int which) { return which == 0 ? MX_ROWS : which == 1 ? MX_SCAN : -1; }
 
 /* what the call is asked for, after the checks that need neither the list nor a device */
@@ -247,20 +199,20 @@ static int mx_check_params(uint32_t flags, int kp_dim, bool want_pts, bool want_
                            int64_t capacity, int n_pairs, mx_what *w)
 {
     w->gk = MX_NONE; w->hk = 0;
-    if (flags & ~(uint32_t)MI_DEGENSAC_CORR_STORE_ROWS) return mx_einval("flags: unknown bit (MI_DEGENSAC_CORR_STORE_ROWS = 1)");
-    if ((want_pts || want_resid) && kp_dim != 2 && kp_dim != 6) return mx_einval("keypoint rows must be [n,2] or [n,6]");
+    if (flags & ~(uint32_t)MI_DEGENSAC_CORR_STORE_ROWS) return mi_einval("flags: unknown bit (MI_DEGENSAC_CORR_STORE_ROWS = 1)");
+    if ((want_pts || want_resid) && kp_dim != 2 && kp_dim != 6) return mi_einval("keypoint rows must be [n,2] or [n,6]");
     if (want_resid) {
-        if (!models) return mx_einval("resid needs models");
-        if (!gp) return mx_einval("resid needs guide params (homography, error_type)");
-        if (gp->struct_size != 0 && gp->struct_size < (int32_t)sizeof(mi_degensac_guide_params)) return mx_einval("guide params: struct_size too small");
-        if (gp->homography != 0 && gp->homography != 1) return mx_einval("homography must be 0 or 1");
+        if (!models) return mi_einval("resid needs models");
+        if (!gp) return mi_einval("resid needs guide params (homography, error_type)");
+        if (gp->struct_size != 0 && gp->struct_size < (int32_t)sizeof(mi_degensac_guide_params)) return mi_einval("guide params: struct_size too small");
+        if (gp->homography != 0 && gp->homography != 1) return mi_einval("homography must be 0 or 1");
         mt_gate g;
         const int rc = mt_guided_gate(gp->homography, gp->error_type, 0.0, &g);      /* px_th is not read: the gate kind and its messages */
         if (rc) return rc;
         w->gk = g.gk; w->hk = g.hk;
     }
-    if (capacity < 0) return mx_einval("capacity < 0");
-    if (n_pairs < 0) return mx_einval("n_pairs < 0");
+    if (capacity < 0) return mi_einval("capacity < 0");
+    if (n_pairs < 0) return mi_einval("n_pairs < 0");
     return 0;
 }
 
@@ -268,9 +220,9 @@ static int mx_check_params(uint32_t flags, int kp_dim, bool want_pts, bool want_
 static int mx_check_batch_offsets(const int64_t *o1, const int64_t *o2, int n_pairs)
 {
     for (const int64_t *o : {o1, o2}) {
-        if (!o || o[0] < 0) return mx_einval("offsets must be given and start at >= 0");
-        for (int p = 0; p < n_pairs; p++) if (o[p + 1] < o[p]) return mx_einval("offsets must be non-decreasing");
-        if (o[n_pairs] - o[0] > 0x3fffffff) return mx_einval("too many descriptor rows in one batch");
+        if (!o || o[0] < 0) return mi_einval("offsets must be given and start at >= 0");
+        for (int p = 0; p < n_pairs; p++) if (o[p + 1] < o[p]) return mi_einval("offsets must be non-decreasing");
+        if (o[n_pairs] - o[0] > 0x3fffffff) return mi_einval("too many descriptor rows in one batch");
     }
     return 0;
 }
@@ -279,7 +231,7 @@ static int mx_check_batch_offsets(const int64_t *o1, const int64_t *o2, int n_pa
 static int mx_check_store_rows(uint32_t flags, int64_t end1, int64_t end2)
 {
     if ((flags & MI_DEGENSAC_CORR_STORE_ROWS) && (end1 > 0x7fffffff || end2 > 0x7fffffff))
-        return mx_einval("MI_DEGENSAC_CORR_STORE_ROWS: the stores' rows do not fit int32 (offsets beyond 0x7fffffff)");
+        return mi_einval("MI_DEGENSAC_CORR_STORE_ROWS: the stores' rows do not fit int32 (offsets beyond 0x7fffffff)");
     return 0;
 }
 
@@ -298,14 +250,12 @@ static int mx_rows_dev(const std::vector<mt_pair_rows> &rows, int64_t n_out, con
     for (int p = 0; p < K; p++) out[p] = rows[p].out;
     out[K] = N;
     memcpy(tab.data() + a_rec, rows.data(), (size_t)K * sizeof(mt_pair_rows));
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
     const bool hsym = w.gk == MX_H_SYM && N > 0;
-    const size_t a_cnt = up(tab.size()), a_base = a_cnt + up((size_t)nb * 4), a_hp = a_base + up((size_t)nb * 4),
-                 a_all = a_hp + (hsym ? up((size_t)K * 18 * 8) : 0);
-    char *blk = nullptr;
-    MXCHK(hipMallocAsync((void **)&blk, a_all, s));
-    struct Free { char *p; hipStream_t s; ~Free() { (void)hipFreeAsync(p, s); } } fr{blk, s};
-    int rc = mt_batch_upload(device, s, tab.data(), tab.size(), blk); if (rc) return rc;
+    const size_t a_cnt = mi_up256(tab.size()), a_base = a_cnt + mi_up256((size_t)nb * 4), a_hp = a_base + mi_up256((size_t)nb * 4),
+                 a_all = a_hp + (hsym ? mi_up256((size_t)K * 18 * 8) : 0);
+    MiScratch scr; int rc = scr.alloc(a_all, s); if (rc) return rc;
+    char *blk = scr.p;
+    rc = mt_batch_upload(device, s, tab.data(), tab.size(), blk); if (rc) return rc;
     mx_args a;
     memset(&a, 0, sizeof a);
     a.out = (const int32_t *)blk; a.rec = (const mt_pair_rows *)(blk + a_rec); a.K = K; a.N = N;
@@ -318,14 +268,14 @@ static int mx_rows_dev(const std::vector<mt_pair_rows> &rows, int64_t n_out, con
     a.vec = ((((uintptr_t)d_rows) & 7u) == 0 ? MX_VEC_ROWS : 0) | ((((uintptr_t)d_pts) & 15u) == 0 ? MX_VEC_PTS : 0);
     if (nb > 0) {
         hipLaunchKernelGGL(mx_count_kernel, dim3(nb), dim3(256), 0, s, a, cnt);
-        MXCHK(hipGetLastError());
+        MICHK(hipGetLastError());
     }
     hipLaunchKernelGGL(mx_scan_kernel, dim3(1), dim3(MX_SCAN), 0, s, (const int32_t *)cnt, nb, base, d_total, a.out, K, N, d_corr_offsets);
-    MXCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     if (nb > 0) {
         if (hsym) {
             hipLaunchKernelGGL(mx_prepare_kernel, dim3((K + 255) / 256), dim3(256), 0, s, d_models, K, hprep);
-            MXCHK(hipGetLastError());
+            MICHK(hipGetLastError());
         }
         const dim3 grid(nb), block(256);
         switch (w.gk) {
@@ -335,7 +285,7 @@ static int mx_rows_dev(const std::vector<mt_pair_rows> &rows, int64_t n_out, con
         case MX_H_SYM: hipLaunchKernelGGL((mx_write_kernel<MX_H_SYM>), grid, block, 0, s, a); break;
         default: hipLaunchKernelGGL((mx_write_kernel<MX_NONE>), grid, block, 0, s, a); break;
         }
-        MXCHK(hipGetLastError());
+        MICHK(hipGetLastError());
     }
     return 0;
 }
@@ -346,13 +296,13 @@ static int mx_dev(const std::vector<mt_pair_rows> &rows, int n_pairs, int64_t n_
                   int64_t capacity, int device, hipStream_t s, int64_t *d_corr_offsets, int64_t *d_total, int32_t *d_rows, int32_t *d_entry, double *d_pts,
                   double *d_resid)
 {
-    if (!d_corr_offsets || !d_total) return mx_einval("NULL argument: d_corr_offsets and d_total are always written");
+    if (!d_corr_offsets || !d_total) return mi_einval("NULL argument: d_corr_offsets and d_total are always written");
     if (n_pairs > 0 && n_out > 0 && (!d_match || (capacity > 0 && !d_rows) || ((d_pts || d_resid) && (!d_kp1 || !d_kp2))))
-        return mx_einval("NULL argument");
-    MxDevGuard dg; int rc = dg.enter(device); if (rc) return rc;
+        return mi_einval("NULL argument");
+    MiDevGuard dg; int rc = dg.enter(device); if (rc) return rc;
     if (n_pairs == 0) {                                              /* total = 0 and corr_offsets[0] = 0, asynchronously */
-        MXCHK(hipMemsetAsync(d_total, 0, 8, s));
-        MXCHK(hipMemsetAsync(d_corr_offsets, 0, 8, s));
+        MICHK(hipMemsetAsync(d_total, 0, 8, s));
+        MICHK(hipMemsetAsync(d_corr_offsets, 0, 8, s));
         return 0;
     }
     const bool kp = d_pts || d_resid;
@@ -407,42 +357,28 @@ static int mx_host(const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t
                    double *resid)
 {
     const int K = (int)rows.size();
-    if (!corr_offsets || !total) return mx_einval("NULL argument: corr_offsets and total are always written");
+    if (!corr_offsets || !total) return mi_einval("NULL argument: corr_offsets and total are always written");
     if (K == 0) { *total = 0; corr_offsets[0] = 0; return 0; }
     const bool kp = pts || resid;
-    if (n_out > 0 && (!match || (capacity > 0 && !out_rows) || (kp && (!kp1 || !kp2)))) return mx_einval("NULL argument");
-    MxDevGuard dg; int rc = dg.enter(device); if (rc) return rc;
+    if (n_out > 0 && (!match || (capacity > 0 && !out_rows) || (kp && (!kp1 || !kp2)))) return mi_einval("NULL argument");
+    MiDevGuard dg; int rc = dg.enter(device); if (rc) return rc;
     const int64_t cap = std::min(capacity, n_out);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t a_keep = up((size_t)n_out * 4), a_k1 = a_keep + (keep ? up((size_t)n_out) : 0), a_k2 = a_k1 + (kp ? up((size_t)n1 * kd * 8) : 0),
-                 a_mo = a_k2 + (kp && !same ? up((size_t)n2 * kd * 8) : 0), a_co = a_mo + (resid ? up((size_t)K * 72) : 0),
-                 a_to = a_co + up((size_t)(K + 1) * 8), a_ro = a_to + 256, a_en = a_ro + up((size_t)cap * 8), a_pt = a_en + (entry ? up((size_t)cap * 4) : 0),
-                 a_re = a_pt + (pts ? up((size_t)cap * 32) : 0), a_all = a_re + (resid ? up((size_t)cap * 8) : 0);
-    char *D = nullptr;
-    struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
-    MXCHK(hipMalloc((void **)&D, a_all));
-    if (n_out > 0) MXCHK(hipMemcpy(D, match, (size_t)n_out * 4, hipMemcpyHostToDevice));
-    if (keep && n_out > 0) MXCHK(hipMemcpy(D + a_keep, keep, (size_t)n_out, hipMemcpyHostToDevice));
-    if (kp && n1 > 0) MXCHK(hipMemcpy(D + a_k1, kp1 + off1_0 * kd, (size_t)n1 * kd * 8, hipMemcpyHostToDevice));
-    if (kp && !same && n2 > 0) MXCHK(hipMemcpy(D + a_k2, kp2 + off2_0 * kd, (size_t)n2 * kd * 8, hipMemcpyHostToDevice));
-    if (resid) MXCHK(hipMemcpy(D + a_mo, models, (size_t)K * 72, hipMemcpyHostToDevice));
-    rc = mx_rows_dev(rows, n_out, (const int32_t *)D, keep ? (const uint8_t *)(D + a_keep) : nullptr, flags, off1_0, off2_0,
-                     kp ? (const double *)(D + a_k1) : nullptr, kp ? (const double *)(D + (same ? a_k1 : a_k2)) : nullptr, kd,
-                     resid ? (const double *)(D + a_mo) : nullptr, w, cap, device, nullptr, (int64_t *)(D + a_co), (int64_t *)(D + a_to),
-                     (int32_t *)(D + a_ro), entry ? (int32_t *)(D + a_en) : nullptr, pts ? (double *)(D + a_pt) : nullptr,
-                     resid ? (double *)(D + a_re) : nullptr);
+    MiStage st;
+    const int i_ma = st.in(match, (size_t)n_out * 4), i_ke = st.in(keep, (size_t)n_out), i_k1 = st.in(kp ? kp1 + off1_0 * kd : nullptr, (size_t)n1 * kd * 8),
+              i_k2 = same ? i_k1 : st.in(kp ? kp2 + off2_0 * kd : nullptr, (size_t)n2 * kd * 8), i_mo = st.in(resid ? models : nullptr, (size_t)K * 72),
+              o_co = st.out(corr_offsets, (size_t)(K + 1) * 8), o_to = st.out(total, 8), o_ro = st.late(out_rows, (size_t)cap * 8),
+              o_en = st.late(entry, (size_t)cap * 4), o_pt = st.late(pts, (size_t)cap * 32), o_re = st.late(resid, (size_t)cap * 8);
+    rc = st.upload(); if (rc) return rc;
+    rc = mx_rows_dev(rows, n_out, st.dev<int32_t>(i_ma), st.dev<uint8_t>(i_ke), flags, off1_0, off2_0, st.dev<double>(i_k1), st.dev<double>(i_k2), kd,
+                     st.dev<double>(i_mo), w, cap, device, nullptr, st.dev<int64_t>(o_co), st.dev<int64_t>(o_to), st.dev<int32_t>(o_ro),
+                     st.dev<int32_t>(o_en), st.dev<double>(o_pt), st.dev<double>(o_re));
     if (rc) return rc;
-    MXCHK(hipStreamSynchronize(nullptr));
-    MXCHK(hipMemcpy(corr_offsets, D + a_co, (size_t)(K + 1) * 8, hipMemcpyDeviceToHost));
-    MXCHK(hipMemcpy(total, D + a_to, 8, hipMemcpyDeviceToHost));
+    rc = st.finish(); if (rc) return rc;
     const size_t n = (size_t)std::min(*total, cap);
-    if (n > 0) {
-        MXCHK(hipMemcpy(out_rows, D + a_ro, n * 8, hipMemcpyDeviceToHost));
-        if (entry) MXCHK(hipMemcpy(entry, D + a_en, n * 4, hipMemcpyDeviceToHost));
-        if (pts) MXCHK(hipMemcpy(pts, D + a_pt, n * 32, hipMemcpyDeviceToHost));
-        if (resid) MXCHK(hipMemcpy(resid, D + a_re, n * 8, hipMemcpyDeviceToHost));
-    }
-    return 0;
+    rc = st.fetch(o_ro, n * 8); if (rc) return rc;
+    rc = st.fetch(o_en, n * 4); if (rc) return rc;
+    rc = st.fetch(o_pt, n * 32); if (rc) return rc;
+    return st.fetch(o_re, n * 8);
 }
 
 extern "C" int mi_degensac_correspondences_pairs(const int64_t *offsets1, int n_images1, const int64_t *offsets2, int n_images2, const int32_t *pairs,

@@ -109,7 +109,7 @@ int mt_batch_fginn_mark(const int32_t *idx, const mt_pair_rows *d_rows, int n_pa
 {
     if (n_pairs <= 0) return 0;
     hipLaunchKernelGGL(mf_mark_kernel, dim3(n_pairs), dim3(256), 0, s, idx, d_rows, kt, kd, rr, list, count);
-    MTCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     return 0;
 }
 
@@ -133,20 +133,18 @@ int mt_batch_fginn(int norm, int words, const void *dq, const void *dt, const do
     }
     const int qtiles = (int)((tab.size() * 4 - b_rows) / 32);
     int t_chunk, splits; mt_batch_split(qtiles, max_n2, device, &t_chunk, &splits);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t a_list = up(tab.size() * 4), a_cnt = a_list + up((size_t)n_rows * 4), a_part = a_cnt + up((size_t)K * 4),
+    const size_t a_list = mi_up256(tab.size() * 4), a_cnt = a_list + mi_up256((size_t)n_rows * 4), a_part = a_cnt + mi_up256((size_t)K * 4),
                  a_all = a_part + (splits > 1 ? (size_t)splits * n_rows * sizeof(mt_best) : 0);
-    char *buf = nullptr;
-    MTCHK(hipMallocAsync((void **)&buf, a_all, s));
-    struct Free { char *p; hipStream_t s; ~Free() { (void)hipFreeAsync(p, s); } } fr{buf, s};
-    int rc = mt_batch_upload(device, s, tab.data(), tab.size() * 4, buf); if (rc) return rc;
+    MiScratch scr; int rc = scr.alloc(a_all, s); if (rc) return rc;
+    char *buf = scr.p;
+    rc = mt_batch_upload(device, s, tab.data(), tab.size() * 4, buf); if (rc) return rc;
     const mt_pair_rows *d_rows = (const mt_pair_rows *)buf;
     const int4 *d_tiles = (const int4 *)(buf + b_rows);
     int32_t *list = (int32_t *)(buf + a_list), *cnt = (int32_t *)(buf + a_cnt);
     mt_best *part = splits > 1 ? (mt_best *)(buf + a_part) : nullptr;
     const double rr = r * r;
     hipLaunchKernelGGL(mf_mark_kernel, dim3(K), dim3(256), 0, s, idx, d_rows, kt, kd, rr, list, cnt);
-    MTCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     const dim3 grid(qtiles, splits), block(256);
 #define MF_RESCAN(N) do { if (ident) MF_RESCAN_(N, 1); else MF_RESCAN_(N, 2); } while (0)
 #define MF_RESCAN_(N, M) hipLaunchKernelGGL((mf_rescan_kernel<N, M>), grid, block, 0, s, (const uint32_t *)dq, (const uint32_t *)dt, words, d_tiles, list, \
@@ -154,11 +152,11 @@ int mt_batch_fginn(int norm, int words, const void *dq, const void *dt, const do
     if (norm == MI_DEGENSAC_NORM_L2) MF_RESCAN(0); else if (norm == MI_DEGENSAC_NORM_HAMMING) MF_RESCAN(1); else MF_RESCAN(2);
 #undef MF_RESCAN
 #undef MF_RESCAN_
-    MTCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     if (part) {
         hipLaunchKernelGGL(mf_merge_kernel, dim3(K), dim3(256), 0, s, part, splits, n_rows, norm != MI_DEGENSAC_NORM_HAMMING ? 1 : 0, d_rows, list, cnt, idx,
             dist);
-        MTCHK(hipGetLastError());
+        MICHK(hipGetLastError());
     }
     return 0;
 }
@@ -166,10 +164,10 @@ int mt_batch_fginn(int norm, int words, const void *dq, const void *dt, const do
 /* the checks the two 2-NN + FGINN entry points share beyond their layouts */
 static int mf_check(int norm, int dim, int n_pairs, int kp_dim, double spatial_th)
 {
-    if (n_pairs < 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
+    if (n_pairs < 0) return mi_einval("bad argument");
     int rc = mt_check_norm(norm, dim); if (rc) return rc;
-    if (kp_dim != 2 && kp_dim != 6) { snprintf(mt_err, sizeof mt_err, "keypoint rows must be [n,2] or [n,6]"); return MI_DEGENSAC_EINVAL; }
-    if (const char *e = mt_spatial_th_error(spatial_th)) { snprintf(mt_err, sizeof mt_err, "%s", e); return MI_DEGENSAC_EINVAL; }
+    if (kp_dim != 2 && kp_dim != 6) return mi_einval("keypoint rows must be [n,2] or [n,6]");
+    if (const char *e = mt_spatial_th_error(spatial_th)) return mi_einval(e);
     return 0;
 }
 
@@ -180,12 +178,10 @@ extern "C" int mi_degensac_match_fginn_knn2_batch_dev(int norm, const void *d_de
     int rc = mf_check(norm, dim, n_pairs, kp_dim, spatial_th); if (rc) return rc;
     const int words = mt_row_words(norm, dim);
     if (n_pairs == 0) return 0;
-    if (!mt_check_offsets(offsets1_host, n_pairs) || !mt_check_offsets(offsets2_host, n_pairs)) {
-        snprintf(mt_err, sizeof mt_err, "offsets must be non-negative and non-decreasing"); return MI_DEGENSAC_EINVAL; }
+    if (!mt_check_offsets(offsets1_host, n_pairs) || !mt_check_offsets(offsets2_host, n_pairs)) return mi_einval("offsets must be non-negative and non-decreasing");
     const int64_t n1 = offsets1_host[n_pairs] - offsets1_host[0], n2 = offsets2_host[n_pairs] - offsets2_host[0];
-    if ((n1 > 0 && (!d_desc1 || !d_idx || !d_dist)) || (n2 > 0 && (!d_desc2 || !d_kp2))) { snprintf(mt_err, sizeof mt_err, "NULL argument");
-        return MI_DEGENSAC_EINVAL; }
-    MtDevGuard g; rc = g.enter(device); if (rc) return rc;
+    if ((n1 > 0 && (!d_desc1 || !d_idx || !d_dist)) || (n2 > 0 && (!d_desc2 || !d_kp2))) return mi_einval("NULL argument");
+    MiDevGuard g; rc = g.enter(device); if (rc) return rc;
     std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
     mt_ragged_rows(offsets1_host, offsets2_host, n_pairs, o1, o2, rows);
     const uint32_t *q1 = (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words, *q2 = (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words;
@@ -207,9 +203,8 @@ extern "C" int mi_degensac_match_fginn_knn2_pairs_dev(int norm, const void *d_de
     std::vector<mt_pair_rows> rows(n_pairs);
     int64_t n_out, n_back;
     rc = mt_pairs_layout(offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, rows.data(), &n_out, &n_back); if (rc) return rc;
-    if ((n_out > 0 && (!d_desc1 || !d_idx || !d_dist)) || (n_out > 0 && n_back > 0 && (!d_desc2 || !d_kp2))) { snprintf(mt_err, sizeof mt_err, "NULL argument");
-        return MI_DEGENSAC_EINVAL; }
-    MtDevGuard g; rc = g.enter(device); if (rc) return rc;
+    if ((n_out > 0 && (!d_desc1 || !d_idx || !d_dist)) || (n_out > 0 && n_back > 0 && (!d_desc2 || !d_kp2))) return mi_einval("NULL argument");
+    MiDevGuard g; rc = g.enter(device); if (rc) return rc;
     const uint32_t *q1 = (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words, *q2 = (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words;
     rc = mt_batch_knn2(norm, words, q1, q2, rows.data(), n_pairs, (int)n_out, 0, device, (hipStream_t)stream, d_idx, d_dist); if (rc) return rc;
     return mt_batch_fginn(norm, words, q1, q2, d_kp2 + (size_t)offsets2_host[0] * kp_dim, kp_dim, rows.data(), n_pairs, (int)n_out, spatial_th, device,

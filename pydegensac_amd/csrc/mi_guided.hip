@@ -36,6 +36,7 @@
 #include <vector>
 #include "../../include/mi_degensac.h"
 #include "mi_match_batch.h"
+#include "mi_host.h"
 #include "dg_geom.h"
 
 #define MG_W    4                 /* waves per workgroup */
@@ -300,33 +301,14 @@ __global__ __launch_bounds__(256) void mg_decide_kernel(const int32_t *idx, cons
 }
 
 /* ---- host side ---------------------------------------------------------------------------------------------------------- */
-#define MGCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { char b_[256]; snprintf(b_, sizeof b_, "%s failed: %s", #x, hipGetErrorString(e_)); \
-    mt_set_error(b_); (void)hipGetLastError(); return MI_DEGENSAC_EHIP; } } while (0)
-static int mg_einval(const char *msg) { mt_set_error(msg); return MI_DEGENSAC_EINVAL; }
-
-struct MgDevGuard {
-    int prev = -1; bool armed = false;
-    int enter(int device)
-    {
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n == 0) { (void)hipGetLastError(); mt_set_error("no HIP device: this library has no CPU path");
-            return MI_DEGENSAC_ENODEV; }
-        if (device < 0 || device >= n) { mt_set_error("device index out of range"); return MI_DEGENSAC_ENODEV; }
-        if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-        if (prev != device) { MGCHK(hipSetDevice(device)); armed = prev >= 0; }
-        return 0;
-    }
-    ~MgDevGuard() { if (armed) (void)hipSetDevice(prev); }
-};
-
 int mt_guided_gate(int homography, int error_type, double px_th, mt_gate *g)
 {
-    if (!(px_th >= 0)) return mg_einval("px_th must be >= 0 (not NaN)");
+    if (!(px_th >= 0)) return mi_einval("px_th must be >= 0 (not NaN)");
     if (!homography) {
-        if (error_type != 0 && error_type != 1) return mg_einval("error_type must be 0 or 1 for the fundamental matrix");
+        if (error_type != 0 && error_type != 1) return mi_einval("error_type must be 0 or 1 for the fundamental matrix");
         g->gk = error_type; g->hk = 0; g->th = px_th * px_th;
     } else {
-        if (error_type < 0 || error_type > 4) return mg_einval("error_type must be 0..4 for the homography");
+        if (error_type < 0 || error_type > 4) return mi_einval("error_type must be 0..4 for the homography");
         g->gk = error_type == 0 ? MG_H_SAMPSON : MG_H_SYM; g->hk = error_type;
         g->th = (error_type == 2 || error_type == 4) ? px_th : px_th * px_th;
     }
@@ -367,7 +349,7 @@ int mt_batch_guided_knn2(int norm, int words, const void *dq, const void *dt, co
     const int64_t tiles = mg_tile_table(rows, n_pairs, swap, tab, &a_rows);
     const size_t bytes = tab.size();
     char *d_tab = nullptr;
-    MGCHK(hipMallocAsync((void **)&d_tab, bytes, s));
+    MICHK(hipMallocAsync((void **)&d_tab, bytes, s));
     int rc = mt_batch_upload(device, s, tab.data(), bytes, d_tab);
     if (rc) { (void)hipFreeAsync(d_tab, s); return rc; }
     const dim3 grid((unsigned)tiles), block(256);
@@ -377,7 +359,7 @@ int mt_batch_guided_knn2(int norm, int words, const void *dq, const void *dt, co
 #undef MG_LAUNCH
     const hipError_t le = hipGetLastError();
     (void)hipFreeAsync(d_tab, s);
-    MGCHK(le);
+    MICHK(le);
     return 0;
 }
 
@@ -389,12 +371,10 @@ int mt_batch_guided_fginn(int norm, int words, const void *dq, const void *dt, c
     if (n_pairs <= 0 || n_rows == 0) return 0;
     std::vector<char> tab; size_t a_rows;
     const int64_t tiles = mg_tile_table(rows, n_pairs, 0, tab, &a_rows);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t a_list = up(tab.size()), a_cnt = a_list + up((size_t)n_rows * 4), a_all = a_cnt + up((size_t)n_pairs * 4);
-    char *blk = nullptr;
-    MGCHK(hipMallocAsync((void **)&blk, a_all, s));
-    struct Free { char *p; hipStream_t s; ~Free() { (void)hipFreeAsync(p, s); } } fr{blk, s};
-    int rc = mt_batch_upload(device, s, tab.data(), tab.size(), blk); if (rc) return rc;
+    const size_t a_list = mi_up256(tab.size()), a_cnt = a_list + mi_up256((size_t)n_rows * 4), a_all = a_cnt + mi_up256((size_t)n_pairs * 4);
+    MiScratch scr; int rc = scr.alloc(a_all, s); if (rc) return rc;
+    char *blk = scr.p;
+    rc = mt_batch_upload(device, s, tab.data(), tab.size(), blk); if (rc) return rc;
     const mt_pair_rows *d_rows = (const mt_pair_rows *)(blk + a_rows);
     int32_t *list = (int32_t *)(blk + a_list), *cnt = (int32_t *)(blk + a_cnt);
     const double rr = r * r;
@@ -404,7 +384,7 @@ int mt_batch_guided_fginn(int norm, int words, const void *dq, const void *dt, c
         (const int32_t *)blk, d_rows, n_pairs, d_models, g.hk, g.th, g.tb, g.screen, list, cnt, rr, idx, dist)
     MG_DISPATCH(norm, g.gk, MG_LAUNCH)
 #undef MG_LAUNCH
-    MGCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     return 0;
 }
 
@@ -413,7 +393,7 @@ int mt_batch_guided_decide(const int32_t *d_idx, const float *d_dist, const int3
 {
     if (n_pairs <= 0) return 0;
     hipLaunchKernelGGL(mg_decide_kernel, dim3(n_pairs), dim3(256), 0, s, d_idx, d_dist, d_off1, d_off2, rule, d_back, d_bdist, d_match, d_count);
-    MGCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     return 0;
 }
 
@@ -421,20 +401,20 @@ int mt_batch_guided_decide(const int32_t *d_idx, const float *d_dist, const int3
 /* norm, dim, keypoint width and the gate: what both layouts refuse before they look at offsets or a list */
 static int mg_check_gate(int norm, int dim, int kp_dim, const mi_degensac_guide_params *gp, mt_gate *g)
 {
-    if (!mt_norm_known(norm) || dim <= 0) return mg_einval("bad norm or descriptor dim");
-    if (const char *e = mt_norm_dim_error(norm, dim)) return mg_einval(e);
-    if (kp_dim != 2 && kp_dim != 6) return mg_einval("keypoint rows must be [n,2] or [n,6]");
-    if (!gp) return mg_einval("guide params are NULL");
-    if (gp->struct_size != 0 && gp->struct_size < (int32_t)sizeof(mi_degensac_guide_params)) return mg_einval("guide params: struct_size too small");
-    if (gp->homography != 0 && gp->homography != 1) return mg_einval("homography must be 0 or 1");
+    if (!mt_norm_known(norm) || dim <= 0) return mi_einval("bad norm or descriptor dim");
+    if (const char *e = mt_norm_dim_error(norm, dim)) return mi_einval(e);
+    if (kp_dim != 2 && kp_dim != 6) return mi_einval("keypoint rows must be [n,2] or [n,6]");
+    if (!gp) return mi_einval("guide params are NULL");
+    if (gp->struct_size != 0 && gp->struct_size < (int32_t)sizeof(mi_degensac_guide_params)) return mi_einval("guide params: struct_size too small");
+    if (gp->homography != 0 && gp->homography != 1) return mi_einval("homography must be 0 or 1");
     return mt_guided_gate(gp->homography, gp->error_type, gp->px_th, g);
 }
 
 /* the ratio and the decision rule (mt_decide_rule); honour: the entry point reads second_nn, which NO_RATIO / BACK_RATIO exclude */
 static int mg_check_ratio(const mi_degensac_match_params *mp, int honour, mt_rule *rule)
 {
-    if (!mp) return mg_einval("match params are NULL");
-    if (const char *e = mt_decide_rule(mp, honour, rule)) return mg_einval(e);
+    if (!mp) return mi_einval("match params are NULL");
+    if (const char *e = mt_decide_rule(mp, honour, rule)) return mi_einval(e);
     return 0;
 }
 
@@ -445,13 +425,13 @@ static int mg_check_second(const mi_degensac_match_params *mp, int honour, mg_se
 {
     sn->fginn = 0; sn->r = 0.0;
     if (!honour) return 0;
-    if (const char *e = mt_second_nn(mp, &sn->fginn, &sn->r)) return mg_einval(e);
+    if (const char *e = mt_second_nn(mp, &sn->fginn, &sn->r)) return mi_einval(e);
     return 0;
 }
 /* the radius of the guided_fginn_knn2 entry points */
 static int mg_check_radius(double spatial_th)
 {
-    if (const char *e = mt_spatial_th_error(spatial_th)) return mg_einval(e);
+    if (const char *e = mt_spatial_th_error(spatial_th)) return mi_einval(e);
     return 0;
 }
 
@@ -459,12 +439,12 @@ static int mg_check_radius(double spatial_th)
 static int mg_check(int norm, int dim, int kp_dim, const mi_degensac_guide_params *gp, const int64_t *o1, const int64_t *o2, int n_pairs, mt_gate *g)
 {
     int rc = mg_check_gate(norm, dim, kp_dim, gp, g); if (rc) return rc;
-    if (n_pairs < 0) return mg_einval("n_pairs < 0");
+    if (n_pairs < 0) return mi_einval("n_pairs < 0");
     if (n_pairs == 0) return 0;
     for (const int64_t *o : {o1, o2}) {
-        if (!o || o[0] < 0) return mg_einval("offsets must be given and start at >= 0");
-        for (int p = 0; p < n_pairs; p++) if (o[p + 1] < o[p]) return mg_einval("offsets must be non-decreasing");
-        if (o[n_pairs] - o[0] > 0x3fffffff) return mg_einval("too many descriptor rows in one batch");
+        if (!o || o[0] < 0) return mi_einval("offsets must be given and start at >= 0");
+        for (int p = 0; p < n_pairs; p++) if (o[p + 1] < o[p]) return mi_einval("offsets must be non-decreasing");
+        if (o[n_pairs] - o[0] > 0x3fffffff) return mi_einval("too many descriptor rows in one batch");
     }
     return 0;
 }
@@ -475,7 +455,7 @@ static int mg_check_pairs(int norm, int dim, int kp_dim, const mi_degensac_guide
 {
     *n_out = *n_back = 0;
     int rc = mg_check_gate(norm, dim, kp_dim, gp, g); if (rc) return rc;
-    if (n_pairs < 0) return mg_einval("n_pairs < 0");
+    if (n_pairs < 0) return mi_einval("n_pairs < 0");
     if (n_pairs == 0) return 0;
     rows.resize(n_pairs);
     return mt_pairs_layout(off1, m1, off2, m2, pairs, n_pairs, rows.data(), n_out, n_back);
@@ -492,8 +472,8 @@ static int mg_knn2_batch_dev(int fginn, double r, int norm, const void *d_desc1,
     if (fginn) { rc = mg_check_radius(r); if (rc) return rc; }
     if (n_pairs == 0) return 0;
     const int64_t n1 = offsets1_host[n_pairs] - offsets1_host[0], n2 = offsets2_host[n_pairs] - offsets2_host[0];
-    if (!d_models || (n1 > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist)) || (n2 > 0 && (!d_desc2 || !d_kp2))) return mg_einval("NULL argument");
-    MgDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+    if (!d_models || (n1 > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist)) || (n2 > 0 && (!d_desc2 || !d_kp2))) return mi_einval("NULL argument");
+    MiDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     const int words = mg_words(norm, dim);
     std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
     mt_ragged_rows(offsets1_host, offsets2_host, n_pairs, o1, o2, rows);
@@ -538,16 +518,14 @@ static int mg_rows_dev(const mi_degensac_match_params *mp, const mt_rule &rule, 
     for (int p = 0; p < K; p++) { o32[p] = rows[p].out; o32[K + 1 + p] = rows[p].back; }
     o32[K] = (int32_t)n_out; o32[2 * K + 1] = (int32_t)n_back;
     /* one stream-ordered block: tables | reverse idx | reverse dist | counts (when the caller gives none on the device) */
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t a_bidx = up(o32.size() * 4), a_bdist = a_bidx + (mutual ? up((size_t)n_back * 8) : 0),
-                 a_cnt = a_bdist + (mutual ? up((size_t)n_back * 8) : 0), a_all = a_cnt + up((size_t)K * 4);
-    char *blk = nullptr;
-    MGCHK(hipMallocAsync((void **)&blk, a_all, s));
-    struct Free { char *p; hipStream_t s; ~Free() { (void)hipFreeAsync(p, s); } } fr{blk, s};
+    const size_t a_bidx = mi_up256(o32.size() * 4), a_bdist = a_bidx + (mutual ? mi_up256((size_t)n_back * 8) : 0),
+                 a_cnt = a_bdist + (mutual ? mi_up256((size_t)n_back * 8) : 0), a_all = a_cnt + mi_up256((size_t)K * 4);
+    MiScratch scr; int rc = scr.alloc(a_all, s); if (rc) return rc;
+    char *blk = scr.p;
     const int32_t *d_out = (const int32_t *)blk, *d_back = d_out + (K + 1);
     int32_t *bidx = mutual ? (int32_t *)(blk + a_bidx) : nullptr, *cnt = d_counts ? d_counts : (int32_t *)(blk + a_cnt);
     float *bdist = (float *)(blk + a_bdist);
-    int rc = mt_batch_upload(device, s, o32.data(), o32.size() * 4, blk); if (rc) return rc;
+    rc = mt_batch_upload(device, s, o32.data(), o32.size() * 4, blk); if (rc) return rc;
     rc = mt_batch_guided_knn2(mp->norm, words, q1, q2, kp1, kp2, kd, rows.data(), K, (int)n_out, d_models, g, 0, device, s, idx, dist); if (rc) return rc;
     /* FGINN inside the gate judges the forward search only: the reverse search and the mutual check stay the plain ones (slot 0) */
     if (sn.fginn) { rc = mt_batch_guided_fginn(mp->norm, words, q1, q2, kp1, kp2, kd, rows.data(), K, (int)n_out, d_models, g, sn.r, device, s, idx, dist);
@@ -556,8 +534,8 @@ static int mg_rows_dev(const mi_degensac_match_params *mp, const mt_rule &rule, 
         if (rc) return rc; }
     rc = mt_batch_guided_decide(idx, dist, d_out, d_back, K, rule, bidx, mutual ? bdist : nullptr, s, match, cnt); if (rc) return rc;
     if (h_counts) {                                                  /* the only synchronisation, and only when asked for */
-        MGCHK(hipMemcpyAsync(h_counts, cnt, (size_t)K * 4, hipMemcpyDeviceToHost, s));
-        MGCHK(hipStreamSynchronize(s));
+        MICHK(hipMemcpyAsync(h_counts, cnt, (size_t)K * 4, hipMemcpyDeviceToHost, s));
+        MICHK(hipStreamSynchronize(s));
     }
     return 0;
 }
@@ -571,8 +549,8 @@ static int mg_batch_dev(int honour, const mi_degensac_match_params *mp, const vo
     mg_second sn; rc = mg_check_second(mp, honour, &sn); if (rc) return rc;
     if (K == 0) return 0;
     const int64_t n1 = off1[K] - off1[0], n2 = off2[K] - off2[0];
-    if (!d_models || (n1 > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist || !d_match)) || (n2 > 0 && (!d_desc2 || !d_kp2))) return mg_einval("NULL argument");
-    MgDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+    if (!d_models || (n1 > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist || !d_match)) || (n2 > 0 && (!d_desc2 || !d_kp2))) return mi_einval("NULL argument");
+    MiDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     const int words = mg_words(mp->norm, mp->dim);
     std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
     mt_ragged_rows(off1, off2, K, o1, o2, rows);
@@ -609,32 +587,20 @@ static int mg_rows_host(const mi_degensac_match_params *mp, const mt_rule &rule,
                         int32_t *counts)
 {
     const int K = (int)rows.size();
-    MgDevGuard dg; int rc = dg.enter(device); if (rc) return rc;
+    MiDevGuard dg; int rc = dg.enter(device); if (rc) return rc;
     const int64_t n1 = off1[m1] - off1[0], n2 = off2[m2] - off2[0];
     const size_t row = mt_row_bytes(mp->norm, mp->dim);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t a_d2 = up(n1 * row), a_k1 = a_d2 + (same ? 0 : up(n2 * row)), a_k2 = a_k1 + up((size_t)n1 * kd * 8),
-                 a_mo = a_k2 + (same ? 0 : up((size_t)n2 * kd * 8)), a_ix = a_mo + up((size_t)K * 72), a_ds = a_ix + up((size_t)n_out * 8),
-                 a_ma = a_ds + up((size_t)n_out * 8), a_all = a_ma + up((size_t)n_out * 4);
-    char *D = nullptr;
-    struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
-    MGCHK(hipMalloc((void **)&D, a_all));
-    MGCHK(hipMemcpy(D, (const char *)desc1 + off1[0] * row, n1 * row, hipMemcpyHostToDevice));
-    MGCHK(hipMemcpy(D + a_k1, kp1 + off1[0] * kd, (size_t)n1 * kd * 8, hipMemcpyHostToDevice));
-    if (!same) {
-        MGCHK(hipMemcpy(D + a_d2, (const char *)desc2 + off2[0] * row, n2 * row, hipMemcpyHostToDevice));
-        MGCHK(hipMemcpy(D + a_k2, kp2 + off2[0] * kd, (size_t)n2 * kd * 8, hipMemcpyHostToDevice));
-    }
-    MGCHK(hipMemcpy(D + a_mo, models, (size_t)K * 72, hipMemcpyHostToDevice));
+    MiStage st;
+    const int i_d1 = st.in((const char *)desc1 + off1[0] * row, n1 * row), i_k1 = st.in(kp1 + off1[0] * kd, (size_t)n1 * kd * 8),
+              i_d2 = same ? i_d1 : st.in((const char *)desc2 + off2[0] * row, n2 * row), i_k2 = same ? i_k1 : st.in(kp2 + off2[0] * kd, (size_t)n2 * kd * 8),
+              i_mo = st.in(models, (size_t)K * 72), o_ix = st.out(idx, (size_t)n_out * 8), o_ds = st.out(dist, (size_t)n_out * 8),
+              o_ma = st.out(match, (size_t)n_out * 4);
+    rc = st.upload(); if (rc) return rc;
     std::vector<int32_t> cnt(K);
-    rc = mg_rows_dev(mp, rule, (const uint32_t *)D, (const uint32_t *)(same ? D : D + a_d2), (const double *)(D + a_k1), (const double *)(D + (same ? a_k1 : a_k2)),
-                     kd, rows, n_out, n_back, (const double *)(D + a_mo), g, sn, device, nullptr, (int32_t *)(D + a_ix), (float *)(D + a_ds),
-                     (int32_t *)(D + a_ma), nullptr, cnt.data());
+    rc = mg_rows_dev(mp, rule, st.dev<uint32_t>(i_d1), st.dev<uint32_t>(i_d2), st.dev<double>(i_k1), st.dev<double>(i_k2), kd, rows, n_out, n_back,
+                     st.dev<double>(i_mo), g, sn, device, nullptr, st.dev<int32_t>(o_ix), st.dev<float>(o_ds), st.dev<int32_t>(o_ma), nullptr, cnt.data());
     if (rc) return rc;
-    MGCHK(hipStreamSynchronize(nullptr));
-    MGCHK(hipMemcpy(idx, D + a_ix, (size_t)n_out * 8, hipMemcpyDeviceToHost));
-    MGCHK(hipMemcpy(dist, D + a_ds, (size_t)n_out * 8, hipMemcpyDeviceToHost));
-    MGCHK(hipMemcpy(match, D + a_ma, (size_t)n_out * 4, hipMemcpyDeviceToHost));
+    rc = st.finish(); if (rc) return rc;
     if (counts) memcpy(counts, cnt.data(), (size_t)K * 4);
     return 0;
 }
@@ -650,7 +616,7 @@ static int mg_batch_host(int honour, const mi_degensac_match_params *mp, const v
     mg_second sn; rc = mg_check_second(mp, honour, &sn); if (rc) return rc;
     const int K = n_pairs;
     if (K == 0) return 0;
-    if (!desc1 || !desc2 || !kp1 || !kp2 || !models || !idx || !dist || !match) return mg_einval("NULL argument");
+    if (!desc1 || !desc2 || !kp1 || !kp2 || !models || !idx || !dist || !match) return mi_einval("NULL argument");
     std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
     mt_ragged_rows(offsets1, offsets2, K, o1, o2, rows);
     return mg_rows_host(mp, rule, desc1, desc2, offsets1, K, offsets2, K, kp1, kp2, kp_dim, false, rows, o1[K], o2[K], models, g, sn, device,
@@ -685,8 +651,8 @@ static int mg_knn2_pairs_dev(int fginn, double r, int norm, const void *d_desc1,
     if (rc) return rc;
     if (fginn) { rc = mg_check_radius(r); if (rc) return rc; }
     if (n_pairs == 0) return 0;
-    if (!d_models || (n_out > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist)) || (n_back > 0 && (!d_desc2 || !d_kp2))) return mg_einval("NULL argument");
-    MgDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+    if (!d_models || (n_out > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist)) || (n_back > 0 && (!d_desc2 || !d_kp2))) return mi_einval("NULL argument");
+    MiDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     const int words = mg_words(norm, dim);
     const uint32_t *q1 = (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words, *q2 = (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words;
     const double *k1 = d_kp1 + (size_t)offsets1_host[0] * kp_dim, *k2 = d_kp2 + (size_t)offsets2_host[0] * kp_dim;
@@ -726,8 +692,8 @@ static int mg_pairs_dev(int honour, const mi_degensac_match_params *mp, const vo
     mg_second sn; rc = mg_check_second(mp, honour, &sn); if (rc) return rc;
     if (n_pairs == 0) return 0;
     if (!d_models || (n_out > 0 && (!d_desc1 || !d_kp1 || !d_idx || !d_dist || !d_match)) || (n_back > 0 && (!d_desc2 || !d_kp2)))
-        return mg_einval("NULL argument");
-    MgDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+        return mi_einval("NULL argument");
+    MiDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     const int words = mg_words(mp->norm, mp->dim);
     return mg_rows_dev(mp, rule, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words, (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words,
                        d_kp1 + (size_t)offsets1_host[0] * kp_dim, d_kp2 + (size_t)offsets2_host[0] * kp_dim, kp_dim, rows, n_out, n_back, d_models, g, sn,
@@ -745,7 +711,7 @@ static int mg_pairs_host(int honour, const mi_degensac_match_params *mp, const v
     if (rc) return rc;
     mg_second sn; rc = mg_check_second(mp, honour, &sn); if (rc) return rc;
     if (n_pairs == 0) return 0;
-    if (!desc1 || !desc2 || !kp1 || !kp2 || !models || !idx || !dist || !match) return mg_einval("NULL argument");
+    if (!desc1 || !desc2 || !kp1 || !kp2 || !models || !idx || !dist || !match) return mi_einval("NULL argument");
     const bool same = desc1 == desc2 && kp1 == kp2 && n_images1 == n_images2 && !memcmp(offsets1, offsets2, ((size_t)n_images1 + 1) * 8);
     return mg_rows_host(mp, rule, desc1, desc2, offsets1, n_images1, offsets2, n_images2, kp1, kp2, kp_dim, same, rows, n_out, n_back, models, g, sn, device,
                         idx, dist, match, counts);

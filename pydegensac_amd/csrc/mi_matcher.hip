@@ -27,6 +27,7 @@
 #include <vector>
 #include "../../include/mi_degensac.h"
 #include "mi_match_batch.h"
+#include "mi_host.h"
 
 #define MT_Q   64            /* queries per workgroup */
 #define MT_T   64            /* train rows per LDS tile */
@@ -361,30 +362,13 @@ __global__ __launch_bounds__(256) void mt_scatter_fh_kernel(const int32_t *e_of_
 static thread_local char mt_err[256] = "";
 extern "C" const char *mi_degensac_match_last_error(void) { return mt_err; }
 void mt_set_error(const char *msg) { snprintf(mt_err, sizeof mt_err, "%s", msg); }
-#define MTCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { snprintf(mt_err, sizeof mt_err, "%s failed: %s", #x, hipGetErrorString(e_)); \
-    (void)hipGetLastError(); return MI_DEGENSAC_EHIP; } } while (0)
-
-struct MtDevGuard {
-    int prev = -1; bool armed = false;
-    int enter(int device)
-    {
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n == 0) { (void)hipGetLastError();
-            snprintf(mt_err, sizeof mt_err, "no HIP device: this library has no CPU path"); return MI_DEGENSAC_ENODEV; }
-        if (device < 0 || device >= n) { snprintf(mt_err, sizeof mt_err, "device index out of range"); return MI_DEGENSAC_ENODEV; }
-        if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-        if (prev != device) { MTCHK(hipSetDevice(device)); armed = prev >= 0; }
-        return 0;
-    }
-    ~MtDevGuard() { if (armed) (void)hipSetDevice(prev); }
-};
 
 /* norm and dim of a dense entry point (refused before the library looks for a device); uint8 rows are passed padded to whole
  * 32-bit words */
 static int mt_check_norm(int norm, int dim)
 {
-    if (!mt_norm_known(norm) || dim <= 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
-    if (const char *e = mt_norm_dim_error(norm, dim)) { snprintf(mt_err, sizeof mt_err, "%s", e); return MI_DEGENSAC_EINVAL; }
+    if (!mt_norm_known(norm) || dim <= 0) return mi_einval("bad argument");
+    if (const char *e = mt_norm_dim_error(norm, dim)) return mi_einval(e);
     return 0;
 }
 
@@ -399,10 +383,10 @@ static int mt_check_norm(int norm, int dim)
 extern "C" int mi_degensac_match_knn2_dev(int norm, const void *d_desc1, int n1, const void *d_desc2, int n2, int dim, int device,
                                           void *stream, int32_t *d_idx, float *d_dist)
 {
-    if (n1 < 0 || n2 < 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
+    if (n1 < 0 || n2 < 0) return mi_einval("bad argument");
     int rc = mt_check_norm(norm, dim); if (rc) return rc;
     const int words = mt_row_words(norm, dim);
-    MtDevGuard g; rc = g.enter(device); if (rc) return rc;
+    MiDevGuard g; rc = g.enter(device); if (rc) return rc;
     if (n1 == 0) return 0;
     /* train splits: enough workgroups to cover the device about twice, never less than one 64-row tile per split */
     const int qtiles = (n1 + MT_Q - 1) / MT_Q, ttiles = n2 > 0 ? (n2 + MT_T - 1) / MT_T : 1;
@@ -411,7 +395,7 @@ extern "C" int mi_degensac_match_knn2_dev(int norm, const void *d_desc1, int n1,
     const int t_chunk = ((ttiles + splits - 1) / splits) * MT_T;
     splits = n2 > 0 ? (n2 + t_chunk - 1) / t_chunk : 1;
     mt_best *part = nullptr;
-    if (splits > 1) MTCHK(hipMallocAsync((void **)&part, (size_t)splits * n1 * sizeof(mt_best), (hipStream_t)stream));
+    if (splits > 1) MICHK(hipMallocAsync((void **)&part, (size_t)splits * n1 * sizeof(mt_best), (hipStream_t)stream));
     const dim3 grid(qtiles, splits), block(256);
     MT_LAUNCH_NORM(mt_knn2_kernel, norm, words, grid, block, (hipStream_t)stream, (const uint32_t *)d_desc1, n1, (const uint32_t *)d_desc2, n2, words,
         n2 > 0 ? t_chunk : MT_T, d_idx, d_dist, part);
@@ -422,27 +406,27 @@ extern "C" int mi_degensac_match_knn2_dev(int norm, const void *d_desc1, int n1,
         le = hipGetLastError();
     }
     if (part) (void)hipFreeAsync(part, (hipStream_t)stream);
-    MTCHK(le);
+    MICHK(le);
     return 0;
 }
 
 extern "C" int mi_degensac_match_filter_dev(const int32_t *d_idx, const float *d_dist, int n1, float ratio, const int32_t *d_back_idx_or_null,
                                             int device, void *stream, uint8_t *d_keep)
 {
-    if (n1 < 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
-    MtDevGuard g; int rc = g.enter(device); if (rc) return rc;
+    if (n1 < 0) return mi_einval("bad argument");
+    MiDevGuard g; int rc = g.enter(device); if (rc) return rc;
     if (n1 == 0) return 0;
     hipLaunchKernelGGL(mt_filter_kernel, dim3((n1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_idx, d_dist, n1, mt_rule{ratio, 0, 0.f},
         d_back_idx_or_null, (const float *)nullptr, d_keep);
-    MTCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     return 0;
 }
 
 /* the rule of a dense call: no keypoints here, so an FGINN request can only be refused */
 static int mt_dense_rule(const mi_degensac_match_params *mp, int honour_second_nn, mt_rule *rule)
 {
-    if (!mp) { snprintf(mt_err, sizeof mt_err, "match params are NULL"); return MI_DEGENSAC_EINVAL; }
-    if (const char *e = mt_decide_rule(mp, honour_second_nn, rule)) { snprintf(mt_err, sizeof mt_err, "%s", e); return MI_DEGENSAC_EINVAL; }
+    if (!mp) return mi_einval("match params are NULL");
+    if (const char *e = mt_decide_rule(mp, honour_second_nn, rule)) return mi_einval(e);
     return 0;
 }
 
@@ -450,17 +434,16 @@ extern "C" int mi_degensac_match_decide_dev(const mi_degensac_match_params *mp, 
                                             const int32_t *d_back_idx, const float *d_back_dist, int device, void *stream, uint8_t *d_keep)
 {
     mt_rule rule; int rc = mt_dense_rule(mp, 0, &rule); if (rc) return rc;
-    if (n1 < 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
+    if (n1 < 0) return mi_einval("bad argument");
     const bool mutual = mp->mutual != 0;
-    if (n1 > 0 && (!d_idx || !d_dist || !d_keep)) { snprintf(mt_err, sizeof mt_err, "NULL argument"); return MI_DEGENSAC_EINVAL; }
-    if (n1 > 0 && mutual && !d_back_idx) { snprintf(mt_err, sizeof mt_err, "mutual needs d_back_idx, the reverse search's idx"); return MI_DEGENSAC_EINVAL; }
-    if (n1 > 0 && (rule.flags & MI_DEGENSAC_DECIDE_BACK_RATIO) && !d_back_dist) {
-        snprintf(mt_err, sizeof mt_err, "BACK_RATIO needs d_back_dist, the reverse search's dist"); return MI_DEGENSAC_EINVAL; }
-    MtDevGuard g; rc = g.enter(device); if (rc) return rc;
+    if (n1 > 0 && (!d_idx || !d_dist || !d_keep)) return mi_einval("NULL argument");
+    if (n1 > 0 && mutual && !d_back_idx) return mi_einval("mutual needs d_back_idx, the reverse search's idx");
+    if (n1 > 0 && (rule.flags & MI_DEGENSAC_DECIDE_BACK_RATIO) && !d_back_dist) return mi_einval("BACK_RATIO needs d_back_dist, the reverse search's dist");
+    MiDevGuard g; rc = g.enter(device); if (rc) return rc;
     if (n1 == 0) return 0;
     hipLaunchKernelGGL(mt_filter_kernel, dim3((n1 + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_idx, d_dist, n1, rule,
         mutual ? d_back_idx : (const int32_t *)nullptr, mutual ? d_back_dist : (const float *)nullptr, d_keep);
-    MTCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     return 0;
 }
 
@@ -480,66 +463,66 @@ extern "C" int mi_degensac_match_ex(const mi_degensac_match_params *mp, const vo
 {
     mt_rule rule; int rc = mt_dense_rule(mp, 1, &rule); if (rc) return rc;
     int fginn; double r;
-    if (const char *e = mt_second_nn(mp, &fginn, &r)) { snprintf(mt_err, sizeof mt_err, "%s", e); return MI_DEGENSAC_EINVAL; }
-    if (fginn) { snprintf(mt_err, sizeof mt_err, "the FGINN rule (second_nn = 1) is not part of the dense call: it has no keypoints"); return MI_DEGENSAC_EINVAL; }
+    if (const char *e = mt_second_nn(mp, &fginn, &r)) return mi_einval(e);
+    if (fginn) return mi_einval("the FGINN rule (second_nn = 1) is not part of the dense call: it has no keypoints");
     return mt_match_host(mp->norm, desc1, n1, desc2, n2, mp->dim, mp->ratio, mp->mutual, &rule, device, idx, dist, keep);
 }
 
 static int mt_match_host(int norm, const void *desc1, int n1, const void *desc2, int n2, int dim, float ratio, int mutual, const mt_rule *rule,
                          int device, int32_t *idx, float *dist, uint8_t *keep)
 {
-    if (!desc1 || !desc2 || !idx || !dist || n1 < 0 || n2 < 0 || dim <= 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
+    if (!desc1 || !desc2 || !idx || !dist || n1 < 0 || n2 < 0 || dim <= 0) return mi_einval("bad argument");
     int rc = mt_check_norm(norm, dim); if (rc) return rc;
-    MtDevGuard g; rc = g.enter(device); if (rc) return rc;
+    MiDevGuard g; rc = g.enter(device); if (rc) return rc;
     if (n1 == 0) return 0;
     const size_t b1 = (size_t)n1 * mt_row_bytes(norm, dim), b2 = (size_t)n2 * mt_row_bytes(norm, dim);
     char *d1 = nullptr, *d2 = nullptr; int32_t *di = nullptr, *dbi = nullptr; float *dd = nullptr, *dbd = nullptr; uint8_t *dk = nullptr;
     struct Free { char *&a, *&b; int32_t *&c, *&d; float *&e, *&f; uint8_t *&g;
                   ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(d); (void)hipFree(e); (void)hipFree(f); (void)hipFree(g);
                       } } fr{d1, d2, di, dbi, dd, dbd, dk};
-    MTCHK(hipMalloc((void **)&d1, b1 ? b1 : 4)); MTCHK(hipMalloc((void **)&d2, b2 ? b2 : 4));
-    MTCHK(hipMalloc((void **)&di, (size_t)n1 * 8)); MTCHK(hipMalloc((void **)&dd, (size_t)n1 * 8));
-    MTCHK(hipMemcpy(d1, desc1, b1, hipMemcpyHostToDevice)); MTCHK(hipMemcpy(d2, desc2, b2, hipMemcpyHostToDevice));
+    MICHK(hipMalloc((void **)&d1, b1 ? b1 : 4)); MICHK(hipMalloc((void **)&d2, b2 ? b2 : 4));
+    MICHK(hipMalloc((void **)&di, (size_t)n1 * 8)); MICHK(hipMalloc((void **)&dd, (size_t)n1 * 8));
+    MICHK(hipMemcpy(d1, desc1, b1, hipMemcpyHostToDevice)); MICHK(hipMemcpy(d2, desc2, b2, hipMemcpyHostToDevice));
     rc = mi_degensac_match_knn2_dev(norm, d1, n1, d2, n2, dim, device, nullptr, di, dd); if (rc) return rc;
     if (keep) {
-        MTCHK(hipMalloc((void **)&dk, (size_t)n1));
+        MICHK(hipMalloc((void **)&dk, (size_t)n1));
         if (mutual && n2 > 0) {
-            MTCHK(hipMalloc((void **)&dbi, (size_t)n2 * 8)); MTCHK(hipMalloc((void **)&dbd, (size_t)n2 * 8));
+            MICHK(hipMalloc((void **)&dbi, (size_t)n2 * 8)); MICHK(hipMalloc((void **)&dbd, (size_t)n2 * 8));
             rc = mi_degensac_match_knn2_dev(norm, d2, n2, d1, n1, dim, device, nullptr, dbi, dbd); if (rc) return rc;
         }
         if (!rule) { rc = mi_degensac_match_filter_dev(di, dd, n1, ratio, dbi, device, nullptr, dk); if (rc) return rc; }
         else {
             hipLaunchKernelGGL(mt_filter_kernel, dim3((n1 + 255) / 256), dim3(256), 0, (hipStream_t) nullptr, di, dd, n1, *rule, dbi, dbd, dk);
-            MTCHK(hipGetLastError());
+            MICHK(hipGetLastError());
         }
     }
-    MTCHK(hipDeviceSynchronize());
-    MTCHK(hipMemcpy(idx, di, (size_t)n1 * 8, hipMemcpyDeviceToHost)); MTCHK(hipMemcpy(dist, dd, (size_t)n1 * 8, hipMemcpyDeviceToHost));
-    if (keep) MTCHK(hipMemcpy(keep, dk, (size_t)n1, hipMemcpyDeviceToHost));
+    MICHK(hipDeviceSynchronize());
+    MICHK(hipMemcpy(idx, di, (size_t)n1 * 8, hipMemcpyDeviceToHost)); MICHK(hipMemcpy(dist, dd, (size_t)n1 * 8, hipMemcpyDeviceToHost));
+    if (keep) MICHK(hipMemcpy(keep, dk, (size_t)n1, hipMemcpyDeviceToHost));
     return 0;
 }
 
 extern "C" int mi_degensac_kpts_to_xyA_dev(const float *d_kpts, int n, int device, void *stream, double *d_out)
 {
-    if (n < 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
-    MtDevGuard g; int rc = g.enter(device); if (rc) return rc;
+    if (n < 0) return mi_einval("bad argument");
+    MiDevGuard g; int rc = g.enter(device); if (rc) return rc;
     if (n == 0) return 0;
     hipLaunchKernelGGL(mt_kpts_to_xyA_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_kpts, n, d_out);
-    MTCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     return 0;
 }
 extern "C" int mi_degensac_kpts_to_xyA(const float *kpts, int n, int device, double *out)
 {
-    if (!kpts || !out || n < 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
-    MtDevGuard g; int rc = g.enter(device); if (rc) return rc;
+    if (!kpts || !out || n < 0) return mi_einval("bad argument");
+    MiDevGuard g; int rc = g.enter(device); if (rc) return rc;
     if (n == 0) return 0;
     float *dk = nullptr; double *dout = nullptr;
     struct Free { float *&a; double *&b; ~Free() { (void)hipFree(a); (void)hipFree(b); } } fr{dk, dout};
-    MTCHK(hipMalloc((void **)&dk, (size_t)n * 16)); MTCHK(hipMalloc((void **)&dout, (size_t)n * 48));
-    MTCHK(hipMemcpy(dk, kpts, (size_t)n * 16, hipMemcpyHostToDevice));
+    MICHK(hipMalloc((void **)&dk, (size_t)n * 16)); MICHK(hipMalloc((void **)&dout, (size_t)n * 48));
+    MICHK(hipMemcpy(dk, kpts, (size_t)n * 16, hipMemcpyHostToDevice));
     rc = mi_degensac_kpts_to_xyA_dev(dk, n, device, nullptr, dout); if (rc) return rc;
-    MTCHK(hipDeviceSynchronize());
-    MTCHK(hipMemcpy(out, dout, (size_t)n * 48, hipMemcpyDeviceToHost));
+    MICHK(hipDeviceSynchronize());
+    MICHK(hipMemcpy(out, dout, (size_t)n * 48, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -574,16 +557,16 @@ int mt_batch_upload(int device, hipStream_t s, const void *h, size_t bytes, void
         (void)hipGetLastError();
         if (!busy) busy = &e;
     }
-    if (!b && busy && mine >= 16) { MTCHK(hipEventSynchronize(busy->ev)); b = busy; }
+    if (!b && busy && mine >= 16) { MICHK(hipEventSynchronize(busy->ev)); b = busy; }
     if (!b) {
         MtPin n{device, nullptr, bytes < ((size_t)1 << 16) ? ((size_t)1 << 16) : bytes + bytes / 4, nullptr};
-        MTCHK(hipHostMalloc((void **)&n.h, n.cap, hipHostMallocDefault));
-        if (hipEventCreateWithFlags(&n.ev, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(n.h); MTCHK(hipErrorOutOfMemory); }
+        MICHK(hipHostMalloc((void **)&n.h, n.cap, hipHostMallocDefault));
+        if (hipEventCreateWithFlags(&n.ev, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(n.h); MICHK(hipErrorOutOfMemory); }
         mt_pins.push_back(n); b = &mt_pins.back();
     }
     memcpy(b->h, h, bytes);
-    MTCHK(hipMemcpyAsync(d, b->h, bytes, hipMemcpyHostToDevice, s));
-    MTCHK(hipEventRecord(b->ev, s));
+    MICHK(hipMemcpyAsync(d, b->h, bytes, hipMemcpyHostToDevice, s));
+    MICHK(hipEventRecord(b->ev, s));
     return 0;
 }
 
@@ -616,7 +599,7 @@ int mt_batch_knn2(int norm, int words, const void *dq, const void *dt, const mt_
     int t_chunk, splits; mt_batch_split(qtiles, max_n2, device, &t_chunk, &splits);
     const size_t b_tiles = ((size_t)qtiles * sizeof(mt_ptile) + 255) / 256 * 256, b_part = splits > 1 ? (size_t)splits * n_rows * sizeof(mt_best) : 0;
     char *buf = nullptr;
-    MTCHK(hipMallocAsync((void **)&buf, b_tiles + b_part, s));
+    MICHK(hipMallocAsync((void **)&buf, b_tiles + b_part, s));
     int rc = mt_batch_upload(device, s, tiles.data(), (size_t)qtiles * sizeof(mt_ptile), buf);
     if (rc) { (void)hipFreeAsync(buf, s); return rc; }
     mt_best *part = splits > 1 ? (mt_best *)(buf + b_tiles) : nullptr;
@@ -630,7 +613,7 @@ int mt_batch_knn2(int norm, int words, const void *dq, const void *dt, const mt_
         le = hipGetLastError();
     }
     (void)hipFreeAsync(buf, s);
-    MTCHK(le);
+    MICHK(le);
     return 0;
 }
 
@@ -640,7 +623,7 @@ int mt_batch_filter_rank(const int32_t *d_idx, const float *d_dist, const int32_
     if (n_pairs <= 0) return 0;
     hipLaunchKernelGGL(mt_filter_rank_kernel, dim3(n_pairs), dim3(256), 0, s, d_idx, d_dist, d_off1, d_off2, rule, d_back, d_bdist, d_keep, d_rank,
         d_count);
-    MTCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     return 0;
 }
 
@@ -651,7 +634,7 @@ int mt_batch_gather(int n_eligible, const int32_t *d_pair_of_e, const int64_t *d
     if (n_eligible <= 0) return 0;
     hipLaunchKernelGGL(mt_gather_kernel, dim3(n_eligible), dim3(256), 0, s, d_pair_of_e, d_est_off, d_out, d_q1, d_t2, d_keep, d_rank, d_idx, d_kp1,
         d_kp2, kp_dim, d_seeds, d_pts1, d_pts2, d_seeds_e);
-    MTCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     return 0;
 }
 
@@ -662,7 +645,7 @@ int mt_batch_scatter(int n_pairs, const int32_t *d_e_of_p, const int64_t *d_est_
     if (n_pairs <= 0) return 0;
     hipLaunchKernelGGL(mt_scatter_kernel, dim3(n_pairs), dim3(256), 0, s, d_e_of_p, d_est_off, d_off1, d_keep, d_rank, d_idx, d_model_e, d_stats_e,
         d_mask_e, d_model, d_stats, d_match, d_inlier);
-    MTCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     return 0;
 }
 
@@ -674,7 +657,7 @@ int mt_batch_scatter_fh(int n_pairs, const mt_half &f, const mt_half &h, const i
     hipLaunchKernelGGL(mt_scatter_fh_kernel, dim3(n_pairs), dim3(256), 0, s, f.e_of_p, f.est_off, h.e_of_p, h.est_off, d_off1, d_keep, d_rank, d_idx,
         f.model_e, f.stats_e, f.mask_e, h.model_e, h.stats_e, h.mask_e, d_model_f, d_stats_f, d_model_h, d_stats_h, d_match, d_inlier_f, d_inlier_h,
         d_summary);
-    MTCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     return 0;
 }
 
@@ -690,13 +673,12 @@ extern "C" int mi_degensac_match_knn2_batch_dev(int norm, const void *d_desc1, c
                                                 const int64_t *offsets2_host, int n_pairs, int dim, int device, void *stream, int32_t *d_idx,
                                                 float *d_dist)
 {
-    if (n_pairs < 0) { snprintf(mt_err, sizeof mt_err, "bad argument"); return MI_DEGENSAC_EINVAL; }
+    if (n_pairs < 0) return mi_einval("bad argument");
     int rc = mt_check_norm(norm, dim); if (rc) return rc;
     const int words = mt_row_words(norm, dim);
     if (n_pairs == 0) return 0;
-    if (!mt_check_offsets(offsets1_host, n_pairs) || !mt_check_offsets(offsets2_host, n_pairs)) {
-        snprintf(mt_err, sizeof mt_err, "offsets must be non-negative and non-decreasing"); return MI_DEGENSAC_EINVAL; }
-    MtDevGuard g; rc = g.enter(device); if (rc) return rc;
+    if (!mt_check_offsets(offsets1_host, n_pairs) || !mt_check_offsets(offsets2_host, n_pairs)) return mi_einval("offsets must be non-negative and non-decreasing");
+    MiDevGuard g; rc = g.enter(device); if (rc) return rc;
     std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
     mt_ragged_rows(offsets1_host, offsets2_host, n_pairs, o1, o2, rows);
     return mt_batch_knn2(norm, words, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words,
@@ -709,11 +691,11 @@ int mt_pairs_layout(const int64_t *off1, int m1, const int64_t *off2, int m2, co
                     int64_t *n_out, int64_t *n_back)
 {
     *n_out = *n_back = 0;
-    if (n_pairs < 0 || m1 < 0 || m2 < 0) { snprintf(mt_err, sizeof mt_err, "n_pairs, n_images1 and n_images2 must be >= 0"); return MI_DEGENSAC_EINVAL; }
+    if (n_pairs < 0 || m1 < 0 || m2 < 0) return mi_einval("n_pairs, n_images1 and n_images2 must be >= 0");
     if (n_pairs == 0) return 0;
-    if (!pairs) { snprintf(mt_err, sizeof mt_err, "the pair list is NULL"); return MI_DEGENSAC_EINVAL; }
-    if (!mt_check_offsets(off1, m1) || !mt_check_offsets(off2, m2)) {
-        snprintf(mt_err, sizeof mt_err, "store offsets must be non-negative and non-decreasing, with at most 0x3fffffff rows in a store"); return MI_DEGENSAC_EINVAL; }
+    if (!pairs) return mi_einval("the pair list is NULL");
+    if (!mt_check_offsets(off1, m1) || !mt_check_offsets(off2, m2))
+        return mi_einval("store offsets must be non-negative and non-decreasing, with at most 0x3fffffff rows in a store");
     int64_t o = 0, b = 0;
     for (int p = 0; p < n_pairs; p++) {
         const int i = pairs[2 * p], j = pairs[2 * p + 1];
@@ -722,9 +704,8 @@ int mt_pairs_layout(const int64_t *off1, int m1, const int64_t *off2, int m2, co
         const int64_t nq = off1[i + 1] - off1[i], nt = off2[j + 1] - off2[j];
         rows[p] = mt_pair_rows{(int32_t)o, (int32_t)(off1[i] - off1[0]), (int32_t)nq, (int32_t)(off2[j] - off2[0]), (int32_t)nt, (int32_t)b};
         o += nq; b += nt;
-        if (o > 0x3fffffff || b > 0x3fffffff) {
-            snprintf(mt_err, sizeof mt_err, "too many rows in one pair list: the output rows and the reverse-search rows are limited to 0x3fffffff each");
-            return MI_DEGENSAC_EINVAL; }
+        if (o > 0x3fffffff || b > 0x3fffffff)
+            return mi_einval("too many rows in one pair list: the output rows and the reverse-search rows are limited to 0x3fffffff each");
     }
     *n_out = o; *n_back = b;
     return 0;
@@ -734,15 +715,15 @@ extern "C" int mi_degensac_match_knn2_pairs_dev(int norm, const void *d_desc1, c
                                                 const int64_t *offsets2_host, int n_images2, const int32_t *pairs_host, int n_pairs, int dim,
                                                 int device, void *stream, int32_t *d_idx, float *d_dist)
 {
-    if (n_pairs < 0) { snprintf(mt_err, sizeof mt_err, "n_pairs < 0"); return MI_DEGENSAC_EINVAL; }
+    if (n_pairs < 0) return mi_einval("n_pairs < 0");
     int rc = mt_check_norm(norm, dim); if (rc) return rc;
     const int words = mt_row_words(norm, dim);
     if (n_pairs == 0) return 0;
     std::vector<mt_pair_rows> rows(n_pairs);
     int64_t n_out, n_back;
     rc = mt_pairs_layout(offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, rows.data(), &n_out, &n_back); if (rc) return rc;
-    if ((n_out > 0 && (!d_desc1 || !d_idx || !d_dist)) || (n_out > 0 && n_back > 0 && !d_desc2)) { snprintf(mt_err, sizeof mt_err, "NULL argument"); return MI_DEGENSAC_EINVAL; }
-    MtDevGuard g; rc = g.enter(device); if (rc) return rc;
+    if ((n_out > 0 && (!d_desc1 || !d_idx || !d_dist)) || (n_out > 0 && n_back > 0 && !d_desc2)) return mi_einval("NULL argument");
+    MiDevGuard g; rc = g.enter(device); if (rc) return rc;
     return mt_batch_knn2(norm, words, (const uint32_t *)d_desc1 + (size_t)offsets1_host[0] * words,
                          (const uint32_t *)d_desc2 + (size_t)offsets2_host[0] * words,
                          rows.data(), n_pairs, (int)n_out, 0, device, (hipStream_t)stream, d_idx, d_dist);

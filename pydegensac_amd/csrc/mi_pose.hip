@@ -21,13 +21,14 @@
 #include <algorithm>
 #include "../../include/mi_degensac.h"
 #include "mi_match_batch.h"
+#include "mi_host.h"
+#include "mi_dev_util.h"
 
 #define PS_T     256                      /* threads per workgroup */
 #define PS_NW    (PS_T / 64)
 #define PS_LOADS 4                        /* rows per thread and step */
 #define PS_STEP  (PS_LOADS * PS_T)        /* rows per workgroup and step */
 #define PS_GRID  256                      /* cap on the grid: further entries by the grid stride */
-#define PS_DBL_MAX 1.7976931348623157e308
 #define PS_SWEEPS 6                       /* one-sided Jacobi sweeps of the 3 x 3 decomposition */
 
 struct ps_args {
@@ -55,13 +56,11 @@ struct ps_shared {
     int cnt[PS_NW][5];
 };
 
-__device__ __forceinline__ bool ps_finite(double x) { return fabs(x) <= PS_DBL_MAX; }
-
 /* the candidates of F under the two cameras of S->cam into S->cand / S->c2 (one thread); returns the status */
 __device__ __forceinline__ int ps_decompose(ps_shared *S, const double *F)
 {
     const double fx1 = S->cam[0], fy1 = S->cam[1], cx1 = S->cam[2], cy1 = S->cam[3], fx2 = S->cam[4], fy2 = S->cam[5], cx2 = S->cam[6], cy2 = S->cam[7];
-    if (!(ps_finite(fx1) && ps_finite(fy1) && ps_finite(fx2) && ps_finite(fy2)) || fx1 == 0.0 || fy1 == 0.0 || fx2 == 0.0 || fy2 == 0.0)
+    if (!(mi_finite(fx1) && mi_finite(fy1) && mi_finite(fx2) && mi_finite(fy2)) || fx1 == 0.0 || fy1 == 0.0 || fx2 == 0.0 || fy2 == 0.0)
         return MI_DEGENSAC_POSE_BAD_CAMERA;
     double G[9], E[9];
 #pragma unroll
@@ -76,7 +75,7 @@ __device__ __forceinline__ int ps_decompose(ps_shared *S, const double *F)
     }
     double m = 0.0; bool fin = true;
 #pragma unroll
-    for (int i = 0; i < 9; i++) { const double x = fabs(E[i]); fin = fin && x <= PS_DBL_MAX; if (x > m) m = x; }
+    for (int i = 0; i < 9; i++) { const double x = fabs(E[i]); fin = fin && x <= MI_DBL_MAX; if (x > m) m = x; }
     if (!fin || !(m > 0.0)) return MI_DEGENSAC_POSE_BAD_MODEL;
     double A[9];
 #pragma unroll
@@ -120,13 +119,13 @@ __device__ __forceinline__ int ps_decompose(ps_shared *S, const double *F)
             Ra[3 * r + c] = (u2[r] * v0[c] - u1[r] * v1[c]) + t[r] * v2[c];
             Rb[3 * r + c] = (u1[r] * v1[c] - u2[r] * v0[c]) + t[r] * v2[c];
         }
-    fin = ps_finite(t[0]) && ps_finite(t[1]) && ps_finite(t[2]);
+    fin = mi_finite(t[0]) && mi_finite(t[1]) && mi_finite(t[2]);
 #pragma unroll
     for (int h = 0; h < 2; h++) {
         double *R = h ? Rb : Ra;
         const double det = (R[0] * (R[4] * R[8] - R[5] * R[7]) - R[1] * (R[3] * R[8] - R[5] * R[6])) + R[2] * (R[3] * R[7] - R[4] * R[6]);
 #pragma unroll
-        for (int i = 0; i < 9; i++) { if (det < 0.0) R[i] = -R[i]; fin = fin && ps_finite(R[i]); }
+        for (int i = 0; i < 9; i++) { if (det < 0.0) R[i] = -R[i]; fin = fin && mi_finite(R[i]); }
     }
     if (!fin) return MI_DEGENSAC_POSE_BAD_MODEL;
 #pragma unroll
@@ -298,40 +297,21 @@ __global__ __launch_bounds__(PS_T) void ps_pose_kernel(ps_args a)
 }
 
 /* ---- host side ---------------------------------------------------------------------------------------------------------- */
-#define PSCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { char b_[256]; snprintf(b_, sizeof b_, "%s failed: %s", #x, hipGetErrorString(e_)); \
-    mt_set_error(b_); (void)hipGetLastError(); return MI_DEGENSAC_EHIP; } } while (0)
-static int ps_einval(const char *msg) { mt_set_error(msg); return MI_DEGENSAC_EINVAL; }
-
-struct PsDevGuard {
-    int prev = -1; bool armed = false;
-    int enter(int device)
-    {
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n == 0) { (void)hipGetLastError(); mt_set_error("no HIP device: this library has no CPU path");
-            return MI_DEGENSAC_ENODEV; }
-        if (device < 0 || device >= n) { mt_set_error("device index out of range"); return MI_DEGENSAC_ENODEV; }
-        if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-        if (prev != device) { PSCHK(hipSetDevice(device)); armed = prev >= 0; }
-        return 0;
-    }
-    ~PsDevGuard() { if (armed) (void)hipSetDevice(prev); }
-};
-
 extern "C" int mi_degensac_pose_tile(int which) { return which == 0 ? PS_STEP : which == 1 ? PS_GRID : -1; }
 
 /* the refusals of include/mi_degensac.h, in that order; needs no device */
 static int ps_check(const void *pts, const void *off, const void *F, const void *cams, int n_cams, int K, int64_t cap, double cos_min, const void *pose,
                     const void *front, const void *info)
 {
-    if (K < 0) return ps_einval("n_entries < 0");
-    if (cap < 0) return ps_einval("cap < 0");
-    if (cap > 0x3fffffff) return ps_einval("too many rows in one list (cap > 0x3fffffff)");
-    if (n_cams < 0) return ps_einval("n_cams < 0");
-    if (!(cos_min >= -1.0 && cos_min <= 1.0)) return ps_einval("cos_min should lie in [-1, 1]");
-    if (!off) return ps_einval("NULL argument: corr_offsets");
-    if (K > 0 && (!F || !cams)) return ps_einval("NULL argument: F and cams");
-    if (K > 0 && (!pose || !info)) return ps_einval("NULL argument: pose and info");
-    if (cap > 0 && (!pts || !front)) return ps_einval("NULL argument: pts and front");
+    if (K < 0) return mi_einval("n_entries < 0");
+    if (cap < 0) return mi_einval("cap < 0");
+    if (cap > 0x3fffffff) return mi_einval("too many rows in one list (cap > 0x3fffffff)");
+    if (n_cams < 0) return mi_einval("n_cams < 0");
+    if (!(cos_min >= -1.0 && cos_min <= 1.0)) return mi_einval("cos_min should lie in [-1, 1]");
+    if (!off) return mi_einval("NULL argument: corr_offsets");
+    if (K > 0 && (!F || !cams)) return mi_einval("NULL argument: F and cams");
+    if (K > 0 && (!pose || !info)) return mi_einval("NULL argument: pose and info");
+    if (cap > 0 && (!pts || !front)) return mi_einval("NULL argument: pts and front");
     return 0;
 }
 
@@ -342,13 +322,13 @@ extern "C" int mi_degensac_pose_lists_dev(const double *d_pts, const int64_t *d_
 {
     int rc = ps_check(d_pts, d_corr_offsets, d_F, d_cams, n_cams, n_entries, cap, cos_min, d_pose, d_front, d_info); if (rc) return rc;
     if (n_entries == 0 && cap == 0) return 0;
-    PsDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+    MiDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (cap > 0) {                                                    /* positions that no entry owns, and rows that are not used, keep 0 / NaN */
-        PSCHK(hipMemsetAsync(d_front, 0, (size_t)cap, s));
-        if (d_X) PSCHK(hipMemsetAsync(d_X, 0xff, (size_t)cap * 24, s));              /* all bits set: a NaN */
-        if (d_depth) PSCHK(hipMemsetAsync(d_depth, 0xff, (size_t)cap * 16, s));
-        if (d_cosang) PSCHK(hipMemsetAsync(d_cosang, 0xff, (size_t)cap * 8, s));
+        MICHK(hipMemsetAsync(d_front, 0, (size_t)cap, s));
+        if (d_X) MICHK(hipMemsetAsync(d_X, 0xff, (size_t)cap * 24, s));              /* all bits set: a NaN */
+        if (d_depth) MICHK(hipMemsetAsync(d_depth, 0xff, (size_t)cap * 16, s));
+        if (d_cosang) MICHK(hipMemsetAsync(d_cosang, 0xff, (size_t)cap * 8, s));
     }
     if (n_entries == 0) return 0;
     ps_args a;
@@ -358,7 +338,7 @@ extern "C" int mi_degensac_pose_lists_dev(const double *d_pts, const int64_t *d_
     a.K = n_entries; a.n_cams = n_cams; a.cap = cap; a.cos_min = cos_min;
     const dim3 grid((unsigned)std::min(n_entries, PS_GRID)), block(PS_T);
     hipLaunchKernelGGL(ps_pose_kernel, grid, block, 0, s, a);
-    PSCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     return 0;
 }
 
@@ -368,28 +348,18 @@ extern "C" int mi_degensac_pose_lists(const double *pts, const int64_t *corr_off
 {
     int rc = ps_check(pts, corr_offsets, F, cams, n_cams, n_entries, cap, cos_min, pose, front, info); if (rc) return rc;
     if (n_entries == 0 && cap == 0) return 0;
-    PsDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+    MiDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     const size_t K = (size_t)n_entries, C = (size_t)cap, NC = (size_t)n_cams;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    /* inputs: pts, off, keep, F, cams, idx; outputs: pose, front, info, X, depth, cosang, cand, cand_front */
-    const size_t sz[14] = {C * 32, (K + 1) * 8, C, K * 72, NC * 32, K * 8, K * 96, C, K * 20, C * 24, C * 16, C * 8, K * 384, K * 16};
-    size_t at[15]; at[0] = 0;
-    for (int i = 0; i < 14; i++) at[i + 1] = at[i] + up(sz[i]);
-    char *D = nullptr;
-    struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
-    PSCHK(hipMalloc((void **)&D, at[14] + 256));
-    const void *in[6] = {pts, corr_offsets, keep, F, cams, cam_idx};
-    for (int i = 0; i < 6; i++)
-        if (in[i] && sz[i]) PSCHK(hipMemcpy(D + at[i], in[i], sz[i], hipMemcpyHostToDevice));
-    void *out[8] = {pose, front, info, X, depth, cosang, cand, cand_front};
-    auto dv = [&](int i, const void *h) { return h ? (void *)(D + at[i]) : nullptr; };
-    rc = mi_degensac_pose_lists_dev((const double *)D, (const int64_t *)(D + at[1]), (const uint8_t *)dv(2, keep), (const double *)(D + at[3]),
-                                    (const double *)(D + at[4]), n_cams, (const int32_t *)dv(5, cam_idx), n_entries, cap, cos_min, device, nullptr,
-                                    (double *)(D + at[6]), (uint8_t *)(D + at[7]), (int32_t *)(D + at[8]), (double *)dv(9, X), (double *)dv(10, depth),
-                                    (double *)dv(11, cosang), (double *)dv(12, cand), (int32_t *)dv(13, cand_front));
+    MiStage st;
+    const int i_pts = st.in(pts, C * 32), i_off = st.in(corr_offsets, (K + 1) * 8), i_keep = st.in(keep, C), i_F = st.in(F, K * 72),
+              i_cams = st.in(cams, NC * 32), i_idx = st.in(cam_idx, K * 8), o_pose = st.out(pose, K * 96), o_front = st.out(front, C),
+              o_info = st.out(info, K * 20), o_X = st.out(X, C * 24), o_depth = st.out(depth, C * 16), o_cos = st.out(cosang, C * 8),
+              o_cand = st.out(cand, K * 384), o_cf = st.out(cand_front, K * 16);
+    rc = st.upload(); if (rc) return rc;
+    rc = mi_degensac_pose_lists_dev(st.dev<double>(i_pts), st.dev<int64_t>(i_off), st.dev<uint8_t>(i_keep), st.dev<double>(i_F), st.dev<double>(i_cams),
+                                    n_cams, st.dev<int32_t>(i_idx), n_entries, cap, cos_min, device, nullptr, st.dev<double>(o_pose),
+                                    st.dev<uint8_t>(o_front), st.dev<int32_t>(o_info), st.dev<double>(o_X), st.dev<double>(o_depth),
+                                    st.dev<double>(o_cos), st.dev<double>(o_cand), st.dev<int32_t>(o_cf));
     if (rc) return rc;
-    PSCHK(hipStreamSynchronize(nullptr));
-    for (int i = 0; i < 8; i++)
-        if (out[i] && sz[6 + i]) PSCHK(hipMemcpy(out[i], D + at[6 + i], sz[6 + i], hipMemcpyDeviceToHost));
-    return 0;
+    return st.finish();
 }

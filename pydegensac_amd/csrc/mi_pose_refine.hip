@@ -20,13 +20,14 @@
 #include <algorithm>
 #include "../../include/mi_degensac.h"
 #include "mi_match_batch.h"
+#include "mi_host.h"
+#include "mi_dev_util.h"
 
 #define PR_T     256                      /* threads per workgroup */
 #define PR_NW    (PR_T / 64)
 #define PR_LOADS 4                        /* rows per thread and step */
 #define PR_STEP  (PR_LOADS * PR_T)        /* rows per workgroup and step */
 #define PR_GRID  256                      /* cap on the grid: further entries by the grid stride */
-#define PR_DBL_MAX 1.7976931348623157e308
 #define PR_NS    21                       /* sums of a pass: cost, g[5], A[15] */
 #define PR_RUNNING (-1)
 
@@ -58,9 +59,6 @@ struct pr_shared {
     int cnt[PR_NW];
     int status, go, trials, accepted;
 };
-
-__device__ __forceinline__ bool pr_finite(double x) { return fabs(x) <= PR_DBL_MAX; }
-__device__ __forceinline__ double pr_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 /* column j of X = cross(x, column j of R) */
 __device__ __forceinline__ void pr_cross_mat(const double *x, const double *R, double *X)
@@ -323,18 +321,18 @@ __global__ __launch_bounds__(PR_T) void pr_refine_kernel(pr_args a)
                     for (int i = 0; i < 4; i++) { cm[i] = a.cams[4 * (size_t)i1 + i]; cm[4 + i] = a.cams[4 * (size_t)i2 + i]; }
 #pragma unroll
                     for (int i = 0; i < 8; i++) S.cam[i] = cm[i];
-                    if (pr_finite(cm[0]) && pr_finite(cm[1]) && pr_finite(cm[4]) && pr_finite(cm[5]) && cm[0] != 0.0 && cm[1] != 0.0 && cm[4] != 0.0 &&
+                    if (mi_finite(cm[0]) && mi_finite(cm[1]) && mi_finite(cm[4]) && mi_finite(cm[5]) && cm[0] != 0.0 && cm[1] != 0.0 && cm[4] != 0.0 &&
                         cm[5] != 0.0) {
                         bool fin = true;
 #pragma unroll
-                        for (int i = 0; i < 12; i++) fin = fin && pr_finite(S.tri[i]);
+                        for (int i = 0; i < 12; i++) fin = fin && mi_finite(S.tri[i]);
                         const double tt = (S.tri[9] * S.tri[9] + S.tri[10] * S.tri[10]) + S.tri[11] * S.tri[11];
                         st = MI_DEGENSAC_REFINE_BAD_POSE;
                         if (fin && tt > 0.0) { st = PR_RUNNING; pr_model(&S, S.tri); }
                     }
                 }
             }
-            S.status = st; S.trials = 0; S.accepted = 0; S.lambda = 1e-3; S.cost0 = pr_nan(); S.go = 0;
+            S.status = st; S.trials = 0; S.accepted = 0; S.lambda = 1e-3; S.cost0 = mi_nan(); S.go = 0;
         }
         __syncthreads();
         int used = 0;
@@ -347,7 +345,7 @@ __global__ __launch_bounds__(PR_T) void pr_refine_kernel(pr_args a)
 #pragma unroll
                 for (int i = 0; i < 18; i++) S.cur[i] = S.tri[i];
                 if (used < 5) S.status = MI_DEGENSAC_REFINE_SHORT;
-                else if (!pr_finite(c0)) S.status = MI_DEGENSAC_REFINE_NOT_FINITE;
+                else if (!mi_finite(c0)) S.status = MI_DEGENSAC_REFINE_NOT_FINITE;
                 else {
 #pragma unroll
                     for (int k = 0; k < PR_NS; k++) S.sum[k] = pr_sum(&S, k);
@@ -387,7 +385,7 @@ __global__ __launch_bounds__(PR_T) void pr_refine_kernel(pr_args a)
         if (tid < 12) a.pose_out[12 * (size_t)p + tid] = status == MI_DEGENSAC_REFINE_BAD_POSE ? 0.0 : posed ? S.cur[tid] : mine;
         if (a.F && tid < 9) a.F[9 * (size_t)p + tid] = posed ? S.Fm[tid] : 0.0;
         if (tid == 0) {
-            a.cost[2 * (size_t)p] = ran ? S.cost0 : pr_nan(); a.cost[2 * (size_t)p + 1] = ran ? S.sum[0] : pr_nan();
+            a.cost[2 * (size_t)p] = ran ? S.cost0 : mi_nan(); a.cost[2 * (size_t)p + 1] = ran ? S.sum[0] : mi_nan();
             int32_t *o = a.info + 4 * (size_t)p;
             o[0] = posed ? used : 0; o[1] = ran ? S.trials : 0; o[2] = ran ? S.accepted : 0; o[3] = status;
         }
@@ -395,41 +393,22 @@ __global__ __launch_bounds__(PR_T) void pr_refine_kernel(pr_args a)
 }
 
 /* ---- host side ---------------------------------------------------------------------------------------------------------- */
-#define PRCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { char b_[256]; snprintf(b_, sizeof b_, "%s failed: %s", #x, hipGetErrorString(e_)); \
-    mt_set_error(b_); (void)hipGetLastError(); return MI_DEGENSAC_EHIP; } } while (0)
-static int pr_einval(const char *msg) { mt_set_error(msg); return MI_DEGENSAC_EINVAL; }
-
-struct PrDevGuard {
-    int prev = -1; bool armed = false;
-    int enter(int device)
-    {
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n == 0) { (void)hipGetLastError(); mt_set_error("no HIP device: this library has no CPU path");
-            return MI_DEGENSAC_ENODEV; }
-        if (device < 0 || device >= n) { mt_set_error("device index out of range"); return MI_DEGENSAC_ENODEV; }
-        if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-        if (prev != device) { PRCHK(hipSetDevice(device)); armed = prev >= 0; }
-        return 0;
-    }
-    ~PrDevGuard() { if (armed) (void)hipSetDevice(prev); }
-};
-
 extern "C" int mi_degensac_pose_refine_tile(int which) { return which == 0 ? PR_STEP : which == 1 ? PR_GRID : -1; }
 
 /* the refusals of include/mi_degensac.h, in that order; needs no device */
 static int pr_check(const void *pts, const void *off, const void *pose, const void *cams, int n_cams, int K, int64_t cap, int max_trials, double ftol,
                     const void *pose_out, const void *cost, const void *info)
 {
-    if (K < 0) return pr_einval("n_entries < 0");
-    if (cap < 0) return pr_einval("cap < 0");
-    if (cap > 0x3fffffff) return pr_einval("too many rows in one list (cap > 0x3fffffff)");
-    if (n_cams < 0) return pr_einval("n_cams < 0");
-    if (max_trials < 0 || max_trials > 100) return pr_einval("max_trials should lie in 0 .. 100");
-    if (!(ftol >= 0.0)) return pr_einval("ftol should be a number >= 0");
-    if (!off) return pr_einval("NULL argument: corr_offsets");
-    if (K > 0 && (!pose || !cams)) return pr_einval("NULL argument: pose and cams");
-    if (K > 0 && (!pose_out || !cost || !info)) return pr_einval("NULL argument: pose_out, cost and info");
-    if (cap > 0 && !pts) return pr_einval("NULL argument: pts");
+    if (K < 0) return mi_einval("n_entries < 0");
+    if (cap < 0) return mi_einval("cap < 0");
+    if (cap > 0x3fffffff) return mi_einval("too many rows in one list (cap > 0x3fffffff)");
+    if (n_cams < 0) return mi_einval("n_cams < 0");
+    if (max_trials < 0 || max_trials > 100) return mi_einval("max_trials should lie in 0 .. 100");
+    if (!(ftol >= 0.0)) return mi_einval("ftol should be a number >= 0");
+    if (!off) return mi_einval("NULL argument: corr_offsets");
+    if (K > 0 && (!pose || !cams)) return mi_einval("NULL argument: pose and cams");
+    if (K > 0 && (!pose_out || !cost || !info)) return mi_einval("NULL argument: pose_out, cost and info");
+    if (cap > 0 && !pts) return mi_einval("NULL argument: pts");
     return 0;
 }
 
@@ -440,9 +419,9 @@ extern "C" int mi_degensac_pose_refine_lists_dev(const double *d_pts, const int6
 {
     int rc = pr_check(d_pts, d_corr_offsets, d_pose, d_cams, n_cams, n_entries, cap, max_trials, ftol, d_pose_out, d_cost, d_info); if (rc) return rc;
     if (n_entries == 0 && cap == 0) return 0;
-    PrDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+    MiDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (cap > 0 && d_resid) PRCHK(hipMemsetAsync(d_resid, 0xff, (size_t)cap * 8, s));      /* all bits set: a NaN where no used row is written */
+    if (cap > 0 && d_resid) MICHK(hipMemsetAsync(d_resid, 0xff, (size_t)cap * 8, s));      /* all bits set: a NaN where no used row is written */
     if (n_entries == 0) return 0;
     pr_args a;
     memset(&a, 0, sizeof a);
@@ -451,7 +430,7 @@ extern "C" int mi_degensac_pose_refine_lists_dev(const double *d_pts, const int6
     a.K = n_entries; a.n_cams = n_cams; a.cap = cap; a.max_trials = max_trials; a.ftol = ftol;
     const dim3 grid((unsigned)std::min(n_entries, PR_GRID)), block(PR_T);
     hipLaunchKernelGGL(pr_refine_kernel, grid, block, 0, s, a);
-    PRCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     return 0;
 }
 
@@ -461,28 +440,17 @@ extern "C" int mi_degensac_pose_refine_lists(const double *pts, const int64_t *c
 {
     int rc = pr_check(pts, corr_offsets, pose, cams, n_cams, n_entries, cap, max_trials, ftol, pose_out, cost, info); if (rc) return rc;
     if (n_entries == 0 && cap == 0) return 0;
-    PrDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+    MiDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     const size_t K = (size_t)n_entries, C = (size_t)cap, NC = (size_t)n_cams;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    /* inputs: pts, off, keep, pose, cams, idx; outputs: pose_out, cost, info, resid, F */
-    const size_t sz[11] = {C * 32, (K + 1) * 8, C, K * 96, NC * 32, K * 8, K * 96, K * 16, K * 16, C * 8, K * 72};
-    size_t at[12]; at[0] = 0;
-    for (int i = 0; i < 11; i++) at[i + 1] = at[i] + up(sz[i]);
-    char *D = nullptr;
-    struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
-    PRCHK(hipMalloc((void **)&D, at[11] + 256));
-    const void *in[6] = {pts, corr_offsets, keep, pose, cams, cam_idx};
-    for (int i = 0; i < 6; i++)
-        if (in[i] && sz[i]) PRCHK(hipMemcpy(D + at[i], in[i], sz[i], hipMemcpyHostToDevice));
-    void *out[5] = {pose_out, cost, info, resid, F};
-    auto dv = [&](int i, const void *h) { return h ? (void *)(D + at[i]) : nullptr; };
-    rc = mi_degensac_pose_refine_lists_dev((const double *)D, (const int64_t *)(D + at[1]), (const uint8_t *)dv(2, keep), (const double *)(D + at[3]),
-                                           (const double *)(D + at[4]), n_cams, (const int32_t *)dv(5, cam_idx), n_entries, cap, max_trials, ftol,
-                                           device, nullptr, (double *)(D + at[6]), (double *)(D + at[7]), (int32_t *)(D + at[8]),
-                                           (double *)dv(9, resid), (double *)dv(10, F));
+    MiStage st;
+    const int i_pts = st.in(pts, C * 32), i_off = st.in(corr_offsets, (K + 1) * 8), i_keep = st.in(keep, C), i_pose = st.in(pose, K * 96),
+              i_cams = st.in(cams, NC * 32), i_idx = st.in(cam_idx, K * 8), o_pose = st.out(pose_out, K * 96), o_cost = st.out(cost, K * 16),
+              o_info = st.out(info, K * 16), o_res = st.out(resid, C * 8), o_F = st.out(F, K * 72);
+    rc = st.upload(); if (rc) return rc;
+    rc = mi_degensac_pose_refine_lists_dev(st.dev<double>(i_pts), st.dev<int64_t>(i_off), st.dev<uint8_t>(i_keep), st.dev<double>(i_pose),
+                                           st.dev<double>(i_cams), n_cams, st.dev<int32_t>(i_idx), n_entries, cap, max_trials, ftol, device, nullptr,
+                                           st.dev<double>(o_pose), st.dev<double>(o_cost), st.dev<int32_t>(o_info), st.dev<double>(o_res),
+                                           st.dev<double>(o_F));
     if (rc) return rc;
-    PRCHK(hipStreamSynchronize(nullptr));
-    for (int i = 0; i < 5; i++)
-        if (out[i] && sz[6 + i]) PRCHK(hipMemcpy(out[i], D + at[6 + i], sz[6 + i], hipMemcpyDeviceToHost));
-    return 0;
+    return st.finish();
 }

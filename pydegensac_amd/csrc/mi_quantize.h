@@ -1,5 +1,5 @@
 /* Float descriptors -> the uint8 rows of MI_DEGENSAC_NORM_L2_U8 (include/mi_degensac.h, mi_degensac_desc_quantize*), included at the end
- * of mi_matcher.hip (compiled with -ffp-contract=off; uses its mt_err / MTCHK / MtDevGuard).
+ * of mi_matcher.hip (compiled with -ffp-contract=off; host plumbing: mi_host.h).
  *
  * One row is held by LPR = 64, 32 or 16 lanes of a wave (the smallest that covers its words: 4 columns per lane), so a wave holds
  * 1, 2 or 4 rows and a 256-thread workgroup 4, 8 or 16.  Lane i of a row owns columns 4 i .. 4 i + 3: one float4 load when
@@ -72,7 +72,7 @@ extern "C" int64_t mi_degensac_desc_quantize_pass_rows(int dim)
     return (int64_t)MQ_MAX_GRID * 4 * (64 / mq_lanes_per_row(dim));
 }
 
-#define MQ_REFUSE(msg) do { snprintf(mt_err, sizeof mt_err, "%s", msg); return MI_DEGENSAC_EINVAL; } while (0)
+#define MQ_REFUSE(msg) return mi_einval(msg)
 
 /* every refusal of the two entry points, before a device is looked for; *empty = the call has nothing to do */
 static int mq_check(const mi_degensac_quant_params *qp, const void *in, int64_t n, int dim, const void *out, bool *empty)
@@ -99,7 +99,7 @@ extern "C" int mi_degensac_desc_quantize_dev(const mi_degensac_quant_params *qp,
     bool empty; int rc = mq_check(qp, d_desc, n, dim, d_out, &empty); if (rc || empty) return rc;
     if (((uintptr_t)d_desc & 3) || ((uintptr_t)d_out & 3) || ((uintptr_t)d_clipped_or_null & 3))
         MQ_REFUSE("d_desc, d_out and d_clipped should be 4-byte aligned (the output rows are written as 32-bit words)");
-    MtDevGuard g; rc = g.enter(device); if (rc) return rc;
+    MiDevGuard g; rc = g.enter(device); if (rc) return rc;
     const int lpr = mq_lanes_per_row(dim), rpb = 4 * (64 / lpr);
     const int64_t blocks = (n + rpb - 1) / rpb;
     const dim3 grid((unsigned)(blocks < MQ_MAX_GRID ? blocks : MQ_MAX_GRID)), block(256);
@@ -108,7 +108,7 @@ extern "C" int mi_degensac_desc_quantize_dev(const mi_degensac_quant_params *qp,
     if (lpr == 16)      hipLaunchKernelGGL(mq_quantize_kernel<16>, grid, block, 0, (hipStream_t)stream, a);
     else if (lpr == 32) hipLaunchKernelGGL(mq_quantize_kernel<32>, grid, block, 0, (hipStream_t)stream, a);
     else                hipLaunchKernelGGL(mq_quantize_kernel<64>, grid, block, 0, (hipStream_t)stream, a);
-    MTCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     return 0;
 }
 
@@ -116,16 +116,16 @@ extern "C" int mi_degensac_desc_quantize(const mi_degensac_quant_params *qp, con
                                          int32_t *clipped_or_null)
 {
     bool empty; int rc = mq_check(qp, desc, n, dim, out, &empty); if (rc || empty) return rc;
-    MtDevGuard g; rc = g.enter(device); if (rc) return rc;
+    MiDevGuard g; rc = g.enter(device); if (rc) return rc;
     const size_t out_dim = (size_t)((dim + 3) & ~3), bi = (size_t)n * dim * sizeof(float), bo = (size_t)n * out_dim, bc = (size_t)n * sizeof(int32_t);
     float *di = nullptr; uint8_t *dout = nullptr; int32_t *dc = nullptr;
     struct Free { float *&a; uint8_t *&b; int32_t *&c; ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); } } fr{di, dout, dc};
-    MTCHK(hipMalloc((void **)&di, bi)); MTCHK(hipMalloc((void **)&dout, bo));
-    if (clipped_or_null) MTCHK(hipMalloc((void **)&dc, bc));
-    MTCHK(hipMemcpy(di, desc, bi, hipMemcpyHostToDevice));
+    MICHK(hipMalloc((void **)&di, bi)); MICHK(hipMalloc((void **)&dout, bo));
+    if (clipped_or_null) MICHK(hipMalloc((void **)&dc, bc));
+    MICHK(hipMemcpy(di, desc, bi, hipMemcpyHostToDevice));
     rc = mi_degensac_desc_quantize_dev(qp, di, n, dim, device, nullptr, dout, dc); if (rc) return rc;
-    MTCHK(hipDeviceSynchronize());
-    MTCHK(hipMemcpy(out, dout, bo, hipMemcpyDeviceToHost));
-    if (clipped_or_null) MTCHK(hipMemcpy(clipped_or_null, dc, bc, hipMemcpyDeviceToHost));
+    MICHK(hipDeviceSynchronize());
+    MICHK(hipMemcpy(out, dout, bo, hipMemcpyDeviceToHost));
+    if (clipped_or_null) MICHK(hipMemcpy(clipped_or_null, dc, bc, hipMemcpyDeviceToHost));
     return 0;
 }

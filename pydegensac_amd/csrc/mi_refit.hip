@@ -32,6 +32,7 @@
 #include "dg_kernel_h.h"
 #include "../../include/mi_degensac.h"
 #include "mi_match_batch.h"
+#include "mi_host.h"
 
 #define RF_LOADS 4                        /* rows per thread and step */
 #define RF_STEP  (RF_LOADS * DG_T)        /* rows per workgroup and step */
@@ -227,42 +228,23 @@ __global__ __launch_bounds__(DG_T) void rf_refit_kernel(rf_args a)
 }
 
 /* ---- host side ---------------------------------------------------------------------------------------------------------- */
-#define RFCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { char b_[256]; snprintf(b_, sizeof b_, "%s failed: %s", #x, hipGetErrorString(e_)); \
-    mt_set_error(b_); (void)hipGetLastError(); return MI_DEGENSAC_EHIP; } } while (0)
-static int rf_einval(const char *msg) { mt_set_error(msg); return MI_DEGENSAC_EINVAL; }
-
-struct RfDevGuard {
-    int prev = -1; bool armed = false;
-    int enter(int device)
-    {
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n == 0) { (void)hipGetLastError(); mt_set_error("no HIP device: this library has no CPU path");
-            return MI_DEGENSAC_ENODEV; }
-        if (device < 0 || device >= n) { mt_set_error("device index out of range"); return MI_DEGENSAC_ENODEV; }
-        if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-        if (prev != device) { RFCHK(hipSetDevice(device)); armed = prev >= 0; }
-        return 0;
-    }
-    ~RfDevGuard() { if (armed) (void)hipSetDevice(prev); }
-};
-
 extern "C" int mi_degensac_refit_tile(int which) { return which == 0 ? RF_STEP : which == 1 ? RF_GRID : -1; }
 
 /* the refusals of include/mi_degensac.h, in that order; needs no device */
 static int rf_check(const void *pts, const void *off, const void *models, const void *models_out, const void *inlier, int K, int64_t cap,
                     const mi_degensac_guide_params *gp, int max_fits, mt_gate *g)
 {
-    if (K < 0) return rf_einval("n_entries < 0");
-    if (cap < 0) return rf_einval("cap < 0");
-    if (cap > 0x3fffffff) return rf_einval("too many rows in one list (cap > 0x3fffffff)");
-    if (max_fits < 0) return rf_einval("max_fits < 0");
-    if (!gp) return rf_einval("guide params are NULL");
-    if (gp->struct_size != 0 && gp->struct_size < (int32_t)sizeof(mi_degensac_guide_params)) return rf_einval("guide params: struct_size too small");
-    if (gp->homography != 0 && gp->homography != 1) return rf_einval("homography must be 0 or 1");
+    if (K < 0) return mi_einval("n_entries < 0");
+    if (cap < 0) return mi_einval("cap < 0");
+    if (cap > 0x3fffffff) return mi_einval("too many rows in one list (cap > 0x3fffffff)");
+    if (max_fits < 0) return mi_einval("max_fits < 0");
+    if (!gp) return mi_einval("guide params are NULL");
+    if (gp->struct_size != 0 && gp->struct_size < (int32_t)sizeof(mi_degensac_guide_params)) return mi_einval("guide params: struct_size too small");
+    if (gp->homography != 0 && gp->homography != 1) return mi_einval("homography must be 0 or 1");
     const int rc = mt_guided_gate(gp->homography, gp->error_type, gp->px_th, g); if (rc) return rc;
-    if (!off) return rf_einval("NULL argument: corr_offsets");
-    if (K > 0 && (!models || !models_out)) return rf_einval("NULL argument: models and models_out");
-    if (cap > 0 && (!pts || !inlier)) return rf_einval("NULL argument: pts and inlier");
+    if (!off) return mi_einval("NULL argument: corr_offsets");
+    if (K > 0 && (!models || !models_out)) return mi_einval("NULL argument: models and models_out");
+    if (cap > 0 && (!pts || !inlier)) return mi_einval("NULL argument: pts and inlier");
     return 0;
 }
 
@@ -272,17 +254,16 @@ extern "C" int mi_degensac_refit_lists_dev(const double *d_pts, const int64_t *d
 {
     mt_gate g; int rc = rf_check(d_pts, d_corr_offsets, d_models, d_models_out, d_inlier, n_entries, cap, gp, max_fits, &g); if (rc) return rc;
     if (n_entries == 0 && cap == 0) return 0;
-    RfDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+    MiDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (cap > 0) {                                                    /* positions that no entry owns keep 0 / NaN */
-        RFCHK(hipMemsetAsync(d_inlier, 0, (size_t)cap, s));
-        if (d_resid) RFCHK(hipMemsetAsync(d_resid, 0xff, (size_t)cap * 8, s));      /* all bits set: a NaN */
+        MICHK(hipMemsetAsync(d_inlier, 0, (size_t)cap, s));
+        if (d_resid) MICHK(hipMemsetAsync(d_resid, 0xff, (size_t)cap * 8, s));      /* all bits set: a NaN */
     }
     if (n_entries == 0) return 0;
-    char *blk = nullptr;
     const size_t a_list = (size_t)cap * 64, a_all = a_list + (size_t)cap * 4 + 256;
-    RFCHK(hipMallocAsync((void **)&blk, a_all, s));
-    struct Free { char *p; hipStream_t s; ~Free() { (void)hipFreeAsync(p, s); } } fr{blk, s};
+    MiScratch scr; rc = scr.alloc(a_all, s); if (rc) return rc;
+    char *blk = scr.p;
     rf_args a;
     memset(&a, 0, sizeof a);
     a.pts = (const dg_pt *)d_pts; a.off = d_corr_offsets; a.models = d_models; a.models_out = d_models_out; a.models_user = d_models_user;
@@ -295,7 +276,7 @@ extern "C" int mi_degensac_refit_lists_dev(const double *d_pts, const int64_t *d
     case RF_H_SAMPSON: hipLaunchKernelGGL((rf_refit_kernel<RF_H_SAMPSON>), grid, block, 0, s, a); break;
     default: hipLaunchKernelGGL((rf_refit_kernel<RF_H_SYM>), grid, block, 0, s, a); break;
     }
-    RFCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     return 0;
 }
 
@@ -305,30 +286,14 @@ extern "C" int mi_degensac_refit_lists(const double *pts, const int64_t *corr_of
 {
     mt_gate g; int rc = rf_check(pts, corr_offsets, models, models_out, inlier, n_entries, cap, gp, max_fits, &g); if (rc) return rc;
     if (n_entries == 0 && cap == 0) return 0;
-    RfDevGuard dg; rc = dg.enter(device); if (rc) return rc;
-    const int K = n_entries;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t a_off = up((size_t)cap * 32), a_mo = a_off + up((size_t)(K + 1) * 8), a_out = a_mo + up((size_t)K * 72), a_us = a_out + up((size_t)K * 72),
-                 a_inf = a_us + up((size_t)K * 72), a_inl = a_inf + up((size_t)K * 16), a_res = a_inl + up((size_t)cap), a_all = a_res + up((size_t)cap * 8);
-    char *D = nullptr;
-    struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
-    RFCHK(hipMalloc((void **)&D, a_all + 256));
-    if (cap > 0) RFCHK(hipMemcpy(D, pts, (size_t)cap * 32, hipMemcpyHostToDevice));
-    RFCHK(hipMemcpy(D + a_off, corr_offsets, (size_t)(K + 1) * 8, hipMemcpyHostToDevice));
-    if (K > 0) RFCHK(hipMemcpy(D + a_mo, models, (size_t)K * 72, hipMemcpyHostToDevice));
-    rc = mi_degensac_refit_lists_dev((const double *)D, (const int64_t *)(D + a_off), (const double *)(D + a_mo), K, cap, gp, max_fits, device, nullptr,
-                                     (double *)(D + a_out), (uint8_t *)(D + a_inl), models_user ? (double *)(D + a_us) : nullptr,
-                                     info ? (int32_t *)(D + a_inf) : nullptr, resid ? (double *)(D + a_res) : nullptr);
+    MiDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+    const size_t K = (size_t)n_entries, C = (size_t)cap;
+    MiStage st;
+    const int i_pts = st.in(pts, C * 32), i_off = st.in(corr_offsets, (K + 1) * 8), i_mo = st.in(models, K * 72), o_out = st.out(models_out, K * 72),
+              o_inl = st.out(inlier, C), o_us = st.out(models_user, K * 72), o_inf = st.out(info, K * 16), o_res = st.out(resid, C * 8);
+    rc = st.upload(); if (rc) return rc;
+    rc = mi_degensac_refit_lists_dev(st.dev<double>(i_pts), st.dev<int64_t>(i_off), st.dev<double>(i_mo), n_entries, cap, gp, max_fits, device, nullptr,
+                                     st.dev<double>(o_out), st.dev<uint8_t>(o_inl), st.dev<double>(o_us), st.dev<int32_t>(o_inf), st.dev<double>(o_res));
     if (rc) return rc;
-    RFCHK(hipStreamSynchronize(nullptr));
-    if (K > 0) {
-        RFCHK(hipMemcpy(models_out, D + a_out, (size_t)K * 72, hipMemcpyDeviceToHost));
-        if (models_user) RFCHK(hipMemcpy(models_user, D + a_us, (size_t)K * 72, hipMemcpyDeviceToHost));
-        if (info) RFCHK(hipMemcpy(info, D + a_inf, (size_t)K * 16, hipMemcpyDeviceToHost));
-    }
-    if (cap > 0) {
-        RFCHK(hipMemcpy(inlier, D + a_inl, (size_t)cap, hipMemcpyDeviceToHost));
-        if (resid) RFCHK(hipMemcpy(resid, D + a_res, (size_t)cap * 8, hipMemcpyDeviceToHost));
-    }
-    return 0;
+    return st.finish();
 }

@@ -39,6 +39,8 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include "../../include/mi_degensac.h"
 #include "mi_match_batch.h"
+#include "mi_host.h"
+#include "mi_dev_util.h"
 
 #define TK_ROWS 1024              /* sorted positions per workgroup: 256 threads x 4 consecutive positions */
 #define TK_SCAN 256               /* workgroup counts per step of the scan */
@@ -116,53 +118,21 @@ __device__ __forceinline__ unsigned tk_starts(const uint32_t *key, int64_t i0, i
     return f;
 }
 
-/* the starts of the wave's lower lanes (before this thread's four positions), and of the whole wave */
-__device__ __forceinline__ void tk_wave_prefix(unsigned f, int lane, int *before, int *total)
-{
-    const unsigned long long below = (1ull << lane) - 1ull;
-    int b = 0, t = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const unsigned long long bal = __ballot((f >> j) & 1u);
-        b += __popcll(bal & below); t += __popcll(bal);
-    }
-    *before = b; *total = t;
-}
-
 __global__ __launch_bounds__(256) void tk_count_kernel(const uint32_t *key, int R, int32_t *cnt)
 {
-    __shared__ int wsum[4];
     uint32_t k[4];
     const unsigned f = tk_starts(key, (int64_t)blockIdx.x * TK_ROWS + (int64_t)threadIdx.x * 4, R, k);
     int before, total;
-    tk_wave_prefix(f, threadIdx.x & 63, &before, &total);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = total;
-    __syncthreads();
-    if (threadIdx.x == 0) cnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    mi_wave_prefix(f, threadIdx.x & 63, &before, &total);
+    mi_block_count(total, cnt);
 }
 
 /* one workgroup: base[b] = the track starts before workgroup b, *n_tracks, and *n_obs = the sorted keys below R */
 __global__ __launch_bounds__(TK_SCAN) void tk_scan_kernel(const int32_t *cnt, int nb, int32_t *base, const uint32_t *key, int R, int64_t *n_tracks,
                                                           int64_t *n_obs)
 {
-    __shared__ int wsum[TK_SCAN / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int64_t carry = 0;
-    for (int s = 0; s < nb; s += TK_SCAN) {                           /* uniform over the workgroup */
-        const int i = s + tid;
-        const int c = i < nb ? cnt[i] : 0;
-        int v = c;
-        for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(v, d); if (lane >= d) v += t; }
-        if (lane == 63) wsum[wv] = v;
-        __syncthreads();
-        int wbase = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < TK_SCAN / 64; w++) { if (w < wv) wbase += wsum[w]; all += wsum[w]; }
-        if (i < nb) base[i] = (int32_t)(carry + wbase + v - c);
-        carry += all;
-        __syncthreads();
-    }
-    if (tid == 0) {
+    const int64_t carry = mi_block_scan<TK_SCAN>(cnt, nb, base);
+    if (threadIdx.x == 0) {
         *n_tracks = carry;
         int64_t lo = 0, hi = R;                                       /* the first position whose key is R */
         while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (key[mid] < (uint32_t)R) lo = mid + 1; else hi = mid; }
@@ -192,7 +162,7 @@ __global__ __launch_bounds__(256) void tk_write_kernel(const uint32_t *key, cons
     const unsigned f = tk_starts(key, i0, R, k);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     int before, total;
-    tk_wave_prefix(f, lane, &before, &total);
+    mi_wave_prefix(f, lane, &before, &total);
     if (lane == 0) wsum[wv] = total;
     __syncthreads();
     int t = base[blockIdx.x] + before;                                /* the track starts before this thread's first position */
@@ -241,41 +211,22 @@ __global__ __launch_bounds__(256) void tk_images_kernel(const uint32_t *key, con
 }
 
 /* ---- host side ---------------------------------------------------------------------------------------------------------- */
-#define TKCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { char b_[256]; snprintf(b_, sizeof b_, "%s failed: %s", #x, hipGetErrorString(e_)); \
-    mt_set_error(b_); (void)hipGetLastError(); return MI_DEGENSAC_EHIP; } } while (0)
-static int tk_einval(const char *msg) { mt_set_error(msg); return MI_DEGENSAC_EINVAL; }
-
-struct TkDevGuard {
-    int prev = -1; bool armed = false;
-    int enter(int device)
-    {
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n == 0) { (void)hipGetLastError(); mt_set_error("no HIP device: this library has no CPU path");
-            return MI_DEGENSAC_ENODEV; }
-        if (device < 0 || device >= n) { mt_set_error("device index out of range"); return MI_DEGENSAC_ENODEV; }
-        if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-        if (prev != device) { TKCHK(hipSetDevice(device)); armed = prev >= 0; }
-        return 0;
-    }
-    ~TkDevGuard() { if (armed) (void)hipSetDevice(prev); }
-};
-
 extern "C" int mi_degensac_tracks_tile(int which) { return which == 0 ? TK_ROWS : which == 1 ? TK_SCAN : -1; }
 
 /* the refusals of include/mi_degensac.h, in that order; needs no device */
 static int tk_check(const int64_t *offsets, int n_images, const int32_t *rows, int64_t n_edges, const void *track, const void *n_tracks,
                     const void *n_obs, const void *track_offsets, const void *obs, const void *obs_image, const void *track_images)
 {
-    if (n_images < 0) return tk_einval("n_images < 0");
-    if (!offsets) return tk_einval("NULL argument: offsets");
-    if (offsets[0] < 0) return tk_einval("offsets must be non-decreasing and start at >= 0");
-    for (int i = 0; i < n_images; i++) if (offsets[i + 1] < offsets[i]) return tk_einval("offsets must be non-decreasing and start at >= 0");
-    if (offsets[n_images] > 0x7fffffff) return tk_einval("the store's rows do not fit int32 (offsets beyond 0x7fffffff)");
-    if (n_edges < 0 || n_edges > 0x3fffffff) return tk_einval("n_edges must lie in 0 .. 0x3fffffff");
-    if (!rows && n_edges > 0) return tk_einval("NULL argument: rows of a list that is not empty");
-    if (!track || !n_tracks || !n_obs || !track_offsets) return tk_einval("NULL argument: track, n_tracks, n_obs and track_offsets are always written");
-    if ((obs_image || track_images) && !obs) return tk_einval("obs_image and track_images need obs");
-    if (((uintptr_t)rows) & 3u) return tk_einval("rows must be 4-byte aligned");
+    if (n_images < 0) return mi_einval("n_images < 0");
+    if (!offsets) return mi_einval("NULL argument: offsets");
+    if (offsets[0] < 0) return mi_einval("offsets must be non-decreasing and start at >= 0");
+    for (int i = 0; i < n_images; i++) if (offsets[i + 1] < offsets[i]) return mi_einval("offsets must be non-decreasing and start at >= 0");
+    if (offsets[n_images] > 0x7fffffff) return mi_einval("the store's rows do not fit int32 (offsets beyond 0x7fffffff)");
+    if (n_edges < 0 || n_edges > 0x3fffffff) return mi_einval("n_edges must lie in 0 .. 0x3fffffff");
+    if (!rows && n_edges > 0) return mi_einval("NULL argument: rows of a list that is not empty");
+    if (!track || !n_tracks || !n_obs || !track_offsets) return mi_einval("NULL argument: track, n_tracks, n_obs and track_offsets are always written");
+    if ((obs_image || track_images) && !obs) return mi_einval("obs_image and track_images need obs");
+    if (((uintptr_t)rows) & 3u) return mi_einval("rows must be 4-byte aligned");
     return 0;
 }
 
@@ -287,28 +238,26 @@ static int tk_run(const int64_t *offsets, int n_images, const int32_t *d_rows, i
     const int64_t first = offsets[0];
     const int R = (int)(offsets[n_images] - first);
     if (R == 0) {                                                    /* no node: zero tracks, track_offsets [1] = 0 */
-        TKCHK(hipMemsetAsync(d_n_tracks, 0, 8, s));
-        TKCHK(hipMemsetAsync(d_n_obs, 0, 8, s));
-        TKCHK(hipMemsetAsync(d_track_offsets, 0, 8, s));
+        MICHK(hipMemsetAsync(d_n_tracks, 0, 8, s));
+        MICHK(hipMemsetAsync(d_n_obs, 0, 8, s));
+        MICHK(hipMemsetAsync(d_track_offsets, 0, 8, s));
         return 0;
     }
     const int nb = (int)(((int64_t)R + TK_ROWS - 1) / TK_ROWS), g256 = (int)(((int64_t)R + 255) / 256);
     unsigned bits = 1;
     while (((uint32_t)R >> bits) != 0) bits++;                       /* the keys are <= R */
     size_t sort_bytes = 0;
-    TKCHK(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (unsigned)R,
+    MICHK(rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint32_t *)nullptr, (uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr, (unsigned)R,
                                     0u, bits, s));
     std::vector<int32_t> rel((size_t)n_images + 1);
     for (int i = 0; i <= n_images; i++) rel[i] = (int32_t)(offsets[i] - first);
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t w = up((size_t)R * 4);
-    const size_t a_par = up(rel.size() * 4), a_lab = a_par + w, a_mul = a_lab + (d_label ? 0 : w), a_k0 = a_mul + up((size_t)R), a_k1 = a_k0 + w,
-                 a_v0 = a_k1 + w, a_v1 = a_v0 + w, a_cnt = a_v1 + w, a_base = a_cnt + up((size_t)nb * 4), a_sort = a_base + up((size_t)nb * 4),
-                 a_all = a_sort + up(sort_bytes);
-    char *blk = nullptr;
-    TKCHK(hipMallocAsync((void **)&blk, a_all, s));
-    struct Free { char *p; hipStream_t s; ~Free() { (void)hipFreeAsync(p, s); } } fr{blk, s};
-    int rc = mt_batch_upload(device, s, rel.data(), rel.size() * 4, blk); if (rc) return rc;
+    const size_t w = mi_up256((size_t)R * 4);
+    const size_t a_par = mi_up256(rel.size() * 4), a_lab = a_par + w, a_mul = a_lab + (d_label ? 0 : w), a_k0 = a_mul + mi_up256((size_t)R), a_k1 = a_k0 + w,
+                 a_v0 = a_k1 + w, a_v1 = a_v0 + w, a_cnt = a_v1 + w, a_base = a_cnt + mi_up256((size_t)nb * 4), a_sort = a_base + mi_up256((size_t)nb * 4),
+                 a_all = a_sort + mi_up256(sort_bytes);
+    MiScratch scr; int rc = scr.alloc(a_all, s); if (rc) return rc;
+    char *blk = scr.p;
+    rc = mt_batch_upload(device, s, rel.data(), rel.size() * 4, blk); if (rc) return rc;
     const int32_t *d_rel = (const int32_t *)blk;
     int32_t *parent = (int32_t *)(blk + a_par), *label = d_label ? d_label : (int32_t *)(blk + a_lab);
     uint8_t *multi = (uint8_t *)(blk + a_mul);
@@ -316,29 +265,29 @@ static int tk_run(const int64_t *offsets, int n_images, const int32_t *d_rows, i
     int32_t *v0 = (int32_t *)(blk + a_v0), *v1 = (int32_t *)(blk + a_v1), *cnt = (int32_t *)(blk + a_cnt), *base = (int32_t *)(blk + a_base);
 
     hipLaunchKernelGGL(tk_init_kernel, dim3(g256), dim3(256), 0, s, parent, multi, R);
-    TKCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     if (n_edges > 0) {
         const int lb = (int)std::min<int64_t>((n_edges + 255) / 256, TK_LINK_BLOCKS);
         hipLaunchKernelGGL(tk_link_kernel, dim3(lb), dim3(256), 0, s, d_rows, n_edges, d_total, (((uintptr_t)d_rows) & 7u) == 0 ? 1 : 0, first, R, parent);
-        TKCHK(hipGetLastError());
+        MICHK(hipGetLastError());
     }
     hipLaunchKernelGGL(tk_compress_kernel, dim3(g256), dim3(256), 0, s, (const int32_t *)parent, R, label, multi);
-    TKCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     hipLaunchKernelGGL(tk_keys_kernel, dim3(g256), dim3(256), 0, s, (const int32_t *)label, (const uint8_t *)multi, R, k0, v0);
-    TKCHK(hipGetLastError());
-    TKCHK(rocprim::radix_sort_pairs((void *)(blk + a_sort), sort_bytes, k0, k1, v0, v1, (unsigned)R, 0u, bits, s));
+    MICHK(hipGetLastError());
+    MICHK(rocprim::radix_sort_pairs((void *)(blk + a_sort), sort_bytes, k0, k1, v0, v1, (unsigned)R, 0u, bits, s));
     hipLaunchKernelGGL(tk_count_kernel, dim3(nb), dim3(256), 0, s, (const uint32_t *)k1, R, cnt);
-    TKCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     hipLaunchKernelGGL(tk_scan_kernel, dim3(1), dim3(TK_SCAN), 0, s, (const int32_t *)cnt, nb, base, (const uint32_t *)k1, R, d_n_tracks, d_n_obs);
-    TKCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     tk_out o{d_track, d_track_offsets, d_obs, d_obs_image, d_track_images, d_n_tracks, d_n_obs};
     hipLaunchKernelGGL(tk_write_kernel, dim3(nb), dim3(256), 0, s, (const uint32_t *)k1, (const int32_t *)v1, (const int32_t *)base, R, (int32_t)first,
                        d_rel, n_images, o);
-    TKCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     if (d_track_images) {
         hipLaunchKernelGGL(tk_images_kernel, dim3(g256), dim3(256), 0, s, (const uint32_t *)k1, (const int32_t *)v1, R, d_rel, n_images,
                            (const int64_t *)d_n_obs, (const int32_t *)d_track, d_track_images);
-        TKCHK(hipGetLastError());
+        MICHK(hipGetLastError());
     }
     return 0;
 }
@@ -349,7 +298,7 @@ extern "C" int mi_degensac_tracks_dev(const int64_t *offsets_host, int n_images,
 {
     int rc = tk_check(offsets_host, n_images, d_rows, n_edges, d_track, d_n_tracks, d_n_obs, d_track_offsets, d_obs, d_obs_image, d_track_images);
     if (rc) return rc;
-    TkDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+    MiDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     return tk_run(offsets_host, n_images, d_rows, n_edges, d_total, device, (hipStream_t)stream, d_label, d_track, d_n_tracks, d_n_obs, d_track_offsets,
                   d_obs, d_obs_image, d_track_images);
 }
@@ -359,33 +308,15 @@ extern "C" int mi_degensac_tracks(const int64_t *offsets, int n_images, const in
                                   int32_t *track_images)
 {
     int rc = tk_check(offsets, n_images, rows, n_edges, track, n_tracks, n_obs, track_offsets, obs, obs_image, track_images); if (rc) return rc;
-    TkDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+    MiDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     const size_t R = (size_t)(offsets[n_images] - offsets[0]), half = R / 2;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t w = up(R * 4);
-    const size_t a_tot = up((size_t)n_edges * 8), a_cnt = a_tot + 256, a_lab = a_cnt + 256, a_trk = a_lab + (label ? w : 0), a_to = a_trk + w,
-                 a_obs = a_to + up((half + 1) * 8), a_oi = a_obs + (obs ? w : 0), a_ti = a_oi + (obs_image ? w : 0),
-                 a_all = a_ti + (track_images ? up(half * 4) : 0);
-    char *D = nullptr;
-    struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
-    TKCHK(hipMalloc((void **)&D, a_all + 256));
-    if (n_edges > 0) TKCHK(hipMemcpy(D, rows, (size_t)n_edges * 8, hipMemcpyHostToDevice));
-    if (total >= 0) TKCHK(hipMemcpy(D + a_tot, &total, 8, hipMemcpyHostToDevice));
-    int64_t *d_cnt = (int64_t *)(D + a_cnt);                         /* n_tracks, n_obs */
-    rc = tk_run(offsets, n_images, (const int32_t *)D, n_edges, total >= 0 ? (const int64_t *)(D + a_tot) : nullptr, device, nullptr,
-                label ? (int32_t *)(D + a_lab) : nullptr, (int32_t *)(D + a_trk), d_cnt, d_cnt + 1, (int64_t *)(D + a_to),
-                obs ? (int32_t *)(D + a_obs) : nullptr, obs_image ? (int32_t *)(D + a_oi) : nullptr, track_images ? (int32_t *)(D + a_ti) : nullptr);
+    MiStage st;
+    const int i_rows = st.in(rows, (size_t)n_edges * 8), i_tot = st.in(total >= 0 ? &total : nullptr, 8), o_nt = st.out(n_tracks, 8), o_no = st.out(n_obs, 8),
+              o_to = st.out(track_offsets, (half + 1) * 8), o_lab = st.out(label, R * 4), o_trk = st.out(track, R * 4), o_obs = st.out(obs, R * 4),
+              o_oi = st.out(obs_image, R * 4), o_ti = st.out(track_images, half * 4);
+    rc = st.upload(); if (rc) return rc;
+    rc = tk_run(offsets, n_images, st.dev<int32_t>(i_rows), n_edges, st.dev<int64_t>(i_tot), device, nullptr, st.dev<int32_t>(o_lab), st.dev<int32_t>(o_trk),
+                st.dev<int64_t>(o_nt), st.dev<int64_t>(o_no), st.dev<int64_t>(o_to), st.dev<int32_t>(o_obs), st.dev<int32_t>(o_oi), st.dev<int32_t>(o_ti));
     if (rc) return rc;
-    TKCHK(hipStreamSynchronize(nullptr));
-    TKCHK(hipMemcpy(n_tracks, d_cnt, 8, hipMemcpyDeviceToHost));
-    TKCHK(hipMemcpy(n_obs, d_cnt + 1, 8, hipMemcpyDeviceToHost));
-    TKCHK(hipMemcpy(track_offsets, D + a_to, (half + 1) * 8, hipMemcpyDeviceToHost));
-    if (R > 0) {
-        if (label) TKCHK(hipMemcpy(label, D + a_lab, R * 4, hipMemcpyDeviceToHost));
-        TKCHK(hipMemcpy(track, D + a_trk, R * 4, hipMemcpyDeviceToHost));
-        if (obs) TKCHK(hipMemcpy(obs, D + a_obs, R * 4, hipMemcpyDeviceToHost));
-        if (obs_image) TKCHK(hipMemcpy(obs_image, D + a_oi, R * 4, hipMemcpyDeviceToHost));
-        if (track_images && half > 0) TKCHK(hipMemcpy(track_images, D + a_ti, half * 4, hipMemcpyDeviceToHost));
-    }
-    return 0;
+    return st.finish();
 }

@@ -23,6 +23,8 @@
 #include <algorithm>
 #include "../../include/mi_degensac.h"
 #include "mi_match_batch.h"
+#include "mi_host.h"
+#include "mi_dev_util.h"
 
 #ifndef TR_G
 /* lanes per track.  Measured (profiles/triangulate.log, kernel alone): 64 lanes take 0.052 ms against 0.095 ms on the benchmark collection
@@ -34,7 +36,6 @@
 #define TR_GPW   (TR_T / TR_G)            /* tracks per workgroup and stride step */
 #define TR_CH    64                       /* rays per staging area of the pair pass */
 #define TR_GRID  1024                     /* cap on the grid: further tracks by the grid stride */
-#define TR_DBL_MAX 1.7976931348623157e308
 static_assert(TR_G >= 2 && TR_G <= 64 && (TR_G & (TR_G - 1)) == 0 && TR_CH % TR_G == 0, "a group is a power of two inside one wave");
 
 struct tr_args {
@@ -58,10 +59,6 @@ struct tr_args {
 
 struct tr_ob { double x, y, fx, fy, cx, cy, R[9], t[3]; };
 
-__device__ __forceinline__ bool tr_finite(double x) { return fabs(x) <= TR_DBL_MAX; }
-__device__ __forceinline__ double tr_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-__device__ __forceinline__ double tr_inf() { return __longlong_as_double(0x7ff0000000000000LL); }
-
 /* the observation at position p of the tables: true when it is used; an index out of range is never used as one */
 __device__ __forceinline__ bool tr_load(const tr_args &a, int64_t p, bool valid, tr_ob &o)
 {
@@ -75,11 +72,11 @@ __device__ __forceinline__ bool tr_load(const tr_args &a, int64_t p, bool valid,
     o.x = a.kps[2 * (size_t)r]; o.y = a.kps[2 * (size_t)r + 1];
     const double *c = a.cams + 4 * (size_t)m, *q = a.poses + 12 * (size_t)m;
     o.fx = c[0]; o.fy = c[1]; o.cx = c[2]; o.cy = c[3];
-    bool fin = tr_finite(o.x) && tr_finite(o.y) && tr_finite(o.fx) && tr_finite(o.fy) && o.fx != 0.0 && o.fy != 0.0;
+    bool fin = mi_finite(o.x) && mi_finite(o.y) && mi_finite(o.fx) && mi_finite(o.fy) && o.fx != 0.0 && o.fy != 0.0;
 #pragma unroll
-    for (int i = 0; i < 9; i++) { o.R[i] = q[i]; fin = fin && tr_finite(o.R[i]); }
+    for (int i = 0; i < 9; i++) { o.R[i] = q[i]; fin = fin && mi_finite(o.R[i]); }
 #pragma unroll
-    for (int i = 0; i < 3; i++) { o.t[i] = q[9 + i]; fin = fin && tr_finite(o.t[i]); }
+    for (int i = 0; i < 3; i++) { o.t[i] = q[9 + i]; fin = fin && mi_finite(o.t[i]); }
     return fin;
 }
 
@@ -238,14 +235,14 @@ __device__ __forceinline__ void tr_stage(const tr_args &a, int64_t b0, int n, in
         double w[3];
         tr_ray(o, w);
 #pragma unroll
-        for (int j = 0; j < 3; j++) W[j][k] = u ? w[j] : tr_nan();
+        for (int j = 0; j < 3; j++) W[j][k] = u ? w[j] : mi_nan();
     }
 }
 
 /* the smallest product of two rays of used observations (all of them finite here: the linear system was positive definite) */
 __device__ __forceinline__ double tr_cosang(const tr_args &a, int64_t b0, int n, int lane, double (*WA)[TR_CH], double (*WB)[TR_CH])
 {
-    double mn = tr_inf();
+    double mn = mi_inf();
     for (int a0 = 0; a0 < n; a0 += TR_CH) {
         tr_group_fence();                                              /* the readers of the previous round are through */
         tr_stage(a, b0, n, lane, a0, WA);
@@ -286,7 +283,7 @@ __global__ __launch_bounds__(TR_T) void tr_triangulate_kernel(tr_args a)
     if (a.nt) { const int64_t v = a.nt[0]; nt = v < 0 ? 0 : v < a.T ? v : a.T; }
     for (int64_t k = (int64_t)blockIdx.x * TR_GPW + grp; k < a.T; k += (int64_t)gridDim.x * TR_GPW) {
         int status = MI_DEGENSAC_TRI_SHORT, used = 0, n_ok = 0, accepted = 0, trials = 0;
-        double X[3] = {tr_nan(), tr_nan(), tr_nan()}, cost0 = tr_nan(), cost1 = tr_nan(), cosang = tr_nan();
+        double X[3] = {mi_nan(), mi_nan(), mi_nan()}, cost0 = mi_nan(), cost1 = mi_nan(), cosang = mi_nan();
         if (k < nt) {                                                  /* a track beyond n_tracks gets the outputs of an empty one */
             const int64_t b = a.off[k], e = a.off[k + 1];
             const bool whole = b >= 0 && b <= e && e <= a.M;
@@ -297,7 +294,7 @@ __global__ __launch_bounds__(TR_T) void tr_triangulate_kernel(tr_args a)
                 used = tr_linear(a, b, n, lane, s);
                 if (used >= 2) {
                     const bool pd = tr_solve(s, s + 6, Y);
-                    if (!pd || !(tr_finite(Y[0]) && tr_finite(Y[1]) && tr_finite(Y[2]))) status = MI_DEGENSAC_TRI_DEGENERATE;
+                    if (!pd || !(mi_finite(Y[0]) && mi_finite(Y[1]) && mi_finite(Y[2]))) status = MI_DEGENSAC_TRI_DEGENERATE;
                     else {
                         tr_pass(a, b, n, lane, Y, s);
                         cost0 = s[0];
@@ -309,7 +306,7 @@ __global__ __launch_bounds__(TR_T) void tr_triangulate_kernel(tr_args a)
 #pragma unroll
                             for (int j = 0; j < 3; j++) Z[j] = Y[j] - dl[j];
                             tr_pass(a, b, n, lane, Z, s2);
-                            if (!(tr_finite(s2[0]) && s2[0] < cur)) break;          /* the first rejected trial ends the run */
+                            if (!(mi_finite(s2[0]) && s2[0] < cur)) break;          /* the first rejected trial ends the run */
                             accepted++;
                             const bool done = (cur - s2[0]) <= a.ftol * cur;
 #pragma unroll
@@ -340,25 +337,6 @@ __global__ __launch_bounds__(TR_T) void tr_triangulate_kernel(tr_args a)
 }
 
 /* ---- host side ---------------------------------------------------------------------------------------------------------- */
-#define TRCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { char b_[256]; snprintf(b_, sizeof b_, "%s failed: %s", #x, hipGetErrorString(e_)); \
-    mt_set_error(b_); (void)hipGetLastError(); return MI_DEGENSAC_EHIP; } } while (0)
-static int tr_einval(const char *msg) { mt_set_error(msg); return MI_DEGENSAC_EINVAL; }
-
-struct TrDevGuard {
-    int prev = -1; bool armed = false;
-    int enter(int device)
-    {
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n == 0) { (void)hipGetLastError(); mt_set_error("no HIP device: this library has no CPU path");
-            return MI_DEGENSAC_ENODEV; }
-        if (device < 0 || device >= n) { mt_set_error("device index out of range"); return MI_DEGENSAC_ENODEV; }
-        if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-        if (prev != device) { TRCHK(hipSetDevice(device)); armed = prev >= 0; }
-        return 0;
-    }
-    ~TrDevGuard() { if (armed) (void)hipSetDevice(prev); }
-};
-
 extern "C" int mi_degensac_triangulate_tile(int which) { return which == 0 ? TR_G : which == 1 ? TR_GRID : which == 2 ? TR_GPW : which == 3 ? TR_CH : -1; }
 
 /* the refusals of include/mi_degensac.h, in that order; needs no device */
@@ -366,21 +344,21 @@ static int tr_check(const void *off, const void *obs, const void *img, const voi
                     int64_t T, int64_t M, double min_angle_deg, double max_reproj_px, int max_iters, double ftol, const void *X, const void *info,
                     const void *cost, const void *cosang)
 {
-    if (T < 0) return tr_einval("n_tracks_max < 0");
-    if (T > 0x3fffffff) return tr_einval("too many tracks (n_tracks_max > 0x3fffffff)");
-    if (M < 0) return tr_einval("n_obs_max < 0");
-    if (M > 0x3fffffff) return tr_einval("too many observations (n_obs_max > 0x3fffffff)");
-    if (rows < 0 || rows > 0x7fffffff) return tr_einval("rows should lie in 0 .. 0x7fffffff");
-    if (n_images < 0) return tr_einval("n_images < 0");
-    if (!(min_angle_deg >= 0.0 && min_angle_deg <= 180.0)) return tr_einval("min_angle_deg should be a number in [0, 180]");
-    if (!(max_reproj_px >= 0.0)) return tr_einval("max_reproj_px should be a number >= 0");
-    if (max_iters < 0 || max_iters > 100) return tr_einval("max_iters should lie in 0 .. 100");
-    if (!(ftol >= 0.0)) return tr_einval("ftol should be a number >= 0");
-    if (!off) return tr_einval("NULL argument: track_offsets");
-    if (M > 0 && (!obs || !img)) return tr_einval("NULL argument: obs and obs_image");
-    if (T > 0 && (!X || !info || !cost || !cosang)) return tr_einval("NULL argument: X, info, cost and cosang");
-    if (rows > 0 && !kps) return tr_einval("NULL argument: kps");
-    if (n_images > 0 && (!cams || !poses)) return tr_einval("NULL argument: cams and poses");
+    if (T < 0) return mi_einval("n_tracks_max < 0");
+    if (T > 0x3fffffff) return mi_einval("too many tracks (n_tracks_max > 0x3fffffff)");
+    if (M < 0) return mi_einval("n_obs_max < 0");
+    if (M > 0x3fffffff) return mi_einval("too many observations (n_obs_max > 0x3fffffff)");
+    if (rows < 0 || rows > 0x7fffffff) return mi_einval("rows should lie in 0 .. 0x7fffffff");
+    if (n_images < 0) return mi_einval("n_images < 0");
+    if (!(min_angle_deg >= 0.0 && min_angle_deg <= 180.0)) return mi_einval("min_angle_deg should be a number in [0, 180]");
+    if (!(max_reproj_px >= 0.0)) return mi_einval("max_reproj_px should be a number >= 0");
+    if (max_iters < 0 || max_iters > 100) return mi_einval("max_iters should lie in 0 .. 100");
+    if (!(ftol >= 0.0)) return mi_einval("ftol should be a number >= 0");
+    if (!off) return mi_einval("NULL argument: track_offsets");
+    if (M > 0 && (!obs || !img)) return mi_einval("NULL argument: obs and obs_image");
+    if (T > 0 && (!X || !info || !cost || !cosang)) return mi_einval("NULL argument: X, info, cost and cosang");
+    if (rows > 0 && !kps) return mi_einval("NULL argument: kps");
+    if (n_images > 0 && (!cams || !poses)) return mi_einval("NULL argument: cams and poses");
     return 0;
 }
 
@@ -396,11 +374,11 @@ extern "C" int mi_degensac_triangulate_tracks_dev(const int64_t *d_track_offsets
                       d_X, d_info, d_cost, d_cosang);
     if (rc) return rc;
     if (T == 0 && M == 0) return 0;
-    TrDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+    MiDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (M > 0 && d_err) TRCHK(hipMemsetAsync(d_err, 0xff, (size_t)M * 8, s));          /* all bits set: a NaN where no used observation is written */
-    if (M > 0 && d_depth) TRCHK(hipMemsetAsync(d_depth, 0xff, (size_t)M * 8, s));
-    if (M > 0 && d_ok) TRCHK(hipMemsetAsync(d_ok, 0, (size_t)M, s));
+    if (M > 0 && d_err) MICHK(hipMemsetAsync(d_err, 0xff, (size_t)M * 8, s));          /* all bits set: a NaN where no used observation is written */
+    if (M > 0 && d_depth) MICHK(hipMemsetAsync(d_depth, 0xff, (size_t)M * 8, s));
+    if (M > 0 && d_ok) MICHK(hipMemsetAsync(d_ok, 0, (size_t)M, s));
     if (T == 0) return 0;
     tr_args a;
     memset(&a, 0, sizeof a);
@@ -411,7 +389,7 @@ extern "C" int mi_degensac_triangulate_tracks_dev(const int64_t *d_track_offsets
     const int64_t wgs = (T + TR_GPW - 1) / TR_GPW;
     const dim3 grid((unsigned)std::min<int64_t>(wgs, TR_GRID)), block(TR_T);
     hipLaunchKernelGGL(tr_triangulate_kernel, grid, block, 0, s, a);
-    TRCHK(hipGetLastError());
+    MICHK(hipGetLastError());
     return 0;
 }
 
@@ -426,29 +404,18 @@ extern "C" int mi_degensac_triangulate_tracks(const int64_t *track_offsets, cons
                       cosang);
     if (rc) return rc;
     if (T == 0 && M == 0) return 0;
-    TrDevGuard dg; rc = dg.enter(device); if (rc) return rc;
+    MiDevGuard dg; rc = dg.enter(device); if (rc) return rc;
     const size_t t = (size_t)T, m = (size_t)M, r = (size_t)rows, ni = (size_t)n_images;
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    /* inputs: off, obs, img, n_tracks, kps, cams, poses; outputs: X, info, cost, cosang, err, ok, depth */
-    const size_t sz[14] = {(t + 1) * 8, m * 4, m * 4, 8, r * 16, ni * 32, ni * 96, t * 24, t * 20, t * 16, t * 8, m * 8, m, m * 8};
-    size_t at[15]; at[0] = 0;
-    for (int i = 0; i < 14; i++) at[i + 1] = at[i] + up(sz[i]);
-    char *D = nullptr;
-    struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
-    TRCHK(hipMalloc((void **)&D, at[14] + 256));
-    const void *in[7] = {track_offsets, obs, obs_image, n_tracks >= 0 ? &n_tracks : nullptr, kps, cams, poses};
-    for (int i = 0; i < 7; i++)
-        if (in[i] && sz[i]) TRCHK(hipMemcpy(D + at[i], in[i], sz[i], hipMemcpyHostToDevice));
-    void *out[7] = {X, info, cost, cosang, err, ok, depth};
-    auto dv = [&](int i, const void *h) { return h ? (void *)(D + at[i]) : nullptr; };
-    rc = mi_degensac_triangulate_tracks_dev((const int64_t *)D, (const int32_t *)dv(1, obs), (const int32_t *)dv(2, obs_image),
-                                            (const int64_t *)dv(3, in[3]), (const double *)dv(4, kps), rows, (const double *)dv(5, cams),
-                                            (const double *)dv(6, poses), n_images, T, M, min_angle_deg, max_reproj_px, max_iters, ftol, device, nullptr,
-                                            (double *)dv(7, X), (int32_t *)dv(8, info), (double *)dv(9, cost), (double *)dv(10, cosang),
-                                            (double *)dv(11, err), (uint8_t *)dv(12, ok), (double *)dv(13, depth));
+    MiStage st;
+    const int i_off = st.in(track_offsets, (t + 1) * 8), i_obs = st.in(obs, m * 4), i_img = st.in(obs_image, m * 4),
+              i_nt = st.in(n_tracks >= 0 ? &n_tracks : nullptr, 8), i_kps = st.in(kps, r * 16), i_cams = st.in(cams, ni * 32), i_poses = st.in(poses, ni * 96),
+              o_X = st.out(X, t * 24), o_info = st.out(info, t * 20), o_cost = st.out(cost, t * 16), o_cos = st.out(cosang, t * 8), o_err = st.out(err, m * 8),
+              o_ok = st.out(ok, m), o_depth = st.out(depth, m * 8);
+    rc = st.upload(); if (rc) return rc;
+    rc = mi_degensac_triangulate_tracks_dev(st.dev<int64_t>(i_off), st.dev<int32_t>(i_obs), st.dev<int32_t>(i_img), st.dev<int64_t>(i_nt), st.dev<double>(i_kps),
+                                            rows, st.dev<double>(i_cams), st.dev<double>(i_poses), n_images, T, M, min_angle_deg, max_reproj_px, max_iters,
+                                            ftol, device, nullptr, st.dev<double>(o_X), st.dev<int32_t>(o_info), st.dev<double>(o_cost),
+                                            st.dev<double>(o_cos), st.dev<double>(o_err), st.dev<uint8_t>(o_ok), st.dev<double>(o_depth));
     if (rc) return rc;
-    TRCHK(hipStreamSynchronize(nullptr));
-    for (int i = 0; i < 7; i++)
-        if (out[i] && sz[7 + i]) TRCHK(hipMemcpy(out[i], D + at[7 + i], sz[7 + i], hipMemcpyDeviceToHost));
-    return 0;
+    return st.finish();
 }

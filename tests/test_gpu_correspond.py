@@ -464,6 +464,30 @@ def test_numpy_entry_points(oracle_port):
         assert np.array_equal(g["rows"], want["rows"][co[p]:co[p + 1]]) and np.array_equal(g["pts"], want["pts"][co[p]:co[p + 1]])
 
 
+def test_host_form_with_every_optional_output_equals_the_device_form():
+    """mi_degensac_correspondences_pairs with entry, pts and resid given, on 2 entries with one empty and a capacity one below the total:
+    what it writes is what the device form writes on the same inputs, bit for bit"""
+    import torch
+    o = np.array([0, 6, 6, 12], np.int64); pr = np.array([[1, 0], [0, 2]], np.int32)          # image 1 is empty: entry 0 has no row
+    match = np.array([0, 7, -1, 3, 5, 2], np.int32); keep = np.array([1, 1, 1, 0, 1, 1], np.uint8)      # rows 0, 4, 5 are selected
+    rng = np.random.default_rng(21)
+    kps = rng.uniform(0, 100, (12, 2)); M = rng.normal(size=(2, 9)); gp = _lib.GuideParams(False, 0, 0.0); cap = 2
+    dev = _raw("pairs", (o, o, pr), _t(match), _t(keep), 0, _t(kps), _t(kps), 2, _t(M), gp, cap, want_resid=True)
+    torch.cuda.synchronize()
+    dev = [_np(x) for x in dev]
+    assert dev[2][0] == 3 and dev[1].tolist() == [0, 0, 3] and dev[3].tolist() == [1, 1]
+    host = [np.full((cap, 2), -1, np.int32), np.full(3, -5, np.int64), np.full(1, -5, np.int64), np.full(cap, -1, np.int32),
+            np.full((cap, 4), np.nan), np.full(cap, np.nan)]
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)          # noqa: E731
+    lp = o.ctypes.data_as(C.POINTER(C.c_int64))
+    rc = _lib.lib().mi_degensac_correspondences_pairs(lp, 3, lp, 3, pr.ctypes.data_as(C.POINTER(C.c_int32)), 2, vp(match), vp(keep), 0, vp(kps), vp(kps), 2,
+                                                      vp(M), C.byref(gp), cap, 0, vp(host[1]), vp(host[2]), vp(host[0]), vp(host[3]), vp(host[4]),
+                                                      vp(host[5]))
+    _lib.check_match(rc)
+    for h, d in zip(host, dev):
+        assert h.tobytes() == np.ascontiguousarray(d).tobytes()
+
+
 def test_a_second_stream():
     import torch
     c, pairs, match, keep = _case(3 * R + 5, 15)

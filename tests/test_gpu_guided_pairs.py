@@ -379,6 +379,12 @@ def test_stores_whose_first_offset_is_above_zero(oracle_port, model, et, norm, d
                      _p(idx, C.c_int32), _p(dist, C.c_float), _p(match, C.c_int32), _p(cnt, C.c_int32)))
     assert np.array_equal(idx, wi) and np.array_equal(_bits(dist), _bits(wd)) and np.array_equal(match, wm)
     assert list(cnt) == [int((w[0] >= 0).sum()) for w in want]
+    # host pointers without the one optional output, counts
+    i0 = np.full((n, 2), -7, np.int32); d0 = np.full((n, 2), -7, np.float32); m0 = np.full(n, -7, np.int32)
+    _lib.check_match(L.mi_degensac_match_guided_pairs(C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), _p(o1, C.c_int64), m,
+                     _p(o2, C.c_int64), m, _p(prs, C.c_int32), K, _lib.dptr(X1), _lib.dptr(X2), kd, _lib.dptr(Mh), C.byref(gp), 0,
+                     _p(i0, C.c_int32), _p(d0, C.c_float), _p(m0, C.c_int32), None))
+    assert np.array_equal(i0, idx) and np.array_equal(_bits(d0), _bits(dist)) and np.array_equal(m0, match)
     # device pointers: the guided 2-NN + decision (device counts and host counts), then the guided 2-NN alone
     dA, dB, dX1, dX2, dM = _t(A), _t(B), _t(X1), _t(X2), _t(Mh)
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)

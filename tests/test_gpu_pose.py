@@ -239,6 +239,10 @@ def test_numpy_form_per_entry_cameras_and_keep():
                                 min_parallax_deg=sc["deg"], with_points=True, with_candidates=True)
     _compare(sc, _as_results(K, len(sc["pts"]), res))
     assert len(matcher.relative_pose(sc["pts"], sc["off"], sc["F"].reshape(K, 3, 3), sc["cams"], pairs=sc["idx"])) == 4
+    # the same call without any optional output: R, t, front and info are the bits of the call above
+    bare = matcher.relative_pose(sc["pts"], sc["off"], sc["F"].reshape(K, 3, 3), sc["cams"], pairs=sc["idx"], keep=sc["keep"].astype(bool),
+                                 min_parallax_deg=sc["deg"])
+    assert len(bare) == 4 and all(a.tobytes() == b.tobytes() for a, b in zip(bare, res[:4]))
 
 
 def test_tensor_form_by_index_shared_camera_and_two_stores(torch):

@@ -213,6 +213,10 @@ def test_numpy_form_per_entry_cameras_and_keep():
                               keep=sc["keep"].astype(bool), max_trials=1, ftol=0.5, with_resid=True, with_F=True)
     _same(_as_results(K, res), _want("keep", 1, 0.5))
     assert len(matcher.refine_pose(sc["pts"], sc["off"], sc["pose"][:, :9].reshape(K, 3, 3), sc["pose"][:, 9:], sc["cams"], pairs=sc["idx"])) == 4
+    # the same call without any optional output: R, t, cost and info are the bits of the call above
+    bare = matcher.refine_pose(sc["pts"], sc["off"], sc["pose"][:, :9].reshape(K, 3, 3), sc["pose"][:, 9:], sc["cams"], pairs=sc["idx"],
+                               keep=sc["keep"].astype(bool), max_trials=1, ftol=0.5)
+    assert len(bare) == 4 and all(np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes() for a, b in zip(bare, res[:4]))
 
 
 def test_tensor_form_by_index_shared_camera_and_two_stores(torch):

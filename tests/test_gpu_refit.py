@@ -264,6 +264,21 @@ def test_numpy_entry_point(oracle_port):
     _compare(oracle_port, sc, dict(models=M.reshape(-1, 9), inlier=inl.astype(np.uint8), info=info, resid=resid), ref)
 
 
+def test_host_form_without_optional_outputs_equals_the_device_form(torch):
+    """mi_degensac_refit_lists with models_user, info and resid NULL, on 2 entries with one empty: models_out and inlier are what the device
+    form writes on the same inputs, bit for bit"""
+    rng = np.random.default_rng(5)
+    pts = rng.uniform(0.0, 100.0, (9, 4)); pts[:, 3] = pts[:, 1]; pts[8, 3] += 50.0          # 8 rows on y2 = y1, one far off it
+    sc = dict(pts=pts, off=np.array([0, 0, 9], np.int64), models=np.tile([0.0, 0, 0, 0, 0, -1, 0, 1, 0], (2, 1)), model="F", et=0, px_th=0.5)
+    dev, _ = _call(torch, sc)
+    assert dev["info"][0].tolist() == [0, 0, 0, R.SHORT] and dev["info"][1, 0] == 8
+    out = np.full((2, 9), -7.0); inl = np.full(9, 77, np.uint8); gp = _lib.GuideParams(False, 0, 0.5)
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)          # noqa: E731
+    _lib.check_match(_lib.lib().mi_degensac_refit_lists(vp(sc["pts"]), vp(sc["off"]), vp(sc["models"]), 2, 9, C.byref(gp), 4, 0, vp(out), vp(inl),
+                                                        None, None, None))
+    assert np.array_equal(out.view(np.int64), np.ascontiguousarray(dev["models"]).view(np.int64)) and np.array_equal(inl, dev["inlier"])
+
+
 def test_h_user_and_driver_form(torch, oracle_port):
     """the tensor call on H: driver_form=True is the C call; driver_form=False converts on the device in both directions, so it is compared
     with the restatement on the driver form the device's own conversion made, and its output with inv(H_c^T) of the driver-form output to

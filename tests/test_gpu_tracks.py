@@ -328,6 +328,22 @@ def test_numpy_entry_point():
     assert got["n_tracks"] == 0 and len(got["label"]) == 0 and got["track_offsets"].tolist() == [0]
 
 
+def test_host_form_without_optional_outputs_equals_the_device_form():
+    """mi_degensac_tracks with label, obs, obs_image and track_images NULL, on 3 images with one empty: what it writes is what the device
+    form writes on the same inputs, bit for bit (fills included), and the device form itself equals the restatement"""
+    off = np.array([0, 4, 4, 9], np.int64)
+    rows = np.array([[0, 5], [5, 8], [1, 6], [3, 3], [2, -1]], np.int32)
+    R, M, nulls = 9, 5, ("label", "obs", "obs_image", "track_images")
+    dev = _read(_raw(off, _t(rows), M, None, nulls), R, nulls)
+    assert tr.equal(dev, tr.tracks(rows, off), [k for k in tr.NAMES if k not in nulls]) and dev["n_tracks"] == 2
+    track = np.full(R, GUARD, np.int32); to = np.full(R // 2 + 1, GUARD, np.int64); n = np.full(2, GUARD, np.int64)
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)          # noqa: E731
+    _lib.check_match(_lib.lib().mi_degensac_tracks(off.ctypes.data_as(C.POINTER(C.c_int64)), 3, vp(rows), M, -1, 0, None, vp(track), vp(n[0:]),
+                                                   vp(n[1:]), vp(to), None, None, None))
+    assert (int(n[0]), int(n[1])) == (dev["n_tracks"], dev["n_obs"])
+    assert np.array_equal(track, dev["track"]) and np.array_equal(to, dev["track_offsets"])
+
+
 def test_reused_output_buffers_are_overwritten_down_to_the_fills():
     rows, off, rng = _mixed(17, R=1200, M=500)
     R = 1200
