@@ -1,32 +1,15 @@
 /* Host side of the C-ABI (include/mi_degensac.h): per-device state, contexts, the per-(device, stream)
  * scratch cache and the batch launch.  Included by mi_degensac.hip after the device headers. */
 #include <math.h>
-#include "mi_match_batch.h"
+#include "mi_estimator.h"
 
 static thread_local char g_err[512] = "";
-static void set_err(const char *fmt, const char *a = "", const char *b = "") { snprintf(g_err, sizeof g_err, fmt, a, b); }
-/* a failed call must not leave HIP's per-thread "last error" set: other users of the runtime in this process
- * (e.g. torch's lazy device initialisation) treat a stale error as their own */
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err("%s failed: %s", #x, hipGetErrorString(e_)); (void)hipGetLastError(); \
-    return MI_DEGENSAC_EHIP; } } while (0)
+void est_set_error(const char *fmt, const char *a, const char *b) { snprintf(g_err, sizeof g_err, fmt, a, b); }
 
 extern "C" const char *mi_degensac_last_error(void) { return g_err; }
 extern "C" const char *mi_degensac_version(void) { return "mi_degensac 0.2 (gfx950)"; }
 extern "C" const char *mi_degensac_kernel_name(int homography) { return homography ? "dg_find_homography_kernel" : "dg_find_fundamental_kernel"; }
 extern "C" int mi_degensac_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; } return n; }
-
-/* the calling thread's current device is put back when an entry point returns (the library may be embedded next to
- * PyTorch, whose allocations follow the current device) */
-struct DevGuard {
-    int prev = -1; bool armed = false;
-    int enter(int device)
-    {
-        if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-        if (prev != device) { HIPCHK(hipSetDevice(device)); armed = prev >= 0; }
-        return 0;
-    }
-    ~DevGuard() { if (armed) (void)hipSetDevice(prev); }
-};
 
 /* ---- per-device state: RNG tables uploaded once, device limits, the LDS exchange-order self-check ---- */
 struct DevState { bool init = false; int max_lds = 0, cus = 0, pool_par_ok = 0;
@@ -298,6 +281,7 @@ static int fill_params(const mi_degensac_params *p, int homography, int dim, dg_
     }
     return 0;
 }
+int est_check_params(const mi_degensac_params *prm, int homography, int dim) { dg_params chk; return fill_params(prm, homography, dim, &chk); }
 
 #ifdef MI_DEGENSAC_DEV
 static int *g_trace_dev = nullptr; static int g_trace_cap = 0;
@@ -346,11 +330,9 @@ static int launch_batch_impl(int homography, const double *d_p1, const double *d
  * (Round 6 built a "mixed-width" form of this launch — a 256-thread and a 128-thread kernel side by side on two streams, sharing the
  * ticket counter, with the narrow launch's long pairs handed to the wide one through a cross queue — measured it slower (154-168 ms
  * against 131 ms on C2 x 4096: profiles/r6_ab_mixed_width.log, DESIGN.md 3) and took it out again; commit d779705 has it.) */
-static int launch_batch(int homography, const double *d_p1, const double *d_p2, const int64_t *d_off, const int64_t *h_off,
-                        int n_pairs, int dim, const mi_degensac_params *prm, const uint32_t *d_seeds, int device,
-                        hipStream_t stream, double *d_model, uint8_t *d_mask, int32_t *d_stats, const mi_degensac_diag *diag = nullptr,
-                        int *d_err_copy = nullptr /* device word of the caller: receives the launch's error word (copied on `stream` right behind the kernel)
-                         */)
+int est_launch_batch(int homography, const double *d_p1, const double *d_p2, const int64_t *d_off, const int64_t *h_off,
+                     int n_pairs, int dim, const mi_degensac_params *prm, const uint32_t *d_seeds, int device,
+                     hipStream_t stream, double *d_model, uint8_t *d_mask, int32_t *d_stats, const mi_degensac_diag *diag, int *d_err_copy)
 {
     if (n_pairs <= 0) return 0;
     if (device < 0 || device >= 64) { set_err("bad device index"); return MI_DEGENSAC_EINVAL; }
@@ -629,7 +611,7 @@ static int batch_dev(int homography, const double *d_pts1, const double *d_pts2,
     if (device < 0 || device >= 64) { set_err("bad device index"); return MI_DEGENSAC_EINVAL; }
     if (mi_degensac_device_count() == 0) { set_err("no HIP device: this library has no CPU path"); return MI_DEGENSAC_ENODEV; }
     DevGuard g; int rc = g.enter(device); if (rc) return rc;
-    return launch_batch(homography, d_pts1, d_pts2, d_offsets, offsets_host, n_pairs, dim, prm, d_seeds, device, (hipStream_t)stream, d_M, d_mask, d_stats,
+    return est_launch_batch(homography, d_pts1, d_pts2, d_offsets, offsets_host, n_pairs, dim, prm, d_seeds, device, (hipStream_t)stream, d_M, d_mask, d_stats,
         diag);
 }
 extern "C" int mi_degensac_find_fundamental_batch_dev(const double *d_pts1, const double *d_pts2, const int64_t *d_offsets,
@@ -778,7 +760,7 @@ static int ctx_batch(mi_degensac_ctx *c, int homography, const double *p1, const
     if (timing) HIPCHK(hipEventRecord(ev[0], c->stream));
     HIPCHK(hipMemcpyAsync(c->d_io, c->h_pin, in_bytes, hipMemcpyHostToDevice, c->stream));
     if (timing) HIPCHK(hipEventRecord(ev[1], c->stream));
-    rc = launch_batch(homography, (const double *)(c->d_io + o_p1), (const double *)(c->d_io + o_p2), (const int64_t *)(c->d_io + o_off), ho,
+    rc = est_launch_batch(homography, (const double *)(c->d_io + o_p1), (const double *)(c->d_io + o_p2), (const int64_t *)(c->d_io + o_off), ho,
                       n_pairs, dim, prm, (const uint32_t *)(c->d_io + o_seed), c->device, c->stream,
                       (double *)(c->d_io + o_model), (uint8_t *)(c->d_io + o_mask), (int32_t *)(c->d_io + o_stats), nullptr, (int *)(c->d_io + o_err));
     if (rc) return rc;
@@ -878,6 +860,19 @@ static int thread_ctx(int device, mi_degensac_ctx **out)
     }
     *out = t.c[device];
     return 0;
+}
+int est_thread_stream(int device, hipStream_t *stream)
+{
+    mi_degensac_ctx *c; int rc = thread_ctx(device, &c); if (rc) return rc;
+    *stream = c->stream;
+    return 0;
+}
+int est_rerun(int device, int homography, const double *p1, const double *p2, const int64_t *off, int n_pairs, int dim, const mi_degensac_params *prm,
+              const uint32_t *seeds, double *model, uint8_t *mask, int32_t *stats)
+{
+    mi_degensac_ctx *c; int rc = thread_ctx(device, &c); if (rc) return rc;
+    const mi_degensac_params p2s = rerun_params(prm, homography);
+    return ctx_batch(c, homography, p1, p2, off, n_pairs, dim, &p2s, seeds, model, mask, stats, 1);
 }
 
 extern "C" int mi_degensac_find_fundamental_batch(const double *pts1, const double *pts2, const int64_t *offsets, int n_pairs, int dim,
@@ -1044,7 +1039,7 @@ static int pair_resids(int homography, const double *p1, const double *p2, int n
     HIPCHK(hipMemset(dh, 0, ((size_t)n + 3) * 4));
     mi_degensac_diag dg; dg.d_resids = nr ? dr : nullptr; dg.resid_runs = resid_runs; dg.struct_size = (int32_t)sizeof dg; dg.d_hist = hist ? dh : nullptr;
         dg.d_screen = nullptr;
-    rc = launch_batch(homography, d1, d2, doff, off, 1, dim, prm, ds, device, nullptr, dm, dk, dst, &dg); if (rc) return rc;
+    rc = est_launch_batch(homography, d1, d2, doff, off, 1, dim, prm, ds, device, nullptr, dm, dk, dst, &dg); if (rc) return rc;
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(model, dm, 72, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(mask, dk, (size_t)n, hipMemcpyDeviceToHost));
     if (stats) HIPCHK(hipMemcpy(stats, dst, 64, hipMemcpyDeviceToHost));
@@ -1061,539 +1056,3 @@ extern "C" int mi_degensac_find_homography_resids(const double *pts1, const doub
 extern "C" int mi_degensac_find_fundamental_hist(const double *pts1, const double *pts2, int n, int dim, const mi_degensac_params *prm,
         uint32_t seed, int device, double *F, uint8_t *mask, int32_t *stats, int32_t *hist)
 { return pair_resids(0, pts1, pts2, n, dim, prm, seed, device, F, mask, stats, nullptr, 0, hist); }
-
-/* ---- batched match-and-verify (include/mi_degensac.h mi_degensac_match_verify_batch[_dev]) ---------------------------------
- * matching, ratio test and ranks on the device -> ONE read of the per-pair tentative counts -> gather of the eligible pairs'
- * tentatives -> launch_batch -> scatter back to pair / query order.  Scratch: two stream-ordered blocks per call. */
-static int match_rc(int rc) { if (rc) set_err("%s", mi_degensac_match_last_error()); return rc; }
-
-/* everything of a match-and-verify call but its row layout */
-static int mv_check_params(int homography, const mi_degensac_match_params *mp, int kp_dim, int n_pairs)
-{
-    if (homography != 0 && homography != 1) { set_err("homography must be 0 or 1"); return MI_DEGENSAC_EINVAL; }
-    if (!mp) { set_err("match params are NULL"); return MI_DEGENSAC_EINVAL; }
-    if (!mt_norm_known(mp->norm) || mp->dim <= 0) { set_err("bad norm or descriptor dim"); return MI_DEGENSAC_EINVAL; }
-    if (const char *e = mt_norm_dim_error(mp->norm, mp->dim)) { set_err("%s", e); return MI_DEGENSAC_EINVAL; }
-    { mt_rule rule; if (const char *e = mt_decide_rule(mp, 1, &rule)) { set_err("%s", e); return MI_DEGENSAC_EINVAL; } }   /* the ratio too */
-    if (kp_dim != 2 && kp_dim != 6) { set_err("keypoint rows must be [n,2] or [n,6]"); return MI_DEGENSAC_EINVAL; }
-    { int fg; double r; if (const char *e = mt_second_nn(mp, &fg, &r)) { set_err("%s", e); return MI_DEGENSAC_EINVAL; } }
-    if (n_pairs < 0) { set_err("n_pairs < 0"); return MI_DEGENSAC_EINVAL; }
-    return 0;
-}
-
-static int mv_check(int homography, const mi_degensac_match_params *mp, const int64_t *off1, const int64_t *off2, int kp_dim, int n_pairs)
-{
-    int rc = mv_check_params(homography, mp, kp_dim, n_pairs); if (rc) return rc;
-    if (n_pairs == 0) return 0;
-    for (const int64_t *o : {off1, off2}) {
-        if (!o || o[0] < 0) { set_err("offsets must be given and start at >= 0"); return MI_DEGENSAC_EINVAL; }
-        for (int p = 0; p < n_pairs; p++) if (o[p + 1] < o[p]) { set_err("offsets must be non-decreasing"); return MI_DEGENSAC_EINVAL; }
-        if (o[n_pairs] - o[0] > 0x3fffffff) { set_err("too many descriptor rows in one batch"); return MI_DEGENSAC_EINVAL; }
-    }
-    return 0;
-}
-
-/* stream-ordered device blocks freed (on the stream) when the call returns, whichever way: block A (the matching half) and one block B
- * per estimator run on its tentatives (b2: the second model of the *_fh_* calls) */
-struct MvBlocks {
-    hipStream_t s; char *a = nullptr, *b = nullptr, *b2 = nullptr;
-    ~MvBlocks() { if (a) (void)hipFreeAsync(a, s); if (b) (void)hipFreeAsync(b, s); if (b2) (void)hipFreeAsync(b2, s); }
-};
-
-/* Where pair p's rows are, as int32 tables on the device (columns of mt_pair_rows).  out [K + 1]: its rows of idx / dist / keep / rank /
- * match / inlier; q1 / t2 [K]: the first keypoint row of its query image in kp1 and of its train image in kp2; back [K]: its first row
- * of the reverse search. */
-struct MvRows { const int32_t *out, *q1, *t2, *back; };
-
-/* what the matching half leaves on s (in block A) for the estimating half: nothing of it depends on the model */
-struct MvMatched { MvRows R; const int32_t *cnt, *rank, *idx; const uint8_t *keep; const double *kp1, *kp2; };
-
-/* the second half of a match-and-verify call, after the filter has written keep / rank / cnt on s: (a) the read of the counts */
-static int mv_counts(int K, const int32_t *cnt, hipStream_t s, std::vector<int32_t> &counts, int32_t *h_counts)
-{
-    /* the one synchronisation: the estimator's launch is sized and configured from the tentative counts on the host */
-    counts.resize(K);
-    HIPCHK(hipMemcpyAsync(counts.data(), cnt, (size_t)K * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (h_counts) memcpy(h_counts, counts.data(), (size_t)K * 4);
-    return 0;
-}
-
-/* (b) one model on the counted tentatives: its eligible list, block B (into b), gather and estimator on s; `half` says where the results
- * lie for the scatter stage */
-static int mv_half(int homography, int K, int kd, const mi_degensac_params *prm, const MvMatched &m, const std::vector<int32_t> &counts,
-                   const uint32_t *d_seeds, int device, hipStream_t s, char *&b, mt_half &half)
-{
-    int rc;
-    const int min_pts = homography ? 4 : 8;
-    std::vector<int64_t> est_off(1, 0); std::vector<int32_t> e_of_p(K, -1), pair_of_e;
-    for (int p = 0; p < K; p++)
-        if (counts[p] >= min_pts) { e_of_p[p] = (int32_t)pair_of_e.size(); pair_of_e.push_back(p); est_off.push_back(est_off.back() + counts[p]); }
-    const int E = (int)pair_of_e.size(); const int64_t T = est_off.back();
-
-    /* block B: est_off | e_of_p | pair_of_e (one upload), seeds, models, stats, the estimator's input rows and masks */
-    const size_t c_eoff = 0, c_eop = (size_t)(E + 1) * 8, c_poe = c_eop + (size_t)K * 4, c_all = c_poe + (size_t)E * 4;
-    std::vector<char> tab(c_all);
-    memcpy(tab.data() + c_eoff, est_off.data(), (size_t)(E + 1) * 8); memcpy(tab.data() + c_eop, e_of_p.data(), (size_t)K * 4);
-    if (E) memcpy(tab.data() + c_poe, pair_of_e.data(), (size_t)E * 4);
-    const size_t g_seed = align_up(c_all, 256), g_model = g_seed + align_up((size_t)E * 4, 256), g_stats = g_model + align_up((size_t)E * 72, 256),
-                 g_p1 = g_stats + align_up((size_t)E * 64, 256), g_p2 = g_p1 + align_up((size_t)T * kd * 8, 256),
-                 g_mask = g_p2 + align_up((size_t)T * kd * 8, 256), g_all = g_mask + align_up((size_t)T, 256);
-    HIPCHK(hipMallocAsync((void **)&b, g_all, s));
-    char *B = b;
-    const int64_t *d_eoff = (const int64_t *)(B + c_eoff); const int32_t *d_eop = (const int32_t *)(B + c_eop), *d_poe = (const int32_t *)(B + c_poe);
-    uint32_t *seeds_e = (uint32_t *)(B + g_seed); double *model_e = (double *)(B + g_model), *pts1 = (double *)(B + g_p1), *pts2 = (double *)(B + g_p2);
-    int32_t *stats_e = (int32_t *)(B + g_stats); uint8_t *mask_e = (uint8_t *)(B + g_mask);
-    half = mt_half{d_eop, d_eoff, model_e, stats_e, mask_e};
-    rc = match_rc(mt_batch_upload(device, s, tab.data(), c_all, B)); if (rc) return rc;
-    if (E > 0) {
-        rc = match_rc(mt_batch_gather(E, d_poe, d_eoff, m.R.out, m.R.q1, m.R.t2, m.keep, m.rank, m.idx, m.kp1, m.kp2, kd, d_seeds, s, pts1, pts2, seeds_e));
-        if (rc) return rc;
-        rc = launch_batch(homography, pts1, pts2, d_eoff, est_off.data(), E, kd, prm, seeds_e, device, s, model_e, mask_e, stats_e);
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-/* one model: counts, its half, the scatter back to pair / query order */
-static int mv_estimate(int homography, int K, int kd, const mi_degensac_params *prm, const MvMatched &m, const uint32_t *d_seeds, int device,
-                       hipStream_t s, MvBlocks &blk, double *d_model, int32_t *d_stats, int32_t *match, uint8_t *inlier, int32_t *h_counts)
-{
-    std::vector<int32_t> counts; mt_half h;
-    int rc = mv_counts(K, m.cnt, s, counts, h_counts); if (rc) return rc;
-    if ((rc = mv_half(homography, K, kd, prm, m, counts, d_seeds, device, s, blk.b, h))) return rc;
-    return match_rc(mt_batch_scatter(K, h.e_of_p, h.est_off, m.R.out, m.keep, m.rank, m.idx, h.model_e, h.stats_e, h.mask_e, s, d_model, d_stats, match, inlier));
-}
-
-/* the outputs of the two-model calls (include/mi_degensac.h mi_degensac_match_verify_fh_*), on the device; match / inlier_* at the first
- * output row */
-struct MvOutFH { double *model_f, *model_h; int32_t *match; uint8_t *inlier_f, *inlier_h; int32_t *stats_f, *stats_h, *summary; };
-
-/* both models on the same tentatives: the counts are read ONCE, then the fundamental matrix's half and the homography's half run one
- * after the other on s (each persistent estimator fills the device), and one scatter writes both and the per-pair summary */
-static int mv_estimate_fh(int K, int kd, const mi_degensac_params *prm_f, const mi_degensac_params *prm_h, const MvMatched &m, const uint32_t *d_seeds,
-                          int device, hipStream_t s, MvBlocks &blk, const MvOutFH &o, int32_t *h_counts)
-{
-    std::vector<int32_t> counts; mt_half f, h;
-    int rc = mv_counts(K, m.cnt, s, counts, h_counts); if (rc) return rc;
-    if ((rc = mv_half(0, K, kd, prm_f, m, counts, d_seeds, device, s, blk.b, f))) return rc;
-    if ((rc = mv_half(1, K, kd, prm_h, m, counts, d_seeds, device, s, blk.b2, h))) return rc;
-    return match_rc(mt_batch_scatter_fh(K, f, h, m.R.out, m.keep, m.rank, m.idx, s, o.model_f, o.stats_f, o.model_h, o.stats_h, o.match, o.inlier_f,
-                                        o.inlier_h, o.summary));
-}
-
-/* the pair list's refusals and its rows (see the pair-list section below); with_fginn: the *_fginn_pairs* entry points, which honour
- * second_nn / spatial_th where the plain ones refuse them */
-static int mvp_check(int homography, const mi_degensac_match_params *mp, int kd, const int64_t *off1, int m1, const int64_t *off2, int m2,
-                     const int32_t *pairs, int K, bool with_fginn, std::vector<mt_pair_rows> &rows, int64_t *n_out, int64_t *n_back)
-{
-    int rc = mv_check_params(homography, mp, kd, K); if (rc) return rc;
-    int fginn; double r; (void)mt_second_nn(mp, &fginn, &r);
-    if (fginn && !with_fginn) { set_err("the FGINN rule (second_nn = 1) is not part of the pair-list entry points: use mi_degensac_match_verify_batch*"
-                                        " or, over a pair list, mi_degensac_match_verify_fginn_pairs*"); return MI_DEGENSAC_EINVAL; }
-    *n_out = *n_back = 0;
-    if (K == 0) return 0;
-    rows.resize(K);
-    return match_rc(mt_pairs_layout(off1, m1, off2, m2, pairs, K, rows.data(), n_out, n_back));
-}
-
-static int mv_check_prm(const mi_degensac_params *prm, int homography, int kd) { dg_params chk; return fill_params(prm, homography, kd, &chk); }
-static int mv_check_device(int device)
-{
-    if (device < 0 || device >= 64) { set_err("bad device index"); return MI_DEGENSAC_EINVAL; }
-    if (mi_degensac_device_count() == 0) { set_err("no HIP device: this library has no CPU path"); return MI_DEGENSAC_ENODEV; }
-    return 0;
-}
-static int mv_check_null(const void *d_desc1, const void *d_desc2, const double *d_kp1, const double *d_kp2, int64_t n_out, int64_t n_back,
-                         const uint32_t *d_seeds, const double *d_model, const int32_t *d_match, const uint8_t *d_inlier)
-{
-    if (!d_seeds || !d_model || (n_out > 0 && (!d_desc1 || !d_kp1 || !d_match || !d_inlier)) || (n_back > 0 && (!d_desc2 || !d_kp2))) {
-        set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
-    return 0;
-}
-
-/* The matching half of the device path, arguments checked and the device current: pair p's rows are rows[p], n_out output rows and
- * n_back rows of the reverse search in all; side 1 / 2 (descriptors and keypoints) start at row r1 / r2 of the arrays passed.  The FGINN
- * step (mp->second_nn) takes the same rows as the 2-NN in front of it.  Everything is enqueued on s into block A; m says where it lies. */
-static int mv_match(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const double *d_kp1, const double *d_kp2, int64_t r1,
-                    int64_t r2, int kd, const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t n_back, int device, hipStream_t s, MvBlocks &blk,
-                    MvMatched &m)
-{
-    const int K = (int)rows.size();
-    int rc;
-    const int words = mt_row_words(mp->norm, mp->dim);
-    const bool mutual = mp->mutual != 0;
-    /* every row pointer moves to its side's first row; the tables: out [K + 1] | q1 [K] | t2 [K] | back [K] */
-    const uint32_t *q1 = (const uint32_t *)d_desc1 + (size_t)r1 * words, *q2 = (const uint32_t *)d_desc2 + (size_t)r2 * words;
-    const double *kp1 = d_kp1 + (size_t)r1 * kd, *kp2 = d_kp2 + (size_t)r2 * kd;
-    std::vector<int32_t> tab(4 * (size_t)K + 1);
-    for (int p = 0; p < K; p++) { tab[p] = rows[p].out; tab[K + 1 + p] = rows[p].q; tab[2 * K + 1 + p] = rows[p].t; tab[3 * K + 1 + p] = rows[p].back; }
-    tab[K] = (int32_t)n_out;
-
-    /* block A: tables, forward (and backward) 2-NN, keep / rank / count */
-    const size_t b_tab = align_up(tab.size() * 4, 256), b_idx = align_up((size_t)n_out * 8, 256), b_bidx = mutual ? align_up((size_t)n_back * 8, 256) : 0,
-                 b_keep = align_up((size_t)n_out, 256), b_cnt = align_up((size_t)K * 4, 256);
-    const size_t a_idx = b_tab, a_dist = a_idx + b_idx, a_bidx = a_dist + b_idx, a_bdist = a_bidx + b_bidx, a_keep = a_bdist + b_bidx,
-                 a_rank = a_keep + b_keep, a_cnt = a_rank + b_idx, a_all = a_cnt + b_cnt;
-    HIPCHK(hipMallocAsync((void **)&blk.a, a_all, s));
-    char *A = blk.a;
-    const int32_t *d_out = (const int32_t *)A;
-    const MvRows R{d_out, d_out + (K + 1), d_out + (2 * K + 1), d_out + (3 * K + 1)};
-    int32_t *idx = (int32_t *)(A + a_idx), *bidx = mutual ? (int32_t *)(A + a_bidx) : nullptr, *rank = (int32_t *)(A + a_rank), *cnt = (int32_t *)(A + a_cnt);
-    float *dist = (float *)(A + a_dist), *bdist = (float *)(A + a_bdist);
-    uint8_t *keep = (uint8_t *)(A + a_keep);
-    m = MvMatched{R, cnt, rank, idx, keep, kp1, kp2};
-    rc = match_rc(mt_batch_upload(device, s, tab.data(), tab.size() * 4, A)); if (rc) return rc;
-    rc = match_rc(mt_batch_knn2(mp->norm, words, q1, q2, rows.data(), K, (int)n_out, 0, device, s, idx, dist)); if (rc) return rc;
-    int fginn; double fginn_r; (void)mt_second_nn(mp, &fginn, &fginn_r);
-    if (fginn) { rc = match_rc(mt_batch_fginn(mp->norm, words, q1, q2, kp2, kd, rows.data(), K, (int)n_out, fginn_r, device, s, idx, dist)); if (rc) return rc; }
-    if (mutual) { rc = match_rc(mt_batch_knn2(mp->norm, words, q2, q1, rows.data(), K, (int)n_back, 1, device, s, bidx, bdist)); if (rc) return rc; }
-    mt_rule rule; (void)mt_decide_rule(mp, 1, &rule);
-    return match_rc(mt_batch_filter_rank(idx, dist, R.out, R.back, K, rule, bidx, mutual ? bdist : nullptr, s, keep, rank, cnt));
-}
-
-/* The device path of both forms, arguments checked: the matching half, then the estimating half; match / inlier are at the first output
- * row. */
-static int match_verify_rows(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const double *d_kp1,
-                             const double *d_kp2, int64_t r1, int64_t r2, int kd, const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t n_back,
-                             const mi_degensac_params *prm, const uint32_t *d_seeds, int device, hipStream_t s, double *d_model, int32_t *match, uint8_t *inlier, int32_t *d_stats, int32_t *h_counts)
-{
-    DevGuard g; int rc = g.enter(device); if (rc) return rc;
-    MvBlocks blk{s}; MvMatched m;
-    if ((rc = mv_match(mp, d_desc1, d_desc2, d_kp1, d_kp2, r1, r2, kd, rows, n_out, n_back, device, s, blk, m))) return rc;
-    return mv_estimate(homography, (int)rows.size(), kd, prm, m, d_seeds, device, s, blk, d_model, d_stats, match, inlier, h_counts);
-}
-
-/* the same with both models (mi_degensac_match_verify_fh_*): one matching half, one read of the counts */
-static int match_verify_fh_rows(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const double *d_kp1, const double *d_kp2,
-                                int64_t r1, int64_t r2, int kd, const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t n_back,
-                                const mi_degensac_params *prm_f, const mi_degensac_params *prm_h, const uint32_t *d_seeds, int device, hipStream_t s,
-                                const MvOutFH &o, int32_t *h_counts)
-{
-    DevGuard g; int rc = g.enter(device); if (rc) return rc;
-    MvBlocks blk{s}; MvMatched m;
-    if ((rc = mv_match(mp, d_desc1, d_desc2, d_kp1, d_kp2, r1, r2, kd, rows, n_out, n_back, device, s, blk, m))) return rc;
-    return mv_estimate_fh((int)rows.size(), kd, prm_f, prm_h, m, d_seeds, device, s, blk, o, h_counts);
-}
-
-extern "C" int mi_degensac_match_verify_batch_dev(int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
-        const int64_t *offsets1_host, const int64_t *offsets2_host, const double *d_kp1, const double *d_kp2, int kp_dim, int n_pairs,
-        const mi_degensac_params *prm, const uint32_t *d_seeds, int device, void *stream, double *d_model, int32_t *d_match, uint8_t *d_inlier,
-        int32_t *d_stats, int32_t *h_counts)
-{
-    int rc = mv_check(homography, mp, offsets1_host, offsets2_host, kp_dim, n_pairs);
-    if (rc || n_pairs == 0) return rc;
-    std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
-    mt_ragged_rows(offsets1_host, offsets2_host, n_pairs, o1, o2, rows);
-    const int64_t n1 = o1[n_pairs], n2 = o2[n_pairs];
-    if ((rc = mv_check_prm(prm, homography, kp_dim)) || (rc = mv_check_device(device)) ||
-        (rc = mv_check_null(d_desc1, d_desc2, d_kp1, d_kp2, n1, n2, d_seeds, d_model, d_match, d_inlier))) return rc;
-    return match_verify_rows(homography, mp, d_desc1, d_desc2, d_kp1, d_kp2, offsets1_host[0], offsets2_host[0], kp_dim, rows, n1, n2, prm, d_seeds, device, (hipStream_t)stream, d_model, d_match + offsets1_host[0], d_inlier + offsets1_host[0],
-                             d_stats, h_counts);
-}
-
-/* The host-pointer forms' re-run of the pairs discarded after a hand-over time-out (bit 10 of stats[15]): exactly their tentatives,
- * in the order the device gathered them (query order).  Pair p owns the rows out[p] .. out[p+1] of mt / in; the keypoints of its
- * query r are row b1[p] + r - out[p] of k1, those of train row t (pair-local) row b2[p] + t of k2. */
-static int mv_rerun(mi_degensac_ctx *c, int homography, int kd, int K, const mi_degensac_params *prm, const uint32_t *seeds, const int64_t *out,
-                    const int64_t *b1, const int64_t *b2, const double *k1, const double *k2, const int32_t *mt, double *model, uint8_t *in,
-                    std::vector<int32_t> &st)
-{
-    std::vector<int> redo;
-    for (int p = 0; p < K; p++) if (st[(size_t)p * 16 + 15] & 1024) redo.push_back(p);
-    if (redo.empty()) return 0;
-    std::vector<double> q1, q2; std::vector<int64_t> qo(1, 0); std::vector<uint32_t> qs;
-    for (int p : redo) {
-        for (int64_t i = out[p]; i < out[p + 1]; i++) if (mt[i] >= 0) {
-            const int64_t a = b1[p] + (i - out[p]), b = b2[p] + mt[i];
-            q1.insert(q1.end(), k1 + a * kd, k1 + (a + 1) * kd);
-            q2.insert(q2.end(), k2 + b * kd, k2 + (b + 1) * kd);
-        }
-        qo.push_back((int64_t)q1.size() / kd); qs.push_back(seeds[p]);
-    }
-    const int R = (int)redo.size();
-    const mi_degensac_params p2s = rerun_params(prm, homography);
-    std::vector<double> qm((size_t)R * 9); std::vector<uint8_t> qk((size_t)qo.back()); std::vector<int32_t> qst((size_t)R * 16);
-    int rc = ctx_batch(c, homography, q1.data(), q2.data(), qo.data(), R, kd, &p2s, qs.data(), qm.data(), qk.data(), qst.data(), 1);
-    if (rc) return rc;
-    for (int r = 0; r < R; r++) {
-        const int p = redo[r]; int64_t k = qo[r];
-        memcpy(model + (size_t)p * 9, qm.data() + (size_t)r * 9, 72);
-        for (int64_t i = out[p]; i < out[p + 1]; i++) if (mt[i] >= 0) in[i] = qk[k++];
-        memcpy(st.data() + (size_t)p * 16, qst.data() + (size_t)r * 16, 64); st[(size_t)p * 16 + 15] |= 2048;     /* bit 11: run again */
-    }
-    return 0;
-}
-
-/* The host-pointer forms: side 1 (rows off1[0] .. off1[m1] of desc1 / kp1) goes to the device, side 2 too unless `same` says both sides
- * name the same arrays, then the seeds; the device path runs on the calling thread's stream, the per-pair results come back (match /
- * inlier: at the first output row); pairs discarded after a hand-over time-out go through mv_rerun (ctx_batch's re-run, depth 1) on
- * exactly their gathered tentatives. */
-static int match_verify_host(int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *off1, int m1,
-                             const int64_t *off2, int m2, const double *kp1, const double *kp2, int kd, bool same, const std::vector<mt_pair_rows> &rows,
-                             int64_t n_out, int64_t n_back, const mi_degensac_params *prm, const uint32_t *seeds, int device, double *model, int32_t *match, uint8_t *inlier, int32_t *stats, int32_t *counts)
-{
-    const int K = (int)rows.size();
-    mi_degensac_ctx *c; int rc = thread_ctx(device, &c); if (rc) return rc;
-    DevGuard g; rc = g.enter(device); if (rc) return rc;
-    const int64_t n1 = off1[m1] - off1[0], n2 = off2[m2] - off2[0];
-    const size_t row = mt_row_bytes(mp->norm, mp->dim);
-    const size_t s_d1 = align_up(n1 * row, 256), s_d2 = same ? 0 : align_up(n2 * row, 256), s_k1 = align_up((size_t)n1 * kd * 8, 256),
-                 s_k2 = same ? 0 : align_up((size_t)n2 * kd * 8, 256), s_sd = align_up((size_t)K * 4, 256), s_mo = align_up((size_t)K * 72, 256),
-                 s_ma = align_up((size_t)n_out * 4, 256), s_in = align_up((size_t)n_out, 256), s_st = align_up((size_t)K * 64, 256);
-    const size_t a_d2 = s_d1, a_k1 = a_d2 + s_d2, a_k2 = a_k1 + s_k1, a_sd = a_k2 + s_k2, a_mo = a_sd + s_sd, a_ma = a_mo + s_mo, a_in = a_ma + s_ma,
-                 a_st = a_in + s_in, a_all = a_st + s_st;
-    const double *h_k1 = kp1 + off1[0] * kd, *h_k2 = kp2 + off2[0] * kd;
-    char *D = nullptr;
-    struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
-    HIPCHK(hipMalloc((void **)&D, a_all));
-    HIPCHK(hipMemcpy(D, (const char *)desc1 + off1[0] * row, n1 * row, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(D + a_k1, h_k1, (size_t)n1 * kd * 8, hipMemcpyHostToDevice));
-    if (!same) {
-        HIPCHK(hipMemcpy(D + a_d2, (const char *)desc2 + off2[0] * row, n2 * row, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(D + a_k2, h_k2, (size_t)n2 * kd * 8, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMemcpy(D + a_sd, seeds, (size_t)K * 4, hipMemcpyHostToDevice));
-    std::vector<int32_t> cnt(K), st((size_t)K * 16);
-    if ((rc = mv_check_prm(prm, homography, kd))) return rc;
-    rc = match_verify_rows(homography, mp, D, same ? D : D + a_d2, (const double *)(D + a_k1), (const double *)(D + (same ? a_k1 : a_k2)), 0, 0, kd, rows,
-                           n_out, n_back, prm, (const uint32_t *)(D + a_sd), device, c->stream, (double *)(D + a_mo), (int32_t *)(D + a_ma),
-                           (uint8_t *)(D + a_in), (int32_t *)(D + a_st), cnt.data());
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(model, D + a_mo, (size_t)K * 72, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(match, D + a_ma, (size_t)n_out * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(inlier, D + a_in, (size_t)n_out, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(st.data(), D + a_st, (size_t)K * 64, hipMemcpyDeviceToHost));
-    std::vector<int64_t> out(K + 1), b1(K), b2(K);
-    for (int p = 0; p < K; p++) { out[p] = rows[p].out; b1[p] = rows[p].q; b2[p] = rows[p].t; }
-    out[K] = n_out;
-    rc = mv_rerun(c, homography, kd, K, prm, seeds, out.data(), b1.data(), b2.data(), h_k1, h_k2, match, model, inlier, st);
-    if (rc) return rc;
-    if (stats) memcpy(stats, st.data(), (size_t)K * 64);
-    if (counts) memcpy(counts, cnt.data(), (size_t)K * 4);
-    return 0;
-}
-
-/* the ragged batch never asks whether its two sides are the same arrays: both are uploaded */
-extern "C" int mi_degensac_match_verify_batch(int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2,
-        const int64_t *offsets1, const int64_t *offsets2, const double *kp1, const double *kp2, int kd, int K, const mi_degensac_params *prm,
-        const uint32_t *seeds, int device, double *model, int32_t *match, uint8_t *inlier, int32_t *stats, int32_t *counts)
-{
-    int rc = mv_check(homography, mp, offsets1, offsets2, kd, K);
-    if (rc || K == 0) return rc;
-    if (!desc1 || !desc2 || !kp1 || !kp2 || !seeds || !model || !match || !inlier) { set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
-    std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
-    mt_ragged_rows(offsets1, offsets2, K, o1, o2, rows);
-    return match_verify_host(homography, mp, desc1, desc2, offsets1, K, offsets2, K, kp1, kp2, kd, false, rows, o1[K], o2[K], prm, seeds, device, model, match + offsets1[0], inlier + offsets1[0], stats, counts);
-}
-
-/* ---- match-and-verify over a pair list (include/mi_degensac.h mi_degensac_match_verify_pairs[_dev]) --------------------------
- * The same path with descriptors and keypoints stored once per image: mt_pairs_layout fills the rows from the stores' offsets and the
- * (i, j) list, where the ragged batch takes the identity list over its own offsets; everything after the layout step is shared. */
-static int match_verify_pairs_dev(bool with_fginn, int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
-        const int64_t *offsets1_host, int n_images1, const int64_t *offsets2_host, int n_images2, const double *d_kp1, const double *d_kp2, int kp_dim,
-        const int32_t *pairs_host, int n_pairs, const mi_degensac_params *prm, const uint32_t *d_seeds, int device, void *stream, double *d_model,
-        int32_t *d_match, uint8_t *d_inlier, int32_t *d_stats, int32_t *h_counts)
-{
-    std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
-    int rc = mvp_check(homography, mp, kp_dim, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, with_fginn, rows, &n_out, &n_back);
-    if (rc || n_pairs == 0) return rc;
-    if ((rc = mv_check_prm(prm, homography, kp_dim)) ||
-        (rc = mv_check_null(d_desc1, d_desc2, d_kp1, d_kp2, n_out, n_back, d_seeds, d_model, d_match, d_inlier)) || (rc = mv_check_device(device))) return rc;
-    return match_verify_rows(homography, mp, d_desc1, d_desc2, d_kp1, d_kp2, offsets1_host[0], offsets2_host[0], kp_dim, rows, n_out, n_back, prm, d_seeds,
-                             device, (hipStream_t)stream, d_model, d_match, d_inlier, d_stats, h_counts);
-}
-
-/* each store goes to the device once: one copy when both sides name the same arrays */
-static int match_verify_pairs(bool with_fginn, int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2,
-        const int64_t *offsets1, int n_images1, const int64_t *offsets2, int n_images2, const double *kp1, const double *kp2, int kd,
-        const int32_t *pairs, int K, const mi_degensac_params *prm, const uint32_t *seeds, int device, double *model, int32_t *match,
-        uint8_t *inlier, int32_t *stats, int32_t *counts)
-{
-    std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
-    int rc = mvp_check(homography, mp, kd, offsets1, n_images1, offsets2, n_images2, pairs, K, with_fginn, rows, &n_out, &n_back);
-    if (rc || K == 0) return rc;
-    if (!desc1 || !desc2 || !kp1 || !kp2 || !seeds || !model || !match || !inlier) { set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
-    const bool same = desc1 == desc2 && kp1 == kp2 && n_images1 == n_images2 && !memcmp(offsets1, offsets2, ((size_t)n_images1 + 1) * 8);
-    return match_verify_host(homography, mp, desc1, desc2, offsets1, n_images1, offsets2, n_images2, kp1, kp2, kd, same, rows, n_out, n_back, prm, seeds,
-                             device, model, match, inlier, stats, counts);
-}
-
-#define MVP_DEV_ARGS int homography, const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2, const int64_t *offsets1_host, \
-        int n_images1, const int64_t *offsets2_host, int n_images2, const double *d_kp1, const double *d_kp2, int kp_dim, const int32_t *pairs_host, \
-        int n_pairs, const mi_degensac_params *prm, const uint32_t *d_seeds, int device, void *stream, double *d_model, int32_t *d_match, \
-        uint8_t *d_inlier, int32_t *d_stats, int32_t *h_counts
-#define MVP_DEV_PASS homography, mp, d_desc1, d_desc2, offsets1_host, n_images1, offsets2_host, n_images2, d_kp1, d_kp2, kp_dim, pairs_host, n_pairs, prm, \
-        d_seeds, device, stream, d_model, d_match, d_inlier, d_stats, h_counts
-#define MVP_HOST_ARGS int homography, const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1, int n_images1, \
-        const int64_t *offsets2, int n_images2, const double *kp1, const double *kp2, int kd, const int32_t *pairs, int K, \
-        const mi_degensac_params *prm, const uint32_t *seeds, int device, double *model, int32_t *match, uint8_t *inlier, int32_t *stats, int32_t *counts
-#define MVP_HOST_PASS homography, mp, desc1, desc2, offsets1, n_images1, offsets2, n_images2, kp1, kp2, kd, pairs, K, prm, seeds, device, model, match, \
-        inlier, stats, counts
-extern "C" int mi_degensac_match_verify_pairs_dev(MVP_DEV_ARGS) { return match_verify_pairs_dev(false, MVP_DEV_PASS); }
-extern "C" int mi_degensac_match_verify_pairs(MVP_HOST_ARGS) { return match_verify_pairs(false, MVP_HOST_PASS); }
-/* the FGINN forms: the same calls without the refusal of second_nn = 1 (second_nn = 0 or the layout before spatial_th: the plain calls) */
-extern "C" int mi_degensac_match_verify_fginn_pairs_dev(MVP_DEV_ARGS) { return match_verify_pairs_dev(true, MVP_DEV_PASS); }
-extern "C" int mi_degensac_match_verify_fginn_pairs(MVP_HOST_ARGS) { return match_verify_pairs(true, MVP_HOST_PASS); }
-#undef MVP_DEV_ARGS
-#undef MVP_DEV_PASS
-#undef MVP_HOST_ARGS
-#undef MVP_HOST_PASS
-
-/* ---- match once, verify F and H (include/mi_degensac.h mi_degensac_match_verify_fh_*) -----------------------------------------
- * The matching half of the calls above once, then both estimators on its tentatives: mv_match -> mv_counts (the one synchronisation)
- * -> mv_half for F (pairs with >= 8 tentatives) -> mv_half for H (>= 4) -> mt_batch_scatter_fh.  Every refusal comes before a device is
- * looked for. */
-static int mvfh_check_prm(const mi_degensac_params *prm_f, const mi_degensac_params *prm_h, int kd)
-{
-    int rc = mv_check_prm(prm_f, 0, kd); if (rc) return rc;
-    return mv_check_prm(prm_h, 1, kd);
-}
-static int mvfh_check_null(const void *d_desc1, const void *d_desc2, const double *d_kp1, const double *d_kp2, int64_t n_out, int64_t n_back,
-                           const uint32_t *d_seeds, const MvOutFH &o, bool need_summary)
-{
-    if (!d_seeds || !o.model_f || !o.model_h || (need_summary && !o.summary) ||
-        (n_out > 0 && (!d_desc1 || !d_kp1 || !o.match || !o.inlier_f || !o.inlier_h)) || (n_back > 0 && (!d_desc2 || !d_kp2))) {
-        set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
-    return 0;
-}
-
-extern "C" int mi_degensac_match_verify_fh_batch_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
-        const int64_t *offsets1_host, const int64_t *offsets2_host, const double *d_kp1, const double *d_kp2, int kp_dim, int n_pairs,
-        const mi_degensac_params *prm_f, const mi_degensac_params *prm_h, const uint32_t *d_seeds, int device, void *stream, double *d_model_f,
-        double *d_model_h, int32_t *d_match, uint8_t *d_inlier_f, uint8_t *d_inlier_h, int32_t *d_stats_f, int32_t *d_stats_h, int32_t *d_summary,
-        int32_t *h_counts)
-{
-    int rc = mv_check(0, mp, offsets1_host, offsets2_host, kp_dim, n_pairs);
-    if (rc || n_pairs == 0) return rc;
-    std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
-    mt_ragged_rows(offsets1_host, offsets2_host, n_pairs, o1, o2, rows);
-    const int64_t n1 = o1[n_pairs], n2 = o2[n_pairs], r1 = offsets1_host[0];
-    const MvOutFH o{d_model_f, d_model_h, d_match ? d_match + r1 : nullptr, d_inlier_f ? d_inlier_f + r1 : nullptr, d_inlier_h ? d_inlier_h + r1 : nullptr,
-                    d_stats_f, d_stats_h, d_summary};
-    if ((rc = mvfh_check_prm(prm_f, prm_h, kp_dim)) || (rc = mvfh_check_null(d_desc1, d_desc2, d_kp1, d_kp2, n1, n2, d_seeds, o, true)) ||
-        (rc = mv_check_device(device))) return rc;
-    return match_verify_fh_rows(mp, d_desc1, d_desc2, d_kp1, d_kp2, r1, offsets2_host[0], kp_dim, rows, n1, n2, prm_f, prm_h, d_seeds, device,
-                                (hipStream_t)stream, o, h_counts);
-}
-
-extern "C" int mi_degensac_match_verify_fh_pairs_dev(const mi_degensac_match_params *mp, const void *d_desc1, const void *d_desc2,
-        const int64_t *offsets1_host, int n_images1, const int64_t *offsets2_host, int n_images2, const double *d_kp1, const double *d_kp2, int kp_dim,
-        const int32_t *pairs_host, int n_pairs, const mi_degensac_params *prm_f, const mi_degensac_params *prm_h, const uint32_t *d_seeds, int device,
-        void *stream, double *d_model_f, double *d_model_h, int32_t *d_match, uint8_t *d_inlier_f, uint8_t *d_inlier_h, int32_t *d_stats_f,
-        int32_t *d_stats_h, int32_t *d_summary, int32_t *h_counts)
-{
-    std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
-    int rc = mvp_check(0, mp, kp_dim, offsets1_host, n_images1, offsets2_host, n_images2, pairs_host, n_pairs, true, rows, &n_out, &n_back);
-    if (rc || n_pairs == 0) return rc;
-    const MvOutFH o{d_model_f, d_model_h, d_match, d_inlier_f, d_inlier_h, d_stats_f, d_stats_h, d_summary};
-    if ((rc = mvfh_check_prm(prm_f, prm_h, kp_dim)) || (rc = mvfh_check_null(d_desc1, d_desc2, d_kp1, d_kp2, n_out, n_back, d_seeds, o, true)) ||
-        (rc = mv_check_device(device))) return rc;
-    return match_verify_fh_rows(mp, d_desc1, d_desc2, d_kp1, d_kp2, offsets1_host[0], offsets2_host[0], kp_dim, rows, n_out, n_back, prm_f, prm_h,
-                                d_seeds, device, (hipStream_t)stream, o, h_counts);
-}
-
-/* the host outputs of the two-model calls; match / inlier_* at the first output row */
-struct MvHostFH { double *model_f, *model_h; int32_t *match; uint8_t *inlier_f, *inlier_h; int32_t *stats_f, *stats_h, *summary, *counts; };
-
-/* The host-pointer forms, as match_verify_host: one upload, the device path, the results back, then mv_rerun per model for the pairs
- * whose stats row OF THAT MODEL carries bit 10; the summary of a pair run again is counted again from its masks. */
-static int match_verify_fh_host(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *off1, int m1,
-                                const int64_t *off2, int m2, const double *kp1, const double *kp2, int kd, bool same,
-                                const std::vector<mt_pair_rows> &rows, int64_t n_out, int64_t n_back, const mi_degensac_params *prm_f,
-                                const mi_degensac_params *prm_h, const uint32_t *seeds, int device, const MvHostFH &h)
-{
-    const int K = (int)rows.size();
-    mi_degensac_ctx *c; int rc = thread_ctx(device, &c); if (rc) return rc;
-    DevGuard g; rc = g.enter(device); if (rc) return rc;
-    const int64_t n1 = off1[m1] - off1[0], n2 = off2[m2] - off2[0];
-    const size_t row = mt_row_bytes(mp->norm, mp->dim);
-    const size_t s_d1 = align_up(n1 * row, 256), s_d2 = same ? 0 : align_up(n2 * row, 256), s_k1 = align_up((size_t)n1 * kd * 8, 256),
-                 s_k2 = same ? 0 : align_up((size_t)n2 * kd * 8, 256), s_sd = align_up((size_t)K * 4, 256), s_mo = align_up((size_t)K * 72, 256),
-                 s_ma = align_up((size_t)n_out * 4, 256), s_in = align_up((size_t)n_out, 256), s_st = align_up((size_t)K * 64, 256),
-                 s_su = align_up((size_t)K * 16, 256);
-    const size_t a_d2 = s_d1, a_k1 = a_d2 + s_d2, a_k2 = a_k1 + s_k1, a_sd = a_k2 + s_k2, a_mf = a_sd + s_sd, a_mh = a_mf + s_mo, a_ma = a_mh + s_mo,
-                 a_if = a_ma + s_ma, a_ih = a_if + s_in, a_sf = a_ih + s_in, a_sh = a_sf + s_st, a_su = a_sh + s_st, a_all = a_su + s_su;
-    const double *h_k1 = kp1 + off1[0] * kd, *h_k2 = kp2 + off2[0] * kd;
-    char *D = nullptr;
-    struct Free { char *&p; ~Free() { (void)hipFree(p); } } fr{D};
-    HIPCHK(hipMalloc((void **)&D, a_all));
-    HIPCHK(hipMemcpy(D, (const char *)desc1 + off1[0] * row, n1 * row, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(D + a_k1, h_k1, (size_t)n1 * kd * 8, hipMemcpyHostToDevice));
-    if (!same) {
-        HIPCHK(hipMemcpy(D + a_d2, (const char *)desc2 + off2[0] * row, n2 * row, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(D + a_k2, h_k2, (size_t)n2 * kd * 8, hipMemcpyHostToDevice));
-    }
-    HIPCHK(hipMemcpy(D + a_sd, seeds, (size_t)K * 4, hipMemcpyHostToDevice));
-    std::vector<int32_t> cnt(K), stf((size_t)K * 16), sth((size_t)K * 16), sum((size_t)K * 4);
-    const MvOutFH o{(double *)(D + a_mf), (double *)(D + a_mh), (int32_t *)(D + a_ma), (uint8_t *)(D + a_if), (uint8_t *)(D + a_ih),
-                    (int32_t *)(D + a_sf), (int32_t *)(D + a_sh), (int32_t *)(D + a_su)};
-    rc = match_verify_fh_rows(mp, D, same ? D : D + a_d2, (const double *)(D + a_k1), (const double *)(D + (same ? a_k1 : a_k2)), 0, 0, kd, rows, n_out,
-                              n_back, prm_f, prm_h, (const uint32_t *)(D + a_sd), device, c->stream, o, cnt.data());
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(h.model_f, o.model_f, (size_t)K * 72, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h.model_h, o.model_h, (size_t)K * 72, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h.match, o.match, (size_t)n_out * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h.inlier_f, o.inlier_f, (size_t)n_out, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h.inlier_h, o.inlier_h, (size_t)n_out, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(stf.data(), o.stats_f, (size_t)K * 64, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(sth.data(), o.stats_h, (size_t)K * 64, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(sum.data(), o.summary, (size_t)K * 16, hipMemcpyDeviceToHost));
-    std::vector<int64_t> out(K + 1), b1(K), b2(K);
-    for (int p = 0; p < K; p++) { out[p] = rows[p].out; b1[p] = rows[p].q; b2[p] = rows[p].t; }
-    out[K] = n_out;
-    std::vector<uint8_t> redo(K, 0);
-    for (int p = 0; p < K; p++) redo[p] = ((stf[(size_t)p * 16 + 15] | sth[(size_t)p * 16 + 15]) & 1024) != 0;
-    rc = mv_rerun(c, 0, kd, K, prm_f, seeds, out.data(), b1.data(), b2.data(), h_k1, h_k2, h.match, h.model_f, h.inlier_f, stf); if (rc) return rc;
-    rc = mv_rerun(c, 1, kd, K, prm_h, seeds, out.data(), b1.data(), b2.data(), h_k1, h_k2, h.match, h.model_h, h.inlier_h, sth); if (rc) return rc;
-    for (int p = 0; p < K; p++) if (redo[p]) {
-        int32_t nf = 0, nh = 0, nfh = 0;
-        for (int64_t i = out[p]; i < out[p + 1]; i++) { nf += h.inlier_f[i] != 0; nh += h.inlier_h[i] != 0; nfh += h.inlier_f[i] && h.inlier_h[i]; }
-        sum[(size_t)p * 4 + 1] = nf; sum[(size_t)p * 4 + 2] = nh; sum[(size_t)p * 4 + 3] = nfh;
-    }
-    if (h.stats_f) memcpy(h.stats_f, stf.data(), (size_t)K * 64);
-    if (h.stats_h) memcpy(h.stats_h, sth.data(), (size_t)K * 64);
-    if (h.summary) memcpy(h.summary, sum.data(), (size_t)K * 16);
-    if (h.counts) memcpy(h.counts, cnt.data(), (size_t)K * 4);
-    return 0;
-}
-
-static int mvfh_check_host_null(const void *desc1, const void *desc2, const double *kp1, const double *kp2, const uint32_t *seeds, const MvHostFH &h)
-{
-    if (!desc1 || !desc2 || !kp1 || !kp2 || !seeds || !h.model_f || !h.model_h || !h.match || !h.inlier_f || !h.inlier_h) {
-        set_err("NULL argument"); return MI_DEGENSAC_EINVAL; }
-    return 0;
-}
-
-extern "C" int mi_degensac_match_verify_fh_batch(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
-        const int64_t *offsets2, const double *kp1, const double *kp2, int kd, int K, const mi_degensac_params *prm_f, const mi_degensac_params *prm_h,
-        const uint32_t *seeds, int device, double *model_f, double *model_h, int32_t *match, uint8_t *inlier_f, uint8_t *inlier_h, int32_t *stats_f,
-        int32_t *stats_h, int32_t *summary, int32_t *counts)
-{
-    int rc = mv_check(0, mp, offsets1, offsets2, kd, K);
-    if (rc || K == 0) return rc;
-    const int64_t r1 = offsets1[0];
-    const MvHostFH h{model_f, model_h, match ? match + r1 : nullptr, inlier_f ? inlier_f + r1 : nullptr, inlier_h ? inlier_h + r1 : nullptr, stats_f,
-                     stats_h, summary, counts};
-    if ((rc = mvfh_check_prm(prm_f, prm_h, kd)) || (rc = mvfh_check_host_null(desc1, desc2, kp1, kp2, seeds, h))) return rc;
-    std::vector<int64_t> o1, o2; std::vector<mt_pair_rows> rows;
-    mt_ragged_rows(offsets1, offsets2, K, o1, o2, rows);
-    return match_verify_fh_host(mp, desc1, desc2, offsets1, K, offsets2, K, kp1, kp2, kd, false, rows, o1[K], o2[K], prm_f, prm_h, seeds, device, h);
-}
-
-extern "C" int mi_degensac_match_verify_fh_pairs(const mi_degensac_match_params *mp, const void *desc1, const void *desc2, const int64_t *offsets1,
-        int n_images1, const int64_t *offsets2, int n_images2, const double *kp1, const double *kp2, int kd, const int32_t *pairs, int K,
-        const mi_degensac_params *prm_f, const mi_degensac_params *prm_h, const uint32_t *seeds, int device, double *model_f, double *model_h,
-        int32_t *match, uint8_t *inlier_f, uint8_t *inlier_h, int32_t *stats_f, int32_t *stats_h, int32_t *summary, int32_t *counts)
-{
-    std::vector<mt_pair_rows> rows; int64_t n_out, n_back;
-    int rc = mvp_check(0, mp, kd, offsets1, n_images1, offsets2, n_images2, pairs, K, true, rows, &n_out, &n_back);
-    if (rc || K == 0) return rc;
-    const MvHostFH h{model_f, model_h, match, inlier_f, inlier_h, stats_f, stats_h, summary, counts};
-    if ((rc = mvfh_check_prm(prm_f, prm_h, kd)) || (rc = mvfh_check_host_null(desc1, desc2, kp1, kp2, seeds, h))) return rc;
-    const bool same = desc1 == desc2 && kp1 == kp2 && n_images1 == n_images2 && !memcmp(offsets1, offsets2, ((size_t)n_images1 + 1) * 8);
-    return match_verify_fh_host(mp, desc1, desc2, offsets1, n_images1, offsets2, n_images2, kp1, kp2, kd, same, rows, n_out, n_back, prm_f, prm_h, seeds,
-                                device, h);
-}

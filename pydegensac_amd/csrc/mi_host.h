@@ -1,7 +1,8 @@
 /* The host plumbing under the matcher, the guided stage and the list stages (correspondences, tracks, refit, pose, pose refinement,
  * triangulation): the HIP error check, the EINVAL refusal, the device guard, the stream-ordered scratch block and the staging block of
  * the host-pointer forms.  Not part of the C-ABI.  Every message goes through mt_set_error to mi_degensac_match_last_error().
- * (The estimator units keep their own DevGuard / HIPCHK in mi_degensac_host.inc: they report through mi_degensac_last_error.) */
+ * (The estimator host and the match-and-verify stage have their own DevGuard / HIPCHK in mi_estimator.h: they report through
+ * mi_degensac_last_error.) */
 #ifndef MI_HOST_H
 #define MI_HOST_H
 #include <hip/hip_runtime.h>
@@ -48,8 +49,8 @@ struct MiScratch {
  * an absent optional: its slot takes no room and dev() gives null for it, so the _dev form sees the same "absent".
  *   upload()   lays the slots out at 256-byte steps, makes the one hipMalloc (never for 0 bytes; freed at scope exit on every return path)
  *              and copies every input that is neither null nor empty;
- *   the caller runs its _dev form on the null stream with dev<T>(slot);
- *   finish()   the one hipStreamSynchronize(nullptr), then every out() that is neither null nor empty comes back;
+ *   the caller runs its _dev form with dev<T>(slot), on the null stream or on a stream s of its own;
+ *   finish(s)  the one hipStreamSynchronize of that stream, then every out() that is neither null nor empty comes back;
  *   fetch()    the first `bytes` of a late() slot, after finish(). */
 struct MiStage {
     enum { IN, OUT, LATE };
@@ -71,9 +72,9 @@ struct MiStage {
             if (s.kind == IN && s.bytes) MICHK(hipMemcpy(D + s.at, s.h, s.bytes, hipMemcpyHostToDevice));
         return 0;
     }
-    int finish()
+    int finish(hipStream_t s = nullptr)
     {
-        MICHK(hipStreamSynchronize(nullptr));
+        MICHK(hipStreamSynchronize(s));
         for (const Slot &s : sl)
             if (s.kind == OUT && s.bytes) MICHK(hipMemcpy(s.h, D + s.at, s.bytes, hipMemcpyDeviceToHost));
         return 0;

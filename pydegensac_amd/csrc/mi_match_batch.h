@@ -1,5 +1,5 @@
 /* Internal interface between the batched matcher stages (mi_matcher.hip) and the match-and-verify orchestration in
- * mi_degensac_host.inc, which needs launch_batch.  Not part of the C-ABI: hidden symbols of libmi_degensac.so.
+ * mi_match_verify.hip, which reaches the estimator through mi_estimator.h.  Not part of the C-ABI: hidden symbols of libmi_degensac.so.
  *
  * The batched stages have one row layout, mt_pair_rows, for the ragged batch and for a pair list over image stores.  Rows and row
  * offsets passed here are relative (offs[0] = 0) and every device pointer is already moved to its side's first row.

@@ -15,7 +15,7 @@
  * every thread keeps a 4 x 4 block of running sums in registers and its own running top-2 per query; the 16 threads
  * sharing a query merge their candidates at the end.  The train set is additionally split over blockIdx.y (see mt_knn2_kernel).
  * The batched form (mt_knn2_batch_kernel) runs the same tile body over every pair's query tiles in one launch and feeds the match-and-
- * verify path in mi_degensac_host.inc (filter + rank, gather, scatter below).  It has one row layout, mt_pair_rows (mi_match_batch.h),
+ * verify path in mi_match_verify.hip (filter + rank, gather, scatter below).  It has one row layout, mt_pair_rows (mi_match_batch.h),
  * and two ways to fill it: a pair list over image stores (mi_degensac_match_*_pairs*: rows stored once per image, a list of (i, j);
  * mt_pairs_layout) and the ragged batch (mi_degensac_match_*_batch*), which is the list whose entry p is (image p, image p) with its
  * answers at its queries' own rows (mt_identity_rows). */

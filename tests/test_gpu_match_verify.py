@@ -355,3 +355,88 @@ def test_uneven_sides_with_fginn_equal_the_composed_calls(mutual):
     assert int(inl[int(o1[3]):].sum()) >= 8
     plain = tensor_api.match_and_verify_batch_tensors(k1, k2, a, b, UNEVEN1, UNEVEN2, model="F", mutual=mutual, max_iters=2000, seeds=seeds)
     assert cnt[3] > plain[4][3]                                         # the twins veto matches under the plain rule only
+
+
+# ---- the host-pointer forms with and without their optional outputs -------------------------------------------------------------------
+# three views of one scene and a list whose entries are: estimated by both models; short for both (< 4 tentatives); estimated by H only
+# (4 .. 7); entry 0 the other way round
+FOLD_COUNTS = [41, 39, 40]
+FOLD_LIST = [(0, 1), (2, 1), (0, 2), (1, 0)]
+FOLD_SEEDS = [5, 4000000000, 7, 11]
+FOLD_RATIO = 0.8
+
+
+@functools.lru_cache(maxsize=None)
+def _fold_scene():
+    """(xy [120, 2], desc float32 [120, 32]) under FOLD_COUNTS: image 0 is the first view of a two-view scene; image 1 holds the second
+    views of its rows 0 .. 29 with near-equal descriptors and 9 unrelated rows, image 2 those of its rows 30 .. 35 and 34 unrelated
+    rows, both shuffled.  Under FOLD_RATIO with the mutual check the list's tentative counts are 30, 1, 7, 30 (stated by the tests)."""
+    rng = np.random.default_rng(55)
+    n, dim = sum(FOLD_COUNTS), 32
+    p1, p2, _, _ = syn.two_view_fundamental(41, 0.8, 0.1, seed=52)
+    xy = rng.uniform(0, 500, (n, 2)); desc = rng.normal(size=(n, dim)).astype(np.float32)
+    near = lambda rows: desc[rows] + 0.1 * rng.normal(size=(len(rows), dim)).astype(np.float32)          # noqa: E731
+    xy[:41] = p1[:, :2]
+    perm = rng.permutation(39)
+    xy[41:80] = np.r_[p2[:30, :2], xy[71:80]][perm]; desc[41:80] = np.r_[near(np.arange(30)), desc[71:80]][perm]
+    perm = rng.permutation(40)
+    xy[80:] = np.r_[p2[30:36, :2], xy[86:]][perm]; desc[80:] = np.r_[near(np.arange(30, 36)), desc[86:]][perm]
+    return xy, desc
+
+
+def _fold_stores(front=3, back=2):
+    """_fold_scene between junk rows (the stores' first offsets are above zero): (desc, xy, a second copy of each in other memory, the
+    offsets [4])"""
+    xy, desc = _fold_scene(); rng = np.random.default_rng(56)
+    frame = lambda x: np.concatenate([rng.normal(size=(front,) + x.shape[1:]), x, rng.normal(size=(back,) + x.shape[1:])]).astype(x.dtype)          # noqa: E731
+    A, X = frame(desc), frame(xy)
+    return A, X, A.copy(), X.copy(), np.r_[0, np.cumsum(FOLD_COUNTS)].astype(np.int64) + front
+
+
+def _fold_pairs_host(entry, head, prms, outs, optional, second):
+    """one call of a pair-list host-pointer entry on _fold_stores: head = the arguments in front of the match params, prms = the
+    estimator params, outs = the required output arrays, optional = the optional ones or None for NULL each; second = pass side 2 as
+    distinct arrays of equal content (else the same store is named on both sides)"""
+    A, X, A2, X2, o = _fold_stores()
+    if not second:
+        A2, X2 = A, X
+    K = len(FOLD_LIST); M = len(FOLD_COUNTS)
+    mp = _lib.MatchParams(0, A.shape[1], FOLD_RATIO, True)
+    seeds = np.asarray(FOLD_SEEDS, np.uint32); prs = np.ascontiguousarray(FOLD_LIST, np.int32)
+    lp, dp = C.POINTER(C.c_int64), C.POINTER(C.c_double)
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))          # noqa: E731
+    rc = entry(*head, C.byref(mp), A.ctypes.data, A2.ctypes.data, o.ctypes.data_as(lp), M, o.ctypes.data_as(lp), M, X.ctypes.data_as(dp),
+               X2.ctypes.data_as(dp), 2, ptr(prs), K, *[C.byref(p) for p in prms], ptr(seeds), 0, *[ptr(a) for a in outs], *[ptr(a) for a in optional])
+    assert rc == 0, _lib.lib().mi_degensac_last_error()
+
+
+@pytest.mark.parametrize("model", ["F", "H"])
+def test_pair_list_host_form_with_and_without_its_optional_outputs(model):
+    """mi_degensac_match_verify_pairs on stores whose first offsets are above zero, with one entry short for both models and one that
+    only H can take: model / match / inlier are the same bytes with stats and counts given, with both NULL, and with the store passed
+    as two distinct equal copies (both sides uploaded), and they are the bytes of the _dev form"""
+    import torch
+    xy, desc = _fold_scene(); K = len(FOLD_LIST)
+    tk, td = _t(xy), _t(desc)
+    want = tensor_api.match_and_verify_pairs_tensors(tk, tk, td, td, FOLD_COUNTS, FOLD_COUNTS, FOLD_LIST, model=model, ratio=FOLD_RATIO, mutual=True,
+                                                     max_iters=2000, seeds=FOLD_SEEDS)
+    torch.cuda.synchronize()
+    cnt = want[4]; n = int(want[5][-1])
+    assert list(cnt) == [30, 1, 7, 30] and n == 41 + 40 + 41 + 39
+    assert list(want[3][:, MI_ST_SAMPLES].cpu().numpy() > 0) == [True, False, model == "H", True]
+    prm = matcher.estimator_params(model, max_iters=2000)
+    first = None
+    for optional, second in ((True, False), (False, False), (True, True)):
+        Mh = np.zeros((K, 9)); mh = np.full(n, -7, np.int32); ih = np.full(n, 7, np.uint8)
+        opt = [np.zeros((K, 16), np.int32), np.zeros(K, np.int32)] if optional else [None, None]
+        _fold_pairs_host(_lib.lib().mi_degensac_match_verify_pairs, (int(model == "H"),), [prm], [Mh, mh, ih], opt, second)
+        if first is None:
+            first = (Mh, mh, ih)
+            Mu = _t(Mh).view(K, 3, 3)
+            Mu = tensor_api._h_user_form(Mu) if model == "H" else Mu
+            assert torch.equal(Mu.view(torch.int64), want[0].contiguous().view(torch.int64))
+            assert np.array_equal(mh, want[1].cpu().numpy()) and np.array_equal(ih.astype(bool), want[2].cpu().numpy()) and ih.max() <= 1
+        for a, b in zip(first, (Mh, mh, ih)):
+            assert a.tobytes() == b.tobytes(), (optional, second)
+        if optional:
+            assert np.array_equal(opt[0][:, DET], want[3].cpu().numpy()[:, DET]) and np.array_equal(opt[1], cnt), second

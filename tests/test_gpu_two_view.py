@@ -360,6 +360,41 @@ def test_c_pair_list_entry_on_stores_whose_first_offsets_are_above_zero():
     _c_check(o, cnt, want, slice(0, n))
 
 
+# ---- the host-pointer form with and without its optional outputs ---------------------------------------------------------------------------
+def test_pair_list_host_form_with_and_without_its_optional_outputs():
+    """mi_degensac_match_verify_fh_pairs on the stores of tests/test_gpu_match_verify._fold_stores (first offsets above zero; one entry
+    short for both models, one that only H can take): F / H / match / inlier_f / inlier_h are the same bytes with stats_f, stats_h,
+    summary and counts given, with all four NULL, and with the store passed as two distinct equal copies (both sides uploaded), and they
+    are the bytes of the _dev form"""
+    import torch
+    from tests.test_gpu_match_verify import FOLD_COUNTS, FOLD_LIST, FOLD_RATIO, FOLD_SEEDS, _fold_pairs_host, _fold_scene
+    xy, desc = _fold_scene(); K = len(FOLD_LIST)
+    tk, td = _t(xy), _t(desc)
+    want = tensor_api.match_and_verify_fh_pairs_tensors(tk, tk, td, td, FOLD_COUNTS, FOLD_COUNTS, FOLD_LIST, ratio=FOLD_RATIO, mutual=True,
+                                                        seeds=FOLD_SEEDS, f_params=LP["F"], h_params=LP["H"])
+    torch.cuda.synchronize()
+    cnt = want[8]; n = int(want[9][-1])
+    assert list(cnt) == [30, 1, 7, 30] and n == 41 + 40 + 41 + 39
+    assert list(want[5][:, 0].cpu().numpy() > 0) == [True, False, False, True] and list(want[6][:, 0].cpu().numpy() > 0) == [True, False, True, True]
+    prms = [matcher.estimator_params("F", **LP["F"]), matcher.estimator_params("H", **LP["H"])]
+    first = None
+    for optional, second in ((True, False), (False, False), (True, True)):
+        req = [np.zeros((K, 9)), np.zeros((K, 9)), np.full(n, -7, np.int32), np.full(n, 7, np.uint8), np.full(n, 7, np.uint8)]
+        opt = [np.zeros((K, 16), np.int32), np.zeros((K, 16), np.int32), np.full((K, 4), -7, np.int32), np.zeros(K, np.int32)] if optional else [None] * 4
+        _fold_pairs_host(_lib.lib().mi_degensac_match_verify_fh_pairs, (), prms, req, opt, second)
+        if first is None:
+            first = req
+            assert torch.equal(_bits(_t(req[0]).view(K, 3, 3)), _bits(want[0]))
+            assert torch.equal(_bits(tensor_api._h_user_form(_t(req[1]).view(K, 3, 3))), _bits(want[1]))
+            assert np.array_equal(req[2], want[2].cpu().numpy()) and max(req[3].max(), req[4].max()) <= 1
+            assert np.array_equal(req[3].astype(bool), want[3].cpu().numpy()) and np.array_equal(req[4].astype(bool), want[4].cpu().numpy())
+        for a, b in zip(first, req):
+            assert a.tobytes() == b.tobytes(), (optional, second)
+        if optional:
+            assert np.array_equal(opt[0][:, DET], want[5].cpu().numpy()[:, DET]) and np.array_equal(opt[1][:, DET], want[6].cpu().numpy()[:, DET]), second
+            assert np.array_equal(opt[2], want[7].cpu().numpy()) and np.array_equal(opt[3], cnt), second
+
+
 # ---- a second stream ------------------------------------------------------------------------------------------------------------------------
 def test_second_stream_gives_the_same_bits():
     import torch
