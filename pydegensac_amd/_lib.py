@@ -417,25 +417,37 @@ def tri_group():
     return int(lib().mi_degensac_triangulate_tile(0))
 
 
-def check(rc):
+def check(rc, last_error="mi_degensac_last_error", value_error=True):
     if rc != 0:
-        msg = lib().mi_degensac_last_error().decode()
-        if rc == -1:
+        msg = getattr(lib(), last_error)().decode()
+        if rc == -1 and value_error:
             raise ValueError(msg)          # std::invalid_argument -> ValueError in the reference binding
         raise MiDegensacError(f"mi_degensac error {rc}: {msg}")
 
 
-def check_match(rc):
-    """check() for the matcher-stage entry points, whose message is mi_degensac_match_last_error()"""
-    if rc != 0:
-        msg = lib().mi_degensac_match_last_error().decode()
-        if rc == -1:
-            raise ValueError(msg)
-        raise MiDegensacError(f"mi_degensac error {rc}: {msg}")
+def check_match(rc, value_error=True):
+    """check() for the matcher-stage entry points, whose message is mi_degensac_match_last_error(); value_error=False: the calls that
+    have always raised MiDegensacError for an invalid argument too"""
+    check(rc, "mi_degensac_match_last_error", value_error)
 
 
 def dptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+# keyed by the dtype itself: its name is slow to form, and this sits under every call
+_POINTERS = {np.dtype(name): C.POINTER(ct) for name, ct in (("float64", C.c_double), ("float32", C.c_float), ("int64", C.c_int64),
+                                                            ("int32", C.c_int32), ("uint32", C.c_uint32), ("uint8", C.c_uint8))}
+
+
+def ptr(a):
+    """a numpy array as the typed pointer the argtypes table asks for"""
+    return a.ctypes.data_as(_POINTERS[a.dtype])
+
+
+def vptr(a, empty_none=False):
+    """a numpy array as void *; None stays None (a nullable argument), and with empty_none so does an array without elements"""
+    return None if a is None or (empty_none and a.size == 0) else a.ctypes.data_as(C.c_void_p)
 
 
 def make_params(px_th, conf, max_iters, error_type, sym_check, laf_coef, degen=True, flags=0, tuning=0):

@@ -47,6 +47,48 @@ def _prep(desc1, desc2, norm):
     return _NORMS[norm], np.ascontiguousarray(a), np.ascontiguousarray(b)
 
 
+# ---- the argument checks' small parts: every text is the caller's, which check comes first is the caller's order ----
+def _float(x, text):
+    """float(x); raises ValueError(text) for what has no float value"""
+    try:
+        return float(x)
+    except (TypeError, ValueError):
+        raise ValueError(text)
+
+
+def _number(x, text, lo=-np.inf, hi=np.inf):
+    """a real number (not a bool) with lo <= x <= hi, as a float; NaN is outside every range; raises ValueError(text)"""
+    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not lo <= float(x) <= hi:
+        raise ValueError(text)
+    return float(x)
+
+
+def _integer(x, text, lo=None, hi=None):
+    """an integer (not a bool) with lo <= x <= hi where a bound is given, as an int; raises ValueError(text)"""
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or (lo is not None and x < lo) or (hi is not None and x > hi):
+        raise ValueError(text)
+    return int(x)
+
+
+def _sd(x):
+    """(shape, dtype) of an optional array or tensor, as the check_* functions take it"""
+    return None if x is None else (tuple(x.shape), x.dtype)
+
+
+def _rows_list(arrays, text):
+    """one array per pair / image as a list of arrays, all 2-D with the dtype and width of entry 0, and at least one; raises
+    ValueError(text)"""
+    a = [np.asarray(x) for x in arrays]
+    if len(a) == 0 or any(x.ndim != 2 or x.dtype != a[0].dtype or x.shape[1] != a[0].shape[1] for x in a):
+        raise ValueError(text)
+    return a
+
+
+def _knn_out(n, with_match):
+    """the 2-NN result arrays of n query rows with their fills: idx -1, dist inf, and with with_match match -1 (else None)"""
+    return np.full((n, 2), -1, np.int32), np.full((n, 2), np.inf, np.float32), np.full(n, -1, np.int32) if with_match else None
+
+
 # the decision rule of a matcher call (include/mi_degensac.h MI_DEGENSAC_DECIDE_*): ratio as a float (1.0 where it is not read), mutual as
 # a bool, decide = the bit flags, max_dist as a float (0.0 where it is not read)
 Rule = collections.namedtuple("Rule", "ratio mutual decide max_dist")
@@ -62,10 +104,7 @@ def check_rule(ratio, mutual=False, max_dist=None, fginn=False):
     if ratio is None:
         decide |= _lib.DECIDE_NO_RATIO; r = 1.0
     else:
-        try:
-            r = float(ratio)
-        except (TypeError, ValueError):
-            raise ValueError("ratio should be a number, or None for no ratio test")
+        r = _float(ratio, "ratio should be a number, or None for no ratio test")
         if not np.isfinite(r) or r <= 0:
             raise ValueError("ratio should be finite and > 0")
     if isinstance(mutual, str):
@@ -76,10 +115,7 @@ def check_rule(ratio, mutual=False, max_dist=None, fginn=False):
         decide |= _lib.DECIDE_BACK_RATIO
     md = 0.0
     if max_dist is not None:
-        try:
-            md = float(max_dist)
-        except (TypeError, ValueError):
-            raise ValueError("max_dist should be a number")
+        md = _float(max_dist, "max_dist should be a number")
         if not (np.isfinite(md) and md >= 0 and md <= float(np.finfo(np.float32).max)):
             raise ValueError("max_dist should be finite and >= 0")
         decide |= _lib.DECIDE_MAX_DIST
@@ -92,21 +128,16 @@ def _run(desc1, desc2, norm, ratio, mutual, want_keep, device, max_dist=None):
     rule = check_rule(ratio, mutual, max_dist)
     code, a, b = _prep(desc1, desc2, norm)
     n1, n2, dim = a.shape[0], b.shape[0], a.shape[1]
-    idx = np.full((n1, 2), -1, np.int32); dist = np.full((n1, 2), np.inf, np.float32)
+    idx, dist, _ = _knn_out(n1, False)
     keep = np.zeros(n1, np.uint8) if want_keep else None
-    out = (idx.ctypes.data_as(C.POINTER(C.c_int32)), dist.ctypes.data_as(C.POINTER(C.c_float)),
-           keep.ctypes.data_as(C.POINTER(C.c_uint8)) if want_keep else None)
+    out = (_lib.ptr(idx), _lib.ptr(dist), _lib.ptr(keep) if want_keep else None)
     if rule.decide == 0:
         rc = _lib.lib().mi_degensac_match(code, a.ctypes.data_as(C.c_void_p), n1, b.ctypes.data_as(C.c_void_p), n2, dim, rule.ratio,
                                           int(rule.mutual), int(device), *out)
     else:
         mp = _lib.match_params(code, dim, rule)
         rc = _lib.lib().mi_degensac_match_ex(C.byref(mp), a.ctypes.data_as(C.c_void_p), n1, b.ctypes.data_as(C.c_void_p), n2, int(device), *out)
-    if rc != 0:
-        msg = _lib.lib().mi_degensac_match_last_error().decode()
-        if rc == -1:
-            raise ValueError(msg)
-        raise _lib.MiDegensacError(f"mi_degensac error {rc}: {msg}")
+    _lib.check_match(rc)
     return idx, dist, keep
 
 
@@ -191,9 +222,7 @@ def kpts_to_xyA(kpts, device=0):
     if k.ndim != 2 or k.shape[1] != 4:
         raise ValueError("keypoints should be an array [n, 4] = (x, y, size, angle)")
     out = np.zeros((k.shape[0], 6))
-    rc = _lib.lib().mi_degensac_kpts_to_xyA(k.ctypes.data_as(C.POINTER(C.c_float)), k.shape[0], int(device), _lib.dptr(out))
-    if rc != 0:
-        raise _lib.MiDegensacError(f"mi_degensac error {rc}: {_lib.lib().mi_degensac_match_last_error().decode()}")
+    _lib.check_match(_lib.lib().mi_degensac_kpts_to_xyA(_lib.ptr(k), k.shape[0], int(device), _lib.dptr(out)), value_error=False)
     return out
 
 
@@ -218,18 +247,11 @@ def quant_params(preset="rootsift", normalize=None, scale=None, offset=None):
     elif isinstance(nz, bool) or nz not in (QUANT_NONE, QUANT_L2, QUANT_L1ROOT):
         raise ValueError('normalize should be "none", "l2" or "l1root"')
     if scale is not None:
-        try:
-            sc = float(scale)
-        except (TypeError, ValueError):
-            raise ValueError("scale should be a number")
+        sc = _float(scale, "scale should be a number")
     if not (np.isfinite(sc) and sc > 0):
         raise ValueError("scale should be finite and > 0")
     if offset is not None:
-        if isinstance(offset, bool) or not isinstance(offset, (int, np.integer)):
-            raise ValueError("offset should be an integer 0 .. 255")
-        of = int(offset)
-    if not 0 <= of <= 255:
-        raise ValueError("offset should be an integer 0 .. 255")
+        of = _integer(offset, "offset should be an integer 0 .. 255", 0, 255)
     return int(nz), float(sc), of
 
 
@@ -279,10 +301,7 @@ def _check_sides(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_
     if model not in ("F", "H"):
         raise ValueError("model should be 'F' or 'H'")
     if ratio is not None:                       # None = no ratio test (check_rule)
-        try:
-            r = float(ratio)
-        except (TypeError, ValueError):
-            raise ValueError("ratio should be a number")
+        r = _float(ratio, "ratio should be a number")
         if not np.isfinite(r) or r <= 0:
             raise ValueError("ratio should be finite and > 0")
     if len(d1_shape) != 2 or len(d2_shape) != 2 or d1_shape[1] != d2_shape[1] or d1_shape[1] == 0:
@@ -302,8 +321,17 @@ def _check_sides(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_
         raise ValueError("norm 'l2_u8' needs uint8 descriptors")
     if norm == "l2_u8" and d1_shape[1] > L2_U8_MAX_DIM:
         raise ValueError(f"norm 'l2_u8' takes dim <= {L2_U8_MAX_DIM}: use float32 descriptors with norm 'l2' beyond that")
+    kind = _kps_kind((k1_shape, k1_dtype), (k2_shape, k2_dtype))
+    if k1_shape[0] != d1_shape[0] or k2_shape[0] != d2_shape[0]:
+        raise ValueError("one keypoint row per descriptor row")
+    return _NORMS[norm], kind
+
+
+def _kps_kind(kps1, kps2):
+    """the layout of the two sides' keypoints, each (shape, dtype): "xy" for float64 rows [n, 2] / [n, 6], "kpts" for float32 [n, 4];
+    raises ValueError"""
     kinds = []
-    for shp, dt in ((k1_shape, k1_dtype), (k2_shape, k2_dtype)):
+    for shp, dt in (kps1, kps2):
         name = _dtype_name(dt)
         if len(shp) == 2 and name == "float64" and shp[1] in (2, 6):
             kinds.append(("xy", shp[1]))
@@ -313,9 +341,7 @@ def _check_sides(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_
             raise ValueError("keypoints should be float64 [n, 2] / [n, 6] rows or float32 [n, 4] = (x, y, size, angle)")
     if kinds[0] != kinds[1]:
         raise ValueError("kps1 and kps2 should have the same layout")
-    if k1_shape[0] != d1_shape[0] or k2_shape[0] != d2_shape[0]:
-        raise ValueError("one keypoint row per descriptor row")
-    return _NORMS[norm], kinds[0][0]
+    return kinds[0][0]
 
 
 def _counts_to_offsets(counts, n_rows, per, side_by_side):
@@ -381,20 +407,58 @@ def check_match_pairs_args(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_
                          "match_and_verify_fginn_pairs / match_and_verify_fginn_pairs_tensors over a pair list")
     code, kind = _check_sides(model, ratio, norm, d1_shape, d1_dtype, d2_shape, d2_dtype, k1_shape, k1_dtype, k2_shape, k2_dtype)
     offs = _counts_to_offsets((counts1, counts2), (d1_shape[0], d2_shape[0]), "image", True)
+    pr, po = _check_pair_list(pairs, offs[0], offs[1])
+    return code, kind, offs[0], offs[1], pr, po, None if seeds is None else _seeds_u32(seeds, len(pr))
+
+
+def _check_pair_list(pairs, o1, o2):
+    """a pair list over two stores with the image offsets o1 / o2 -> (pairs as contiguous int32 [K, 2], pair_offsets int64 [K + 1]);
+    raises ValueError"""
     pr = np.asarray(pairs)
     if pr.ndim != 2 or pr.shape[1] != 2 or not np.issubdtype(pr.dtype, np.integer):
         raise ValueError("pairs should be an integer array [K, 2] of (image of store 1, image of store 2)")
     K = pr.shape[0]
     if K == 0:
         raise ValueError("at least one pair")
-    m1, m2 = len(offs[0]) - 1, len(offs[1]) - 1
+    m1, m2 = len(o1) - 1, len(o2) - 1
     if (pr < 0).any() or (pr[:, 0] >= m1).any() or (pr[:, 1] >= m2).any():
         raise ValueError(f"pairs hold an image index outside its store ({m1} and {m2} images)")
     pr = np.ascontiguousarray(pr, np.int32)
-    po = np.zeros(K + 1, np.int64); np.cumsum(np.diff(offs[0])[pr[:, 0]], out=po[1:])
-    if po[-1] > 0x3fffffff or np.diff(offs[1])[pr[:, 1]].sum() > 0x3fffffff:
+    po = np.zeros(K + 1, np.int64); np.cumsum(np.diff(o1)[pr[:, 0]], out=po[1:])
+    if po[-1] > 0x3fffffff or np.diff(o2)[pr[:, 1]].sum() > 0x3fffffff:
         raise ValueError("too many rows in one pair list")
-    return code, kind, offs[0], offs[1], pr, po, None if seeds is None else _seeds_u32(seeds, K)
+    return pr, po
+
+
+# ---- a checked layout and the entry points' layout arguments: the order inside each family is the ABI (include/mi_degensac.h) ----
+# pr None = the ragged batch (entry p = pair p, po = o1), else a pair list over image stores; K entries, n output rows
+Layout = collections.namedtuple("Layout", "name o1 o2 pr po K n")
+
+
+def layout(o1, o2, pr=None, po=None):
+    if pr is None:
+        return Layout("batch", o1, o2, None, o1, len(o1) - 1, int(o1[-1]))
+    return Layout("pairs", o1, o2, pr, po, len(pr), int(po[-1]))
+
+
+def _stores(L):
+    return _lib.ptr(L.o1), len(L.o1) - 1, _lib.ptr(L.o2), len(L.o2) - 1
+
+
+def knn_layout(L, dim):
+    """mi_degensac_match_knn2_* / _fginn_knn2_*: the arguments between the descriptors and (FGINN: the keypoints,) the device"""
+    return (_lib.ptr(L.o1), _lib.ptr(L.o2), L.K, dim) if L.pr is None else _stores(L) + (_lib.ptr(L.pr), L.K, dim)
+
+
+def verify_layout(L, kp1, kp2, kp_dim):
+    """mi_degensac_match_verify_* and _verify_fh_*: the arguments between the descriptors and the estimator's parameter block(s); kp1 /
+    kp2 = the keypoint pointers as the entry point takes them"""
+    return (_lib.ptr(L.o1), _lib.ptr(L.o2), kp1, kp2, kp_dim, L.K) if L.pr is None else _stores(L) + (kp1, kp2, kp_dim, _lib.ptr(L.pr), L.K)
+
+
+def guided_layout(L, kp1, kp2, kp_dim):
+    """mi_degensac_match_guided_*: the arguments between the descriptors and the models"""
+    return (_lib.ptr(L.o1), _lib.ptr(L.o2), kp1, kp2, kp_dim, L.K) if L.pr is None else _stores(L) + (_lib.ptr(L.pr), L.K, kp1, kp2, kp_dim)
 
 
 def exhaustive_pairs(n, ordered=False):
@@ -410,10 +474,7 @@ def exhaustive_pairs(n, ordered=False):
 
 def check_fginn_th(fginn_th, name="fginn_th"):
     """the FGINN radius of the matcher calls: a finite number >= 0; raises ValueError"""
-    try:
-        r = float(fginn_th)
-    except (TypeError, ValueError):
-        raise ValueError(f"{name} should be a number")
+    r = _float(fginn_th, f"{name} should be a number")
     if not (np.isfinite(r) and r >= 0):
         raise ValueError(f"{name} should be finite and >= 0")
     return r
@@ -456,11 +517,7 @@ def check_guided_args(model, px_th, error_type, models_shape, models_dtype, K):
         raise ValueError(f"models should be [K, 3, 3] = [{K}, 3, 3], one model per pair")
     if _dtype_name(models_dtype) != "float64":
         raise ValueError("models should be float64")
-    px = _MODEL_DEFAULTS[model][0] if px_th is None else px_th
-    try:
-        px = float(px)
-    except (TypeError, ValueError):
-        raise ValueError("px_th should be a number")
+    px = _float(_MODEL_DEFAULTS[model][0] if px_th is None else px_th, "px_th should be a number")
     if not px >= 0:
         raise ValueError("px_th should be >= 0 (and not NaN)")
     et = _error_type(error_type_dict_fundamental if model == "F" else error_type_dict_homography, error_type)
@@ -485,6 +542,11 @@ def _h_user_form(M):
     return out
 
 
+def _driver_models(M, model, driver_form, K):
+    """the models of a call as the library takes them: contiguous float64 [K, 9], H in the driver's form"""
+    return np.ascontiguousarray(M if (model == "F" or driver_form) else _h_driver_form(M), np.float64).reshape(K, 9)
+
+
 def _set_last_stats(st, cnt):
     """the per-pair stats rows [K, 16] and tentative counts [K] of a match-and-verify call -> last_stats()"""
     from . import api
@@ -500,13 +562,10 @@ def _stack_pairs(kps1_list, kps2_list, desc1_list, desc2_list, model, ratio, nor
     K = len(desc1_list)
     if not (len(kps1_list) == len(kps2_list) == len(desc2_list) == K):
         raise ValueError("kps1_list, kps2_list, desc1_list and desc2_list should hold one entry per pair")
-    a = [np.asarray(x) for x in desc1_list]; b = [np.asarray(x) for x in desc2_list]
-    k1 = [np.asarray(x) for x in kps1_list]; k2 = [np.asarray(x) for x in kps2_list]
     if K == 0:
         raise ValueError("at least one pair")
-    for lst in (a, b, k1, k2):
-        if any(x.ndim != 2 or x.dtype != lst[0].dtype or x.shape[1] != lst[0].shape[1] for x in lst):
-            raise ValueError("every pair's arrays should be 2-D with the dtype and width of pair 0")
+    a, b, k1, k2 = (_rows_list(lst, "every pair's arrays should be 2-D with the dtype and width of pair 0")
+                    for lst in (desc1_list, desc2_list, kps1_list, kps2_list))
     c1 = [x.shape[0] for x in a]; c2 = [x.shape[0] for x in b]
     if [x.shape[0] for x in k1] != c1 or [x.shape[0] for x in k2] != c2:
         raise ValueError("one keypoint row per descriptor row")
@@ -525,21 +584,26 @@ def _finish_pairs(code, kind, A, B, K1, K2, device):
     return A, B, np.ascontiguousarray(K1, np.float64), np.ascontiguousarray(K2, np.float64)
 
 
-def _guided_host(code, A, B, K1, K2, o1, o2, Md, model, rule, px, et, device, fginn_r=None):
-    """mi_degensac_match_guided_batch (fginn_r, a checked radius: mi_degensac_match_guided_fginn_batch) on prepared host arrays; Md =
-    [K, 9] driver-form models.  Returns (match, idx, dist, counts)."""
-    K = len(o1) - 1; n1 = A.shape[0]
-    idx = np.full((n1, 2), -1, np.int32); dist = np.full((n1, 2), np.inf, np.float32); match = np.full(n1, -1, np.int32)
-    cnt = np.zeros(K, np.int32)
-    Md = np.ascontiguousarray(Md, np.float64).reshape(K, 9)
+def _guided_host(L, code, A, B, K1, K2, Md, model, rule, px, et, device, fginn_r=None):
+    """mi_degensac_match_guided_batch / _pairs (fginn_r, a checked radius: mi_degensac_match_guided_fginn_*) on prepared host arrays;
+    L = the checked layout, Md = [K, 9] driver-form models.  Returns (match, idx, dist, counts)."""
+    idx, dist, match = _knn_out(L.n, True)
+    cnt = np.zeros(L.K, np.int32)
     mp = _lib.match_params(code, A.shape[1], rule, fginn_r); gp = _lib.GuideParams(model == "H", et, px)
-    rc = guided_entry("batch", fginn_r)(C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p),
-                                        o1.ctypes.data_as(C.POINTER(C.c_int64)), o2.ctypes.data_as(C.POINTER(C.c_int64)),
-                                        _lib.dptr(K1), _lib.dptr(K2), K1.shape[1], K, _lib.dptr(Md), C.byref(gp), int(device),
-                                        idx.ctypes.data_as(C.POINTER(C.c_int32)), dist.ctypes.data_as(C.POINTER(C.c_float)),
-                                        match.ctypes.data_as(C.POINTER(C.c_int32)), cnt.ctypes.data_as(C.POINTER(C.c_int32)))
+    rc = guided_entry(L.name, fginn_r)(C.byref(mp), _lib.vptr(A), _lib.vptr(B), *guided_layout(L, _lib.dptr(K1), _lib.dptr(K2), K1.shape[1]),
+                                       _lib.dptr(Md), C.byref(gp), int(device), _lib.ptr(idx), _lib.ptr(dist), _lib.ptr(match), _lib.ptr(cnt))
     _lib.check_match(rc)
     return match, idx, dist, cnt
+
+
+def _guided_matches(L, match, dist):
+    """per entry of L (query indices, train indices, distances) of the queries with a guided match, in query order"""
+    out = []
+    for p in range(L.K):
+        m = match[L.po[p]:L.po[p + 1]]
+        q = np.flatnonzero(m >= 0)
+        out.append((q.astype(np.int64), m[q].astype(np.int64), dist[L.po[p]:L.po[p + 1]][q, 0]))
+    return out
 
 
 def guided_match_batch(kps1_list, kps2_list, desc1_list, desc2_list, models, model="F", ratio=0.9, mutual=False, px_th=None,
@@ -564,14 +628,9 @@ def guided_match_batch(kps1_list, kps2_list, desc1_list, desc2_list, models, mod
     px, et = check_guided_args(model, px_th, error_type, M.shape, M.dtype, K)
     fr = None if fginn_th is None else check_fginn_th(fginn_th)
     A, B, K1, K2 = _finish_pairs(code, kind, A, B, K1, K2, device)
-    Md = M if (model == "F" or driver_form) else _h_driver_form(M)
-    match, _, dist, _ = _guided_host(code, A, B, K1, K2, o1, o2, Md, model, rule, px, et, device, fr)
-    out = []
-    for p in range(K):
-        m = match[o1[p]:o1[p + 1]]
-        q = np.flatnonzero(m >= 0)
-        out.append((q.astype(np.int64), m[q].astype(np.int64), dist[o1[p]:o1[p + 1]][q, 0]))
-    return out
+    L = layout(o1, o2)
+    match, _, dist, _ = _guided_host(L, code, A, B, K1, K2, _driver_models(M, model, driver_form, K), model, rule, px, et, device, fr)
+    return _guided_matches(L, match, dist)
 
 
 def guided_match(kps1, kps2, desc1, desc2, M, model="F", ratio=0.9, mutual=False, px_th=None, error_type="sampson", norm=None,
@@ -609,26 +668,37 @@ def match_and_verify_batch(kps1_list, kps2_list, desc1_list, desc2_list, model="
     prm = estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
     A, B, K1, K2 = _finish_pairs(code, kind, A, B, K1, K2, device)
     sd = _seeds_u32(seeds, K)
-    mp = _lib.match_params(code, A.shape[1], rule, fginn_th)
-    n1 = A.shape[0]
-    M = np.zeros((K, 9)); match = np.full(n1, -1, np.int32); inl = np.zeros(n1, np.uint8)
-    st = np.zeros((K, 16), np.int32); cnt = np.zeros(K, np.int32)
-    rc = _lib.lib().mi_degensac_match_verify_batch(1 if model == "H" else 0, C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p),
-                                                   o1.ctypes.data_as(C.POINTER(C.c_int64)), o2.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                   _lib.dptr(K1), _lib.dptr(K2), K1.shape[1], K, C.byref(prm),
-                                                   sd.ctypes.data_as(C.POINTER(C.c_uint32)), int(device), _lib.dptr(M),
-                                                   match.ctypes.data_as(C.POINTER(C.c_int32)), inl.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                   st.ctypes.data_as(C.POINTER(C.c_int32)), cnt.ctypes.data_as(C.POINTER(C.c_int32)))
+    L = layout(o1, o2)
+    # guide: the driver-form models as the library wrote them, before the inversion to the user-facing H
+    guide = (lambda M: _guided_host(L, code, A, B, K1, K2, M, model, rule, prm.px_th, prm.error_type, device, gfr)[0]) if guided else None
+    M, match, inl, gm = _verify_host(_lib.lib().mi_degensac_match_verify_batch, L, model, _lib.match_params(code, A.shape[1], rule, fginn_th),
+                                     A, B, K1, K2, prm, sd, device, guide)
+    res = (M, _cut(L, match), _cut(L, inl, bool))
+    return res + (_cut(L, gm),) if guided else res
+
+
+def _verify_out(K, n):
+    """the outputs of one estimator over a layout with their fills: (model [K, 9], inlier [n] uint8, stats [K, 16])"""
+    return np.zeros((K, 9)), np.zeros(n, np.uint8), np.zeros((K, 16), np.int32)
+
+
+def _cut(L, x, dtype=None):
+    """a per-row output as one array per entry of L"""
+    return [x[L.po[p]:L.po[p + 1]] if dtype is None else x[L.po[p]:L.po[p + 1]].astype(dtype) for p in range(L.K)]
+
+
+def _verify_host(entry, L, model, mp, A, B, K1, K2, prm, sd, device, guide=None):
+    """a host-pointer single-model mi_degensac_match_verify_* call on prepared arrays, for both layouts; guide (nullable) gets the
+    driver-form models [K, 9].  Returns (model [K, 3, 3] — H user-facing —, match [n], inlier [n] uint8, what guide returned)."""
+    M, inl, st = _verify_out(L.K, L.n)
+    match = np.full(L.n, -1, np.int32); cnt = np.zeros(L.K, np.int32)
+    rc = entry(1 if model == "H" else 0, C.byref(mp), _lib.vptr(A), _lib.vptr(B), *verify_layout(L, _lib.dptr(K1), _lib.dptr(K2), K1.shape[1]),
+               C.byref(prm), _lib.ptr(sd), int(device), _lib.dptr(M), _lib.ptr(match), _lib.ptr(inl), _lib.ptr(st), _lib.ptr(cnt))
     _lib.check(rc)
     _set_last_stats(st, cnt)
-    gm = None
-    if guided:                  # the driver-form models as the library wrote them, before the inversion below
-        gm = _guided_host(code, A, B, K1, K2, o1, o2, M, model, rule, prm.px_th, prm.error_type, device, gfr)[0]
-    M = M.reshape(K, 3, 3)
-    if model == "H":
-        M = _h_user_form(M)
-    res = (M, [match[o1[p]:o1[p + 1]] for p in range(K)], [inl[o1[p]:o1[p + 1]].astype(bool) for p in range(K)])
-    return res + ([gm[o1[p]:o1[p + 1]] for p in range(K)],) if guided else res
+    gm = guide(M) if guide else None
+    M = M.reshape(L.K, 3, 3)
+    return _h_user_form(M) if model == "H" else M, match, inl, gm
 
 
 def _stack_stores(kps_list, desc_list, kps2_list, desc2_list):
@@ -643,11 +713,8 @@ def _stack_stores(kps_list, desc_list, kps2_list, desc2_list):
             raise ValueError("one keypoint array per descriptor array")
         if len(dl) == 0:
             raise ValueError("at least one image per store")
-        d = [np.asarray(x) for x in dl]; k = [np.asarray(x) for x in kl]
-        for lst in (d, k):
-            if any(x.ndim != 2 or x.dtype != lst[0].dtype or x.shape[1] != lst[0].shape[1] for x in lst):
-                raise ValueError("every image's arrays should be 2-D with the dtype and width of image 0")
-        c = [x.shape[0] for x in d]
+        d, k = (_rows_list(lst, "every image's arrays should be 2-D with the dtype and width of image 0") for lst in (dl, kl))
+        c =[x.shape[0] for x in d]
         if [x.shape[0] for x in k] != c:
             raise ValueError("one keypoint row per descriptor row")
         stores.append((np.concatenate(d), np.concatenate(k), np.asarray(c, np.int64)))
@@ -710,22 +777,10 @@ def _match_verify_pairs(fginn_r, kps_list, desc_list, pairs, model, ratio, mutua
     if sd is None:
         sd = _seeds_u32(None, K)
     A, K1, B, K2 = _finish_stores(code, kind, A, K1, B, K2, one, device)              # one store: uploaded once
-    mp = _lib.match_params(code, A.shape[1], rule, fginn_r)
-    n = int(po[-1])
-    M = np.zeros((K, 9)); match = np.full(n, -1, np.int32); inl = np.zeros(n, np.uint8)
-    st = np.zeros((K, 16), np.int32); cnt = np.zeros(K, np.int32)
-    lp = C.POINTER(C.c_int64); ip = C.POINTER(C.c_int32)
+    L = layout(o1, o2, pr, po)
     entry = _lib.lib().mi_degensac_match_verify_pairs if fginn_r is None else _lib.lib().mi_degensac_match_verify_fginn_pairs
-    rc = entry(1 if model == "H" else 0, C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), o1.ctypes.data_as(lp), len(o1) - 1,
-               o2.ctypes.data_as(lp), len(o2) - 1, _lib.dptr(K1), _lib.dptr(K2), K1.shape[1], pr.ctypes.data_as(ip), K, C.byref(prm),
-               sd.ctypes.data_as(C.POINTER(C.c_uint32)), int(device), _lib.dptr(M), match.ctypes.data_as(ip), inl.ctypes.data_as(C.POINTER(C.c_uint8)),
-               st.ctypes.data_as(ip), cnt.ctypes.data_as(ip))
-    _lib.check(rc)
-    _set_last_stats(st, cnt)
-    M = M.reshape(K, 3, 3)
-    if model == "H":
-        M = _h_user_form(M)
-    return M, [match[po[p]:po[p + 1]] for p in range(K)], [inl[po[p]:po[p + 1]].astype(bool) for p in range(K)]
+    M, match, inl, _ = _verify_host(entry, L, model, _lib.match_params(code, A.shape[1], rule, fginn_r), A, B, K1, K2, prm, sd, device)
+    return M, _cut(L, match), _cut(L, inl, bool)
 
 
 # ---- match once, verify F and H (include/mi_degensac.h mi_degensac_match_verify_fh_*) ----
@@ -774,18 +829,19 @@ def _set_last_stats_fh(stf, sth, cnt):
     api._tls.stats = stats
 
 
-def _fh_host(entry, mp, A, B, layout, prm_f, prm_h, sd, device, K, n):
-    """a host-pointer mi_degensac_match_verify_fh_* call on prepared arrays; layout = its arguments between the descriptors and the
-    parameter blocks.  Returns (F [K, 3, 3], H [K, 3, 3] user-facing, match [n], inlier_f [n], inlier_h [n], summary [K, 4])."""
-    F = np.zeros((K, 9)); H = np.zeros((K, 9)); match = np.full(n, -1, np.int32); inf = np.zeros(n, np.uint8); inh = np.zeros(n, np.uint8)
-    stf = np.zeros((K, 16), np.int32); sth = np.zeros((K, 16), np.int32); summ = np.zeros((K, 4), np.int32); cnt = np.zeros(K, np.int32)
-    ip = C.POINTER(C.c_int32); bp = C.POINTER(C.c_uint8)
-    rc = entry(C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), *layout, C.byref(prm_f), C.byref(prm_h),
-               sd.ctypes.data_as(C.POINTER(C.c_uint32)), int(device), _lib.dptr(F), _lib.dptr(H), match.ctypes.data_as(ip), inf.ctypes.data_as(bp),
-               inh.ctypes.data_as(bp), stf.ctypes.data_as(ip), sth.ctypes.data_as(ip), summ.ctypes.data_as(ip), cnt.ctypes.data_as(ip))
+def _fh_host(L, mp, A, B, K1, K2, prm_f, prm_h, sd, device):
+    """the host-pointer mi_degensac_match_verify_fh_* call of the layout L on prepared arrays.  Returns (F [K, 3, 3], H [K, 3, 3]
+    user-facing, [match_p], [inlier_f_p], [inlier_h_p], summary [K, 4])."""
+    K = L.K
+    F, inf, stf = _verify_out(K, L.n); H, inh, sth = _verify_out(K, L.n)
+    match = np.full(L.n, -1, np.int32); summ = np.zeros((K, 4), np.int32); cnt = np.zeros(K, np.int32)
+    rc = getattr(_lib.lib(), f"mi_degensac_match_verify_fh_{L.name}")(
+        C.byref(mp), _lib.vptr(A), _lib.vptr(B), *verify_layout(L, _lib.dptr(K1), _lib.dptr(K2), K1.shape[1]), C.byref(prm_f), C.byref(prm_h),
+        _lib.ptr(sd), int(device), _lib.dptr(F), _lib.dptr(H), _lib.ptr(match), _lib.ptr(inf), _lib.ptr(inh), _lib.ptr(stf), _lib.ptr(sth),
+        _lib.ptr(summ), _lib.ptr(cnt))
     _lib.check(rc)
     _set_last_stats_fh(stf, sth, cnt)
-    return F.reshape(K, 3, 3), _h_user_form(H.reshape(K, 3, 3)), match, inf, inh, summ
+    return F.reshape(K, 3, 3), _h_user_form(H.reshape(K, 3, 3)), _cut(L, match), _cut(L, inf, bool), _cut(L, inh, bool), summ
 
 
 def match_and_verify_fh_batch(kps1_list, kps2_list, desc1_list, desc2_list, ratio=0.9, mutual=False, norm=None, fginn_th=None, seeds=None,
@@ -804,12 +860,7 @@ def match_and_verify_fh_batch(kps1_list, kps2_list, desc1_list, desc2_list, rati
     prm_f, prm_h = two_view_params(f_params, h_params)
     A, B, K1, K2 = _finish_pairs(code, kind, A, B, K1, K2, device)
     sd = _seeds_u32(seeds, K)
-    lp = C.POINTER(C.c_int64)
-    F, H, match, inf, inh, summ = _fh_host(_lib.lib().mi_degensac_match_verify_fh_batch, _lib.match_params(code, A.shape[1], rule, fginn_th), A, B,
-                                           (o1.ctypes.data_as(lp), o2.ctypes.data_as(lp), _lib.dptr(K1), _lib.dptr(K2), K1.shape[1], K), prm_f, prm_h,
-                                           sd, device, K, A.shape[0])
-    cut = lambda x, t=None: [x[o1[p]:o1[p + 1]] if t is None else x[o1[p]:o1[p + 1]].astype(t) for p in range(K)]          # noqa: E731
-    return F, H, cut(match), cut(inf, bool), cut(inh, bool), summ
+    return _fh_host(layout(o1, o2), _lib.match_params(code, A.shape[1], rule, fginn_th), A, B, K1, K2, prm_f, prm_h, sd, device)
 
 
 def match_and_verify_fh_pairs(kps_list, desc_list, pairs, ratio=0.9, mutual=False, norm=None, fginn_th=None, seeds=None, f_params=None,
@@ -829,12 +880,7 @@ def match_and_verify_fh_pairs(kps_list, desc_list, pairs, ratio=0.9, mutual=Fals
     if sd is None:
         sd = _seeds_u32(None, K)
     A, K1, B, K2 = _finish_stores(code, kind, A, K1, B, K2, one, device)              # one store: uploaded once
-    lp = C.POINTER(C.c_int64)
-    F, H, match, inf, inh, summ = _fh_host(_lib.lib().mi_degensac_match_verify_fh_pairs, _lib.match_params(code, A.shape[1], rule, fr), A, B,
-                                           (o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, _lib.dptr(K1), _lib.dptr(K2),
-                                            K1.shape[1], pr.ctypes.data_as(C.POINTER(C.c_int32)), K), prm_f, prm_h, sd, device, K, int(po[-1]))
-    cut = lambda x, t=None: [x[po[p]:po[p + 1]] if t is None else x[po[p]:po[p + 1]].astype(t) for p in range(K)]          # noqa: E731
-    return F, H, cut(match), cut(inf, bool), cut(inh, bool), summ
+    return _fh_host(layout(o1, o2, pr, po), _lib.match_params(code, A.shape[1], rule, fr), A, B, K1, K2, prm_f, prm_h, sd, device)
 
 
 def guided_match_pairs(kps_list, desc_list, pairs, models, model="F", ratio=0.9, mutual=False, px_th=None, error_type="sampson", norm=None,
@@ -856,23 +902,9 @@ def guided_match_pairs(kps_list, desc_list, pairs, models, model="F", ratio=0.9,
     px, et = check_guided_args(model, px_th, error_type, M.shape, M.dtype, K)
     fr = None if fginn_th is None else check_fginn_th(fginn_th)
     A, K1, B, K2 = _finish_stores(code, kind, A, K1, B, K2, one, device)
-    Md = np.ascontiguousarray(M if (model == "F" or driver_form) else _h_driver_form(M), np.float64).reshape(K, 9)
-    n = int(po[-1])
-    idx = np.full((n, 2), -1, np.int32); dist = np.full((n, 2), np.inf, np.float32); match = np.full(n, -1, np.int32)
-    cnt = np.zeros(K, np.int32)
-    mp = _lib.match_params(code, A.shape[1], rule, fr); gp = _lib.GuideParams(model == "H", et, px)
-    lp = C.POINTER(C.c_int64); ip = C.POINTER(C.c_int32)
-    rc = guided_entry("pairs", fr)(C.byref(mp), A.ctypes.data_as(C.c_void_p), B.ctypes.data_as(C.c_void_p), o1.ctypes.data_as(lp),
-                                   len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, pr.ctypes.data_as(ip), K, _lib.dptr(K1),
-                                   _lib.dptr(K2), K1.shape[1], _lib.dptr(Md), C.byref(gp), int(device), idx.ctypes.data_as(ip),
-                                   dist.ctypes.data_as(C.POINTER(C.c_float)), match.ctypes.data_as(ip), cnt.ctypes.data_as(ip))
-    _lib.check_match(rc)
-    out = []
-    for p in range(K):
-        m = match[po[p]:po[p + 1]]
-        q = np.flatnonzero(m >= 0)
-        out.append((q.astype(np.int64), m[q].astype(np.int64), dist[po[p]:po[p + 1]][q, 0]))
-    return out
+    L = layout(o1, o2, pr, po)
+    match, _, dist, _ = _guided_host(L, code, A, B, K1, K2, _driver_models(M, model, driver_form, K), model, rule, px, et, device, fr)
+    return _guided_matches(L, match, dist)
 
 
 def check_correspond_args(match_shape, match_dtype, counts1, counts2, pairs, keep=None, kps1=None, kps2=None, models=None, model="F",
@@ -893,22 +925,12 @@ def check_correspond_args(match_shape, match_dtype, counts1, counts2, pairs, kee
     if pairs is None:
         if len(cs[0]) != len(cs[1]):
             raise ValueError("counts1 and counts2 should have one entry per pair")
-        pr = None; K = len(cs[0]); po = o1.copy(); nt_rows = o2[-1]
+        pr = None; K = len(cs[0]); po = o1.copy()
+        if po[-1] > 0x3fffffff or o2[-1] > 0x3fffffff:
+            raise ValueError("too many rows in one pair list")
     else:
-        pr = np.asarray(pairs)
-        if pr.ndim != 2 or pr.shape[1] != 2 or not np.issubdtype(pr.dtype, np.integer):
-            raise ValueError("pairs should be an integer array [K, 2] of (image of store 1, image of store 2)")
-        K = pr.shape[0]
-        if K == 0:
-            raise ValueError("at least one pair")
-        m1, m2 = len(o1) - 1, len(o2) - 1
-        if (pr < 0).any() or (pr[:, 0] >= m1).any() or (pr[:, 1] >= m2).any():
-            raise ValueError(f"pairs hold an image index outside its store ({m1} and {m2} images)")
-        pr = np.ascontiguousarray(pr, np.int32)
-        po = np.zeros(K + 1, np.int64); np.cumsum(np.diff(o1)[pr[:, 0]], out=po[1:])
-        nt_rows = np.diff(o2)[pr[:, 1]].sum()
-    if po[-1] > 0x3fffffff or nt_rows > 0x3fffffff:
-        raise ValueError("too many rows in one pair list")
+        pr, po = _check_pair_list(pairs, o1, o2)
+        K = len(pr)
     N = int(po[-1])
     if tuple(match_shape) != (N,) or _dtype_name(match_dtype) != "int32":
         raise ValueError(f"match should be int32 [N] = [{N}], one value per output row of the list")
@@ -918,20 +940,9 @@ def check_correspond_args(match_shape, match_dtype, counts1, counts2, pairs, kee
         raise ValueError("kps1 and kps2 go together")
     kind = None
     if kps1 is not None:
-        kinds = []
-        for shp, dt in (kps1, kps2):
-            name = _dtype_name(dt)
-            if len(shp) == 2 and name == "float64" and shp[1] in (2, 6):
-                kinds.append(("xy", shp[1]))
-            elif len(shp) == 2 and name == "float32" and shp[1] == 4:
-                kinds.append(("kpts", 4))
-            else:
-                raise ValueError("keypoints should be float64 [n, 2] / [n, 6] rows or float32 [n, 4] = (x, y, size, angle)")
-        if kinds[0] != kinds[1]:
-            raise ValueError("kps1 and kps2 should have the same layout")
+        kind = _kps_kind(kps1, kps2)
         if kps1[0][0] != o1[-1] or kps2[0][0] != o2[-1]:
             raise ValueError("counts do not add up to the number of keypoint rows")
-        kind = kinds[0][0]
     if models is not None:
         if kps1 is None:
             raise ValueError("models (the residuals) need kps1 and kps2")
@@ -939,21 +950,15 @@ def check_correspond_args(match_shape, match_dtype, counts1, counts2, pairs, kee
             raise ValueError(f"models should be [K, 3, 3] = [{K}, 3, 3], one model per list entry")
         if _dtype_name(models[1]) != "float64":
             raise ValueError("models should be float64")
-    if capacity is None:
-        cap = N
-    else:
-        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 0:
-            raise ValueError("capacity should be an integer >= 0 (or None = one position per output row)")
-        cap = int(capacity)
+    cap = N if capacity is None else _integer(capacity, "capacity should be an integer >= 0 (or None = one position per output row)", 0)
     return o1, o2, pr, po, kind, et, cap
 
 
 def correspond_layout(o1, o2, pr):
     """the layout arguments of the mi_degensac_correspondences_* entry points: (layout name, ctypes arguments, K)"""
-    lp = C.POINTER(C.c_int64)
     if pr is None:
-        return "batch", (o1.ctypes.data_as(lp), o2.ctypes.data_as(lp), len(o1) - 1), len(o1) - 1
-    return "pairs", (o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, pr.ctypes.data_as(C.POINTER(C.c_int32)), len(pr)), len(pr)
+        return "batch", (_lib.ptr(o1), _lib.ptr(o2), len(o1) - 1), len(o1) - 1
+    return "pairs", (_lib.ptr(o1), len(o1) - 1, _lib.ptr(o2), len(o2) - 1, _lib.ptr(pr), len(pr)), len(pr)
 
 
 def _correspondences(match, counts1, counts2, pairs, keep, kps_list, kps2_list, models, model, error_type, driver_form, store_rows, device):
@@ -963,16 +968,11 @@ def _correspondences(match, counts1, counts2, pairs, keep, kps_list, kps2_list, 
         raise ValueError("kps2_list names a second store: give kps_list too")
     K1 = K2 = None
     if kps_list is not None:
-        stores = []
-        for kl in (kps_list,) if kps2_list is None else (kps_list, kps2_list):
-            k = [np.asarray(x) for x in kl]
-            if len(k) == 0 or any(x.ndim != 2 or x.dtype != k[0].dtype or x.shape[1] != k[0].shape[1] for x in k):
-                raise ValueError("every image's keypoints should be 2-D with the dtype and width of image 0 (at least one image per store)")
-            stores.append(np.concatenate(k))
+        text = "every image's keypoints should be 2-D with the dtype and width of image 0 (at least one image per store)"
+        stores = [np.concatenate(_rows_list(kl, text)) for kl in ((kps_list,) if kps2_list is None else (kps_list, kps2_list))]
         K1, K2 = stores[0], stores[-1]
     M = None if models is None else np.asarray(models)
-    sd = lambda x: None if x is None else (x.shape, x.dtype)          # noqa: E731
-    o1, o2, pr, po, kind, et, cap = check_correspond_args(match.shape, match.dtype, counts1, counts2, pairs, sd(kp), sd(K1), sd(K2), sd(M), model,
+    o1, o2, pr, po, kind, et, cap = check_correspond_args(match.shape, match.dtype, counts1, counts2, pairs, _sd(kp), _sd(K1), _sd(K2), _sd(M), model,
                                                           error_type, None)
     name, layout, K = correspond_layout(o1, o2, pr)
     match = np.ascontiguousarray(match)
@@ -982,15 +982,13 @@ def _correspondences(match, counts1, counts2, pairs, keep, kps_list, kps2_list, 
         same = K2 is K1
         K1 = np.ascontiguousarray(kpts_to_xyA(K1, device) if kind == "kpts" else K1, np.float64)
         K2 = K1 if same else np.ascontiguousarray(kpts_to_xyA(K2, device) if kind == "kpts" else K2, np.float64)
-    Md = None
-    if M is not None:
-        Md = np.ascontiguousarray(M if (model == "F" or driver_form) else _h_driver_form(M), np.float64).reshape(K, 9)
-    co = np.zeros(K + 1, np.int64); total = np.zeros(1, np.int64)
+    Md = None if M is None else _driver_models(M, model, driver_form, K)
+    co =np.zeros(K + 1, np.int64); total = np.zeros(1, np.int64)
     rows = np.full((cap, 2), -1, np.int32)
     pts = None if K1 is None else np.full((cap, 4), np.nan)
     resid = None if Md is None else np.full(cap, np.nan)
     gp = _lib.GuideParams(model == "H", et, 0.0)
-    vp = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)          # noqa: E731
+    vp = _lib.vptr
     rc = getattr(_lib.lib(), f"mi_degensac_correspondences_{name}")(*layout, vp(match), vp(kp), _lib.CORR_STORE_ROWS if store_rows else 0, vp(K1),
                                                                    vp(K2), 0 if K1 is None else K1.shape[1], vp(Md), C.byref(gp), cap, int(device),
                                                                    vp(co), vp(total), vp(rows), None, vp(pts), vp(resid))
@@ -1040,8 +1038,8 @@ def check_tracks_args(rows_shape, rows_dtype, counts, total=None):
         raise ValueError("rows should be int32 [M, 2] of store rows, as the correspondence export writes them with store_rows=True")
     if rows_shape[0] > 0x3fffffff:
         raise ValueError("too many edges in one list")
-    if total is not None and (isinstance(total, bool) or not isinstance(total, (int, np.integer))):
-        raise ValueError("total should be an integer (or None = all edges)")
+    if total is not None:
+        _integer(total, "total should be an integer (or None = all edges)")
     return off, int(off[-1]), int(rows_shape[0])
 
 
@@ -1060,7 +1058,7 @@ def tracks(rows, counts, total=None, device=0):
     half = R // 2
     label = np.empty(R, np.int32); track = np.empty(R, np.int32); obs = np.empty(R, np.int32); oi = np.empty(R, np.int32)
     to = np.empty(half + 1, np.int64); ti = np.empty(half, np.int32); n = np.zeros(2, np.int64)
-    vp = lambda x: x.ctypes.data_as(C.c_void_p)          # noqa: E731
+    vp = _lib.vptr
     rc = _lib.lib().mi_degensac_tracks(off.ctypes.data_as(C.POINTER(C.c_int64)), len(off) - 1, vp(rows) if M else None, M,
                                        -1 if total is None else int(total), int(device), vp(label), vp(track), vp(n[0:]), vp(n[1:]), vp(to), vp(obs),
                                        vp(oi), vp(ti))
@@ -1075,17 +1073,23 @@ def check_refit_args(pts_shape, pts_dtype, off_shape, off_dtype, models_shape, m
     """The argument checks of refit_correspondences / refit_correspondences_tensors on shapes and dtype names (numpy or torch): pts float64
     [cap, 4], corr_offsets int64 [K + 1], models float64 [K, 3, 3], px_th >= 0 (None = the model's default), error_type one of the model's
     names, max_fits an integer >= 0.  Returns (K, cap, px_th, error_type code, max_fits); raises ValueError."""
+    K, cap, (px, et) = _check_list_inputs(pts_shape, pts_dtype, off_shape, off_dtype,
+                                          lambda K: check_guided_args(model, px_th, error_type, models_shape, models_dtype, K))
+    return K, cap, px, et, _integer(max_fits, "max_fits should be an integer >= 0", 0)
+
+
+def _check_list_inputs(pts_shape, pts_dtype, off_shape, off_dtype, check_models):
+    """corr_offsets and pts of the calls on exported lists; check_models(K) runs between the two, where every such call checks its models.
+    Returns (K, cap, what check_models returned); raises ValueError."""
     if len(off_shape) != 1 or off_shape[0] < 1 or _dtype_name(off_dtype) != "int64":
         raise ValueError("corr_offsets should be int64 [K + 1], as the correspondence export returns it")
     K = int(off_shape[0]) - 1
-    px, et = check_guided_args(model, px_th, error_type, models_shape, models_dtype, K)
+    got = check_models(K)
     if len(pts_shape) != 2 or pts_shape[1] != 4 or _dtype_name(pts_dtype) != "float64":
         raise ValueError("pts should be float64 [cap, 4] = x1, y1, x2, y2, as the correspondence export returns it")
     if pts_shape[0] > 0x3fffffff:
         raise ValueError("too many rows in one list")
-    if isinstance(max_fits, bool) or not isinstance(max_fits, (int, np.integer)) or max_fits < 0:
-        raise ValueError("max_fits should be an integer >= 0")
-    return K, int(pts_shape[0]), px, et, int(max_fits)
+    return K, int(pts_shape[0]), got
 
 
 def refit_correspondences(pts, corr_offsets, models, model="F", px_th=None, error_type="sampson", driver_form=False, max_fits=4, with_resid=False,
@@ -1100,11 +1104,11 @@ def refit_correspondences(pts, corr_offsets, models, model="F", px_th=None, erro
     _lib.REFIT_* status)[, resid [cap] under the returned model])."""
     P = np.ascontiguousarray(np.asarray(pts)); o = np.ascontiguousarray(np.asarray(corr_offsets)); M = np.asarray(models)
     K, cap, px, et, mf = check_refit_args(P.shape, P.dtype, o.shape, o.dtype, M.shape, M.dtype, model, px_th, error_type, max_fits)
-    Md = np.ascontiguousarray(M if (model == "F" or driver_form) else _h_driver_form(M), np.float64).reshape(K, 9)
+    Md = _driver_models(M, model, driver_form, K)
     out = np.zeros((K, 9)); user = np.zeros((K, 9)); inl = np.zeros(cap, np.uint8); info = np.zeros((K, 4), np.int32)
     resid = np.full(cap, np.nan) if with_resid else None
     gp = _lib.GuideParams(model == "H", et, px)
-    vp = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)          # noqa: E731
+    vp = _lib.vptr
     rc = _lib.lib().mi_degensac_refit_lists(vp(P), vp(o), vp(Md), K, cap, C.byref(gp), mf, int(device), vp(out), vp(inl), vp(user), vp(info),
                                             vp(resid))
     _lib.check_match(rc)
@@ -1119,16 +1123,10 @@ def check_pose_args(pts_shape, pts_dtype, off_shape, off_dtype, models_shape, mo
     float64 [K, 8] (one row of two cameras fx, fy, cx, cy per entry) and cams2 must be None; with pairs int32 / int64 [K, 2] cams1 is
     float64 [n_images, 4] and cams2 None (= cams1) or float64 [n_images_2, 4]; keep bool / uint8 [cap]; min_parallax_deg a number in
     [0, 180].  Returns (K, cap, rows of cams1, rows of cams2 or None, cos_min); raises ValueError."""
-    if len(off_shape) != 1 or off_shape[0] < 1 or _dtype_name(off_dtype) != "int64":
-        raise ValueError("corr_offsets should be int64 [K + 1], as the correspondence export returns it")
-    K = int(off_shape[0]) - 1
-    if tuple(models_shape) != (K, 3, 3) or _dtype_name(models_dtype) != "float64":
-        raise ValueError("models should be float64 [K, 3, 3], one fundamental matrix per entry of corr_offsets")
-    if len(pts_shape) != 2 or pts_shape[1] != 4 or _dtype_name(pts_dtype) != "float64":
-        raise ValueError("pts should be float64 [cap, 4] = x1, y1, x2, y2, as the correspondence export returns it")
-    if pts_shape[0] > 0x3fffffff:
-        raise ValueError("too many rows in one list")
-    cap = int(pts_shape[0])
+    def check_models(K):
+        if tuple(models_shape) != (K, 3, 3) or _dtype_name(models_dtype) != "float64":
+            raise ValueError("models should be float64 [K, 3, 3], one fundamental matrix per entry of corr_offsets")
+    K, cap, _ = _check_list_inputs(pts_shape, pts_dtype, off_shape, off_dtype, check_models)
     if _dtype_name(cams1_dtype) != "float64":
         raise ValueError("cams1 should be float64")
     n2 = None
@@ -1150,10 +1148,25 @@ def check_pose_args(pts_shape, pts_dtype, off_shape, off_dtype, models_shape, mo
             raise ValueError("too many cameras")
     if keep is not None and (tuple(keep[0]) != (cap,) or _dtype_name(keep[1]) not in ("bool", "uint8")):
         raise ValueError("keep should be bool or uint8 [cap], one flag per row of pts")
-    if isinstance(min_parallax_deg, bool) or not isinstance(min_parallax_deg, (int, float, np.integer, np.floating)) \
-            or not 0.0 <= float(min_parallax_deg) <= 180.0:
-        raise ValueError("min_parallax_deg should be a number in [0, 180]")
-    return K, cap, int(cams1_shape[0]), n2, float(np.cos(np.deg2rad(float(min_parallax_deg))))
+    deg = _number(min_parallax_deg, "min_parallax_deg should be a number in [0, 180]", 0.0, 180.0)
+    return K, cap, int(cams1_shape[0]), n2, float(np.cos(np.deg2rad(deg)))
+
+
+def _cam_index(pairs, n1, n2):
+    """pairs [K, 2] of a pose call as int32 rows of the camera table (store 1's n1 cameras, then store 2's when n2 is not None); an image
+    outside its store becomes -1, so that an image of store 1 cannot reach into store 2's rows"""
+    wide = pairs.astype(np.int64) + np.array([0, 0 if n2 is None else n1], np.int64)
+    if n2 is not None:
+        wide[(pairs[:, 0] < 0) | (pairs[:, 0] >= n1), 0] = -1
+        wide[pairs[:, 1] < 0, 1] = -1
+    return np.ascontiguousarray(np.clip(wide, -1, 0x7fffffff).astype(np.int32))
+
+
+def _cameras(c1, c2, pr, K, n1, n2):
+    """the camera table and the entries' rows in it for the pose calls -> (cams [n_cams, 4], cam_idx int32 [K, 2] or None = two rows per entry)"""
+    if pr is None:
+        return np.ascontiguousarray(c1).reshape(2 * K, 4), None
+    return np.ascontiguousarray(c1 if c2 is None else np.concatenate([c1, c2])), _cam_index(pr, n1, n2)
 
 
 def relative_pose(pts, corr_offsets, models, cams1, pairs=None, cams2=None, keep=None, min_parallax_deg=1.5, with_points=False, with_candidates=False,
@@ -1171,20 +1184,10 @@ def relative_pose(pts, corr_offsets, models, cams1, pairs=None, cams2=None, keep
     c1 = np.asarray(cams1); c2 = None if cams2 is None else np.asarray(cams2)
     pr = None if pairs is None else np.asarray(pairs)
     kp = None if keep is None else np.asarray(keep)
-    sd = lambda x: None if x is None else (x.shape, x.dtype)          # noqa: E731
-    K, cap, n1, n2, cos_min = check_pose_args(P.shape, P.dtype, o.shape, o.dtype, M.shape, M.dtype, c1.shape, c1.dtype, sd(pr), sd(c2), sd(kp),
+    K, cap, n1, n2, cos_min = check_pose_args(P.shape, P.dtype, o.shape, o.dtype, M.shape, M.dtype, c1.shape, c1.dtype, _sd(pr), _sd(c2), _sd(kp),
                                               min_parallax_deg)
     F = np.ascontiguousarray(M, np.float64).reshape(K, 9)
-    idx = None
-    if pr is None:
-        cams = np.ascontiguousarray(c1).reshape(2 * K, 4)
-    else:
-        cams = np.ascontiguousarray(c1 if c2 is None else np.concatenate([c1, c2]))
-        wide = pr.astype(np.int64) + np.array([0, 0 if c2 is None else n1], np.int64)
-        if c2 is not None:                                            # an image of store 1 must not reach into store 2's rows
-            wide[(pr[:, 0] < 0) | (pr[:, 0] >= n1), 0] = -1
-            wide[pr[:, 1] < 0, 1] = -1
-        idx = np.ascontiguousarray(np.clip(wide, -1, 0x7fffffff).astype(np.int32))
+    cams, idx = _cameras(c1, c2, pr, K, n1, n2)
     if kp is not None:
         kp = np.ascontiguousarray(kp).view(np.uint8)
     pose = np.zeros((K, 12)); front = np.zeros(cap, np.uint8); info = np.zeros((K, 5), np.int32)
@@ -1193,7 +1196,7 @@ def relative_pose(pts, corr_offsets, models, cams1, pairs=None, cams2=None, keep
     cosang = np.full(cap, np.nan) if with_points else None
     cand = np.zeros((K, 4, 12)) if with_candidates else None
     cf = np.zeros((K, 4), np.int32) if with_candidates else None
-    vp = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)          # noqa: E731
+    vp = _lib.vptr
     rc = _lib.lib().mi_degensac_pose_lists(vp(P), vp(o), vp(kp), vp(F), vp(cams), len(cams), vp(idx), K, cap, cos_min, int(device), vp(pose),
                                            vp(front), vp(info), vp(X), vp(depth), vp(cosang), vp(cand), vp(cf))
     _lib.check_match(rc)
@@ -1214,11 +1217,7 @@ def check_refine_args(pts_shape, pts_dtype, off_shape, off_dtype, R_shape, R_dty
     if len(t_shape) != 2 or t_shape[1] != 3 or (K >= 0 and t_shape[0] != K) or _dtype_name(t_dtype) != "float64":
         raise ValueError("t should be float64 [K, 3], one baseline direction per entry of corr_offsets")
     K, cap, n1, n2, _ = check_pose_args(pts_shape, pts_dtype, off_shape, off_dtype, R_shape, R_dtype, cams1_shape, cams1_dtype, pairs, cams2, keep)
-    if isinstance(max_trials, bool) or not isinstance(max_trials, (int, np.integer)) or not 0 <= int(max_trials) <= 100:
-        raise ValueError("max_trials should be an integer in 0 .. 100")
-    if isinstance(ftol, bool) or not isinstance(ftol, (int, float, np.integer, np.floating)) or not float(ftol) >= 0.0:
-        raise ValueError("ftol should be a number >= 0")
-    return K, cap, n1, n2, int(max_trials), float(ftol)
+    return K, cap, n1, n2, _integer(max_trials, "max_trials should be an integer in 0 .. 100", 0, 100), _number(ftol, "ftol should be a number >= 0", 0.0)
 
 
 def refine_pose(pts, corr_offsets, R, t, cams1, pairs=None, cams2=None, keep=None, max_trials=20, ftol=1e-12, with_resid=False, with_F=False,
@@ -1237,26 +1236,16 @@ def refine_pose(pts, corr_offsets, R, t, cams1, pairs=None, cams2=None, keep=Non
     c1 = np.asarray(cams1); c2 = None if cams2 is None else np.asarray(cams2)
     pr = None if pairs is None else np.asarray(pairs)
     kp = None if keep is None else np.asarray(keep)
-    sd = lambda x: None if x is None else (x.shape, x.dtype)          # noqa: E731
-    K, cap, n1, n2, mt, ft = check_refine_args(P.shape, P.dtype, o.shape, o.dtype, Rm.shape, Rm.dtype, tv.shape, tv.dtype, c1.shape, c1.dtype, sd(pr),
-                                               sd(c2), sd(kp), max_trials, ftol)
+    K, cap, n1, n2, mt, ft = check_refine_args(P.shape, P.dtype, o.shape, o.dtype, Rm.shape, Rm.dtype, tv.shape, tv.dtype, c1.shape, c1.dtype, _sd(pr),
+                                               _sd(c2), _sd(kp), max_trials, ftol)
     pose = np.ascontiguousarray(np.concatenate([Rm.reshape(K, 9), tv], 1))
-    idx = None
-    if pr is None:
-        cams = np.ascontiguousarray(c1).reshape(2 * K, 4)
-    else:
-        cams = np.ascontiguousarray(c1 if c2 is None else np.concatenate([c1, c2]))
-        wide = pr.astype(np.int64) + np.array([0, 0 if c2 is None else n1], np.int64)
-        if c2 is not None:                                            # an image of store 1 must not reach into store 2's rows
-            wide[(pr[:, 0] < 0) | (pr[:, 0] >= n1), 0] = -1
-            wide[pr[:, 1] < 0, 1] = -1
-        idx = np.ascontiguousarray(np.clip(wide, -1, 0x7fffffff).astype(np.int32))
+    cams, idx = _cameras(c1, c2, pr, K, n1, n2)
     if kp is not None:
         kp = np.ascontiguousarray(kp).view(np.uint8)
     out = np.zeros((K, 12)); cost = np.full((K, 2), np.nan); info = np.zeros((K, 4), np.int32)
     resid = np.full(cap, np.nan) if with_resid else None
     F = np.zeros((K, 9)) if with_F else None
-    vp = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)          # noqa: E731
+    vp = _lib.vptr
     rc = _lib.lib().mi_degensac_pose_refine_lists(vp(P), vp(o), vp(kp), vp(pose), vp(cams), len(cams), vp(idx), K, cap, mt, ft, int(device), vp(out),
                                                   vp(cost), vp(info), vp(resid), vp(F))
     _lib.check_match(rc)
@@ -1273,7 +1262,6 @@ def check_triangulate_args(off_shape, off_dtype, obs_shape, obs_dtype, img_shape
     [n_images, 3]; n_tracks None or (shape, dtype) = int64 [1]; min_angle_deg a number in [0, 180], max_reproj_px a number >= 0, max_iters
     an integer in 0 .. 100, ftol a number >= 0.  Returns (T, M, rows, n_images, min_angle_deg, max_reproj_px, max_iters, ftol); raises
     ValueError."""
-    num = (int, float, np.integer, np.floating)
     if len(off_shape) != 1 or off_shape[0] < 1 or _dtype_name(off_dtype) != "int64":
         raise ValueError("track_offsets should be int64 [T + 1], as the tracks call returns it")
     T = int(off_shape[0]) - 1
@@ -1294,15 +1282,10 @@ def check_triangulate_args(off_shape, off_dtype, obs_shape, obs_dtype, img_shape
         raise ValueError("t should be float64 [n_images, 3], X_cam = R X + t")
     if n_tracks is not None and (tuple(n_tracks[0]) != (1,) or _dtype_name(n_tracks[1]) != "int64"):
         raise ValueError("n_tracks should be int64 [1], as the tracks call returns it (or None = all T)")
-    if isinstance(min_angle_deg, bool) or not isinstance(min_angle_deg, num) or not 0.0 <= float(min_angle_deg) <= 180.0:
-        raise ValueError("min_angle_deg should be a number in [0, 180]")
-    if isinstance(max_reproj_px, bool) or not isinstance(max_reproj_px, num) or not float(max_reproj_px) >= 0.0:
-        raise ValueError("max_reproj_px should be a number >= 0")
-    if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or not 0 <= int(max_iters) <= 100:
-        raise ValueError("max_iters should be an integer in 0 .. 100")
-    if isinstance(ftol, bool) or not isinstance(ftol, num) or not float(ftol) >= 0.0:
-        raise ValueError("ftol should be a number >= 0")
-    return T, int(obs_shape[0]), int(kps_shape[0]), n, float(min_angle_deg), float(max_reproj_px), int(max_iters), float(ftol)
+    ang = _number(min_angle_deg, "min_angle_deg should be a number in [0, 180]", 0.0, 180.0)
+    px = _number(max_reproj_px, "max_reproj_px should be a number >= 0", 0.0)
+    mi = _integer(max_iters, "max_iters should be an integer in 0 .. 100", 0, 100)
+    return T, int(obs_shape[0]), int(kps_shape[0]), n, ang, px, mi, _number(ftol, "ftol should be a number >= 0", 0.0)
 
 
 def triangulate_tracks(track_offsets, obs, obs_image, kps, cams, R, t, n_tracks=None, min_angle_deg=1.5, max_reproj_px=4.0, max_iters=10, ftol=1e-12,
@@ -1322,8 +1305,8 @@ def triangulate_tracks(track_offsets, obs, obs_image, kps, cams, R, t, n_tracks=
         raise ValueError(f"triangulate_tracks: unknown keyword {sorted(unknown)[0]!r}")
     o = np.ascontiguousarray(np.asarray(track_offsets)); ob = np.ascontiguousarray(np.asarray(obs)); oi = np.ascontiguousarray(np.asarray(obs_image))
     kp = np.asarray(kps); cm = np.asarray(cams); Rm = np.asarray(R); tv = np.asarray(t)
-    if n_tracks is not None and (isinstance(n_tracks, bool) or not isinstance(n_tracks, (int, np.integer))):
-        raise ValueError("n_tracks should be an integer (or None = all T)")
+    if n_tracks is not None:
+        _integer(n_tracks, "n_tracks should be an integer (or None = all T)")
     T, M, rows, n, ang, px, mi, ft = check_triangulate_args(o.shape, o.dtype, ob.shape, ob.dtype, oi.shape, oi.dtype, kp.shape, kp.dtype, cm.shape, cm.dtype,
                                                             Rm.shape, Rm.dtype, tv.shape, tv.dtype, None, min_angle_deg, max_reproj_px, max_iters, ftol)
     xy = np.ascontiguousarray(kp[:, :2]); cm = np.ascontiguousarray(cm)
@@ -1332,7 +1315,7 @@ def triangulate_tracks(track_offsets, obs, obs_image, kps, cams, R, t, n_tracks=
     err = np.full(M, np.nan) if with_obs else None
     ok = np.zeros(M, np.uint8) if with_obs else None
     depth = np.full(M, np.nan) if with_obs else None
-    vp = lambda x: None if x is None or x.size == 0 else x.ctypes.data_as(C.c_void_p)          # noqa: E731
+    vp = lambda x: _lib.vptr(x, empty_none=True)          # noqa: E731
     rc = _lib.lib().mi_degensac_triangulate_tracks(vp(o), vp(ob), vp(oi), -1 if n_tracks is None else max(int(n_tracks), 0), vp(xy), rows, vp(cm),
                                                    vp(poses), n, T, M, ang, px, mi, ft, int(device), vp(X), vp(info), vp(cost), vp(cosang), vp(err),
                                                    vp(ok), vp(depth))

@@ -13,6 +13,79 @@ import numpy as np
 
 from . import _lib
 from .api import error_type_dict_fundamental, error_type_dict_homography
+from .matcher import _sd
+
+
+# ---- the plumbing every call shares: the two tensor refusals, pointers, the stream, keeping inputs alive, result fills ----
+def _require(names, tensors, device=None):
+    """The two tensor refusals of a call, under the names its texts use.  device None: every argument is a torch tensor.  "same": they
+    live on one device; "cuda": and it is a ROCm one (where "same" leaves that to _desc_pair, whose text differs)."""
+    import torch
+    if device is None:
+        if not all(isinstance(t, torch.Tensor) for t in tensors):
+            raise ValueError(f"{names} must be torch tensors on a ROCm device")
+    elif any(t.device != tensors[0].device for t in tensors) or (device == "cuda" and tensors[0].device.type != "cuda"):
+        raise ValueError(f"{names} must live on the same ROCm device")
+
+
+def _p(t, empty_none=False):
+    """the device pointer of a tensor; None stays None (a nullable argument), and with empty_none so does a tensor without elements"""
+    return None if t is None or (empty_none and t.numel() == 0) else t.data_ptr()
+
+
+def _stream(dev):
+    """(device index, current stream, its handle as the entry points take it)"""
+    import torch
+    stream = torch.cuda.current_stream(dev)
+    return dev.index or 0, stream, C.c_void_p(stream.cuda_stream)
+
+
+def _keep_alive(stream, *tensors):
+    """the kernels read their inputs asynchronously: keep them alive until the stream reaches this point"""
+    for t in tensors:
+        if t is not None:
+            t.record_stream(stream)
+
+
+def _knn_out(n, dev, with_match=False):
+    """the 2-NN result tensors of n query rows with their fills: idx -1, dist inf, and with with_match match -1 (else None)"""
+    import torch
+    return (torch.full((n, 2), -1, dtype=torch.int32, device=dev), torch.full((n, 2), float("inf"), dtype=torch.float32, device=dev),
+            torch.full((n,), -1, dtype=torch.int32, device=dev) if with_match else None)
+
+
+def _store_kps(kind, kps1, kps2, per_store):
+    """the keypoints of the two sides as float64 rows; per_store: a store named on both sides is converted once"""
+    conv = kpts_to_xyA_tensors if kind == "kpts" else (lambda k: k.contiguous())
+    k1 = conv(kps1)
+    return k1, k1 if per_store and kps2 is kps1 else conv(kps2)
+
+
+def _driver_models(models, model, driver_form, K):
+    """the models of a call as the library takes them: contiguous float64 [K, 9], the user-facing H converted on the device"""
+    M = models.contiguous()
+    if model == "H" and not driver_form:
+        M = _h_driver_form(M)
+    return M.reshape(K, 9).contiguous()
+
+
+def _cam_index(pairs, n1, n2):
+    """matcher._cam_index on a device tensor, without a host round trip"""
+    import torch
+    wide = pairs.to(torch.int64)
+    if n2 is not None:                                                # an image of store 1 must not reach into store 2's rows
+        a = torch.where((wide[:, 0] < 0) | (wide[:, 0] >= n1), -1, wide[:, 0])
+        b = torch.where(wide[:, 1] < 0, -1, wide[:, 1] + n1)
+        wide = torch.stack([a, b], 1)
+    return wide.clamp(-1, 0x7fffffff).to(torch.int32).contiguous()
+
+
+def _cameras(cams1, cams2, pairs, K, n1, n2):
+    """the camera table of the pose calls -> (cams, n_cams, cam_idx int32 [K, 2] or None = two rows per entry)"""
+    import torch
+    if pairs is None:
+        return cams1.contiguous(), 2 * K, None
+    return cams1.contiguous() if cams2 is None else torch.cat([cams1, cams2]), n1 + (n2 or 0), _cam_index(pairs, n1, n2)
 
 
 def _prep(pts1, pts2, counts):
@@ -48,15 +121,11 @@ def _run(which, pts1, pts2, counts, prm, seeds, min_n):
     model = torch.zeros((P, 9), dtype=torch.float64, device=dev)
     mask = torch.zeros(int(offs[-1]), dtype=torch.uint8, device=dev)
     stats = torch.zeros((P, 16), dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream(dev)
+    di, stream, sp = _stream(dev)
     fn = _lib.lib().mi_degensac_find_fundamental_batch_dev if which == "F" else _lib.lib().mi_degensac_find_homography_batch_dev
-    rc = fn(pts1.data_ptr(), pts2.data_ptr(), d_off.data_ptr(), offs.ctypes.data_as(C.POINTER(C.c_int64)), P, int(pts1.shape[1]),
-            C.byref(prm), d_seeds.data_ptr(), dev.index or 0, C.c_void_p(stream.cuda_stream),
-            model.data_ptr(), mask.data_ptr(), stats.data_ptr())
+    rc = fn(_p(pts1), _p(pts2), _p(d_off), _lib.ptr(offs), P, int(pts1.shape[1]), C.byref(prm), _p(d_seeds), di, sp, _p(model), _p(mask), _p(stats))
     _lib.check(rc)
-    # the kernel reads d_off / d_seeds asynchronously: keep them alive until the stream reaches this point
-    for t in (d_off, d_seeds, pts1, pts2):
-        t.record_stream(stream)
+    _keep_alive(stream, d_off, d_seeds, pts1, pts2)
     return model.view(P, 3, 3), mask.to(torch.bool), stats, offs
 
 
@@ -114,15 +183,10 @@ def knn_match_tensors(desc1, desc2, norm=None):
     if a.data_ptr() % 4: a = a.clone()
     if b.data_ptr() % 4: b = b.clone()
     n1, n2, dim = a.shape[0], b.shape[0], a.shape[1]
-    idx = torch.full((n1, 2), -1, dtype=torch.int32, device=dev)
-    dist = torch.full((n1, 2), float("inf"), dtype=torch.float32, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    rc = _lib.lib().mi_degensac_match_knn2_dev(norm, a.data_ptr(), n1, b.data_ptr(), n2, dim, dev.index or 0, C.c_void_p(stream.cuda_stream),
-                                               idx.data_ptr(), dist.data_ptr())
-    if rc != 0:
-        raise _lib.MiDegensacError(f"mi_degensac error {rc}: {_lib.lib().mi_degensac_match_last_error().decode()}")
-    for t in (a, b):
-        t.record_stream(stream)
+    idx, dist, _ = _knn_out(n1, dev)
+    di, stream, sp = _stream(dev)
+    _lib.check_match(_lib.lib().mi_degensac_match_knn2_dev(norm, _p(a), n1, _p(b), n2, dim, di, sp, _p(idx), _p(dist)), value_error=False)
+    _keep_alive(stream, a, b)
     return idx, dist
 
 
@@ -132,12 +196,9 @@ def match_filter_tensors(idx, dist, ratio=0.9, back=None):
     import torch
     dev = idx.device; n1 = idx.shape[0]
     keep = torch.zeros(n1, dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    rc = _lib.lib().mi_degensac_match_filter_dev(idx.data_ptr(), dist.data_ptr(), n1, float(ratio), back.data_ptr() if back is not None else None,
-                                                 dev.index or 0, C.c_void_p(stream.cuda_stream), keep.data_ptr())
-    _lib.check_match(rc)
-    for t in (idx, dist) + ((back,) if back is not None else ()):
-        t.record_stream(stream)
+    di, stream, sp = _stream(dev)
+    _lib.check_match(_lib.lib().mi_degensac_match_filter_dev(_p(idx), _p(dist), n1, float(ratio), _p(back), di, sp, _p(keep)))
+    _keep_alive(stream, idx, dist, back)
     return keep
 
 
@@ -153,15 +214,10 @@ def match_decide_tensors(idx, dist, ratio=0.9, back=None, back_dist=None, max_di
     rule = matcher.check_rule(ratio, "ratio" if back_ratio else back is not None, max_dist)
     dev = idx.device; n1 = idx.shape[0]
     keep = torch.zeros(n1, dtype=torch.uint8, device=dev)
-    stream = torch.cuda.current_stream(dev)
+    di, stream, sp = _stream(dev)
     mp = _lib.MatchParamsEx(0, 0, rule.ratio, rule.mutual, None, rule.decide, rule.max_dist)
-    rc = _lib.lib().mi_degensac_match_decide_dev(C.byref(mp), idx.data_ptr(), dist.data_ptr(), n1, back.data_ptr() if back is not None else None,
-                                                 back_dist.data_ptr() if back_dist is not None else None, dev.index or 0,
-                                                 C.c_void_p(stream.cuda_stream), keep.data_ptr())
-    _lib.check_match(rc)
-    for t in (idx, dist, back, back_dist):
-        if t is not None:
-            t.record_stream(stream)
+    _lib.check_match(_lib.lib().mi_degensac_match_decide_dev(C.byref(mp), _p(idx), _p(dist), n1, _p(back), _p(back_dist), di, sp, _p(keep)))
+    _keep_alive(stream, idx, dist, back, back_dist)
     return keep
 
 
@@ -180,18 +236,8 @@ def match_snn_tensors(desc1, desc2, ratio=0.9, mutual=False, norm=None, *, max_d
             keep = torch.zeros(idx.shape[0], dtype=torch.uint8, device=idx.device)
         else:
             keep = match_decide_tensors(idx, dist, ratio, back, bdist, max_dist, bool(rule.decide & _lib.DECIDE_BACK_RATIO))
-        sel = torch.nonzero(keep, as_tuple=False).flatten()
-        return sel, idx[sel, 0].to(torch.int64), dist[sel, 0]
-    dev = idx.device; n1 = idx.shape[0]
-    keep = torch.zeros(n1, dtype=torch.uint8, device=dev)
-    back = knn_match_tensors(desc2, desc1, norm)[0] if mutual and desc2.shape[0] > 0 else None
-    stream = torch.cuda.current_stream(dev)
-    rc = _lib.lib().mi_degensac_match_filter_dev(idx.data_ptr(), dist.data_ptr(), n1, float(ratio), back.data_ptr() if back is not None else None,
-                                                 dev.index or 0, C.c_void_p(stream.cuda_stream), keep.data_ptr())
-    if rc != 0:
-        raise _lib.MiDegensacError(f"mi_degensac error {rc}: {_lib.lib().mi_degensac_match_last_error().decode()}")
-    if back is not None:
-        back.record_stream(stream)
+    else:
+        keep = match_filter_tensors(idx, dist, ratio, knn_match_tensors(desc2, desc1, norm)[0] if mutual and desc2.shape[0] > 0 else None)
     sel = torch.nonzero(keep, as_tuple=False).flatten()
     return sel, idx[sel, 0].to(torch.int64), dist[sel, 0]
 
@@ -203,11 +249,9 @@ def kpts_to_xyA_tensors(kpts):
         raise ValueError("keypoints should be a float32 tensor [n, 4] = (x, y, size, angle) on a ROCm device")
     k = kpts.contiguous(); dev = k.device
     out = torch.zeros((k.shape[0], 6), dtype=torch.float64, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    rc = _lib.lib().mi_degensac_kpts_to_xyA_dev(k.data_ptr(), k.shape[0], dev.index or 0, C.c_void_p(stream.cuda_stream), out.data_ptr())
-    if rc != 0:
-        raise _lib.MiDegensacError(f"mi_degensac error {rc}: {_lib.lib().mi_degensac_match_last_error().decode()}")
-    k.record_stream(stream)
+    di, stream, sp = _stream(dev)
+    _lib.check_match(_lib.lib().mi_degensac_kpts_to_xyA_dev(_p(k), k.shape[0], di, sp, _p(out)), value_error=False)
+    _keep_alive(stream, k)
     return out
 
 
@@ -231,12 +275,10 @@ def quantize_descriptors_tensors(desc, preset="rootsift", *, normalize=None, sca
               and out.is_contiguous() and out.data_ptr() % 4 == 0):
         raise ValueError(f"out should be a contiguous, 4-byte aligned uint8 tensor [{n}, {out_dim}] on the descriptors' device")
     clipped = torch.empty(n, dtype=torch.int32, device=dev) if return_clipped else None
-    stream = torch.cuda.current_stream(dev)
+    di, stream, sp = _stream(dev)
     qp = _lib.QuantParams(nz, sc, of)
-    rc = _lib.lib().mi_degensac_desc_quantize_dev(C.byref(qp), a.data_ptr(), n, dim, dev.index or 0, C.c_void_p(stream.cuda_stream), out.data_ptr(),
-                                                  clipped.data_ptr() if return_clipped else None)
-    _lib.check_match(rc)
-    a.record_stream(stream)
+    _lib.check_match(_lib.lib().mi_degensac_desc_quantize_dev(C.byref(qp), _p(a), n, dim, di, sp, _p(out), _p(clipped)))
+    _keep_alive(stream, a)
     return (out, clipped) if return_clipped else out
 
 
@@ -261,25 +303,36 @@ def knn_match_batch_tensors(desc1, desc2, counts1, counts2, norm=None):
     next counts2[p] rows of desc2.  Returns (idx [N1, 2] int32 with indices LOCAL to the pair, dist [N1, 2] float32) on the device,
     per pair bit-identical to knn_match_tensors on that pair; asynchronous on the current stream.  norm: None = the dtype's norm
     (float32 L2, uint8 Hamming), or "l2" / "hamming" / "l2_u8" (uint8 rows under L2, dim <= 256)."""
-    import torch
     from . import matcher
-    if not (isinstance(desc1, torch.Tensor) and isinstance(desc2, torch.Tensor)):
-        raise ValueError("descriptors must be torch tensors on a ROCm device")
+    _require("descriptors", (desc1, desc2))
     code, _, o1, o2 = matcher.check_match_verify_args("F", 1.0, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
                                                       (desc1.shape[0], 2), np.float64, (desc2.shape[0], 2), np.float64, counts1, counts2)
-    a, b = _desc_pair(desc1, desc2)
-    dev = a.device; n1 = a.shape[0]; K = len(o1) - 1
-    idx = torch.full((n1, 2), -1, dtype=torch.int32, device=dev)
-    dist = torch.full((n1, 2), float("inf"), dtype=torch.float32, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    rc = _lib.lib().mi_degensac_match_knn2_batch_dev(code, a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                     o2.ctypes.data_as(C.POINTER(C.c_int64)), K, int(a.shape[1]), dev.index or 0,
-                                                     C.c_void_p(stream.cuda_stream), idx.data_ptr(), dist.data_ptr())
-    if rc != 0:
-        raise _lib.MiDegensacError(f"mi_degensac error {rc}: {_lib.lib().mi_degensac_match_last_error().decode()}")
-    for t in (a, b):
-        t.record_stream(stream)
+    return _knn2_dev(matcher.layout(o1, o2), code, *_desc_pair(desc1, desc2), value_error=False)
+
+
+def _knn2_dev(L, code, a, b, k2=None, r=None, value_error=True):
+    """mi_degensac_match_knn2_* (k2 and r given: mi_degensac_match_fginn_knn2_*, the FGINN second neighbour at radius r on the keypoints
+    k2) of the checked layout L on prepared device tensors, asynchronous on the current stream.  Returns (idx [n, 2], dist [n, 2])."""
+    from . import matcher
+    dev = a.device
+    idx, dist, _ = _knn_out(L.n, dev)
+    di, stream, sp = _stream(dev)
+    fginn = () if k2 is None else (_p(k2), int(k2.shape[1]), r)
+    entry = getattr(_lib.lib(), f"mi_degensac_match_{'' if k2 is None else 'fginn_'}knn2_{L.name}_dev")
+    _lib.check_match(entry(code, _p(a), _p(b), *matcher.knn_layout(L, int(a.shape[1])), *fginn, di, sp, _p(idx), _p(dist)), value_error)
+    _keep_alive(stream, a, b, k2)
     return idx, dist
+
+
+def _fginn_knn2_args(desc1, desc2, kps2, spatial_th):
+    """the checks of the two FGINN knn2 calls in front of their layout check -> the checked radius"""
+    from . import matcher
+    import torch
+    _require("desc1, desc2 and kps2", (desc1, desc2, kps2))
+    r = matcher.check_fginn_th(spatial_th, "spatial_th")
+    if kps2.dim() != 2 or kps2.dtype != torch.float64 or kps2.shape[1] not in (2, 6):
+        raise ValueError("keypoints should be float64 [n, 2] / [n, 6] rows")
+    return r
 
 
 def knn_match_fginn_batch_tensors(desc1, desc2, kps2, counts1, counts2, spatial_th=10.0, norm=None):
@@ -289,52 +342,27 @@ def knn_match_fginn_batch_tensors(desc1, desc2, kps2, counts1, counts2, spatial_
     slot 0 (dx*dx + dy*dy >= spatial_th**2 in float64; NaN never competes), -1 / inf when there is none.  spatial_th=0 with finite
     keypoints gives knn_match_batch_tensors bit for bit.  Returns (idx [N1, 2] int32, dist [N1, 2] float32) on the device,
     asynchronous on the current stream (no host synchronisation)."""
-    import torch
     from . import matcher
-    if not all(isinstance(t, torch.Tensor) for t in (desc1, desc2, kps2)):
-        raise ValueError("desc1, desc2 and kps2 must be torch tensors on a ROCm device")
-    r = matcher.check_fginn_th(spatial_th, "spatial_th")
-    if kps2.dim() != 2 or kps2.dtype != torch.float64 or kps2.shape[1] not in (2, 6):
-        raise ValueError("keypoints should be float64 [n, 2] / [n, 6] rows")
+    r = _fginn_knn2_args(desc1, desc2, kps2, spatial_th)
     code, _, o1, o2 = matcher.check_match_verify_args("F", 1.0, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
                                                       (desc1.shape[0], kps2.shape[1]), np.float64, tuple(kps2.shape), kps2.dtype, counts1, counts2)
-    if kps2.device != desc1.device:
-        raise ValueError("desc1, desc2 and kps2 must live on the same ROCm device")
-    a, b = _desc_pair(desc1, desc2)
-    k2 = kps2.contiguous()
-    dev = a.device; n1 = a.shape[0]; K = len(o1) - 1
-    idx = torch.full((n1, 2), -1, dtype=torch.int32, device=dev)
-    dist = torch.full((n1, 2), float("inf"), dtype=torch.float32, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    lp = C.POINTER(C.c_int64)
-    rc = _lib.lib().mi_degensac_match_fginn_knn2_batch_dev(code, a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(lp), o2.ctypes.data_as(lp), K,
-                                                           int(a.shape[1]), k2.data_ptr(), int(k2.shape[1]), r, dev.index or 0,
-                                                           C.c_void_p(stream.cuda_stream), idx.data_ptr(), dist.data_ptr())
-    _lib.check_match(rc)
-    for t in (a, b, k2):
-        t.record_stream(stream)
-    return idx, dist
+    _require("desc1, desc2 and kps2", (desc1, kps2), "same")
+    return _knn2_dev(matcher.layout(o1, o2), code, *_desc_pair(desc1, desc2), kps2.contiguous(), r)
 
 
-def _guided_dev(code, a, b, k1, k2, o1, o2, Md, model, rule, px, et, fginn_r=None):
-    """mi_degensac_match_guided_batch_dev (fginn_r, a checked radius: mi_degensac_match_guided_fginn_batch_dev) on prepared device
-    tensors (Md: [K, 9] driver-form models), asynchronous on the current stream.  Returns (match [N1] int32, idx [N1, 2] int32,
-    dist [N1, 2] float32)."""
-    import torch
+def _guided_dev(L, code, a, b, k1, k2, Md, model, rule, px, et, fginn_r=None):
+    """mi_degensac_match_guided_{batch,pairs}_dev (fginn_r, a checked radius: mi_degensac_match_guided_fginn_*_dev) of the checked layout
+    L on prepared device tensors (Md: [K, 9] driver-form models), asynchronous on the current stream.  Returns (match [n] int32,
+    idx [n, 2] int32, dist [n, 2] float32)."""
     from . import matcher
-    dev = a.device; n1 = a.shape[0]; K = len(o1) - 1
-    idx = torch.full((n1, 2), -1, dtype=torch.int32, device=dev)
-    dist = torch.full((n1, 2), float("inf"), dtype=torch.float32, device=dev)
-    match = torch.full((n1,), -1, dtype=torch.int32, device=dev)
+    dev = a.device
+    idx, dist, match = _knn_out(L.n, dev, True)
     mp = _lib.match_params(code, a.shape[1], rule, fginn_r); gp = _lib.GuideParams(model == "H", et, px)
-    stream = torch.cuda.current_stream(dev)
-    rc = matcher.guided_entry("batch_dev", fginn_r)(C.byref(mp), a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                    o2.ctypes.data_as(C.POINTER(C.c_int64)), k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]), K,
-                                                    Md.data_ptr(), C.byref(gp), dev.index or 0, C.c_void_p(stream.cuda_stream), idx.data_ptr(),
-                                                    dist.data_ptr(), match.data_ptr(), None, None)
+    di, stream, sp = _stream(dev)
+    rc = matcher.guided_entry(f"{L.name}_dev", fginn_r)(C.byref(mp), _p(a), _p(b), *matcher.guided_layout(L, _p(k1), _p(k2), int(k1.shape[1])),
+                                                        _p(Md), C.byref(gp), di, sp, _p(idx), _p(dist), _p(match), None, None)
     _lib.check_match(rc)
-    for t in (a, b, k1, k2, Md):
-        t.record_stream(stream)
+    _keep_alive(stream, a, b, k1, k2, Md)
     return match, idx, dist
 
 
@@ -367,28 +395,28 @@ def guided_match_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, model
     of mutual stays the plain one.
     ratio=None, mutual="ratio" and max_dist: the rule of matcher.check_rule in its guided form (a missing slot 1 has dist = inf and passes
     either ratio test)."""
-    import torch
     from . import matcher
     rule = matcher.check_rule(ratio, mutual, max_dist, fginn=fginn_th is not None)
     ts = (kps1, kps2, desc1, desc2, models)
-    if not all(isinstance(t, torch.Tensor) for t in ts):
-        raise ValueError("kps1, kps2, desc1, desc2 and models must be torch tensors on a ROCm device")
+    _require(_GUIDED_NAMES, ts)
     code, kind, o1, o2 = matcher.check_match_verify_args(model, ratio, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
                                                          tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype, counts1, counts2)
-    K = len(o1) - 1
-    px, et = matcher.check_guided_args(model, px_th, error_type, tuple(models.shape), models.dtype, K)
+    return _guided_tensors(matcher.layout(o1, o2), code, kind, ts, model, rule, px_th, error_type, driver_form, fginn_th, False)
+
+
+_GUIDED_NAMES = "kps1, kps2, desc1, desc2 and models"
+
+
+def _guided_tensors(L, code, kind, ts, model, rule, px_th, error_type, driver_form, fginn_th, per_store):
+    """the two guided calls after their layout check: the guided stage's own checks, the device refusal, the conversions, the call"""
+    from . import matcher
+    kps1, kps2, desc1, desc2, models = ts
+    px, et = matcher.check_guided_args(model, px_th, error_type, tuple(models.shape), models.dtype, L.K)
     fr = None if fginn_th is None else matcher.check_fginn_th(fginn_th)
-    if any(t.device != desc1.device for t in ts) or desc1.device.type != "cuda":
-        raise ValueError("kps1, kps2, desc1, desc2 and models must live on the same ROCm device")
+    _require(_GUIDED_NAMES, ts, "cuda")
     a, b = _desc_pair(desc1, desc2)
-    if kind == "kpts":
-        k1 = kpts_to_xyA_tensors(kps1); k2 = kpts_to_xyA_tensors(kps2)
-    else:
-        k1 = kps1.contiguous(); k2 = kps2.contiguous()
-    M = models.contiguous()
-    if model == "H" and not driver_form:
-        M = _h_driver_form(M)
-    return _guided_dev(code, a, b, k1, k2, o1, o2, M.reshape(K, 9).contiguous(), model, rule, px, et, fr)
+    k1, k2 = _store_kps(kind, kps1, kps2, per_store)
+    return _guided_dev(L, code, a, b, k1, k2, _driver_models(models, model, driver_form, L.K), model, rule, px, et, fr)
 
 
 def _h_user_form(M):
@@ -402,30 +430,38 @@ def _h_user_form(M):
     return torch.where(found, inv, torch.zeros_like(M))
 
 
-def _match_verify_dev(entry, layout, model, mp, prm, a, b, k1, k2, sd, K, n, guide=None):
-    """The match-and-verify call of both layouts after the argument checks: entry = the *_dev entry point, layout = its arguments
-    between the descriptors and the estimator's params, sd = uint32 seeds [K], n = output rows.  guide (nullable) gets the driver-form
-    models [K, 9] as the library wrote them, on the same stream.  Returns (model [K, 3, 3] — H as the user-facing form —, match [n],
-    inlier [n] bool, stats [K, 16], n_tentatives [K] numpy int64, what guide returned)."""
+def _verify_in(L, sd, dev):
+    """what every match-and-verify call has once: (seeds on the device, match [n] filled with -1, the host counts [K])"""
     import torch
-    dev = a.device
     # pinned + non_blocking: a pageable copy would wait for the stream (the call's one synchronisation is the count read)
     d_seeds = torch.from_numpy(sd.view(np.int32)).pin_memory().to(dev, non_blocking=True)
-    M = torch.zeros((K, 9), dtype=torch.float64, device=dev)
-    match = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    inlier = torch.zeros(n, dtype=torch.uint8, device=dev)
-    stats = torch.zeros((K, 16), dtype=torch.int32, device=dev)
-    cnt = np.zeros(K, np.int32)
-    stream = torch.cuda.current_stream(dev)
-    rc = entry(1 if model == "H" else 0, C.byref(mp), a.data_ptr(), b.data_ptr(), *layout, C.byref(prm), d_seeds.data_ptr(), dev.index or 0,
-               C.c_void_p(stream.cuda_stream), M.data_ptr(), match.data_ptr(), inlier.data_ptr(), stats.data_ptr(),
-               cnt.ctypes.data_as(C.POINTER(C.c_int32)))
+    return d_seeds, torch.full((L.n,), -1, dtype=torch.int32, device=dev), np.zeros(L.K, np.int32)
+
+
+def _verify_out(L, dev):
+    """the outputs of one estimator over a layout with their fills: (model [K, 9], inlier [n] uint8, stats [K, 16])"""
+    import torch
+    return (torch.zeros((L.K, 9), dtype=torch.float64, device=dev), torch.zeros(L.n, dtype=torch.uint8, device=dev),
+            torch.zeros((L.K, 16), dtype=torch.int32, device=dev))
+
+
+def _match_verify_dev(entry, L, model, mp, prm, a, b, k1, k2, sd, guide=None):
+    """The match-and-verify call of both layouts after the argument checks: entry = the *_dev entry point of the checked layout L, sd =
+    uint32 seeds [K].  guide (nullable) gets the driver-form models [K, 9] as the library wrote them, on the same stream.  Returns
+    (model [K, 3, 3] — H as the user-facing form —, match [n], inlier [n] bool, stats [K, 16], n_tentatives [K] numpy int64, what guide
+    returned)."""
+    import torch
+    from . import matcher
+    dev = a.device
+    d_seeds, match, cnt = _verify_in(L, sd, dev)
+    M, inlier, stats = _verify_out(L, dev)
+    di, stream, sp = _stream(dev)
+    rc = entry(1 if model == "H" else 0, C.byref(mp), _p(a), _p(b), *matcher.verify_layout(L, _p(k1), _p(k2), int(k1.shape[1])), C.byref(prm),
+               _p(d_seeds), di, sp, _p(M), _p(match), _p(inlier), _p(stats), _lib.ptr(cnt))
     _lib.check(rc)
-    # the estimator and the scatter read these asynchronously: keep them alive until the stream reaches this point
-    for t in (a, b, k1, k2, d_seeds):
-        t.record_stream(stream)
+    _keep_alive(stream, a, b, k1, k2, d_seeds)
     gm = guide(M) if guide else None
-    M = M.view(K, 3, 3)
+    M = M.view(L.K, 3, 3)
     return _h_user_form(M) if model == "H" else M, match, inlier.to(torch.bool), stats, cnt.astype(np.int64), gm
 
 
@@ -451,33 +487,28 @@ def match_and_verify_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2, m
     guided_fginn_th: None, or the radius of guided_match_batch_tensors(fginn_th=) for the guided stage (FGINN inside the gate; a query
     whose only gated companions lie inside the radius is kept).  It is passed on only with guided=True and is a ValueError without it.
     ratio=None, mutual="ratio" and max_dist: the rule of matcher.check_rule, for the tentatives and (guided form) the guided stage."""
-    import torch
     from . import matcher
     gfr = matcher.check_guided_fginn_th(guided, guided_fginn_th)
     rule = matcher.check_rule(ratio, mutual, max_dist, fginn=fginn_th is not None)
     if gfr is not None:
         matcher.check_rule(ratio, mutual, max_dist, fginn=True)
     ts = (kps1, kps2, desc1, desc2)
-    if not all(isinstance(t, torch.Tensor) for t in ts):
-        raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
+    _require(_VERIFY_NAMES, ts)
     code, kind, o1, o2 = matcher.check_match_verify_args(model, ratio, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
                                                          tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype, counts1, counts2, fginn_th)
-    if any(t.device != desc1.device for t in ts):
-        raise ValueError("kps1, kps2, desc1 and desc2 must live on the same ROCm device")
+    _require(_VERIFY_NAMES, ts, "same")
     prm = matcher.estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
     a, b = _desc_pair(desc1, desc2)
-    K = len(o1) - 1; n1 = a.shape[0]
-    if kind == "kpts":
-        k1 = kpts_to_xyA_tensors(kps1); k2 = kpts_to_xyA_tensors(kps2)
-    else:
-        k1 = kps1.contiguous(); k2 = kps2.contiguous()
-    sd = matcher._seeds_u32(None if seeds is None else np.asarray(seeds).ravel(), K)
-    lp = C.POINTER(C.c_int64)
-    guide = (lambda M: _guided_dev(code, a, b, k1, k2, o1, o2, M, model, rule, prm.px_th, prm.error_type, gfr)[0]) if guided else None
-    res = _match_verify_dev(_lib.lib().mi_degensac_match_verify_batch_dev, (o1.ctypes.data_as(lp), o2.ctypes.data_as(lp), k1.data_ptr(), k2.data_ptr(),
-                                                                          int(k1.shape[1]), K),
-                            model, _lib.match_params(code, a.shape[1], rule, fginn_th), prm, a, b, k1, k2, sd, K, n1, guide)
+    k1, k2 = _store_kps(kind, kps1, kps2, False)
+    L = matcher.layout(o1, o2)
+    sd = matcher._seeds_u32(None if seeds is None else np.asarray(seeds).ravel(), L.K)
+    guide = (lambda M: _guided_dev(L, code, a, b, k1, k2, M, model, rule, prm.px_th, prm.error_type, gfr)[0]) if guided else None
+    res = _match_verify_dev(_lib.lib().mi_degensac_match_verify_batch_dev, L, model, _lib.match_params(code, a.shape[1], rule, fginn_th), prm,
+                            a, b, k1, k2, sd, guide)
     return res if guided else res[:5]
+
+
+_VERIFY_NAMES = "kps1, kps2, desc1 and desc2"
 
 
 # ---- the pair-list form: image stores + (i, j) image indices (include/mi_degensac.h mi_degensac_match_*_pairs*) ----
@@ -489,26 +520,12 @@ def knn_match_pairs_tensors(desc1, desc2, counts1, counts2, pairs, norm=None):
     indices LOCAL to image j, dist [N, 2] float32, pair_offsets [K + 1] host int64): pair p owns the rows pair_offsets[p] ..
     pair_offsets[p + 1], counts1[pairs[p, 0]] of them, and they are bit for bit what knn_match_batch_tensors returns for the pair's
     copied rows.  Asynchronous on the current stream."""
-    import torch
     from . import matcher
-    if not (isinstance(desc1, torch.Tensor) and isinstance(desc2, torch.Tensor)):
-        raise ValueError("descriptors must be torch tensors on a ROCm device")
+    _require("descriptors", (desc1, desc2))
     code, _, o1, o2, pr, po, _ = matcher.check_match_pairs_args("F", 1.0, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
                                                                 (desc1.shape[0], 2), np.float64, (desc2.shape[0], 2), np.float64, counts1, counts2,
                                                                 pairs)
-    a, b = _desc_pair(desc1, desc2)
-    dev = a.device; n = int(po[-1]); K = len(pr)
-    idx = torch.full((n, 2), -1, dtype=torch.int32, device=dev)
-    dist = torch.full((n, 2), float("inf"), dtype=torch.float32, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    lp = C.POINTER(C.c_int64)
-    rc = _lib.lib().mi_degensac_match_knn2_pairs_dev(code, a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp),
-                                                     len(o2) - 1, pr.ctypes.data_as(C.POINTER(C.c_int32)), K, int(a.shape[1]), dev.index or 0,
-                                                     C.c_void_p(stream.cuda_stream), idx.data_ptr(), dist.data_ptr())
-    _lib.check_match(rc)
-    for t in (a, b):
-        t.record_stream(stream)
-    return idx, dist, po
+    return _knn2_dev(matcher.layout(o1, o2, pr, po), code, *_desc_pair(desc1, desc2)) + (po,)
 
 
 def knn_match_fginn_pairs_tensors(desc1, desc2, kps2, counts1, counts2, pairs, spatial_th=10.0, norm=None):
@@ -519,33 +536,13 @@ def knn_match_fginn_pairs_tensors(desc1, desc2, kps2, counts1, counts2, pairs, s
     copied, and per entry the rows are bit for bit what knn_match_fginn_batch_tensors returns for the entry's copied rows.  Returns
     (idx [N, 2] int32 with indices LOCAL to image j, dist [N, 2] float32, pair_offsets [K + 1] host int64); asynchronous on the current
     stream (no host synchronisation)."""
-    import torch
     from . import matcher
-    if not all(isinstance(t, torch.Tensor) for t in (desc1, desc2, kps2)):
-        raise ValueError("desc1, desc2 and kps2 must be torch tensors on a ROCm device")
-    r = matcher.check_fginn_th(spatial_th, "spatial_th")
-    if kps2.dim() != 2 or kps2.dtype != torch.float64 or kps2.shape[1] not in (2, 6):
-        raise ValueError("keypoints should be float64 [n, 2] / [n, 6] rows")
+    r = _fginn_knn2_args(desc1, desc2, kps2, spatial_th)
     code, _, o1, o2, pr, po, _ = matcher.check_match_pairs_args("F", 1.0, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
                                                                 (desc1.shape[0], kps2.shape[1]), np.float64, tuple(kps2.shape), kps2.dtype,
                                                                 counts1, counts2, pairs)
-    if kps2.device != desc1.device:
-        raise ValueError("desc1, desc2 and kps2 must live on the same ROCm device")
-    a, b = _desc_pair(desc1, desc2)
-    k2 = kps2.contiguous()
-    dev = a.device; n = int(po[-1]); K = len(pr)
-    idx = torch.full((n, 2), -1, dtype=torch.int32, device=dev)
-    dist = torch.full((n, 2), float("inf"), dtype=torch.float32, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    lp = C.POINTER(C.c_int64)
-    rc = _lib.lib().mi_degensac_match_fginn_knn2_pairs_dev(code, a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(lp), len(o1) - 1,
-                                                           o2.ctypes.data_as(lp), len(o2) - 1, pr.ctypes.data_as(C.POINTER(C.c_int32)), K,
-                                                           int(a.shape[1]), k2.data_ptr(), int(k2.shape[1]), r, dev.index or 0,
-                                                           C.c_void_p(stream.cuda_stream), idx.data_ptr(), dist.data_ptr())
-    _lib.check_match(rc)
-    for t in (a, b, k2):
-        t.record_stream(stream)
-    return idx, dist, po
+    _require("desc1, desc2 and kps2", (desc1, kps2), "same")
+    return _knn2_dev(matcher.layout(o1, o2, pr, po), code, *_desc_pair(desc1, desc2), kps2.contiguous(), r) + (po,)
 
 
 def match_and_verify_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs, model="F", ratio=0.9, mutual=False, px_th=None, conf=None,
@@ -587,54 +584,46 @@ def _match_verify_pairs_tensors(fginn_r, kps1, kps2, desc1, desc2, counts1, coun
                                 max_dist=None):
     """the body of the two pair-list match-and-verify calls: fginn_r None = the plain call (which refuses fginn_th), a checked radius =
     the FGINN call and its entry point; ratio / mutual / max_dist: the rule of matcher.check_rule"""
-    import torch
     from . import matcher
     rule = matcher.check_rule(ratio, mutual, max_dist, fginn=fginn_r is not None)
     ts = (kps1, kps2, desc1, desc2)
-    if not all(isinstance(t, torch.Tensor) for t in ts):
-        raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
+    _require(_VERIFY_NAMES, ts)
     code, kind, o1, o2, pr, po, sd = matcher.check_match_pairs_args(model, ratio, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape),
                                                                     desc2.dtype, tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype,
                                                                     counts1, counts2, pairs, seeds, guided, fginn_th)
-    if any(t.device != desc1.device for t in ts):
-        raise ValueError("kps1, kps2, desc1 and desc2 must live on the same ROCm device")
+    _require(_VERIFY_NAMES, ts, "same")
     prm = matcher.estimator_params(model, px_th, conf, max_iters, laf_consistensy_coef, error_type, symmetric_error_check, enable_degeneracy_check)
     a, b = _desc_pair(desc1, desc2)
-    K = len(pr); n = int(po[-1])
-    conv = kpts_to_xyA_tensors if kind == "kpts" else (lambda k: k.contiguous())
-    k1 = conv(kps1); k2 = k1 if kps2 is kps1 else conv(kps2)          # once per store, not per pair
+    L = matcher.layout(o1, o2, pr, po)
+    k1, k2 = _store_kps(kind, kps1, kps2, True)          # once per store, not per pair
     if sd is None:
-        sd = matcher._seeds_u32(None, K)
-    lp = C.POINTER(C.c_int64)
-    layout = (o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]),
-              pr.ctypes.data_as(C.POINTER(C.c_int32)), K)
+        sd = matcher._seeds_u32(None, L.K)
     entry = _lib.lib().mi_degensac_match_verify_pairs_dev if fginn_r is None else _lib.lib().mi_degensac_match_verify_fginn_pairs_dev
-    return _match_verify_dev(entry, layout, model, _lib.match_params(code, a.shape[1], rule, fginn_r), prm, a, b, k1, k2, sd, K, n)[:5] + (po,)
+    return _match_verify_dev(entry, L, model, _lib.match_params(code, a.shape[1], rule, fginn_r), prm, a, b, k1, k2, sd)[:5] + (po,)
 
 
 # ---- match once, verify F and H (include/mi_degensac.h mi_degensac_match_verify_fh_*) ----
-def _match_verify_fh_dev(entry, layout, mp, prm_f, prm_h, a, b, k1, k2, sd, K, n):
-    """_match_verify_dev for the two-model entry points: one call, both estimators on the same tentatives.  Returns (F [K, 3, 3],
-    H [K, 3, 3] user-facing, match [n], inlier_f [n] bool, inlier_h [n] bool, stats_f [K, 16], stats_h [K, 16], summary [K, 4],
-    n_tentatives [K] numpy int64)."""
+def _match_verify_fh_dev(L, code, kind, ts, rule, fginn_r, prm_f, prm_h, sd, per_store):
+    """The two-model call of both layouts after the argument checks: the device refusal, the conversions, then one call with both
+    estimators on the same tentatives.  Returns (F [K, 3, 3], H [K, 3, 3] user-facing, match [n], inlier_f [n] bool, inlier_h [n] bool,
+    stats_f [K, 16], stats_h [K, 16], summary [K, 4], n_tentatives [K] numpy int64)."""
     import torch
-    dev = a.device
-    # pinned + non_blocking: a pageable copy would wait for the stream (the call's one synchronisation is the count read)
-    d_seeds = torch.from_numpy(sd.view(np.int32)).pin_memory().to(dev, non_blocking=True)
-    MF = torch.zeros((K, 9), dtype=torch.float64, device=dev); MH = torch.zeros((K, 9), dtype=torch.float64, device=dev)
-    match = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    inf = torch.zeros(n, dtype=torch.uint8, device=dev); inh = torch.zeros(n, dtype=torch.uint8, device=dev)
-    stf = torch.zeros((K, 16), dtype=torch.int32, device=dev); sth = torch.zeros((K, 16), dtype=torch.int32, device=dev)
+    from . import matcher
+    kps1, kps2, desc1, desc2 = ts
+    _require(_VERIFY_NAMES, ts, "same")
+    a, b = _desc_pair(desc1, desc2)
+    k1, k2 = _store_kps(kind, kps1, kps2, per_store)
+    dev = a.device; K = L.K
+    d_seeds, match, cnt = _verify_in(L, sd, dev)
+    MF, inf, stf = _verify_out(L, dev); MH, inh, sth = _verify_out(L, dev)
     summ = torch.zeros((K, 4), dtype=torch.int32, device=dev)
-    cnt = np.zeros(K, np.int32)
-    stream = torch.cuda.current_stream(dev)
-    rc = entry(C.byref(mp), a.data_ptr(), b.data_ptr(), *layout, C.byref(prm_f), C.byref(prm_h), d_seeds.data_ptr(), dev.index or 0,
-               C.c_void_p(stream.cuda_stream), MF.data_ptr(), MH.data_ptr(), match.data_ptr(), inf.data_ptr(), inh.data_ptr(), stf.data_ptr(),
-               sth.data_ptr(), summ.data_ptr(), cnt.ctypes.data_as(C.POINTER(C.c_int32)))
+    mp = _lib.match_params(code, a.shape[1], rule, fginn_r)
+    di, stream, sp = _stream(dev)
+    rc = getattr(_lib.lib(), f"mi_degensac_match_verify_fh_{L.name}_dev")(
+        C.byref(mp), _p(a), _p(b), *matcher.verify_layout(L, _p(k1), _p(k2), int(k1.shape[1])), C.byref(prm_f), C.byref(prm_h), _p(d_seeds), di, sp,
+        _p(MF), _p(MH), _p(match), _p(inf), _p(inh), _p(stf), _p(sth), _p(summ), _lib.ptr(cnt))
     _lib.check(rc)
-    # the estimators and the scatter read these asynchronously: keep them alive until the stream reaches this point
-    for t in (a, b, k1, k2, d_seeds):
-        t.record_stream(stream)
+    _keep_alive(stream, a, b, k1, k2, d_seeds)
     return MF.view(K, 3, 3), _h_user_form(MH.view(K, 3, 3)), match, inf.to(torch.bool), inh.to(torch.bool), stf, sth, summ, cnt.astype(np.int64)
 
 
@@ -657,29 +646,16 @@ def match_and_verify_fh_batch_tensors(kps1, kps2, desc1, desc2, counts1, counts2
     classifies the pairs.
     The guided stage is not part of this call (there is no guided= keyword): guided_match_batch_tensors / guided_match_pairs_tensors take
     either returned model as it is.  ratio=None, mutual="ratio" and max_dist: the rule of matcher.check_rule."""
-    import torch
     from . import matcher
     rule = matcher.check_rule(ratio, mutual, max_dist, fginn=fginn_th is not None)
     ts = (kps1, kps2, desc1, desc2)
-    if not all(isinstance(t, torch.Tensor) for t in ts):
-        raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
+    _require(_VERIFY_NAMES, ts)
     code, kind, o1, o2 = matcher.check_match_verify_args("H", ratio, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape), desc2.dtype,
                                                          tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype, counts1, counts2, fginn_th)
-    K = len(o1) - 1
-    sd = matcher._seeds_u32(None if seeds is None else np.asarray(seeds).ravel(), K)
+    L = matcher.layout(o1, o2)
+    sd = matcher._seeds_u32(None if seeds is None else np.asarray(seeds).ravel(), L.K)
     prm_f, prm_h = matcher.two_view_params(f_params, h_params)
-    if any(t.device != desc1.device for t in ts):
-        raise ValueError("kps1, kps2, desc1 and desc2 must live on the same ROCm device")
-    a, b = _desc_pair(desc1, desc2)
-    n1 = a.shape[0]
-    if kind == "kpts":
-        k1 = kpts_to_xyA_tensors(kps1); k2 = kpts_to_xyA_tensors(kps2)
-    else:
-        k1 = kps1.contiguous(); k2 = kps2.contiguous()
-    lp = C.POINTER(C.c_int64)
-    return _match_verify_fh_dev(_lib.lib().mi_degensac_match_verify_fh_batch_dev,
-                                (o1.ctypes.data_as(lp), o2.ctypes.data_as(lp), k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]), K),
-                                _lib.match_params(code, a.shape[1], rule, fginn_th), prm_f, prm_h, a, b, k1, k2, sd, K, n1)
+    return _match_verify_fh_dev(L, code, kind, ts, rule, fginn_th, prm_f, prm_h, sd, False)
 
 
 def match_and_verify_fh_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs, ratio=0.9, mutual=False, norm=None, fginn_th=None,
@@ -696,30 +672,18 @@ def match_and_verify_fh_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2
     pair_offsets [K + 1] host int64) with N = pair_offsets[K].
     The guided stage is not part of this call (there is no guided= keyword): guided_match_pairs_tensors / guided_match_batch_tensors take
     either returned model as it is."""
-    import torch
     from . import matcher
     rule = matcher.check_rule(ratio, mutual, max_dist, fginn=fginn_th is not None)
     ts = (kps1, kps2, desc1, desc2)
-    if not all(isinstance(t, torch.Tensor) for t in ts):
-        raise ValueError("kps1, kps2, desc1 and desc2 must be torch tensors on a ROCm device")
+    _require(_VERIFY_NAMES, ts)
     fr = None if fginn_th is None else matcher.check_fginn_th(fginn_th)
     code, kind, o1, o2, pr, po, sd = matcher.check_match_pairs_args("H", ratio, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape),
                                                                     desc2.dtype, tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype,
                                                                     counts1, counts2, pairs, seeds)
     prm_f, prm_h = matcher.two_view_params(f_params, h_params)
-    if any(t.device != desc1.device for t in ts):
-        raise ValueError("kps1, kps2, desc1 and desc2 must live on the same ROCm device")
-    a, b = _desc_pair(desc1, desc2)
-    K = len(pr); n = int(po[-1])
-    conv = kpts_to_xyA_tensors if kind == "kpts" else (lambda k: k.contiguous())
-    k1 = conv(kps1); k2 = k1 if kps2 is kps1 else conv(kps2)          # once per store, not per pair
     if sd is None:
-        sd = matcher._seeds_u32(None, K)
-    lp = C.POINTER(C.c_int64)
-    layout = (o1.ctypes.data_as(lp), len(o1) - 1, o2.ctypes.data_as(lp), len(o2) - 1, k1.data_ptr(), k2.data_ptr(), int(k1.shape[1]),
-              pr.ctypes.data_as(C.POINTER(C.c_int32)), K)
-    return _match_verify_fh_dev(_lib.lib().mi_degensac_match_verify_fh_pairs_dev, layout, _lib.match_params(code, a.shape[1], rule, fr),
-                                prm_f, prm_h, a, b, k1, k2, sd, K, n) + (po,)
+        sd = matcher._seeds_u32(None, len(pr))
+    return _match_verify_fh_dev(matcher.layout(o1, o2, pr, po), code, kind, ts, rule, fr, prm_f, prm_h, sd, True) + (po,)
 
 
 def guided_match_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs, models, model="F", ratio=0.9, mutual=False, px_th=None,
@@ -738,69 +702,33 @@ def guided_match_pairs_tensors(kps1, kps2, desc1, desc2, counts1, counts2, pairs
     keypoints of the entry's train image in store 2; a needy query is rescanned through its image's rows in store 1 and answered at
     its output row (two different rows in a list), nothing is copied.  A query whose only gated companions lie inside the radius is kept.
     ratio=None, mutual="ratio" and max_dist as in guided_match_batch_tensors."""
-    import torch
     from . import matcher
     rule = matcher.check_rule(ratio, mutual, max_dist, fginn=fginn_th is not None)
     ts = (kps1, kps2, desc1, desc2, models)
-    if not all(isinstance(t, torch.Tensor) for t in ts):
-        raise ValueError("kps1, kps2, desc1, desc2 and models must be torch tensors on a ROCm device")
+    _require(_GUIDED_NAMES, ts)
     code, kind, o1, o2, pr, po, _ = matcher.check_match_pairs_args(model, ratio, norm, tuple(desc1.shape), desc1.dtype, tuple(desc2.shape),
                                                                    desc2.dtype, tuple(kps1.shape), kps1.dtype, tuple(kps2.shape), kps2.dtype,
                                                                    counts1, counts2, pairs)
-    K = len(pr); n = int(po[-1])
-    px, et = matcher.check_guided_args(model, px_th, error_type, tuple(models.shape), models.dtype, K)
-    fr = None if fginn_th is None else matcher.check_fginn_th(fginn_th)
-    if any(t.device != desc1.device for t in ts) or desc1.device.type != "cuda":
-        raise ValueError("kps1, kps2, desc1, desc2 and models must live on the same ROCm device")
-    a, b = _desc_pair(desc1, desc2)
-    conv = kpts_to_xyA_tensors if kind == "kpts" else (lambda k: k.contiguous())
-    k1 = conv(kps1); k2 = k1 if kps2 is kps1 else conv(kps2)          # once per store, not per pair
-    M = models.contiguous()
-    if model == "H" and not driver_form:
-        M = _h_driver_form(M)
-    M = M.reshape(K, 9).contiguous()
-    dev = a.device
-    idx = torch.full((n, 2), -1, dtype=torch.int32, device=dev)
-    dist = torch.full((n, 2), float("inf"), dtype=torch.float32, device=dev)
-    match = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    mp = _lib.match_params(code, a.shape[1], rule, fr); gp = _lib.GuideParams(model == "H", et, px)
-    stream = torch.cuda.current_stream(dev)
-    lp = C.POINTER(C.c_int64)
-    rc = matcher.guided_entry("pairs_dev", fr)(C.byref(mp), a.data_ptr(), b.data_ptr(), o1.ctypes.data_as(lp), len(o1) - 1,
-                                               o2.ctypes.data_as(lp), len(o2) - 1, pr.ctypes.data_as(C.POINTER(C.c_int32)), K, k1.data_ptr(),
-                                               k2.data_ptr(), int(k1.shape[1]), M.data_ptr(), C.byref(gp), dev.index or 0,
-                                               C.c_void_p(stream.cuda_stream), idx.data_ptr(), dist.data_ptr(), match.data_ptr(), None, None)
-    _lib.check_match(rc)
-    for t in (a, b, k1, k2, M):
-        t.record_stream(stream)
-    return match, idx, dist, po
+    # once per store, not per pair
+    return _guided_tensors(matcher.layout(o1, o2, pr, po), code, kind, ts, model, rule, px_th, error_type, driver_form, fginn_th, True) + (po,)
 
 
 def _correspondences_tensors(match, counts1, counts2, pairs, keep, kps1, kps2, models, model, error_type, driver_form, store_rows, with_entry,
                              capacity):
     import torch
     from . import matcher
+    names = "match, keep, kps1, kps2 and models"
     ts = [t for t in (match, keep, kps1, kps2, models) if t is not None]
-    if not all(isinstance(t, torch.Tensor) for t in ts):
-        raise ValueError("match, keep, kps1, kps2 and models must be torch tensors on a ROCm device")
-    sd = lambda t: None if t is None else (tuple(t.shape), t.dtype)          # noqa: E731
-    o1, o2, pr, po, kind, et, cap = matcher.check_correspond_args(tuple(match.shape), match.dtype, counts1, counts2, pairs, sd(keep), sd(kps1),
-                                                                  sd(kps2), sd(models), model, error_type, capacity)
-    if any(t.device != match.device for t in ts) or match.device.type != "cuda":
-        raise ValueError("match, keep, kps1, kps2 and models must live on the same ROCm device")
+    _require(names, ts)
+    o1, o2, pr, po, kind, et, cap = matcher.check_correspond_args(tuple(match.shape), match.dtype, counts1, counts2, pairs, _sd(keep), _sd(kps1),
+                                                                  _sd(kps2), _sd(models), model, error_type, capacity)
+    _require(names, ts, "cuda")
     name, layout, K = matcher.correspond_layout(o1, o2, pr)
     dev = match.device
     m = match.contiguous()
     kp = None if keep is None else keep.contiguous().view(torch.uint8)
-    k1 = k2 = M = None
-    if kps1 is not None:
-        conv = kpts_to_xyA_tensors if kind == "kpts" else (lambda k: k.contiguous())
-        k1 = conv(kps1); k2 = k1 if kps2 is kps1 else conv(kps2)          # once per store
-    if models is not None:
-        M = models.contiguous()
-        if model == "H" and not driver_form:
-            M = _h_driver_form(M)
-        M = M.reshape(K, 9).contiguous()
+    k1, k2 = (None, None) if kps1 is None else _store_kps(kind, kps1, kps2, True)
+    M = None if models is None else _driver_models(models, model, driver_form, K)
     rows = torch.full((cap, 2), -1, dtype=torch.int32, device=dev)
     co = torch.empty(K + 1, dtype=torch.int64, device=dev)
     total = torch.empty(1, dtype=torch.int64, device=dev)
@@ -808,16 +736,13 @@ def _correspondences_tensors(match, counts1, counts2, pairs, keep, kps1, kps2, m
     pts = None if k1 is None else torch.full((cap, 4), float("nan"), dtype=torch.float64, device=dev)
     resid = None if M is None else torch.full((cap,), float("nan"), dtype=torch.float64, device=dev)
     gp = _lib.GuideParams(model == "H", et, 0.0)
-    stream = torch.cuda.current_stream(dev)
-    p = lambda t: None if t is None else t.data_ptr()          # noqa: E731
+    di, stream, sp = _stream(dev)
+    p = _p
     rc = getattr(_lib.lib(), f"mi_degensac_correspondences_{name}_dev")(*layout, p(m), p(kp), _lib.CORR_STORE_ROWS if store_rows else 0, p(k1), p(k2),
-                                                                       0 if k1 is None else int(k1.shape[1]), p(M), C.byref(gp), cap,
-                                                                       dev.index or 0, C.c_void_p(stream.cuda_stream), co.data_ptr(),
-                                                                       total.data_ptr(), p(rows), p(entry), p(pts), p(resid))
+                                                                       0 if k1 is None else int(k1.shape[1]), p(M), C.byref(gp), cap, di, sp,
+                                                                       p(co), p(total), p(rows), p(entry), p(pts), p(resid))
     _lib.check_match(rc)
-    for t in (m, kp, k1, k2, M):
-        if t is not None:
-            t.record_stream(stream)
+    _keep_alive(stream, m, kp, k1, k2, M)
     return rows, co, total, entry, pts, resid
 
 
@@ -870,15 +795,14 @@ def tracks_tensors(rows, counts, total=None, with_label=False):
     hold -1.  Every output is a pure function of the input: the same bits on every call.  Asynchronous on the current stream."""
     import torch
     from . import matcher
-    if not isinstance(rows, torch.Tensor) or (total is not None and not isinstance(total, torch.Tensor)):
-        raise ValueError("rows (and total) must be torch tensors on a ROCm device")
+    ts = [rows] + ([] if total is None else [total])
+    _require("rows (and total)", ts)
     off, R, M = matcher.check_tracks_args(tuple(rows.shape), rows.dtype, counts)
     if not rows.is_contiguous():
         raise ValueError("rows should be a contiguous int32 [M, 2] tensor")
     if total is not None and (tuple(total.shape) != (1,) or total.dtype != torch.int64):
         raise ValueError("total should be int64 [1] on the device, as the correspondence export returns it")
-    if rows.device.type != "cuda" or (total is not None and total.device != rows.device):
-        raise ValueError("rows and total must live on the same ROCm device")
+    _require("rows and total", ts, "cuda")
     dev = rows.device
     half = R // 2
     i32 = lambda n: torch.empty(max(n, 1), dtype=torch.int32, device=dev)          # noqa: E731  (an address also where n == 0)
@@ -886,15 +810,12 @@ def tracks_tensors(rows, counts, total=None, with_label=False):
     label = i32(R) if with_label else None
     to = torch.empty(half + 1, dtype=torch.int64, device=dev)
     nt = torch.empty(1, dtype=torch.int64, device=dev); no = torch.empty(1, dtype=torch.int64, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    p = lambda t: None if t is None else t.data_ptr()          # noqa: E731
-    rc = _lib.lib().mi_degensac_tracks_dev(off.ctypes.data_as(C.POINTER(C.c_int64)), len(off) - 1, p(rows) if M else None, M, p(total),
-                                           dev.index or 0, C.c_void_p(stream.cuda_stream), p(label), p(track), p(nt), p(no), p(to), p(obs), p(oi),
-                                           p(ti))
+    di, stream, sp = _stream(dev)
+    p = _p
+    rc = _lib.lib().mi_degensac_tracks_dev(_lib.ptr(off), len(off) - 1, p(rows) if M else None, M, p(total), di, sp, p(label), p(track), p(nt), p(no),
+                                           p(to), p(obs), p(oi), p(ti))
     _lib.check_match(rc)
-    for t in (rows, total):
-        if t is not None:
-            t.record_stream(stream)
+    _keep_alive(stream, rows, total)
     out = (track[:R], nt, to, obs[:R], oi[:R], ti[:half], no)
     return out + (label[:R],) if with_label else out
 
@@ -916,31 +837,24 @@ def refit_correspondences_tensors(pts, corr_offsets, models, model="F", px_th=No
     import torch
     from . import matcher
     ts = (pts, corr_offsets, models)
-    if not all(isinstance(t, torch.Tensor) for t in ts):
-        raise ValueError("pts, corr_offsets and models must be torch tensors on a ROCm device")
+    _require("pts, corr_offsets and models", ts)
     K, cap, px, et, mf = matcher.check_refit_args(tuple(pts.shape), pts.dtype, tuple(corr_offsets.shape), corr_offsets.dtype, tuple(models.shape),
                                                   models.dtype, model, px_th, error_type, max_fits)
-    if any(t.device != pts.device for t in ts) or pts.device.type != "cuda":
-        raise ValueError("pts, corr_offsets and models must live on the same ROCm device")
+    _require("pts, corr_offsets and models", ts, "cuda")
     dev = pts.device
     P = pts.contiguous(); o = corr_offsets.contiguous()
-    M = models.contiguous()
-    if model == "H" and not driver_form:
-        M = _h_driver_form(M)
-    M = M.reshape(K, 9).contiguous()
+    M = _driver_models(models, model, driver_form, K)
     out = torch.empty((K, 9), dtype=torch.float64, device=dev)
     user = torch.empty((K, 9), dtype=torch.float64, device=dev) if (model == "H" and not driver_form) else None
     inl = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)          # (an address also where cap == 0)
     info = torch.empty((K, 4), dtype=torch.int32, device=dev)
     resid = torch.empty(max(cap, 1), dtype=torch.float64, device=dev) if with_resid else None
     gp = _lib.GuideParams(model == "H", et, px)
-    stream = torch.cuda.current_stream(dev)
-    p = lambda t: None if t is None else t.data_ptr()          # noqa: E731
-    rc = _lib.lib().mi_degensac_refit_lists_dev(p(P), p(o), p(M), K, cap, C.byref(gp), mf, dev.index or 0, C.c_void_p(stream.cuda_stream), p(out),
-                                                p(inl), p(user), p(info), p(resid))
+    di, stream, sp = _stream(dev)
+    p = _p
+    rc = _lib.lib().mi_degensac_refit_lists_dev(p(P), p(o), p(M), K, cap, C.byref(gp), mf, di, sp, p(out), p(inl), p(user), p(info), p(resid))
     _lib.check_match(rc)
-    for t in (P, o, M):
-        t.record_stream(stream)
+    _keep_alive(stream, P, o, M)
     res = ((out if user is None else user).view(K, 3, 3), inl[:cap].view(torch.bool), info)
     return res + (resid[:cap],) if with_resid else res
 
@@ -964,29 +878,15 @@ def relative_pose_tensors(pts, corr_offsets, models, cams1, pairs=None, cams2=No
     import torch
     from . import matcher
     opt = [t for t in (pairs, cams2, keep) if t is not None]
+    names = "pts, corr_offsets, models, cams1 (and pairs, cams2, keep)"
     ts = [pts, corr_offsets, models, cams1] + opt
-    if not all(isinstance(t, torch.Tensor) for t in ts):
-        raise ValueError("pts, corr_offsets, models, cams1 (and pairs, cams2, keep) must be torch tensors on a ROCm device")
-    sd = lambda t: None if t is None else (tuple(t.shape), t.dtype)          # noqa: E731
+    _require(names, ts)
     K, cap, n1, n2, cos_min = matcher.check_pose_args(tuple(pts.shape), pts.dtype, tuple(corr_offsets.shape), corr_offsets.dtype, tuple(models.shape),
-                                                      models.dtype, tuple(cams1.shape), cams1.dtype, sd(pairs), sd(cams2), sd(keep), min_parallax_deg)
-    if any(t.device != pts.device for t in ts) or pts.device.type != "cuda":
-        raise ValueError("pts, corr_offsets, models, cams1 (and pairs, cams2, keep) must live on the same ROCm device")
+                                                      models.dtype, tuple(cams1.shape), cams1.dtype, _sd(pairs), _sd(cams2), _sd(keep), min_parallax_deg)
+    _require(names, ts, "cuda")
     dev = pts.device
     P = pts.contiguous(); o = corr_offsets.contiguous(); F = models.contiguous()
-    idx = None
-    if pairs is None:
-        cams = cams1.contiguous()
-        n_cams = 2 * K
-    else:
-        cams = cams1.contiguous() if cams2 is None else torch.cat([cams1, cams2])
-        n_cams = n1 + (n2 or 0)
-        wide = pairs.to(torch.int64)
-        if cams2 is not None:                                         # an image of store 1 must not reach into store 2's rows
-            a = torch.where((wide[:, 0] < 0) | (wide[:, 0] >= n1), -1, wide[:, 0])
-            b = torch.where(wide[:, 1] < 0, -1, wide[:, 1] + n1)
-            wide = torch.stack([a, b], 1)
-        idx = wide.clamp(-1, 0x7fffffff).to(torch.int32).contiguous()
+    cams, n_cams, idx = _cameras(cams1, cams2, pairs, K, n1, n2)
     kp = None if keep is None else keep.contiguous().view(torch.uint8)
     f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
     rows = max(cap, 1)                                                # (an address also where cap == 0)
@@ -996,14 +896,12 @@ def relative_pose_tensors(pts, corr_offsets, models, cams1, pairs=None, cams2=No
     cosang = f64(rows) if with_points else None
     cand = f64(K, 4, 12) if with_candidates else None
     cf = torch.empty((K, 4), dtype=torch.int32, device=dev) if with_candidates else None
-    stream = torch.cuda.current_stream(dev)
-    p = lambda t: None if t is None else t.data_ptr()          # noqa: E731
-    rc = _lib.lib().mi_degensac_pose_lists_dev(p(P), p(o), p(kp), p(F), p(cams), n_cams, p(idx), K, cap, cos_min, dev.index or 0,
-                                               C.c_void_p(stream.cuda_stream), p(pose), p(front), p(info), p(X), p(depth), p(cosang), p(cand), p(cf))
+    di, stream, sp = _stream(dev)
+    p = _p
+    rc = _lib.lib().mi_degensac_pose_lists_dev(p(P), p(o), p(kp), p(F), p(cams), n_cams, p(idx), K, cap, cos_min, di, sp, p(pose), p(front), p(info),
+                                               p(X), p(depth), p(cosang), p(cand), p(cf))
     _lib.check_match(rc)
-    for t in (P, o, F, cams, idx, kp):
-        if t is not None:
-            t.record_stream(stream)
+    _keep_alive(stream, P, o, F, cams, idx, kp)
     res = (pose[:, :9].reshape(K, 3, 3), pose[:, 9:], front[:cap].view(torch.bool), info)
     if with_points:
         res += (X[:cap], depth[:cap], cosang[:cap])
@@ -1030,44 +928,28 @@ def refine_pose_tensors(pts, corr_offsets, R, t, cams1, pairs=None, cams2=None, 
     if unknown:
         raise ValueError(f"refine_pose_tensors: unknown keyword {sorted(unknown)[0]!r}")
     opt = [x for x in (pairs, cams2, keep) if x is not None]
+    names = "pts, corr_offsets, R, t, cams1 (and pairs, cams2, keep)"
     ts = [pts, corr_offsets, R, t, cams1] + opt
-    if not all(isinstance(x, torch.Tensor) for x in ts):
-        raise ValueError("pts, corr_offsets, R, t, cams1 (and pairs, cams2, keep) must be torch tensors on a ROCm device")
-    sd = lambda x: None if x is None else (tuple(x.shape), x.dtype)          # noqa: E731
+    _require(names, ts)
     K, cap, n1, n2, mt, ft = matcher.check_refine_args(tuple(pts.shape), pts.dtype, tuple(corr_offsets.shape), corr_offsets.dtype, tuple(R.shape), R.dtype,
-                                                       tuple(t.shape), t.dtype, tuple(cams1.shape), cams1.dtype, sd(pairs), sd(cams2), sd(keep),
+                                                       tuple(t.shape), t.dtype, tuple(cams1.shape), cams1.dtype, _sd(pairs), _sd(cams2), _sd(keep),
                                                        max_trials, ftol)
-    if any(x.device != pts.device for x in ts) or pts.device.type != "cuda":
-        raise ValueError("pts, corr_offsets, R, t, cams1 (and pairs, cams2, keep) must live on the same ROCm device")
+    _require(names, ts, "cuda")
     dev = pts.device
     P = pts.contiguous(); o = corr_offsets.contiguous()
     pose = torch.cat([R.reshape(K, 9), t], 1).contiguous()
-    idx = None
-    if pairs is None:
-        cams = cams1.contiguous()
-        n_cams = 2 * K
-    else:
-        cams = cams1.contiguous() if cams2 is None else torch.cat([cams1, cams2])
-        n_cams = n1 + (n2 or 0)
-        wide = pairs.to(torch.int64)
-        if cams2 is not None:                                         # an image of store 1 must not reach into store 2's rows
-            a = torch.where((wide[:, 0] < 0) | (wide[:, 0] >= n1), -1, wide[:, 0])
-            b = torch.where(wide[:, 1] < 0, -1, wide[:, 1] + n1)
-            wide = torch.stack([a, b], 1)
-        idx = wide.clamp(-1, 0x7fffffff).to(torch.int32).contiguous()
+    cams, n_cams, idx = _cameras(cams1, cams2, pairs, K, n1, n2)
     kp = None if keep is None else keep.contiguous().view(torch.uint8)
     f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
     out = f64(K, 12); cost = f64(K, 2); info = torch.empty((K, 4), dtype=torch.int32, device=dev)
     resid = f64(max(cap, 1)) if with_resid else None                  # (an address also where cap == 0)
     F = f64(K, 9) if with_F else None
-    stream = torch.cuda.current_stream(dev)
-    p = lambda x: None if x is None else x.data_ptr()          # noqa: E731
-    rc = _lib.lib().mi_degensac_pose_refine_lists_dev(p(P), p(o), p(kp), p(pose), p(cams), n_cams, p(idx), K, cap, mt, ft, dev.index or 0,
-                                                      C.c_void_p(stream.cuda_stream), p(out), p(cost), p(info), p(resid), p(F))
+    di, stream, sp = _stream(dev)
+    p = _p
+    rc = _lib.lib().mi_degensac_pose_refine_lists_dev(p(P), p(o), p(kp), p(pose), p(cams), n_cams, p(idx), K, cap, mt, ft, di, sp, p(out), p(cost),
+                                                      p(info), p(resid), p(F))
     _lib.check_match(rc)
-    for x in (P, o, pose, cams, idx, kp):
-        if x is not None:
-            x.record_stream(stream)
+    _keep_alive(stream, P, o, pose, cams, idx, kp)
     res = (out[:, :9].reshape(K, 3, 3), out[:, 9:], cost, info)
     if with_resid:
         res += (resid[:cap],)
@@ -1095,15 +977,13 @@ def triangulate_tracks_tensors(track_offsets, obs, obs_image, kps, cams, R, t, n
     if unknown:
         raise ValueError(f"triangulate_tracks_tensors: unknown keyword {sorted(unknown)[0]!r}")
     ts = [track_offsets, obs, obs_image, kps, cams, R, t] + ([] if n_tracks is None else [n_tracks])
-    if not all(isinstance(x, torch.Tensor) for x in ts):
-        raise ValueError("track_offsets, obs, obs_image, kps, cams, R, t (and n_tracks) must be torch tensors on a ROCm device")
-    sd = lambda x: None if x is None else (tuple(x.shape), x.dtype)          # noqa: E731
+    names = "track_offsets, obs, obs_image, kps, cams, R, t (and n_tracks)"
+    _require(names, ts)
     T, M, rows, n, ang, px, mi, ft = matcher.check_triangulate_args(tuple(track_offsets.shape), track_offsets.dtype, tuple(obs.shape), obs.dtype,
                                                                     tuple(obs_image.shape), obs_image.dtype, tuple(kps.shape), kps.dtype, tuple(cams.shape),
-                                                                    cams.dtype, tuple(R.shape), R.dtype, tuple(t.shape), t.dtype, sd(n_tracks),
+                                                                    cams.dtype, tuple(R.shape), R.dtype, tuple(t.shape), t.dtype, _sd(n_tracks),
                                                                     min_angle_deg, max_reproj_px, max_iters, ftol)
-    if any(x.device != obs.device for x in ts) or obs.device.type != "cuda":
-        raise ValueError("track_offsets, obs, obs_image, kps, cams, R, t (and n_tracks) must live on the same ROCm device")
+    _require(names, ts, "cuda")
     dev = obs.device
     o = track_offsets.contiguous(); ob = obs.contiguous(); oi = obs_image.contiguous(); cm = cams.contiguous()
     xy = kps[:, :2].contiguous()
@@ -1114,14 +994,11 @@ def triangulate_tracks_tensors(track_offsets, obs, obs_image, kps, cams, R, t, n
     err = f64(max(M, 1)) if with_obs else None
     depth = f64(max(M, 1)) if with_obs else None
     ok = torch.empty(max(M, 1), dtype=torch.uint8, device=dev) if with_obs else None
-    stream = torch.cuda.current_stream(dev)
-    p = lambda x: None if x is None or x.numel() == 0 else x.data_ptr()          # noqa: E731
-    rc = _lib.lib().mi_degensac_triangulate_tracks_dev(p(o), p(ob), p(oi), p(n_tracks), p(xy), rows, p(cm), p(poses), n, T, M, ang, px, mi, ft,
-                                                       dev.index or 0, C.c_void_p(stream.cuda_stream), p(X), p(info), p(cost), p(cosang), p(err), p(ok),
-                                                       p(depth))
+    di, stream, sp = _stream(dev)
+    p = lambda x: _p(x, empty_none=True)          # noqa: E731
+    rc = _lib.lib().mi_degensac_triangulate_tracks_dev(p(o), p(ob), p(oi), p(n_tracks), p(xy), rows, p(cm), p(poses), n, T, M, ang, px, mi, ft, di, sp,
+                                                       p(X), p(info), p(cost), p(cosang), p(err), p(ok), p(depth))
     _lib.check_match(rc)
-    for x in (o, ob, oi, n_tracks, xy, cm, poses):
-        if x is not None:
-            x.record_stream(stream)
+    _keep_alive(stream, o, ob, oi, n_tracks, xy, cm, poses)
     res = (X[:T], info[:T], cost[:T], cosang[:T])
     return res + (err[:M], ok[:M].view(torch.bool), depth[:M]) if with_obs else res
