@@ -1192,6 +1192,112 @@ int mi_degensac_triangulate_tracks(const int64_t *track_offsets, const int32_t *
  * the pair pass (-1 for any other value) */
 int mi_degensac_triangulate_tile(int which);
 
+/* ---- refinement of camera poses against triangulated tracks (mi_camera_refine.hip) -----------------------------------------------------
+ * The triangulation takes the poses as exact and gives every track a point; this call is the other block of the reprojection problem:
+ * with the points held fixed, every camera's six degrees of freedom are refined on the reprojection error, in pixels, of its
+ * observations (COLMAP's pose refinement after registration, the motion-only step of a SLAM back end).  Alternated with the
+ * triangulation it is a block-coordinate bundle adjustment on the device with no host read between the steps.  Per image, on the device
+ * and without a host synchronisation: ranges, the number of tracks and the number of observations per image are read from device memory.
+ * Inputs (device arrays on one device): d_track_offsets [T + 1], d_obs [M], d_obs_image [M], d_n_tracks [1] (nullable: all T), d_kps
+ * [rows, 2], d_cams [n_images, 4] and d_poses [n_images, 12] exactly as mi_degensac_triangulate_tracks_dev takes them, and
+ *   d_X [T, 3] float64              the points as that call wrote them; a row with a number that is not finite is simply not used
+ *   d_obs_keep [M] uint8            (nullable: all) the position p is used only where d_obs_keep[p] != 0; the triangulation's d_ok goes in
+ *                                   as it is, and with it every used observation lies in front of its camera at the start
+ *   d_refine [n_images] uint8       (nullable: all) an image with 0 is scored but not moved (status FIXED): this fixes the gauge when a
+ *                                   caller alternates with the triangulation
+ * Every step below is ONE IEEE float64 operation per written operator, no contraction; a sum of three terms is (a + b) + c.  Only + - * /
+ * sqrt, comparisons and |x| occur on the device.
+ * Used observations.  Let nt = min(max(*d_n_tracks, 0), T).  Track k < nt with 0 <= o[k] <= o[k + 1] <= M owns the positions o[k] ..
+ * o[k + 1]; a track with another pair of offsets owns nothing.  The owned position p of track k is USED by image m = d_obs_image[p] when m
+ * lies in [0, n_images), r = d_obs[p] lies in [0, rows), x, y = d_kps[r] are finite, the three numbers of d_X[k] are finite and d_obs_keep
+ * allows p.  Anything else is skipped and never used as an index.  Whether a position is used does not depend on a pose or a camera.
+ * The used observations of an image are ordered by ascending position p: that is the order i = 0, 1, .. of every sum below and of
+ * d_img_obs.  The ranges of two tracks must not overlap.
+ * Statuses of an image, in their order of precedence:
+ *   BAD_CAMERA   fx or fy of d_cams[m] is zero or not finite
+ *   BAD_POSE     one of the twelve numbers of d_poses[m] is not finite
+ *   SHORT        fewer than 3 used observations
+ *   NOT_FINITE   the cost of the start pose is not finite
+ *   BEHIND       a used observation has a Zc that is not > 0 (a NaN included) at the start pose
+ *   FIXED        d_refine[m] == 0: the start pose is scored, both costs are that cost, no trial is made
+ *   CONVERGED, STALLED, MAX_TRIALS   the three ends of a run (below)
+ * With one of the first five the pose is copied through unchanged (its bytes, whatever they are) and no position of d_err is written;
+ * both costs are NaN for the first four, and for BEHIND both are the cost of the start pose (it is finite, or the status would be
+ * NOT_FINITE).  The info row is (used, trials, accepted, status) with the used observations of the image whatever the status, and 0
+ * trials for everything but the three ends of a run.
+ * One pass at a pose (R, t), per used observation with its point X and keypoint x, y:
+ *   P[i] = (R[i][0] X[0] + R[i][1] X[1]) + R[i][2] X[2];  Xc = P[0] + t[0], Yc = P[1] + t[1], Zc = P[2] + t[2]  (the triangulation's Xc, Yc,
+ *   Zc, with the name P for the sum before t is added);  u = Xc / Zc, v = Yc / Zc;  rx = (fx u + cx) - x, ry = (fy v + cy) - y;
+ *   ax = fx / Zc, ex = (fx u) / Zc, ay = fy / Zc, ey = (fy v) / Zc  (all as in the triangulation's pass).
+ *   The update is a rotation on the left and a free translation, R' = C(w) R, t' = t + tau, so that X_cam' = C(w) (R X) + t + tau and at
+ *   w = tau = 0 the derivative of X_cam is -[P]x with respect to w and I with respect to tau.  The Jacobian of (rx, ry) with respect to
+ *   (w[0], w[1], w[2], tau[0], tau[1], tau[2]):
+ *     Jx = (-(ex P[1]),  ax P[2] + ex P[0],  -(ax P[1]),  ax,  0,  -ex)
+ *     Jy = (-(ay P[2] + ey P[1]),  ey P[0],  ay P[0],  0,  ay,  -ey)
+ *   The two zeros are +0.0 and take part like any number.
+ *   The 28 sums of a pass, each term ONE sum of two products, in this order: cost = sum (rx rx + ry ry); g_k = sum (Jx[k] rx + Jy[k] ry)
+ *   for k = 0 .. 5; A_kl = sum (Jx[k] Jx[l] + Jy[k] Jy[l]) for k <= l in the order 00 01 02 03 04 05 11 12 13 14 15 22 23 24 25 33 34 35
+ *   44 45 55.  Each sum: thread tau of the 256 adds the terms of the image's used observations i == tau (mod 256) in ascending i into an
+ *   accumulator that starts as +0.0.  Inside each wave of 64, for m = 32, 16, 8, 4, 2, 1: lane l < m takes v[l] + v[l + m]; lane 0 holds
+ *   the wave's sum w.  The sum is ((w0 + w1) + w2) + w3 over the four waves.  A pass also counts, as an integer, the used observations
+ *   whose Zc is not > 0: `behind`.
+ * The run: lambda = 1e-3; one pass at the start pose gives cost, g, A and behind (cost not finite: NOT_FINITE; else behind > 0: BEHIND;
+ * else d_refine[m] == 0: FIXED); the start cost is kept.  Then up to max_trials trials; before each, if max_trials trials have run the
+ * status is MAX_TRIALS.  One trial is the trial of mi_degensac_pose_refine_lists_dev with 6 in place of 5:
+ *   M[k][k] = A_kk + lambda A_kk, M[k][l] = A_lk for l < k.  Unpivoted Cholesky M = L L^T, for j = 0 .. 5: x = M[j][j], then x = x -
+ *   L[j][k] L[j][k] for k = 0 .. j - 1 in turn; x not > 0 (a NaN included): the trial is REJECTED and has no pass; L[j][j] = sqrt(x); for
+ *   i = j + 1 .. 5: x = M[i][j], x = x - L[i][k] L[j][k] for k = 0 .. j - 1 in turn, L[i][j] = x / L[j][j].
+ *   y: for i = 0 .. 5: x = -g_i, x = x - L[i][k] y[k] for k = 0 .. i - 1 in turn, y[i] = x / L[i][i].
+ *   delta: for i = 5 .. 0: x = y[i], x = x - L[k][i] delta[k] for k = i + 1 .. 5 in turn, delta[i] = x / L[i][i].
+ *   w = delta[0 .. 2], C = C(w) the Cayley rotation written out there (a = 0.5 w, aa = dot(a, a), p = 1 - aa, d = 1 + aa, ..).
+ *   R'[i][j] = (C[i][0] R[0][j] + C[i][1] R[1][j]) + C[i][2] R[2][j];  t'[j] = t[j] + delta[3 + j].
+ *   one pass at (R', t') gives cost', g', A', behind'.  ACCEPTED iff cost' < cost (a NaN is not) and behind' == 0, else REJECTED.
+ *   accepted: the pose and its sums become the current ones; lambda = max(lambda / 10, 1e-12); if (cost - cost') <= ftol cost with the
+ *   cost before the step, the status is CONVERGED.  rejected: lambda = 10 lambda; if lambda > 1e12 the status is STALLED.
+ * max_trials = 0 scores only (MAX_TRIALS, end cost = start cost).
+ * Outputs:
+ *   d_poses_out [n_images, 12]   the final pose; may be d_poses itself (an image reads only its own twelve numbers, before it writes
+ *                                them), must not overlap it otherwise
+ *   d_cost [n_images, 2]         cost in px^2 at the start and at the final pose
+ *   d_info [n_images, 4] int32   used observations, trials run (rejected ones included), trials accepted, status
+ *   d_err [M]                    (nullable) sqrt(rx rx + ry ry) of the used observations of an image with one of the last four statuses
+ *                                at its final pose, from one more pass, at the observation's TRACK-MAJOR position p, next to the
+ *                                triangulation's d_err; every other position keeps NaN
+ *   d_img_offsets [n_images + 1] int64, d_img_obs [M] int32   (each nullable) the image-major table the call builds: image m owns
+ *                                d_img_obs[io[m] .. io[m + 1]], the positions p of its used observations in ascending order;
+ *                                io[n_images] is the number of used observations, and every element of d_img_obs behind it is -1
+ * Kernels: a fill and `mark` (the sort key of every position: its image when it is used, else n_images; and the track that owns it),
+ * a stable rocprim::radix_sort_pairs of (key, position) over the key bits, `bounds` (io[m] = the lower bound of m in the sorted keys) and
+ * `refine`: one workgroup of 256 threads per image, images by a grid stride over at most mi_degensac_camera_refine_tile(1) workgroups.
+ * No atomics, no workgroup waits for another, a fixed order of every sum: the same bits on every call.  Asynchronous on `stream`; the
+ * temporaries (20 bytes per position and rocprim's) are taken and returned stream-ordered.
+ * Refused with MI_DEGENSAC_EINVAL and a message in mi_degensac_match_last_error(), before a device is looked for and in this order:
+ * n_tracks_max < 0 or > 0x3fffffff; n_obs_max < 0 or > 0x3fffffff; rows < 0 or > 0x7fffffff; n_images < 0; max_trials outside 0 .. 100;
+ * an ftol that is NaN or < 0; NULL d_track_offsets; for n_obs_max > 0 NULL d_obs or d_obs_image; for rows > 0 NULL d_kps; for
+ * n_tracks_max > 0 NULL d_X; for n_images > 0 NULL d_cams or d_poses, then NULL d_poses_out, d_cost or d_info.  n_tracks_max == 0,
+ * n_obs_max == 0 and n_images == 0 succeed: without observations every image is SHORT (or has a bad camera or pose); without images the
+ * fills of d_err (NaN), d_img_offsets (one 0) and d_img_obs (-1) are all that is written, and with n_obs_max == 0 as well nothing is
+ * written and no device is looked for. */
+enum { MI_DEGENSAC_CAMREF_CONVERGED = 0, MI_DEGENSAC_CAMREF_STALLED = 1, MI_DEGENSAC_CAMREF_MAX_TRIALS = 2, MI_DEGENSAC_CAMREF_FIXED = 3,
+       MI_DEGENSAC_CAMREF_BEHIND = 4, MI_DEGENSAC_CAMREF_NOT_FINITE = 5, MI_DEGENSAC_CAMREF_SHORT = 6, MI_DEGENSAC_CAMREF_BAD_POSE = 7,
+       MI_DEGENSAC_CAMREF_BAD_CAMERA = 8 };
+int mi_degensac_camera_refine_tracks_dev(const int64_t *d_track_offsets, const int32_t *d_obs, const int32_t *d_obs_image,
+                                         const int64_t *d_n_tracks /*nullable*/, const double *d_kps, int64_t rows, const double *d_cams,
+                                         const double *d_poses, int n_images, const double *d_X, const uint8_t *d_obs_keep /*nullable*/,
+                                         const uint8_t *d_refine /*nullable*/, int64_t n_tracks_max, int64_t n_obs_max, int max_trials,
+                                         double ftol, int device, void *stream, double *d_poses_out, double *d_cost, int32_t *d_info,
+                                         double *d_err /*nullable*/, int64_t *d_img_offsets /*nullable*/, int32_t *d_img_obs /*nullable*/);
+/* the same on host pointers (blocking): the inputs go to the device once, every output that is asked for comes back whole; n_tracks is
+ * passed by value, < 0 = all n_tracks_max */
+int mi_degensac_camera_refine_tracks(const int64_t *track_offsets, const int32_t *obs, const int32_t *obs_image, int64_t n_tracks,
+                                     const double *kps, int64_t rows, const double *cams, const double *poses, int n_images, const double *X,
+                                     const uint8_t *obs_keep /*nullable*/, const uint8_t *refine /*nullable*/, int64_t n_tracks_max,
+                                     int64_t n_obs_max, int max_trials, double ftol, int device, double *poses_out, double *cost,
+                                     int32_t *info, double *err /*nullable*/, int64_t *img_offsets /*nullable*/, int32_t *img_obs /*nullable*/);
+/* the tile constants: which = 0 observations per workgroup and step of a row pass, 1 the cap on the grid of `refine`, 2 lanes per track
+ * of `mark` (-1 for any other value) */
+int mi_degensac_camera_refine_tile(int which);
+
 /* ---- unit-level device entry points (parity tests of the kernels' building blocks) ------------ */
 /* score n_models fundamental (kind 0: Sampson, 1: symmetric epipolar) or homography (kind 10..14:
  * H Sampson, symm_sq_max, symm_max, symm_sq_sum, symm_sum) models against all n points: I (<= th)

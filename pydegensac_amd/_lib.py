@@ -56,6 +56,12 @@ REFINE_CONVERGED, REFINE_STALLED, REFINE_MAX_TRIALS, REFINE_SHORT, REFINE_NOT_FI
 # of its info rows (MI_DEGENSAC_TRI_*)
 TRI_GRID, TRI_CHUNK = 1024, 64
 TRI_OK, TRI_NARROW, TRI_DEGENERATE, TRI_SHORT, TRI_TRUNCATED = range(5)
+# the refinement of camera poses against tracks (csrc/mi_camera_refine.hip CR_STEP / CR_GRID / CR_G, mi_degensac_camera_refine_tile):
+# observations per workgroup and step of a row pass, the cap on the grid, lanes per track of the mark kernel; the status column of its info
+# rows (MI_DEGENSAC_CAMREF_*)
+CAMREF_STEP, CAMREF_GRID, CAMREF_GROUP = 512, 256, 16
+(CAMREF_CONVERGED, CAMREF_STALLED, CAMREF_MAX_TRIALS, CAMREF_FIXED, CAMREF_BEHIND, CAMREF_NOT_FINITE, CAMREF_SHORT, CAMREF_BAD_POSE,
+ CAMREF_BAD_CAMERA) = range(9)
 
 
 class Params(C.Structure):
@@ -386,6 +392,17 @@ def lib():
             l.mi_degensac_triangulate_tracks.argtypes = [vp, vp, vp, C.c_int64] + tail + [vp] * 7
             l.mi_degensac_triangulate_tile.restype = C.c_int
             l.mi_degensac_triangulate_tile.argtypes = [C.c_int]
+        if hasattr(l, "mi_degensac_camera_refine_tracks_dev"):            # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            # track_offsets, obs, obs_image, n_tracks, kps, rows, cams, poses, n_images, X, obs_keep, refine, T, M, max_trials, ftol,
+            # device[, stream] | poses_out, cost, info, err, img_offsets, img_obs
+            vp = C.c_void_p
+            tail = [vp, C.c_int64, vp, vp, C.c_int, vp, vp, vp, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_int]
+            l.mi_degensac_camera_refine_tracks_dev.restype = C.c_int
+            l.mi_degensac_camera_refine_tracks_dev.argtypes = [vp, vp, vp, vp] + tail + [vp] + [vp] * 6
+            l.mi_degensac_camera_refine_tracks.restype = C.c_int
+            l.mi_degensac_camera_refine_tracks.argtypes = [vp, vp, vp, C.c_int64] + tail + [vp] * 6
+            l.mi_degensac_camera_refine_tile.restype = C.c_int
+            l.mi_degensac_camera_refine_tile.argtypes = [C.c_int]
         l.mi_degensac_kpts_to_xyA.restype = C.c_int
         l.mi_degensac_kpts_to_xyA.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, dp]
         l.mi_degensac_kpts_to_xyA_dev.restype = C.c_int

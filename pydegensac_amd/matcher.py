@@ -1324,6 +1324,65 @@ def triangulate_tracks(track_offsets, obs, obs_image, kps, cams, R, t, n_tracks=
     return res + (err, ok.astype(bool), depth) if with_obs else res
 
 
+def check_camera_refine_args(off_shape, off_dtype, obs_shape, obs_dtype, img_shape, img_dtype, kps_shape, kps_dtype, cams_shape, cams_dtype, R_shape,
+                             R_dtype, t_shape, t_dtype, X_shape, X_dtype, n_tracks=None, obs_keep=None, refine=None, max_trials=20, ftol=1e-12):
+    """The argument checks of refine_cameras / refine_cameras_tensors on shapes and dtype names (numpy or torch): the tables, kps, cams, R,
+    t and n_tracks as check_triangulate_args, which is called for them; X float64 [T, 3]; obs_keep None or (shape, dtype) = uint8 / bool
+    [M]; refine None or (shape, dtype) = uint8 / bool [n_images]; max_trials an integer in 0 .. 100, ftol a number >= 0.  Returns (T, M,
+    rows, n_images, max_trials, ftol); raises ValueError."""
+    T, M, rows, n = check_triangulate_args(off_shape, off_dtype, obs_shape, obs_dtype, img_shape, img_dtype, kps_shape, kps_dtype, cams_shape, cams_dtype,
+                                           R_shape, R_dtype, t_shape, t_dtype, n_tracks)[:4]
+    if tuple(X_shape) != (T, 3) or _dtype_name(X_dtype) != "float64":
+        raise ValueError("X should be float64 [T, 3], one point per track as the triangulation returns it")
+    if obs_keep is not None and (tuple(obs_keep[0]) != (M,) or _dtype_name(obs_keep[1]) not in ("uint8", "bool")):
+        raise ValueError("obs_keep should be uint8 or bool [M], one flag per element of obs")
+    if refine is not None and (tuple(refine[0]) != (n,) or _dtype_name(refine[1]) not in ("uint8", "bool")):
+        raise ValueError("refine should be uint8 or bool [n_images], one flag per row of cams")
+    return T, M, rows, n, _integer(max_trials, "max_trials should be an integer in 0 .. 100", 0, 100), _number(ftol, "ftol should be a number >= 0", 0.0)
+
+
+def refine_cameras(track_offsets, obs, obs_image, kps, cams, R, t, X, n_tracks=None, obs_keep=None, refine=None, max_trials=20, ftol=1e-12,
+                   with_err=False, with_table=False, device=0, **unknown):
+    """Refine camera poses against triangulated tracks (include/mi_degensac.h mi_degensac_camera_refine_tracks, blocking, numpy): with
+    the points X [T, 3] of triangulate_tracks held fixed, per image a Levenberg-Marquardt run over the six degrees of freedom of its
+    world-to-camera pose (R' = C(w) R, t' = t + tau) on the reprojection error, in pixels, of its used observations.  Tables, kps, cams,
+    R, t and n_tracks as triangulate_tracks takes them.  An observation is used when its indices are in range, its keypoint and its
+    track's point are finite and obs_keep [M] (None: all; triangulate_tracks' `ok` as it is) allows it.  refine [n_images] (None: all):
+    an image with 0 is scored but not moved.  At most max_trials trial steps per image; an accepted step that lowers the cost by no more
+    than ftol times the cost ends the run; a step that puts an observation behind the camera is rejected.
+    Returns (R [n_images, 3, 3], t [n_images, 3], cost [n_images, 2] = (start, end), info [n_images, 4] int32 = (observations used,
+    trials, trials accepted, _lib.CAMREF_* status)[, err [M]: the reprojection error in px of the used observations at the final pose, at
+    their positions in obs, NaN elsewhere][, img_offsets [n_images + 1] int64, img_obs [M] int32: the positions into obs of every image's
+    used observations, ascending inside an image, -1 behind the last])."""
+    if unknown:
+        raise ValueError(f"refine_cameras: unknown keyword {sorted(unknown)[0]!r}")
+    o = np.ascontiguousarray(np.asarray(track_offsets)); ob = np.ascontiguousarray(np.asarray(obs)); oi = np.ascontiguousarray(np.asarray(obs_image))
+    kp = np.asarray(kps); cm = np.asarray(cams); Rm = np.asarray(R); tv = np.asarray(t); Xm = np.asarray(X)
+    ok = None if obs_keep is None else np.asarray(obs_keep)
+    rf = None if refine is None else np.asarray(refine)
+    if n_tracks is not None:
+        _integer(n_tracks, "n_tracks should be an integer (or None = all T)")
+    T, M, rows, n, mt, ft = check_camera_refine_args(o.shape, o.dtype, ob.shape, ob.dtype, oi.shape, oi.dtype, kp.shape, kp.dtype, cm.shape, cm.dtype,
+                                                     Rm.shape, Rm.dtype, tv.shape, tv.dtype, Xm.shape, Xm.dtype, None, _sd(ok), _sd(rf), max_trials, ftol)
+    xy = np.ascontiguousarray(kp[:, :2]); cm = np.ascontiguousarray(cm); Xm = np.ascontiguousarray(Xm)
+    poses = np.ascontiguousarray(np.concatenate([Rm.reshape(n, 9), tv], 1))
+    ok = None if ok is None else np.ascontiguousarray(ok).view(np.uint8)
+    rf = None if rf is None else np.ascontiguousarray(rf).view(np.uint8)
+    out = np.zeros((n, 12)); cost = np.full((n, 2), np.nan); info = np.zeros((n, 4), np.int32)
+    err = np.full(M, np.nan) if with_err else None
+    io = np.zeros(n + 1, np.int64) if with_table else None
+    iobs = np.full(M, -1, np.int32) if with_table else None
+    vp = lambda x: _lib.vptr(x, empty_none=True)          # noqa: E731
+    rc = _lib.lib().mi_degensac_camera_refine_tracks(vp(o), vp(ob), vp(oi), -1 if n_tracks is None else max(int(n_tracks), 0), vp(xy), rows, vp(cm),
+                                                     vp(poses), n, vp(Xm), vp(ok), vp(rf), T, M, mt, ft, int(device), vp(out), vp(cost), vp(info), vp(err),
+                                                     vp(io), vp(iobs))
+    _lib.check_match(rc)
+    res = (out[:, :9].reshape(n, 3, 3), out[:, 9:], cost, info)
+    if with_err:
+        res += (err,)
+    return res + (io, iobs) if with_table else res
+
+
 def pose_config(info, min_front_ratio=0.5, min_wide_ratio=0.0):
     """What the info rows [K, 5] of relative_pose / relative_pose_tensors (numpy, or a tensor, which is copied to the host) say about a
     pair that two_view_config put into class 2, "planar or panoramic": int8 [K] with 2 = panoramic (wide <= min_wide_ratio * front,

@@ -1002,3 +1002,55 @@ def triangulate_tracks_tensors(track_offsets, obs, obs_image, kps, cams, R, t, n
     _keep_alive(stream, o, ob, oi, n_tracks, xy, cm, poses)
     res = (X[:T], info[:T], cost[:T], cosang[:T])
     return res + (err[:M], ok[:M].view(torch.bool), depth[:M]) if with_obs else res
+
+
+def refine_cameras_tensors(track_offsets, obs, obs_image, kps, cams, R, t, X, n_tracks=None, obs_keep=None, refine=None, max_trials=20, ftol=1e-12,
+                           with_err=False, with_table=False, **unknown):
+    """Refine camera poses against triangulated tracks, on the device and without a host synchronisation (include/mi_degensac.h
+    mi_degensac_camera_refine_tracks_dev): the other block of the reprojection problem after triangulate_tracks_tensors.  The tables,
+    kps, cams, R, t and n_tracks go in exactly as that call takes them and X [T, 3] float64 as it returned it (NaN rows are simply not
+    used); obs_keep [M] uint8 / bool (None: all) takes its `ok` as it is, and with it every used observation lies in front of its camera
+    at the start; refine [n_images] uint8 / bool (None: all): an image with 0 is scored but not moved, which fixes the gauge when the two
+    calls alternate.  Per image a Levenberg-Marquardt run over the six degrees of freedom of its pose (R' = C(w) R, t' = t + tau) on the
+    reprojection error in pixels with the points held fixed: at most max_trials trial steps, an accepted step that lowers the cost by no
+    more than ftol times the cost ends the run, a step that puts an observation behind the camera is rejected.  The call regroups the
+    track-major tables by image itself (a stable sort on the device), so nothing is read back.
+    Returns (R [n_images, 3, 3], t [n_images, 3], cost [n_images, 2] = (start, end), info [n_images, 4] int32 = (observations used,
+    trials, trials accepted, _lib.CAMREF_* status)[, err [M]: the reprojection error in px of the used observations at the final pose, at
+    their positions in obs, next to the triangulation's err, NaN elsewhere][, img_offsets [n_images + 1] int64, img_obs [M] int32: the
+    positions into obs of every image's used observations, ascending inside an image, -1 behind the last]) on the device, asynchronous
+    on the current stream.  An image without a usable start (CAMREF_BAD_CAMERA, BAD_POSE, SHORT, NOT_FINITE, BEHIND) keeps its pose."""
+    import torch
+    from . import matcher
+    if unknown:
+        raise ValueError(f"refine_cameras_tensors: unknown keyword {sorted(unknown)[0]!r}")
+    ts = [track_offsets, obs, obs_image, kps, cams, R, t, X] + [x for x in (n_tracks, obs_keep, refine) if x is not None]
+    names = "track_offsets, obs, obs_image, kps, cams, R, t, X (and n_tracks, obs_keep, refine)"
+    _require(names, ts)
+    T, M, rows, n, mt, ft = matcher.check_camera_refine_args(tuple(track_offsets.shape), track_offsets.dtype, tuple(obs.shape), obs.dtype,
+                                                             tuple(obs_image.shape), obs_image.dtype, tuple(kps.shape), kps.dtype, tuple(cams.shape),
+                                                             cams.dtype, tuple(R.shape), R.dtype, tuple(t.shape), t.dtype, tuple(X.shape), X.dtype,
+                                                             _sd(n_tracks), _sd(obs_keep), _sd(refine), max_trials, ftol)
+    _require(names, ts, "cuda")
+    dev = obs.device
+    o = track_offsets.contiguous(); ob = obs.contiguous(); oi = obs_image.contiguous(); cm = cams.contiguous(); Xc = X.contiguous()
+    xy = kps[:, :2].contiguous()
+    poses = torch.cat([R.reshape(n, 9), t], 1).contiguous()
+    ok = None if obs_keep is None else obs_keep.contiguous().view(torch.uint8)
+    rf = None if refine is None else refine.contiguous().view(torch.uint8)
+    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
+    out = f64(max(n, 1), 12); cost = f64(max(n, 1), 2)                # (an address also where n_images == 0)
+    info = torch.empty((max(n, 1), 4), dtype=torch.int32, device=dev)
+    err = f64(max(M, 1)) if with_err else None
+    io = torch.zeros(n + 1, dtype=torch.int64, device=dev) if with_table else None          # (n_images == 0 and M == 0 write nothing)
+    iobs = torch.empty(max(M, 1), dtype=torch.int32, device=dev) if with_table else None
+    di, stream, sp = _stream(dev)
+    p = lambda x: _p(x, empty_none=True)          # noqa: E731
+    rc = _lib.lib().mi_degensac_camera_refine_tracks_dev(p(o), p(ob), p(oi), p(n_tracks), p(xy), rows, p(cm), p(poses), n, p(Xc), p(ok), p(rf), T, M, mt,
+                                                         ft, di, sp, p(out), p(cost), p(info), p(err), p(io), p(iobs))
+    _lib.check_match(rc)
+    _keep_alive(stream, o, ob, oi, n_tracks, xy, cm, poses, Xc, ok, rf)
+    res = (out[:n, :9].reshape(n, 3, 3), out[:n, 9:], cost[:n], info[:n])
+    if with_err:
+        res += (err[:M],)
+    return res + (io, iobs[:M]) if with_table else res
