@@ -1298,6 +1298,91 @@ int mi_degensac_camera_refine_tracks(const int64_t *track_offsets, const int32_t
  * of `mark` (-1 for any other value) */
 int mi_degensac_camera_refine_tile(int which);
 
+/* ---- rotation averaging: global camera rotations from pairwise poses (mi_rotavg.hip) -----------------------------------------------------
+ * The pose calls end with one (R, t) per PAIR, the track calls start from one world-to-camera pose per IMAGE.  This call is the first step
+ * between them, the one global structure-from-motion front ends run first: from the two-view graph one rotation per image, and per pair
+ * the cosine of the angle by which its relative rotation disagrees with them (the usual filter for pairs whose pose is wrong).  Camera
+ * positions (translation averaging) are not part of it.  On the device and without a host synchronisation: the host never learns how
+ * many sweeps were needed.
+ * Inputs (device arrays on one device):
+ *   d_pairs [K, 2] int32, d_R_rel [K, 9] float64   edge e joins the images i = pairs[e][0] and j = pairs[e][1] of ONE store of n_images
+ *                                   images, X_j = R_rel[e] X_i: the pair list and the R of mi_degensac_pose_lists_dev /
+ *                                   mi_degensac_pose_refine_lists_dev (the first nine numbers of their pose rows, so d_R_rel is read with
+ *                                   a row length of 9: pass a compact copy)
+ *   d_weight [K] float64            (nullable: 1) e.g. the wide rows of the pose call's info
+ *   d_edge_keep [K] uint8           (nullable: all)
+ *   d_R0 [n_images, 9], d_known [n_images] uint8   (both or neither) the cameras with d_known != 0 start SET with the nine numbers of
+ *                                   d_R0 (their bytes, whatever they are) and are never moved.  With neither, camera `root` starts set
+ *                                   with the identity and is never moved.  Such a camera is called KNOWN below.
+ * Every step below is ONE IEEE float64 operation per written operator, no contraction; a sum of three terms is (a + b) + c.  Only + - * /
+ * and comparisons occur on the device.
+ * Used edges.  Edge e is USED when d_edge_keep[e] != 0, i and j lie in [0, n_images), i != j, d_weight[e] > 0 and finite, and
+ * |s - 3| <= 1e-6 for s = the sum of r r over the nine numbers of R_rel[e] in their order (the zeros of a failed pose entry, a NaN and an
+ * infinity fail it).  Anything else is unused and never used as an index.  Repeats and both orientations of a pair are separate edges.
+ * Half-edges.  Edge e has the half-edges h = 2 e (camera i, other end j) and h = 2 e + 1 (camera j, other end i).  The half-edges of the
+ * used edges are grouped by camera, ascending in h inside a camera: position 0, 1, .. deg - 1 of the camera.
+ * State.  Per camera `set` (with the sweep in which it was set), a matrix R, `step` and `opposed`, in two buffers.  At the start a known
+ * camera is set in sweep 0 with its matrix, every other camera is not set and has zeros; step is NaN and opposed 0 for all.  Sweep s =
+ * 1, 2, .. reads the state sweep s - 1 left and nothing else (Jacobi: the result cannot depend on scheduling).  Per camera c:
+ *   known: copied.
+ *   The prediction of c over the half-edge h of edge e with other end o:  P = R_rel[e] R_o for h odd (c is the second image), P =
+ *   R_rel[e]^T R_o for h even.  Every 3 x 3 product here is P[i][j] = (A[i][0] B[0][j] + A[i][1] B[1][j]) + A[i][2] B[2][j].
+ *   not set: among its half-edges whose other end is set, the one with the largest weight, ties to the lowest position; R_c = its
+ *     prediction, c is set in sweep s (a max-weight breadth-first start, one level per sweep).  Without one the camera is copied.
+ *   set and not known: per half-edge whose other end is set, Q = P R_c^T (Q[i][j] = (P[i][0] R_c[j][0] + P[i][1] R_c[j][1]) + P[i][2]
+ *     R_c[j][2]), q = 1 + ((Q[0][0] + Q[1][1]) + Q[2][2]).  If q > 2^-10 does not hold (a NaN included) the half-edge is OPPOSED: it is
+ *     counted and adds nothing.  Else w = ((Q[2][1] - Q[1][2]) / q, (Q[0][2] - Q[2][0]) / q, (Q[1][0] - Q[0][1]) / q): the vector a with
+ *     Q = Ca(a) for the rational Cayley map Ca(a) = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a), |a| = tan(angle / 2).  (The C(w) of
+ *     the two refinements is Ca(0.5 w).)  m = (w0 w0 + w1 w1) + w2 w2.  f = weight, or with a robust_deg f = weight (g g) for g = s2 /
+ *     (s2 + m), s2 = sigma sigma, sigma = tan(robust_deg pi / 360) computed once on the host.  The sums S = sum f and W_k = sum (f w_k):
+ *     lane l of G = mi_degensac_rotation_average_tile(0) adds the terms of the positions l, l + G, .. in ascending order into an
+ *     accumulator that starts as +0.0; then for m = G / 2, .., 2, 1 every lane takes v[l] + v[l xor m].  If S > 0: u_k = W_k / S, step_c =
+ *     (u0 u0 + u1 u1) + u2 u2, a_k = damping u_k, b_k = a_k + a_k, aa = (a0 a0 + a1 a1) + a2 a2, p = 1 - aa, d = 1 + aa,
+ *       C = ((p + b0 a0) / d, (b0 a1 - b2) / d, (b0 a2 + b1) / d;  (b1 a0 + b2) / d, (p + b1 a1) / d, (b1 a2 - b0) / d;
+ *            (b2 a0 - b1) / d, (b2 a1 + b0) / d, (p + b2 a2) / d),   R_c <- C R_c.
+ *     Otherwise R_c and step_c are copied.  opposed_c = the count of this sweep (0 for a camera that is known, not set, or set in s).
+ *   damping = 0.5 is the lazy Jacobi step: it cannot oscillate on a bipartite graph, which the full step can.
+ * Convergence.  Sweep s CHANGED something when it set a camera or gave some step_c > tol tol.  changed[0] = 1.  A sweep that finds
+ * changed[s - 1] == 0 does nothing, and so does every later one; the outputs are the state after the last sweep that did something:
+ * the first one that changed nothing, or sweep `sweeps`.  All `sweeps` launches are queued.
+ * Outputs:
+ *   d_R [n_images, 9]            the world-to-camera rotation; zeros for a camera that was never set
+ *   d_info [n_images, 4] int32   (half-edges of used edges, the sweep in which the camera was set: 0 known, -1 never, opposed half-edges
+ *                                in the last sweep that ran, status).  KNOWN; OK = set by the call; UNREACHED = has half-edges but
+ *                                was not set; ISOLATED = not known and no half-edge
+ *   d_step [n_images]            the last step_c the camera was given, NaN where none was
+ *   d_summary [4] int64          (sweeps that changed something, cameras set, edges used, global status).  NO_ROOT = no known camera;
+ *                                else CONVERGED = a sweep changed nothing; else MAX_SWEEPS (sweeps == 0 included)
+ *   d_edge_cos [K]               (nullable) for a used edge whose two ends are set c = ((d0 + d1) + d2 - 1) / 2 with T = R_rel[e] R_i and
+ *                                d_k = (T[k][0] R_j[k][0] + T[k][1] R_j[k][1]) + T[k][2] R_j[k][2]: the cosine of the angle between
+ *                                R_rel and R_j R_i^T.  NaN elsewhere
+ * Kernels: `mark` (the key of every half-edge: its camera, or n_images for an unused edge), a stable rocprim::radix_sort_pairs of (key,
+ * half-edge) over the key bits, `init` (off[c] = the lower bound of c in the sorted keys, and the start state), one `sweep` launch per
+ * sweep (G lanes per camera, 256 / G cameras per workgroup, further cameras by a grid stride over at most
+ * mi_degensac_rotation_average_tile(1) workgroups, no barrier; the only atomic is the integer OR into changed[s]) and `finish` (an
+ * integer add for the cameras set).  The same bits on every call.  Asynchronous on `stream`; the temporaries (16 bytes per
+ * half-edge, 180 per camera, 4 per sweep and rocprim's) are taken and returned stream-ordered.
+ * Refused with MI_DEGENSAC_EINVAL and a message in mi_degensac_match_last_error(), before a device is looked for and in this order:
+ * n_images outside 1 .. 2^24; n_pairs < 0 or > 0x3fffffff; sweeps outside 0 .. 4096; a damping outside (0, 1]; a robust_deg that is
+ * neither 0 (= no robust factor) nor in (0, 180); a tol that is NaN or < 0; root outside [0, n_images) (also when d_known is given);
+ * for n_pairs > 0 NULL d_pairs or d_R_rel; exactly one of d_R0 and d_known; NULL d_R, d_info, d_step or d_summary.  n_pairs == 0
+ * succeeds: every camera is KNOWN or ISOLATED. */
+enum { MI_DEGENSAC_ROTAVG_KNOWN = 0, MI_DEGENSAC_ROTAVG_OK = 1, MI_DEGENSAC_ROTAVG_UNREACHED = 2, MI_DEGENSAC_ROTAVG_ISOLATED = 3 };
+enum { MI_DEGENSAC_ROTAVG_CONVERGED = 0, MI_DEGENSAC_ROTAVG_MAX_SWEEPS = 1, MI_DEGENSAC_ROTAVG_NO_ROOT = 2 };
+int mi_degensac_rotation_average_dev(const int32_t *d_pairs, const double *d_R_rel, const double *d_weight /*nullable*/,
+                                     const uint8_t *d_edge_keep /*nullable*/, int64_t n_pairs, int n_images, const double *d_R0 /*nullable*/,
+                                     const uint8_t *d_known /*nullable*/, int root, int sweeps, double damping, double robust_deg, double tol,
+                                     int device, void *stream, double *d_R, int32_t *d_info, double *d_step, int64_t *d_summary,
+                                     double *d_edge_cos /*nullable*/);
+/* the same on host pointers (blocking): the inputs go to the device once, every output that is asked for comes back whole */
+int mi_degensac_rotation_average(const int32_t *pairs, const double *R_rel, const double *weight /*nullable*/,
+                                 const uint8_t *edge_keep /*nullable*/, int64_t n_pairs, int n_images, const double *R0 /*nullable*/,
+                                 const uint8_t *known /*nullable*/, int root, int sweeps, double damping, double robust_deg, double tol, int device,
+                                 double *R, int32_t *info, double *step, int64_t *summary, double *edge_cos /*nullable*/);
+/* the tile constants: which = 0 G = lanes per camera, 1 the cap on the grid of a sweep, 2 cameras (groups) per workgroup (-1 for any
+ * other value) */
+int mi_degensac_rotation_average_tile(int which);
+
 /* ---- unit-level device entry points (parity tests of the kernels' building blocks) ------------ */
 /* score n_models fundamental (kind 0: Sampson, 1: symmetric epipolar) or homography (kind 10..14:
  * H Sampson, symm_sq_max, symm_max, symm_sq_sum, symm_sum) models against all n points: I (<= th)

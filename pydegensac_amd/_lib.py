@@ -62,6 +62,12 @@ TRI_OK, TRI_NARROW, TRI_DEGENERATE, TRI_SHORT, TRI_TRUNCATED = range(5)
 CAMREF_STEP, CAMREF_GRID, CAMREF_GROUP = 512, 256, 16
 (CAMREF_CONVERGED, CAMREF_STALLED, CAMREF_MAX_TRIALS, CAMREF_FIXED, CAMREF_BEHIND, CAMREF_NOT_FINITE, CAMREF_SHORT, CAMREF_BAD_POSE,
  CAMREF_BAD_CAMERA) = range(9)
+# rotation averaging (csrc/mi_rotavg.hip RA_GRID / RA_CPW, mi_degensac_rotation_average_tile): the cap on the grid of a sweep, cameras per
+# workgroup; the lanes per camera are a build constant (RA_G) that rotavg_group() reads from the loaded library; the status column of its
+# info rows and the global status of its summary (MI_DEGENSAC_ROTAVG_*)
+ROTAVG_GRID, ROTAVG_CAMERAS = 1024, 16
+ROTAVG_KNOWN, ROTAVG_OK, ROTAVG_UNREACHED, ROTAVG_ISOLATED = range(4)
+ROTAVG_CONVERGED, ROTAVG_MAX_SWEEPS, ROTAVG_NO_ROOT = range(3)
 
 
 class Params(C.Structure):
@@ -403,6 +409,17 @@ def lib():
             l.mi_degensac_camera_refine_tracks.argtypes = [vp, vp, vp, C.c_int64] + tail + [vp] * 6
             l.mi_degensac_camera_refine_tile.restype = C.c_int
             l.mi_degensac_camera_refine_tile.argtypes = [C.c_int]
+        if hasattr(l, "mi_degensac_rotation_average_dev"):                # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            # pairs, R_rel, weight, edge_keep, K, n_images, R0, known, root, sweeps, damping, robust_deg, tol, device[, stream] | R, info, step,
+            # summary, edge_cos
+            vp = C.c_void_p
+            head = [vp, vp, vp, vp, C.c_int64, C.c_int, vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int]
+            l.mi_degensac_rotation_average_dev.restype = C.c_int
+            l.mi_degensac_rotation_average_dev.argtypes = head + [vp] + [vp] * 5
+            l.mi_degensac_rotation_average.restype = C.c_int
+            l.mi_degensac_rotation_average.argtypes = head + [vp] * 5
+            l.mi_degensac_rotation_average_tile.restype = C.c_int
+            l.mi_degensac_rotation_average_tile.argtypes = [C.c_int]
         l.mi_degensac_kpts_to_xyA.restype = C.c_int
         l.mi_degensac_kpts_to_xyA.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, dp]
         l.mi_degensac_kpts_to_xyA_dev.restype = C.c_int
@@ -432,6 +449,12 @@ def lib():
 def tri_group():
     """lanes per track of the loaded library's triangulation kernel (mi_degensac_triangulate_tile(0)): the order of its sums depends on it"""
     return int(lib().mi_degensac_triangulate_tile(0))
+
+
+def rotavg_group():
+    """lanes per camera of the loaded library's rotation-averaging sweep (mi_degensac_rotation_average_tile(0)): the order of its sums
+    depends on it"""
+    return int(lib().mi_degensac_rotation_average_tile(0))
 
 
 def check(rc, last_error="mi_degensac_last_error", value_error=True):

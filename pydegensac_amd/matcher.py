@@ -1383,6 +1383,85 @@ def refine_cameras(track_offsets, obs, obs_image, kps, cams, R, t, X, n_tracks=N
     return res + (io, iobs) if with_table else res
 
 
+def check_rotavg_args(pairs_shape, pairs_dtype, R_shape, R_dtype, n_images, weight=None, edge_keep=None, R0=None, known=None, root=0, sweeps=200,
+                      damping=0.5, robust_deg=5.0, tol=1e-9):
+    """The argument checks of average_rotations / average_rotations_tensors on shapes and dtype names (numpy or torch): pairs int32 or
+    int64 [K, 2] over ONE store of n_images images, R_rel float64 [K, 3, 3]; weight None or (shape, dtype) = float64 [K]; edge_keep None
+    or uint8 / bool [K]; R0 float64 [n_images, 3, 3] and known uint8 / bool [n_images], both or neither; n_images an integer in 1 ..
+    2^24, root in 0 .. n_images - 1, sweeps in 0 .. 4096, damping a number in (0, 1], robust_deg None or a number in (0, 180), tol a
+    number >= 0.  Returns (K, n_images, root, sweeps, damping, robust_deg as the library takes it (0 = none), tol); raises ValueError."""
+    n = _integer(n_images, "n_images should be an integer in 1 .. 2^24", 1, 1 << 24)
+    if len(pairs_shape) != 2 or pairs_shape[1] != 2 or _dtype_name(pairs_dtype) not in ("int32", "int64") or pairs_shape[0] > 0x3fffffff:
+        raise ValueError("pairs should be int32 or int64 [K, 2]: both columns are images of one store (a two-store list has no global frame)")
+    K = int(pairs_shape[0])
+    if tuple(R_shape) != (K, 3, 3) or _dtype_name(R_dtype) != "float64":
+        raise ValueError("R_rel should be float64 [K, 3, 3], X_j = R_rel X_i per row of pairs, as the pose calls return R")
+    if weight is not None and (tuple(weight[0]) != (K,) or _dtype_name(weight[1]) != "float64"):
+        raise ValueError("weight should be float64 [K], one per row of pairs")
+    if edge_keep is not None and (tuple(edge_keep[0]) != (K,) or _dtype_name(edge_keep[1]) not in ("uint8", "bool")):
+        raise ValueError("edge_keep should be uint8 or bool [K], one flag per row of pairs")
+    if (R0 is None) != (known is None):
+        raise ValueError("R0 and known go together: both or neither")
+    if R0 is not None and (tuple(R0[0]) != (n, 3, 3) or _dtype_name(R0[1]) != "float64"):
+        raise ValueError("R0 should be float64 [n_images, 3, 3]")
+    if known is not None and (tuple(known[0]) != (n,) or _dtype_name(known[1]) not in ("uint8", "bool")):
+        raise ValueError("known should be uint8 or bool [n_images]")
+    rt = _integer(root, "root should be an integer in 0 .. n_images - 1", 0, n - 1)
+    sw = _integer(sweeps, "sweeps should be an integer in 0 .. 4096", 0, 4096)
+    dm = _number(damping, "damping should be a number in (0, 1]", 0.0, 1.0)
+    if dm == 0.0:
+        raise ValueError("damping should be a number in (0, 1]")
+    rb = 0.0
+    if robust_deg is not None:
+        rb = _number(robust_deg, "robust_deg should be None or a number in (0, 180)", 0.0, 180.0)
+        if rb in (0.0, 180.0):
+            raise ValueError("robust_deg should be None or a number in (0, 180)")
+    return K, n, rt, sw, dm, rb, _number(tol, "tol should be a number >= 0", 0.0)
+
+
+def average_rotations(pairs, R_rel, n_images, weight=None, edge_keep=None, R0=None, known=None, root=0, sweeps=200, damping=0.5, robust_deg=5.0,
+                      tol=1e-9, with_edges=False, device=0, **unknown):
+    """Rotation averaging (include/mi_degensac.h mi_degensac_rotation_average, blocking, numpy): one world-to-camera rotation per image
+    from the relative rotations of a pair list.  pairs [K, 2] (int32 or int64, both columns images of one store of n_images images) and
+    R_rel [K, 3, 3] float64 as relative_pose / refine_pose return R for that list: X_j = R_rel X_i with i, j = pairs[k].  weight [K]
+    float64 (None: 1; e.g. the pose call's info[:, 3]) and edge_keep [K] bool / uint8 (None: all; e.g. info[:, 4] == POSE_OK).  An edge
+    with an end out of range, i == j, a weight that is not > 0 and finite, or an R_rel whose squared elements do not add up to 3 within
+    1e-6 (the zeros of a failed pose entry) is unused.  The gauge: camera `root` is held at the identity, or the cameras with known [n]
+    != 0 are held at R0 [n, 3, 3] (registering new images against an existing reconstruction).  Cameras are first set breadth-first over
+    their heaviest edge, one level per sweep, then every camera that is not held moves by `damping` times the weighted mean of its
+    edges' residual rotation vectors (Cayley vectors, |w| = tan(angle / 2)); with robust_deg an edge's weight is multiplied by
+    (s^2 / (s^2 + |w|^2))^2, s = tan(robust_deg / 2).  At most `sweeps` Jacobi sweeps; one that sets no camera and gives no camera a
+    squared mean above tol^2 is the last.
+    Returns (R [n, 3, 3], zeros where a camera was never set; info [n, 4] int32 = (half-edges used, the sweep in which the camera was
+    set: 0 held, -1 never, opposed edges in the last sweep, _lib.ROTAVG_KNOWN / OK / UNREACHED / ISOLATED); step [n]: the squared norm of
+    the camera's last mean vector, NaN where none was formed; summary [4] int64 = (sweeps that changed something, cameras set, edges
+    used, _lib.ROTAVG_CONVERGED / MAX_SWEEPS / NO_ROOT)[, edge_cos [K]: the cosine of the angle between R_rel and R_j R_i^T at the end,
+    NaN for an edge that is unused or has an end that was never set])."""
+    if unknown:
+        raise ValueError(f"average_rotations: unknown keyword {sorted(unknown)[0]!r}")
+    pr = np.asarray(pairs); Rr = np.asarray(R_rel)
+    w = None if weight is None else np.asarray(weight)
+    kp = None if edge_keep is None else np.asarray(edge_keep)
+    r0 = None if R0 is None else np.asarray(R0)
+    kn = None if known is None else np.asarray(known)
+    K, n, rt, sw, dm, rb, tl = check_rotavg_args(pr.shape, pr.dtype, Rr.shape, Rr.dtype, n_images, _sd(w), _sd(kp), _sd(r0), _sd(kn), root, sweeps, damping,
+                                                 robust_deg, tol)
+    pr = np.ascontiguousarray(np.clip(pr, -1, 0x7fffffff).astype(np.int32)); Rr = np.ascontiguousarray(Rr)
+    w = None if w is None else np.ascontiguousarray(w)
+    kp = None if kp is None else np.ascontiguousarray(kp).view(np.uint8)
+    r0 = None if r0 is None else np.ascontiguousarray(r0)
+    kn = None if kn is None else np.ascontiguousarray(kn).view(np.uint8)
+    R = np.zeros((n, 3, 3)); info = np.zeros((n, 4), np.int32); step = np.full(n, np.nan); summary = np.zeros(4, np.int64)
+    cosv = np.full(K, np.nan) if with_edges else None
+    vp = _lib.vptr
+    ve = lambda x: _lib.vptr(x, empty_none=True)          # noqa: E731
+    rc = _lib.lib().mi_degensac_rotation_average(ve(pr), ve(Rr), ve(w), ve(kp), K, n, vp(r0), vp(kn), rt, sw, dm, rb, tl, int(device), vp(R), vp(info),
+                                                 vp(step), vp(summary), ve(cosv))
+    _lib.check_match(rc)
+    res = (R, info, step, summary)
+    return res + (cosv,) if with_edges else res
+
+
 def pose_config(info, min_front_ratio=0.5, min_wide_ratio=0.0):
     """What the info rows [K, 5] of relative_pose / relative_pose_tensors (numpy, or a tensor, which is copied to the host) say about a
     pair that two_view_config put into class 2, "planar or panoramic": int8 [K] with 2 = panoramic (wide <= min_wide_ratio * front,

@@ -1054,3 +1054,53 @@ def refine_cameras_tensors(track_offsets, obs, obs_image, kps, cams, R, t, X, n_
     if with_err:
         res += (err[:M],)
     return res + (io, iobs[:M]) if with_table else res
+
+
+def average_rotations_tensors(pairs, R_rel, n_images, weight=None, edge_keep=None, R0=None, known=None, root=0, sweeps=200, damping=0.5,
+                              robust_deg=5.0, tol=1e-9, with_edges=False, **unknown):
+    """Rotation averaging on the device and without a host synchronisation (include/mi_degensac.h mi_degensac_rotation_average_dev): the
+    step between the pair-list calls, which end with one (R, t) per pair, and the track calls, which start from one pose per image.
+    pairs [K, 2] (int32 or int64, both columns images of ONE store of n_images images) and R_rel [K, 3, 3] float64 exactly as
+    relative_pose_tensors / refine_pose_tensors return R for that list: X_j = R_rel X_i with i, j = pairs[k].  weight [K] float64 (None:
+    1), e.g. the pose call's info[:, 3].double(); edge_keep [K] bool / uint8 (None: all), e.g. info[:, 4] == _lib.POSE_OK: tensor
+    expressions, nothing is read back.  An edge with an end out of range, i == j, a weight that is not > 0 and finite, or an R_rel whose
+    squared elements do not add up to 3 within 1e-6 (the zeros of a failed pose entry) is unused.  The gauge: camera `root` is held at
+    the identity, or the cameras with known [n] != 0 are held at R0 [n, 3, 3] (this also registers new images against an existing
+    reconstruction).  Cameras are first set breadth-first over their heaviest edge, one level per sweep; then every camera that is not
+    held moves by `damping` times the weighted mean of its edges' residual Cayley vectors (|w| = tan(angle / 2)); with robust_deg an
+    edge's weight is multiplied by (s^2 / (s^2 + |w|^2))^2, s = tan(robust_deg / 2).  `sweeps` Jacobi sweeps are queued, one launch
+    each; the first that sets no camera and gives no camera a squared mean above tol^2 is the last that does anything.
+    Returns (R [n, 3, 3] world-to-camera, zeros where a camera was never set; info [n, 4] int32 = (half-edges used, the sweep in which
+    the camera was set: 0 held, -1 never, opposed edges in the last sweep, _lib.ROTAVG_KNOWN / OK / UNREACHED / ISOLATED); step [n]: the
+    squared norm of the camera's last mean vector, NaN where none was formed; summary [4] int64 = (sweeps that changed something, cameras
+    set, edges used, _lib.ROTAVG_CONVERGED / MAX_SWEEPS / NO_ROOT)[, edge_cos [K]: the cosine of the angle between R_rel and R_j R_i^T
+    at the end, NaN for an edge that is unused or has an end that was never set]) on the device, asynchronous on the current stream.
+    Camera positions are not estimated."""
+    import torch
+    from . import matcher
+    if unknown:
+        raise ValueError(f"average_rotations_tensors: unknown keyword {sorted(unknown)[0]!r}")
+    ts = [pairs, R_rel] + [x for x in (weight, edge_keep, R0, known) if x is not None]
+    names = "pairs, R_rel (and weight, edge_keep, R0, known)"
+    _require(names, ts)
+    K, n, rt, sw, dm, rb, tl = matcher.check_rotavg_args(tuple(pairs.shape), pairs.dtype, tuple(R_rel.shape), R_rel.dtype, n_images, _sd(weight),
+                                                         _sd(edge_keep), _sd(R0), _sd(known), root, sweeps, damping, robust_deg, tol)
+    _require(names, ts, "cuda")
+    dev = R_rel.device
+    pr = pairs.contiguous() if pairs.dtype == torch.int32 else pairs.clamp(-1, 0x7fffffff).to(torch.int32).contiguous()
+    Rr = R_rel.contiguous()
+    w = None if weight is None else weight.contiguous()
+    kp = None if edge_keep is None else edge_keep.contiguous().view(torch.uint8)
+    r0 = None if R0 is None else R0.contiguous()
+    kn = None if known is None else known.contiguous().view(torch.uint8)
+    R = torch.empty((n, 3, 3), dtype=torch.float64, device=dev); info = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    step = torch.empty(n, dtype=torch.float64, device=dev); summary = torch.empty(4, dtype=torch.int64, device=dev)
+    cosv = torch.empty(max(K, 1), dtype=torch.float64, device=dev) if with_edges else None          # (an address also where K == 0)
+    di, stream, sp = _stream(dev)
+    p = lambda x: _p(x, empty_none=True)          # noqa: E731
+    rc = _lib.lib().mi_degensac_rotation_average_dev(p(pr), p(Rr), p(w), p(kp), K, n, _p(r0), _p(kn), rt, sw, dm, rb, tl, di, sp, _p(R), _p(info),
+                                                     _p(step), _p(summary), _p(cosv))
+    _lib.check_match(rc)
+    _keep_alive(stream, pr, Rr, w, kp, r0, kn)
+    res = (R, info, step, summary)
+    return res + (cosv[:K],) if with_edges else res
