@@ -1414,7 +1414,10 @@ int mi_degensac_solve7(const double *pts1, const double *pts2, int n, int dim,
  * where the device can differ from a host run of the reference in the last bits.
  * op 5 = op 3 with TWO problems per wave (dg_eig2.h: problem 2t in lanes 0..31 of wave t, 2t + 1 in lanes 32..63), same output.
  * op 6 / 7 = timing of op 3 / op 5: every wave solves its problem(s) flag[0] times (on entry) and leaves the 100 MHz ticks that took
- * in out[wave]. */
+ * in out[wave].
+ * op 8 / 9 / 10 = dg_cr_cos / dg_cr_acos / dg_cr_pow13 (dg_crmath.h) as compiled for the device, one argument per lane: in 1, out 1,
+ * flag = 0.  What op 4 calls, by itself: the correctly rounded cos on [0, pi], acos on [-1, 1] and pow(x, 1.0/3) on (1e-290, 1e290);
+ * outside those ranges the device library's own value. */
 int mi_degensac_mat3(int op, const double *in, int count, int device, double *out, int32_t *flag);
 /* the screening counts of the scoring phase (dg_score_tiles.h) for given fundamental-matrix models over a point set:
  * c1[m] = level-1 count (single precision, loosest denominator, rounding-widened threshold), c2[m] = level-2 count

@@ -293,7 +293,7 @@ extern "C" int mi_degensac_solve7(const double *pts1, const double *pts2, int n,
 
 
 /* one problem per lane through the lane-level 3x3 routines of dg_mat3.h (op 0: inverse, 1: right singular vectors,
- * 2: Hdetect) */
+ * 2: Hdetect), op 4: the cubic's roots, ops 8 / 9 / 10: dg_cr_cos / dg_cr_acos / dg_cr_pow13 of one argument */
 __global__ void dg_mat3_kernel(int op, const double *in, int count, double *out, int *flag)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -314,6 +314,11 @@ __global__ void dg_mat3_kernel(int op, const double *in, int count, double *out,
         double po[4], r[3] = {0, 0, 0}; for (int i = 0; i < 4; i++) po[i] = in[(size_t)t * 4 + i];
         flag[t] = dg_rroots3(po, r);
         for (int i = 0; i < 3; i++) out[(size_t)t * 3 + i] = r[i];
+    } else if (op >= 8) {
+        /* the three functions rroots3 takes from dg_crmath.h, as compiled for the device */
+        const double x = in[t];
+        out[t] = op == 8 ? dg_cr_cos(x) : op == 9 ? dg_cr_acos(x) : dg_cr_pow13(x);
+        flag[t] = 0;
     } else {
         /* in: F (9), seven correspondences x1 y1 x2 y2 (28), triplet (3, as doubles) */
         double F[9], u7[7][4]; unsigned char ids[3];
@@ -377,15 +382,16 @@ __global__ void dg_eig9x2_kernel(const double *in, int count, double *out, int *
 extern "C" int mi_degensac_mat3(int op, const double *in, int count, int device, double *out, int32_t *flag)
 {
     DG_UNIT_ENTER(device);
-    if (op < 0 || op > 7 || count < 0) { set_err("bad op"); return MI_DEGENSAC_EINVAL; }
-    const int reps = op >= 6 ? (flag[0] > 0 ? flag[0] : 1) : 0;            /* ops 6 / 7: repetitions per block, passed in flag[0] */
-    const size_t ni = op == 4 ? 4 : (op == 3 || op >= 5) ? 81 : op == 2 ? 40 : 9, no = op == 4 ? 3 : (op == 3 || op >= 5) ? 90 : op == 1 ? 12 : 9;
+    if (op < 0 || op > 10 || count < 0) { set_err("bad op"); return MI_DEGENSAC_EINVAL; }
+    const bool eig = op == 3 || (op >= 5 && op <= 7);
+    const int reps = (op == 6 || op == 7) ? (flag[0] > 0 ? flag[0] : 1) : 0;   /* ops 6 / 7: repetitions per block, passed in flag[0] */
+    const size_t ni = op >= 8 ? 1 : op == 4 ? 4 : eig ? 81 : op == 2 ? 40 : 9, no = op >= 8 ? 1 : op == 4 ? 3 : eig ? 90 : op == 1 ? 12 : 9;
     DevBuf<double> di, dout; DevBuf<int> df;
     if (di.alloc(count * ni) || dout.alloc(count * no) || df.alloc(count)) { set_err("device allocation failed"); return MI_DEGENSAC_ENOMEM; }
     HIPCHK(hipMemcpy(di.p, in, count * ni * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemset(df.p, 0, (size_t)count * sizeof(int)));
     if (count && op == 3) hipLaunchKernelGGL(dg_eig9_kernel, dim3(count), dim3(64), 0, 0, di.p, count, dout.p, df.p);
-    else if (count && op >= 5) {
+    else if (count && eig) {
         const int two = (op == 5 || op == 7) ? 1 : 0;
         hipLaunchKernelGGL(dg_eig9x2_kernel, dim3(two ? (count + 1) / 2 : count), dim3(64), 0, 0, di.p, count, dout.p, df.p, reps, two);
     }
