@@ -1011,6 +1011,82 @@ int mi_degensac_pose_lists(const double *pts, const int64_t *corr_offsets, const
 /* the tile constants: which = 0 rows per workgroup and step of a row pass, 1 the cap on the grid (-1 for any other value) */
 int mi_degensac_pose_tile(int which);
 
+/* ---- relative pose from a homography on exported correspondence lists (mi_pose_h.hip) ---------------------------------------------------
+ * The pose call above takes (R, t) from F.  For a pair whose points lie on a plane, or whose cameras share a centre, F is degenerate: a
+ * family of fundamental matrices fits and the estimator returns an arbitrary member, whose decomposition is a wrong pose.  Such a pair
+ * (class 2 of the F + H verification) has its pose in the homography instead, which this call decomposes: G = K2^-1 H K1 = R + (t / d)
+ * n^T for a plane n . X = d in the frame of camera 1, or G = R for a pure rotation.  Rows, offsets, keep, cameras and camera indices
+ * exactly as mi_degensac_pose_lists_dev takes them; one more input per entry:
+ *   H[p]         d_H[9 p ..], row-major, x2 ~ H x1 (any scale, either sign): the homography in the CALLER'S form, H = (M^T)^-1 for a
+ *                model M in the driver's form as the estimator, the refit and dg_HDs take it.
+ * Every step below is ONE IEEE float64 operation per written operator (+ - * / and sqrt only), no contraction; a sum of three terms is
+ * (first + second) + third; a product with +-1 is exact.  Per entry (statuses in their order of precedence):
+ *   range, cameras   as in mi_degensac_pose_lists_dev: MI_DEGENSAC_POSE_TRUNCATED, MI_DEGENSAC_POSE_BAD_CAMERA
+ *   G = K2^-1 H K1   L = H K1: L[i][0] = H[i][0] fx1, L[i][1] = H[i][1] fy1, L[i][2] = (H[i][0] cx1 + H[i][1] cy1) + H[i][2]; then
+ *                G[0][j] = (L[0][j] - cx2 L[2][j]) / fx2, G[1][j] = (L[1][j] - cy2 L[2][j]) / fy2, G[2][j] = L[2][j].
+ *                m = the largest |G[i][j]|; an entry that is not finite, or m == 0: MI_DEGENSAC_POSE_BAD_MODEL.  A = G / m.
+ *   V, sigma     the one-sided Jacobi rule of mi_degensac_pose_lists_dev on A, word for word: six sweeps, the same rotation, the same
+ *                descending sort with ties keeping the lower column: v1, v2, v3, b1, b2, b3 (b_i = A v_i) and sigma1 >= sigma2 >= sigma3.
+ *                sigma3 not > 0: BAD_MODEL (a homography has full rank).
+ *   sign         s = -1 if det A < 0, else 1, with det A = (A00 (A11 A22 - A12 A21) - A01 (A10 A22 - A12 A20)) + A02 (A10 A21 - A11 A20):
+ *                s A / sigma2 has the middle singular value 1 and both cameras on one side of the plane.
+ *   rotation     if sigma1 - sigma3 <= rotation_eps sigma2 the status is MI_DEGENSAC_POSE_ROTATION: u_i = b_i / sigma_i (i = 1, 2, 3),
+ *                R[r][c] = (u1[r] v1[c] + u2[r] v2[c]) + u3[r] v3[c], negated when its determinant (the formula above) is < 0; a number
+ *                that is not finite: BAD_MODEL.  The single candidate is (R, t = 0) in slot 0, there is no normal, t_over_d = 0.
+ *   solutions    otherwise, by the construction of Ma, Soatto, Kosecka & Sastry (An Invitation to 3-D Vision, theorem 5.19) from V alone:
+ *                N = s A / sigma2 (N[i][j] = s (A[i][j] / sigma2)), h_i = N v_i taken as h_i[r] = s (b_i[r] / sigma2),
+ *                k1 = sigma1 / sigma2, k3 = sigma3 / sigma2, p = sqrt((1 - k3) (1 + k3)), q = sqrt((k1 - 1) (k1 + 1)),
+ *                w = sqrt((k1 - k3) (k1 + k3)).  For the two signs, a = (p v1 + q v3) / w and g = (p h1 + q h3) / w, then a = (p v1 - q v3)
+ *                / w and g = (p h1 - q h3) / w (g = N a): v2 and a are the unit vectors whose length N keeps, so with
+ *                n = v2 x a, rn = h2 x g (cross products as in the pose call: (1 2 - 2 1), (2 0 - 0 2), (0 1 - 1 0)):
+ *                R[r][c] = (h2[r] v2[c] + g[r] a[c]) + rn[r] n[c],   T[r] = ((N[r][0] n[0] + N[r][1] n[1]) + N[r][2] n[2]) - rn[r]   (= t / d),
+ *                t_over_d = sqrt((T[0]^2 + T[1]^2) + T[2]^2), t = T / t_over_d.
+ *   candidates   in this order, (Ra, ta, na) from the + sign and (Rb, tb, nb) from the - sign: 0: (Ra, ta, na), 1: (Rb, tb, nb),
+ *                2: (Ra, -ta, -na), 3: (Rb, -tb, -nb); the meaning is X2 = R X1 + t, |t| = 1, n the unit normal of the plane in the frame
+ *                of camera 1.  A candidate with a number that is not finite: BAD_MODEL.  c2 per candidate as in the pose call.
+ * Per used row and candidate, rays, midpoint, lambda1, lambda2, X and cosang are the pose call's rule unchanged.  A row is
+ *   front        iff lambda1 > 0 and lambda2 > 0 and (n[0] d1[0] + n[1] d1[1]) + n[2] > 0: it triangulates in front of both cameras and
+ *                the plane is seen from its visible side; a NaN is not front.  Of a pair (q, q + 2) at most one passes the plane-side test,
+ *                so two of the four survive by construction; what tells the remaining two apart is only the rows that lie beyond the
+ *                other solution's plane, and info[2] says when there were none.
+ *   rotation     front iff (R[2][0] d1[0] + R[2][1] d1[1]) + R[2][2] > 0 (the ray lies in front of camera 2); cosang as above (the
+ *                angle that the rotation leaves between the two rays); there are no depths and no midpoint.
+ * The chosen pose is the candidate with the most front rows among the used rows; ties go to the first in the order above.  No used row:
+ * MI_DEGENSAC_POSE_EMPTY.  With a status other than OK and ROTATION the pose is twelve zeros, the info row is (0, 0, 0, 0, status) and no
+ * row of the entry is written.  Ranges must not overlap.
+ * Outputs:
+ *   d_pose [K, 12]          R row-major, then t, of the chosen candidate (ROTATION: t = 0); goes into mi_degensac_pose_refine_lists_dev
+ *                           (which answers t = 0 with REFINE_BAD_POSE) and mi_degensac_rotation_average_dev as the pose call's does
+ *   d_front [cap] uint8     1 for the used rows that are front under the chosen candidate; every other position keeps 0
+ *   d_info [K, 5] int32     rows used, front rows of the chosen candidate, the largest front count of the other three (ROTATION: 0), wide
+ *                           rows (ROTATION: 0), status
+ *   d_normal [K, 3]         n of the chosen candidate; zeros without a pose and for ROTATION
+ *   d_t_over_d [K]          baseline over plane distance of the chosen candidate, before t was normalised; 0 likewise
+ *   d_X [cap, 3], d_depth [cap, 2], d_cosang [cap]   (each nullable) as in the pose call; ROTATION writes cosang only
+ *   d_cand [K, 4, 12], d_cand_normal [K, 4, 3], d_cand_front [K, 4] int32   (each nullable) all candidates and normals (zeros for
+ *                           TRUNCATED, BAD_CAMERA, BAD_MODEL; ROTATION: slot 0 only) and their front counts (zeros unless OK or ROTATION)
+ * One workgroup per entry, no atomics, counts by wave ballots and integer adds: the same bits on every call.  Asynchronous on `stream`;
+ * the call needs no temporaries.  d_corr_offsets and d_cam_idx are device data and are checked on the device, not on the host.
+ * Refused with MI_DEGENSAC_EINVAL and a message in mi_degensac_match_last_error(), before a device is looked for and in this order:
+ * n_entries < 0; cap < 0 or > 0x3fffffff; n_cams < 0; a cos_min that is NaN or outside [-1, 1]; a rotation_eps that is NaN or < 0; NULL
+ * d_corr_offsets; for n_entries > 0 NULL d_H or d_cams, then NULL d_pose, d_info, d_normal or d_t_over_d; for cap > 0 NULL d_pts or
+ * d_front.  n_entries == 0 and cap == 0 succeed (with n_entries == 0 the fills are all that is written). */
+enum { MI_DEGENSAC_POSE_ROTATION = 5 };
+int mi_degensac_pose_h_lists_dev(const double *d_pts, const int64_t *d_corr_offsets, const uint8_t *d_keep /*nullable*/, const double *d_H,
+                                 const double *d_cams, int n_cams, const int32_t *d_cam_idx /*nullable*/, int n_entries, int64_t cap,
+                                 double cos_min, double rotation_eps, int device, void *stream, double *d_pose, uint8_t *d_front,
+                                 int32_t *d_info, double *d_normal, double *d_t_over_d, double *d_X /*nullable*/, double *d_depth /*nullable*/,
+                                 double *d_cosang /*nullable*/, double *d_cand /*nullable*/, double *d_cand_normal /*nullable*/,
+                                 int32_t *d_cand_front /*nullable*/);
+/* the same on host pointers (blocking): the inputs go to the device once, every output that is asked for comes back whole */
+int mi_degensac_pose_h_lists(const double *pts, const int64_t *corr_offsets, const uint8_t *keep /*nullable*/, const double *H,
+                             const double *cams, int n_cams, const int32_t *cam_idx /*nullable*/, int n_entries, int64_t cap, double cos_min,
+                             double rotation_eps, int device, double *pose, uint8_t *front, int32_t *info, double *normal, double *t_over_d,
+                             double *X /*nullable*/, double *depth /*nullable*/, double *cosang /*nullable*/, double *cand /*nullable*/,
+                             double *cand_normal /*nullable*/, int32_t *cand_front /*nullable*/);
+/* the tile constants: which = 0 rows per workgroup and step of a row pass, 1 the cap on the grid (-1 for any other value) */
+int mi_degensac_pose_h_tile(int which);
+
 /* ---- refinement of relative poses on exported correspondence lists ---------------------------------------------------------------------
  * The pose call takes (R, t) from E = K2^T F K1 of an uncalibrated F, which is no essential matrix, and snaps it to one without looking
  * at the rows again.  This call follows it with what every structure-from-motion front end runs next: a Levenberg-Marquardt refinement

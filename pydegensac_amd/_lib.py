@@ -47,6 +47,10 @@ REFIT_FIXED, REFIT_MAX_FITS, REFIT_SHORT, REFIT_BAD_FIT, REFIT_WORSE, REFIT_TRUN
 # grid; the status column of its info rows (MI_DEGENSAC_POSE_*)
 POSE_STEP, POSE_GRID = 1024, 256
 POSE_OK, POSE_BAD_MODEL, POSE_BAD_CAMERA, POSE_TRUNCATED, POSE_EMPTY = range(5)
+# the relative pose from a homography (csrc/mi_pose_h.hip PH_STEP / PH_GRID, mi_degensac_pose_h_tile): the same tile constants; its info
+# rows reuse the POSE_* statuses and add POSE_ROTATION for a pure rotation (MI_DEGENSAC_POSE_ROTATION)
+POSE_H_STEP, POSE_H_GRID = 1024, 256
+POSE_ROTATION = 5
 # the pose refinement (csrc/mi_pose_refine.hip PR_STEP / PR_GRID, mi_degensac_pose_refine_tile): rows per workgroup and step of a row pass,
 # the cap on the grid; the status column of its info rows (MI_DEGENSAC_REFINE_*)
 REFINE_STEP, REFINE_GRID = 1024, 256
@@ -377,6 +381,17 @@ def lib():
             l.mi_degensac_pose_lists.argtypes = head + [vp] * 8
             l.mi_degensac_pose_tile.restype = C.c_int
             l.mi_degensac_pose_tile.argtypes = [C.c_int]
+        if hasattr(l, "mi_degensac_pose_h_lists_dev"):                    # (absent from older builds loaded through MI_DEGENSAC_LIB)
+            # pts, corr_offsets, keep, H, cams, n_cams, cam_idx, K, cap, cos_min, rotation_eps, device[, stream] | pose, front, info, normal,
+            # t_over_d, X, depth, cosang, cand, cand_normal, cand_front
+            vp = C.c_void_p
+            head = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_int]
+            l.mi_degensac_pose_h_lists_dev.restype = C.c_int
+            l.mi_degensac_pose_h_lists_dev.argtypes = head + [vp] + [vp] * 11
+            l.mi_degensac_pose_h_lists.restype = C.c_int
+            l.mi_degensac_pose_h_lists.argtypes = head + [vp] * 11
+            l.mi_degensac_pose_h_tile.restype = C.c_int
+            l.mi_degensac_pose_h_tile.argtypes = [C.c_int]
         if hasattr(l, "mi_degensac_pose_refine_lists_dev"):               # (absent from older builds loaded through MI_DEGENSAC_LIB)
             # pts, corr_offsets, keep, pose, cams, n_cams, cam_idx, K, cap, max_trials, ftol, device[, stream] | pose_out, cost, info, resid, F
             vp = C.c_void_p

@@ -1206,6 +1206,91 @@ def relative_pose(pts, corr_offsets, models, cams1, pairs=None, cams2=None, keep
     return res + (cand, cf) if with_candidates else res
 
 
+def check_pose_h_args(pts_shape, pts_dtype, off_shape, off_dtype, models_shape, models_dtype, cams1_shape, cams1_dtype, pairs=None, cams2=None,
+                      keep=None, min_parallax_deg=1.5, rotation_eps=1e-3):
+    """The argument checks of homography_pose / homography_pose_tensors: those of check_pose_args (models are homographies here), and
+    rotation_eps a number >= 0.  Returns (K, cap, rows of cams1, rows of cams2 or None, cos_min, rotation_eps); raises ValueError."""
+    try:
+        res = check_pose_args(pts_shape, pts_dtype, off_shape, off_dtype, models_shape, models_dtype, cams1_shape, cams1_dtype, pairs, cams2, keep,
+                              min_parallax_deg)
+    except ValueError as err:
+        raise ValueError(str(err).replace("one fundamental matrix per entry", "one homography per entry")) from None
+    return res + (_number(rotation_eps, "rotation_eps should be a number >= 0", 0.0),)
+
+
+def homography_pose(pts, corr_offsets, models, cams1, pairs=None, cams2=None, keep=None, min_parallax_deg=1.5, rotation_eps=1e-3, driver_form=False,
+                    with_points=False, with_candidates=False, device=0):
+    """Relative pose from a homography on exported correspondence lists (include/mi_degensac.h mi_degensac_pose_h_lists, blocking, numpy):
+    the pose of a pair that two_view_config put into class 2, planar or panoramic, on which the F of relative_pose is degenerate.  pts,
+    corr_offsets, cameras, pairs and keep exactly as relative_pose takes them; models [K, 3, 3] are the homographies of a verify, F + H or
+    refit call in the caller's form (x2 ~ H x1), or with driver_form=True in the driver's.  Per entry G = K2^-1 H K1 is decomposed into
+    its four solutions G = R + (t / d) n^T, and the one under which most used rows triangulate in front of both cameras and see the plane
+    from its visible side is chosen (ties go to the first); a G whose singular values differ by no more than rotation_eps times the middle
+    one is a pure rotation: status _lib.POSE_ROTATION, R = the rotation, t = 0.
+    Returns (R [K, 3, 3], t [K, 3], front [cap] bool, info [K, 5] int32 = (rows used, front rows of the chosen candidate, the largest
+    front count of the other three, wide rows, _lib.POSE_* status), normal [K, 3] = the unit plane normal in the frame of camera 1,
+    t_over_d [K] = baseline over plane distance[, X [cap, 3], depth [cap, 2], cosang [cap]][, cand [K, 4, 12], cand_normal [K, 4, 3],
+    cand_front [K, 4]]).  The meaning is relative_pose's: X2 = R X1 + t, |t| = 1."""
+    P = np.ascontiguousarray(np.asarray(pts)); o = np.ascontiguousarray(np.asarray(corr_offsets)); M = np.asarray(models)
+    c1 = np.asarray(cams1); c2 = None if cams2 is None else np.asarray(cams2)
+    pr = None if pairs is None else np.asarray(pairs)
+    kp = None if keep is None else np.asarray(keep)
+    K, cap, n1, n2, cos_min, eps = check_pose_h_args(P.shape, P.dtype, o.shape, o.dtype, M.shape, M.dtype, c1.shape, c1.dtype, _sd(pr), _sd(c2), _sd(kp),
+                                                     min_parallax_deg, rotation_eps)
+    H = np.ascontiguousarray(_h_user_form(M) if driver_form else M, np.float64).reshape(K, 9)
+    cams, idx = _cameras(c1, c2, pr, K, n1, n2)
+    if kp is not None:
+        kp = np.ascontiguousarray(kp).view(np.uint8)
+    pose = np.zeros((K, 12)); front = np.zeros(cap, np.uint8); info = np.zeros((K, 5), np.int32); normal = np.zeros((K, 3)); tod = np.zeros(K)
+    X = np.full((cap, 3), np.nan) if with_points else None
+    depth = np.full((cap, 2), np.nan) if with_points else None
+    cosang = np.full(cap, np.nan) if with_points else None
+    cand = np.zeros((K, 4, 12)) if with_candidates else None
+    cn = np.zeros((K, 4, 3)) if with_candidates else None
+    cf = np.zeros((K, 4), np.int32) if with_candidates else None
+    vp = _lib.vptr
+    rc = _lib.lib().mi_degensac_pose_h_lists(vp(P), vp(o), vp(kp), vp(H), vp(cams), len(cams), vp(idx), K, cap, cos_min, eps, int(device), vp(pose),
+                                             vp(front), vp(info), vp(normal), vp(tod), vp(X), vp(depth), vp(cosang), vp(cand), vp(cn), vp(cf))
+    _lib.check_match(rc)
+    res = (pose[:, :9].reshape(K, 3, 3), pose[:, 9:], front.astype(bool), info, normal, tod)
+    if with_points:
+        res += (X, depth, cosang)
+    return res + (cand, cn, cf) if with_candidates else res
+
+
+def check_select_args(cls_shape, K_f, K_h):
+    """the shape checks of select_pose / select_pose_tensors: both pose results are for the K pairs of cls"""
+    if len(cls_shape) != 1 or K_f != cls_shape[0] or K_h != cls_shape[0]:
+        raise ValueError("cls should be [K], one class per pair, and pose_f and pose_h the results of the two pose calls on the same K pairs")
+    return int(cls_shape[0])
+
+
+def select_pose(cls, pose_f, pose_h, corr_offsets=None):
+    """Per pair the pose to keep: pose_h's R, t, front and info where cls [K] (two_view_config) says 2 and the status of pose_h is POSE_OK
+    or POSE_ROTATION, else pose_f's.  pose_f = (R, t, front, info, ...) of relative_pose, pose_h likewise of homography_pose, both on the
+    same lists.  front is chosen per row by the row's pair, which takes the lists' corr_offsets [K + 1]; without it front is None.
+    Returns (R [K, 3, 3], t [K, 3], front [cap] bool or None, info [K, 5], use_h [K] bool, edge_keep [K] bool = the pairs whose R is
+    valid, for average_rotations: status POSE_OK or POSE_ROTATION of the selected pose; a ROTATION pair has a valid R although its t is
+    zero and refine_pose answers it with REFINE_BAD_POSE)."""
+    c = np.asarray(cls); Rf, tf, ff, inf = (np.asarray(x) for x in pose_f[:4]); Rh, th, fh, inh = (np.asarray(x) for x in pose_h[:4])
+    K = check_select_args(c.shape, len(inf), len(inh))
+    sh = inh[:, 4]
+    use_h = (c == 2) & ((sh == _lib.POSE_OK) | (sh == _lib.POSE_ROTATION))
+    R = np.where(use_h[:, None, None], Rh, Rf); t = np.where(use_h[:, None], th, tf); info = np.where(use_h[:, None], inh, inf)
+    front = None
+    if corr_offsets is not None:
+        o = np.asarray(corr_offsets)
+        if o.shape != (K + 1,) or ff.shape != fh.shape:
+            raise ValueError("corr_offsets should be [K + 1], the offsets of the lists both pose calls ran on")
+        if K == 0 or len(ff) == 0:
+            front = ff.copy()
+        else:
+            entry = np.minimum(np.searchsorted(o[1:], np.arange(len(ff)), side="right"), K - 1)
+            front = np.where(use_h[entry], fh, ff)
+    st = info[:, 4]
+    return R, t, front, info, use_h, (st == _lib.POSE_OK) | (st == _lib.POSE_ROTATION)
+
+
 def check_refine_args(pts_shape, pts_dtype, off_shape, off_dtype, R_shape, R_dtype, t_shape, t_dtype, cams1_shape, cams1_dtype, pairs=None, cams2=None,
                       keep=None, max_trials=20, ftol=1e-12):
     """The argument checks of refine_pose / refine_pose_tensors on shapes and dtype names (numpy or torch): R float64 [K, 3, 3] and t

@@ -176,6 +176,36 @@ def image_collection(m=8, n=500, inlier_ratio=0.5, sigma=0.1, dim=64, seed=0, de
     return kps, descs
 
 
+def planar_collection(m=8, n=500, inlier_ratio=0.5, sigma=0.1, dim=64, seed=0, desc_sigma=0.15, kind="planar"):
+    """image_collection's sibling for the pairs on which a fundamental matrix is degenerate.  kind "planar": the cameras of
+    collection_cameras(m) look at points of ONE plane (a facade through (0, 0, 6), tilted about both axes), so every pair is related by
+    the homography K (R + t n^T / d) K^-1.  kind "panoramic": the same rotations about one centre (every t = 0) look at a 3-D cloud, so
+    every pair is related by K R K^-1.  Keypoints, clutter, descriptors and the row permutation as in image_collection; its outputs are
+    not touched by this function.  Returns ([kps_i [n, 2]], [desc_i [n, dim] float32], dict(K, poses = [(R_i, t_i)], normal, X))."""
+    if kind not in ("planar", "panoramic"):
+        raise ValueError("kind should be 'planar' or 'panoramic'")
+    rng = np.random.default_rng([seed, 0 if kind == "planar" else 1])
+    K, poses = collection_cameras(m)
+    x, y = rng.uniform(-2.4, 2.4, n), rng.uniform(-1.8, 1.8, n)
+    normal = np.array([0.25, -0.15, 1.0]); normal = normal / np.linalg.norm(normal)
+    if kind == "planar":
+        X = np.stack([x, y, 6.0 - (normal[0] * x + normal[1] * y) / normal[2]], 1)
+    else:
+        X = np.stack([x, y, rng.uniform(4, 8, n)], 1); poses = [(R, np.zeros(3)) for R, _ in poses]; normal = np.zeros(3)
+    base = rng.normal(size=(n, dim)).astype(np.float32)
+    n_in = int(round(n * inlier_ratio))
+    kps, descs = [], []
+    for R, t in poses:
+        seen = rng.permutation(n)[:n_in]
+        p = np.stack([rng.uniform(0, IMG_W, n), rng.uniform(0, IMG_H, n)], 1)
+        d = rng.normal(size=(n, dim)).astype(np.float32)
+        p[:n_in] = _project(K, R, t, X[seen]) + rng.normal(0, sigma, (n_in, 2))
+        d[:n_in] = base[seen] + desc_sigma * rng.normal(size=(n_in, dim)).astype(np.float32)
+        perm = rng.permutation(n)
+        kps.append(np.ascontiguousarray(p[perm])); descs.append(np.ascontiguousarray(d[perm]))
+    return kps, descs, dict(K=K, poses=poses, normal=normal, X=X)
+
+
 def collection_truth(m=8, n=500, inlier_ratio=0.5, sigma=0.1, dim=64, seed=0, desc_sigma=0.15):
     """What image_collection(m, n, inlier_ratio, sigma, dim, seed, desc_sigma) drew: the cloud X [n, 3] and, per image, point [n] int64 = the
     cloud index of every keypoint, -1 for clutter.  The generator's draws are replayed one for one, so the keypoint i of image k is

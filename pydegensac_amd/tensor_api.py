@@ -908,6 +908,91 @@ def relative_pose_tensors(pts, corr_offsets, models, cams1, pairs=None, cams2=No
     return res + (cand, cf) if with_candidates else res
 
 
+def homography_pose_tensors(pts, corr_offsets, models, cams1, pairs=None, cams2=None, keep=None, min_parallax_deg=1.5, rotation_eps=1e-3,
+                            driver_form=False, with_points=False, with_candidates=False):
+    """Relative pose from a homography on exported correspondence lists, on the device and without a host synchronisation
+    (include/mi_degensac.h mi_degensac_pose_h_lists_dev): the pose of a pair that matcher.two_view_config put into class 2, planar or
+    panoramic, on which the F of relative_pose_tensors is degenerate.  pts, corr_offsets, cameras, pairs and keep exactly as
+    relative_pose_tensors takes them; models [K, 3, 3] float64 are the homographies of a verify, F + H or refit call in the caller's form
+    (x2 ~ H x1), or with driver_form=True in the driver's.  Per entry G = K2^-1 H K1 is decomposed into its four solutions G = R + (t / d)
+    n^T; the one under which most used rows triangulate in front of both cameras and see the plane from its visible side is chosen (ties
+    go to the first).  A G whose singular values differ by no more than rotation_eps times the middle one is a pure rotation: status
+    _lib.POSE_ROTATION, R the rotation, t = 0.  The kernel reads the entries' lengths from corr_offsets itself, so nothing is read back.
+    Returns (R [K, 3, 3], t [K, 3], front [cap] bool, info [K, 5] int32 = (rows used, front rows of the chosen candidate, the largest
+    front count of the other three, wide rows, _lib.POSE_* status), normal [K, 3] = the unit plane normal in the frame of camera 1 (zeros
+    when there is none), t_over_d [K] = baseline over plane distance[, X [cap, 3], depth [cap, 2], cosang [cap]][, cand [K, 4, 12],
+    cand_normal [K, 4, 3], cand_front [K, 4]]) on the device, asynchronous on the current stream.  The meaning is the pose call's: X2 = R
+    X1 + t, |t| = 1; R, t, front and info go into refine_pose_tensors and average_rotations_tensors as its results do."""
+    import torch
+    from . import matcher
+    opt = [t for t in (pairs, cams2, keep) if t is not None]
+    names = "pts, corr_offsets, models, cams1 (and pairs, cams2, keep)"
+    ts = [pts, corr_offsets, models, cams1] + opt
+    _require(names, ts)
+    K, cap, n1, n2, cos_min, eps = matcher.check_pose_h_args(tuple(pts.shape), pts.dtype, tuple(corr_offsets.shape), corr_offsets.dtype,
+                                                             tuple(models.shape), models.dtype, tuple(cams1.shape), cams1.dtype, _sd(pairs), _sd(cams2),
+                                                             _sd(keep), min_parallax_deg, rotation_eps)
+    _require(names, ts, "cuda")
+    dev = pts.device
+    P = pts.contiguous(); o = corr_offsets.contiguous()
+    H = (_h_user_form(models.contiguous()) if driver_form else models).contiguous()
+    cams, n_cams, idx = _cameras(cams1, cams2, pairs, K, n1, n2)
+    kp = None if keep is None else keep.contiguous().view(torch.uint8)
+    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
+    rows = max(cap, 1)                                                # (an address also where cap == 0)
+    pose = f64(K, 12); front = torch.empty(rows, dtype=torch.uint8, device=dev); info = torch.empty((K, 5), dtype=torch.int32, device=dev)
+    normal = f64(K, 3); tod = f64(K)
+    X = f64(rows, 3) if with_points else None
+    depth = f64(rows, 2) if with_points else None
+    cosang = f64(rows) if with_points else None
+    cand = f64(K, 4, 12) if with_candidates else None
+    cn = f64(K, 4, 3) if with_candidates else None
+    cf = torch.empty((K, 4), dtype=torch.int32, device=dev) if with_candidates else None
+    di, stream, sp = _stream(dev)
+    p = _p
+    rc = _lib.lib().mi_degensac_pose_h_lists_dev(p(P), p(o), p(kp), p(H), p(cams), n_cams, p(idx), K, cap, cos_min, eps, di, sp, p(pose), p(front),
+                                                 p(info), p(normal), p(tod), p(X), p(depth), p(cosang), p(cand), p(cn), p(cf))
+    _lib.check_match(rc)
+    _keep_alive(stream, P, o, H, cams, idx, kp)
+    res = (pose[:, :9].reshape(K, 3, 3), pose[:, 9:], front[:cap].view(torch.bool), info, normal, tod)
+    if with_points:
+        res += (X[:cap], depth[:cap], cosang[:cap])
+    return res + (cand, cn, cf) if with_candidates else res
+
+
+def select_pose_tensors(cls, pose_f, pose_h, corr_offsets=None):
+    """matcher.select_pose on device tensors, as plain `where` expressions without a host read: per pair pose_h's R, t, front and info
+    where cls [K] (the classes of matcher.two_view_config as an integer tensor on the device) says 2 and pose_h's status is POSE_OK or
+    POSE_ROTATION, else pose_f's.  pose_f and pose_h are the results of relative_pose_tensors and homography_pose_tensors on the same
+    lists.  front is chosen per row by the row's pair, which takes the lists' corr_offsets [K + 1] (non-decreasing; a binary search on
+    the device); without it front is None.  Returns (R [K, 3, 3], t [K, 3], front [cap] bool or None, info [K, 5], use_h [K] bool,
+    edge_keep [K] bool = the pairs whose R is valid, for average_rotations_tensors: status POSE_OK or POSE_ROTATION of the selected pose;
+    a ROTATION pair has a valid R although its t is zero and refine_pose_tensors answers it with REFINE_BAD_POSE)."""
+    import torch
+    from . import matcher
+    Rf, tf, ff, inf = pose_f[:4]; Rh, th, fh, inh = pose_h[:4]
+    ts = [cls, Rf, tf, ff, inf, Rh, th, fh, inh] + ([] if corr_offsets is None else [corr_offsets])
+    names = "cls, pose_f, pose_h (and corr_offsets)"
+    _require(names, ts)
+    K = matcher.check_select_args(tuple(cls.shape), inf.shape[0], inh.shape[0])
+    _require(names, ts, "same")
+    sh = inh[:, 4]
+    use_h = (cls == 2) & ((sh == _lib.POSE_OK) | (sh == _lib.POSE_ROTATION))
+    R = torch.where(use_h[:, None, None], Rh, Rf); t = torch.where(use_h[:, None], th, tf); info = torch.where(use_h[:, None], inh, inf)
+    front = None
+    if corr_offsets is not None:
+        if tuple(corr_offsets.shape) != (K + 1,) or ff.shape != fh.shape:
+            raise ValueError("corr_offsets should be [K + 1], the offsets of the lists both pose calls ran on")
+        cap = ff.shape[0]
+        if K == 0 or cap == 0:
+            front = ff.clone()
+        else:
+            entry = torch.searchsorted(corr_offsets[1:].contiguous(), torch.arange(cap, device=ff.device), right=True).clamp(max=K - 1)
+            front = torch.where(use_h[entry], fh, ff)
+    st = info[:, 4]
+    return R, t, front, info, use_h, (st == _lib.POSE_OK) | (st == _lib.POSE_ROTATION)
+
+
 def refine_pose_tensors(pts, corr_offsets, R, t, cams1, pairs=None, cams2=None, keep=None, max_trials=20, ftol=1e-12, with_resid=False,
                         with_F=False, **unknown):
     """Refine relative poses on exported correspondence lists, on the device and without a host synchronisation (include/mi_degensac.h
