@@ -43,11 +43,11 @@ TRACK_ROWS, TRACK_SCAN = 1024, 256
 # grid; the status column of its info rows (MI_DEGENSAC_REFIT_*)
 REFIT_STEP, REFIT_GRID = 1024, 256
 REFIT_FIXED, REFIT_MAX_FITS, REFIT_SHORT, REFIT_BAD_FIT, REFIT_WORSE, REFIT_TRUNCATED = range(6)
-# the relative pose (csrc/mi_pose.hip PS_STEP / PS_GRID, mi_degensac_pose_tile): rows per workgroup and step of a row pass, the cap on the
+# the relative pose (csrc/mi_pose_dev.h MI_POSE_STEP / MI_POSE_GRID, mi_degensac_pose_tile): rows per workgroup and step of a row pass, the cap on the
 # grid; the status column of its info rows (MI_DEGENSAC_POSE_*)
 POSE_STEP, POSE_GRID = 1024, 256
 POSE_OK, POSE_BAD_MODEL, POSE_BAD_CAMERA, POSE_TRUNCATED, POSE_EMPTY = range(5)
-# the relative pose from a homography (csrc/mi_pose_h.hip PH_STEP / PH_GRID, mi_degensac_pose_h_tile): the same tile constants; its info
+# the relative pose from a homography (csrc/mi_pose_dev.h MI_POSE_STEP / MI_POSE_GRID, mi_degensac_pose_h_tile): the same tile constants; its info
 # rows reuse the POSE_* statuses and add POSE_ROTATION for a pure rotation (MI_DEGENSAC_POSE_ROTATION)
 POSE_H_STEP, POSE_H_GRID = 1024, 256
 POSE_ROTATION = 5
@@ -370,28 +370,15 @@ def lib():
             l.mi_degensac_refit_lists.argtypes = [vp, vp, vp, C.c_int, C.c_int64, gpp, C.c_int, C.c_int] + [vp] * 5
             l.mi_degensac_refit_tile.restype = C.c_int
             l.mi_degensac_refit_tile.argtypes = [C.c_int]
-        if hasattr(l, "mi_degensac_pose_lists_dev"):                      # (absent from older builds loaded through MI_DEGENSAC_LIB)
-            # pts, corr_offsets, keep, F, cams, n_cams, cam_idx, K, cap, cos_min, device[, stream] | pose, front, info, X, depth, cosang, cand,
-            # cand_front
-            vp = C.c_void_p
-            head = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int64, C.c_double, C.c_int]
-            l.mi_degensac_pose_lists_dev.restype = C.c_int
-            l.mi_degensac_pose_lists_dev.argtypes = head + [vp] + [vp] * 8
-            l.mi_degensac_pose_lists.restype = C.c_int
-            l.mi_degensac_pose_lists.argtypes = head + [vp] * 8
-            l.mi_degensac_pose_tile.restype = C.c_int
-            l.mi_degensac_pose_tile.argtypes = [C.c_int]
-        if hasattr(l, "mi_degensac_pose_h_lists_dev"):                    # (absent from older builds loaded through MI_DEGENSAC_LIB)
-            # pts, corr_offsets, keep, H, cams, n_cams, cam_idx, K, cap, cos_min, rotation_eps, device[, stream] | pose, front, info, normal,
-            # t_over_d, X, depth, cosang, cand, cand_normal, cand_front
-            vp = C.c_void_p
-            head = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int64, C.c_double, C.c_double, C.c_int]
-            l.mi_degensac_pose_h_lists_dev.restype = C.c_int
-            l.mi_degensac_pose_h_lists_dev.argtypes = head + [vp] + [vp] * 11
-            l.mi_degensac_pose_h_lists.restype = C.c_int
-            l.mi_degensac_pose_h_lists.argtypes = head + [vp] * 11
-            l.mi_degensac_pose_h_tile.restype = C.c_int
-            l.mi_degensac_pose_h_tile.argtypes = [C.c_int]
+        # pts, corr_offsets, keep, F | H, cams, n_cams, cam_idx, K, cap, cos_min[, rotation_eps], device[, stream] | pose, front, info[, normal,
+        # t_over_d], X, depth, cosang, cand[, cand_normal], cand_front
+        for name, scalars, n_out in (("pose", [C.c_double], 8), ("pose_h", [C.c_double, C.c_double], 11)):
+            if hasattr(l, "mi_degensac_%s_lists_dev" % name):             # (absent from older builds loaded through MI_DEGENSAC_LIB)
+                vp = C.c_void_p
+                head = [vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int64] + scalars + [C.c_int]
+                for fn, args in (("lists_dev", head + [vp] + [vp] * n_out), ("lists", head + [vp] * n_out), ("tile", [C.c_int])):
+                    f = getattr(l, "mi_degensac_%s_%s" % (name, fn))
+                    f.restype = C.c_int; f.argtypes = args
         if hasattr(l, "mi_degensac_pose_refine_lists_dev"):               # (absent from older builds loaded through MI_DEGENSAC_LIB)
             # pts, corr_offsets, keep, pose, cams, n_cams, cam_idx, K, cap, max_trials, ftol, device[, stream] | pose_out, cost, info, resid, F
             vp = C.c_void_p

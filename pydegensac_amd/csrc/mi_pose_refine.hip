@@ -22,6 +22,7 @@
 #include "mi_match_batch.h"
 #include "mi_host.h"
 #include "mi_dev_util.h"
+#include "mi_pose_dev.h"
 
 #define PR_T     256                      /* threads per workgroup */
 #define PR_NW    (PR_T / 64)
@@ -312,24 +313,14 @@ __global__ __launch_bounds__(PR_T) void pr_refine_kernel(pr_args a)
         if (tid == 0) {
             int st = MI_DEGENSAC_REFINE_TRUNCATED;
             if (whole) {
-                const int64_t i1 = a.cam_idx ? (int64_t)a.cam_idx[2 * (size_t)p] : 2 * (int64_t)p;
-                const int64_t i2 = a.cam_idx ? (int64_t)a.cam_idx[2 * (size_t)p + 1] : 2 * (int64_t)p + 1;
                 st = MI_DEGENSAC_REFINE_BAD_CAMERA;
-                if (i1 >= 0 && i1 < a.n_cams && i2 >= 0 && i2 < a.n_cams) {
-                    double cm[8];
+                if (mi_pose_cameras(a.cams, a.n_cams, a.cam_idx, p, S.cam)) {
+                    bool fin = true;
 #pragma unroll
-                    for (int i = 0; i < 4; i++) { cm[i] = a.cams[4 * (size_t)i1 + i]; cm[4 + i] = a.cams[4 * (size_t)i2 + i]; }
-#pragma unroll
-                    for (int i = 0; i < 8; i++) S.cam[i] = cm[i];
-                    if (mi_finite(cm[0]) && mi_finite(cm[1]) && mi_finite(cm[4]) && mi_finite(cm[5]) && cm[0] != 0.0 && cm[1] != 0.0 && cm[4] != 0.0 &&
-                        cm[5] != 0.0) {
-                        bool fin = true;
-#pragma unroll
-                        for (int i = 0; i < 12; i++) fin = fin && mi_finite(S.tri[i]);
-                        const double tt = (S.tri[9] * S.tri[9] + S.tri[10] * S.tri[10]) + S.tri[11] * S.tri[11];
-                        st = MI_DEGENSAC_REFINE_BAD_POSE;
-                        if (fin && tt > 0.0) { st = PR_RUNNING; pr_model(&S, S.tri); }
-                    }
+                    for (int i = 0; i < 12; i++) fin = fin && mi_finite(S.tri[i]);
+                    const double tt = (S.tri[9] * S.tri[9] + S.tri[10] * S.tri[10]) + S.tri[11] * S.tri[11];
+                    st = MI_DEGENSAC_REFINE_BAD_POSE;
+                    if (fin && tt > 0.0) { st = PR_RUNNING; pr_model(&S, S.tri); }
                 }
             }
             S.status = st; S.trials = 0; S.accepted = 0; S.lambda = 1e-3; S.cost0 = mi_nan(); S.go = 0;

@@ -1117,15 +1117,16 @@ def refit_correspondences(pts, corr_offsets, models, model="F", px_th=None, erro
 
 
 def check_pose_args(pts_shape, pts_dtype, off_shape, off_dtype, models_shape, models_dtype, cams1_shape, cams1_dtype, pairs=None, cams2=None, keep=None,
-                    min_parallax_deg=1.5):
+                    min_parallax_deg=1.5, model_text="one fundamental matrix per entry"):
     """The argument checks of relative_pose / relative_pose_tensors on shapes and dtype names (numpy or torch): pts float64 [cap, 4],
     corr_offsets int64 [K + 1], models float64 [K, 3, 3] (F); pairs, cams2 and keep are None or (shape, dtype): without pairs cams1 is
     float64 [K, 8] (one row of two cameras fx, fy, cx, cy per entry) and cams2 must be None; with pairs int32 / int64 [K, 2] cams1 is
     float64 [n_images, 4] and cams2 None (= cams1) or float64 [n_images_2, 4]; keep bool / uint8 [cap]; min_parallax_deg a number in
-    [0, 180].  Returns (K, cap, rows of cams1, rows of cams2 or None, cos_min); raises ValueError."""
+    [0, 180]; model_text is what the message about models calls them.  Returns (K, cap, rows of cams1, rows of cams2 or None, cos_min);
+    raises ValueError."""
     def check_models(K):
         if tuple(models_shape) != (K, 3, 3) or _dtype_name(models_dtype) != "float64":
-            raise ValueError("models should be float64 [K, 3, 3], one fundamental matrix per entry of corr_offsets")
+            raise ValueError("models should be float64 [K, 3, 3], " + model_text + " of corr_offsets")
     K, cap, _ = _check_list_inputs(pts_shape, pts_dtype, off_shape, off_dtype, check_models)
     if _dtype_name(cams1_dtype) != "float64":
         raise ValueError("cams1 should be float64")
@@ -1169,6 +1170,40 @@ def _cameras(c1, c2, pr, K, n1, n2):
     return np.ascontiguousarray(c1 if c2 is None else np.concatenate([c1, c2])), _cam_index(pr, n1, n2)
 
 
+def _pose_lists(from_h, pts, corr_offsets, models, cams1, pairs, cams2, keep, min_parallax_deg, with_points, with_candidates, device, rotation_eps=None,
+                driver_form=False):
+    """the numpy body of relative_pose (from_h False) and homography_pose (True: rotation_eps and driver_form, normal and t_over_d behind
+    info, cand_normal between cand and cand_front)"""
+    P = np.ascontiguousarray(np.asarray(pts)); o = np.ascontiguousarray(np.asarray(corr_offsets)); M = np.asarray(models)
+    c1 = np.asarray(cams1); c2 = None if cams2 is None else np.asarray(cams2)
+    pr = None if pairs is None else np.asarray(pairs)
+    kp = None if keep is None else np.asarray(keep)
+    shapes = (P.shape, P.dtype, o.shape, o.dtype, M.shape, M.dtype, c1.shape, c1.dtype, _sd(pr), _sd(c2), _sd(kp), min_parallax_deg)
+    if from_h:
+        K, cap, n1, n2, cos_min, eps = check_pose_h_args(*shapes, rotation_eps)
+    else:
+        K, cap, n1, n2, cos_min = check_pose_args(*shapes)
+    M = np.ascontiguousarray(_h_user_form(M) if from_h and driver_form else M, np.float64).reshape(K, 9)
+    cams, idx = _cameras(c1, c2, pr, K, n1, n2)
+    if kp is not None:
+        kp = np.ascontiguousarray(kp).view(np.uint8)
+    pose = np.zeros((K, 12)); front = np.zeros(cap, np.uint8); info = np.zeros((K, 5), np.int32)
+    plane = (np.zeros((K, 3)), np.zeros(K)) if from_h else ()         # normal, t_over_d
+    pts3 = (np.full((cap, 3), np.nan), np.full((cap, 2), np.nan), np.full(cap, np.nan)) if with_points else (None,) * 3          # X, depth, cosang
+    cand = np.zeros((K, 4, 12)) if with_candidates else None
+    cn = (np.zeros((K, 4, 3)) if with_candidates else None,) if from_h else ()
+    cf = np.zeros((K, 4), np.int32) if with_candidates else None
+    vp = _lib.vptr
+    entry = _lib.lib().mi_degensac_pose_h_lists if from_h else _lib.lib().mi_degensac_pose_lists
+    rc = entry(vp(P), vp(o), vp(kp), vp(M), vp(cams), len(cams), vp(idx), K, cap, cos_min, *((eps,) if from_h else ()), int(device), vp(pose), vp(front),
+               vp(info), *map(vp, plane), *map(vp, pts3), vp(cand), *map(vp, cn), vp(cf))
+    _lib.check_match(rc)
+    res = (pose[:, :9].reshape(K, 3, 3), pose[:, 9:], front.astype(bool), info) + plane
+    if with_points:
+        res += pts3
+    return res + (cand,) + cn + (cf,) if with_candidates else res
+
+
 def relative_pose(pts, corr_offsets, models, cams1, pairs=None, cams2=None, keep=None, min_parallax_deg=1.5, with_points=False, with_candidates=False,
                   device=0):
     """Relative pose and triangulation on exported correspondence lists (include/mi_degensac.h mi_degensac_pose_lists, blocking, numpy):
@@ -1180,41 +1215,15 @@ def relative_pose(pts, corr_offsets, models, cams1, pairs=None, cams2=None, keep
     Returns (R [K, 3, 3], t [K, 3], front [cap] bool, info [K, 5] int32 = (rows used, front rows of the chosen candidate, the largest
     front count of the other three, wide rows, _lib.POSE_* status)[, X [cap, 3] in the frame of camera 1, depth [cap, 2], cosang [cap]]
     [, cand [K, 4, 12], cand_front [K, 4]])."""
-    P = np.ascontiguousarray(np.asarray(pts)); o = np.ascontiguousarray(np.asarray(corr_offsets)); M = np.asarray(models)
-    c1 = np.asarray(cams1); c2 = None if cams2 is None else np.asarray(cams2)
-    pr = None if pairs is None else np.asarray(pairs)
-    kp = None if keep is None else np.asarray(keep)
-    K, cap, n1, n2, cos_min = check_pose_args(P.shape, P.dtype, o.shape, o.dtype, M.shape, M.dtype, c1.shape, c1.dtype, _sd(pr), _sd(c2), _sd(kp),
-                                              min_parallax_deg)
-    F = np.ascontiguousarray(M, np.float64).reshape(K, 9)
-    cams, idx = _cameras(c1, c2, pr, K, n1, n2)
-    if kp is not None:
-        kp = np.ascontiguousarray(kp).view(np.uint8)
-    pose = np.zeros((K, 12)); front = np.zeros(cap, np.uint8); info = np.zeros((K, 5), np.int32)
-    X = np.full((cap, 3), np.nan) if with_points else None
-    depth = np.full((cap, 2), np.nan) if with_points else None
-    cosang = np.full(cap, np.nan) if with_points else None
-    cand = np.zeros((K, 4, 12)) if with_candidates else None
-    cf = np.zeros((K, 4), np.int32) if with_candidates else None
-    vp = _lib.vptr
-    rc = _lib.lib().mi_degensac_pose_lists(vp(P), vp(o), vp(kp), vp(F), vp(cams), len(cams), vp(idx), K, cap, cos_min, int(device), vp(pose),
-                                           vp(front), vp(info), vp(X), vp(depth), vp(cosang), vp(cand), vp(cf))
-    _lib.check_match(rc)
-    res = (pose[:, :9].reshape(K, 3, 3), pose[:, 9:], front.astype(bool), info)
-    if with_points:
-        res += (X, depth, cosang)
-    return res + (cand, cf) if with_candidates else res
+    return _pose_lists(False, pts, corr_offsets, models, cams1, pairs, cams2, keep, min_parallax_deg, with_points, with_candidates, device)
 
 
 def check_pose_h_args(pts_shape, pts_dtype, off_shape, off_dtype, models_shape, models_dtype, cams1_shape, cams1_dtype, pairs=None, cams2=None,
                       keep=None, min_parallax_deg=1.5, rotation_eps=1e-3):
     """The argument checks of homography_pose / homography_pose_tensors: those of check_pose_args (models are homographies here), and
     rotation_eps a number >= 0.  Returns (K, cap, rows of cams1, rows of cams2 or None, cos_min, rotation_eps); raises ValueError."""
-    try:
-        res = check_pose_args(pts_shape, pts_dtype, off_shape, off_dtype, models_shape, models_dtype, cams1_shape, cams1_dtype, pairs, cams2, keep,
-                              min_parallax_deg)
-    except ValueError as err:
-        raise ValueError(str(err).replace("one fundamental matrix per entry", "one homography per entry")) from None
+    res = check_pose_args(pts_shape, pts_dtype, off_shape, off_dtype, models_shape, models_dtype, cams1_shape, cams1_dtype, pairs, cams2, keep,
+                          min_parallax_deg, "one homography per entry")
     return res + (_number(rotation_eps, "rotation_eps should be a number >= 0", 0.0),)
 
 
@@ -1231,31 +1240,8 @@ def homography_pose(pts, corr_offsets, models, cams1, pairs=None, cams2=None, ke
     front count of the other three, wide rows, _lib.POSE_* status), normal [K, 3] = the unit plane normal in the frame of camera 1,
     t_over_d [K] = baseline over plane distance[, X [cap, 3], depth [cap, 2], cosang [cap]][, cand [K, 4, 12], cand_normal [K, 4, 3],
     cand_front [K, 4]]).  The meaning is relative_pose's: X2 = R X1 + t, |t| = 1."""
-    P = np.ascontiguousarray(np.asarray(pts)); o = np.ascontiguousarray(np.asarray(corr_offsets)); M = np.asarray(models)
-    c1 = np.asarray(cams1); c2 = None if cams2 is None else np.asarray(cams2)
-    pr = None if pairs is None else np.asarray(pairs)
-    kp = None if keep is None else np.asarray(keep)
-    K, cap, n1, n2, cos_min, eps = check_pose_h_args(P.shape, P.dtype, o.shape, o.dtype, M.shape, M.dtype, c1.shape, c1.dtype, _sd(pr), _sd(c2), _sd(kp),
-                                                     min_parallax_deg, rotation_eps)
-    H = np.ascontiguousarray(_h_user_form(M) if driver_form else M, np.float64).reshape(K, 9)
-    cams, idx = _cameras(c1, c2, pr, K, n1, n2)
-    if kp is not None:
-        kp = np.ascontiguousarray(kp).view(np.uint8)
-    pose = np.zeros((K, 12)); front = np.zeros(cap, np.uint8); info = np.zeros((K, 5), np.int32); normal = np.zeros((K, 3)); tod = np.zeros(K)
-    X = np.full((cap, 3), np.nan) if with_points else None
-    depth = np.full((cap, 2), np.nan) if with_points else None
-    cosang = np.full(cap, np.nan) if with_points else None
-    cand = np.zeros((K, 4, 12)) if with_candidates else None
-    cn = np.zeros((K, 4, 3)) if with_candidates else None
-    cf = np.zeros((K, 4), np.int32) if with_candidates else None
-    vp = _lib.vptr
-    rc = _lib.lib().mi_degensac_pose_h_lists(vp(P), vp(o), vp(kp), vp(H), vp(cams), len(cams), vp(idx), K, cap, cos_min, eps, int(device), vp(pose),
-                                             vp(front), vp(info), vp(normal), vp(tod), vp(X), vp(depth), vp(cosang), vp(cand), vp(cn), vp(cf))
-    _lib.check_match(rc)
-    res = (pose[:, :9].reshape(K, 3, 3), pose[:, 9:], front.astype(bool), info, normal, tod)
-    if with_points:
-        res += (X, depth, cosang)
-    return res + (cand, cn, cf) if with_candidates else res
+    return _pose_lists(True, pts, corr_offsets, models, cams1, pairs, cams2, keep, min_parallax_deg, with_points, with_candidates, device, rotation_eps,
+                       driver_form)
 
 
 def check_select_args(cls_shape, K_f, K_h):

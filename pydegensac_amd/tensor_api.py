@@ -859,6 +859,49 @@ def refit_correspondences_tensors(pts, corr_offsets, models, model="F", px_th=No
     return res + (resid[:cap],) if with_resid else res
 
 
+def _pose_lists_tensors(from_h, pts, corr_offsets, models, cams1, pairs, cams2, keep, min_parallax_deg, with_points, with_candidates, rotation_eps=None,
+                        driver_form=False):
+    """the tensor body of relative_pose_tensors (from_h False) and homography_pose_tensors (True: rotation_eps and driver_form, normal and
+    t_over_d behind info, cand_normal between cand and cand_front)"""
+    import torch
+    from . import matcher
+    opt = [t for t in (pairs, cams2, keep) if t is not None]
+    names = "pts, corr_offsets, models, cams1 (and pairs, cams2, keep)"
+    ts = [pts, corr_offsets, models, cams1] + opt
+    _require(names, ts)
+    shapes = (tuple(pts.shape), pts.dtype, tuple(corr_offsets.shape), corr_offsets.dtype, tuple(models.shape), models.dtype, tuple(cams1.shape),
+              cams1.dtype, _sd(pairs), _sd(cams2), _sd(keep), min_parallax_deg)
+    if from_h:
+        K, cap, n1, n2, cos_min, eps = matcher.check_pose_h_args(*shapes, rotation_eps)
+    else:
+        K, cap, n1, n2, cos_min = matcher.check_pose_args(*shapes)
+    _require(names, ts, "cuda")
+    dev = pts.device
+    P = pts.contiguous(); o = corr_offsets.contiguous()
+    M = (_h_user_form(models.contiguous()) if from_h and driver_form else models).contiguous()
+    cams, n_cams, idx = _cameras(cams1, cams2, pairs, K, n1, n2)
+    kp = None if keep is None else keep.contiguous().view(torch.uint8)
+    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
+    rows = max(cap, 1)                                                # (an address also where cap == 0)
+    pose = f64(K, 12); front = torch.empty(rows, dtype=torch.uint8, device=dev); info = torch.empty((K, 5), dtype=torch.int32, device=dev)
+    plane = (f64(K, 3), f64(K)) if from_h else ()                     # normal, t_over_d
+    pts3 = (f64(rows, 3), f64(rows, 2), f64(rows)) if with_points else (None,) * 3          # X, depth, cosang
+    cand = f64(K, 4, 12) if with_candidates else None
+    cn = (f64(K, 4, 3) if with_candidates else None,) if from_h else ()
+    cf = torch.empty((K, 4), dtype=torch.int32, device=dev) if with_candidates else None
+    di, stream, sp = _stream(dev)
+    p = _p
+    entry = _lib.lib().mi_degensac_pose_h_lists_dev if from_h else _lib.lib().mi_degensac_pose_lists_dev
+    rc = entry(p(P), p(o), p(kp), p(M), p(cams), n_cams, p(idx), K, cap, cos_min, *((eps,) if from_h else ()), di, sp, p(pose), p(front), p(info),
+               *map(p, plane), *map(p, pts3), p(cand), *map(p, cn), p(cf))
+    _lib.check_match(rc)
+    _keep_alive(stream, P, o, M, cams, idx, kp)
+    res = (pose[:, :9].reshape(K, 3, 3), pose[:, 9:], front[:cap].view(torch.bool), info) + plane
+    if with_points:
+        res += tuple(x[:cap] for x in pts3)
+    return res + (cand,) + cn + (cf,) if with_candidates else res
+
+
 def relative_pose_tensors(pts, corr_offsets, models, cams1, pairs=None, cams2=None, keep=None, min_parallax_deg=1.5, with_points=False,
                           with_candidates=False):
     """Relative pose and triangulation on exported correspondence lists, on the device and without a host synchronisation
@@ -875,37 +918,7 @@ def relative_pose_tensors(pts, corr_offsets, models, cams1, pairs=None, cams2=No
     front count of the other three, wide rows, _lib.POSE_* status)[, X [cap, 3] in the frame of camera 1, depth [cap, 2] along the two
     rays, cosang [cap]][, cand [K, 4, 12], cand_front [K, 4]]) on the device, asynchronous on the current stream.  Rows that are not
     used, and rows of an entry without a pose (status != POSE_OK: R and t are zeros), keep front = False and NaN."""
-    import torch
-    from . import matcher
-    opt = [t for t in (pairs, cams2, keep) if t is not None]
-    names = "pts, corr_offsets, models, cams1 (and pairs, cams2, keep)"
-    ts = [pts, corr_offsets, models, cams1] + opt
-    _require(names, ts)
-    K, cap, n1, n2, cos_min = matcher.check_pose_args(tuple(pts.shape), pts.dtype, tuple(corr_offsets.shape), corr_offsets.dtype, tuple(models.shape),
-                                                      models.dtype, tuple(cams1.shape), cams1.dtype, _sd(pairs), _sd(cams2), _sd(keep), min_parallax_deg)
-    _require(names, ts, "cuda")
-    dev = pts.device
-    P = pts.contiguous(); o = corr_offsets.contiguous(); F = models.contiguous()
-    cams, n_cams, idx = _cameras(cams1, cams2, pairs, K, n1, n2)
-    kp = None if keep is None else keep.contiguous().view(torch.uint8)
-    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
-    rows = max(cap, 1)                                                # (an address also where cap == 0)
-    pose = f64(K, 12); front = torch.empty(rows, dtype=torch.uint8, device=dev); info = torch.empty((K, 5), dtype=torch.int32, device=dev)
-    X = f64(rows, 3) if with_points else None
-    depth = f64(rows, 2) if with_points else None
-    cosang = f64(rows) if with_points else None
-    cand = f64(K, 4, 12) if with_candidates else None
-    cf = torch.empty((K, 4), dtype=torch.int32, device=dev) if with_candidates else None
-    di, stream, sp = _stream(dev)
-    p = _p
-    rc = _lib.lib().mi_degensac_pose_lists_dev(p(P), p(o), p(kp), p(F), p(cams), n_cams, p(idx), K, cap, cos_min, di, sp, p(pose), p(front), p(info),
-                                               p(X), p(depth), p(cosang), p(cand), p(cf))
-    _lib.check_match(rc)
-    _keep_alive(stream, P, o, F, cams, idx, kp)
-    res = (pose[:, :9].reshape(K, 3, 3), pose[:, 9:], front[:cap].view(torch.bool), info)
-    if with_points:
-        res += (X[:cap], depth[:cap], cosang[:cap])
-    return res + (cand, cf) if with_candidates else res
+    return _pose_lists_tensors(False, pts, corr_offsets, models, cams1, pairs, cams2, keep, min_parallax_deg, with_points, with_candidates)
 
 
 def homography_pose_tensors(pts, corr_offsets, models, cams1, pairs=None, cams2=None, keep=None, min_parallax_deg=1.5, rotation_eps=1e-3,
@@ -923,41 +936,8 @@ def homography_pose_tensors(pts, corr_offsets, models, cams1, pairs=None, cams2=
     when there is none), t_over_d [K] = baseline over plane distance[, X [cap, 3], depth [cap, 2], cosang [cap]][, cand [K, 4, 12],
     cand_normal [K, 4, 3], cand_front [K, 4]]) on the device, asynchronous on the current stream.  The meaning is the pose call's: X2 = R
     X1 + t, |t| = 1; R, t, front and info go into refine_pose_tensors and average_rotations_tensors as its results do."""
-    import torch
-    from . import matcher
-    opt = [t for t in (pairs, cams2, keep) if t is not None]
-    names = "pts, corr_offsets, models, cams1 (and pairs, cams2, keep)"
-    ts = [pts, corr_offsets, models, cams1] + opt
-    _require(names, ts)
-    K, cap, n1, n2, cos_min, eps = matcher.check_pose_h_args(tuple(pts.shape), pts.dtype, tuple(corr_offsets.shape), corr_offsets.dtype,
-                                                             tuple(models.shape), models.dtype, tuple(cams1.shape), cams1.dtype, _sd(pairs), _sd(cams2),
-                                                             _sd(keep), min_parallax_deg, rotation_eps)
-    _require(names, ts, "cuda")
-    dev = pts.device
-    P = pts.contiguous(); o = corr_offsets.contiguous()
-    H = (_h_user_form(models.contiguous()) if driver_form else models).contiguous()
-    cams, n_cams, idx = _cameras(cams1, cams2, pairs, K, n1, n2)
-    kp = None if keep is None else keep.contiguous().view(torch.uint8)
-    f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)          # noqa: E731
-    rows = max(cap, 1)                                                # (an address also where cap == 0)
-    pose = f64(K, 12); front = torch.empty(rows, dtype=torch.uint8, device=dev); info = torch.empty((K, 5), dtype=torch.int32, device=dev)
-    normal = f64(K, 3); tod = f64(K)
-    X = f64(rows, 3) if with_points else None
-    depth = f64(rows, 2) if with_points else None
-    cosang = f64(rows) if with_points else None
-    cand = f64(K, 4, 12) if with_candidates else None
-    cn = f64(K, 4, 3) if with_candidates else None
-    cf = torch.empty((K, 4), dtype=torch.int32, device=dev) if with_candidates else None
-    di, stream, sp = _stream(dev)
-    p = _p
-    rc = _lib.lib().mi_degensac_pose_h_lists_dev(p(P), p(o), p(kp), p(H), p(cams), n_cams, p(idx), K, cap, cos_min, eps, di, sp, p(pose), p(front),
-                                                 p(info), p(normal), p(tod), p(X), p(depth), p(cosang), p(cand), p(cn), p(cf))
-    _lib.check_match(rc)
-    _keep_alive(stream, P, o, H, cams, idx, kp)
-    res = (pose[:, :9].reshape(K, 3, 3), pose[:, 9:], front[:cap].view(torch.bool), info, normal, tod)
-    if with_points:
-        res += (X[:cap], depth[:cap], cosang[:cap])
-    return res + (cand, cn, cf) if with_candidates else res
+    return _pose_lists_tensors(True, pts, corr_offsets, models, cams1, pairs, cams2, keep, min_parallax_deg, with_points, with_candidates, rotation_eps,
+                               driver_form)
 
 
 def select_pose_tensors(cls, pose_f, pose_h, corr_offsets=None):

@@ -21,25 +21,13 @@ from tests import pose_ref as R
 OK, BAD_MODEL, BAD_CAMERA, TRUNCATED, EMPTY, ROTATION = range(6)
 TOL = R.TOL
 ROT_EPS = 1e-3
-SWEEPS = 6
 f8 = np.float64
+jacobi, _det, _dot, _cross = R.jacobi, R._det, R._dot, R._cross          # one restatement of the Jacobi rule for both calls
 
 
 def h_from_pose(Rm, t, n, d, cam1, cam2):
     """H = K2 (R + t n^T / d) K1^-1 of the plane n . X = d in the frame of camera 1 (x2 ~ H x1)"""
     return R.kmat(cam2) @ (np.asarray(Rm) + np.outer(t, n) / d) @ np.linalg.inv(R.kmat(cam1))
-
-
-def _det(M):
-    return (M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6])) + M[2] * (M[3] * M[7] - M[4] * M[6])
-
-
-def _dot(x, y):
-    return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]
-
-
-def _cross(x, y):
-    return [x[1] * y[2] - x[2] * y[1], x[2] * y[0] - x[0] * y[2], x[0] * y[1] - x[1] * y[0]]
 
 
 def normalised_g(H, cam1, cam2):
@@ -63,29 +51,6 @@ def normalised_g(H, cam1, cam2):
         if not m > 0:
             return None, BAD_MODEL
         return [x / m for x in G], OK
-
-
-def jacobi(A, sort=True):
-    """step 2: the one-sided Jacobi rule of the pose call -> (sigma [3], v [3][3] columns, b [3][3] columns), sorted descending"""
-    v = [[f8(1), f8(0), f8(0)], [f8(0), f8(1), f8(0)], [f8(0), f8(0), f8(1)]]
-    b = [[A[0], A[3], A[6]], [A[1], A[4], A[7]], [A[2], A[5], A[8]]]
-    with np.errstate(all="ignore"):
-        for _ in range(SWEEPS):
-            for i, j in ((0, 1), (0, 2), (1, 2)):
-                al, be, ga = _dot(b[i], b[i]), _dot(b[j], b[j]), _dot(b[i], b[j])
-                if ga != 0:
-                    z = (be - al) / (f8(2.0) * ga)
-                    t = (f8(1.0) if z >= 0 else f8(-1.0)) / (abs(z) + np.sqrt(f8(1.0) + z * z))
-                    c = f8(1.0) / np.sqrt(f8(1.0) + t * t); s = c * t
-                    for k in range(3):
-                        x, y, p, q = b[i][k], b[j][k], v[i][k], v[j][k]
-                        b[i][k] = c * x - s * y; b[j][k] = s * x + c * y; v[i][k] = c * p - s * q; v[j][k] = s * p + c * q
-        sg = [np.sqrt(_dot(x, x)) for x in b]
-    if sort:
-        for i, j in ((0, 1), (1, 2), (0, 1)):
-            if sg[j] > sg[i]:
-                sg[i], sg[j] = sg[j], sg[i]; v[i], v[j] = v[j], v[i]; b[i], b[j] = b[j], b[i]
-    return sg, v, b
 
 
 def decompose(H, cam1, cam2, rotation_eps=ROT_EPS, broken=None):

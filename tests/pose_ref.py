@@ -1,11 +1,16 @@
-"""The relative pose on exported correspondence lists (include/mi_degensac.h mi_degensac_pose_lists*) restated in numpy, in two parts.
+"""The relative pose on exported correspondence lists (include/mi_degensac.h mi_degensac_pose_lists*) restated in numpy, in three parts.
+
+decompose: the header's rule from F and two cameras to the four candidates, one numpy float64 operation per written operator in the header's
+order (numpy contracts nothing; + - * / and sqrt are correctly rounded on both sides), so the device's candidates can be demanded bit for
+bit.  Its Jacobi rule (jacobi) is the one that tests/pose_h_ref.py decomposes the calibrated homography with.
 
 from_candidates: the per-row rule and the counts GIVEN the four candidates of every entry, in the header's operation order.  Every line
 below is one numpy ufunc on float64 (arrays over the rows of an entry: an elementwise ufunc is the scalar IEEE operation per element,
 numpy contracts nothing), every sum of three terms is (first + second) + third, so the results can be demanded bit for bit.
 
 candidates_svd: an independent decomposition of E = K2^T F K1 with numpy.linalg.svd (Hartley & Zisserman 9.6.2), in no particular order
-and with none of the header's operation orders: the device's four candidates are compared with it as a set, to 1e-9.
+and with none of the header's operation orders: the device's four candidates are compared with it as a set, to 1e-9.  A Jacobi rule
+that sweeps its column pairs in another order passes that comparison and fails the bitwise one (broken="order").
 
 The scenes of test_gpu_pose.py live here (gpu_scenes) so that test_pose_cpu.py can state their margin without a device."""
 import functools
@@ -16,6 +21,8 @@ from pydegensac_amd import synthetic as syn
 
 OK, BAD_MODEL, BAD_CAMERA, TRUNCATED, EMPTY = range(5)
 TOL = 1e-9                                                             # the project's model tolerance
+SWEEPS = 6
+f8 = np.float64
 
 
 def cos_min(deg):
@@ -36,6 +43,105 @@ def relative(poses, i, j):
     (Ri, ti), (Rj, tj) = poses[i], poses[j]
     R = Rj @ Ri.T; t = tj - R @ ti
     return R, t / np.linalg.norm(t)
+
+
+# ---- part 0: the decomposition, operation for operation ----
+def _det(M):
+    return (M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6])) + M[2] * (M[3] * M[7] - M[4] * M[6])
+
+
+def _dot(x, y):
+    return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]
+
+
+def _cross(x, y):
+    return [x[1] * y[2] - x[2] * y[1], x[2] * y[0] - x[0] * y[2], x[0] * y[1] - x[1] * y[0]]
+
+
+def jacobi(A, sort=True, broken=None):
+    """the one-sided Jacobi rule of the pose calls on nine float64 -> (sigma [3], v [3][3] columns, b [3][3] columns), sorted descending.
+    broken="order": the column pairs of a sweep as (0 1) (1 2) (0 2), which converges as well and rounds differently."""
+    v = [[f8(1), f8(0), f8(0)], [f8(0), f8(1), f8(0)], [f8(0), f8(0), f8(1)]]
+    b = [[A[0], A[3], A[6]], [A[1], A[4], A[7]], [A[2], A[5], A[8]]]
+    with np.errstate(all="ignore"):
+        for _ in range(SWEEPS):
+            for i, j in ((0, 1), (1, 2), (0, 2)) if broken == "order" else ((0, 1), (0, 2), (1, 2)):
+                al, be, ga = _dot(b[i], b[i]), _dot(b[j], b[j]), _dot(b[i], b[j])
+                if ga != 0:
+                    z = (be - al) / (f8(2.0) * ga)
+                    t = (f8(1.0) if z >= 0 else f8(-1.0)) / (abs(z) + np.sqrt(f8(1.0) + z * z))
+                    c = f8(1.0) / np.sqrt(f8(1.0) + t * t); s = c * t
+                    for k in range(3):
+                        x, y, p, q = b[i][k], b[j][k], v[i][k], v[j][k]
+                        b[i][k] = c * x - s * y; b[j][k] = s * x + c * y; v[i][k] = c * p - s * q; v[j][k] = s * p + c * q
+        sg = [np.sqrt(_dot(x, x)) for x in b]
+    if sort:
+        for i, j in ((0, 1), (1, 2), (0, 1)):
+            if sg[j] > sg[i]:
+                sg[i], sg[j] = sg[j], sg[i]; v[i], v[j] = v[j], v[i]; b[i], b[j] = b[j], b[i]
+    return sg, v, b
+
+
+def decompose(F, cam1, cam2, broken=None):
+    """The header's rule from F and two cameras (focal lengths finite and not zero) up to the candidates: dict(status = OK | BAD_MODEL,
+    cand [4, 12], c2 [4, 3], rotated = whether any Jacobi rotation was applied, det = the determinants of Ra and Rb before their flip).
+    BAD_MODEL leaves zeros.  broken: "order" goes to jacobi."""
+    out = dict(status=BAD_MODEL, cand=np.zeros((4, 12)), c2=np.zeros((4, 3)), rotated=False, det=(f8(0), f8(0)))
+    F = [f8(x) for x in np.asarray(F, np.float64).reshape(9)]
+    fx1, fy1, cx1, cy1 = (f8(x) for x in cam1); fx2, fy2, cx2, cy2 = (f8(x) for x in cam2)
+    with np.errstate(all="ignore"):
+        G = [None] * 9; E = [None] * 9
+        for i in range(3):
+            G[3 * i] = F[3 * i] * fx1; G[3 * i + 1] = F[3 * i + 1] * fy1
+            G[3 * i + 2] = (F[3 * i] * cx1 + F[3 * i + 1] * cy1) + F[3 * i + 2]
+        for j in range(3):
+            E[j] = fx2 * G[j]; E[3 + j] = fy2 * G[3 + j]
+            E[6 + j] = (cx2 * G[j] + cy2 * G[3 + j]) + G[6 + j]
+        m = f8(0.0)
+        for x in E:
+            if not np.isfinite(x):
+                return out
+            if abs(x) > m:
+                m = abs(x)
+        if not m > 0:
+            return out
+        A = [x / m for x in E]
+        sg, v, b = jacobi(A, broken=broken)
+        cols = [[A[i], A[3 + i], A[6 + i]] for i in range(3)]          # (columns that are orthogonal as given stay as they are: ga == 0 throughout)
+        out["rotated"] = any(_dot(cols[i], cols[j]) != 0 for i, j in ((0, 1), (0, 2), (1, 2)))
+        if not sg[1] > 0:
+            return out
+        u1 = [b[0][r] / sg[0] for r in range(3)]; u2 = [b[1][r] / sg[1] for r in range(3)]
+        t = _cross(u1, u2)
+        nrm = np.sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2])
+        t = [x / nrm for x in t]
+        Ra = [(u2[r] * v[0][c] - u1[r] * v[1][c]) + t[r] * v[2][c] for r in range(3) for c in range(3)]
+        Rb = [(u1[r] * v[1][c] - u2[r] * v[0][c]) + t[r] * v[2][c] for r in range(3) for c in range(3)]
+        out["det"] = (_det(Ra), _det(Rb))
+        if out["det"][0] < 0:
+            Ra = [-x for x in Ra]
+        if out["det"][1] < 0:
+            Rb = [-x for x in Rb]
+        if not (np.isfinite(t).all() and np.isfinite(Ra).all() and np.isfinite(Rb).all()):
+            return out
+        for q in range(4):
+            Rm = Ra if q < 2 else Rb; sgn = f8(-1.0) if q & 1 else f8(1.0)
+            tq = [sgn * x for x in t]
+            out["cand"][q, :9] = Rm; out["cand"][q, 9:] = tq
+            out["c2"][q] = [-((Rm[j] * tq[0] + Rm[3 + j] * tq[1]) + Rm[6 + j] * tq[2]) for j in range(3)]
+    out["status"] = OK
+    return out
+
+
+def decompose_scene(sc, broken=None):
+    """decompose on every entry of a scene -> list of its dicts; None where the entry's range or cameras are refused (the device writes
+    zeros there as it does for BAD_MODEL)"""
+    out = []
+    for p in range(len(sc["off"]) - 1):
+        i1, i2 = (2 * p, 2 * p + 1) if sc["idx"] is None else (int(sc["idx"][p, 0]), int(sc["idx"][p, 1]))
+        st = entry_status(sc["F"][p], sc["cams"], i1, i2, int(sc["off"][p]), int(sc["off"][p + 1]), len(sc["pts"]))
+        out.append(None if st in (TRUNCATED, BAD_CAMERA) else decompose(sc["F"][p], sc["cams"][i1], sc["cams"][i2], broken))
+    return out
 
 
 # ---- part 2: the independent decomposition ----
@@ -309,3 +415,26 @@ def exact_scene():
     sc = _scene([(rows, F, one, one)], 1.5)
     sc["fragile"] = True                                             # counts hang on exact zeros: only the device's own candidates state them
     return sc
+
+
+EDGES = ("rank2", "equal_sigma", "diagonal", "negative_det", "tiny", "huge", "rank1")
+
+
+@functools.lru_cache(maxsize=None)
+def edge_scene():
+    """The edges of the decomposition, one entry and one row each, identity cameras (E is F to the bit) but for the two scaled models:
+    an exact rank-2 E of small integers (largest entry 8: A = E / m is exact); sigma1 == sigma2 exactly, E = [t]x R of integers from a
+    rational rotation; a diagonal E, whose columns are orthogonal as given (ga == 0 skips every rotation); the second one with a column
+    halved, whose sigma sort exchanges columns of V an odd number of times, so that Ra has determinant -1 before its flip; a pose's F under
+    two real cameras times 1e-150 and times 1e150; a rank-1 E whose columns are b, b / 2, b / 4 (the first rotation of pair (0 1) has z =
+    -3 / 4, t = -1 / 2, s = -c / 2 exactly, so s b + c (b / 2) is 0 to the bit, and so on: sigma2 == 0), BAD_MODEL with zeros.
+    test_pose_cpu.py asserts each of these properties on the restatement."""
+    rng = np.random.default_rng(23)
+    one = np.array([1.0, 1.0, 0.0, 0.0])
+    Rq = np.array([[1.0, -4, 8], [8, 4, 1], [-4, 7, 4]]); Rq = Rq * np.sign(np.linalg.det(Rq))          # 9 x a rotation
+    tx = np.array([[0.0, -2, 2], [2, 0, -1], [-2, 1, 0]])                                                # [t]x of t = (1, 2, 2)
+    _, F, _, _, ci, cj = pair_rows(1, 6, 3, 23)
+    models = dict(rank2=(np.array([[1.0, 2, 4], [2, -1, 4], [3, 1, 8]]), one, one), equal_sigma=(tx @ Rq, one, one),
+                  diagonal=(np.diag([1.0, 1.0, 0.0]), one, one), negative_det=((tx @ Rq) * np.array([0.5, 1.0, 1.0]), one, one),
+                  tiny=(F * 1e-150, ci, cj), huge=(F * 1e150, ci, cj), rank1=(np.outer([1.0, 2, 4], [1.0, 0.5, 0.25]), one, one))
+    return _scene([(rng.uniform(-0.5, 0.5, (1, 4)), *models[k]) for k in EDGES], 1.5)

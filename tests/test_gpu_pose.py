@@ -1,6 +1,6 @@
 """GPU: relative pose and triangulation on exported correspondence lists (include/mi_degensac.h mi_degensac_pose_lists*, csrc/mi_pose.hip)
 against tests/pose_ref.py.  The decomposition is compared with numpy's SVD: the device's four candidates equal numpy's four as a set, to
-1e-9.  Everything behind the candidates is demanded BIT FOR BIT: from the device's own candidates and cameras the restatement gives
+1e-9, and BIT FOR BIT with the restatement of the header's rule (pose_ref.decompose).  Everything behind the candidates is demanded BIT FOR BIT: from the device's own candidates and cameras the restatement gives
 cand_front, front, info, X, depth and cosang, with guard elements around every output.  The chosen pose is compared with the restatement
 on numpy's candidates to 1e-9 wherever front > runner-up (test_pose_cpu.py asserts that for every entry of these scenes that has a pose and
 at least 8 used rows).  Entry lengths sit at the edges of a wave (63 .. 65), of a load of the workgroup (255 .. 257) and of a step of the row
@@ -124,6 +124,24 @@ def test_pose_equals_restatement(torch, name):
     sc = R.gpu_scenes()[name]
     got, _ = _call(torch, sc)
     _compare(sc, got)
+
+
+@pytest.mark.parametrize("name", SCENES + ["decomposition_edges"])
+def test_candidates_equal_restatement(torch, name):
+    """the four candidates BIT FOR BIT against pose_ref.decompose, the header's decomposition operation for operation (numpy's SVD above
+    holds them to 1e-9 only, which a Jacobi rule in another operation order passes: test_pose_cpu.py shows one); every scene, and the
+    edges of the decomposition with one row per entry: rank 2 exactly, sigma1 == sigma2, columns orthogonal as given, a negative
+    determinant before the flip, F x 1e-150 and x 1e150, and rank 1 (BAD_MODEL, zeros)"""
+    sc = R.edge_scene() if name == "decomposition_edges" else R.gpu_scenes()[name]
+    K = len(sc["off"]) - 1
+    got, _ = _call(torch, sc)
+    want = R.decompose_scene(sc)
+    cand = np.array([np.zeros((4, 12)) if d is None else d["cand"] for d in want])
+    assert _bits(got["cand"].reshape(K, 4, 12), cand), [p for p in range(K) if not _bits(got["cand"].reshape(K, 4, 12)[p], cand[p])][:8]
+    model = np.array([d is not None and d["status"] == R.OK for d in want])
+    assert np.array_equal(np.isin(got["info"][:, 4], (R.OK, R.EMPTY)), model)
+    if name == "decomposition_edges":
+        assert got["info"][:, 4].tolist() == [R.OK] * 6 + [R.BAD_MODEL] and not got["cand"][6].any() and got["cand"][:6].any(axis=1).all()
 
 
 def test_every_status_and_the_fills(torch):

@@ -189,6 +189,63 @@ def test_broken_restatements_are_rejected():
     assert np.abs(R.reference(sc)["pose"][0, 9:] - tg).max() <= R.TOL
 
 
+def _all_scenes():
+    return dict(R.gpu_scenes(), decomposition_edges=R.edge_scene())
+
+
+def test_decomposition_restated_agrees_with_numpys_svd():
+    """pose_ref.decompose, which test_gpu_pose.py demands bit for bit, on every entry of its scenes: the same four candidates as
+    numpy's SVD to TOL, the header's slot order, c2 = -R^T t; BAD_MODEL exactly where the independent status says so or the rank is below 2"""
+    n = 0
+    for name, sc in _all_scenes().items():
+        for p, (d, s) in enumerate(zip(R.decompose_scene(sc), R.svd_candidates_of(sc))):
+            if d is None:
+                continue
+            if d["status"] != R.OK:
+                assert not d["cand"].any() and (s is None or (name, p) == ("decomposition_edges", 6)), (name, p)
+                continue
+            n += 1
+            assert s is not None and R.same_set(d["cand"], s), (name, p)
+            c = d["cand"]
+            assert np.array_equal(c[0, :9], c[1, :9]) and np.array_equal(c[2, :9], c[3, :9]) and np.array_equal(c[0, 9:], -c[1, 9:])
+            assert np.array_equal(c[0, 9:], c[2, 9:]) and np.array_equal(c[2, 9:], -c[3, 9:])
+            for q in range(4):
+                assert np.abs(d["c2"][q] + c[q, :9].reshape(3, 3).T @ c[q, 9:]).max() < 1e-15
+    assert n > 350
+
+
+def test_decomposition_edges_are_what_they_claim():
+    sc = R.edge_scene(); dec = dict(zip(R.EDGES, R.decompose_scene(sc)))
+    assert np.diff(sc["off"]).tolist() == [1] * 7 and len(R.EDGES) == 7
+    E = {k: sc["F"][i].reshape(3, 3) for i, k in enumerate(R.EDGES)}
+    assert [dec[k]["status"] for k in R.EDGES] == [R.OK] * 6 + [R.BAD_MODEL] and not dec["rank1"]["cand"].any()
+    assert round(np.linalg.det(E["rank2"])) == 0 and np.abs(E["rank2"]).max() == 8 and np.array_equal(E["rank2"], np.round(E["rank2"]))
+    assert np.array_equal(E["equal_sigma"] @ E["equal_sigma"].T @ E["equal_sigma"], 729.0 * E["equal_sigma"])          # E E^T E = sigma^2 E, in integers
+    assert not dec["diagonal"]["rotated"] and all(dec[k]["rotated"] for k in R.EDGES if k != "diagonal")
+    assert dec["negative_det"]["det"][0] < 0 and dec["tiny"]["det"][0] > 0
+    assert np.abs(sc["F"][4]).max() < 1e-150 and np.abs(sc["F"][5]).max() > 1e140
+    assert dec["tiny"]["cand"].tobytes() != dec["huge"]["cand"].tobytes() and R.same_set(dec["tiny"]["cand"], dec["huge"]["cand"])
+    assert np.linalg.matrix_rank(E["rank1"]) == 1 and E["rank1"].all()
+
+
+def test_reordered_jacobi_is_rejected_by_the_bits_only():
+    """a Jacobi rule that takes the column pairs of a sweep as (0 1) (1 2) (0 2) converges as the header's does: on every entry of every
+    scene its candidates are numpy's to TOL, which is all that the comparison with the SVD asks.  The bitwise comparison of
+    test_candidates_equal_restatement rejects it in every scene that has an entry with a rotation to apply."""
+    for name, sc in _all_scenes().items():
+        good = R.decompose_scene(sc); bad = R.decompose_scene(sc, "order"); svd = R.svd_candidates_of(sc)
+        differ = 0
+        for g, b, s in zip(good, bad, svd):
+            if g is None or g["status"] != R.OK:
+                assert g is None or not b["cand"].any()
+                continue
+            assert b["status"] == R.OK and R.same_set(b["cand"], s), name
+            differ += g["cand"].tobytes() != b["cand"].tobytes()
+        assert differ > 0 or name == "exact", name          # (the exact scene's E is [t]x of a unit axis: nothing to rotate)
+    sc = R.gpu_scenes()["lengths"]
+    assert all(g["cand"].tobytes() != b["cand"].tobytes() for g, b in zip(R.decompose_scene(sc), R.decompose_scene(sc, "order")))
+
+
 def test_every_gpu_scene_entry_with_a_pose_has_a_clear_winner():
     """every entry of every scene of test_gpu_pose.py that has a pose and at least 8 used rows has front > runner-up in the restatement:
     the condition under which the GPU tests compare the chosen pose.  No such entry is left out: the assertion runs over all of them, and
